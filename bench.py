@@ -17,11 +17,13 @@ Multi-GPU, one process per GPU over RCCL:
 `python bench.py --gpus N` launches its own N ranks (torch.distributed.run, 127.0.0.1) when it is not already
 running under a launcher; under a launcher WORLD_SIZE must equal --gpus. A box with fewer than N GPUs fails loudly.
 
-Prints ONE JSON line on rank 0 (see README/DESIGN.md for the field meanings):
-  value            whole-job Mpoints/s over all ranks (median of the --repeats timed blocks of --steps steps each)
-  repeats          median/min/max ms_per_step over --repeats blocks of --steps steps
+Prints ONE JSON line on rank 0 (see README/DESIGN.md for the field meanings). A plain run sets up, warms up, times ONE block
+of exactly --steps steps, writes that block's last outputs when --dump-outputs DIR is given, and prints the headline:
+  value            whole-job Mpoints/s over all ranks of the --steps timed steps (ms_per_step: one step's milliseconds)
+With --full the line also carries every other figure and check, each from runs of its own after the headline block:
+  repeats          median/min/max ms_per_step over --repeats blocks of --steps steps (the first one is the headline's)
   roofline         dominant kernel: algorithmic bytes per launch / its average duration measured with HIP events on
-                   the codec's stream inside the timed region
+                   the codec's stream in a block of --steps steps of its own
   cpu_baseline     the real reference (oracle/_ref, kind "reference") or the C port (kind "port") timed on the
                    host cores on a bounded sample of the same workload (rank 0, N=1 only)
   e2e              PCIe-inclusive and single-cloud figures (never `value`), each next to the reference on the host
@@ -546,6 +548,43 @@ def config_figures(dev, steps: int):
     return out
 
 
+DUMP_SAMPLE_BYTES = 1 << 21   # stream bytes written by --dump-outputs when the streams are longer
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, d_out, offsets, d_chunk_sizes, d_modes):
+    """--dump-outputs: what the caller of the timed call holds after its last step, as float .npy files in out_dir:
+      stream_offsets       float64 [clouds + 1]   offset of every cloud's framed stream in the output (the last one = bytes)
+      chunk_sizes          float64 [chunks]       the encoder's chunk sizes
+      modes                float32 [clouds x adaptive fields]  the committed adaptive-int modes
+      stream_crc32         float64 [clouds]       CRC-32 of every cloud's framed stream, all of its bytes
+      stream_sample        float32                stream bytes: all of them up to DUMP_SAMPLE_BYTES, else one byte at a seeded
+                                                  position in each of DUMP_SAMPLE_BYTES equal strata of the output
+      stream_sample_index  float64                the positions of stream_sample
+    The workload's clouds come from seeded generators, so the same arguments give the same inputs in every run."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    total = int(offsets[-1])
+    stream = d_out[:total].cpu().numpy()
+    crc = [zlib.crc32(stream[int(offsets[k]):int(offsets[k + 1])]) for k in range(len(offsets) - 1)]
+    if total <= DUMP_SAMPLE_BYTES:
+        index = np.arange(total, dtype=np.int64)
+    else:
+        bounds = np.arange(DUMP_SAMPLE_BYTES + 1, dtype=np.int64) * total // DUMP_SAMPLE_BYTES
+        index = np.random.default_rng(2024).integers(bounds[:-1], bounds[1:])
+    arrays = {"stream_offsets": np.asarray(offsets, dtype=np.float64),
+              "chunk_sizes": d_chunk_sizes.cpu().numpy().astype(np.float64),
+              "modes": d_modes.cpu().numpy().astype(np.float32),
+              "stream_crc32": np.asarray(crc, dtype=np.float64),
+              "stream_sample": stream[index].astype(np.float32),
+              "stream_sample_index": index.astype(np.float64)}
+    size = sum(a.nbytes for a in arrays.values())
+    if size > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {size} bytes of outputs exceed {DUMP_LIMIT_BYTES} (fewer --clouds)")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -574,23 +613,31 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=50)  # (a step is 0.3 ms: 3 steps left the first timed block 5 % behind the others)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps (the first one is `value`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every figure and check beyond the headline (repeats, roofline, decode, chunk_table, bit_exact, "
+                         "cpu_baseline, e2e, transcode, configs); a plain run only times --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, rank 0)")
+    ap.add_argument("--repeats", type=int, default=5,
+                    help="with --full: timed blocks of --steps steps for `repeats` (the first one is `value`'s)")
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOAD_DESC))
     ap.add_argument("--shard", default="clouds", choices=("clouds", "chunks"))
     ap.add_argument("--clouds", type=int, default=None, help="clouds per step per GPU (default 32; 1 with --shard chunks)")
     ap.add_argument("--points", type=int, default=None, help="points per cloud (default 1M; 10M with --shard chunks)")
     ap.add_argument("--distinct", type=int, default=4, help="distinct synthetic clouds generated (tiled to --clouds)")
-    ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    ap.add_argument("--e2e-seconds", type=float, default=6.0, help="budget of the e2e legs (0 = skip; N=1 only)")
+    ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0, help="with --full: budget of the cpu_baseline leg")
+    ap.add_argument("--e2e-seconds", type=float, default=6.0, help="with --full: budget of the e2e legs (0 = skip; N=1 only)")
     ap.add_argument("--transcode-messages", type=int, default=256,
-                    help="messages of the batch-transcoder leg (BASELINE configs[3], ZSTD; 0 = skip; N=1 only)")
+                    help="with --full: messages of the batch-transcoder leg (BASELINE configs[3], ZSTD; 0 = skip; N=1 only)")
     ap.add_argument("--config-legs", type=int, default=1,
-                    help="1: the `configs` object (encode + decode of the other BASELINE configs, N=1 only); 0 = skip")
+                    help="with --full, 1: the `configs` object (encode + decode of the other BASELINE configs, N=1 only); 0 = skip")
     ap.add_argument("--no-verify", dest="verify", action="store_false",
-                    help="skip the bit-exactness check of the timed batch's streams (outside the timed region)")
+                    help="with --full: skip the bit-exactness check of the timed batch's streams (outside the timed region)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.clouds is None:
         args.clouds = 1 if args.shard == "chunks" else 32
     if args.points is None:
@@ -698,11 +745,9 @@ def main():
     for _ in range(args.warmup):
         one_step()
     codec.status()  # raises on device-side errors
-    codec.enable_timing(max(1, args.steps))
 
-    block_times = []
-    kms, kms_blocks = None, []
-    for rep in range(max(1, args.repeats)):
+    def timed_block():
+        """--steps steps between two barriers (max over ranks): seconds."""
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -716,25 +761,32 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        block_times.append(elapsed)
-        if points_local:  # (the slots hold the block's last --steps calls)
-            kms_blocks.append([codec.kernel_ms(s) for s in range(args.steps)])
+        return elapsed
+
+    # value / ms_per_step: ONE block of exactly --steps steps, without the per-kernel event records
+    elapsed = timed_block()
     codec.status()
-    # value / ms_per_step: the MEDIAN block of --steps steps (round 4; the first block is reported next to it); round 5: the
-    # per-kernel HIP-event times are those of the same block
-    elapsed = float(np.median(block_times))
-    if kms_blocks:
-        kms = kms_blocks[int(np.argsort(block_times)[len(block_times) // 2])]
-
-    if kms:
-        regular_ms = float(np.mean([k["regular"] for k in kms]))
-        sections_ms = float(np.mean([k["sections"] for k in kms]))
-        compact_ms = float(np.mean([k["compact"] for k in kms]))
-        device_ms = float(np.mean([k["total"] for k in kms]))
-    else:
-        regular_ms = sections_ms = compact_ms = device_ms = float("nan")
-
     offsets = d_offsets.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_out, offsets, d_chunk_sizes[:n_chunks], d_modes[:n_clouds * na])
+
+    if args.full:
+        # `repeats`: the headline block and --repeats - 1 more like it; then the per-kernel HIP-event times (roofline,
+        # device_ms_per_step) from a block of their own, so that the event records never sit in the headline's steps
+        block_times = [elapsed] + [timed_block() for _ in range(max(1, args.repeats) - 1)]
+        codec.enable_timing(args.steps)
+        timed_block()
+        codec.status()
+        kms = [codec.kernel_ms(s) for s in range(args.steps)] if points_local else None
+        codec.enable_timing(0)
+        if kms:
+            regular_ms = float(np.mean([k["regular"] for k in kms]))
+            sections_ms = float(np.mean([k["sections"] for k in kms]))
+            compact_ms = float(np.mean([k["compact"] for k in kms]))
+            device_ms = float(np.mean([k["total"] for k in kms]))
+        else:
+            regular_ms = sections_ms = compact_ms = device_ms = float("nan")
+
     total_out = int(offsets[-1])
     out_bpp = total_out / max(1, points_local)
 
@@ -750,9 +802,9 @@ def main():
         else:
             job_bytes = int(sum(int(g.item()) for g in exchanged["sizes"]))
 
-    # extra (not `value`): decode of the streams just produced, device resident, same synchronisation bracket
+    # extra (not `value`, --full): decode of the streams just produced, device resident, same synchronisation bracket
     decode = None
-    if points_local:  # (every rank: the job-wide decode figure of a multi-GPU run is the slowest rank's)
+    if args.full and points_local:  # (every rank: the job-wide decode figure of a multi-GPU run is the slowest rank's)
         d_dec = torch.empty(max(1, host.size), dtype=torch.uint8, device=dev)
         so = offsets.astype(np.uint64)
         dec_steps = max(1, args.steps // 2)
@@ -809,7 +861,7 @@ def main():
     # a device-side stage 2 or any other consumer on the GPU starts from there. Same steps, same bracket; the table is
     # framed afterwards (outside the timed region) and compared with the streams of the timed batch.
     chunk_table = None
-    if rank == 0 and points_local and args.shard == "clouds":
+    if args.full and rank == 0 and points_local and args.shard == "clouds":
         try:
             ct_codec = native.Codec(plan, device=local_rank, stream=stream.cuda_stream)
             for _ in range(max(1, args.warmup)):
@@ -856,7 +908,7 @@ def main():
     # outside the timed region with the compiled reference (oracle/_ref) or, where that is absent, the C port: every
     # distinct cloud against the checker, every tiled copy against its first occurrence
     bit_exact = None
-    if points_local and args.shard == "clouds" and args.verify:  # (every rank checks its own streams)
+    if args.full and points_local and args.shard == "clouds" and args.verify:  # (every rank checks its own streams)
         from oracle import binding
         try:
             checker, checker_kind = binding.RefLib(), "reference"
@@ -878,7 +930,7 @@ def main():
     # job-wide figures of this rank count (round 4: the same object for every --workload and --gpus, so that the first run on
     # a multi-GPU node is a measurement): the slowest rank's decode, every rank's bit-exactness
     job = None
-    if dist is not None and world > 1:
+    if args.full and dist is not None and world > 1:
         t = torch.tensor([decode["ms_per_step"] if decode else 0.0, 1.0 if (bit_exact is None or bit_exact["ok"]) else 0.0],
                          dtype=torch.float64, device=dev)
         tmax, tmin = t.clone(), t.clone()
@@ -893,6 +945,33 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         mpts = points_job * args.steps / elapsed / 1e6
+        if args.shard == "clouds":
+            par = f"whole clouds sharded over {world} GPU(s), no data-path collective (RCCL: barrier, size all-gather)"
+        else:
+            par = (f"one cloud cut into chunk ranges over {world} GPU(s); per step: mode probe on rank 0, RCCL broadcast of "
+                   f"{na} mode byte(s), encode with forced modes, RCCL all-gather of the byte counts")
+        result = {
+            "metric": "encode Mpoints/s (stage-1, pre-ZSTD)",
+            "value": mpts,
+            "unit": "Mpoints/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": "f32->i32 (u8 varint stream)",
+            "data": f"synthetic lidar64 generator (cloudini_amd/synth.py), {len(distinct)} distinct clouds tiled, "
+                    "inputs resident in HBM",
+            "config": {"workload": WORKLOAD_DESC[args.workload].format(clouds=args.clouds, points=pts_per_cloud),
+                       "clouds_per_gpu": n_clouds if args.shard == "clouds" else None, "points_per_cloud": pts_per_cloud,
+                       "point_step": step, "shard": args.shard, "parallelism": par},
+            "input_MBps": points_job * step * args.steps / elapsed / 1e6,
+            "job_stage1_bytes": job_bytes,
+            "stage1_bytes_per_point": out_bpp,
+        }
+    if rank == 0 and args.full:
         n_ch_cloud = (pts_per_cloud + 32767) // 32768
         # regular-stream bytes per point: payload minus sections. Measured from the stream size when there are no
         # adaptive fields; otherwise from the float-only schema of the same buffer (V5 == V4 bytes for float-only
@@ -934,35 +1013,12 @@ def main():
                     traffic, traffic_src = float(t["hbm_bytes_per_launch"]), "profiles/" + name
                     break
         blocks_ms = np.asarray(block_times) / args.steps * 1e3
-        if args.shard == "clouds":
-            par = f"whole clouds sharded over {world} GPU(s), no data-path collective (RCCL: barrier, size all-gather)"
-        else:
-            par = (f"one cloud cut into chunk ranges over {world} GPU(s); per step: mode probe on rank 0, RCCL broadcast of "
-                   f"{na} mode byte(s), encode with forced modes, RCCL all-gather of the byte counts")
-        result = {
-            "metric": "encode Mpoints/s (stage-1, pre-ZSTD)",
-            "value": mpts,
-            "unit": "Mpoints/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "f32->i32 (u8 varint stream)",
-            "data": f"synthetic lidar64 generator (cloudini_amd/synth.py), {len(distinct)} distinct clouds tiled, "
-                    "inputs resident in HBM",
-            "config": {"workload": WORKLOAD_DESC[args.workload].format(clouds=args.clouds, points=pts_per_cloud),
-                       "clouds_per_gpu": n_clouds if args.shard == "clouds" else None, "points_per_cloud": pts_per_cloud,
-                       "point_step": step, "shard": args.shard, "parallelism": par},
+        result.update({
             "repeats": {"blocks": int(blocks_ms.size), "steps_per_block": args.steps,
                         "ms_per_step_median": float(np.median(blocks_ms)), "ms_per_step_min": float(blocks_ms.min()),
                         "ms_per_step_max": float(blocks_ms.max()),
                         "ms_per_step_first_block": float(blocks_ms[0]),
                         "value_median": points_job / (float(np.median(blocks_ms)) * 1e-3) / 1e6},
-            "input_MBps": points_job * step * args.steps / elapsed / 1e6,
-            "job_stage1_bytes": job_bytes,
             "bit_exact": bit_exact["ok"] if bit_exact else None,
             "bit_exact_detail": bit_exact,
             "decode": decode,
@@ -972,7 +1028,6 @@ def main():
                                                                        if job["decode_ms_per_step_max_over_ranks"] else None),
                                                  stage1_bytes=job_bytes),
             "chunk_table": chunk_table,
-            "stage1_bytes_per_point": out_bpp,
             "device_ms_per_step": {dominant: regular_ms, "sections": sections_ms,
                                    "k_finish": compact_ms, "all_kernels": device_ms},
             "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBPS,
@@ -987,7 +1042,7 @@ def main():
                          "whole_step_ms": ms_per_step,
                          "whole_step_GBps": points_local * (step + out_bpp) / (ms_per_step * 1e-3) / 1e9,
                          "whole_step_frac": points_local * (step + out_bpp) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS},
-        }
+        })
         if args.cpu_baseline_seconds > 0 and world == 1:
             result["cpu_baseline"] = cpu_baseline(info, distinct[0], args.cpu_baseline_seconds)
             result["speedup_vs_cpu_1core"] = mpts / result["cpu_baseline"]["value"]
@@ -1008,6 +1063,7 @@ def main():
                 result["configs"] = config_figures(dev, max(3, args.steps // 2))
             except Exception as exc:
                 result["configs"] = {"error": repr(exc)}
+    if rank == 0:
         print(json.dumps(result))
         sys.stdout.flush()
     if dist is not None:

@@ -54,12 +54,44 @@ def test_chunk_shard_needs_one_cloud():
 
 @pytest.mark.gpu
 def test_single_rank_line():
-    r = run(["--gpus", "1", "--clouds", "2", "--points", "100000"] + SMALL)
+    r = run(["--gpus", "1", "--clouds", "2", "--points", "100000", "--full"] + SMALL)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json_line(r.stdout)
     assert d["n_gpus"] == 1 and d["scaling"] == "weak" and d["steps"] == 2 and d["warmup"] == 1
     assert d["repeats"]["blocks"] == 2 and d["value"] > 0
     assert d["roofline"]["frac"] > 0 and d["decode"]["value"] > 0
+    assert d["bit_exact"] is True
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline alone; --dump-outputs writes what the timed call handed back, here the whole streams
+    (they are shorter than the sample), which must be the oracle's streams of the workload's seeded clouds."""
+    import zlib
+
+    import numpy as np
+    from cloudini_amd import synth
+    from oracle.binding import Oracle
+
+    r = run(["--gpus", "1", "--clouds", "2", "--points", "100000", "--steps", "3", "--warmup", "1",
+             "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json_line(r.stdout)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["higher_is_better"] is True
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Mpoints/s" and d["metric"] and d["dtype"]
+    assert not {"repeats", "roofline", "decode", "bit_exact", "cpu_baseline", "e2e", "transcode", "configs"} & set(d)
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"stream_offsets", "chunk_sizes", "modes", "stream_crc32", "stream_sample", "stream_sample_index"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64_000_000
+    info, c0 = synth.lidar_xyzi(100000, seed=42)
+    _info, c1 = synth.lidar_xyzi(100000, seed=43)
+    streams = [Oracle().encode_stage1(info, c) for c in (c0, c1)]
+    want = np.concatenate(streams)
+    assert np.array_equal(got["stream_offsets"], [0, streams[0].size, want.size]) and want.size == d["job_stage1_bytes"]
+    assert np.array_equal(got["stream_crc32"], [zlib.crc32(s) for s in streams])
+    assert np.array_equal(got["stream_sample_index"], np.arange(want.size))
+    assert np.array_equal(got["stream_sample"], want.astype(np.float32))
 
 
 @pytest.mark.gpu
