@@ -169,7 +169,7 @@ struct cldn_hip_codec {
   DevBuf d_cols[kMaxAdaptive];
   DevBuf d_ranks[kMaxAdaptive];
   DevBuf d_dec_meta, d_pre_ptrs;
-  DevBuf d_dec_cols[8];       // decode: dense columns of the adaptive fields that k_decode_points takes its integer fields from
+  DevBuf d_dec_cols[8];       // decode: dense columns of the adaptive fields that the point kernel takes its integer fields from
   // stage 2 on the device (cldn_hip_codec_set_stage2): the stage-1 streams stay in d_s1, the LZ4 blocks go straight into the output
   // chunk table of the last cldn_hip_encode_stage1_chunks call (cldn_hip_frame_chunks frames it)
   bool ct_valid = false;
@@ -846,10 +846,8 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   const uint8_t* variant_ptr = points_loc == CLDN_HIP_DEVICE ? (const uint8_t*)points : nullptr;
   const bool wide = c->plan.wide;  // stage1_wide.h: the plan's arrays live in device memory, one segment per chunk
   const uint32_t piece_pts = (c->pipeline == 1 || wide) ? 0u : stage1_piece_points(plan, variant_ptr);
-  static const bool intra_env0 = dev_env_int("CLDN_HIP_INTRA", 0) != 0;  // A/B switch
-  const bool intra_env = intra_env0 || table != nullptr;  // chunk tables want one regular segment per chunk
-  static const bool quad_major_env = dev_env_int("CLDN_HIP_QUAD_MAJOR", 1) != 0;
-  int rc = upload_batch_shape(c, cloud_points, n_clouds, piece_pts, piece_pts != 0u && intra_env && quad_major_env, &n_chunks, &n_points);
+  const bool intra_env = table != nullptr;  // chunk tables want one regular segment per chunk
+  int rc = upload_batch_shape(c, cloud_points, n_clouds, piece_pts, piece_pts != 0u && intra_env, &n_chunks, &n_points);
   if (rc != CLDN_HIP_OK) return rc;
   if (n_points && !points && !cloud_ptrs) return fail(CLDN_HIP_ERR_ARG, "points is NULL");
   if (cloud_ptrs)
@@ -877,12 +875,8 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   // Sub-chunks: the regular stream of a chunk is produced as `subs` independent sub-streams (one workgroup each)
   // that the compaction kernel concatenates; this multiplies the parallelism of small batches at no extra work.
   uint32_t subs = 1;
-  if (const int forced = dev_env_int("CLDN_HIP_SUBCHUNKS", 0)) {
-    subs = (uint32_t)forced;
-  } else {
-    while (subs < 32u && (uint64_t)n_chunks * subs < 6000u) subs *= 2u;
-  }
-  if (subs < 1u || subs > 32u || (subs & (subs - 1u)) || wide) subs = 1u;
+  while (subs < 32u && (uint64_t)n_chunks * subs < 6000u) subs *= 2u;
+  if (wide) subs = 1u;
   const bool pieces = piece_pts != 0u && n_chunks != 0u;   // regular stream by the piece kernel
   const bool intra = pieces && intra_env;
   const uint32_t piece_wgs = ((((kPointsPerChunk + piece_pts - 1u) / std::max(1u, piece_pts)) + 3u) & ~3u) / 4u;  // workgroups (4 pieces) per full chunk
@@ -1167,28 +1161,6 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
     if (modes && (size_t)n_clouds * n_adaptive)
       HIP_TRY(hipMemcpyAsync(modes, c->d_modes.p, (size_t)n_clouds * n_adaptive, hipMemcpyDeviceToDevice, c->stream));
     return CLDN_HIP_OK;
-  }
-
-  if (const char* dump = dev_env("CLDN_HIP_DEBUG_DUMP")) {  // diagnostics: segment table of the last call
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    std::vector<Seg> hs((size_t)n_chunks * segs_per_chunk);
-    std::vector<ChunkDesc> hc(n_chunks);
-    if (n_chunks) {
-      HIP_TRY(hipMemcpy(hs.data(), (uint8_t*)c->d_status.p + z_segs, hs.size() * sizeof(Seg), hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(hc.data(), c->d_chunks.p, hc.size() * sizeof(ChunkDesc), hipMemcpyDeviceToHost));
-    }
-    if (FILE* f = fopen(dump, "w")) {
-      fprintf(f, "subs %u sub_points %u sub_stride %u segs_per_chunk %u slot_stride %llu\n", subs, sub_points, sub_stride,
-              segs_per_chunk, (unsigned long long)slot_stride);
-      for (uint32_t ci = 0; ci < n_chunks; ++ci) {
-        fprintf(f, "chunk %u first %llu n %u cloud %u:", ci, (unsigned long long)hc[ci].first_point, hc[ci].n_points,
-                hc[ci].cloud);
-        for (uint32_t k = 0; k < segs_per_chunk; ++k)
-          fprintf(f, " [%u,%u]", hs[(size_t)ci * segs_per_chunk + k].off, hs[(size_t)ci * segs_per_chunk + k].size);
-        fprintf(f, "\n");
-      }
-      fclose(f);
-    }
   }
 
   const size_t modes_bytes = (size_t)n_clouds * n_adaptive;

@@ -26,8 +26,8 @@
 //   k_lz4_emit_lds  per sub-range: the sub-range staged in LDS, its sequences assembled in an LDS image of the output span it
 //                 owns, 16-byte stores STRAIGHT INTO THE FRAMED STREAMS (round 5: no block slots, no second framing pass).
 //                 Every literal byte is copied by the wave of the sub-range it lies in, however long a literal run is.
-//                 k_lz4_emit (CLDN_HIP_LZ4_EMIT_DIRECT=1) is the round-3 kernel without the LDS image: the fallback for a
-//                 span that does not fit the image, and the A/B reference.
+//                 lz_emit_direct (the round-3 emit without the LDS image) is the fallback for a span that does not fit
+//                 the image.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -485,13 +485,6 @@ __device__ __forceinline__ void lz_emit_direct(const LzEmitArgs& A, uint32_t idx
   }
 }
 
-#ifdef CLDN_DEV  // (the round-3 emit kernel: an A/B reference of the development build, CLDN_HIP_LZ4_EMIT_DIRECT=1)
-__global__ __launch_bounds__(64) void k_lz4_emit(const LzEmitArgs A) {
-  const uint32_t total = A.sub_first[A.n_chunks];
-  for (uint32_t idx = blockIdx.x; idx < total; idx += gridDim.x) lz_emit_direct(A, idx, A.sub_chunk[idx], threadIdx.x);
-}
-#endif
-
 // k_lz4_emit_lds (round 5): the same bytes as lz_emit_direct, moved through LDS. The direct kernel's lanes read and write
 // their own literal runs with scattered 4-byte accesses (64 different lines per instruction: the texture addresser is what
 // it waits for); here the sub-range's input is staged with whole-line loads, the sequences are assembled in an LDS image
@@ -835,11 +828,6 @@ int lz4_launch(const Lz4Launch& L) {
   A.out_capacity = L.out_capacity;
   A.sub_bytes = sub_bytes;
   A.max_matches = max_matches;
-#ifdef CLDN_DEV
-  static const bool direct = dev_env("CLDN_HIP_LZ4_EMIT_DIRECT") != nullptr;  // (the kernel of rounds 3-4, for A/B runs)
-  if (direct) hipLaunchKernelGGL(k_lz4_emit, dim3(grid), dim3(64), 0, L.stream, A);
-  else
-#endif
   if (L.fast) hipLaunchKernelGGL(k_lz4_emit_lds<kLzFastSubBytes>, dim3(grid), dim3(64), 0, L.stream, A);
   else hipLaunchKernelGGL(k_lz4_emit_lds<kLzSubBytes>, dim3(grid), dim3(64), 0, L.stream, A);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_emit");

@@ -1,57 +1,25 @@
-// stage1_decode_fast.h -- k_decode_points: stage-1 decode of chunks whose regular stream is one fused FloatN encoder
-// (3 or 4 int32-delta varint tokens per point; FieldDecoderFloatN_Lossy::decode, src/field_decoder.cpp:43-86), with
-// the chunk's Palette sections (decodeV5AdaptiveIntSection, src/v5_codec.cpp:764-879, mode 1) folded into the same
-// pass. Included by stage1_kernels.hip behind stage1_decode.h.
-//
-// k_decode_varint walks the 16 byte positions of every thread with the full token logic under a predicate (233
-// lane-instructions per token); here the two jobs are separated:
-//   phase A  byte-parallel and cheap: every thread flags the token ends in its 16 bytes, one block scan numbers them,
-//            and the byte behind every NOPS-th end -- where a point starts -- goes into an LDS list in point order;
-//   phase B  point-parallel, every lane busy: a thread takes 3 consecutive points; for each it reads the 4 * (NOPS + 1)
-//            bytes behind the point's start from the LDS copy of the tile and walks the NOPS tokens in registers (a
-//            token's length is the position of its first byte with a clear MSB; the window is shifted by it), sums
-//            the deltas, a segmented block scan (NaN markers reset a lane) turns them into values, and the values leave
-//            through an LDS transposition so that a store instruction covers consecutive points.
-// A tile starts exactly at a point boundary (the next tile begins behind the last token it consumed), so no point is
-// ever cut and nothing but the per-lane running values is carried between tiles.
+// stage1_decode_fast.h -- what the point kernel (k_decode_points_w, stage1_decode_wave.h) builds on: the stage-1 decode of
+// chunks whose regular stream is one fused FloatN encoder (3 or 4 int32-delta varint tokens per point;
+// FieldDecoderFloatN_Lossy::decode, src/field_decoder.cpp:43-86), with the chunk's Palette sections
+// (decodeV5AdaptiveIntSection, src/v5_codec.cpp:764-879, mode 1) folded into the same pass. Included by stage1_decode.hip
+// behind stage1_decode.h: the byte-window helpers, k_locate_sections, the column kernels in front of the point kernel
+// (k_sections_cols_fast, k_decode_sections_cols) and fp_setup.
 //
 // Sections: where the regular stream ends is not written anywhere. With one adaptive field the place is guessed from
 // the end of the payload (a Palette section's size is a function of its entry count: all counts are tried, the guess is
-// checked against where the tiles really end); with two, a counting pre-pass over the token-end flags finds it. If every section of the chunk is a Palette with at most kFastPalEntries entries (intensity, ring,
-// reflectivity ... of real lidars), their tables go to LDS and every point is completed when it is written: x, y, z
-// and its integer fields together, so that each output line is written once by one workgroup (the separate section
-// kernel re-dirtied every 64-byte line: WRITE_SIZE was 1.97x the output). Other sections are left to
-// k_decode_sections / k_decode_general exactly as before, and so is every chunk this kernel finds irregular (tokens of
-// more than 5 bytes, a stream that ends early, an index beyond its palette): reg_end[c] = kDecRedo hands it to
-// k_decode_varint, which keeps the reference's error reporting.
+// checked against where the point pass really ends); with two, a counting pre-pass over the token-end flags finds it. If
+// every section of the chunk is a Palette with at most kFastPalEntries entries (intensity, ring, reflectivity ... of real
+// lidars), their tables go to LDS and every point is completed when it is written: x, y, z and its integer fields
+// together, so that each output line is written once by one workgroup (the separate section kernel re-dirtied every
+// 64-byte line: WRITE_SIZE was 1.97x the output). Other sections are left to k_decode_sections / k_decode_general, and so
+// is every chunk the point kernel finds irregular (tokens of more than 5 bytes, a stream that ends early, an index beyond
+// its palette): reg_end[c] = kDecRedo hands it to k_decode_varint, which keeps the reference's error reporting.
 #pragma once
 
 namespace cldn {
 
-constexpr uint32_t kFpPPT = 3;                          // points per thread and tile
-constexpr uint32_t kFpThreads = 512;                    // 8 waves; four workgroups share a CU
-constexpr uint32_t kFpTileBytes = kFpThreads * 16u;     // 8 KiB of stream per tile
-constexpr uint32_t kFpTilePoints = kFpThreads * kFpPPT; // at most 1536 points leave per tile
 constexpr uint32_t kFastPalEntries = 1024;
 constexpr uint32_t kFastPalFields = 2;
-
-// NF = Palette sections the instantiation can fold (0, 1, 2 = min(adaptive fields of the plan, kFastPalFields)): the
-// staging area and the palette tables are sized for it, so that XYZ(I) clouds with one integer field keep four
-// workgroups per CU (the 4-lane layout with room for two folded fields needs 46 KB and gets three)
-template <int NOPS, int NF = 2>
-struct FpLds {
-  static constexpr uint32_t kTileOff = 0;                                   // [16 zero bytes][tile][32 pad]
-  static constexpr uint32_t kPosOff = 16u + kFpTileBytes + 32u;             // u16 [kFpTilePoints + 1 + 7]: where point q starts
-  static constexpr uint32_t kPosEntries = 1u + kFpTilePoints + 7u;
-  static constexpr uint32_t kWorkEnd = (kPosOff + kPosEntries * 2u + 15u) & ~15u;
-  static constexpr uint32_t kStageBytes = kFpTilePoints * (NOPS + NF) * 4u;  // decoded points (floats + folded
-                                                                                         // fields), overlays tile + list
-  static constexpr uint32_t kScanOff = (kWorkEnd > kStageBytes ? kWorkEnd : kStageBytes);
-  static constexpr uint32_t kWaveRec = NOPS * 4u + 8u;                      // per wave: int[NOPS] + flags; [16], [17] = carry
-  static constexpr uint32_t kPalOff = (kScanOff + 18u * kWaveRec + 15u) & ~15u;     // (read and written in turns)
-  static constexpr uint32_t kMiscOff = kPalOff + (uint32_t)NF * kFastPalEntries * 4u;
-  static constexpr uint32_t kTotal = kMiscOff + 512u;
-};
 
 // 16 payload bytes at payload offset `o` (any alignment of the stream); bytes behind the payload read as 0xff
 // (continuation bytes: no token ends there)
@@ -188,7 +156,7 @@ struct FpSection {   // a Palette section folded into the point pass
 // step; the wave that holds the last token walks its quarter again and finds the byte. A light kernel (no LDS to speak
 // of, eight workgroups per CU): the count is a plain streaming read of the regular stream.
 // reg_end_pre[c] = the offset, 0xffffffff = not found / not looked for (one-field plans whose section looks like a small
-// Palette from the end of the payload are left to k_decode_points' own guess). grid = n_chunks, NW * 64 threads.
+// Palette from the end of the payload are left to the point kernel's own guess). grid = n_chunks, NW * 64 threads.
 // ---------------------------------------------------------------------------------------------------------------
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void k_locate_sections(const DevPlan plan, const uint8_t* __restrict__ streams,
@@ -233,7 +201,7 @@ __global__ __launch_bounds__(NW * 64) void k_locate_sections(const DevPlan plan,
     // 1..n behind it, a token end in front of it and exactly 2 r token ends between p + 5 and the payload's end is a
     // candidate; one candidate = the section (a regular token stream does not hold a 3 followed by a count whose upper
     // bytes are 0: zeros are NaN markers). Spares the count over the whole payload (C4: 274 MB per batch); like the
-    // Palette guess it is verified by where k_decode_points' tiles end.
+    // Palette guess it is verified by where the point kernel's pass ends.
     constexpr uint32_t T = NW * 64u, W = T * 16u;
     __shared__ __attribute__((aligned(16))) uint32_t win[W / 4u + 4u];
     __shared__ uint32_t end_mask[T], end_pre[T], scan_tmp[32], cand[2];
@@ -781,7 +749,7 @@ __global__ __launch_bounds__(kScfThreads) void k_sections_cols_fast(const DevPla
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// k_decode_sections_cols: in front of k_decode_points, for chunks whose sections it cannot fold from a palette table
+// k_decode_sections_cols: in front of k_decode_points_w, for chunks whose sections it cannot fold from a palette table
 // (DeltaVarint / Rle / DeltaRle sections, large palettes). The sections are decoded into DENSE COLUMNS (value i of
 // the chunk at col[a] + (first_point + i) * bpv) with the parallel section decoder (decode_sections_core); the point
 // kernel then reads a point's integer fields next to its floats and writes every point ONCE -- round 2 decoded these
@@ -827,7 +795,7 @@ __global__ __launch_bounds__(kDvThreads) void k_decode_sections_cols(const DevPl
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// fp_setup: what both point kernels (k_decode_points, k_decode_points_w) do before their first byte of regular stream:
+// fp_setup: what the point kernel (k_decode_points_w) does before their first byte of regular stream:
 // find out where the chunk's sections begin if that is cheap (columns from k_decode_sections_cols, or a lone Palette seen
 // from the end of the payload, or -- two fields, no columns -- a count over the payload), read the headers of sections
 // that can be folded into the point pass and copy their palette tables to LDS. All threads of the workgroup call it
@@ -968,470 +936,6 @@ __device__ __forceinline__ uint32_t fp_setup(const DevPlan& plan, const uint8_t*
   }
   *from_cols_out = from_cols;
   return reg_size;
-}
-
-template <int NOPS, int NF>
-__global__ __launch_bounds__(kFpThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_decode_points(const DevPlan plan, const uint8_t* __restrict__ streams,
-                                                              const DecChunk* __restrict__ chunks, uint8_t* __restrict__ out,
-                                                              uint32_t* __restrict__ reg_end, uint8_t* __restrict__ sec_done,
-                                                              uint32_t uses_v5, uint32_t* __restrict__ status,
-                                                              const uint8_t* __restrict__ col0, const uint8_t* __restrict__ col1,
-                                                              const uint32_t* __restrict__ reg_end_pre,
-                                                              const uint8_t* __restrict__ sec_cols, uint32_t fill_zero) {
-  using L = FpLds<NOPS, NF>;
-  constexpr uint32_t NFA = NF ? NF : 1;  // array extents (NF == 0: nothing is ever folded)
-  constexpr int T = kFpThreads;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint32_t* tile = reinterpret_cast<uint32_t*>(smem + L::kTileOff);             // dwords; byte 16 = first tile byte
-  uint16_t* pos_list = reinterpret_cast<uint16_t*>(smem + L::kPosOff);          // [0] = end of the token before the tile
-  float* stage = reinterpret_cast<float*>(smem);                                // overlays tile and list in phase B
-  uint8_t* scanrec = smem + L::kScanOff;
-  uint32_t* pal = reinterpret_cast<uint32_t*>(smem + L::kPalOff);
-  uint32_t* misc = reinterpret_cast<uint32_t*>(smem + L::kMiscOff);             // [0] irregular, [2..34) scan scratch,
-                                                                                // [40..) pre-pass, [64..) sections
-  const uint32_t c = blockIdx.x;
-  const uint32_t tid = threadIdx.x;
-  const uint32_t lane = tid & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const DecChunk dc = chunks[c];
-  if (!dc.valid) {
-    if (tid == 0) sec_done[c] = 0u;
-    return;
-  }
-  const uint8_t* src = streams + dc.src_off;
-  const uint32_t src_size = dc.src_size;
-  const uint32_t n = dc.n_points;
-  const uint32_t step = plan.point_step;
-  uint8_t* base = out + (size_t)dc.first_point * step;
-
-  if (tid < 4u) tile[tid] = 0u;  // the 16 bytes in front of a tile: token ends
-  if (tid == 0) {
-    misc[0] = 0u;
-    misc[1] = 0u;            // a folded Palette index was out of range
-    misc[40] = 0xffffffffu;  // pre-pass: payload offset behind the regular stream
-    misc[42] = 0xffffffffu;  // entries of the Palette section found by its size (smallest hit)
-    misc[64] = 0u;           // sections folded in
-  }
-  if (tid < (uint32_t)(NOPS + 2)) reinterpret_cast<uint32_t*>(scanrec + 16u * L::kWaveRec)[tid] = 0u;  // carry of tile 0: values 0
-  __syncthreads();
-
-  bool from_cols = false;
-  const uint32_t reg_size = fp_setup<NOPS, NF, T>(plan, src, src_size, n, uses_v5, c, reg_end_pre, sec_cols, misc, pal, &from_cols);
-  const uint32_t n_fold = misc[64];
-
-  // folded Palette sections: parameters in (uniform) registers for the read-out
-  uint32_t fs_off[NFA], fs_bpv[NFA], fs_count[NFA], fs_bits[NFA];
-  const uint8_t* fs_idx[NFA];
-#pragma unroll
-  for (uint32_t a = 0; a < NFA; ++a) {
-    const FpSection sct = reinterpret_cast<const FpSection*>(misc + 72)[a < n_fold ? a : 0u];
-    fs_off[a] = sct.field_off;
-    fs_bpv[a] = sct.bpv;
-    fs_count[a] = sct.count;
-    fs_bits[a] = a < n_fold ? sct.bits : 0u;
-    fs_idx[a] = src + (a < n_fold ? sct.index_off : 0u);
-  }
-  // which store forms the layout allows (uniform)
-  bool contig = ((step | plan.ops[0].offset) & 3u) == 0u;
-#pragma unroll
-  for (int o = 1; o < NOPS; ++o) contig = contig && plan.ops[o].offset == plan.ops[0].offset + 4u * (uint32_t)o;
-  bool packed = true;  // the floats back to back at any alignment, all of them stored
-#pragma unroll
-  for (int o = 0; o < NOPS; ++o) packed = packed && plan.ops[o].offset != 0xffffffffu && plan.ops[o].offset == plan.ops[0].offset + 4u * (uint32_t)o;
-  float res[NOPS];
-  uint32_t foff[NOPS];
-#pragma unroll
-  for (int o = 0; o < NOPS; ++o) {
-    res[o] = plan.ops[o].res_f;
-    foff[o] = plan.ops[o].offset;
-  }
-
-  // ---------------------------------------------------------------------------------------------------------
-  // tiles
-  // ---------------------------------------------------------------------------------------------------------
-  uint32_t pos = 0u;       // payload offset of the tile (a point boundary)
-  uint32_t pts_done = 0u;
-  uint32_t par = 0u;       // which carry record this tile reads (it writes the other one)
-  bool bad = false;
-  uint32_t b[4];           // my 16 bytes of the tile (those of the next tile are fetched while this one is decoded)
-  fp_load16(src, src_size, tid * 16u, b);
-  while (pts_done < n) {
-    if (pos >= src_size) { bad = true; break; }
-    // ---- phase A: bytes -> LDS; the byte where every point starts -> list
-    *reinterpret_cast<uint4*>(tile + 4u + tid * 4u) = make_uint4(b[0], b[1], b[2], b[3]);
-    const uint32_t ends = fp_ends16(b);
-    uint32_t n_tile;
-    const uint32_t tb = block_exclusive_scan<T>((uint32_t)__builtin_popcount(ends), misc + 2, &n_tile);  // barrier inside
-    const uint32_t want_pts = min(kFpTilePoints, n - pts_done);
-    {
-      // my token ends are tokens tb, tb + 1, ... of the tile; point q starts behind the end of token q * NOPS - 1.
-      // Only those ends are listed: the tokens inside a point are found by walking its bytes in phase B.
-      const uint32_t tq = tb / (uint32_t)NOPS;
-      const uint32_t rank0 = (uint32_t)(NOPS - 1) - (tb - tq * (uint32_t)NOPS);  // ends of mine to skip first
-      uint32_t m = ends;
-#pragma unroll
-      for (uint32_t i = 0; i + 1u < (uint32_t)NOPS; ++i) {
-        const uint32_t mm = m & (m - 1u);
-        m = (i < rank0) ? mm : m;
-      }
-      uint32_t q = tq + 1u;
-      while (m != 0u && q <= want_pts) {
-        pos_list[q] = (uint16_t)(tid * 16u + (uint32_t)__builtin_ctz(m) + 1u);
-        ++q;
-#pragma unroll
-        for (int i = 0; i < NOPS; ++i) m &= m - 1u;
-      }
-      if (tid == 0) pos_list[0] = (uint16_t)0u;
-    }
-    __syncthreads();
-    const uint32_t npts = min(n_tile / (uint32_t)NOPS, want_pts);  // whole points of this tile
-    if (npts == 0u) { bad = true; break; }           // 16 KiB without NOPS token ends: not a FloatN stream
-    const uint32_t next_pos = pos + (uint32_t)pos_list[npts];  // behind the last token this tile consumes
-    if (pts_done + npts < n) fp_load16(src, src_size, next_pos + tid * 16u, b);  // (`ends` is all this tile still needs of b)
-
-    // ---- phase B: my points [q0, q0 + kFpPPT)
-    const uint32_t q0 = tid * kFpPPT;
-    int32_t dlt[kFpPPT][NOPS];   // 0x80000000 = the NaN marker (no token of at most 4 bytes decodes to it)
-    bool long_tok = false;
-    bool any_marker = false;
-#pragma unroll
-    for (uint32_t i = 0; i < kFpPPT; ++i) {
-      // points behind the tile's last one run the same straight-line code on whatever the list holds (masked into the
-      // tile); nothing of theirs is used: they come after every real point in scan order
-      const bool have = (q0 + i) < npts;
-      const uint32_t byte0 = 16u + ((uint32_t)pos_list[q0 + i] & (kFpTileBytes - 1u));  // byte index in the LDS copy
-      const uint32_t di = byte0 >> 2, sh = (byte0 & 3u) * 8u;
-      uint32_t d[NOPS + 1];
-#pragma unroll
-      for (int k = 0; k <= NOPS; ++k) d[k] = tile[di + (uint32_t)k];
-      uint32_t W[NOPS];  // W[k] = bytes [4k, 4k + 4) behind the current token's start
-#pragma unroll
-      for (int k = 0; k < NOPS; ++k) W[k] = __builtin_amdgcn_alignbit(d[k + 1], d[k], sh);
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) {
-        // Tokens of up to 4 bytes (|delta| < 2^27 ticks) are decoded here with 32-bit arithmetic; a longer one
-        // (special values, damaged streams) sends the chunk to k_decode_varint.
-        const uint32_t w = W[0];
-        const uint32_t t = ~w & 0x80808080u;     // the bytes that can end the token
-        const uint32_t keep = t ^ (t - 1u);      // everything up to and including the first of them
-        const uint32_t wk = w & keep;            // == 0: the marker byte 0x00
-        const uint32_t lo = wk & 0x7f7f7f7fu;
-        const uint32_t u = (lo & 0x7fu) | (((lo >> 8) & 0x7fu) << 7) | (((lo >> 16) & 0x7fu) << 14) | ((lo >> 24) << 21);
-        // no end in 4 bytes; or an overlong zero, which decodeVarint rejects
-        long_tok = long_tok || (have && (t == 0u || (lo == 0u && wk != 0u)));
-        any_marker = any_marker || wk == 0u;
-        const uint32_t u1 = u - 1u;
-        dlt[i][o] = (int32_t)((u1 >> 1) ^ (0u - (u1 & 1u)));   // u == 0 -> 0x80000000
-        if (o + 1 < NOPS) {
-          const uint32_t adv = (uint32_t)__ffs((int)t);  // bits of this token: 8, 16, 24, 32
-#pragma unroll
-          for (int k = 0; k + 1 < NOPS - o; ++k) W[k] = (uint32_t)(((((uint64_t)W[k + 1]) << 32) | W[k]) >> adv);
-        }
-      }
-    }
-    // folded Palette fields of my points: their indexes are consecutive bits, one 8-byte window holds all kFpPPT
-    uint32_t pv[NFA][kFpPPT];
-    const uint32_t SP = (uint32_t)NOPS + n_fold;  // dwords per staged point
-    if (from_cols) {
-#pragma unroll
-      for (uint32_t a = 0; a < NFA; ++a) {
-        if (a >= n_fold) break;  // uniform
-        const uint8_t* colp = (a == 0u ? col0 : col1) + ((size_t)dc.first_point + pts_done) * fs_bpv[a];
-#pragma unroll
-        for (uint32_t i = 0; i < kFpPPT; ++i) {
-          const uint32_t q = min(q0 + i, npts - 1u);  // (points behind the tile's last one read a valid slot; unused)
-          pv[a][i] = fs_bpv[a] == 2u ? (uint32_t)reinterpret_cast<const uint16_t*>(colp)[q] : reinterpret_cast<const uint32_t*>(colp)[q];
-        }
-      }
-    } else if (n_fold != 0u) {
-#pragma unroll
-      for (uint32_t a = 0; a < NFA; ++a) {
-        if (a >= n_fold) break;  // uniform
-        const uint32_t bits = fs_bits[a];
-        uint64_t w64 = 0u;
-        if (bits != 0u && q0 < npts) {
-          const uint32_t bit0 = (pts_done + q0) * bits;                 // < 32768 * 10
-          const uint8_t* ib = fs_idx[a] + (bit0 >> 3);
-          const uint32_t mis = (uint32_t)((uintptr_t)ib & 3u);
-          const uint8_t* al = ib - mis;                                 // index_off >= 3: still inside the payload
-          if (al + 8u <= src + src_size) {  // kFpPPT * 10 + 7 bits <= 5 bytes: two aligned dwords cover them
-            const uint32_t* iq = reinterpret_cast<const uint32_t*>(al);
-            w64 = ((((uint64_t)iq[1]) << 32) | iq[0]) >> (mis * 8u + (bit0 & 7u));
-          } else {                          // the section's last bytes
-            const uint32_t avail = (uint32_t)(src + src_size - ib);
-            for (uint32_t k = 0; k < 5u && k < avail; ++k) w64 |= ((uint64_t)ib[k]) << (8u * k);
-            w64 >>= (bit0 & 7u);
-          }
-        }
-        bool beyond = false;
-#pragma unroll
-        for (uint32_t i = 0; i < kFpPPT; ++i) {
-          const uint32_t idx = (uint32_t)(w64 >> (i * bits)) & ((1u << bits) - 1u);  // < kFastPalEntries
-          beyond = beyond || ((q0 + i) < npts && idx >= fs_count[a]);
-          pv[a][i] = pal[a * kFastPalEntries + idx];
-        }
-        if (beyond) misc[1] = 1u;  // index beyond the palette: the serial decoder redoes the sections and raises the error
-      }
-    }
-    // local sums per lane with NaN resets, then the segmented scan over the threads
-    int32_t acc[NOPS];
-    uint32_t fl = 0u;
-    const bool wave_marker = __ballot(any_marker) != 0ull;  // (markers of points that do not exist only cost time)
-#pragma unroll
-    for (int o = 0; o < NOPS; ++o) acc[o] = 0;
-    int32_t inc[NOPS];
-    uint32_t fin = 0u;
-    if (!wave_marker) {  // no marker in this wave (the rule for lidar data): plain sums, DPP prefix sums
-#pragma unroll
-      for (uint32_t i = 0; i < kFpPPT; ++i) {
-#pragma unroll
-        for (int o = 0; o < NOPS; ++o) acc[o] = (int32_t)((uint32_t)acc[o] + (uint32_t)dlt[i][o]);
-      }
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) inc[o] = (int32_t)wave_inclusive_scan((uint32_t)acc[o]);
-    } else {
-#pragma unroll
-      for (uint32_t i = 0; i < kFpPPT; ++i) {
-#pragma unroll
-        for (int o = 0; o < NOPS; ++o) {
-          const bool m = dlt[i][o] == (int32_t)0x80000000;
-          acc[o] = m ? 0 : (int32_t)((uint32_t)acc[o] + (uint32_t)dlt[i][o]);
-          if (m) fl |= 1u << o;
-        }
-      }
-      fin = fl;
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) inc[o] = acc[o];
-#pragma unroll
-      for (int dl = 1; dl < 64; dl <<= 1) {
-        const uint32_t of = (uint32_t)__shfl_up((int)fin, dl);
-        int32_t ov[NOPS];
-#pragma unroll
-        for (int o = 0; o < NOPS; ++o) ov[o] = __shfl_up(inc[o], dl);
-        if (lane >= (uint32_t)dl) {
-#pragma unroll
-          for (int o = 0; o < NOPS; ++o)
-            if (!(fin & (1u << o))) inc[o] = (int32_t)((uint32_t)inc[o] + (uint32_t)ov[o]);
-          fin |= of;
-        }
-      }
-    }
-    if (long_tok) misc[0] = 1u;
-    if (lane == 63u) {
-      int32_t* rec = reinterpret_cast<int32_t*>(scanrec + wave * L::kWaveRec);
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) rec[o] = inc[o];
-      *reinterpret_cast<uint32_t*>(scanrec + wave * L::kWaveRec + NOPS * 4u) = fin;
-    }
-    __syncthreads();  // also: every thread is done with the tile bytes and the list -> the staging area may overlay them
-    int32_t in[NOPS];
-    {
-      const int32_t* crec = reinterpret_cast<const int32_t*>(scanrec + (16u + par) * L::kWaveRec);
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) in[o] = crec[o];
-      {
-        // state behind waves 0..wave-1: lane l < 16 holds wave l's record, a 4-step segmented scan over those 16 lanes
-        // (row-local DPP shifts), lane wave-1 then has the combination of all waves before mine
-        int32_t rv[NOPS];
-        uint32_t rfl = 0u;
-        const uint32_t wl = lane & 15u;
-        {
-          const int32_t* rec = reinterpret_cast<const int32_t*>(scanrec + wl * L::kWaveRec);
-#pragma unroll
-          for (int o = 0; o < NOPS; ++o) rv[o] = rec[o];
-          rfl = *reinterpret_cast<const uint32_t*>(scanrec + wl * L::kWaveRec + NOPS * 4u);
-        }
-#define FP_SEG_STEP(DL)                                                                                         \
-  {                                                                                                            \
-    const uint32_t of = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)rfl, 0x110 + DL, 0xf, 0xf, true); /* row_shr */ \
-    int32_t ov[NOPS];                                                                                          \
-    _Pragma("unroll") for (int o = 0; o < NOPS; ++o) ov[o] = __builtin_amdgcn_update_dpp(0, rv[o], 0x110 + DL, 0xf, 0xf, true); \
-    if (wl >= (uint32_t)DL) {                                                                                  \
-      _Pragma("unroll") for (int o = 0; o < NOPS; ++o)                                                         \
-        if (!(rfl & (1u << o))) rv[o] = (int32_t)((uint32_t)rv[o] + (uint32_t)ov[o]);                          \
-      rfl |= of;                                                                                               \
-    }                                                                                                          \
-  }
-        FP_SEG_STEP(1)
-        FP_SEG_STEP(2)
-        FP_SEG_STEP(4)
-        FP_SEG_STEP(8)
-#undef FP_SEG_STEP
-        if (wave > 0u) {
-          const uint32_t pfw = (uint32_t)__builtin_amdgcn_readlane((int)rfl, (int)wave - 1);
-#pragma unroll
-          for (int o = 0; o < NOPS; ++o) {
-            const int32_t pvw = __builtin_amdgcn_readlane(rv[o], (int)wave - 1);
-            in[o] = (pfw & (1u << o)) ? pvw : (int32_t)((uint32_t)in[o] + (uint32_t)pvw);
-          }
-        }
-      }
-      const uint32_t pf = (uint32_t)__shfl_up((int)fin, 1);
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) {
-        const int32_t pv = __shfl_up(inc[o], 1);
-        if (lane > 0u) in[o] = (pf & (1u << o)) ? pv : (int32_t)((uint32_t)in[o] + (uint32_t)pv);
-      }
-    }
-    if (misc[0]) { bad = true; break; }  // uniform (read behind the barrier)
-    // final values -> staging (point-major, NOPS floats per point); the values behind the tile's last point are the
-    // next tile's carry (the record this tile did not read)
-    int32_t* crec_next = reinterpret_cast<int32_t*>(scanrec + (17u - par) * L::kWaveRec);
-    if (!wave_marker) {
-#pragma unroll
-      for (uint32_t i = 0; i < kFpPPT; ++i) {
-#pragma unroll
-        for (int o = 0; o < NOPS; ++o) {
-          in[o] = (int32_t)((uint32_t)in[o] + (uint32_t)dlt[i][o]);
-          stage[(q0 + i) * SP + (uint32_t)o] = __fmul_rn((float)in[o], res[o]);  // points >= npts: harmless slots, never read
-        }
-#pragma unroll
-        for (uint32_t a = 0; a < NFA; ++a)
-          if (a < n_fold) stage[(q0 + i) * SP + (uint32_t)NOPS + a] = __uint_as_float(pv[a][i]);
-        if (q0 + i + 1u == npts) {
-#pragma unroll
-          for (int o = 0; o < NOPS; ++o) crec_next[o] = in[o];
-        }
-      }
-    } else {
-#pragma unroll
-      for (uint32_t i = 0; i < kFpPPT; ++i) {
-#pragma unroll
-        for (int o = 0; o < NOPS; ++o) {
-          const bool m = dlt[i][o] == (int32_t)0x80000000;
-          in[o] = m ? 0 : (int32_t)((uint32_t)in[o] + (uint32_t)dlt[i][o]);
-          const float f = m ? __uint_as_float(0x7fc00000u) : __fmul_rn((float)in[o], res[o]);
-          stage[(q0 + i) * SP + (uint32_t)o] = f;
-        }
-#pragma unroll
-        for (uint32_t a = 0; a < NFA; ++a)
-          if (a < n_fold) stage[(q0 + i) * SP + (uint32_t)NOPS + a] = __uint_as_float(pv[a][i]);
-        if (q0 + i + 1u == npts) {
-#pragma unroll
-          for (int o = 0; o < NOPS; ++o) crec_next[o] = in[o];
-        }
-      }
-    }
-    par ^= 1u;
-    __syncthreads();
-    // ---- read-out: consecutive lanes, consecutive points; folded Palette fields complete the point. The layout
-    // decisions are uniform: one switch per tile picks a straight-line variant (the common lidar layouts get code
-    // without a branch per point).
-    auto store_floats_contig = [&](uint8_t* pt, uint32_t q) {
-      if (NOPS == 3) {
-        FloatVec<3> v;
-        v.v[0] = stage[q * SP]; v.v[1] = stage[q * SP + 1u]; v.v[2] = stage[q * SP + 2u];
-        *reinterpret_cast<FloatVec<3>*>(pt + foff[0]) = v;
-      } else {
-        FloatVec<4> v;
-#pragma unroll
-        for (int o = 0; o < 4; ++o) v.v[o] = stage[q * SP + (uint32_t)o];
-        *reinterpret_cast<FloatVec<4>*>(pt + foff[0]) = v;
-      }
-    };
-    const bool one_u16 = NOPS == 3 && contig && n_fold == 1u && fs_bpv[0] == 2u && ((fs_off[0] | step) & 1u) == 0u;  // XYZ + one 16-bit field
-    // fill_zero (CLDN_HIP_FILL_ZERO: the bytes no field covers may be written as 0): the two common padded layouts leave
-    // as whole 16-byte stores -- XYZ f32 + a 16-bit field in a 16-byte point, XYZ f32 + a 32-bit field at 16 in a
-    // 32-byte point
-    const bool full16 = fill_zero != 0u && one_u16 && step == 16u && foff[0] == 0u && fs_off[0] == 12u && ((uintptr_t)base & 15u) == 0u;
-    const bool full32 = fill_zero != 0u && NOPS == 3 && contig && n_fold == 1u && fs_bpv[0] == 4u && step == 32u && foff[0] == 0u &&
-                        fs_off[0] == 16u && ((uintptr_t)base & 15u) == 0u;
-    if (full16) {
-#pragma unroll
-      for (uint32_t r = 0; r < kFpPPT; ++r) {
-        const uint32_t q = r * (uint32_t)T + tid;
-        if (q < npts) {
-          float4 sv = *reinterpret_cast<const float4*>(stage + q * 4u);  // x, y, z, field
-          sv.w = __uint_as_float(__float_as_uint(sv.w) & 0xffffu);
-          *reinterpret_cast<float4*>(base + (size_t)(pts_done + q) * 16u) = sv;
-        }
-      }
-    } else if (full32) {
-#pragma unroll
-      for (uint32_t r = 0; r < kFpPPT; ++r) {
-        const uint32_t q = r * (uint32_t)T + tid;
-        if (q < npts) {
-          const float4 sv = *reinterpret_cast<const float4*>(stage + q * 4u);  // x, y, z, field
-          float4* pt = reinterpret_cast<float4*>(base + (size_t)(pts_done + q) * 32u);
-          pt[0] = make_float4(sv.x, sv.y, sv.z, 0.0f);
-          pt[1] = make_float4(sv.w, 0.0f, 0.0f, 0.0f);
-        }
-      }
-    } else if (contig && n_fold == 0u) {
-#pragma unroll
-      for (uint32_t r = 0; r < kFpPPT; ++r) {
-        const uint32_t q = r * (uint32_t)T + tid;
-        if (q < npts) store_floats_contig(base + (size_t)(pts_done + q) * step, q);
-      }
-    } else if (one_u16) {
-#pragma unroll
-      for (uint32_t r = 0; r < kFpPPT; ++r) {
-        const uint32_t q = r * (uint32_t)T + tid;
-        if (q < npts) {
-          uint8_t* pt = base + (size_t)(pts_done + q) * step;
-          const float4 sv = *reinterpret_cast<const float4*>(stage + q * 4u);  // x, y, z, field
-          FloatVec<3> v;
-          v.v[0] = sv.x; v.v[1] = sv.y; v.v[2] = sv.z;
-          *reinterpret_cast<FloatVec<3>*>(pt + foff[0]) = v;
-          *reinterpret_cast<uint16_t*>(pt + fs_off[0]) = (uint16_t)__float_as_uint(sv.w);
-        }
-      }
-    } else {
-#pragma unroll
-      for (uint32_t r = 0; r < kFpPPT; ++r) {
-        const uint32_t q = r * (uint32_t)T + tid;
-        if (q < npts) {
-          uint8_t* pt = base + (size_t)(pts_done + q) * step;
-          if (contig) {
-            store_floats_contig(pt, q);
-          } else if (packed) {  // the floats lie back to back at an odd address (18-byte points): ONE unaligned store
-            if (NOPS == 3) {    // (gfx950 takes the misalignment: a memcpy of 12 / 16 bytes is one global_store_dwordx3 / x4)
-              FloatVec<3> v;
-              v.v[0] = stage[q * SP]; v.v[1] = stage[q * SP + 1u]; v.v[2] = stage[q * SP + 2u];
-              __builtin_memcpy(pt + foff[0], &v, 12);
-            } else {
-              FloatVec<4> v;
-#pragma unroll
-              for (int o = 0; o < 4; ++o) v.v[o] = stage[q * SP + (uint32_t)o];
-              __builtin_memcpy(pt + foff[0], &v, 16);
-            }
-          } else {
-#pragma unroll
-            for (int o = 0; o < NOPS; ++o)
-              if (foff[o] != 0xffffffffu) {
-                const float f = stage[q * SP + (uint32_t)o];
-                __builtin_memcpy(pt + foff[o], &f, 4);
-              }
-          }
-#pragma unroll
-          for (uint32_t a = 0; a < NFA; ++a) {
-            if (a >= n_fold) break;  // uniform
-            const uint32_t v = __float_as_uint(stage[q * SP + (uint32_t)NOPS + a]);
-            if (fs_bpv[a] == 2u) {
-              const uint16_t h = (uint16_t)v;
-              __builtin_memcpy(pt + fs_off[a], &h, 2);
-            } else if (fs_bpv[a] == 4u) {
-              __builtin_memcpy(pt + fs_off[a], &v, 4);
-            } else {
-              st_raw(pt + fs_off[a], v, fs_bpv[a]);
-            }
-          }
-        }
-      }
-    }
-    pos = next_pos;
-    pts_done += npts;
-    __syncthreads();  // the staging area is free again
-  }
-  __syncthreads();
-  if (tid == 0) {
-    const bool redo = bad || misc[0] != 0u;
-    reg_end[c] = redo ? kDecRedo : pos;
-    const bool folded = !redo && n_fold != 0u && misc[1] == 0u && pos == reg_size;
-    sec_done[c] = folded ? 2u : 0u;
-    if (!redo) atomicAdd(&status[kStatFastRegular], 1u);
-    if (folded) atomicAdd(&status[kStatFastSections], 1u);
-  }
 }
 
 }  // namespace cldn

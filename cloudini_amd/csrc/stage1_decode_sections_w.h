@@ -374,8 +374,8 @@ __global__ __launch_bounds__(kSwsThreads) void k_sections_w(const DevPlan plan, 
   if (tid == 0) atomicAdd(done_cnt + c, 1u);
 }
 
-// k_sections_dv_cols: the DeltaVarint sections k_section_offsets sized (dsec record with valid == 1) -> the field's dense
-// column, grid (chunks, fields) x 256 threads. The stream kernel's section mode decodes the same sections with its two walks
+// sections_dv_body: a DeltaVarint section k_section_offsets sized (dsec record with valid == 1) -> the field's dense
+// column, 256 threads. The stream kernel's section mode decodes the same sections with its two walks
 // and chains (289 us for the two DeltaVarint fields of an Ouster-style batch); a section is ONE integer op, and what
 // k_sections_cols_fast does for the plans with one integer field is all it takes: slices of 4 KiB in sequence, a thread
 // decodes the tokens that END in its 16 bytes (the first one begins behind the last end among the 8 bytes in front), two block
@@ -467,19 +467,6 @@ __device__ __forceinline__ void sections_dv_body(const DevPlan& plan, const uint
   }
   // every point has its token and the section's last byte ends one
   if (tid == 0u && pre_cnt == n && (src[src_size - 1u] & 0x80u) == 0u) atomicAdd(done_cnt + c, 1u);
-}
-
-__global__ __launch_bounds__(kScfThreads) void k_sections_dv_cols(const DevPlan plan, const uint8_t* __restrict__ streams,
-                                                                  const DecChunk* __restrict__ dsec, uint32_t n_chunks,
-                                                                  uint32_t* __restrict__ done_cnt, const DecColumns cols) {
-  __shared__ __attribute__((aligned(16))) uint32_t tile[kScfTileBytes / 4u + 8u];  // 8 bytes of history, the slice's bytes, slack
-  __shared__ uint32_t vals[kScfTileBytes];
-  __shared__ uint32_t scan[40];
-  __shared__ uint32_t flags[2];
-  const uint32_t c = blockIdx.x, a = blockIdx.y;
-  const DecChunk dc = dsec[(size_t)a * n_chunks + c];
-  if (dc.valid != 1u) return;  // another mode: k_sections_w
-  sections_dv_body(plan, streams, dc, c, a, done_cnt, cols, tile, vals, scan, flags);
 }
 
 // grid = ceil(n_chunks / 256): sec_done[c] = 1 for the chunks whose sections all arrived

@@ -211,11 +211,6 @@ __device__ __forceinline__ uint64_t sw_gorilla(const uint32_t* wbuf, uint32_t bp
 // token changes the window ends the round -- the table is rebuilt for the new window from there. The token's value bits
 // are XOR differences: the op joins the XOR-coded ones in both walks.
 #define SW_PRIO_HOP() __builtin_amdgcn_s_setprio(3)  // (chain hops at the highest wave priority, as in k_decode_points_w)
-#ifdef CLDN_SW_TRACE
-#define SW_T(k) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tr_[k] += t_ - tl_; tl_ = t_; }
-#else
-#define SW_T(k)
-#endif
 template <int NW, int MODE>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 6 : 8, 8))) void k_decode_stream_w(const DevPlan plan, const uint8_t* __restrict__ streams,
                                                              const DecChunk* __restrict__ chunks, uint8_t* __restrict__ out,
@@ -402,16 +397,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
     load_unit((min(p, n_pieces) + 1u) * kSwPiece + min(lane, 5u) * 16u, bh);
   }
   bool gave_up = false;
-#ifdef CLDN_SW_TRACE
-  unsigned long long tr_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = 0;
-  uint32_t trn_ = 0;
-#endif
   __builtin_amdgcn_s_setprio(1);
   for (; p < n_pieces; p += NW) {
-#ifdef CLDN_SW_TRACE
-    if (p == wave) tl_ = __builtin_amdgcn_s_memtime();
-#endif
-    SW_T(7)
     // ---- bytes and end bits -> LDS
     *reinterpret_cast<uint4*>(wbuf + lane * 4u) = make_uint4(b[0], b[1], b[2], b[3]);
     if (lane < 6u) *reinterpret_cast<uint4*>(wbuf + kSwPiece / 4u + lane * 4u) = make_uint4(bh[0], bh[1], bh[2], bh[3]);
@@ -652,7 +639,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
       };
       // MODE 2: the table is built for the window this wave saw last (windows change rarely: the guess is right for all but a
       // few pieces); a piece whose guess was wrong, or whose own '11' tokens change the window, is redone in rounds below
-      SW_T(0)
       uint32_t st_pred = GOR ? st_last : 0u;
       if constexpr (GOR) {
         // a newer guess than this wave's own last piece: the window behind the NEWEST piece in front of this one that has
@@ -677,7 +663,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
       }
       make_jt(st_pred, true);
       wp_wave_sync();
-      SW_T(1)
       // ---- the first lanes follow the jumps from their byte: where the next piece is entered, and after how many points.
       // On the way a candidate leaves a checkpoint in every 128-byte block it passes: its first point there and how many
       // came before -- the owner of the true entry then lists its points eight blocks side by side.
@@ -744,7 +729,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
         ex[1] = x1;
         ec[1] = c1;
       }
-      SW_T(2)
       // ---- chain 1: {entry offset, points in front} of the piece (MODE 2: and the window at its entry)
       uint32_t entry = a0, pts0 = 0u, st = 0u;  // (st: lane o = window of op o)
       SW_PRIO_HOP();  // (round 6: from a record's arrival to this piece's own record at the highest priority, as in k_decode_points_w)
@@ -771,7 +755,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
         pts0 = rv >> 8;
         if (GOR) st = lane < n_ops ? (uint32_t)xg : 0u;
       }
-      SW_T(3)
       if (gave_up) break;
       // (entry 0xff: the piece in front could not be left through a well-formed point -- malformed, or only the bytes
       // behind the regular stream's end; either way nothing starts here)
@@ -1065,7 +1048,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
       return bad;
     };
 
-    SW_T(4)
     // ---- first walk: every op's aggregate over the piece (lane o: op o)
     uint64_t agg_l = 0ull;
     uint32_t aggf_l = 0u;  // lane o: op o was reset inside the piece (a marker)
@@ -1123,7 +1105,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
       irregular = irregular || (have && bad);
     }
     if (__ballot(irregular) != 0ull && lane == 0u) misc[0] = 1u;
-    SW_T(5)
     // ---- chain 2: the running values in front of the piece (lane o: {tag, lo}, {tag | reset, hi} of op o)
     SW_PRIO_HOP();
     if (p != 0u) {
@@ -1157,7 +1138,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
       }
     }
     __builtin_amdgcn_s_setprio(1);
-    SW_T(6)
     // ---- second walk: values, converted and stored; a lane stores its own point
     for (uint32_t r = 0; r * 64u < npts; ++r) {  // uniform
       const uint32_t j = r * 64u + lane;
@@ -1258,15 +1238,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
       }
     }
     wp_wave_sync();
-#ifdef CLDN_SW_TRACE
-    ++trn_;
-#endif
   }
-#ifdef CLDN_SW_TRACE
-  if (MODE == 2 && lane == 0u && (c == 0u || c == 300u) && (wave == 0u || wave == 5u || wave == 11u))
-    printf("chunk %u wave %u pieces %u: A %llu jt %llu chase %llu wait1 %llu list %llu walk1 %llu wait2 %llu walk2 %llu\n", c, wave, trn_, tr_[0], tr_[1], tr_[2],
-           tr_[3], tr_[4], tr_[5], tr_[6], tr_[7]);
-#endif
   if (gave_up && lane == 0u) {
     misc[3] = 1u;
     misc[0] = 1u;

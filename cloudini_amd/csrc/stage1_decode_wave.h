@@ -234,9 +234,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef CLDN_WP_PROF
-  const unsigned long long wp_t0 = __builtin_readcyclecounter();
-#endif
   const DecChunk dc = chunks[c];
   if (!dc.valid) {
     if (tid == 0) sec_done[c] = 0u;
@@ -346,15 +343,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
   if (n_pieces) load_unit(min(p, n_pieces) * kWpPiece + lane * 16u - 16u, b);  // (no payload: nothing may be read)
   __builtin_amdgcn_s_waitcnt(0);  // (everything asked for so far is waited for HERE: a wait at the loop's top would also wait for every piece's stores)
   bool gave_up = false;
-#ifdef CLDN_WP_PROF
-  unsigned long long wp_acc[7] = {0, 0, 0, 0, 0, 0, 0};
-  unsigned long long wp_tl = __builtin_readcyclecounter();
-  const unsigned long long wp_tstart = wp_tl;
-  uint32_t wp_np = 0;
-#define WP_T(i) { const unsigned long long t_ = __builtin_readcyclecounter(); wp_acc[i] += t_ - wp_tl; wp_tl = t_; }
-#else
-#define WP_T(i)
-#endif
   __builtin_amdgcn_s_setprio(1);  // (waves that poll a record step down to 0)
   for (; p < n_pieces; p += p_step) {
     // ---- token ends of my unit; the ends that are tokens of the payload (ev); their numbers
@@ -378,7 +366,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
     const uint32_t incl = wave_inclusive_scan(cl);
     const uint32_t cnt = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     const uint32_t tb = incl - cl;  // (lane 63: cnt -- the halo's tokens follow the piece's)
-    WP_T(0)
     // ---- phase V: every token's value -> its slot
     const uint32_t e20 = (wp_from_lane_below(eraw) >> 12) | (eraw << 4);
     uint32_t flaws = wp_flaws16(b, e20, evc);  // bit j: byte j of my unit gives the chunk back (see the head of the file)
@@ -389,7 +376,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
       load_unit(min(p + p_step, n_pieces) * kWpPiece + lane * 16u - 16u, b);  // my next piece's bytes are requested now (b is free)
       wp_scatter16(pk, e20, ev, vals_lds + tb * 4u, dummy_lds);
     }
-    WP_T(1)
     // ---- chain 1: token ends in front of the piece
     uint32_t T0 = 0u;
     if constexpr (SPLIT) {
@@ -432,7 +418,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
       }
       flaws &= keep;  // (what lies behind it are sections, not tokens)
     }
-    WP_T(2)
     // ---- the points this piece owns: those whose first token ends in it. Point j: slots k0 + NOPS * j + o
     const uint32_t q_first = (T0 + (uint32_t)NOPS - 1u) / (uint32_t)NOPS;  // <= n (T0 < target)
     const uint32_t k0 = q_first * (uint32_t)NOPS - T0;
@@ -536,7 +521,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
         }
       }
     }
-    WP_T(3)
     // ---- chain 2: the values in front of the piece
     int32_t carry[NOPS];
 #pragma unroll
@@ -572,9 +556,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
         const uint32_t pre = (bs_fl & (1u << o)) ? (uint32_t)bs[o] : (uint32_t)carry[o] + (uint32_t)bs[o];
         mine = lane == (uint32_t)o ? pre : mine;
       }
-#ifdef CLDN_WP_HOPDELAY  // (experiment: how much of the kernel is the chain? every hop of chain 2 made CLDN_WP_HOPDELAY x 64 cycles longer)
-      __builtin_amdgcn_s_sleep(CLDN_WP_HOPDELAY);
-#endif
       if (lane < (uint32_t)NOPS)
         wp_rec_store(vrec + (size_t)(p & (kWpRing - 1u)) * NOPS + lane, ((unsigned long long)(p + 1u) << 32) | mine);
       WP_BOOST(1);
@@ -589,7 +570,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
     for (uint32_t a = 0; a < NFA; ++a)
 #pragma unroll
       for (uint32_t r = 0; r < ROWS; ++r) asm volatile("" : "+v"(raw[a][r]));
-    WP_T(4)
     // ---- phase B, second half: values -> floats -> the points. A lane stores its own point.
     const bool piece_flags = bs_fl != 0u;  // uniform: a marker somewhere in the piece
 #pragma unroll
@@ -629,11 +609,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
             pv[a] = pal[a * kFastPalEntries + (idx & (kFastPalEntries - 1u))];
           }
         }
-#ifdef CLDN_WP_ABL
-        if (have && (!(CLDN_WP_ABL & 1) || f[0] == 1234567.0f)) {  // (ablation 1: nothing is stored)
-#else
         if (have) {
-#endif
           uint8_t* pt = base + __umul24(q, step);  // (q < 32768, step <= 1024)
           if (full16) {
             *reinterpret_cast<float4*>(pt) = make_float4(f[0], f[1], f[2], __uint_as_float(pv[0] & 0xffffu));
@@ -723,18 +699,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
       }
     }
     wp_wave_sync();  // the next piece's bytes and list overwrite this one's
-    WP_T(5)
-#ifdef CLDN_WP_PROF
-    ++wp_np;
-#endif
   }
-#ifdef CLDN_WP_PROF
-  if (PASS == 0 && lane == 0u && (c == 0u || c == 700u) && (wave == 0u || wave == 7u || wave == 15u)) {
-    const unsigned long long t_ = __builtin_readcyclecounter();
-    printf("chunk %u wave %u pieces %u: start %llu total %llu prologue %llu | counts %llu V %llu chain1 %llu B1 %llu chain2 %llu B2 %llu\n", c, wave, wp_np,
-           wp_t0, t_ - wp_t0, wp_tstart - wp_t0, wp_acc[0], wp_acc[1], wp_acc[2], wp_acc[3], wp_acc[4], wp_acc[5]);
-  }
-#endif
   if (gave_up && lane == 0u) {
     misc[3] = 1u;
     misc[0] = 1u;

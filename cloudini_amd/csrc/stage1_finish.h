@@ -51,11 +51,6 @@ struct FinishArgs {
   uint32_t* ticket;                   // zero at launch
   uint32_t use_ticket;
   uint32_t test_timeout;              // test hook (cldn_hip_debug_finish_timeout_once): without the ticket the launch reports ST_FINISH_TIMEOUT at once
-  uint32_t copy_mode;                 // fin_copy: 1 = the round-3 loop (one unit per lane, both source units loaded by the lane);
-                                      // anything else = neighbour's unit by DPP, two rows in flight, non-temporal accesses (default)
-  uint32_t ablate;                    // profiling only: 1 no copy, 2 no section body (wrong output)
-  unsigned long long* trace;          // profiling only (CLDN_HIP_FINISH_TRACE): [n_chunks][16] wall_clock64() stamps of the leaders' phases
-  uint32_t order;                     // fused Palette: 0 even chunks section first, odd chunks copy first; 1 all section first; 2 all copy first
   uint32_t* chunk_payload;            // out [n_chunks]
   uint64_t* chunk_dst;                // out [n_chunks]
   uint64_t* stream_offsets;           // out [n_clouds + 1]
@@ -151,7 +146,7 @@ __device__ __forceinline__ void fin_layout(FinishLds& L, uint32_t n_segs, uint32
 // the waves of the chunk's workgroups take the items round-robin: byte-exact copy of the segments, source segments
 // start 16-byte aligned, the destination position is arbitrary (16-byte destination units built with byte funnel shifts)
 __device__ __forceinline__ void fin_copy(const FinishLds& L, const uint8_t* __restrict__ slot, uint8_t* __restrict__ chunk_out,
-                                         uint32_t wid, uint32_t n_waves, uint32_t lane, uint32_t mode) {
+                                         uint32_t wid, uint32_t n_waves, uint32_t lane) {
   const uint32_t n_items = L.n_items, item_units = L.item_units;
   for (uint32_t it = wid; it < n_items; it += n_waves) {
     const uint32_t sidx = L.item_seg[it], u0 = L.item_u0[it];
@@ -190,17 +185,10 @@ __device__ __forceinline__ void fin_copy(const FinishLds& L, const uint8_t* __re
       o.w = funnel_bytes(w3, w4, sb);
       return o;
     };
-    if (mode == 1u) {  // A/B switch: one unit per lane, both of its source units loaded by the lane itself (rounds 2-3)
-      for (uint32_t j = u0 + lane; j < u1; j += 64u) {
-        const uint4 a = src4[j];
-        uint4 b = make_uint4(0u, 0u, 0u, 0u);
-        if (head != 0u) b = src4[j + 1u];
-        dst4[j] = build(a, b);
-      }
-    } else if (u0 < u1) {
+    if (u0 < u1) {
       // the unit behind mine is my neighbour's: lane l takes lane l + 1's load by DPP (wave_shl:1), lane 63 the next
       // row's first unit. All lanes load (clamped index), the loop is wave-uniform. `last` = the last unit that may be
-      // read: one behind the item's last when the units straddle (the per-lane variant reads it as well).
+      // read: one behind the item's last when the units straddle.
       const uint32_t last = head != 0u ? u1 : u1 - 1u;
       auto shl1 = [&](const uint4& a, const uint4& lane63) __attribute__((always_inline)) {
         uint4 r;
@@ -289,7 +277,7 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
   if (tid == 0u) {
     // Order: the workgroup index. The hardware hands out a grid's workgroups in index order (per XCD), so every
     // workgroup a workgroup waits for -- all of lower index -- has started or finished. A.use_ticket replaces that
-    // observation by a ticket counter (CLDN_HIP_FINISH_TICKET=1; one contended atomic per workgroup: 11 us per 1000).
+    // observation by a ticket counter (the retry after ST_FINISH_TIMEOUT; one contended atomic per workgroup: 11 us per 1000).
     L.ticket = A.use_ticket ? atomicAdd(A.ticket, 1u) : blockIdx.x;
     L.timeout = 0u;
     L.base = 0ull;
@@ -301,7 +289,6 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
   const bool leader = (y == 0u);
   const ChunkDesc cd = A.chunks[c];
   const uint32_t n_segs = A.segs_per_chunk;
-  if (A.trace != nullptr && tid == 0u && leader) A.trace[(size_t)c * 16u + 0u] = wall_clock64();
   if (tid < n_segs) L.seg[tid] = A.segs[(size_t)c * n_segs + tid];
 
   // ---- fused Palette: build the table, which gives the section's size
@@ -320,7 +307,7 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
       first = A.fuse_first + cd.first_point;
       if (leader) {
         const P p(smem);
-        if (pal32_build<RawT, T>(p, col, n, A.trace ? A.trace + (size_t)c * 16u + 8u : nullptr)) {
+        if (pal32_build<RawT, T>(p, col, n)) {
           U = p.misc[0];
         } else {
           slow = true;
@@ -343,7 +330,6 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
       }
     }
   }
-  if (A.trace != nullptr && tid == 0u && leader) A.trace[(size_t)c * 16u + 1u] = wall_clock64();
   __syncthreads();  // L.seg is complete
   if (fuse && tid == 0u) {
     L.seg[s_a].size = 3u + U * (uint32_t)sizeof(RawT);
@@ -370,7 +356,7 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
         x[k] = j < c ? fin_load(A.rec + j) : ((unsigned long long)A.epoch << 32);
       }
       // the ranks of the fused section need nothing from outside: they are computed while the records arrive
-      if (FUSE_BPV != 0 && fuse && leader && !slow && !(A.ablate & 2u)) (void)pal32_rank<RawT, T>(P(smem), nullptr);
+      if (FUSE_BPV != 0 && fuse && leader && !slow) (void)pal32_rank<RawT, T>(P(smem), nullptr);
 #pragma unroll
       for (uint32_t k = 0; k < PER; ++k) {
         const uint32_t j = (blk << 10) + tid + k * T;
@@ -409,10 +395,8 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
     return;
   }
   const unsigned long long dst0 = L.base;
-  if (A.trace != nullptr && tid == 0u && leader) A.trace[(size_t)c * 16u + 2u] = wall_clock64();
   if (wave == 0u) fin_layout(L, n_segs, s_a, s_b, (uint32_t)(((uintptr_t)A.out + dst0 + 4ull) & 15ull), lane);  // (the ADDRESS decides: `out` may have any alignment)
   __syncthreads();
-  if (A.trace != nullptr && tid == 0u && leader) A.trace[(size_t)c * 16u + 7u] = wall_clock64();
   const uint32_t payload = L.payload;
   if (dst0 + 4ull + payload > A.out_capacity) {
     if (tid == 0u && leader) atomicOr(A.status, (uint32_t)ST_OUT_OVERFLOW);
@@ -434,7 +418,6 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
     }
   }
 
-  if (A.trace != nullptr && tid == 0u && leader) A.trace[(size_t)c * 16u + 3u] = wall_clock64();
   // ---- placement
   const uint8_t* slot = A.slots + (size_t)c * A.slot_stride;
   // a chunk with three helpers or more (small batches): the leader builds the section, the helpers copy -- the section is the
@@ -443,10 +426,10 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
   const uint32_t wid = leader_copies ? y * (T / 64) + wave : (y - 1u) * (T / 64) + wave;
   const uint32_t n_waves = (leader_copies ? A.splits : A.splits - 1u) * (T / 64);
   const bool copies = leader_copies || !leader;
-  const bool section_first = !fuse || !leader || A.order == 1u || (A.order == 0u && (c & 1u) == 0u);
-  if (!section_first && copies && !(A.ablate & 1u)) fin_copy(L, slot, chunk_out, wid, n_waves, lane, A.copy_mode);
-  if (A.trace != nullptr && tid == 0u && leader) A.trace[(size_t)c * 16u + 4u] = wall_clock64();
-  if (FUSE_BPV != 0 && fuse && leader && !(A.ablate & 2u)) {
+  // fused Palette: even chunks build the section first, odd chunks copy first
+  const bool section_first = !fuse || !leader || (c & 1u) == 0u;
+  if (!section_first && copies) fin_copy(L, slot, chunk_out, wid, n_waves, lane);
+  if (FUSE_BPV != 0 && fuse && leader) {
     const P p(smem);
     uint8_t* sec = chunk_out + 4u + L.doff[s_a];
     uint8_t* idx = chunk_out + 4u + L.doff[s_b];
@@ -463,9 +446,7 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
       sec[2] = (uint8_t)((U >> 8) & 0xffu);  // static_cast<uint16_t>(palette.size()), v5_codec.cpp:464
     }
   }
-  if (A.trace != nullptr && tid == 0u && leader) A.trace[(size_t)c * 16u + 5u] = wall_clock64();
-  if (section_first && copies && !(A.ablate & 1u)) fin_copy(L, slot, chunk_out, wid, n_waves, lane, A.copy_mode);
-  if (A.trace != nullptr && tid == 0u && leader) A.trace[(size_t)c * 16u + 6u] = wall_clock64();
+  if (section_first && copies) fin_copy(L, slot, chunk_out, wid, n_waves, lane);
 }
 
 }  // namespace cldn

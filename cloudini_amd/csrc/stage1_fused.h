@@ -190,7 +190,6 @@ struct FusedArgs {
   uint32_t tail_rel;             // its offset behind plan.ops[0].offset (inside the LOADW dwords loaded per point)
   uint32_t tail_size;            // field bytes
   const uint16_t* tail_windows;  // OP_GORILLA64: k_gorilla_windows' window in front of every piece, [chunk * 128 + piece]
-  uint32_t ablate;               // profiling only (CLDN_HIP_ABLATE): 4 no column stores
   // n_probe != 0: the first n_probe workgroups of the grid are not pieces: workgroup b decides the adaptive-int mode of
   // (cloud b / n_adaptive, field b % n_adaptive) on the first <= 4096 values of the cloud, read from the AoS input
   // (analyzeAdaptiveIntField + selectBestAdaptiveIntMode, src/v5_codec.cpp:387-412, :934-949) -- next to the pieces
@@ -545,17 +544,15 @@ __device__ __forceinline__ void fused_body(const DevPlan& plan, const FusedArgs&
       R += row_bytes;
 
       // AoS -> SoA split of the adaptive-int fields
-      if (!(A.ablate & 4u)) {
 #pragma unroll
-        for (uint32_t a = 0; a < kHoistCols; ++a)
-          if (a < na) col_store(hc_off[a], hc_rel[a], hc_bpv[a], hc_in[a], hc_ptr[a], cur, emits, idx);
-        for (uint32_t a = kHoistCols; a < na; ++a) {  // uniform loop: the plan is read with scalar loads
-          uint32_t f_off, rel, bpv;
-          bool in_regs;
-          uint8_t* colp;
-          col_args(a, f_off, rel, bpv, in_regs, colp);
-          col_store(f_off, rel, bpv, in_regs, colp, cur, emits, idx);
-        }
+      for (uint32_t a = 0; a < kHoistCols; ++a)
+        if (a < na) col_store(hc_off[a], hc_rel[a], hc_bpv[a], hc_in[a], hc_ptr[a], cur, emits, idx);
+      for (uint32_t a = kHoistCols; a < na; ++a) {  // uniform loop: the plan is read with scalar loads
+        uint32_t f_off, rel, bpv;
+        bool in_regs;
+        uint8_t* colp;
+        col_args(a, f_off, rel, bpv, in_regs, colp);
+        col_store(f_off, rel, bpv, in_regs, colp, cur, emits, idx);
       }
     }
   };
@@ -615,7 +612,7 @@ __device__ __forceinline__ void fused_body(const DevPlan& plan, const FusedArgs&
   };
 
   // the four streams of the workgroup go back to back into the workgroup's range of the chunk slot
-  // (one segment of ~11 KB for k_compact instead of four small ones)
+  // (one segment of ~11 KB for k_finish instead of four small ones)
   if (lane == 0u) wg_misc[wave] = R;
   __syncthreads();
   uint32_t before = 0u, total = 0u;

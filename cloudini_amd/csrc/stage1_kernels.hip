@@ -9,9 +9,9 @@
 //                      point / varint tokens; block scan of token bytes; tokens OR-ed into an LDS byte ring;
 //                      ring flushed with 16 B/lane stores. Also splits the V5 adaptive-int fields out into SoA
 //                      columns (the "AoS->SoA channel split") for the section kernel.
-//   k_chunk_offsets    exclusive scan of (4 + payload) over the batch's chunks.
-//   k_compact          concatenates each chunk's segments behind its [u32 size] prefix into the final framed
-//                      stream (byte-exact, arbitrary destination alignment).
+//   k_finish           (stage1_finish.h) adds up the chunks' framed sizes and concatenates each chunk's segments
+//                      behind its [u32 size] prefix into the final framed stream (byte-exact, arbitrary destination
+//                      alignment).
 //
 // This is integer / bit-pack work bounded by HBM bandwidth: no MFMA anywhere.
 #include <hip/hip_runtime.h>
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(T) void k_encode_floatn(const DevPlan plan, const u
                                                      uint8_t* __restrict__ slots, uint64_t slot_stride,
                                                      Seg* __restrict__ segs, uint32_t segs_per_chunk,
                                                      const ColumnPtrs cols, uint32_t subs, uint32_t sub_points,
-                                                     uint32_t sub_stride, uint32_t ablate) {
+                                                     uint32_t sub_stride) {
   constexpr int NW = T / 64;
   constexpr uint32_t ROW = NW * 63u;
   constexpr uint32_t TILE = ROW * PPT;
@@ -571,7 +571,7 @@ __global__ __launch_bounds__(T) void k_encode_floatn(const DevPlan plan, const u
       FloatVec<LOADW> z;
 #pragma unroll
       for (int k = 0; k < LOADW; ++k) z.v[k] = 0.0f;
-      if (idx >= idx_lo && idx < n && !(ablate & 8u)) {
+      if (idx >= idx_lo && idx < n) {
         const uint8_t* a = gbase + (ptrdiff_t)idx * (ptrdiff_t)step;
         if (!UNAL) {
           z = *reinterpret_cast<const FloatVec<LOADW>*>(a);
@@ -695,9 +695,9 @@ __global__ __launch_bounds__(T) void k_encode_floatn(const DevPlan plan, const u
     const uint32_t r_end = R + tile_total;
     const uint32_t target = last ? ((r_end + 15u) & ~15u) : (r_end & ~15u);
 
-    if (plan.n_adaptive && LOADW > LANES && !(ablate & 1u)) {
+    if (plan.n_adaptive && LOADW > LANES) {
       for (uint32_t a = 0; a < plan.n_adaptive; ++a) {
-        if (!col_staged<L3 == 4>(plan, a, LOADW, LANES) || (ablate & 16u)) continue;
+        if (!col_staged<L3 == 4>(plan, a, LOADW, LANES)) continue;
         const uint32_t bpv = plan.adaptive[a].bpv;
         uint8_t* st = colstage + (size_t)a * (TILE * 4u);
 #pragma unroll
@@ -731,10 +731,10 @@ __global__ __launch_bounds__(T) void k_encode_floatn(const DevPlan plan, const u
             const uint32_t nqp = dpp_wave_shr1(isn ? 0u : (0u - (uint32_t)q));
             uint32_t a0, a1, l;
             floatn_token(isn, (int32_t)((uint32_t)q + nqp), a0, a1, l);
-            if (plen[j] && !(ablate & 2u)) ring_put5<RING_BYTES, decltype(windowed)::value>(ring, off, a0, a1, l, win_lo_dw);
+            if (plen[j]) ring_put5<RING_BYTES, decltype(windowed)::value>(ring, off, a0, a1, l, win_lo_dw);
             off += l;
           }
-        } else if (plen[j] && !(ablate & 2u)) {
+        } else if (plen[j]) {
 #pragma unroll
           for (int k = 0; k < LANES; ++k) {
             const uint32_t t = tok[j][k];
@@ -750,12 +750,12 @@ __global__ __launch_bounds__(T) void k_encode_floatn(const DevPlan plan, const u
     // AoS -> SoA split of the adaptive-int fields. Fields covered by the point load are taken from registers;
     // 2/4-byte fields are staged in LDS (written after the scan barrier) and leave as 16-byte stores.
     auto write_columns = [&]() __attribute__((always_inline)) {
-      if (plan.n_adaptive && !(ablate & 1u)) {
+      if (plan.n_adaptive) {
         const uint32_t tile_pts = min(TILE, (uint32_t)n - base);
         for (uint32_t a = 0; a < plan.n_adaptive; ++a) {
           const uint32_t bpv = plan.adaptive[a].bpv;
           uint8_t* gcol = cols.p[a] + (first_point + base) * bpv;
-          const bool staged = col_staged<L3 == 4>(plan, a, LOADW, LANES) && (((uintptr_t)gcol & 15u) == 0u) && !(ablate & 16u);
+          const bool staged = col_staged<L3 == 4>(plan, a, LOADW, LANES) && (((uintptr_t)gcol & 15u) == 0u);
           if (staged) {
             const uint8_t* st = colstage + (size_t)a * (TILE * 4u);
             const uint32_t bytes = tile_pts * bpv;
@@ -801,7 +801,7 @@ __global__ __launch_bounds__(T) void k_encode_floatn(const DevPlan plan, const u
       __syncthreads();
       write_columns();
       if (!PREFETCH && !last) load_tile(base + TILE, cur);
-      if (!(ablate & 4u)) ring_flush_n<T, RING_BYTES>(ring, slot, F, target);
+      ring_flush_n<T, RING_BYTES>(ring, slot, F, target);
       F = target;
     } else {
       for (;;) {
@@ -1125,160 +1125,17 @@ __global__ __launch_bounds__(kGorThreads) void k_gorilla_windows(const DevPlan p
   }
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// k_chunk_offsets: payload size of every chunk, exclusive scan of the framed sizes (4 + payload), per-cloud
-// stream offsets. One workgroup.
-// ------------------------------------------------------------------------------------------------------------
-
-template <int T>
-__global__ __launch_bounds__(T) void k_chunk_offsets(const Seg* __restrict__ segs, uint32_t segs_per_chunk,
-                                                     uint32_t n_chunks, const uint32_t* __restrict__ cloud_first_chunk,
-                                                     uint32_t n_clouds, uint32_t* __restrict__ chunk_payload,
-                                                     uint64_t* __restrict__ chunk_dst,
-                                                     uint64_t* __restrict__ stream_offsets) {
-  __shared__ uint32_t wtot[32];
-  uint64_t running = 0;
-  for (uint32_t base = 0; base < n_chunks; base += T) {
-    const uint32_t c = base + threadIdx.x;
-    uint32_t framed = 0u;
-    if (c < n_chunks) {
-      uint32_t payload = 0u;
-      for (uint32_t s = 0; s < segs_per_chunk; ++s) payload += segs[(size_t)c * segs_per_chunk + s].size;
-      chunk_payload[c] = payload;
-      framed = payload + 4u;
-    }
-    uint32_t total;
-    const uint32_t excl = block_exclusive_scan<T>(framed, wtot, &total);
-    if (c < n_chunks) chunk_dst[c] = running + excl;
-    running += total;
-    __syncthreads();
-  }
-  __syncthreads();
-  // stream offset of cloud k = destination of its first chunk (clouds without chunks inherit the next one)
-  for (uint32_t k = threadIdx.x; k <= n_clouds; k += T) {
-    const uint32_t fc = (k < n_clouds) ? cloud_first_chunk[k] : n_chunks;
-    stream_offsets[k] = (fc < n_chunks) ? chunk_dst[fc] : running;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// k_compact: final framed stream. grid = (n_chunks, splits). The chunk's segment table is read once into LDS and
-// cut into work items of at most kCompactItemUnits 16-byte units; the waves of the chunk's workgroups take items
-// round-robin, so many small segments (sub-chunked small batches) and one large segment (huge batches) both keep
-// every wave busy without a dependent global load per segment. Source segments start 16-byte aligned; the
-// destination position is arbitrary.
-// ------------------------------------------------------------------------------------------------------------
-
+// byte funnel shift: the 4 bytes of hi:lo from byte sb on (k_finish's copy builds 16-byte destination units from them)
 __device__ __forceinline__ uint32_t funnel_bytes(uint32_t lo, uint32_t hi, uint32_t sb) {
   return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (sb * 8u));
-}
-
-constexpr uint32_t kCompactMaxSegs = 96u + 2u * kMaxAdaptive;  // sub-chunk or piece segments + two per section
-constexpr uint32_t kCompactItemUnits = 256u;  // 4 KiB per item
-constexpr uint32_t kCompactMaxItems = 1024u;
-
-template <int T>
-__global__ __launch_bounds__(T) void k_compact(const uint8_t* __restrict__ slots, uint64_t slot_stride,
-                                               const Seg* __restrict__ segs, uint32_t segs_per_chunk,
-                                               const uint32_t* __restrict__ chunk_payload,
-                                               const uint64_t* __restrict__ chunk_dst, uint8_t* __restrict__ out,
-                                               uint64_t out_capacity, uint32_t* __restrict__ status) {
-  __shared__ Seg seg_l[kCompactMaxSegs];
-  __shared__ uint32_t doff_l[kCompactMaxSegs];               // destination offset of every segment behind the size word
-  __shared__ uint32_t item_seg[kCompactMaxItems], item_u0[kCompactMaxItems];
-  __shared__ uint32_t n_items_l;
-  const uint32_t c = blockIdx.x;
-  const uint32_t payload = chunk_payload[c];
-  // work items of 4 KiB, larger when the chunk is so big (wide raw-copied points: up to 32768 * 1024 bytes) that 4 KiB
-  // items would not fit the table
-  const uint32_t item_units = max(kCompactItemUnits, (payload >> 4) / (kCompactMaxItems - kCompactMaxSegs - 8u) + 1u);
-  const uint64_t dst0 = chunk_dst[c];
-  if (dst0 + 4u + payload > out_capacity) {
-    if (threadIdx.x == 0 && blockIdx.y == 0) atomicOr(status, (uint32_t)ST_OUT_OVERFLOW);
-    return;
-  }
-  if (blockIdx.y == 0 && threadIdx.x < 4u) out[dst0 + threadIdx.x] = (uint8_t)(payload >> (8u * threadIdx.x));
-  if (threadIdx.x < segs_per_chunk) seg_l[threadIdx.x] = segs[(size_t)c * segs_per_chunk + threadIdx.x];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t d = 0u, n_items = 0u;
-    for (uint32_t s = 0; s < segs_per_chunk; ++s) {
-      doff_l[s] = d;
-      const uint32_t size = seg_l[s].size;
-      if (size) {
-        // items cover the destination-aligned 16-byte units of the segment (+ one item for a segment without any)
-        const uint32_t head = min(size, (uint32_t)((16u - (uint32_t)((dst0 + 4u + d) & 15u)) & 15u));
-        const uint32_t units = (size - head) >> 4;
-        uint32_t u0 = 0u;
-        do {
-          if (n_items < kCompactMaxItems) {
-            item_seg[n_items] = s;
-            item_u0[n_items] = u0;
-            ++n_items;
-          }
-          u0 += item_units;
-        } while (u0 < units);
-      }
-      d += size;
-    }
-    n_items_l = n_items;
-  }
-  __syncthreads();
-
-  const uint8_t* slot = slots + (size_t)c * slot_stride;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wid = blockIdx.y * (T / 64) + (threadIdx.x >> 6);
-  const uint32_t n_waves = gridDim.y * (T / 64);
-  const uint32_t n_items = n_items_l;
-  for (uint32_t it = wid; it < n_items; it += n_waves) {
-    const uint32_t sidx = item_seg[it], u0 = item_u0[it];
-    const Seg sg = seg_l[sidx];
-    const uint8_t* src = slot + sg.off;
-    uint8_t* dst = out + dst0 + 4u + doff_l[sidx];
-    const uint32_t size = sg.size;
-    // head: bytes until dst is 16-byte aligned; tail: bytes behind the last whole unit (first item of the segment)
-    const uint32_t head = min(size, (uint32_t)((16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u));
-    const uint32_t body_units = (size - head) >> 4;
-    const uint32_t tail = (size - head) & 15u;
-    if (u0 == 0u) {
-      if (lane < head) dst[lane] = src[lane];
-      if (lane >= 32u && lane < 32u + tail) {
-        const uint32_t k = head + body_units * 16u + (lane - 32u);
-        dst[k] = src[k];
-      }
-    }
-    // body: dst-aligned 16-byte units; source bytes [head + 16j, head + 16j + 16) straddle two aligned units
-    const uint32_t sdw = head >> 2, sb = head & 3u;
-    const uint4* src4 = reinterpret_cast<const uint4*>(src);
-    uint4* dst4 = reinterpret_cast<uint4*>(dst + head);
-    const uint32_t u1 = min(body_units, u0 + item_units);
-    for (uint32_t j = u0 + lane; j < u1; j += 64u) {
-      const uint4 a = src4[j];
-      uint4 b = make_uint4(0u, 0u, 0u, 0u);
-      if (head != 0u) b = src4[j + 1u];
-      uint32_t w0, w1, w2, w3, w4;
-      switch (sdw) {
-        case 0: w0 = a.x; w1 = a.y; w2 = a.z; w3 = a.w; w4 = b.x; break;
-        case 1: w0 = a.y; w1 = a.z; w2 = a.w; w3 = b.x; w4 = b.y; break;
-        case 2: w0 = a.z; w1 = a.w; w2 = b.x; w3 = b.y; w4 = b.z; break;
-        default: w0 = a.w; w1 = b.x; w2 = b.y; w3 = b.z; w4 = b.w; break;
-      }
-      uint4 o;
-      o.x = funnel_bytes(w0, w1, sb);
-      o.y = funnel_bytes(w1, w2, sb);
-      o.z = funnel_bytes(w2, w3, sb);
-      o.w = funnel_bytes(w3, w4, sb);
-      dst4[j] = o;
-    }
-  }
 }
 
 }  // namespace cldn
 
 // ------------------------------------------------------------------------------------------------------------
 // V5 adaptive-int sections (src/v5_codec.cpp:258-491). One workgroup per (chunk, adaptive field); input is the
-// SoA column written by k_encode_regular. The same device routines serve k_probe_modes (sizes only, over the
-// first <= 4096 values of a cloud) and k_encode_sections (bytes, over a chunk).
+// SoA column written by k_encode_regular. The general section kernel k_encode_sections and the WIDE route
+// (stage1_wide.h) build a chunk's sections with the device routines below.
 // ------------------------------------------------------------------------------------------------------------
 
 namespace cldn {
@@ -1678,21 +1535,6 @@ __device__ uint32_t palette_pass(const uint8_t* col, uint32_t bpv, uint32_t n, u
   return flags[1];
 }
 
-// Distinct-value count of values [0, n) (mode analysis). Falls back to 8 hash partitions when one table
-// cannot hold the distinct values.
-template <int T>
-__device__ uint32_t palette_count(const uint8_t* col, uint32_t bpv, uint32_t n, PalTable tab, uint64_t* tile_vals,
-                                  uint64_t* miss_mask, uint32_t* flags) {
-  uint32_t u = palette_pass<T>(col, bpv, n, 0u, 1u, tab, tile_vals, miss_mask, flags, nullptr);
-  if (u != 0xffffffffu) return u;
-  u = 0u;
-  for (uint32_t p = 0; p < 8u; ++p) {
-    __syncthreads();
-    u += palette_pass<T>(col, bpv, n, p, 8u, tab, tile_vals, miss_mask, flags, nullptr);
-  }
-  return u;
-}
-
 // Full palette section of one chunk. Writes segment A ([0x01][u16 U][U values]) at dst and segment B (bit-packed
 // indexes) at dst + kPaletteIndexOffset; returns their sizes.
 template <int T>
@@ -1789,49 +1631,6 @@ __device__ __forceinline__ SecLds sec_lds_carve(uint8_t* smem) {
   l.ring = reinterpret_cast<uint32_t*>(smem + ring_off);
   l.wtot = reinterpret_cast<uint32_t*>(smem + ring_off + kRingBytes);
   return l;
-}
-
-// k_probe_modes: grid = (n_clouds, n_adaptive). analyzeAdaptiveIntField + selectBestAdaptiveIntMode
-// (v5_codec.cpp:387-412) over the first min(4096, n) values of the cloud's first chunk (window rule :934-949).
-__global__ __launch_bounds__(kSecThreads) void k_probe_modes(const DevPlan plan, const ChunkDesc* __restrict__ chunks,
-                                                             const uint32_t* __restrict__ cloud_first_chunk,
-                                                             const ColumnPtrs cols, uint8_t* __restrict__ modes) {
-  constexpr int T = kSecThreads;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const SecLds l = sec_lds_carve(smem);
-  const uint32_t cloud = blockIdx.x, a = blockIdx.y;
-  if (modes[cloud * plan.n_adaptive + a] != 0xffu) return;  // decided by k_probe_fast
-  __syncthreads();
-  const uint32_t fc = cloud_first_chunk[cloud];
-  if (fc == cloud_first_chunk[cloud + 1u]) {  // empty cloud
-    if (threadIdx.x == 0) modes[cloud * plan.n_adaptive + a] = 0u;
-    return;
-  }
-  const ChunkDesc cd = chunks[fc];
-  const uint32_t n = cd.n_points > kProbePoints ? kProbePoints : cd.n_points;
-  const uint32_t bpv = plan.adaptive[a].bpv, type = plan.adaptive[a].type;
-  const uint8_t* col = cols.p[a] + (size_t)cd.first_point * bpv;
-
-  const uint32_t delta = section_delta_varint<T, false>(col, bpv, type, n, l.ring, l.wtot, nullptr);
-  __syncthreads();
-  const uint32_t rle = section_runs<T, false, false>(col, bpv, type, n, l.ring, l.wtot, nullptr, l.list_pos, l.list_key);
-  __syncthreads();
-  const uint32_t drle = section_runs<T, false, true>(col, bpv, type, n, l.ring, l.wtot, nullptr, l.list_pos, l.list_key);
-  __syncthreads();
-  PalTable tab;
-  tab.keys = reinterpret_cast<uint64_t*>(l.main);
-  tab.first = reinterpret_cast<uint16_t*>(l.main + kPalSlots * 8u);
-  uint64_t* tile_vals = reinterpret_cast<uint64_t*>(l.main + kPalSlots * 10u);
-  uint64_t* miss_mask = reinterpret_cast<uint64_t*>(l.main + kPalSlots * 10u + T * 8u);
-  uint32_t* flags = reinterpret_cast<uint32_t*>(l.main + kPalSlots * 10u + T * 8u + 128u);
-  const uint32_t U = palette_count<T>(col, bpv, n, tab, tile_vals, miss_mask, flags);
-  const uint32_t pal = 3u + U * bpv + ((palette_bits(U) * n + 7u) >> 3);
-
-  uint32_t mode = 0u, best = delta;  // strict '<' in this order (selectBestAdaptiveIntMode)
-  if (pal < best) { best = pal; mode = 1u; }
-  if (rle < best) { best = rle; mode = 2u; }
-  if (drle < best) { mode = 3u; }
-  if (threadIdx.x == 0) modes[cloud * plan.n_adaptive + a] = (uint8_t)mode;
 }
 
 // k_encode_sections: the safety net behind the fast section kernels. grid = min(n_chunks * n_adaptive, kSecGrid) workgroups
@@ -2001,9 +1800,6 @@ int stage1_configure_kernels() {
     e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFloatnLds);
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_floatn)");
   }
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_probe_modes), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kSecLdsTotal);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_probe_modes)");
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode_sections),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSecLdsTotal);
   if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_sections)");
@@ -2024,8 +1820,7 @@ int stage1_configure_kernels() {
   if (int rc = stage1_configure_decode()) return rc;
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_section_fast), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kD32Lds);
   if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_section_fast)");
-  const void* pk32[] = {reinterpret_cast<const void*>(&k_section_palette32<uint16_t, kS2Threads>),
-                        reinterpret_cast<const void*>(&k_section_palette32<uint16_t, 512>),
+  const void* pk32[] = {reinterpret_cast<const void*>(&k_section_palette32<uint16_t, 512>),
                         reinterpret_cast<const void*>(&k_section_palette32<uint32_t, 512>)};
   for (const void* f : pk32) {
     e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Pal32<uint32_t>::kLds);
@@ -2104,16 +1899,13 @@ static int launch_fused(const EncodeLaunch& L, hipStream_t stream, uint32_t piec
   A.points_end = L.points_end;
   A.pieces = L.pieces + piece0;
   A.cols = L.cols;
-  static const uint32_t ablate_f = (uint32_t)dev_env_int("CLDN_HIP_ABLATE", 0);  // profiling only
-  A.ablate = ablate_f;
   A.slots = L.slots;
   A.slot_stride = L.slot_stride;
   A.piece_stride = L.sub_stride / kFusedWaves;  // sub_stride = one workgroup's range (4 pieces)
   A.segs = L.segs;
   A.segs_per_chunk = L.segs_per_chunk;
   // mode probe next to the pieces: fields of 2 and 4 bytes (the distinct-value structure has to fit the launch's LDS)
-  static const bool probe_in_piece_env = dev_env_int("CLDN_HIP_PROBE_IN_PIECE", 1) != 0;  // A/B switch
-  bool probe_here = probe_in_piece_env && piece0 == 0u && L.plan->n_adaptive != 0u && !L.modes_forced && L.n_clouds != 0u &&
+  bool probe_here = piece0 == 0u && L.plan->n_adaptive != 0u && !L.modes_forced && L.n_clouds != 0u &&
                     (uint64_t)L.n_clouds * L.plan->n_adaptive < (1u << 20);
   for (uint32_t a = 0; a < L.plan->n_adaptive && probe_here; ++a) probe_here = L.plan->adaptive[a].bpv <= 4u;
   A.n_probe = probe_here ? L.n_clouds * L.plan->n_adaptive : 0u;
@@ -2190,13 +1982,12 @@ static int launch_sections(const EncodeLaunch& L, hipStream_t stream, uint32_t c
   uint8_t* flags = L.fallback_flags + (size_t)c0 * na;
   ColumnPtrs rank_cols;
   for (int a = 0; a < kMaxAdaptive; ++a) rank_cols.p[a] = reinterpret_cast<uint8_t*>(L.ranks[a]);
-  static const bool no_fast = dev_env("CLDN_HIP_NO_FAST_SECTIONS") != nullptr;  // A/B switch: general kernels only
   // One launch per kernel type covers all the fields of that type (grid.y): the fields are independent and every one of
   // these kernels is latency-bound at one workgroup per chunk, so a schema with five integer channels gets five times
   // the workgroups in flight instead of five launches in a row.
   SectionFields run16, run32, pal16, pal32, pal64;
   run16.n = run32.n = pal16.n = pal32.n = pal64.n = 0u;
-  for (uint32_t a = 0; a < na && !no_fast; ++a) {
+  for (uint32_t a = 0; a < na; ++a) {
     const uint32_t bpv = L.plan->adaptive[a].bpv;
     const uint32_t hint = L.mode_hint[a];
     if (hint & 0xDu) {  // DeltaVarint / Rle / DeltaRle expected somewhere
@@ -2221,16 +2012,10 @@ static int launch_sections(const EncodeLaunch& L, hipStream_t stream, uint32_t c
     if (runs.n) hipLaunchKernelGGL(k_section_fast, dim3(nch, runs.n), dim3(kS2Threads), kD32Lds, stream, SEC_ARGS(runs));
   }
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_section_fast");
+  // 512-thread workgroups (two bitmap words and two groups of 32 values per thread): four of them fit a CU, so a batch of
+  // up to 1024 chunks is one generation (C2: sections 0.066 ms with 1024 threads, 0.062 ms with 512)
   if (pal16.n)
-  {
-    // 512-thread workgroups (two bitmap words and two groups of 32 values per thread): four of them fit a CU, so a batch
-    // of up to 1024 chunks is one generation (C2: sections 0.066 -> 0.062 ms); CLDN_HIP_PAL32_THREADS=1024 is the A/B switch
-    static const bool pal1024 = dev_env_int("CLDN_HIP_PAL32_THREADS", 0) == 1024;
-    if (pal1024)
-      hipLaunchKernelGGL((k_section_palette32<uint16_t, kS2Threads>), dim3(nch, pal16.n), dim3(kS2Threads), Pal32<uint16_t>::kLds, stream, SEC_ARGS(pal16), rank_cols, L.status);
-    else
-      hipLaunchKernelGGL((k_section_palette32<uint16_t, 512>), dim3(nch, pal16.n), dim3(512), Pal32<uint16_t>::kLds, stream, SEC_ARGS(pal16), rank_cols, L.status);
-  }
+    hipLaunchKernelGGL((k_section_palette32<uint16_t, 512>), dim3(nch, pal16.n), dim3(512), Pal32<uint16_t>::kLds, stream, SEC_ARGS(pal16), rank_cols, L.status);
   if (pal32.n)
     hipLaunchKernelGGL((k_section_palette32<uint32_t, 512>), dim3(nch, pal32.n), dim3(512), Pal32<uint32_t>::kLds, stream, SEC_ARGS(pal32), rank_cols, L.status);
   if (pal64.n)
@@ -2245,29 +2030,9 @@ static int launch_sections(const EncodeLaunch& L, hipStream_t stream, uint32_t c
 
 constexpr uint32_t kNoFusedField = 0xffffffffu;
 
-// profiling only: phase stamps of k_finish's leaders (CLDN_HIP_FINISH_TRACE=1), read back by tools/fintrace.py through
-// cldn_hip_debug_finish_trace (not part of include/cloudini_hip.h)
-static unsigned long long* g_fin_trace = nullptr;
-static uint32_t g_fin_trace_chunks = 0u;
-static unsigned long long* stage1_finish_trace_buffer(uint32_t n_chunks) {
-  if (n_chunks > g_fin_trace_chunks) {
-    if (g_fin_trace) (void)hipFree(g_fin_trace);
-    g_fin_trace = nullptr;
-    if (hipMalloc(&g_fin_trace, (size_t)n_chunks * 16u * sizeof(unsigned long long)) != hipSuccess) return nullptr;
-    g_fin_trace_chunks = n_chunks;
-  }
-  return g_fin_trace;
-}
-extern "C" __attribute__((visibility("default"))) int cldn_hip_debug_finish_trace(unsigned long long* host_out, uint32_t n_chunks) {
-  if (!g_fin_trace || n_chunks > g_fin_trace_chunks) return -1;
-  if (hipDeviceSynchronize() != hipSuccess) return -2;
-  return hipMemcpy(host_out, g_fin_trace, (size_t)n_chunks * 16u * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
-}
-
 // bytes per point of a regular stream made of fixed-size encoders only (XOR-coded floats, raw copies), 0 otherwise
 static uint32_t fixed_point_bytes(const DevPlan& P) {
-  static const bool off = dev_env("CLDN_HIP_NO_FIXED_ENCODE") != nullptr;  // A/B switch
-  if (off || P.n_ops == 0u || P.n_gorilla != 0u) return 0u;
+  if (P.n_ops == 0u || P.n_gorilla != 0u) return 0u;
   uint32_t bytes = 0u;
   for (uint32_t k = 0; k < P.n_ops; ++k) {
     const uint32_t kd = P.ops[k].kind;
@@ -2368,12 +2133,9 @@ static int launch_encode_wide(const EncodeLaunch& L) {
 int stage1_launch_encode(const EncodeLaunch& L) {
   hipError_t e;
   if (L.wide) return launch_encode_wide(L);
-  // CLDN_HIP_FINISH (A/B switch): 0 = the round-2 kernels (k_chunk_offsets + k_compact), 1 = k_finish without the fused
-  // Palette section, 2 (default) = k_finish with it where the schema allows
-  static const int finish_mode = dev_env_int("CLDN_HIP_FINISH", 2);
   // the field whose Palette sections k_finish builds itself: the first 2- or 4-byte adaptive field that may commit Palette
   uint32_t fused_field = kNoFusedField;
-  if (finish_mode >= 2 && L.n_chunks && !L.chunks_only) {
+  if (L.n_chunks && !L.chunks_only) {
     for (uint32_t a = 0; a < L.plan->n_adaptive && fused_field == kNoFusedField; ++a)
       if ((L.plan->adaptive[a].bpv == 2u || L.plan->adaptive[a].bpv == 4u) && (L.mode_hint[a] & 0x2u)) fused_field = a;
   }
@@ -2398,14 +2160,13 @@ int stage1_launch_encode(const EncodeLaunch& L) {
     if (rc != CLDN_HIP_OK) return rc;
   } else if (L.n_chunks && fixed_point_bytes(*L.plan) != 0u) {
     // every per-point encoder writes a fixed number of bytes (lossless floats, raw copies): one thread per point, which also
-    // splits the integer fields off into their columns. CLDN_HIP_NO_FIXED_ENCODE=1: A/B switch (handled in fixed_point_bytes)
+    // splits the integer fields off into their columns
     const uint32_t pb = fixed_point_bytes(*L.plan);
     const uint64_t total_points = (uint64_t)(L.points_end - L.points) / L.plan->point_step;
     const uint64_t total = 4ull * L.n_chunks + (uint64_t)pb * total_points;
     // without integer columns every size is known here: the kernel writes the framed streams themselves (an output that is too
-    // small takes the slot path, whose k_finish reports it). CLDN_HIP_NO_FIXED_DIRECT=1: A/B switch
-    static const bool no_direct = dev_env("CLDN_HIP_NO_FIXED_DIRECT") != nullptr;
-    const bool direct = !no_direct && !L.chunks_only && finish_mode != 0 && L.plan->n_adaptive == 0u && total <= L.out_capacity;
+    // small takes the slot path, whose k_finish reports it)
+    const bool direct = !L.chunks_only && L.plan->n_adaptive == 0u && total <= L.out_capacity;
     hipLaunchKernelGGL(k_encode_fixed, dim3(L.n_chunks, kPointsPerChunk / 256u), dim3(256), 0, L.stream, *L.plan, L.points, L.chunks,
                        L.slots, L.slot_stride, L.segs, L.segs_per_chunk, L.subs, L.sub_points, L.sub_stride, pb, L.cols,
                        direct ? L.out : (uint8_t*)nullptr, L.chunk_payload, L.chunk_dst);
@@ -2424,7 +2185,6 @@ int stage1_launch_encode(const EncodeLaunch& L) {
   } else if (L.n_chunks) {
     int l3 = 3;
     const int lanes = floatn_lanes(*L.plan, L.points, &l3);
-    static const uint32_t ablate = (uint32_t)dev_env_int("CLDN_HIP_ABLATE", 0);  // profiling only
     const bool unal = lanes && floatn_unaligned(*L.plan, L.points);
     const int loadw = lanes ? floatn_loadw(*L.plan, lanes, unal, l3) : 0;
     // LDS: ring, scan scratch and one staging area per adaptive field that can be staged (at most kStagedCols)
@@ -2432,7 +2192,7 @@ int stage1_launch_encode(const EncodeLaunch& L) {
 #define LAUNCH_FLOATN(TT, LL, PP, ...)                                                                                          \
   hipLaunchKernelGGL((k_encode_floatn<TT, LL, PP, kFloatnRing, __VA_ARGS__>), dim3(L.n_chunks * L.subs), dim3(TT), floatn_lds, \
                      L.stream, *L.plan, L.points, L.points_end, L.chunks, L.slots, L.slot_stride, L.segs,          \
-                     L.segs_per_chunk, L.cols, L.subs, L.sub_points, L.sub_stride, ablate)
+                     L.segs_per_chunk, L.cols, L.subs, L.sub_points, L.sub_stride)
     if (l3 == 4 && loadw == 8) LAUNCH_FLOATN(256, 4, 2, 8, false, false, 4);
     else if (l3 == 4 || loadw == 0) goto generic_regular;
     else if (unal && lanes == 3 && loadw == 4) LAUNCH_FLOATN(256, 3, 2, 4, false, true);
@@ -2462,18 +2222,10 @@ int stage1_launch_encode(const EncodeLaunch& L) {
   if (L.events) (void)hipEventRecord(L.events[2], L.stream);
   const uint32_t na = L.plan->n_adaptive;
   if (na && L.n_chunks) {
-    static const bool no_fast = dev_env("CLDN_HIP_NO_FAST_SECTIONS") != nullptr;  // A/B switch: general kernels only
     if (!L.modes_forced && !modes_probed) {
-      if (!no_fast) {
-        hipLaunchKernelGGL(k_probe_fast, dim3(L.n_clouds, na), dim3(kS2Threads), kProbeLds, L.stream, *L.plan, L.chunks,
-                           L.cloud_first_chunk, L.cols, L.modes);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_probe_fast");
-      } else {  // A/B switch: the general probe decides every mode
-        (void)hipMemsetAsync(L.modes, 0xff, (size_t)L.n_clouds * na, L.stream);
-        hipLaunchKernelGGL(k_probe_modes, dim3(L.n_clouds, na), dim3(kSecThreads), kSecLdsTotal, L.stream, *L.plan,
-                           L.chunks, L.cloud_first_chunk, L.cols, L.modes);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_probe_modes");
-      }
+      hipLaunchKernelGGL(k_probe_fast, dim3(L.n_clouds, na), dim3(kS2Threads), kProbeLds, L.stream, *L.plan, L.chunks,
+                         L.cloud_first_chunk, L.cols, L.modes);
+      if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_probe_fast");
     }
     const int rc_sec = launch_sections(L, L.stream, 0u, L.n_chunks, fused_field);
     if (rc_sec != CLDN_HIP_OK) return rc_sec;
@@ -2488,90 +2240,62 @@ int stage1_launch_encode(const EncodeLaunch& L) {
     if (L.events) (void)hipEventRecord(L.events[4], L.stream);
     return CLDN_HIP_OK;
   }
-  if (finish_mode != 0) {
-    if (L.n_chunks == 0u) {  // no chunk, no workgroup: every cloud's stream is empty
-      if ((e = hipMemsetAsync(L.stream_offsets, 0, (size_t)(L.n_clouds + 1u) * sizeof(uint64_t), L.stream)) != hipSuccess)
-        return hip_fail(e, "hipMemsetAsync(stream_offsets)");
+  if (L.n_chunks == 0u) {  // no chunk, no workgroup: every cloud's stream is empty
+    if ((e = hipMemsetAsync(L.stream_offsets, 0, (size_t)(L.n_clouds + 1u) * sizeof(uint64_t), L.stream)) != hipSuccess)
+      return hip_fail(e, "hipMemsetAsync(stream_offsets)");
+  } else {
+    FinishArgs F;
+    F.chunks = L.chunks;
+    F.n_chunks = L.n_chunks;
+    F.cloud_first_chunk = L.cloud_first_chunk;
+    F.n_clouds = L.n_clouds;
+    F.slots = L.slots;
+    F.slot_stride = L.slot_stride;
+    F.segs = L.segs;
+    F.segs_per_chunk = L.segs_per_chunk;
+    F.subs = L.subs;
+    F.rec = L.fin_rec;
+    F.rec2 = L.fin_rec2;
+    F.anchor = L.fin_anchor;
+    F.epoch = L.fin_epoch;
+    F.ticket = L.fin_ticket;
+    F.use_ticket = L.use_ticket ? 1u : 0u;
+    F.test_timeout = L.test_timeout;
+    F.chunk_payload = L.chunk_payload;
+    F.chunk_dst = L.chunk_dst;
+    F.stream_offsets = L.stream_offsets;
+    F.out = L.out;
+    F.out_capacity = L.out_capacity;
+    F.status = L.status;
+    F.modes = L.modes;
+    F.n_adaptive = na;
+    F.fuse_field = fused_field;
+    F.fuse_col = nullptr;
+    F.fuse_first = nullptr;
+    if (fused_field != kNoFusedField) {
+      F.fuse_col = L.cols.p[fused_field];
+      F.fuse_first = L.ranks[fused_field];
+      // small batches: 1024-thread workgroups (a chunk's Palette section is latency-bound: twice the threads, 0.6x the time)
+      const bool big = L.n_chunks < 200u;
+      const uint32_t splits = big ? 4u : (L.n_chunks >= 512u ? 1u : 2u);
+      F.splits = splits;
+      const bool u16 = L.plan->adaptive[fused_field].bpv == 2u;
+      if (big && u16)
+        hipLaunchKernelGGL((k_finish<1024, 2>), dim3(L.n_chunks * splits), dim3(1024), Pal32<uint16_t>::kLds, L.stream, F);
+      else if (big)
+        hipLaunchKernelGGL((k_finish<1024, 4>), dim3(L.n_chunks * splits), dim3(1024), Pal32<uint32_t>::kLds, L.stream, F);
+      else if (u16)
+        hipLaunchKernelGGL((k_finish<512, 2>), dim3(L.n_chunks * splits), dim3(512), Pal32<uint16_t>::kLds, L.stream, F);
+      else
+        hipLaunchKernelGGL((k_finish<512, 4>), dim3(L.n_chunks * splits), dim3(512), Pal32<uint32_t>::kLds, L.stream, F);
     } else {
-      FinishArgs F;
-      F.chunks = L.chunks;
-      F.n_chunks = L.n_chunks;
-      F.cloud_first_chunk = L.cloud_first_chunk;
-      F.n_clouds = L.n_clouds;
-      F.slots = L.slots;
-      F.slot_stride = L.slot_stride;
-      F.segs = L.segs;
-      F.segs_per_chunk = L.segs_per_chunk;
-      F.subs = L.subs;
-      F.rec = L.fin_rec;
-      F.rec2 = L.fin_rec2;
-      F.anchor = L.fin_anchor;
-      F.epoch = L.fin_epoch;
-      F.ticket = L.fin_ticket;
-      static const uint32_t use_ticket = (uint32_t)dev_env_int("CLDN_HIP_FINISH_TICKET", 0);
-      static const uint32_t order = (uint32_t)dev_env_int("CLDN_HIP_FINISH_ORDER", 0);  // A/B switch
-      F.use_ticket = (use_ticket || L.use_ticket) ? 1u : 0u;
-      F.test_timeout = L.test_timeout;
-      F.order = order;
-      static const uint32_t copy_mode = (uint32_t)dev_env_int("CLDN_HIP_FINISH_COPY", 0);  // A/B switch
-      static const uint32_t fin_ablate = (uint32_t)dev_env_int("CLDN_HIP_FINISH_ABLATE", 0);  // profiling only
-      F.copy_mode = copy_mode;
-      F.trace = nullptr;
-      static const bool fin_trace = dev_env("CLDN_HIP_FINISH_TRACE") != nullptr;  // profiling only
-      if (fin_trace) F.trace = stage1_finish_trace_buffer(L.n_chunks);
-      F.ablate = fin_ablate;
-      F.chunk_payload = L.chunk_payload;
-      F.chunk_dst = L.chunk_dst;
-      F.stream_offsets = L.stream_offsets;
-      F.out = L.out;
-      F.out_capacity = L.out_capacity;
-      F.status = L.status;
-      F.modes = L.modes;
-      F.n_adaptive = na;
-      F.fuse_field = fused_field;
-      F.fuse_col = nullptr;
-      F.fuse_first = nullptr;
-      if (fused_field != kNoFusedField) {
-        F.fuse_col = L.cols.p[fused_field];
-        F.fuse_first = L.ranks[fused_field];
-        // small batches: 1024-thread workgroups (a chunk's Palette section is latency-bound: twice the threads, 0.6x the time)
-        static const uint32_t big_at = (uint32_t)dev_env_int("CLDN_HIP_FINISH_1024_BELOW", 200);  // A/B switch
-        const bool big = L.n_chunks < big_at;
-        static const uint32_t splits_env = (uint32_t)dev_env_int("CLDN_HIP_FINISH_SPLITS", 0);  // A/B switch
-        const uint32_t splits = splits_env ? splits_env : (big ? 4u : (L.n_chunks >= 512u ? 1u : 2u));
-        F.splits = splits;
-        const bool u16 = L.plan->adaptive[fused_field].bpv == 2u;
-        if (big && u16)
-          hipLaunchKernelGGL((k_finish<1024, 2>), dim3(L.n_chunks * splits), dim3(1024), Pal32<uint16_t>::kLds, L.stream, F);
-        else if (big)
-          hipLaunchKernelGGL((k_finish<1024, 4>), dim3(L.n_chunks * splits), dim3(1024), Pal32<uint32_t>::kLds, L.stream, F);
-        else if (u16)
-          hipLaunchKernelGGL((k_finish<512, 2>), dim3(L.n_chunks * splits), dim3(512), Pal32<uint16_t>::kLds, L.stream, F);
-        else
-          hipLaunchKernelGGL((k_finish<512, 4>), dim3(L.n_chunks * splits), dim3(512), Pal32<uint32_t>::kLds, L.stream, F);
-      } else {
-        const uint32_t splits = L.n_chunks >= 1024u ? 1u : (L.n_chunks >= 256u ? 4u : 16u);
-        F.splits = splits;
-        static const uint32_t ldspad = (uint32_t)dev_env_int("CLDN_HIP_FINISH_LDSPAD", 0);  // experiment: occupancy
-        hipLaunchKernelGGL((k_finish<256, 0>), dim3(L.n_chunks * splits), dim3(256), ldspad, L.stream, F);
-      }
-      if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_finish");
+      const uint32_t splits = L.n_chunks >= 1024u ? 1u : (L.n_chunks >= 256u ? 4u : 16u);
+      F.splits = splits;
+      hipLaunchKernelGGL((k_finish<256, 0>), dim3(L.n_chunks * splits), dim3(256), 0, L.stream, F);
     }
-    if (L.events) (void)hipEventRecord(L.events[4], L.stream);
-    return CLDN_HIP_OK;
-  }
-#ifdef CLDN_DEV  // (CLDN_HIP_FINISH=0: the round-2 kernels, an A/B reference of the development build)
-  hipLaunchKernelGGL(k_chunk_offsets<1024>, dim3(1), dim3(1024), 0, L.stream, L.segs, L.segs_per_chunk, L.n_chunks,
-                     L.cloud_first_chunk, L.n_clouds, L.chunk_payload, L.chunk_dst, L.stream_offsets);
-  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_chunk_offsets");
-  if (L.n_chunks) {
-    const uint32_t splits = L.n_chunks >= 1024u ? 1u : (L.n_chunks >= 256u ? 4u : 16u);
-    hipLaunchKernelGGL(k_compact<256>, dim3(L.n_chunks, splits), dim3(256), 0, L.stream, L.slots, L.slot_stride,
-                       L.segs, L.segs_per_chunk, L.chunk_payload, L.chunk_dst, L.out, L.out_capacity, L.status);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_compact");
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_finish");
   }
   if (L.events) (void)hipEventRecord(L.events[4], L.stream);
-#endif
   return CLDN_HIP_OK;
 }
 
@@ -2600,10 +2324,6 @@ int stage1_launch_frame(const FrameLaunch& L) {
   F.ticket = L.ticket;
   F.use_ticket = L.use_ticket;
   F.test_timeout = L.test_timeout;
-  F.order = 0u;
-  F.copy_mode = 0u;
-  F.ablate = 0u;
-  F.trace = nullptr;
   F.chunk_payload = L.chunk_payload;
   F.chunk_dst = L.chunk_dst;
   F.stream_offsets = L.stream_offsets;

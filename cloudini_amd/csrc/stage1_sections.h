@@ -8,14 +8,13 @@
 //                             (64-bit CAS on the key, atomicMin on the first-occurrence index), first-occurrence
 //                             ranks from ONE block-wide scan, 32 indexes per thread bit-packed into `bits` dwords.
 #pragma once
-// values of a chunk the Palette build inserts one per thread and round, in index order, before the blocked pass (same-box A/B of
-// k_finish on C2, 4096 / 2048 / 1024: 117.8 / 109.4 / 110.5 us -- the seed's compare-and-swaps contend for the few slots a
-// palette-coded field has; tools/dev/variants.sh stage1_kernels CLDN_PAL_SEED ...)
-#ifndef CLDN_PAL_SEED
-#define CLDN_PAL_SEED 2048u
-#endif
 
 namespace cldn {
+
+// values of a chunk the Palette build inserts one per thread and round, in index order, before the blocked pass (same-box A/B of
+// k_finish on C2, 4096 / 2048 / 1024: 117.8 / 109.4 / 110.5 us -- the seed's compare-and-swaps contend for the few slots a
+// palette-coded field has)
+constexpr uint32_t kPalSeed = 2048u;
 
 // the adaptive fields one section-kernel launch covers: blockIdx.y indexes the list
 struct SectionFields {
@@ -483,7 +482,7 @@ __device__ __forceinline__ Grp8<RawT> grp8_load(const RawT* col, uint32_t i0) {
 // trips per value and no per-value state in registers. A table word holds key and first-occurrence index
 // together (key << SHIFT | index, all-ones = free): claiming is a CAS, lowering the index an atomicMin on the
 // same word; once the ranks are known the index is replaced by the palette rank.
-//   seed    the chunk's first CLDN_PAL_SEED (2048) values in index order, one per thread and round: palette-coded fields have
+//   seed    the chunk's first kPalSeed (2048) values in index order, one per thread and round: palette-coded fields have
 //           few distinct values, so afterwards (nearly) every key sits at its true first index
 //   pass 1  all values, 8 per thread and step; the home words of the 8 are read together and the CAS / probe /
 //           atomicMin path runs only for new keys or lower indexes
@@ -631,30 +630,28 @@ __device__ __forceinline__ void pal32_pack(const Pal32<RawT>& p, const RawT* col
 // clear + seed + pass 1: afterwards the table holds every distinct value with its first index and misc[0] = their
 // number -- unless it returns false (more than kS2PalCapacity distinct values: pal32_slow_* take over)
 template <typename RawT, int T>
-__device__ __forceinline__ bool pal32_build(const Pal32<RawT>& p, const RawT* col, uint32_t n, unsigned long long* tr = nullptr) {
+__device__ __forceinline__ bool pal32_build(const Pal32<RawT>& p, const RawT* col, uint32_t n) {
   using P = Pal32<RawT>;
   using Word = typename P::Word;
   constexpr uint32_t WPT = kS2Threads / T;
   const uint32_t tid = threadIdx.x;
   // the seed's values are requested before the table is cleared, all rounds at once (branch-free loads: one memory
   // latency instead of one per round)
-  uint32_t seedv[CLDN_PAL_SEED / T];
+  uint32_t seedv[kPalSeed / T];
 #pragma unroll
-  for (uint32_t r = 0; r < CLDN_PAL_SEED / T; ++r) seedv[r] = (uint32_t)col[min(r * T + tid, n - 1u)];
+  for (uint32_t r = 0; r < kPalSeed / T; ++r) seedv[r] = (uint32_t)col[min(r * T + tid, n - 1u)];
   for (uint32_t s = tid; s < kS2PalSlots; s += T) p.tab[s] = P::kFree;
 #pragma unroll
   for (uint32_t w = 0; w < WPT; ++w) p.bitmap[w * T + tid] = 0u;
   if (tid < 4u) p.misc[tid] = 0u;
   __syncthreads();
-  if (tr != nullptr && tid == 0u) tr[0] = wall_clock64();
   // seed
 #pragma unroll
-  for (uint32_t r = 0; r < CLDN_PAL_SEED / T; ++r) {
+  for (uint32_t r = 0; r < kPalSeed / T; ++r) {
     const uint32_t i = r * T + tid;
     if (i < n) p.insert(seedv[r], i, p.tab[P::home(seedv[r])]);
   }
   __syncthreads();
-  if (tr != nullptr && tid == 0u) tr[1] = wall_clock64();
   // pass 1: the groups of a batch are requested together (branch-free loads, one memory latency per batch: 8 groups of
   // 2-byte values or 4 groups of 4-byte values = 32 VGPRs); a group's values that are not settled yet -- rare after
   // the seed -- go through ONE insert site, picked off a bit mask
@@ -671,7 +668,7 @@ __device__ __forceinline__ bool pal32_build(const Pal32<RawT>& p, const RawT* co
 #pragma unroll
     for (uint32_t k = 0; k < GB; ++k) {
       const uint32_t i0 = ((b + k) * T + tid) * 8u;
-      if (i0 >= n || i0 + 8u <= CLDN_PAL_SEED) continue;  // (the seed settled the first CLDN_PAL_SEED values)
+      if (i0 >= n || i0 + 8u <= kPalSeed) continue;  // (the seed settled the first kPalSeed values)
       Word w[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) w[j] = p.tab[P::home(g[k].get(j))];

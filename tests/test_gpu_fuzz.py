@@ -74,7 +74,7 @@ def _random_case(seed, wide=False):
 
 import os
 
-# CLDN_FUZZ_EXTRA extra seeds per test (tools/runs/r5_fuzz.sh: 30000); CLDN_FUZZ_BASE: where the extra seeds begin (default:
+# CLDN_FUZZ_EXTRA extra seeds per test (the round-5 campaign: 30000); CLDN_FUZZ_BASE: where the extra seeds begin (default:
 # right behind the fixed ones -- another value runs a campaign over other schemas)
 _EXTRA = int(os.environ.get("CLDN_FUZZ_EXTRA", "0"))
 _BASE = int(os.environ.get("CLDN_FUZZ_BASE", "0"))

@@ -50,9 +50,9 @@ def test_c_abi_exports_every_declared_symbol():
 
 
 def test_shipped_libraries_read_only_the_production_environment_variables():
-    """The default build carries no development switch: libcloudini_hip.so names no CLDN_HIP_*
-    variable at all (dev_env() is a constant outside -DCLDN_DEV builds), the host mirror names its three CLOUDINI_AMD_*
-    settings and the transcoder's timing print; the superseded kernel generations are not in the device code."""
+    """The library carries no development switch: libcloudini_hip.so names no CLDN_HIP_*
+    variable at all and its sources read no environment variable (csrc/host/, the host mirror, reads its three
+    CLOUDINI_AMD_* settings and the transcoder's timing print); the superseded kernel generations are not in the device code."""
     libdir = os.path.join(ROOT, "cloudini_amd", "lib")
     hip = open(os.path.join(libdir, "libcloudini_hip.so"), "rb").read()
     host = open(os.path.join(libdir, "libcloudini_amd.so"), "rb").read()
@@ -60,8 +60,16 @@ def test_shipped_libraries_read_only_the_production_environment_variables():
     assert [n for n in names(hip) if n.startswith(("CLDN_HIP_", "CLOUDINI_AMD_"))] == []
     assert [n for n in names(host) if n.startswith(("CLDN_", "CLOUDINI_AMD_"))] == [
         "CLDN_HOST_TIMING", "CLOUDINI_AMD_DEVICE_LZ4", "CLOUDINI_AMD_PIPELINE", "CLOUDINI_AMD_STAGE2_THREADS"]
-    for dead in (b"k_compact", b"k_chunk_offsets", b"10k_lz4_emitE", b"15k_decode_pointsI"):
+    for dead in (b"k_compact", b"k_chunk_offsets", b"10k_lz4_emitE", b"15k_decode_pointsI", b"13k_probe_modes",
+                 b"18k_sections_dv_cols", b"19k_section_palette32ItLi1024EE"):
         assert dead not in hip, dead
+    csrc = os.path.join(ROOT, "cloudini_amd", "csrc")
+    sources = [f for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip"))]
+    assert len(sources) >= 15
+    for f in sources:
+        text = open(os.path.join(csrc, f)).read()
+        for word in ("dev_env", "CLDN_DEV", "getenv"):
+            assert word not in text, (f, word)
 
 
 @pytest.mark.parametrize("seed", cases.VERY_WIDE_SEEDS[::5])

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Device-resident decode of n x 1 M-point XYZI clouds (and 130 k-point Velodyne clouds): ms per call; run with
-CLDN_HIP_NO_SPLIT_DECODE=1 / CLDN_HIP_SPLIT_PARTS=n to compare launch shapes."""
+"""Device-resident decode of n x 1 M-point XYZI clouds (and 130 k-point Velodyne clouds): ms per call."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

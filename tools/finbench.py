@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""C2 encode step (32 x 1 M XYZI, framed) with per-kernel device times, no checks: for A/B runs of switches whose output is
-deliberately wrong (CLDN_HIP_FINISH_ABLATE) or already covered by the tests (CLDN_HIP_FINISH_COPY)."""
+"""C2 encode step (32 x 1 M XYZI, framed) with per-kernel device times, no checks (FINBENCH_CLOUDS: clouds per call)."""
 import sys, os, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,7 +33,6 @@ for blk in range(5):
     ts.append((time.perf_counter() - t0) / STEPS)
     ks += [codec.kernel_ms(s) for s in range(STEPS)]
 med = lambda k: float(np.median([x[k] for x in ks]))
-tag = " ".join(f"{k}={v}" for k, v in os.environ.items() if k.startswith("CLDN_HIP_"))
-print(f"[{tag}]".ljust(40), f"step {np.median(ts) * 1e3:.4f} ms (min {min(ts) * 1e3:.4f}); regular {med('regular'):.4f} sections {med('sections'):.4f} "
+print(f"[{N_CLOUDS} clouds]".ljust(14), f"step {np.median(ts) * 1e3:.4f} ms (min {min(ts) * 1e3:.4f}); regular {med('regular'):.4f} sections {med('sections'):.4f} "
       f"finish {med('compact'):.4f} all {med('total'):.4f}", flush=True)
 codec.close()
