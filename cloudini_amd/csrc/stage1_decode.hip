@@ -27,6 +27,27 @@ namespace cldn {
 namespace {
 int hip_fail(hipError_t e, const char* what) { return launch_fail(e, what); }
 
+// k_decode_points_w, one entry per (NOPS, NF, SM) the launcher picks -- NOPS float lanes, NF Palette sections folded into the
+// point pass (8: the integer columns of 3..8 channels), SM store mode (stage1_decode_wave.h) -- with the kernels of the
+// chained launch (pass[0]) and of the two SPLIT passes around `carry` (pass[1], pass[2]). lds: every pass's dynamic LDS
+using PointsKernel = void (*)(DevPlan, const uint8_t*, const DecChunk*, uint8_t*, uint32_t*, uint8_t*, uint32_t, uint32_t*,
+                              const uint8_t*, const uint8_t*, const uint32_t*, const uint8_t*, uint32_t, DecColumns, WpSplit);
+struct PointsKernels {
+  uint32_t nops, nf, sm, lds;
+  PointsKernel pass[3];
+  void (*carry)(const uint8_t*, const DecChunk*, WpSplit);
+};
+template <int NOPS, int NF, int SM>
+constexpr PointsKernels points_kernels() {
+  return {NOPS, NF, SM, WpLds<NOPS, NF, 16>::kTotal,
+          {k_decode_points_w<NOPS, NF, 16, 8, SM, 0>, k_decode_points_w<NOPS, NF, 16, 8, SM, 1>, k_decode_points_w<NOPS, NF, 16, 8, SM, 2>},
+          k_wp_carry<NOPS>};
+}
+const PointsKernels kPointsKernels[] = {
+    points_kernels<3, 0, 1>(), points_kernels<3, 1, 1>(), points_kernels<3, 1, 2>(), points_kernels<3, 0, 0>(),
+    points_kernels<3, 1, 0>(), points_kernels<3, 2, 0>(), points_kernels<3, 8, 0>(), points_kernels<4, 0, 0>(),
+    points_kernels<4, 1, 0>(), points_kernels<4, 2, 0>(), points_kernels<4, 8, 0>()};
+
 // the plan the stream kernel decodes DeltaVarint SECTIONS with: op a = the integer field a as a stream of its own, stored
 // into the points
 DevPlan sections_plan(const DevPlan& P) {
@@ -75,27 +96,20 @@ int launch_section_columns(const DecodeLaunch& L, const DevPlan& P, const DecCol
 
 int stage1_configure_decode() {
   hipError_t e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_varint<4, false>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)Dv2Lds<4, false, 16>::kTotal);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_decode_varint<4>)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_varint<8, true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)Dv2Lds<8, true, 8>::kTotal);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_decode_varint<8>)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_tail), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)std::max<uint32_t>(std::max<uint32_t>((uint32_t)Dv2Lds<4, false, 16>::kTotal, kSmallSecLds), (uint32_t)DecSecLds::kTotal));
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_decode_tail)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_sections),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)DecSecLds::kTotal);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_decode_sections)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_sections_cols),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)DecSecLds::kTotal);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_decode_sections_cols)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_stream_w<12, 1>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SwLds<12, 1>::kTotal);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_decode_stream_w form)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_stream_w<12, 2>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SwLds<12, 2>::kTotal);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_decode_stream_w gorilla)");
+  for (const PointsKernels& k : kPointsKernels)
+    for (PointsKernel pass : k.pass)
+      if ((e = allow_lds(pass, k.lds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_decode_points_w)");
+  if ((e = allow_lds(&k_section_dv_w, DvwLds::kTotal)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_section_dv_w)");
+  if ((e = allow_lds(&k_decode_tail, std::max<uint32_t>(std::max<uint32_t>((uint32_t)Dv2Lds<4, false, 16>::kTotal, kSmallSecLds),
+                                                        (uint32_t)DecSecLds::kTotal))) != hipSuccess)
+    return hip_fail(e, "hipFuncSetAttribute(k_decode_tail)");
+  if ((e = allow_lds(&k_decode_sections, DecSecLds::kTotal)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_decode_sections)");
+  if ((e = allow_lds(&k_decode_sections_cols, DecSecLds::kTotal)) != hipSuccess)
+    return hip_fail(e, "hipFuncSetAttribute(k_decode_sections_cols)");
+  if ((e = allow_lds(&k_decode_stream_w<12, 1>, SwLds<12, 1>::kTotal)) != hipSuccess)
+    return hip_fail(e, "hipFuncSetAttribute(k_decode_stream_w form)");
+  if ((e = allow_lds(&k_decode_stream_w<12, 2>, SwLds<12, 2>::kTotal)) != hipSuccess)
+    return hip_fail(e, "hipFuncSetAttribute(k_decode_stream_w gorilla)");
   return CLDN_HIP_OK;
 }
 
@@ -230,24 +244,6 @@ int stage1_launch_decode(const DecodeLaunch& L) {
       const uint8_t* c1 = cols ? L.cols[1] : nullptr;
       const uint8_t* sc = (cols || many) ? L.sec_cols : nullptr;
       const uint32_t fill_zero = L.fill_zero ? 1u : 0u;
-#define LAUNCH_POINTS_W(NOPS_, NF_, SM_)                                                                               \
-  hipLaunchKernelGGL((k_decode_points_w<NOPS_, NF_, 16, 8, SM_>), dim3(L.n_chunks), dim3(16 * 64), (WpLds<NOPS_, NF_, 16>::kTotal), \
-                     L.stream, P, L.streams, reinterpret_cast<const DecChunk*>(L.chunks), L.out, L.reg_end, L.sec_done,   \
-                     L.uses_v5, L.status, c0, c1, L.reg_end_pre, sc, fill_zero, dcols, WpSplit{})
-// SPLIT launches (small batches): counts, PASS 1, carries, PASS 2
-#define LAUNCH_POINTS_SPLIT(NOPS_, NF_, SM_)                                                                              \
-  {                                                                                                                      \
-    hipLaunchKernelGGL(k_wp_counts, dim3(L.n_chunks), dim3(1024), 0, L.stream, L.streams, reinterpret_cast<const DecChunk*>(L.chunks), \
-                       wsp, (uint32_t)(NOPS_ + 1));                                                                      \
-    hipLaunchKernelGGL((k_decode_points_w<NOPS_, NF_, 16, 8, SM_, 1>), dim3(L.n_chunks, split_parts), dim3(16 * 64),      \
-                       (WpLds<NOPS_, NF_, 16>::kTotal), L.stream, P, L.streams, reinterpret_cast<const DecChunk*>(L.chunks), \
-                       L.out, L.reg_end, L.sec_done, L.uses_v5, L.status, c0, c1, L.reg_end_pre, sc, fill_zero, dcols, wsp); \
-    hipLaunchKernelGGL(k_wp_carry<NOPS_>, dim3(L.n_chunks), dim3(64), 0, L.stream, L.streams,                            \
-                       reinterpret_cast<const DecChunk*>(L.chunks), wsp);                                                \
-    hipLaunchKernelGGL((k_decode_points_w<NOPS_, NF_, 16, 8, SM_, 2>), dim3(L.n_chunks, split_parts), dim3(16 * 64),      \
-                       (WpLds<NOPS_, NF_, 16>::kTotal), L.stream, P, L.streams, reinterpret_cast<const DecChunk*>(L.chunks), \
-                       L.out, L.reg_end, L.sec_done, L.uses_v5, L.status, c0, c1, L.reg_end_pre, sc, fill_zero, dcols, wsp); \
-  }
       // store-mode instantiations of the two headline layouts (XYZ, XYZ + one 16-bit field): the layout facts the kernel
       // otherwise keeps as uniform flags are checked here
       int sm = 0;
@@ -277,40 +273,25 @@ int stage1_launch_decode(const DecodeLaunch& L) {
         w += (size_t)L.n_chunks * L.wp_maxp * 20u;
         wsp.carry = (int32_t*)w;
       }
+      const uint32_t nfk = nf <= 2u ? nf : 8u;
+      const PointsKernels* pk = nullptr;
+      for (const PointsKernels& k : kPointsKernels)
+        if (k.nops == P.n_ops && k.nf == nfk && k.sm == (uint32_t)sm) pk = &k;
+      if (!pk) return hip_fail(hipErrorInvalidValue, "k_decode_points_w (no variant)");
+      const DecChunk* chunks = reinterpret_cast<const DecChunk*>(L.chunks);
+      auto launch_points = [&](PointsKernel kernel, dim3 grid, const WpSplit& sp) {
+        hipLaunchKernelGGL(kernel, grid, dim3(16 * 64), pk->lds, L.stream, P, L.streams, chunks, L.out, L.reg_end, L.sec_done,
+                           L.uses_v5, L.status, c0, c1, L.reg_end_pre, sc, fill_zero, dcols, sp);
+      };
       ev_before();
-      if (split_parts > 1u && P.n_ops == 3u && sm == 1) {
-        if (nf == 0u) LAUNCH_POINTS_SPLIT(3, 0, 1)
-        else LAUNCH_POINTS_SPLIT(3, 1, 1)
-      } else if (split_parts > 1u && P.n_ops == 3u && sm == 2) {
-        LAUNCH_POINTS_SPLIT(3, 1, 2)
-      } else if (split_parts > 1u && P.n_ops == 3u && sm == 0) {
-        if (nf == 0u) LAUNCH_POINTS_SPLIT(3, 0, 0)
-        else if (nf == 1u) LAUNCH_POINTS_SPLIT(3, 1, 0)
-        else if (nf == 2u) LAUNCH_POINTS_SPLIT(3, 2, 0)
-        else LAUNCH_POINTS_SPLIT(3, 8, 0)
-      } else if (split_parts > 1u && P.n_ops == 4u && sm == 0) {
-        if (nf == 0u) LAUNCH_POINTS_SPLIT(4, 0, 0)
-        else if (nf == 1u) LAUNCH_POINTS_SPLIT(4, 1, 0)
-        else if (nf == 2u) LAUNCH_POINTS_SPLIT(4, 2, 0)
-        else LAUNCH_POINTS_SPLIT(4, 8, 0)
-      } else if (P.n_ops == 3u && sm == 1) {
-        if (nf == 0u) LAUNCH_POINTS_W(3, 0, 1);
-        else LAUNCH_POINTS_W(3, 1, 1);
-      } else if (P.n_ops == 3u && sm == 2) {
-        LAUNCH_POINTS_W(3, 1, 2);
-      } else if (P.n_ops == 3u) {
-        if (nf == 0u) LAUNCH_POINTS_W(3, 0, 0);
-        else if (nf == 1u) LAUNCH_POINTS_W(3, 1, 0);
-        else if (nf == 2u) LAUNCH_POINTS_W(3, 2, 0);
-        else LAUNCH_POINTS_W(3, 8, 0);
+      if (split_parts > 1u) {  // SPLIT launches (small batches): counts, PASS 1, carries, PASS 2
+        hipLaunchKernelGGL(k_wp_counts, dim3(L.n_chunks), dim3(1024), 0, L.stream, L.streams, chunks, wsp, pk->nops + 1u);
+        launch_points(pk->pass[1], dim3(L.n_chunks, split_parts), wsp);
+        hipLaunchKernelGGL(pk->carry, dim3(L.n_chunks), dim3(64), 0, L.stream, L.streams, chunks, wsp);
+        launch_points(pk->pass[2], dim3(L.n_chunks, split_parts), wsp);
       } else {
-        if (nf == 0u) LAUNCH_POINTS_W(4, 0, 0);
-        else if (nf == 1u) LAUNCH_POINTS_W(4, 1, 0);
-        else if (nf == 2u) LAUNCH_POINTS_W(4, 2, 0);
-        else LAUNCH_POINTS_W(4, 8, 0);
+        launch_points(pk->pass[0], dim3(L.n_chunks), WpSplit{});
       }
-#undef LAUNCH_POINTS_SPLIT
-#undef LAUNCH_POINTS_W
       ev_after();
       if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_decode_points");
     }

@@ -208,7 +208,7 @@ struct FusedArgs {
   uint32_t* status;
 };
 
-// UNAL / L3 / LOADW as in k_encode_floatn.
+// UNAL / L3 / LOADW: see kFusedKernels (stage1_kernels.hip), the layouts the kernel is instantiated for.
 //
 // Memory-level parallelism is explicit: the point loads of ALL rows of the piece are issued before the first row is
 // touched, from straight-line code without a branch around any load (out-of-range lanes load a clamped address), so
@@ -380,7 +380,10 @@ __device__ __forceinline__ void fused_body(const DevPlan& plan, const FusedArgs&
       const int32_t idx = (int32_t)(r * kRowPts + lane) - 1;
       const bool emits = (lane > 0u) && (lane < n + 1u - r * kRowPts);  // idx < n, as one compare against a uniform limit
 
-      // tokens of the row (common case in the float domain, see k_encode_floatn)
+      // tokens of the row. Common case in the float domain: r = rndne(v * m) is an integer-valued float; with |r| < 2^21 on
+      // both sides, r - r_prev, 2d + 0.5 and |.| + 0.5 are all exact, and zigzag(d) + 1 == |2d + 0.5| + 0.5. Anything else
+      // (NaN, Inf, |r| >= 2^21 ticks) marks the row rare. nd = r_prev - r with the DPP value as the first operand (a plain
+      // v_sub_f32_dpp: hipcc's reversed v_subrev_*_dpp returned the operands swapped on gfx950); |2d + 0.5| == |(-2) nd + 0.5|
       uint32_t tok[LANES], lens = 0u, total = 0u;
       bool rare = false;
 #pragma unroll

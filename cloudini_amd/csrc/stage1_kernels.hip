@@ -396,16 +396,7 @@ __global__ __launch_bounds__(T) void k_encode_regular(const DevPlan plan, const 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// k_encode_floatn: the hot kernel. Regular stream == one FieldEncoderFloatN_Lossy (3 or 4 fused float32 lanes at
-// consecutive offsets; src/field_encoder.cpp:42-91), 4-byte aligned layout. Differences to the generic kernel:
-//   * no LDS staging of the input: every lane loads its own point straight from global memory (the wave reads
-//     64 consecutive points = one contiguous, coalesced span);
-//   * each wave covers 63 new points plus, in lane 0, the point before them: the delta reference of lane l is
-//     lane l-1's quantised value, fetched with one DPP wave shift -- no second load, no second quantisation, no
-//     cross-wave exchange. Lane 0 never emits;
-//   * PPT rows of 63*NW points per barrier pair; the cross-wave part of the scan is a single wave scan over the
-//     PPT*NW row/wave totals;
-//   * tokens are built once (<= 5 bytes each) and OR-ed into the byte ring, 1-2 LDS atomics per token.
+// FloatN token helpers of the piece kernel (stage1_fused.h) and the section kernels (stage1_sections.h)
 // ------------------------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ uint32_t dpp_wave_shr1(uint32_t x) {
@@ -447,16 +438,6 @@ __device__ __forceinline__ void ring_put5(uint32_t* ring, uint32_t off, uint32_t
   }
 }
 
-// token of <= 4 bytes at byte `off` (whole tile fits the ring): two dword ORs, the second one predicated
-template <uint32_t RING_BYTES>
-__device__ __forceinline__ void ring_put4(uint32_t* ring, uint32_t off, uint32_t t) {
-  const uint64_t v = ((uint64_t)t) << ((off << 3) & 31u);
-  const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-  uint8_t* rb = reinterpret_cast<uint8_t*>(ring);
-  atomicOr(reinterpret_cast<uint32_t*>(rb + (off & (RING_BYTES - 4u))), lo);
-  if (hi) atomicOr(reinterpret_cast<uint32_t*>(rb + ((off + 4u) & (RING_BYTES - 4u))), hi);
-}
-
 // u < 2^28 -> its four 7-bit groups in the low 7 bits of the four bytes, continuation bits of a token of `l`
 // bytes set (two bit-field inserts per halving step; the stray bits they leave sit on the continuation positions)
 __device__ __forceinline__ uint32_t token4(uint32_t u, uint32_t l) {
@@ -476,23 +457,6 @@ __device__ __forceinline__ void ring_flush_n(uint32_t* ring, uint8_t* dst, uint3
   }
 }
 
-constexpr uint32_t kStagedCols = 2;  // adaptive fields (2 or 4 bytes wide) whose SoA copy is staged through LDS
-
-// adaptive field `a` lies completely inside the `loadw` dwords loaded behind the first float lane. The host picks
-// loadw so that this holds for every field (floatn_loadw) -- except for the padded-fourth-lane layout, whose window
-// is fixed at 8 dwords: CHECK turns the test on for that instantiation only (it costs registers in the others).
-template <bool CHECK>
-__device__ __forceinline__ bool col_in_regs(const DevPlan& plan, uint32_t a, int loadw) {
-  if (!CHECK) return true;
-  const uint32_t off = plan.adaptive[a].offset, off0 = plan.ops[0].offset;
-  return off >= off0 && off - off0 + plan.adaptive[a].bpv <= (uint32_t)loadw * 4u;
-}
-// ... and its SoA copy goes through the LDS staging area
-template <bool CHECK>
-__device__ __forceinline__ bool col_staged(const DevPlan& plan, uint32_t a, int loadw, int lanes) {
-  return loadw > lanes && a < kStagedCols && plan.adaptive[a].bpv <= 4u && col_in_regs<CHECK>(plan, a, loadw);
-}
-
 // bytes [rel, rel + 8) of the dwords loaded for one point (rel + field size <= 4 * LOADW, guaranteed by the host)
 // (three dwords: an 8-byte field at an offset that is no multiple of 4 spans them. Rounds 2-5 took two and shifted -- the top
 // 1..3 bytes of such a field were lost; found by round 6's fuzz range 900000+, seed 923696: a UINT64 field at offset 25)
@@ -508,343 +472,6 @@ __device__ __forceinline__ uint64_t field_from_regs(const FloatVec<LOADW>& pt, u
   }
   const uint32_t mis = rel & 3u;
   return (((uint64_t)__builtin_amdgcn_alignbyte(d2, d1, mis)) << 32) | __builtin_amdgcn_alignbyte(d1, d0, mis);
-}
-
-// UNAL: points are not 4-byte aligned (odd point_step / offset / base, e.g. packed 18-byte points): every lane loads
-// LOADW + 1 dwords from the aligned address below its point and realigns them with v_alignbyte; the dwords may reach
-// into the next point, so only the last points of the whole batch need the guarded path (points_end).
-// L3: dword (behind the first lane) of the fourth lane -- 3 for x y z w back to back, 4 for the PCL / Ouster layout
-// "x y z <pad> intensity" (the fused encoder takes any four offsets, src/field_encoder.cpp:24-40).
-template <int T, int LANES, int PPT, uint32_t RING_BYTES, int LOADW, bool PREFETCH = true, bool UNAL = false, int L3 = 3>
-__global__ __launch_bounds__(T) void k_encode_floatn(const DevPlan plan, const uint8_t* __restrict__ points,
-                                                     const uint8_t* __restrict__ points_end,
-                                                     const ChunkDesc* __restrict__ chunks,
-                                                     uint8_t* __restrict__ slots, uint64_t slot_stride,
-                                                     Seg* __restrict__ segs, uint32_t segs_per_chunk,
-                                                     const ColumnPtrs cols, uint32_t subs, uint32_t sub_points,
-                                                     uint32_t sub_stride) {
-  constexpr int NW = T / 64;
-  constexpr uint32_t ROW = NW * 63u;
-  constexpr uint32_t TILE = ROW * PPT;
-  static_assert(NW * PPT <= 64, "row/wave totals must fit one wave scan");
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint32_t* ring = reinterpret_cast<uint32_t*>(smem);
-  uint32_t* wtot = reinterpret_cast<uint32_t*>(smem + RING_BYTES);
-  uint8_t* colstage = smem + RING_BYTES + 256u;  // [kStagedCols][TILE * 4] SoA staging of the adaptive fields
-
-  const uint32_t tid = threadIdx.x;
-  const uint32_t lane = tid & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t chunk_id = blockIdx.x / subs;
-  const uint32_t sub_id = blockIdx.x - chunk_id * subs;
-  const ChunkDesc cd = chunks[chunk_id];
-  const uint32_t step = plan.point_step;
-  const uint32_t sub_first = sub_id * sub_points;  // first point of this workgroup's sub-chunk inside the chunk
-  // points of this sub-chunk (saturating subtraction, see k_encode_regular)
-  const int32_t n = (int32_t)min(sub_points, cd.n_points - min(cd.n_points, sub_first));
-  const int32_t idx_lo = sub_first > 0u ? -1 : 0;  // the point before the sub-chunk is a valid delta reference
-  const size_t first_point = (size_t)cd.first_point + sub_first;
-  const uint8_t* gbase = points + first_point * step + plan.ops[0].offset;
-  uint8_t* slot = slots + (size_t)chunk_id * slot_stride + (size_t)sub_id * sub_stride;
-  if (n == 0) {  // sub-chunk beyond the end of a short chunk: nothing to read, empty segment
-    if (tid == 0) {
-      Seg s;
-      s.off = sub_id * sub_stride;
-      s.size = 0u;
-      segs[(size_t)chunk_id * segs_per_chunk + sub_id] = s;
-    }
-    return;
-  }
-  float mult[LANES];
-#pragma unroll
-  for (int k = 0; k < LANES; ++k) mult[k] = plan.ops[k].mult_f;
-
-  for (uint32_t i = tid; i < RING_BYTES / 16u; i += T) reinterpret_cast<uint4*>(ring)[i] = make_uint4(0u, 0u, 0u, 0u);
-
-  // LOADW >= LANES dwords are loaded per point (one global_load_dwordx3/x4/...): the extra dwords carry the
-  // adaptive-int fields that live right behind the floats, so their AoS->SoA split needs no second load.
-  FloatVec<LOADW> cur[PPT], nxt[PPT];
-  auto load_tile = [&](uint32_t base, FloatVec<LOADW>(&dst)[PPT]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-      const int32_t idx = (int32_t)(base + (uint32_t)(j * NW + (int)wave) * 63u + lane) - 1;
-      FloatVec<LOADW> z;
-#pragma unroll
-      for (int k = 0; k < LOADW; ++k) z.v[k] = 0.0f;
-      if (idx >= idx_lo && idx < n) {
-        const uint8_t* a = gbase + (ptrdiff_t)idx * (ptrdiff_t)step;
-        if (!UNAL) {
-          z = *reinterpret_cast<const FloatVec<LOADW>*>(a);
-        } else {
-          const uint32_t mis = (uint32_t)((uintptr_t)a & 3u);
-          const uint32_t* q = reinterpret_cast<const uint32_t*>(a - mis);
-          uint32_t d[LOADW + 1];
-          if (reinterpret_cast<const uint8_t*>(q + LOADW + 1) <= points_end) {
-#pragma unroll
-            for (int k = 0; k <= LOADW; ++k) d[k] = q[k];
-          } else {  // last points of the batch: a dword is read only if it holds at least one byte of the buffer
-#pragma unroll
-            for (int k = 0; k <= LOADW; ++k) d[k] = (reinterpret_cast<const uint8_t*>(q + k) < points_end) ? q[k] : 0u;
-          }
-#pragma unroll
-          for (int k = 0; k < LOADW; ++k) z.v[k] = __uint_as_float(__builtin_amdgcn_alignbyte(d[k + 1], d[k], mis));
-        }
-      }
-      dst[j] = z;
-    }
-  };
-  load_tile(0u, cur);
-  __syncthreads();
-
-  // Two copies of the tile loop. Clouds either have NaNs all over (organised depth images) or none (lidar), so the
-  // first tile decides for the sub-chunk: with NaNs around, rows that fail the short-path test get a second try that
-  // treats NaN lanes as marker bytes; without, that code is not even in the loop (it cost the NaN-free loop 7 %).
-  uint32_t R = 0u, F = 0u;
-  auto run_tiles = [&](auto nan_tier_tag) __attribute__((always_inline)) {
-  constexpr bool NAN_TIER = decltype(nan_tier_tag)::value;
-  for (uint32_t base = 0; base < (uint32_t)n; base += TILE) {
-    const bool last = (base + TILE >= (uint32_t)n);
-    if (PREFETCH && !last) load_tile(base + TILE, nxt);  // double buffer: in flight while this tile is encoded
-
-    // Tokens of the row's points. Common case (no NaN in the wave row, every token <= 4 bytes, i.e. |delta| <
-    // 2^27 ticks): one dword per token, built with the short formulas and kept until the scan is done. Rows with a
-    // NaN or a 5-byte token (wave-uniform test) use the general formulas and are rebuilt at emission time.
-    uint32_t tok[PPT][LANES], lens[PPT], plen[PPT], incl[PPT];
-    uint32_t rare_rows = 0u;
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-      const int32_t idx = (int32_t)(base + (uint32_t)(j * NW + (int)wave) * 63u + lane) - 1;
-      const bool emits = (lane > 0u) && (idx < n);
-      lens[j] = 0u;
-      uint32_t total = 0u;
-      bool rare = false;
-#pragma unroll
-      for (int k = 0; k < LANES; ++k) {
-        // Common case in the float domain: r = rndne(v * m) is an integer-valued float; with |r| < 2^21 on both
-        // sides, r - r_prev, 2d + 0.5 and |.| + 0.5 are all exact, and zigzag(d) + 1 == |2d + 0.5| + 0.5. Anything
-        // else (NaN, Inf, |r| >= 2^21 ticks) marks the row rare. The neighbour's r travels negated so that the DPP
-        // move folds into a commutative add (hipcc's v_subrev_*_dpp returned the operands swapped on gfx950).
-        const float r = rintf(__fmul_rn(cur[j].v[(LANES == 4 && k == 3) ? L3 : k], mult[k]));
-        rare |= !(fabsf(r) < 2097152.0f);
-        // nd = r_prev - r with the DPP value as the first operand (a plain v_sub_f32_dpp; the reversed form is the one
-        // that misbehaved); |2d + 0.5| == |(-2) nd + 0.5|
-        const float nd = __fsub_rn(__uint_as_float(dpp_wave_shr1(__float_as_uint(r))), r);
-        const float uf = fabsf(__fmaf_rn(nd, -2.0f, 0.5f)) + 0.5f;
-        const uint32_t u = (uint32_t)uf;
-        const uint32_t l = groups7((uint32_t)__builtin_amdgcn_frexp_expf(uf));  // frexp exponent == bit length of u
-        tok[j][k] = token4(u, l);
-        lens[j] |= l << (8 * k);
-        total += l;
-      }
-      if (__builtin_expect(__ballot(rare) != 0ull, 0)) {
-        // Second tier: the row only has NaNs (organised clouds with invalid pixels) next to in-range values. A NaN
-        // is the marker byte and hands its neighbour a reference of 0; everything else stays in the float domain
-        // and the tokens still fit one dword, so the row keeps the short emission path.
-        bool hard = !NAN_TIER;
-        uint32_t total2 = 0u, lens2 = 0u;
-#pragma unroll
-        for (int k = 0; k < LANES; ++k) {
-          if (!NAN_TIER) break;
-          const float v = cur[j].v[(LANES == 4 && k == 3) ? L3 : k];
-          const bool isn = is_nan_f32(v);
-          const float r = isn ? 0.0f : rintf(__fmul_rn(v, mult[k]));
-          hard |= !(fabsf(r) < 2097152.0f);
-          const float nrp = __uint_as_float(dpp_wave_shr1(__float_as_uint(r) ^ 0x80000000u));
-          const float uf = fabsf(__fmaf_rn(__fadd_rn(r, nrp), 2.0f, 0.5f)) + 0.5f;
-          const uint32_t l = isn ? 1u : groups7((uint32_t)__builtin_amdgcn_frexp_expf(uf));
-          tok[j][k] = isn ? 0u : token4((uint32_t)uf, l);
-          lens2 |= l << (8 * k);
-          total2 += l;
-        }
-        if (NAN_TIER && __ballot(hard) == 0ull) {
-          lens[j] = lens2;
-          total = total2;
-        } else {  // Inf, overflow or a 5-byte token somewhere in the row: general integer formulas
-          rare_rows |= 1u << j;
-          total = 0u;
-#pragma unroll
-          for (int k = 0; k < LANES; ++k) {
-            const float v = cur[j].v[(LANES == 4 && k == 3) ? L3 : k];
-            const bool isn = is_nan_f32(v);
-            const int32_t q = quant_rne_i32(v, mult[k]);
-            const uint32_t nqp = dpp_wave_shr1(isn ? 0u : (0u - (uint32_t)q));  // a NaN resets that lane's reference
-            uint32_t a0, a1, l;
-            floatn_token(isn, (int32_t)((uint32_t)q + nqp), a0, a1, l);
-            total += l;
-          }
-        }
-      }
-      plen[j] = emits ? total : 0u;
-    }
-    if (PPT == 2) {  // both rows' byte counts (< 2^16 each) ride one wave scan
-      const uint32_t pincl = wave_inclusive_scan(plen[0] | (plen[PPT - 1] << 16));
-      incl[0] = pincl & 0xffffu;
-      incl[PPT - 1] = pincl >> 16;
-    } else {
-#pragma unroll
-      for (int j = 0; j < PPT; ++j) incl[j] = wave_inclusive_scan(plen[j]);
-    }
-    if (lane == 63u) {
-#pragma unroll
-      for (int j = 0; j < PPT; ++j) wtot[j * NW + (int)wave] = incl[j];
-    }
-    __syncthreads();
-    const uint32_t wt = (lane < (uint32_t)(NW * PPT)) ? wtot[lane] : 0u;
-    const uint32_t wincl = wave_inclusive_scan(wt);
-    const uint32_t tile_total = (uint32_t)__builtin_amdgcn_readlane((int)wincl, NW * PPT - 1);
-    const uint32_t r_end = R + tile_total;
-    const uint32_t target = last ? ((r_end + 15u) & ~15u) : (r_end & ~15u);
-
-    if (plan.n_adaptive && LOADW > LANES) {
-      for (uint32_t a = 0; a < plan.n_adaptive; ++a) {
-        if (!col_staged<L3 == 4>(plan, a, LOADW, LANES)) continue;
-        const uint32_t bpv = plan.adaptive[a].bpv;
-        uint8_t* st = colstage + (size_t)a * (TILE * 4u);
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-          const int32_t idx = (int32_t)(base + (uint32_t)(j * NW + (int)wave) * 63u + lane) - 1;
-          if (lane > 0u && idx < n) {
-            const uint32_t t = (uint32_t)idx - base;  // point index inside the tile
-            const uint32_t rel = plan.adaptive[a].offset - plan.ops[0].offset;
-            uint64_t raw;
-            if (LOADW == LANES + 1) raw = __float_as_uint(cur[j].v[LOADW - 1]) >> ((rel & 3u) * 8u);  // the one extra dword
-            else raw = field_from_regs<LOADW>(cur[j], rel);
-            if (bpv == 2u) reinterpret_cast<uint16_t*>(st)[t] = (uint16_t)raw;
-            else reinterpret_cast<uint32_t*>(st)[t] = (uint32_t)raw;
-          }
-        }
-      }
-    }
-
-    auto emit_all = [&](auto windowed, uint32_t win_lo_dw) __attribute__((always_inline)) {
-#pragma unroll
-      for (int j = 0; j < PPT; ++j) {
-        const int f = j * NW + (int)wave;
-        const uint32_t rowbase = (f == 0) ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)wincl, f - 1);
-        uint32_t off = R + rowbase + incl[j] - plen[j];
-        if (__builtin_expect((rare_rows & (1u << j)) != 0u, 0)) {  // wave-uniform: rebuild the general tokens (all lanes take part in the DPP)
-#pragma unroll
-          for (int k = 0; k < LANES; ++k) {
-            const float v = cur[j].v[(LANES == 4 && k == 3) ? L3 : k];
-            const bool isn = is_nan_f32(v);
-            const int32_t q = quant_rne_i32(v, mult[k]);
-            const uint32_t nqp = dpp_wave_shr1(isn ? 0u : (0u - (uint32_t)q));
-            uint32_t a0, a1, l;
-            floatn_token(isn, (int32_t)((uint32_t)q + nqp), a0, a1, l);
-            if (plen[j]) ring_put5<RING_BYTES, decltype(windowed)::value>(ring, off, a0, a1, l, win_lo_dw);
-            off += l;
-          }
-        } else if (plen[j]) {
-#pragma unroll
-          for (int k = 0; k < LANES; ++k) {
-            const uint32_t t = tok[j][k];
-            const uint32_t l = (lens[j] >> (8 * k)) & 0xffu;
-            if (decltype(windowed)::value) ring_put5<RING_BYTES, true>(ring, off, t, 0u, l, win_lo_dw);
-            else ring_put4<RING_BYTES>(ring, off, t);
-            off += l;
-          }
-        }
-      }
-    };
-
-    // AoS -> SoA split of the adaptive-int fields. Fields covered by the point load are taken from registers;
-    // 2/4-byte fields are staged in LDS (written after the scan barrier) and leave as 16-byte stores.
-    auto write_columns = [&]() __attribute__((always_inline)) {
-      if (plan.n_adaptive) {
-        const uint32_t tile_pts = min(TILE, (uint32_t)n - base);
-        for (uint32_t a = 0; a < plan.n_adaptive; ++a) {
-          const uint32_t bpv = plan.adaptive[a].bpv;
-          uint8_t* gcol = cols.p[a] + (first_point + base) * bpv;
-          const bool staged = col_staged<L3 == 4>(plan, a, LOADW, LANES) && (((uintptr_t)gcol & 15u) == 0u);
-          if (staged) {
-            const uint8_t* st = colstage + (size_t)a * (TILE * 4u);
-            const uint32_t bytes = tile_pts * bpv;
-            for (uint32_t u = tid; u < (bytes >> 4); u += T)
-              reinterpret_cast<uint4*>(gcol)[u] = reinterpret_cast<const uint4*>(st)[u];
-            const uint32_t tail0 = bytes & ~15u;
-            if (tid < (bytes & 15u)) gcol[tail0 + tid] = st[tail0 + tid];
-            continue;
-          }
-  #pragma unroll
-          for (int j = 0; j < PPT; ++j) {
-            const int32_t idx = (int32_t)(base + (uint32_t)(j * NW + (int)wave) * 63u + lane) - 1;
-            if (lane > 0u && idx < n) {
-              const size_t gi = first_point + (size_t)idx;
-              uint8_t* col = cols.p[a];
-              uint64_t raw;
-              if (LOADW > LANES && col_in_regs<L3 == 4>(plan, a, LOADW)) {
-                raw = field_from_regs<LOADW>(cur[j], plan.adaptive[a].offset - plan.ops[0].offset);
-              } else {
-                const uint8_t* fp = points + gi * step + plan.adaptive[a].offset;
-                raw = 0u;
-                if (((uintptr_t)fp & (bpv - 1u)) == 0u) {
-                  if (bpv == 2u) raw = *reinterpret_cast<const uint16_t*>(fp);
-                  else if (bpv == 4u) raw = *reinterpret_cast<const uint32_t*>(fp);
-                  else raw = *reinterpret_cast<const uint64_t*>(fp);
-                } else {
-                  for (uint32_t b = 0; b < bpv; ++b) raw |= ((uint64_t)fp[b]) << (8u * b);
-                }
-              }
-              if (bpv == 2u) reinterpret_cast<uint16_t*>(col)[gi] = (uint16_t)raw;
-              else if (bpv == 4u) reinterpret_cast<uint32_t*>(col)[gi] = (uint32_t)raw;
-              else reinterpret_cast<uint64_t*>(col)[gi] = raw;
-            }
-          }
-        }
-      }
-    };
-
-    // Without the double buffer the next tile's points are requested as soon as this tile's registers are dead:
-    // the loads fly during the ring flush and the next scan barrier.
-    if (__builtin_expect(r_end - F <= RING_BYTES, 1)) {
-      emit_all(std::false_type{}, 0u);
-      __syncthreads();
-      write_columns();
-      if (!PREFETCH && !last) load_tile(base + TILE, cur);
-      ring_flush_n<T, RING_BYTES>(ring, slot, F, target);
-      F = target;
-    } else {
-      for (;;) {
-        emit_all(std::true_type{}, F >> 2);
-        __syncthreads();
-        const uint32_t nf = min(F + RING_BYTES, target);
-        ring_flush_n<T, RING_BYTES>(ring, slot, F, nf);
-        const bool done = (F + RING_BYTES >= r_end);
-        F = nf;
-        if (done) break;
-        __syncthreads();
-      }
-      write_columns();
-      if (!PREFETCH && !last) load_tile(base + TILE, cur);
-    }
-    R = r_end;
-
-    if (PREFETCH && !last) {
-#pragma unroll
-      for (int j = 0; j < PPT; ++j) cur[j] = nxt[j];
-    }
-    // No barrier here: the next tile's wtot writes sit behind this tile's second barrier (every wave has read
-    // wtot by then) and its ring ORs sit behind its own first barrier (every wave has finished this flush).
-  }
-  };
-  if (LANES == 3) {  // the 4-lane instantiations would lose a wave of occupancy to the second copy
-    bool any_nan = false;
-#pragma unroll
-    for (int j = 0; j < PPT; ++j)
-#pragma unroll
-      for (int k = 0; k < LANES; ++k) any_nan |= is_nan_f32(cur[j].v[(LANES == 4 && k == 3) ? L3 : k]);
-    if (__syncthreads_or(any_nan ? 1 : 0)) run_tiles(std::true_type{});
-    else run_tiles(std::false_type{});
-  } else {
-    run_tiles(std::false_type{});
-  }
-
-  if (tid == 0) {
-    Seg s;
-    s.off = sub_id * sub_stride;
-    s.size = R;
-    segs[(size_t)chunk_id * segs_per_chunk + sub_id] = s;
-  }
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1705,21 +1332,78 @@ namespace {
 constexpr int kRegularThreads = 1024;
 inline uint32_t regular_lds(uint32_t step) { return 2u * regular_tile_lds(kRegularThreads, step) + kRingBytes + 128u; }
 constexpr uint32_t kRegularLdsMax = 2u * (((64u * kMaxPointStep + kMaxPointStep + 48u) + 15u) & ~15u) + kRingBytes + 128u;
-constexpr uint32_t kFloatnRing = 16384;  // >= one tile of 3-lane points at 5 bytes per token (1008 * 15 B); wider tiles use windows
-constexpr uint32_t kFloatnLds = kFloatnRing + 256u + kStagedCols * (4u * 63u * 2u) * 4u + 64u;  // ring, wtot, staged columns (TILE = 504)
 
-// FloatN fast path: the regular stream is exactly one fused 3/4-lane float encoder on a 4-byte aligned layout
-// lanes of the fused FloatN encoder the fast kernel can take (0 = none); *l3 = dword of the fourth lane
-// `tail` (may be NULL): index of ONE more regular op behind the lanes that the piece kernel can append to every point
-// (raw copy, scalar lossy float, Gorilla token), -1 if there is none. Callers that pass NULL get 0 for such plans.
-int floatn_lanes(const DevPlan& p, const uint8_t* points, int* l3, int* tail = nullptr) {
+// Kernel families with several instantiations keep them in one table each: an entry names the instantiation and the
+// dynamic LDS of its launches; the launchers pick an entry, stage1_configure_kernels hands every entry to allow_lds.
+
+// k_encode_regular, the generic op interpreter: [0] points of up to kWidePointStep bytes, [1] wider ones (tiles of 64
+// points). lds: the most a launch takes (regular_lds of the widest point)
+struct RegularKernel {
+  uint32_t lds;
+  decltype(&k_encode_regular<kRegularThreads, false>) kernel;
+};
+const RegularKernel kRegularKernels[] = {{regular_lds(kWidePointStep), k_encode_regular<kRegularThreads, false>},
+                                         {kRegularLdsMax, k_encode_regular<kRegularThreads, true>}};
+
+// k_encode_fused, the piece kernel (stage1_fused.h), one entry per layout it takes. LANES: fused float lanes; LOADW: dwords
+// loaded per point; UNAL: points that are not 4-byte aligned (odd point_step / offset / base, e.g. packed 18-byte points):
+// every lane loads LOADW + 1 dwords from the aligned address below its point and realigns them with v_alignbyte; L3: dword
+// (behind the first lane) of the fourth lane -- 3 for x y z w back to back, 4 for the PCL / Ouster layout
+// "x y z <pad> intensity" (the fused encoder takes any four offsets, src/field_encoder.cpp:24-40); TAIL: one more op behind
+// the lanes. lds: the four piece regions (a launch that also probes 32-bit fields raises it to the probe's hash table)
+struct FusedKernel {
+  int lanes, loadw;
+  bool unal;
+  int l3;
+  bool tail;
+  uint32_t lds;
+  void (*kernel)(DevPlan, FusedArgs);
+};
+template <int LANES, int LOADW, bool UNAL, int L3, bool TAIL = false>
+constexpr FusedKernel fused_kernel() {
+  const uint32_t lds = 16u + kFusedWaves * (TAIL ? fused_region_bytes_tail(LANES) : fused_region_bytes_small(LANES));
+  // instantiations without a TAIL op that prefetch at most 5 dwords per point: the 64-VGPR kernel (8 waves per SIMD)
+  if constexpr (!TAIL && LOADW <= 5) return {LANES, LOADW, UNAL, L3, TAIL, lds, k_encode_fused_w8<LANES, LOADW, UNAL, L3>};
+  else return {LANES, LOADW, UNAL, L3, TAIL, lds, k_encode_fused<LANES, LOADW, UNAL, L3, TAIL>};
+}
+const FusedKernel kFusedKernels[] = {
+    fused_kernel<3, 3, false, 3>(),       fused_kernel<3, 4, false, 3>(),       fused_kernel<3, 8, false, 3>(),
+    fused_kernel<4, 4, false, 3>(),       fused_kernel<4, 8, false, 3>(),       fused_kernel<4, 8, false, 4>(),
+    fused_kernel<3, 4, true, 3>(),        fused_kernel<3, 8, true, 3>(),        fused_kernel<4, 5, true, 3>(),
+    fused_kernel<4, 8, true, 3>(),        fused_kernel<3, 4, false, 3, true>(), fused_kernel<3, 8, false, 3, true>(),
+    fused_kernel<4, 8, false, 3, true>(), fused_kernel<4, 8, false, 4, true>(), fused_kernel<3, 4, true, 3, true>(),
+    fused_kernel<3, 8, true, 3, true>(),  fused_kernel<4, 8, true, 3, true>()};
+
+// k_finish (stage1_finish.h): `threads` per workgroup; bpv 0 (framing only), 2 or 4 (also the Palette section of one
+// 16- or 32-bit field, in the LDS of a Pal32)
+struct FinishKernel {
+  uint32_t threads, bpv, lds;
+  void (*kernel)(FinishArgs);
+};
+template <int T, int FUSE_BPV>
+constexpr FinishKernel finish_kernel() {
+  return {T, FUSE_BPV, FUSE_BPV == 0 ? 0u : (FUSE_BPV == 2 ? Pal32<uint16_t>::kLds : Pal32<uint32_t>::kLds), k_finish<T, FUSE_BPV>};
+}
+const FinishKernel kFinishKernels[] = {finish_kernel<256, 0>(), finish_kernel<512, 2>(), finish_kernel<512, 4>(),
+                                       finish_kernel<1024, 2>(), finish_kernel<1024, 4>()};
+const FinishKernel* finish_variant(uint32_t threads, uint32_t bpv) {
+  for (const FinishKernel& k : kFinishKernels)
+    if (k.threads == threads && k.bpv == bpv) return &k;
+  return nullptr;
+}
+
+// The piece kernel's layouts: the regular stream is one fused 3/4-lane float encoder, optionally followed by one more op.
+// Lanes of the fused FloatN encoder (0 = none); *l3 = dword of the fourth lane; *tail: index of ONE more regular op behind
+// the lanes that the piece kernel can append to every point (raw copy, scalar lossy float, Gorilla token), -1 if there is
+// none
+int floatn_lanes(const DevPlan& p, int* l3, int* tail) {
   *l3 = 3;
-  if (tail) *tail = -1;
+  *tail = -1;
   uint32_t lanes = 0;
   while (lanes < p.n_ops && lanes < 4u && p.ops[lanes].kind == OP_QF32) ++lanes;
   if (lanes != 3u && lanes != 4u) return 0;
   if (p.n_ops != lanes) {
-    if (!tail || p.n_ops != lanes + 1u) return 0;
+    if (p.n_ops != lanes + 1u) return 0;
     const uint32_t k = p.ops[lanes].kind;
     // (XOR fields only exist in lossless schemas, which have no FloatN lanes)
     if (k != OP_COPY && k != OP_LOSSY_F32 && k != OP_LOSSY_F64 && k != OP_GORILLA64) return 0;
@@ -1742,7 +1426,7 @@ bool floatn_unaligned(const DevPlan& p, const uint8_t* points) {
 
 // dwords to load per point so that every adaptive-int field (and the tail op's field) is covered by the point load
 // (0 = not possible)
-int floatn_loadw(const DevPlan& p, int lanes, bool unal, int l3, int tail = -1) {
+int floatn_loadw(const DevPlan& p, int lanes, bool unal, int l3, int tail) {
   const uint32_t off0 = p.ops[0].offset;
   // bytes behind off0 the tail needs; an unaligned 8-byte field is read from three dwords
   uint32_t tail_need = 0;
@@ -1780,66 +1464,31 @@ int hip_fail(hipError_t e, const char* what) { return launch_fail(e, what); }
 }  // namespace
 
 int stage1_configure_kernels() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode_regular<kRegularThreads, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)regular_lds(kWidePointStep));
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_regular)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode_regular<kRegularThreads, true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRegularLdsMax);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_regular wide)");
-  const void* fk[] = {reinterpret_cast<const void*>(&k_encode_floatn<256, 3, 2, kFloatnRing, 3, false>),
-                      reinterpret_cast<const void*>(&k_encode_floatn<256, 3, 2, kFloatnRing, 4, false>),
-                      reinterpret_cast<const void*>(&k_encode_floatn<256, 3, 2, kFloatnRing, 8, false>),
-                      reinterpret_cast<const void*>(&k_encode_floatn<256, 4, 2, kFloatnRing, 4, false>),
-                      reinterpret_cast<const void*>(&k_encode_floatn<256, 4, 2, kFloatnRing, 8, false>),
-                      reinterpret_cast<const void*>(&k_encode_floatn<256, 3, 2, kFloatnRing, 4, false, true>),
-                      reinterpret_cast<const void*>(&k_encode_floatn<256, 3, 2, kFloatnRing, 8, false, true>),
-                      reinterpret_cast<const void*>(&k_encode_floatn<256, 4, 2, kFloatnRing, 5, false, true>),
-                      reinterpret_cast<const void*>(&k_encode_floatn<256, 4, 2, kFloatnRing, 8, false, true>),
-                      reinterpret_cast<const void*>(&k_encode_floatn<256, 4, 2, kFloatnRing, 8, false, false, 4>)};
-  for (const void* f : fk) {
-    e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFloatnLds);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_floatn)");
-  }
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode_sections),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSecLdsTotal);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_sections)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_probe_fast), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kProbeLds);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_probe_fast)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wide_probe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kProbeLds);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_wide_probe)");
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wide_encode), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSecLdsTotal);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_wide_encode)");
-  const void* pk[] = {reinterpret_cast<const void*>(&k_section_palette<uint16_t>),
-                      reinterpret_cast<const void*>(&k_section_palette<uint32_t>),
-                      reinterpret_cast<const void*>(&k_section_palette<uint64_t>)};
-  for (const void* f : pk) {
-    e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kS2PalLds);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_section_palette)");
-  }
-  if (int rc = stage1_configure_decode()) return rc;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_section_fast), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kD32Lds);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_section_fast)");
-  const void* pk32[] = {reinterpret_cast<const void*>(&k_section_palette32<uint16_t, 512>),
-                        reinterpret_cast<const void*>(&k_section_palette32<uint32_t, 512>)};
-  for (const void* f : pk32) {
-    e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Pal32<uint32_t>::kLds);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_section_palette32)");
-  }
-  return CLDN_HIP_OK;
+  hipError_t e;
+  for (const RegularKernel& k : kRegularKernels)
+    if ((e = allow_lds(k.kernel, k.lds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_regular)");
+  for (const FusedKernel& k : kFusedKernels)
+    if ((e = allow_lds(k.kernel, k.lds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_fused)");
+  for (const FinishKernel& k : kFinishKernels)
+    if ((e = allow_lds(k.kernel, k.lds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_finish)");
+  if ((e = allow_lds(&k_encode_sections, kSecLdsTotal)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_sections)");
+  if ((e = allow_lds(&k_probe_fast, kProbeLds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_probe_fast)");
+  if ((e = allow_lds(&k_wide_probe, kProbeLds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_wide_probe)");
+  if ((e = allow_lds(&k_wide_encode, kSecLdsTotal)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_wide_encode)");
+  if ((e = allow_lds(&k_section_fast, kD32Lds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_section_fast)");
+  return stage1_configure_decode();
 }
 
 // ---- single-pass encoder ----
 namespace {
 struct FusedVariant {
-  int lanes, loadw, l3;
-  bool unal;
+  const FusedKernel* k;
   int tail;  // index of the op appended behind the lanes, -1 = none
 };
-// the k_encode_floatn variant table decides whether the point load covers the plan
+// the piece kernel takes the plan when kFusedKernels holds an instantiation for its layout
 bool fused_variant(const DevPlan& p, const uint8_t* points, FusedVariant* v) {
   int l3 = 3, tail = -1;
-  const int lanes = floatn_lanes(p, points, &l3, &tail);
+  const int lanes = floatn_lanes(p, &l3, &tail);
   if (!lanes) return false;
   bool unal = floatn_unaligned(p, points);
   const int loadw = floatn_loadw(p, lanes, unal, l3, tail);
@@ -1847,48 +1496,35 @@ bool fused_variant(const DevPlan& p, const uint8_t* points, FusedVariant* v) {
   // TAIL on an aligned layout whose loaded dwords reach into the next point: the UNAL instantiation (aligned dwords +
   // realignment, here by 0 bytes) has the guard for the last points of the batch
   if (tail >= 0 && !unal && l3 != 4 && p.ops[0].offset + (uint32_t)loadw * 4u > p.point_step) unal = true;
-  bool ok;
-  if (tail >= 0) ok = l3 == 4 ? loadw == 8 : ((lanes == 3 && (loadw == 4 || loadw == 8)) || (lanes == 4 && loadw == 8));
-  else if (l3 == 4) ok = (loadw == 8);
-  else if (unal) ok = (lanes == 3 && (loadw == 4 || loadw == 8)) || (lanes == 4 && (loadw == 5 || loadw == 8));
-  else ok = (lanes == 3 && (loadw == 3 || loadw == 4 || loadw == 8)) || (lanes == 4 && (loadw == 4 || loadw == 8));
-  if (!ok) return false;
-  v->lanes = lanes;
-  v->loadw = loadw;
-  v->l3 = l3;
-  v->unal = unal;
-  v->tail = tail;
-  return true;
+  for (const FusedKernel& k : kFusedKernels) {
+    if (k.lanes == lanes && k.loadw == loadw && k.unal == unal && k.l3 == l3 && k.tail == (tail >= 0)) {
+      v->k = &k;
+      v->tail = tail;
+      return true;
+    }
+  }
+  return false;
 }
 }  // namespace
 
 uint32_t stage1_piece_points(const DevPlan& plan, const uint8_t* points) {
   FusedVariant v;
   if (!fused_variant(plan, points, &v)) return 0u;
-  return fused_piece_points(v.lanes);
+  return fused_piece_points(v.k->lanes);
 }
 
 // the piece kernel takes this plan and its tail op is the Gorilla field: points per piece, else 0
 uint32_t stage1_gorilla_inline_piece_points(const DevPlan& plan, const uint8_t* points) {
   FusedVariant v;
   if (!fused_variant(plan, points, &v) || v.tail < 0 || plan.ops[v.tail].kind != OP_GORILLA64) return 0u;
-  return fused_piece_points(v.lanes);
+  return fused_piece_points(v.k->lanes);
 }
 
 uint32_t stage1_piece_slot_stride(const DevPlan& plan, const uint8_t* points) {
   FusedVariant v;
   if (!fused_variant(plan, points, &v)) return 0u;
-  const uint32_t per_point = 5u * (uint32_t)v.lanes + (v.tail >= 0 ? kTailMaxBytes : 0u);  // worst case, 5 bytes per token
-  return (fused_piece_points(v.lanes) * per_point + 255u) & ~255u;
-}
-
-// instantiations without a TAIL op that prefetch at most 5 dwords per point: the 64-VGPR kernel (8 waves per SIMD)
-template <int LL, int WW, bool UU, int L3>
-static void launch_fused_variant(dim3 grid, dim3 block, uint32_t lds, hipStream_t stream, const DevPlan& plan, const FusedArgs& A) {
-  if constexpr (WW <= 5)
-    hipLaunchKernelGGL((k_encode_fused_w8<LL, WW, UU, L3>), grid, block, lds, stream, plan, A);
-  else
-    hipLaunchKernelGGL((k_encode_fused<LL, WW, UU, L3>), grid, block, lds, stream, plan, A);
+  const uint32_t per_point = 5u * (uint32_t)v.k->lanes + (v.tail >= 0 ? kTailMaxBytes : 0u);  // worst case, 5 bytes per token
+  return (fused_piece_points(v.k->lanes) * per_point + 255u) & ~255u;
 }
 
 static int launch_fused(const EncodeLaunch& L, hipStream_t stream, uint32_t piece0, uint32_t piece1, bool* probed) {
@@ -1927,9 +1563,7 @@ static int launch_fused(const EncodeLaunch& L, hipStream_t stream, uint32_t piec
     A.tail_size = top.size;
     if (top.kind == OP_GORILLA64) A.tail_windows = reinterpret_cast<const uint16_t*>(L.pre.p[top.type]);
   }
-  const uint32_t region = v.tail >= 0 ? fused_region_bytes_tail(v.lanes)
-                                      : fused_region_bytes_small(v.lanes);
-  uint32_t lds = 16u + kFusedWaves * region;
+  uint32_t lds = v.k->lds;
   // the probe workgroups of the launch share its LDS size: a 16-bit field needs its 8 KiB value bitmap, a 32-bit field a
   // hash table of 6144 slots (24.8 KB: above the 18.3 KB of four 3-byte-per-token regions -- such launches keep 6
   // workgroups per CU instead of 8)
@@ -1941,29 +1575,7 @@ static int launch_fused(const EncodeLaunch& L, hipStream_t stream, uint32_t piec
   A.probe_lds = lds;
   if (probed) *probed = A.n_probe != 0u;
   const dim3 grid(A.n_probe + (piece1 - piece0) / kFusedWaves), block(kFusedThreads);
-#define LAUNCH_FUSED(LL, WW, UU, L3) launch_fused_variant<LL, WW, UU, L3>(grid, block, lds, stream, *L.plan, A)
-#define LAUNCH_FUSED_TAIL(LL, WW, UU, L3)                                                                        \
-  hipLaunchKernelGGL((k_encode_fused<LL, WW, UU, L3, true>), grid, block, lds, stream, *L.plan, A)
-  if (v.tail >= 0) {
-    if (v.l3 == 4) LAUNCH_FUSED_TAIL(4, 8, false, 4);
-    else if (v.unal && v.lanes == 3 && v.loadw == 4) LAUNCH_FUSED_TAIL(3, 4, true, 3);
-    else if (v.unal && v.lanes == 3) LAUNCH_FUSED_TAIL(3, 8, true, 3);
-    else if (v.unal) LAUNCH_FUSED_TAIL(4, 8, true, 3);
-    else if (v.lanes == 3 && v.loadw == 4) LAUNCH_FUSED_TAIL(3, 4, false, 3);
-    else if (v.lanes == 3) LAUNCH_FUSED_TAIL(3, 8, false, 3);
-    else LAUNCH_FUSED_TAIL(4, 8, false, 3);
-  } else if (v.l3 == 4) LAUNCH_FUSED(4, 8, false, 4);
-  else if (v.unal && v.lanes == 3 && v.loadw == 4) LAUNCH_FUSED(3, 4, true, 3);
-  else if (v.unal && v.lanes == 3 && v.loadw == 8) LAUNCH_FUSED(3, 8, true, 3);
-  else if (v.unal && v.lanes == 4 && v.loadw == 5) LAUNCH_FUSED(4, 5, true, 3);
-  else if (v.unal && v.lanes == 4 && v.loadw == 8) LAUNCH_FUSED(4, 8, true, 3);
-  else if (v.lanes == 3 && v.loadw == 3) LAUNCH_FUSED(3, 3, false, 3);
-  else if (v.lanes == 3 && v.loadw == 4) LAUNCH_FUSED(3, 4, false, 3);
-  else if (v.lanes == 3 && v.loadw == 8) LAUNCH_FUSED(3, 8, false, 3);
-  else if (v.lanes == 4 && v.loadw == 4) LAUNCH_FUSED(4, 4, false, 3);
-  else LAUNCH_FUSED(4, 8, false, 3);
-#undef LAUNCH_FUSED
-#undef LAUNCH_FUSED_TAIL
+  hipLaunchKernelGGL(v.k->kernel, grid, block, lds, stream, *L.plan, A);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "k_encode_fused");
   return CLDN_HIP_OK;
@@ -2182,42 +1794,12 @@ int stage1_launch_encode(const EncodeLaunch& L) {
       }
       return CLDN_HIP_OK;
     }
-  } else if (L.n_chunks) {
-    int l3 = 3;
-    const int lanes = floatn_lanes(*L.plan, L.points, &l3);
-    const bool unal = lanes && floatn_unaligned(*L.plan, L.points);
-    const int loadw = lanes ? floatn_loadw(*L.plan, lanes, unal, l3) : 0;
-    // LDS: ring, scan scratch and one staging area per adaptive field that can be staged (at most kStagedCols)
-    const uint32_t floatn_lds = kFloatnRing + 256u + std::min<uint32_t>(L.plan->n_adaptive, kStagedCols) * (4u * 63u * 2u) * 4u + 64u;
-#define LAUNCH_FLOATN(TT, LL, PP, ...)                                                                                          \
-  hipLaunchKernelGGL((k_encode_floatn<TT, LL, PP, kFloatnRing, __VA_ARGS__>), dim3(L.n_chunks * L.subs), dim3(TT), floatn_lds, \
-                     L.stream, *L.plan, L.points, L.points_end, L.chunks, L.slots, L.slot_stride, L.segs,          \
-                     L.segs_per_chunk, L.cols, L.subs, L.sub_points, L.sub_stride)
-    if (l3 == 4 && loadw == 8) LAUNCH_FLOATN(256, 4, 2, 8, false, false, 4);
-    else if (l3 == 4 || loadw == 0) goto generic_regular;
-    else if (unal && lanes == 3 && loadw == 4) LAUNCH_FLOATN(256, 3, 2, 4, false, true);
-    else if (unal && lanes == 3 && loadw == 8) LAUNCH_FLOATN(256, 3, 2, 8, false, true);
-    else if (unal && lanes == 4 && loadw == 5) LAUNCH_FLOATN(256, 4, 2, 5, false, true);
-    else if (unal && lanes == 4 && loadw == 8) LAUNCH_FLOATN(256, 4, 2, 8, false, true);
-    else if (unal) goto generic_regular;
-    else if (lanes == 3 && loadw == 3) LAUNCH_FLOATN(256, 3, 2, 3, false);
-    else if (lanes == 3 && loadw == 4) LAUNCH_FLOATN(256, 3, 2, 4, false);
-    else if (lanes == 3 && loadw == 8) LAUNCH_FLOATN(256, 3, 2, 8, false);
-    else if (lanes == 4 && loadw == 4) LAUNCH_FLOATN(256, 4, 2, 4, false);
-    else if (lanes == 4 && loadw == 8) LAUNCH_FLOATN(256, 4, 2, 8, false);
-    else {
-    generic_regular:
-      if (L.plan->point_step <= kWidePointStep)
-        hipLaunchKernelGGL((k_encode_regular<kRegularThreads, false>), dim3(L.n_chunks * L.subs), dim3(kRegularThreads),
-                           regular_lds(L.plan->point_step), L.stream, *L.plan, L.points, L.points_end, L.chunks, L.slots,
-                           L.slot_stride, L.segs, L.segs_per_chunk, L.cols, L.subs, L.sub_points, L.sub_stride, L.pre);
-      else
-        hipLaunchKernelGGL((k_encode_regular<kRegularThreads, true>), dim3(L.n_chunks * L.subs), dim3(kRegularThreads),
-                           regular_lds(L.plan->point_step), L.stream, *L.plan, L.points, L.points_end, L.chunks, L.slots,
-                           L.slot_stride, L.segs, L.segs_per_chunk, L.cols, L.subs, L.sub_points, L.sub_stride, L.pre);
-    }
-#undef LAUNCH_FLOATN
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_encode_regular/floatn");
+  } else if (L.n_chunks) {  // the generic op interpreter
+    const RegularKernel& k = kRegularKernels[L.plan->point_step <= kWidePointStep ? 0 : 1];
+    hipLaunchKernelGGL(k.kernel, dim3(L.n_chunks * L.subs), dim3(kRegularThreads), regular_lds(L.plan->point_step), L.stream, *L.plan,
+                       L.points, L.points_end, L.chunks, L.slots, L.slot_stride, L.segs, L.segs_per_chunk, L.cols, L.subs, L.sub_points,
+                       L.sub_stride, L.pre);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_encode_regular");
   }
   if (L.events) (void)hipEventRecord(L.events[2], L.stream);
   const uint32_t na = L.plan->n_adaptive;
@@ -2272,27 +1854,21 @@ int stage1_launch_encode(const EncodeLaunch& L) {
     F.fuse_field = fused_field;
     F.fuse_col = nullptr;
     F.fuse_first = nullptr;
+    const FinishKernel* fk;
     if (fused_field != kNoFusedField) {
       F.fuse_col = L.cols.p[fused_field];
       F.fuse_first = L.ranks[fused_field];
       // small batches: 1024-thread workgroups (a chunk's Palette section is latency-bound: twice the threads, 0.6x the time)
       const bool big = L.n_chunks < 200u;
-      const uint32_t splits = big ? 4u : (L.n_chunks >= 512u ? 1u : 2u);
-      F.splits = splits;
+      F.splits = big ? 4u : (L.n_chunks >= 512u ? 1u : 2u);
       const bool u16 = L.plan->adaptive[fused_field].bpv == 2u;
-      if (big && u16)
-        hipLaunchKernelGGL((k_finish<1024, 2>), dim3(L.n_chunks * splits), dim3(1024), Pal32<uint16_t>::kLds, L.stream, F);
-      else if (big)
-        hipLaunchKernelGGL((k_finish<1024, 4>), dim3(L.n_chunks * splits), dim3(1024), Pal32<uint32_t>::kLds, L.stream, F);
-      else if (u16)
-        hipLaunchKernelGGL((k_finish<512, 2>), dim3(L.n_chunks * splits), dim3(512), Pal32<uint16_t>::kLds, L.stream, F);
-      else
-        hipLaunchKernelGGL((k_finish<512, 4>), dim3(L.n_chunks * splits), dim3(512), Pal32<uint32_t>::kLds, L.stream, F);
+      fk = finish_variant(big ? 1024u : 512u, u16 ? 2u : 4u);
     } else {
-      const uint32_t splits = L.n_chunks >= 1024u ? 1u : (L.n_chunks >= 256u ? 4u : 16u);
-      F.splits = splits;
-      hipLaunchKernelGGL((k_finish<256, 0>), dim3(L.n_chunks * splits), dim3(256), 0, L.stream, F);
+      F.splits = L.n_chunks >= 1024u ? 1u : (L.n_chunks >= 256u ? 4u : 16u);
+      fk = finish_variant(256u, 0u);
     }
+    if (!fk) return hip_fail(hipErrorInvalidValue, "k_finish (no variant)");
+    hipLaunchKernelGGL(fk->kernel, dim3(L.n_chunks * F.splits), dim3(fk->threads), fk->lds, L.stream, F);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_finish");
   }
   if (L.events) (void)hipEventRecord(L.events[4], L.stream);
@@ -2332,7 +1908,9 @@ int stage1_launch_frame(const FrameLaunch& L) {
   F.status = L.status;
   F.fuse_field = kNoFusedField;
   F.splits = L.n_chunks >= 1024u ? 1u : (L.n_chunks >= 256u ? 4u : 16u);
-  hipLaunchKernelGGL((k_finish<256, 0>), dim3(L.n_chunks * F.splits), dim3(256), 0, L.stream, F);
+  const FinishKernel* fk = finish_variant(256u, 0u);
+  if (!fk) return hip_fail(hipErrorInvalidValue, "k_finish (no variant)");
+  hipLaunchKernelGGL(fk->kernel, dim3(L.n_chunks * F.splits), dim3(fk->threads), fk->lds, L.stream, F);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_finish (frame)");
   return CLDN_HIP_OK;
 }

@@ -132,6 +132,14 @@ constexpr size_t kDecChunkBytes = 48;
 // Launch errors go to the ABI's thread-local error string (cldn_hip_last_error), implemented in hip_abi.hip.
 int launch_fail(hipError_t e, const char* what);
 
+// A launch with more than the 64 KiB of dynamic LDS a runtime grants by default needs hipFuncAttributeMaxDynamicSharedMemorySize:
+// stage1_configure_kernels / _decode pass their kernels through here with the most dynamic LDS a launch of each takes.
+template <class Kernel>
+inline hipError_t allow_lds(Kernel* kernel, uint32_t lds) {
+  if (lds <= 65536u) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 int stage1_configure_kernels();
 int stage1_configure_decode();   // decode TU (stage1_decode.hip); called by stage1_configure_kernels
 int stage1_launch_encode(const EncodeLaunch& L);

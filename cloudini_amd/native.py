@@ -263,7 +263,7 @@ class Codec:
         self._stage2 = int(stage2)
 
     def pipeline(self, mode: int = 0, points_ptr: int = 0) -> int:
-        """Choose the encoder pipeline (cldn_hip_codec_pipeline: 0 auto, 1 tile kernel + slots, 2 piece kernel + slots);
+        """Choose the encoder pipeline (cldn_hip_codec_pipeline: 0 auto, 1 generic kernel + slots, 2 piece kernel + slots);
         returns the pipeline the next call takes."""
         r = lib().cldn_hip_codec_pipeline(self._h, int(mode), C.c_void_p(points_ptr))
         _check(r)

@@ -190,7 +190,7 @@ uint64_t cldn_hip_stage2_bound(const cldn_hip_plan_t* plan, uint64_t n_points, i
 int cldn_hip_codec_force_modes(cldn_hip_codec_t* codec, const uint8_t* modes, uint32_t n_modes);
 
 /* Encoder pipelines (both produce identical bytes; for A/B runs and tests):
- *   1  tile kernel + slots   every schema: workgroup tiles with barriers (k_encode_floatn / k_encode_regular)
+ *   1  generic kernel + slots  every schema: the op interpreter, workgroup tiles with barriers (k_encode_regular)
  *   2  piece kernel + slots  schemas whose per-point stream is one fused FloatN encoder (3 or 4 leading lossy FLOAT32
  *                            fields), optionally followed by one more per-point encoder: one wave per 504/378-point
  *                            piece, barrier-free (cloudini_amd/csrc/stage1_fused.h)

@@ -19,7 +19,7 @@ def _first_diff(a, b):
 
 
 def check_encode(oracle, info, clouds):
-    """Every encoder pipeline the schema allows (piece kernel + slots, tile kernel + slots) against the oracle."""
+    """Every encoder pipeline the schema allows (piece kernel + slots, generic kernel + slots) against the oracle."""
     from cloudini_amd import native
     plan = native.Plan(info)
     codec = native.Codec(plan)
@@ -32,7 +32,7 @@ def check_encode(oracle, info, clouds):
             continue
         taken_all.add(taken)
         streams, chunk_sizes, modes = codec.encode_host(clouds)
-        tag = {1: "tile kernel + slots", 2: "piece kernel + slots"}[taken]
+        tag = {1: "generic kernel + slots", 2: "piece kernel + slots"}[taken]
         pos = 0
         for k, cloud in enumerate(clouds):
             want, want_modes = wants[k]

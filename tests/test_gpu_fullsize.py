@@ -88,7 +88,7 @@ def test_full_size_configs_match_the_reference_itself(reflib, name):
     n = data.size // info.point_step
     codec = native.Codec(native.Plan(info))
     want = reflib.encode_stage1(info, data)
-    for mode in (2, 1):  # piece kernel (where the schema allows it) and tile kernel
+    for mode in (2, 1):  # piece kernel (where the schema allows it) and generic kernel
         codec.pipeline(mode)
         got = codec.encode_host([data])[0][0]
         assert len(got) == len(want) and np.array_equal(got, want), (name, mode)

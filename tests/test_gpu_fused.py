@@ -1,5 +1,5 @@
 """GPU parity of the piece kernel (cloudini_amd/csrc/stage1_fused.h: one wave per 504/378-point piece) and of k_finish
-(stage1_finish.h: sections, chunk sizes and placement in one launch) against the oracle and against the tile-kernel
+(stage1_finish.h: sections, chunk sizes and placement in one launch) against the oracle and against the generic-kernel
 pipeline, on schemas that exercise every section mode, piece / chunk boundaries, padding pieces, forced modes, ragged
 batches and repeated calls on one codec."""
 import numpy as np
@@ -240,7 +240,7 @@ TAIL_KINDS = ["xyz_rgb_copy_step16", "xyz_u8_copy_step13", "dds_gorilla_step26",
 def test_tail_op_behind_the_floatn_lanes(oracle, kind):
     """Layouts whose regular stream is the fused FloatN encoder plus ONE more per-point encoder (FieldEncoderCopy,
     Float_Lossy<float/double>, Float_Gorilla<double>: include/cloudini_lib/field_encoder.hpp:56-60, :342-357, :156-312)
-    take the piece kernel with the tail token appended to every point; the tile/generic pipeline must agree."""
+    take the piece kernel with the tail token appended to every point; the generic-kernel pipeline must agree."""
     from cloudini_amd import native
     info, data = _tail_layout(kind, 32768 * 2 + 777)
     codec = native.Codec(native.Plan(info))

@@ -61,7 +61,8 @@ def test_shipped_libraries_read_only_the_production_environment_variables():
     assert [n for n in names(host) if n.startswith(("CLDN_", "CLOUDINI_AMD_"))] == [
         "CLDN_HOST_TIMING", "CLOUDINI_AMD_DEVICE_LZ4", "CLOUDINI_AMD_PIPELINE", "CLOUDINI_AMD_STAGE2_THREADS"]
     for dead in (b"k_compact", b"k_chunk_offsets", b"10k_lz4_emitE", b"15k_decode_pointsI", b"13k_probe_modes",
-                 b"18k_sections_dv_cols", b"19k_section_palette32ItLi1024EE"):
+                 b"18k_sections_dv_cols", b"19k_section_palette32ItLi1024EE", b"15k_encode_floatnI",
+                 b"17k_section_paletteItE", b"17k_section_paletteIjE"):
         assert dead not in hip, dead
     csrc = os.path.join(ROOT, "cloudini_amd", "csrc")
     sources = [f for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip"))]
