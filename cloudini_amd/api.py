@@ -76,6 +76,9 @@ def lib() -> C.CDLL:
     L.cldn_amd_stage2_threads.restype = C.c_uint32
     L.cldn_amd_set_stage2_threads.restype = C.c_uint32
     L.cldn_amd_set_stage2_threads.argtypes = [C.c_uint32]
+    L.cldn_amd_device_lz4_decode.restype = C.c_int
+    L.cldn_amd_set_device_lz4_decode.restype = C.c_int
+    L.cldn_amd_set_device_lz4_decode.argtypes = [C.c_int]
     for name in ("cldn_GetHeaderAsYAML", "cldn_GetHeaderAsYAMLFromDDS", "cldn_ConvertCompressedMsgToPointCloud2Msg",
                  "cldn_DecodeCompressedData", "cldn_DecodeCompressedMessage"):
         getattr(L, name).restype = C.c_uint32
@@ -141,6 +144,16 @@ def set_device_lz4(on) -> int:
     """LZ4 streams with stage 2 on the GPU (valid LZ4 blocks, not lz4's own bytes): False / 0 off, True / 1 on, 2 = the FAST
     parameters (4 KiB windows). Returns the level in effect."""
     return int(lib().cldn_amd_set_device_lz4(int(on)))
+
+
+def device_lz4_decode() -> bool:
+    return bool(lib().cldn_amd_device_lz4_decode())
+
+
+def set_device_lz4_decode(on) -> bool:
+    """PointcloudDecoder.decode of LZ4 messages (wire version >= 3) with stage 2 undone on the GPU (cldn_hip_decode_lz4) instead
+    of liblz4 on the host pool. Off by default. Returns the value in effect."""
+    return bool(lib().cldn_amd_set_device_lz4_decode(1 if on else 0))
 
 
 def _device_list(devices):
@@ -257,13 +270,15 @@ class PointcloudDecoder:
         n = _check(lib().cldn_amd_decode(_ptr(st), st.size, _ptr(out), out.size, yaml, len(yaml), C.byref(ver)))
         return out[:n], parse_yaml_info(yaml.value.decode(), ver.value)
 
-    def decode(self, info: EncodingInfo, data, fill: int = 0) -> np.ndarray:
-        """PointcloudDecoder::decode(info, compressed_data (no header), output)."""
+    def decode(self, info: EncodingInfo, data, fill: int = 0, output_is_zero: bool = False) -> np.ndarray:
+        """PointcloudDecoder::decode(info, compressed_data (no header), output). output_is_zero: the buffer is handed over
+        all zeros (decodeInto(..., true): what decode(info, data, std::vector&) does for a vector that arrives empty)."""
         st = _u8(data)
         size = int(info.width) * int(info.height) * int(info.point_step)
-        out = np.full(max(1, size), fill, dtype=np.uint8)
+        out = np.full(max(1, size), 0 if output_is_zero else fill, dtype=np.uint8)
         ci, _keep = _c_info(info)
-        n = _check(lib().cldn_amd_decode_noheader(C.byref(ci), _ptr(st) if st.size else None, st.size, _ptr(out), size))
+        call = lib().cldn_amd_decode_noheader_zeroed if output_is_zero else lib().cldn_amd_decode_noheader
+        n = _check(call(C.byref(ci), _ptr(st) if st.size else None, st.size, _ptr(out), size))
         return out[:n]
 
 

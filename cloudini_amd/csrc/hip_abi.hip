@@ -178,6 +178,8 @@ struct cldn_hip_codec {
   size_t ct_segs_off = 0, ct_anchor_off = 0;
   int stage2 = 0;
   DevBuf d_s1, d_s1_offsets, d_lz_matches, d_lz_counts, d_payload2, d_dst2, d_dec_split;
+  // LZ4 blocks back into bytes (cldn_hip_decode_lz4 / cldn_hip_lz4_decompress): one worst-case slot per chunk, the offset tables
+  DevBuf d_lzd_slots, d_lzd_tables;
   DevBuf d_finrec;            // k_finish look-back records (rec, rec2), cleared only when (re)allocated
   int decode_fill = CLDN_HIP_FILL_KEEP;  // cldn_hip_codec_set_decode_fill
   DevBuf d_dec_bits;          // k_mark_token_ends: token-end bitmap of the streams of a decode call
@@ -551,6 +553,7 @@ int cldn_hip_codec_create(const cldn_hip_plan_t* plan, int device, void* hip_str
     c->own_stream = true;
   }
   int rc = stage1_configure_kernels();
+  if (rc == CLDN_HIP_OK) rc = lz4_configure_decode();
   if (rc == CLDN_HIP_OK && c->plan.wide) {
     // WIDE route: [ops | op_aux | adaptive] in one device buffer, the descriptor that points into it
     const cldn_hip_plan& P = c->plan;
@@ -594,7 +597,7 @@ void cldn_hip_codec_destroy(cldn_hip_codec_t* c) {
   (void)guard.enter(c->device);
   (void)hipStreamSynchronize(c->stream);
   DevBuf* bufs[] = {&c->d_in, &c->d_out, &c->d_slots, &c->d_chunks, &c->d_cloud_first, &c->d_finrec, &c->d_dec_rec, &c->d_dec_bits, &c->d_dec_secs, &c->d_s1, &c->d_s1_offsets,
-                    &c->d_lz_matches, &c->d_lz_counts, &c->d_payload2, &c->d_dst2, &c->d_dec_split,
+                    &c->d_lz_matches, &c->d_lz_counts, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables,
                     &c->d_payload, &c->d_dst, &c->d_offsets, &c->d_modes, &c->d_status, &c->d_dec_meta, &c->d_pre_ptrs, &c->d_dec_cols[0], &c->d_dec_cols[1], &c->d_dec_cols[2], &c->d_dec_cols[3], &c->d_dec_cols[4], &c->d_dec_cols[5], &c->d_dec_cols[6], &c->d_dec_cols[7],
                     &c->d_viz_keys, &c->d_viz_first,
                     &c->d_viz_slot, &c->d_viz_blocks, &c->d_viz_total, &c->d_pieces};
@@ -710,6 +713,7 @@ int cldn_hip_codec_status(cldn_hip_codec_t* c) {
     return fail(CLDN_HIP_ERR_DEVICE, "k_finish: a workgroup waited too long for the sizes of the chunks before it (status 0x%x); the codec uses the ticket order from now on, repeat the call", st);
   }
   if (st & ST_OUT_OVERFLOW) return fail(CLDN_HIP_ERR_CAPACITY, "Output buffer too small for the encoded stream");
+  if (st & ST_LZ4_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed");
   if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "malformed stage-1 stream");
   return CLDN_HIP_OK;
 }
@@ -1444,9 +1448,27 @@ int cldn_hip_decode_stage1(cldn_hip_codec_t* c, const void* streams, int streams
                                       points_out, out_capacity, out_loc);
 }
 
+// the framed decode calls. lz4: every chunk of `streams` is [u32 block size][LZ4 block] (cldn_hip_decode_lz4)
+static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
+                         const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
+                         void* points_out, uint64_t out_capacity, int out_loc, bool lz4);
+
 int cldn_hip_decode_stage1_sized(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                                  const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
                                  void* points_out, uint64_t out_capacity, int out_loc) {
+  return decode_framed(c, streams, streams_loc, stream_offsets, cloud_points, n_clouds, chunk_sizes, chunk_sizes_loc, points_out,
+                       out_capacity, out_loc, false);
+}
+
+int cldn_hip_decode_lz4(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
+                        const uint64_t* cloud_points, uint32_t n_clouds, void* points_out, uint64_t out_capacity, int out_loc) {
+  return decode_framed(c, streams, streams_loc, stream_offsets, cloud_points, n_clouds, nullptr, CLDN_HIP_HOST, points_out,
+                       out_capacity, out_loc, true);
+}
+
+static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
+                         const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
+                         void* points_out, uint64_t out_capacity, int out_loc, bool lz4) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   if (chunk_sizes && chunk_sizes_loc != CLDN_HIP_HOST && chunk_sizes_loc != CLDN_HIP_DEVICE)
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
@@ -1600,8 +1622,21 @@ int cldn_hip_decode_stage1_sized(cldn_hip_codec_t* c, const void* streams, int s
     L.done_cnt = (uint32_t*)((uint8_t*)c->d_dec_secs.p + ((rows + 63u) & ~size_t(63)));
     L.secs_ok = (uint8_t*)(L.done_cnt + n_chunks);
   }
+  // LZ4 chunks: a slot per chunk with the capacity the host path gives LZ4_decompress_safe (cloudini.cpp, PointcloudDecoder::
+  // decodeInto: the bound of a chunk's stage-1 payload + 60); the decoders then read the slots as their stream buffer
+  uint64_t decoder_stream_bytes = stream_bytes - base_off;
+  if (lz4 && n_chunks) {
+    const uint64_t capacity = cldn_hip_stage1_bound(&c->plan, kPointsPerChunk) + 60u;
+    if (capacity > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "decode_lz4: a chunk of this schema may exceed 2 GiB");
+    const uint64_t stride = (capacity + 15u) & ~uint64_t(15);
+    decoder_stream_bytes = stride * n_chunks;
+    if ((rc = c->d_lzd_slots.ensure((size_t)decoder_stream_bytes + 256u)) != CLDN_HIP_OK) return rc;
+    L.lz4_slots = (uint8_t*)c->d_lzd_slots.p;
+    L.lz4_slot_stride = stride;
+    L.lz4_capacity = (uint32_t)capacity;
+  }
   if (plan.varint_and_raw && n_chunks) {  // one bit per stream byte + a word per chunk (k_mark_token_ends)
-    if ((rc = c->d_dec_bits.ensure((size_t)((stream_bytes - base_off) / 8u) + (size_t)n_chunks * 4u + 256u)) != CLDN_HIP_OK) return rc;
+    if ((rc = c->d_dec_bits.ensure((size_t)(decoder_stream_bytes / 8u) + (size_t)n_chunks * 4u + 256u)) != CLDN_HIP_OK) return rc;
     L.token_ends = (uint32_t*)c->d_dec_bits.p;
   }
   L.out = d_outp;
@@ -1659,8 +1694,83 @@ int cldn_hip_decode_stage1_sized(cldn_hip_codec_t* c, const void* streams, int s
   uint32_t st = 0;
   HIP_TRY(hipMemcpyAsync(&st, c->d_status.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  if (st & ST_LZ4_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed");
   if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "malformed stage-1 stream (truncated, bad chunk size, bad mode or trailing bytes)");
   if (need) HIP_TRY(hipMemcpy(points_out, d_outp, (size_t)need, hipMemcpyDeviceToHost));
+  return CLDN_HIP_OK;
+}
+
+int cldn_hip_lz4_decompress(cldn_hip_codec_t* c, const void* blocks, int blocks_loc, const uint64_t* block_offsets, uint32_t n_blocks,
+                            void* out, int out_loc, const uint64_t* out_offsets, uint32_t* sizes) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if ((blocks_loc != CLDN_HIP_HOST && blocks_loc != CLDN_HIP_DEVICE) || (out_loc != CLDN_HIP_HOST && out_loc != CLDN_HIP_DEVICE))
+    return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  if (n_blocks == 0) return CLDN_HIP_OK;
+  if (!block_offsets || !out_offsets || !sizes) return fail(CLDN_HIP_ERR_ARG, "lz4_decompress: NULL offsets / sizes");
+  if (out_loc == CLDN_HIP_DEVICE && ((uintptr_t)sizes & 3u)) return fail(CLDN_HIP_ERR_ARG, "lz4_decompress: device sizes must be 4-byte aligned");
+  for (uint32_t k = 0; k < n_blocks; ++k) {
+    if (block_offsets[k + 1] < block_offsets[k] || out_offsets[k + 1] < out_offsets[k])
+      return fail(CLDN_HIP_ERR_ARG, "lz4_decompress: offsets must be ascending");
+    if (block_offsets[k + 1] - block_offsets[k] > 0x7fffffffull || out_offsets[k + 1] - out_offsets[k] > 0x7fffffffull)
+      return fail(CLDN_HIP_ERR_UNSUPPORTED, "lz4_decompress: block or output span of more than 2 GiB");
+  }
+  const uint64_t b0 = block_offsets[0], b_bytes = block_offsets[n_blocks] - b0;
+  const uint64_t o0 = out_offsets[0], o_bytes = out_offsets[n_blocks] - o0;
+  if ((b_bytes && !blocks) || (o_bytes && !out)) return fail(CLDN_HIP_ERR_ARG, "lz4_decompress: NULL buffer");
+  ENTER_DEVICE(c->device);
+  int rc;
+  if ((rc = c->d_status.ensure(256)) != CLDN_HIP_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, 256, c->stream));
+  // tables: [block offsets u64 | out offsets u64] relative to the first block / span, [sizes u32] for HOST outputs
+  const size_t ne = (size_t)n_blocks + 1;
+  if ((rc = c->d_lzd_tables.ensure(ne * 16u + (size_t)n_blocks * 4u)) != CLDN_HIP_OK) return rc;
+  // (staged through the decode calls' ring of page-locked buffers: no wait for the stream unless the ring has gone round)
+  const uint32_t slot = c->dec_stage_next++ % (uint32_t)cldn_hip_codec::kDecStageRing;
+  PinnedBuf& stage = c->h_dec_stage[slot];
+  if (c->dec_stage_ev[slot]) HIP_TRY(hipEventSynchronize(c->dec_stage_ev[slot]));  // its last upload has left the buffer
+  else HIP_TRY(hipEventCreateWithFlags(&c->dec_stage_ev[slot], hipEventDisableTiming));
+  if ((rc = stage.ensure(ne * 16u)) != CLDN_HIP_OK) return rc;
+  uint64_t* h_bo = (uint64_t*)stage.p;
+  uint64_t* h_oo = h_bo + ne;
+  for (size_t k = 0; k < ne; ++k) {
+    h_bo[k] = block_offsets[k] - b0;
+    h_oo[k] = out_offsets[k] - o0;
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_lzd_tables.p, stage.p, ne * 16u, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->dec_stage_ev[slot], c->stream));
+  const uint8_t* d_blocks = (const uint8_t*)blocks + b0;
+  if (blocks_loc == CLDN_HIP_HOST) {
+    if ((rc = c->d_in.ensure((size_t)std::max<uint64_t>(1, b_bytes))) != CLDN_HIP_OK) return rc;
+    if (b_bytes) HIP_TRY(hipMemcpyAsync(c->d_in.p, (const uint8_t*)blocks + b0, (size_t)b_bytes, hipMemcpyHostToDevice, c->stream));
+    d_blocks = (const uint8_t*)c->d_in.p;
+  }
+  uint8_t* d_outp = (uint8_t*)out + o0;
+  uint32_t* d_sizes = sizes;
+  if (out_loc == CLDN_HIP_HOST) {
+    c->pending_total = 0;  // the device output buffer is reused: a deferred encode output waiting in it is gone
+    if ((rc = c->d_out.ensure((size_t)std::max<uint64_t>(1, o_bytes))) != CLDN_HIP_OK) return rc;
+    d_outp = (uint8_t*)c->d_out.p;
+    // bytes of a span behind the decoded ones keep the caller's content: bring it along
+    if (o_bytes) HIP_TRY(hipMemcpyAsync(d_outp, (const uint8_t*)out + o0, (size_t)o_bytes, hipMemcpyHostToDevice, c->stream));
+    d_sizes = (uint32_t*)((uint8_t*)c->d_lzd_tables.p + ne * 16u);
+  }
+  Lz4DecompressLaunch L;
+  L.stream = c->stream;
+  L.blocks = d_blocks;
+  L.block_offsets = (const uint64_t*)c->d_lzd_tables.p;
+  L.n_blocks = n_blocks;
+  L.out = d_outp;
+  L.out_offsets = (const uint64_t*)c->d_lzd_tables.p + ne;
+  L.sizes = d_sizes;
+  L.status = (uint32_t*)c->d_status.p;
+  if ((rc = lz4_launch_decompress(L)) != CLDN_HIP_OK) return rc;
+  if (out_loc == CLDN_HIP_DEVICE) return CLDN_HIP_OK;
+  uint32_t st = 0;
+  HIP_TRY(hipMemcpyAsync(&st, c->d_status.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(sizes, d_sizes, (size_t)n_blocks * 4u, hipMemcpyDeviceToHost, c->stream));
+  if (o_bytes) HIP_TRY(hipMemcpyAsync((uint8_t*)out + o0, d_outp, (size_t)o_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed (sizes[k] == 0xffffffff marks the blocks)");
   return CLDN_HIP_OK;
 }
 

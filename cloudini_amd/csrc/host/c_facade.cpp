@@ -150,6 +150,12 @@ CLDN_EXPORT int cldn_amd_set_device_lz4(int on) {
   return Cloudini::amd_detail::deviceLz4Level();
 }
 
+CLDN_EXPORT int cldn_amd_device_lz4_decode(void) { return Cloudini::amd_detail::deviceLz4Decode() ? 1 : 0; }
+CLDN_EXPORT int cldn_amd_set_device_lz4_decode(int on) {
+  Cloudini::amd_detail::setDeviceLz4Decode(on != 0);
+  return Cloudini::amd_detail::deviceLz4Decode() ? 1 : 0;
+}
+
 CLDN_EXPORT uint32_t cldn_amd_stage2_threads(void) { return Cloudini::amd_detail::stage2Threads(); }
 CLDN_EXPORT uint32_t cldn_amd_set_stage2_threads(uint32_t n) {
   Cloudini::amd_detail::setStage2Threads(n);

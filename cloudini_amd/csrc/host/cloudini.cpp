@@ -946,6 +946,17 @@ void PointcloudDecoder::decodeInto(const EncodingInfo& info, ConstBufferView com
       remaining -= in_chunk;
     }
     if (remaining != 0) throw std::runtime_error("Encoded data ended before all declared points were decoded");
+    if (info.compression_opt == CompressionOption::LZ4 && amd_detail::deviceLz4Decode()) {
+      // stage 2 undone on the device (amd_detail::setDeviceLz4Decode): the chain is validated, the compressed body goes up as it is
+      if (points == 0) return;
+      const uint64_t offsets[2] = {0, compressed_data.size()};
+      cldn_hip_codec_set_decode_fill(impl_->codec, output_is_zero ? CLDN_HIP_FILL_ZERO : CLDN_HIP_FILL_KEEP);
+      const int rc = cldn_hip_decode_lz4(impl_->codec, compressed_data.data(), CLDN_HIP_HOST, offsets, &points, 1, output.data(),
+                                         out_bytes, CLDN_HIP_HOST);
+      cldn_hip_codec_set_decode_fill(impl_->codec, CLDN_HIP_FILL_KEEP);
+      if (rc != CLDN_HIP_OK) throw std::runtime_error(cldn_hip_last_error());
+      return;
+    }
     if (!direct && !refs.empty()) {
       // undo stage 2: every chunk into its own worst-case slot (concurrently when use_threads), then packed into the
       // framed stage-1 stream the device decoder takes
@@ -1014,6 +1025,12 @@ int deviceLz4Level() {
 bool deviceLz4() { return deviceLz4Level() != 0; }
 void setDeviceLz4(bool on) { g_device_lz4.store(on ? 1 : 0); }
 void setDeviceLz4Level(int level) { g_device_lz4.store(level >= 2 ? 2 : (level == 1 ? 1 : 0)); }
+
+namespace {
+std::atomic<bool> g_device_lz4_decode{false};
+}
+bool deviceLz4Decode() { return g_device_lz4_decode.load(); }
+void setDeviceLz4Decode(bool on) { g_device_lz4_decode.store(on); }
 
 void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,

@@ -40,6 +40,11 @@ bool deviceLz4();
 void setDeviceLz4(bool on);
 int deviceLz4Level();            // 0 host pool, 1 CLDN_HIP_STAGE2_LZ4, 2 CLDN_HIP_STAGE2_LZ4_FAST
 void setDeviceLz4Level(int level);
+// The way back: PointcloudDecoder::decode of an LZ4 message (wire version >= 3) uploads the compressed body and lets
+// cldn_hip_decode_lz4 undo stage 2 on the device instead of LZ4_decompress_safe on the host pool. Off by default, no
+// environment variable; with it off every path is what it was.
+bool deviceLz4Decode();
+void setDeviceLz4Decode(bool on);
 
 uint32_t decompressChunkTo(Cloudini::CompressionOption opt, const uint8_t* src, size_t size, uint8_t* dst, size_t dst_cap);
 // worst-case stage-1 bytes of one 32768-point chunk of this schema (without its [u32 size])

@@ -30,15 +30,7 @@ constexpr uint32_t kStatFoldedByGuess = 12;
 constexpr uint32_t kStatDvChunks = 13;
 constexpr uint32_t kStatDvMode = 14;  // chunks whose section k_locate_sections found to begin with mode byte 0 (whoever decodes it)
 
-struct DecChunk {
-  uint64_t src_off;   // offset of the payload inside the batch's stream buffer
-  uint32_t src_size;  // payload bytes
-  uint32_t n_points;
-  uint64_t first_point;
-  uint32_t cloud;
-  uint32_t valid;     // 0 = do not touch; 1 = chunk of n_points points; 2 = unframed payload of a wire-version-2 stream:
-                      // points until the payload is empty, n_points = the points the output buffer has room for
-};
+// (struct DecChunk: stage1_device.h -- the LZ4 block decoder of lz4_decode.hip fills the same table)
 
 // The three per-cloud tables of a call (stream offsets, first point, first chunk; n_clouds + 1 entries each) for calls of a
 // few clouds travel as a kernel argument: no upload in front of the call (round 6: one cloud per call is the ROS plugins' shape)

@@ -141,9 +141,10 @@ int stage1_launch_decode_unframed(const DevPlan& plan, hipStream_t stream, const
   return CLDN_HIP_OK;
 }
 
-int stage1_launch_decode(const DecodeLaunch& L) {
+int stage1_launch_decode(const DecodeLaunch& L0) {
   hipError_t e;
-  if (L.n_clouds == 0) return CLDN_HIP_OK;
+  if (L0.n_clouds == 0) return CLDN_HIP_OK;
+  DecodeLaunch L = L0;  // (cldn_hip_decode_lz4: `streams` becomes the slots once the blocks are decompressed)
   // timing (cldn_hip_codec_decode_ms): events in front of / behind the kernel that decodes the regular streams
   auto ev_before = [&]() { if (L.events) (void)hipEventRecord(L.events[1], L.stream); };
   auto ev_after = [&]() { if (L.events) (void)hipEventRecord(L.events[2], L.stream); };
@@ -166,6 +167,12 @@ int stage1_launch_decode(const DecodeLaunch& L) {
                        L.cloud_first_point, L.cloud_first_chunk, L.n_clouds, reinterpret_cast<DecChunk*>(L.chunks),
                        L.status, T);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_walk_chunks");
+  }
+  if (L.lz4_slots != nullptr) {  // the table so far describes the LZ4 blocks: undo stage 2, chunk by chunk, into the slots
+    const int rc = lz4_launch_decode_chunks(L.stream, L.streams, reinterpret_cast<DecChunk*>(L.chunks), L.n_chunks, L.lz4_slots,
+                                            L.lz4_slot_stride, L.lz4_capacity, L.status);
+    if (rc != CLDN_HIP_OK) return rc;
+    L.streams = L.lz4_slots;
   }
   if (L.n_chunks && L.wide) {  // schemas beyond the launch-argument plan: the serial decoder with the plan in device memory
     hipLaunchKernelGGL(k_decode_wide, dim3(L.n_chunks), dim3(64), 0, L.stream, *L.wide, L.streams, reinterpret_cast<const DecChunk*>(L.chunks),

@@ -112,12 +112,24 @@ constexpr uint32_t kSectionStride = 409600;  // >= 5 + 32768*11 (DeltaRle worst 
                                              // >= align256(3 + 32768*8) + 32768*15/8 (Palette worst case)
 constexpr uint32_t kPaletteIndexOffset = 262400;  // align256(3 + 32768*8)
 
+// One chunk of a decode call (the table k_walk_chunks / k_build_chunks fill, stage1_decode.h).
+struct DecChunk {
+  uint64_t src_off;   // offset of the payload inside the batch's stream buffer
+  uint32_t src_size;  // payload bytes
+  uint32_t n_points;
+  uint64_t first_point;
+  uint32_t cloud;
+  uint32_t valid;     // 0 = do not touch; 1 = chunk of n_points points; 2 = unframed payload of a wire-version-2 stream:
+                      // points until the payload is empty, n_points = the points the output buffer has room for
+};
+
 // status word bits (device side, sticky)
 enum : uint32_t {
   ST_OUT_OVERFLOW = 1u,    // compacted stream did not fit the output capacity
   ST_CORRUPT = 2u,         // decode: malformed input
   ST_PALETTE_FULL = 4u,    // internal: LDS palette table overflowed (handled by the global-table path)
-  ST_FINISH_TIMEOUT = 8u   // internal: a workgroup of k_finish waited too long for a predecessor's chunk size
+  ST_FINISH_TIMEOUT = 8u,  // internal: a workgroup of k_finish waited too long for a predecessor's chunk size
+  ST_LZ4_REJECT = 16u      // set next to ST_CORRUPT: what was malformed is an LZ4 block (lz4_decode.hip)
 };
 
 // ---- piece kernel (stage1_fused.h) ----

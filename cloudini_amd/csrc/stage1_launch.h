@@ -114,6 +114,12 @@ struct DecodeLaunch {
   void* wp_split;                     // device [wp_split_bytes(n_chunks, wp_maxp)]
   uint32_t wp_maxp;                   // pieces (992 bytes) a chunk's payload may have
   uint32_t wp_parts;                  // workgroups per chunk of the point decoder's launch (1 = chained; wp_split_parts or the test hook)
+  // cldn_hip_decode_lz4: `streams` holds [u32 block size][LZ4 block] per chunk. Behind the walk, lz4_launch_decode_chunks
+  // (lz4_decode.hip) decompresses chunk c into lz4_slots + c * lz4_slot_stride and points the chunk table there: every
+  // kernel behind it reads the slots as its stream buffer. NULL = the streams are stage-1 streams.
+  uint8_t* lz4_slots;                 // device [n_chunks * lz4_slot_stride]
+  uint64_t lz4_slot_stride;           // multiple of 16, >= lz4_capacity
+  uint32_t lz4_capacity;              // what a block may decode to (what the host path gives LZ4_decompress_safe)
 };
 // bytes of the SPLIT workspace: per piece t0 (4) + aggregates (5 x 4) + carries (4 x 4), per chunk 4 flag words
 inline size_t wp_split_bytes(uint32_t n_chunks, uint32_t maxp) { return (size_t)n_chunks * maxp * 40u + (size_t)n_chunks * 16u + 256u; }
@@ -218,6 +224,25 @@ struct Lz4Launch {
   uint32_t* status;
 };
 int lz4_launch(const Lz4Launch& L);
+
+// ---- LZ4 blocks back into bytes on the device (lz4_decode.hip) ----
+constexpr uint32_t kLz4Rejected = 0xffffffffu;  // sizes[k] of a block the strict rules refuse
+struct Lz4DecompressLaunch {
+  hipStream_t stream;
+  const uint8_t* blocks;          // device; block k = [block_offsets[k], block_offsets[k + 1])
+  const uint64_t* block_offsets;  // device [n_blocks + 1]
+  uint32_t n_blocks;
+  uint8_t* out;                   // device; block k may write [out_offsets[k], out_offsets[k + 1])
+  const uint64_t* out_offsets;    // device [n_blocks + 1]
+  uint32_t* sizes;                // device [n_blocks]: decoded bytes, or kLz4Rejected
+  uint32_t* status;               // ST_CORRUPT when a block is refused
+};
+int lz4_configure_decode();
+int lz4_launch_decompress(const Lz4DecompressLaunch& L);
+// the chunks of a decode call: chunk c (valid, src_off / src_size = its block in `streams`) -> slot c; on success the entry
+// points at the slot (src_off = c * slot_stride, src_size = decoded bytes), a refused block clears `valid` and raises ST_CORRUPT
+int lz4_launch_decode_chunks(hipStream_t stream, const uint8_t* streams, DecChunk* chunks, uint32_t n_chunks, uint8_t* slots,
+                             uint64_t slot_stride, uint32_t capacity, uint32_t* status);
 
 // applyVizLossyPreprocessing (viz_kernels.hip)
 struct VizLaunch {

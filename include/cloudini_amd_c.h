@@ -101,6 +101,13 @@ uint32_t cldn_amd_stage2_threads(void);
 int cldn_amd_device_lz4(void);
 int cldn_amd_set_device_lz4(int on);
 uint32_t cldn_amd_set_stage2_threads(uint32_t n);
+/* Stage 2 of LZ4 messages UNDONE on the GPU (include/cloudini_hip.h, cldn_hip_decode_lz4): PointcloudDecoder::decode of a
+ * message with compression_opt == LZ4 and wire version >= 3 then validates the chunk chain as always, uploads the compressed
+ * body and decompresses on the device; a block the device refuses throws "LZ4 decompression failed". The device applies the
+ * strict block rules (a match offset of 0 and the damaged blocks liblz4's shortcut paths accept are refused). Version-2
+ * messages and ZSTD keep the host route. Off by default, no environment variable. Both return the value in effect (0, 1). */
+int cldn_amd_device_lz4_decode(void);
+int cldn_amd_set_device_lz4_decode(int on);
 
 #ifdef __cplusplus
 }

@@ -223,6 +223,39 @@ int cldn_hip_decode_stage1_sized(cldn_hip_codec_t* codec, const void* streams, i
                                  const uint32_t* chunk_sizes, int chunk_sizes_loc, void* points_out, uint64_t out_capacity,
                                  int out_loc);
 
+/* Stage 2 undone on the device (the read side of CLDN_HIP_STAGE2_LZ4; what it replaces: DecompressChunk's LZ4_decompress_safe,
+ * src/codec_common.cpp:260-299). Both calls decode ANY valid LZ4 block (liblz4's as well as this library's), one wave per block
+ * with the last 64 KiB of output in LDS (cloudini_amd/csrc/lz4_decode.hip), under the STRICT rule set of
+ * tests/lz4_block_rules.py: wherever it accepts, LZ4_decompress_safe accepts with the same bytes; it refuses a match offset
+ * of 0 (liblz4 usually copies whatever the destination held) and the damaged blocks liblz4's shortcut paths let through.
+ * A refused block never writes outside its span.
+ *
+ * cldn_hip_lz4_decompress: a batch of independent blocks. The codec only lends its device, stream and workspace.
+ *   blocks        block k occupies [block_offsets[k], block_offsets[k+1]) of `blocks`   (block_offsets: HOST [n_blocks + 1])
+ *   out           block k may write [out_offsets[k], out_offsets[k+1]) of `out`: the span's length is the `dstCapacity` of
+ *                 LZ4_decompress_safe and takes part in the verdict                      (out_offsets: HOST [n_blocks + 1])
+ *   sizes         [n_blocks], where `out` lives (DEVICE: 4-byte aligned): decoded bytes, 0xffffffff for a refused block;
+ *                 the other blocks of the batch are still decoded
+ * `blocks` and `out` may have any byte alignment. A refused block is CLDN_HIP_ERR_CORRUPT at once for HOST outputs and through
+ * cldn_hip_codec_status() for DEVICE outputs. Bytes of a span behind the decoded ones keep their content.
+ *
+ * cldn_hip_decode_lz4: the contract of cldn_hip_decode_stage1, but every chunk of a stream is [u32 LE block size][LZ4 block]:
+ * the body of a message with compression_opt == LZ4 (wire version >= 3), and exactly what the encode calls write under
+ * CLDN_HIP_STAGE2_LZ4[_FAST]. Every block is given the capacity the host path gives LZ4_decompress_safe,
+ * cldn_hip_stage1_bound(plan, 32768) + 60, in a workspace slot of its own; the stage-1 decoders read the slots through their
+ * chunk table (no packing pass, no byte of stream or payload crosses to the host). Chunk chain errors, decode fill,
+ * cldn_hip_codec_decode_stats and cldn_hip_codec_decode_ms (ms[1] includes the decompression) behave as for the stage-1 call;
+ * a refused block reports "LZ4 decompression failed".
+ * Measured (MI355X, profiles/r07_a_lz4_decode_bench.txt): 32 x 1 M XYZI clouds, streams in HBM, liblz4 blocks: 9.8 ms per call, of
+ * which 9.4 ms LZ4 (21.9 GB/s of decoded payload; 16 x 1280x800 depth camera clouds 7.3 ms, 14.9 GB/s); the host route needs
+ * 38.6 ms for the same clouds with 16 threads. A block of ten-byte sequences is a serial chain for its one wave (~0.3 us per
+ * sequence; a 200 KiB literal run: 0.135 ms), so ONE 1 M-point message (31 blocks) takes 5.6 ms against 1.2 ms on the host:
+ * the call pays for compressed data that is already on the device or comes in batches. */
+int cldn_hip_lz4_decompress(cldn_hip_codec_t* codec, const void* blocks, int blocks_loc, const uint64_t* block_offsets,
+                            uint32_t n_blocks, void* out, int out_loc, const uint64_t* out_offsets, uint32_t* sizes);
+int cldn_hip_decode_lz4(cldn_hip_codec_t* codec, const void* streams, int streams_loc, const uint64_t* stream_offsets,
+                        const uint64_t* cloud_points, uint32_t n_clouds, void* points_out, uint64_t out_capacity, int out_loc);
+
 /* Wire version 2 (streams written before the chunked format; the reference still reads them, src/cloudini.cpp:665-667):
  * the whole stage-1 payload is ONE unframed run of points without [u32 size] prefixes and without state resets, decoded
  * until it is empty (DecodeV4Stage1Chunk with expected_points = 0, src/v4_codec.cpp:108-115). The output capacity bounds
