@@ -254,3 +254,207 @@ def reject_table():
     t.append(("period 64 over 4000", _seq(bytes(range(64)), 64, 4000) + _seq(_TAIL12), 64 + 4000 + 12, True))
     t.append(("period 65 over 4000", _seq(bytes(range(65)), 65, 4000) + _seq(_TAIL12), 65 + 4000 + 12, True))
     return t
+
+
+# ---- the structural grid ------------------------------------------------------------------------------------------------
+# Blocks no compressor writes: sequences placed at the constants and branches of cloudini_amd/csrc/lz4_decode.hip (lzd_block).
+# The builder appends every sequence's bytes to its own payload, so the expected output depends on no decoder.
+
+_POOL = np.random.RandomState(20240).randint(0, 256, 300000).astype(np.uint8).tobytes()   # literal bytes (never periodic)
+
+
+class _Builder:
+    def __init__(self):
+        self.blk = bytearray()
+        self.out = bytearray()
+
+    def lits(self, n: int) -> bytes:
+        """n literal bytes; which ones depends on where the output stands, so that equal runs differ between blocks."""
+        at = (len(self.out) * 7 + len(self.blk)) % 30011
+        return _POOL[at:at + n]
+
+    def seq(self, ll: int, offset: int, ml: int):
+        """ll literals, then ml bytes from `offset` back (byte-by-byte semantics)."""
+        lit = self.lits(ll)
+        self.blk += _seq(lit, offset, ml)
+        self.out += lit
+        assert 1 <= offset <= len(self.out) and offset <= 65535 and ml >= 4
+        start = len(self.out) - offset
+        if offset >= ml:
+            self.out += self.out[start:start + ml]
+        else:
+            pattern = bytes(self.out[start:])
+            self.out += (pattern * (ml // offset + 1))[:ml]
+        return self
+
+    def fast_chain(self, n_bytes: int):
+        """Exactly n_bytes (0 or >= 3) of input made of sequences the fast path takes: no length bytes, 3..17 bytes each."""
+        assert n_bytes == 0 or n_bytes >= 3
+        k = 0
+        while n_bytes:
+            s = min(n_bytes, 17 if k % 2 else 11)
+            if 0 < n_bytes - s < 3:
+                s = n_bytes - 3
+            ll = s - 3
+            have = len(self.out) + ll
+            self.seq(ll, 1 + (k * 5) % min(have, 40), 4 + k % 15)
+            n_bytes -= s
+            k += 1
+        return self
+
+    def short_chain(self, n_bytes: int):
+        """n_bytes (>= 0) of input made of sequences with literal runs of 15..269 bytes (window copies, one length byte each):
+        what is left below a sequence's smallest size goes into fast-path sequences."""
+        while n_bytes >= 5 + 15 + 3:
+            ll = min(n_bytes - 5 - 3, 15 + (len(self.blk) * 13) % 240)      # 1 token + 1 length byte + ll + 2 offset + 1 match byte
+            if 0 < n_bytes - (5 + ll) < 3:
+                ll += n_bytes - (5 + ll)                                    # (ll stays below 270: one length byte)
+            self.seq(ll, 1 + len(self.blk) % 60, 19 + len(self.blk) % 200)
+            n_bytes -= 5 + ll
+        return self.fast_chain(n_bytes)
+
+    def end(self, tail: int = 12):
+        lit = self.lits(tail)
+        self.blk += _seq(lit)
+        self.out += lit
+        return bytes(self.blk), bytes(self.out)
+
+
+def _lead_in(style: str, p: int) -> "_Builder":
+    """A block whose next sequence starts p input bytes behind the point where the decoder last re-based its look-ahead
+    (style fast: lzd_block loads the look-ahead at the offset bytes of a general-path sequence, 2 bytes in front of the
+    chain), behind one literal run of p bytes (lit) or behind p bytes of window-copied literal runs (short)."""
+    b = _Builder()
+    if style == "lit":
+        return b.seq(max(p, 1), 1, 19)          # (ml 19: a length byte, so that the sequence takes the general path for every p)
+    b.seq(6, 3, 19)
+    return b.fast_chain(p) if style == "fast" else b.short_chain(p)
+
+
+_FIXED = {"a": (3, 6), "b": (20, 30), "c": (15 + 255 + 2, 4 + 15 + 255 + 7)}   # (literals, match length): 0 / 1 / 2 length bytes each
+_LIT_RUNS = [14, 15, 16, 63, 64, 65, 269, 270, 271, 511, 512, 513, 4095, 4096, 4097, 8191, 8192, 8193, 16383, 16384, 16385,
+             32767, 32768, 32769, 65535, 65536, 65537]
+_LONG_ML = [63, 64, 65, 16383, 16384, 16385, 40000, 70000]
+_WRAP_D = [-65, -64, -63, -17, -16, -15, -1, 0, 1, 15, 16, 17, 63, 64, 65]
+
+
+def structure_grid():
+    """Yields (label, block, capacity, payload): valid blocks, one per structural threshold of lzd_block and side of it."""
+    count = [0]
+
+    def emit(label, b, tail=12, room=None):
+        block, payload = b.end(tail)
+        count[0] += 1
+        extra = (0, 64, 0, 17)[count[0] % 4] if room is None else room      # capacity exact, and with room behind the payload
+        return label, block, len(payload) + extra, payload
+
+    # (1) the 64-byte look-ahead in registers (`lv`, in_u8) and the fast path's `jo + 2 <= la_n`: token, every length byte,
+    #     both offset bytes land on both sides of a 64-byte step of the look-ahead;
+    # (2) the 4 KiB input window (kLzdWin, refill): the same around the first window's end and around the second one's
+    sweeps = list(range(0, 71)) + list(range(4030, 4101)) + list(range(8126, 8201))
+    for style, fixed in (("lit", "b"), ("fast", "a"), ("fast", "c"), ("short", "b")):
+        for p in sweeps:
+            if style != "lit" and p in (1, 2):                              # (no sequence has fewer than 3 bytes)
+                continue
+            b = _lead_in(style, p)
+            ll, ml = _FIXED[fixed]
+            b.seq(ll, 1 + p % 23, ml)
+            b.seq(2, 2 + p % 5, 9)              # (a fast-path sequence behind it: the state the general path leaves)
+            yield emit(f"lookahead/{style}/{fixed}/p{p}", b)
+    # runs of 255-valued length bytes across the window's edge: 13 length bytes that start at input byte q
+    for q in range(4026, 4100, 3):
+        for which in ("literal", "match"):
+            b = _lead_in("fast", q - 10)        # (the lead-in's first sequence has 10 bytes: the token below is input byte q)
+            assert len(b.blk) == q
+            if which == "literal":
+                b.seq(15 + 255 * 12 + 5, 700, 7)
+            else:
+                b.seq(3, 2, 4 + 15 + 255 * 12 + 5)
+            b.seq(1, 1000, 40)
+            yield emit(f"length_bytes_at_window_edge/{which}/q{q}", b)
+    # (3) kLzdShortLit = 512 (window copy | direct global copy), the direct copy's 8192 bytes per loop trip, kLzdPiece: literal
+    #     runs that start at input residues 0, 3, 50, 60 (mod 64), as a sequence's literals and as the block's last literals
+    for run in _LIT_RUNS:
+        n_len = 0 if run < 15 else 1 + (run - 15) // 255
+        for res in (0, 3, 50, 60):
+            k = next(k for k in range(1, 90) if (len(_seq(bytes(k), 1, 4)) + 1 + n_len) % 64 == res)
+            b = _Builder().seq(k, 1, 4).seq(run, 1 + run % 9, 5)
+            yield emit(f"literal_run/{run}/res{res}/middle", b)
+            b = _Builder().seq(k, 1, 4)
+            yield emit(f"literal_run/{run}/res{res}/last", b, tail=run)
+    # (4) kLzdPiece = 16384 and the periodic copy's restart per piece (`start = v0 - off`, r0, s64): every offset below 64;
+    # (5) offset < 64 (periodic) | offset >= 64 (64 bytes per step), the reciprocal-based lane mod off
+    for off in list(range(1, 71)) + [127, 128, 129]:
+        for ml in _LONG_ML:
+            b = _Builder().seq(off + off % 5, off, ml)
+            b.seq(3, min(ml // 2 + off, 65535), 21)                         # (reads the match back: the ring behind it is whole)
+            yield emit(f"long_match/off{off}/ml{ml}", b)
+    for off in range(1, 71):                                                # the fast path's match lengths, 4..18
+        b = _Builder().seq(off, off, 19)
+        for ml in range(4, 19):
+            b.seq(2 + ml % 3, off, ml)
+        yield emit(f"fast_match_lengths/off{off}", b)
+    # (6) the 64-lane read-then-write step with an offset next to the ring's size: every offset 65472..65535
+    for off in range(65472, 65536):
+        for ml in (64, 128, 129, 16385):
+            b = _Builder().seq(65536 + 100 - 4, 9, 4)
+            b.seq(0, off, ml)
+            b.seq(1, off, 6)
+            yield emit(f"far_offset/off{off}/ml{ml}", b)
+    # (7) the 64 KiB ring's wrap (kLzdMask): a history that ends d bytes from a multiple of the ring, then each kind of copy
+    for base in (65536, 131072):
+        for d in _WRAP_D:
+            for what in ("short_literals", "long_literals", "periodic", "far", "fast_chain"):
+                b = _Builder().seq(base + d - 4, 100, 4)
+                if what == "short_literals":
+                    b.seq(140, 33, 8)
+                elif what == "long_literals":
+                    b.seq(5000, 33, 8)
+                elif what == "periodic":
+                    b.seq(1, 7, 300)
+                elif what == "far":
+                    b.seq(1, 60000, 500)
+                else:
+                    b.fast_chain(130)
+                b.seq(2, 65000, 150)
+                yield emit(f"ring_wrap/{base}{d:+d}/{what}", b)
+    # (8) kLzdDrainAt = 32768: the fast path's own `out + a - drained < kLzdDrainAt`, literals written out of the look-ahead
+    #     without a look at the drain mark
+    #     (sequences WITHOUT literals matter most: literals that straddle the look-ahead's end go through copy_literals, which
+    #     drains by itself; behind a run of literal-free sequences only the match copy's look at the drain mark is left)
+    for ll, off, ml in ((3, 5, 12), (14, 20000, 18), (0, 3, 4), (0, 2, 18), (7, 64, 17)):
+        first = 20000 if off > 100 else max(ll, 8, off)
+        b = _Builder().seq(first, first, 5)                                 # (a history that is not one byte repeated)
+        target = len(b.out) + 100000                                        # (the ring goes round as well)
+        while len(b.out) < target:
+            b.seq(ll, off, ml)
+        yield emit(f"drain/fast_path_only/ll{ll}_off{off}_ml{ml}", b)
+    for k in range(0, 71):
+        for name, ml in (("general", 40), ("fast", 8)):
+            b = _Builder().seq(32768 - k - 4, 9, 4)
+            assert len(b.out) == 32768 - k
+            b.seq(10, 31000, ml)
+            b.seq(5, 3, 100)
+            yield emit(f"drain/lookahead_literals_at_32768-{k}/{name}", b)
+    # (9) the end of the block (`ip + ll + 9 <= n_in`, `o1 + 12 <= cap`, `o1 + ml + 5 <= cap`): the accepted side of each
+    #     (reject_table() has the other side) -- a last match that ends exactly 5 bytes in front of the capacity, behind it the
+    #     shortest tail there is, at the exact capacity and with 64 bytes to spare. (A final sequence WITHOUT literals exists
+    #     only as the block 00: behind a match the rules want 5 literals, `ip > iend - 4` refuses anything shorter; the block 00
+    #     is in reject_table() at capacity 0 and 64 and is every guard span of the device tests.)
+    for ml in (7, 8, 18, 19, 20, 64, 300):
+        for ll in (0, 1, 13):
+            for room in (0, 64):
+                b = _Builder().seq(8, 8, 4).seq(ll, 3, ml)
+                yield emit(f"end/last_match_{ml}_behind_{ll}_literals/tail5/room{room}", b, tail=5, room=room)
+
+
+def damaged_grid_sample(every: int = 3, max_block: int = 12000, trials: int = 4):
+    """[(label, block, capacity)]: every `every`-th grid block of at most max_block bytes, damaged `trials` ways (fixed seeds)."""
+    out = []
+    for k, (label, block, cap, _payload) in enumerate(structure_grid()):
+        if k % every or len(block) > max_block:
+            continue
+        rs = np.random.RandomState(k)
+        for t in range(trials):
+            out.append((f"{label}/damage{t}", damaged(rs, block), cap))
+    return out

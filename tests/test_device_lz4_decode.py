@@ -59,6 +59,36 @@ def test_rules_accept_only_what_liblz4_accepts():
         assert (R.decode(block, cap) is not None) == ok, name
 
 
+def test_structure_grid_blocks_are_valid_for_the_rules_and_for_liblz4():
+    """Every block of the structural grid decodes to the payload its builder tracked, by the rules and by liblz4."""
+    n = 0
+    labels = set()
+    for label, block, cap, payload in R.structure_grid():
+        n += 1
+        assert label not in labels, label
+        labels.add(label)
+        assert len(payload) <= cap
+        assert R.decode(block, cap) == payload, label
+        assert R.lz4_decompress_safe(block, cap) == payload, label
+    assert 2000 < n < 5000, n
+
+
+def test_damaged_grid_sample_shows_both_verdicts_and_liblz4_agrees():
+    """R.damaged() on a fixed-seed sample of the grid: rules accept => liblz4 accepts, same bytes; both verdicts occur in
+    at least a quarter of the cases each."""
+    cases = R.damaged_grid_sample()
+    accepted = lenient = 0
+    for label, block, cap in cases:
+        got = R.decode(block, cap)
+        if got is not None:
+            accepted += 1
+            assert R.lz4_decompress_safe(block, cap) == got, label
+        elif R.lz4_decompress_safe(block, cap) is not None:
+            lenient += 1
+    print(f"{len(cases)} damaged grid blocks: {accepted} accepted by the rules, {lenient} more by liblz4 alone")
+    assert accepted > len(cases) // 4 and len(cases) - accepted > len(cases) // 4
+
+
 def test_libraries_export_the_calls_and_the_switch_defaults_to_off():
     from cloudini_amd import api, native
     for name in ("cldn_hip_lz4_decompress", "cldn_hip_decode_lz4"):
@@ -245,6 +275,72 @@ def test_lz4_decompress_damaged_corpus():
     cases = R.damaged_corpus()
     sizes, spans, raised = _run_device(codec, cases, r_in=11, r_out=2)
     _check_against_rules(cases, sizes, spans, raised)
+    codec.close()
+
+
+def _grid_slices(grid, per_call=600):
+    for i in range(0, len(grid), per_call):
+        yield grid[i:i + per_call]
+
+
+def _check_grid(codec, grid, r_in, r_out):
+    for part in _grid_slices(grid):
+        sizes, spans, raised = _run_device(codec, [(b, cap) for _l, b, cap, _p in part], r_in=r_in, r_out=r_out)
+        assert not raised, (part[0][0], r_in, r_out)
+        for k, (label, _b, cap, payload) in enumerate(part):
+            assert sizes[k] == len(payload), (label, r_in, r_out, int(sizes[k]))
+            got = spans[k][: len(payload)].tobytes()
+            if got != payload:
+                first = next(i for i in range(len(payload)) if got[i] != payload[i])
+                raise AssertionError(f"{label} at residues ({r_in}, {r_out}): first wrong byte {first} of {len(payload)}")
+            assert np.all(spans[k][len(payload):] == FILL), (label, r_in, r_out)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r_in,r_out", [(0, 0), (5, 11)])
+def test_lz4_decompress_structure_grid(r_in, r_out):
+    """The whole structural grid on device buffers with guard spans: sizes and bytes are the builder's payload."""
+    codec = _codec()
+    _check_grid(codec, list(R.structure_grid()), r_in, r_out)
+    codec.close()
+
+
+@pytest.mark.gpu
+def test_lz4_decompress_structure_grid_at_every_output_residue():
+    """The ring index is output position + (dst & 15): a fixed-seed tenth of the grid at all 16 output residues."""
+    grid = list(R.structure_grid())
+    pick = np.random.RandomState(16).permutation(len(grid))[: len(grid) // 10]
+    tenth = [grid[int(k)] for k in sorted(pick)]
+    codec = _codec()
+    for r in range(16):
+        _check_grid(codec, tenth, (3 * r + 1) % 16, r)
+    codec.close()
+
+
+@pytest.mark.gpu
+def test_lz4_decompress_structure_grid_from_host_buffers():
+    codec = _codec()
+    for part in _grid_slices(list(R.structure_grid())):
+        caps = [cap for _l, _b, cap, _p in part]
+        out = np.full(sum(caps), FILL, dtype=np.uint8)
+        out, sizes, rc = codec.lz4_decompress_host([b for _l, b, _c, _p in part], caps, out=out)
+        assert rc == 0
+        pos = 0
+        for k, (label, _b, cap, payload) in enumerate(part):
+            assert sizes[k] == len(payload), label
+            assert out[pos:pos + len(payload)].tobytes() == payload and np.all(out[pos + len(payload):pos + cap] == FILL), label
+            pos += cap
+    codec.close()
+
+
+@pytest.mark.gpu
+def test_lz4_decompress_damaged_grid_sample():
+    codec = _codec()
+    sample = R.damaged_grid_sample()
+    for part in _grid_slices(sample, 800):
+        cases = [(b, cap) for _l, b, cap in part]
+        sizes, spans, raised = _run_device(codec, cases, r_in=7, r_out=13)
+        _check_against_rules(cases, sizes, spans, raised, [l for l, _b, _c in part])
     codec.close()
 
 

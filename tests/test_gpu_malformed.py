@@ -18,8 +18,10 @@ import numpy as np
 import pytest
 
 import cases
+import lz4_block_rules as R
+import lz4_body as B
 from cloudini_amd import synth
-from cloudini_amd.schema import FieldType as F
+from cloudini_amd.schema import CompressionOption, FieldType as F
 
 pytestmark = pytest.mark.gpu
 
@@ -97,6 +99,7 @@ class _Checker:
         self.codec = native.Codec(native.Plan(info))
         self.accepted = 0
         self.rejected = 0
+        self.lz4_routed = 0
 
     def check(self, stream, n, what):
         info = self.info.copy(width=n, height=1)
@@ -119,6 +122,37 @@ class _Checker:
             self.accepted += 1
         else:
             self.rejected += 1
+        self.check_lz4_route(info, stream, n, what)
+
+    def check_lz4_route(self, info, stream, n, what):
+        """The same row through cldn_hip_decode_lz4 when the stream's chunk chain parses (its sizes add up): every payload as
+        liblz4's block (the strict rules accept those, so the reference is the exact judge here as well)."""
+        pos, payloads = 0, []
+        while pos + 4 <= len(stream):
+            size = int.from_bytes(stream[pos:pos + 4].tobytes(), "little")
+            if size > len(stream) - pos - 4:
+                return
+            payloads.append(stream[pos + 4:pos + 4 + size])
+            pos += 4 + size
+        if pos != len(stream):
+            return
+        body = B.frame([R.lz4_compress(p.tobytes()) for p in payloads])
+        try:
+            want = self.reflib.decode_noheader(info.copy(compression_opt=CompressionOption.LZ4), body, fill=FILL)
+            ref_ok = True
+        except Exception:
+            want, ref_ok = None, False
+        out = np.full(max(1, n * info.point_step), FILL, dtype=np.uint8)
+        try:
+            got = self.codec.decode_lz4_host([body], [n], out=out)[0]
+            gpu_ok = True
+        except self.native.CloudiniHipError as e:
+            assert e.code == -6, (what, e)
+            gpu_ok = False
+        assert gpu_ok == ref_ok, f"{what}, as an LZ4 body: reference {'accepts' if ref_ok else 'rejects'}, HIP path {'accepts' if gpu_ok else 'rejects'}"
+        if ref_ok:
+            assert np.array_equal(got, want), f"{what}, as an LZ4 body: first difference at byte {int(np.nonzero(got != want)[0][0])}"
+        self.lz4_routed += 1
 
     def close(self):
         self.codec.close()
@@ -220,6 +254,7 @@ def test_varint_forms_in_every_lane_kind(reflib, kind):
                     bad[ci] = np.concatenate([ch[:a], long_tok[:keep]])
                     chk.check(_reframe(bad), n, f"{kind}, chunk {ci}: last token of 10 bytes cut after {keep}")
     assert chk.accepted > 20 and chk.rejected > 20, (chk.accepted, chk.rejected)
+    assert chk.lz4_routed == chk.accepted + chk.rejected                     # (every row of this table keeps the chain whole)
     chk.close()
 
 
