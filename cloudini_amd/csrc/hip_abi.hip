@@ -197,7 +197,11 @@ struct cldn_hip_codec {
   bool last_quad_major = false;
   uint64_t pending_total = 0;  // bytes of a deferred host output waiting in d_out (cldn_hip_codec_fetch_output)
   int pipeline = 0;           // cldn_hip_codec_pipeline: 0 auto, 1 generic kernel + slots, 2 piece kernel + slots
-  DevBuf d_viz_keys, d_viz_first, d_viz_slot, d_viz_blocks, d_viz_total;  // applyVizLossyPreprocessing workspace
+  // applyVizLossyPreprocessing workspace (viz_filter_batch): group tables, slot per point, block counts, keep bits, the
+  // cloud / block tables of the batch, survivors per cloud; d_viz_out: the survivors of a fused filter + encode call
+  DevBuf d_viz_keys, d_viz_slot, d_viz_blocks, d_viz_bits, d_viz_tables, d_viz_kept, d_viz_out;
+  PinnedBuf h_viz;                // upload of the cloud / block tables, readback of the counts
+  uint64_t viz_group_slots = 0;   // cldn_hip_debug_viz_group_slots: 0 = kVizGroupSlots
   DevBuf d_pre[kMaxGorilla];
   // WIDE route: the plan's arrays in device memory (uploaded by cldn_hip_codec_create), per-chunk scratch of the encoder,
   // per-op state of the serial decoder, Gorilla token buffers
@@ -599,8 +603,8 @@ void cldn_hip_codec_destroy(cldn_hip_codec_t* c) {
   DevBuf* bufs[] = {&c->d_in, &c->d_out, &c->d_slots, &c->d_chunks, &c->d_cloud_first, &c->d_finrec, &c->d_dec_rec, &c->d_dec_bits, &c->d_dec_secs, &c->d_s1, &c->d_s1_offsets,
                     &c->d_lz_matches, &c->d_lz_counts, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables,
                     &c->d_payload, &c->d_dst, &c->d_offsets, &c->d_modes, &c->d_status, &c->d_dec_meta, &c->d_pre_ptrs, &c->d_dec_cols[0], &c->d_dec_cols[1], &c->d_dec_cols[2], &c->d_dec_cols[3], &c->d_dec_cols[4], &c->d_dec_cols[5], &c->d_dec_cols[6], &c->d_dec_cols[7],
-                    &c->d_viz_keys, &c->d_viz_first,
-                    &c->d_viz_slot, &c->d_viz_blocks, &c->d_viz_total, &c->d_pieces};
+                    &c->d_viz_keys, &c->d_viz_slot, &c->d_viz_blocks, &c->d_viz_bits, &c->d_viz_tables, &c->d_viz_kept, &c->d_viz_out,
+                    &c->d_pieces};
   for (DevBuf* b : bufs) b->release();
   for (int a = 0; a < kMaxAdaptive; ++a) {
     c->d_cols[a].release();
@@ -612,6 +616,7 @@ void cldn_hip_codec_destroy(cldn_hip_codec_t* c) {
   c->d_wide_state.release();
   for (DevBuf& b : c->d_wide_pre) b.release();
   c->h_stage.release();
+  c->h_viz.release();
   for (int k = 0; k < cldn_hip_codec::kDecStageRing; ++k) {
     c->h_dec_stage[k].release();
     if (c->dec_stage_ev[k]) (void)hipEventDestroy(c->dec_stage_ev[k]);
@@ -677,6 +682,15 @@ __attribute__((visibility("default"))) int cldn_hip_debug_decode_split(cldn_hip_
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   if (parts > 16u) return fail(CLDN_HIP_ERR_ARG, "at most 16 workgroups per chunk");
   c->test_split_parts = parts;
+  return CLDN_HIP_OK;
+}
+
+// Test hook, outside the boundary like the ones above: the table slots a cloud group of the viz pre-filter may take
+// (0 = CLDN_HIP_VIZ_GROUP_SLOTS). A cloud whose table alone is larger forms a group of its own, so 1 puts every cloud into its
+// own group (tests/test_viz_batch.py). Bytes never depend on it.
+__attribute__((visibility("default"))) int cldn_hip_debug_viz_group_slots(cldn_hip_codec_t* c, uint64_t slots) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->viz_group_slots = slots;
   return CLDN_HIP_OK;
 }
 
@@ -825,6 +839,24 @@ static int upload_batch_shape(cldn_hip_codec* c, const uint64_t* cloud_points, u
 // table != NULL: chunk-table output (cldn_hip_encode_stage1_chunks): no framing, `out` is not used
 constexpr int kRetryWithTicket = 0x7fff0001;  // encode_stage1_once: k_finish timed out without the ticket, the call is redone with it
 
+// host clouds (one buffer, or one per cloud) into d_in, back to back
+static int stage_host_input(cldn_hip_codec* c, const void* points, const void* const* cloud_ptrs, const uint64_t* cloud_points,
+                           uint32_t n_clouds, uint32_t point_step, uint64_t bytes) {
+  int rc;
+  if ((rc = c->d_in.ensure((size_t)bytes)) != CLDN_HIP_OK) return rc;
+  if (!cloud_ptrs) {
+    HIP_TRY(hipMemcpyAsync(c->d_in.p, points, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    return CLDN_HIP_OK;
+  }
+  size_t at = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) {
+    const size_t b = (size_t)cloud_points[k] * point_step;
+    if (b) HIP_TRY(hipMemcpyAsync((uint8_t*)c->d_in.p + at, cloud_ptrs[k], b, hipMemcpyHostToDevice, c->stream));
+    at += b;
+  }
+  return CLDN_HIP_OK;
+}
+
 static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int points_loc, const void* const* cloud_ptrs,
                               const uint64_t* cloud_points, uint32_t n_clouds, void* out, uint64_t out_capacity, int out_loc,
                               uint64_t* stream_offsets, uint32_t* chunk_sizes, uint8_t* modes,
@@ -959,17 +991,8 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
       HIP_TRY(hipStreamSynchronize(c->stream));  // `ptrs` lives on this stack frame
     }
     if (points_loc == CLDN_HIP_HOST) {
-      if ((rc = c->d_in.ensure((size_t)n_points * step)) != CLDN_HIP_OK) return rc;
-      if (cloud_ptrs) {  // gather: every cloud straight from its own buffer to its place in the batch
-        size_t at = 0;
-        for (uint32_t k = 0; k < n_clouds; ++k) {
-          const size_t bytes = (size_t)cloud_points[k] * step;
-          if (bytes) HIP_TRY(hipMemcpyAsync((uint8_t*)c->d_in.p + at, cloud_ptrs[k], bytes, hipMemcpyHostToDevice, c->stream));
-          at += bytes;
-        }
-      } else {
-        HIP_TRY(hipMemcpyAsync(c->d_in.p, points, (size_t)n_points * step, hipMemcpyHostToDevice, c->stream));
-      }
+      // (gather: every cloud straight from its own buffer to its place in the batch)
+      if ((rc = stage_host_input(c, points, cloud_ptrs, cloud_points, n_clouds, step, n_points * step)) != CLDN_HIP_OK) return rc;
       d_points = (const uint8_t*)c->d_in.p;
     }
     if (out_loc == CLDN_HIP_HOST && !table) {
@@ -1323,11 +1346,10 @@ int cldn_hip_frame_chunks(cldn_hip_codec_t* c, void* out, uint64_t out_capacity,
   return CLDN_HIP_OK;
 }
 
-int cldn_hip_viz_preprocess(cldn_hip_codec_t* c, const void* points, int points_loc, uint64_t n_points,
-                            uint32_t point_step, uint32_t xyz_offset, float resolution, void* out, uint64_t out_capacity,
-                            int out_loc, uint64_t* kept_points) {
-  if (!c || !kept_points) return fail(CLDN_HIP_ERR_ARG, "viz_preprocess: NULL argument");
-  *kept_points = 0;
+}  // extern "C"
+
+// The argument checks the three viz entry points share (texts of cldn_hip_viz_preprocess).
+static int viz_check_args(int points_loc, int out_loc, uint32_t point_step, uint32_t xyz_offset, float resolution) {
   if ((points_loc != CLDN_HIP_HOST && points_loc != CLDN_HIP_DEVICE) ||
       (out_loc != CLDN_HIP_HOST && out_loc != CLDN_HIP_DEVICE))
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
@@ -1336,7 +1358,164 @@ int cldn_hip_viz_preprocess(cldn_hip_codec_t* c, const void* points, int points_
                 point_step);
   if (!(resolution > 0.0f) || !std::isfinite(resolution))
     return fail(CLDN_HIP_ERR_ARG, "viz_preprocess: resolution must be positive and finite");
-  if (n_points >= 0xffffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "viz_preprocess: more than 2^32 - 2 points");
+  return CLDN_HIP_OK;
+}
+
+// points of the batch, after the per-cloud and per-batch limits
+static int viz_batch_points(const uint64_t* cloud_points, uint32_t n_clouds, uint64_t* total_out) {
+  uint64_t total = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) {
+    if (cloud_points[k] >= 0xffffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "viz_preprocess: more than 2^32 - 2 points");
+    total += cloud_points[k];
+    if (total >= 0xffffffffull)  // (block offsets and ranks are 32-bit)
+      return fail(CLDN_HIP_ERR_UNSUPPORTED, "viz_preprocess: more than 2^32 - 2 points in one batch");
+  }
+  *total_out = total;
+  return CLDN_HIP_OK;
+}
+
+// The filter of a batch whose points are on the device (at least one point): cloud / block / group tables from the batch
+// shape, workspace, the launches, the survivor counts back (kept_points: HOST [n_clouds]). One synchronisation.
+static int viz_filter_batch(cldn_hip_codec* c, const uint8_t* d_points, const uint64_t* cloud_points, uint32_t n_clouds,
+                            uint32_t point_step, uint32_t xyz_offset, float resolution, uint8_t* d_out, uint64_t* kept_points,
+                            uint64_t* kept_total) {
+  int rc;
+  uint64_t n_points = 0, n_blocks64 = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) {
+    n_points += cloud_points[k];
+    n_blocks64 += (cloud_points[k] + kVizBlockPoints - 1u) / kVizBlockPoints;
+  }
+  const uint32_t n_blocks = (uint32_t)n_blocks64;  // (< 2^32 points in the batch)
+  const size_t clouds_b = ((size_t)n_clouds * sizeof(VizCloud) + 63u) & ~size_t(63);
+  const size_t blocks_b = ((size_t)n_blocks * sizeof(VizBlock) + 63u) & ~size_t(63);
+  const size_t kept_b = (size_t)(n_clouds + 1u) * sizeof(uint64_t);
+  // (the previous viz call ended with a synchronisation behind its upload and its readback: the staging buffer is free)
+  if ((rc = c->h_viz.ensure(clouds_b + blocks_b + kept_b)) != CLDN_HIP_OK) return rc;
+  VizCloud* hc = (VizCloud*)c->h_viz.p;
+  VizBlock* hb = (VizBlock*)((uint8_t*)c->h_viz.p + clouds_b);
+  uint64_t* h_kept = (uint64_t*)((uint8_t*)c->h_viz.p + clouds_b + blocks_b);
+  const uint64_t limit = c->viz_group_slots ? c->viz_group_slots : (uint64_t)CLDN_HIP_VIZ_GROUP_SLOTS;
+  std::vector<VizGroup> groups(1, VizGroup{0u, 0u, 0ull});
+  uint64_t first = 0, max_slots = 0;
+  uint32_t bi = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) {
+    const uint64_t n = cloud_points[k];
+    const uint64_t cap = n ? viz_table_capacity(n) : 0u;  // zero-point clouds own no table and no block
+    if (groups.back().table_slots && groups.back().table_slots + cap > limit) groups.push_back(VizGroup{bi, 0u, 0ull});
+    VizGroup& G = groups.back();
+    hc[k].first_point = first;
+    hc[k].n_points = n;
+    hc[k].tab_base = G.table_slots;
+    hc[k].cap_mask = cap ? cap - 1u : 0u;
+    hc[k].first_block = bi;
+    hc[k].reserved = 0u;
+    for (uint64_t p = 0; p < n; p += kVizBlockPoints) {
+      hb[bi].cloud = k;
+      hb[bi].first = (uint32_t)p;
+      ++bi;
+    }
+    G.table_slots += cap;
+    G.n_blocks = bi - G.first_block;
+    max_slots = std::max(max_slots, G.table_slots);
+    first += n;
+  }
+  if ((rc = c->d_viz_tables.ensure(clouds_b + blocks_b)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_viz_keys.ensure((size_t)max_slots * 16u)) != CLDN_HIP_OK) return rc;  // {key, first index, pad} per slot
+  if ((rc = c->d_viz_slot.ensure((size_t)n_points * 4u)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_viz_blocks.ensure((size_t)n_blocks * 4u + 16u)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_viz_bits.ensure((size_t)n_blocks * (kVizBlockPoints / 8u) + 16u)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_viz_kept.ensure(kept_b)) != CLDN_HIP_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(c->d_viz_tables.p, c->h_viz.p, clouds_b + blocks_b, hipMemcpyHostToDevice, c->stream));
+  VizLaunch L;
+  L.stream = c->stream;
+  L.points = d_points;
+  L.n_clouds = n_clouds;
+  L.n_blocks = n_blocks;
+  L.point_step = point_step;
+  L.xyz_offset = xyz_offset;
+  L.inv_res = 1.0f / resolution;  // const float inv_res = 1.0f / xyz_res (ros_msg_utils.cpp:272)
+  L.clouds = (const VizCloud*)c->d_viz_tables.p;
+  L.blocks = (const VizBlock*)((const uint8_t*)c->d_viz_tables.p + clouds_b);
+  L.groups = groups.data();
+  L.n_groups = (uint32_t)groups.size();
+  L.keys = (unsigned long long*)c->d_viz_keys.p;
+  L.slot_of = (uint32_t*)c->d_viz_slot.p;
+  L.keep_bits = (unsigned long long*)c->d_viz_bits.p;
+  L.block_count = (uint32_t*)c->d_viz_blocks.p;
+  L.kept = (unsigned long long*)c->d_viz_kept.p;
+  L.out = d_out;
+  if ((rc = viz_launch(L)) != CLDN_HIP_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(h_kept, c->d_viz_kept.p, kept_b, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  memcpy(kept_points, h_kept, (size_t)n_clouds * sizeof(uint64_t));
+  *kept_total = h_kept[n_clouds];
+  return CLDN_HIP_OK;
+}
+
+// cldn_hip_encode_stage1_viz / _gather: the filter into d_viz_out, then the encode call of the survivors from there
+static int encode_stage1_viz_impl(cldn_hip_codec_t* c, const void* points, int points_loc, const void* const* cloud_ptrs,
+                                  const uint64_t* cloud_points, uint32_t n_clouds, uint32_t xyz_offset, float resolution,
+                                  uint64_t* kept_points, void* out, uint64_t out_capacity, int out_loc, uint64_t* stream_offsets,
+                                  uint32_t* chunk_sizes, uint8_t* modes) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (n_clouds && (!cloud_points || !kept_points)) return fail(CLDN_HIP_ERR_ARG, "viz_preprocess: NULL argument");
+  const uint32_t step = c->plan.point_step;
+  int rc;
+  if ((rc = viz_check_args(points_loc, out_loc, step, xyz_offset, resolution)) != CLDN_HIP_OK) return rc;
+  uint64_t n_points = 0;
+  if ((rc = viz_batch_points(cloud_points, n_clouds, &n_points)) != CLDN_HIP_OK) return rc;
+  for (uint32_t k = 0; k < n_clouds; ++k) kept_points[k] = 0;
+  if (n_points && !points && !cloud_ptrs) return fail(CLDN_HIP_ERR_ARG, "viz_preprocess: NULL buffer");
+  if (cloud_ptrs)
+    for (uint32_t k = 0; k < n_clouds; ++k)
+      if (cloud_points[k] && !cloud_ptrs[k]) return fail(CLDN_HIP_ERR_ARG, "cloud %u: NULL buffer", k);
+  // the caller sizes the output for the input counts, whatever the filter keeps (a deferred host output has no buffer yet)
+  if (!(out == nullptr && out_loc == CLDN_HIP_HOST)) {
+    uint64_t need = 0;
+    for (uint32_t k = 0; k < n_clouds; ++k) need += cldn_hip_stage2_bound(&c->plan, cloud_points[k], c->stage2);
+    if (out_capacity < need)
+      return fail(CLDN_HIP_ERR_CAPACITY, "Output buffer too small for worst-case compressed size (%llu < %llu)",
+                  (unsigned long long)out_capacity, (unsigned long long)need);
+  }
+  if (n_points) {
+    ENTER_DEVICE(c->device);
+    const uint64_t bytes = n_points * step;
+    const uint8_t* d_points = (const uint8_t*)points;
+    if (points_loc == CLDN_HIP_HOST) {
+      if ((rc = stage_host_input(c, points, cloud_ptrs, cloud_points, n_clouds, step, bytes)) != CLDN_HIP_OK) return rc;
+      d_points = (const uint8_t*)c->d_in.p;
+    }
+    if ((rc = c->d_viz_out.ensure((size_t)bytes)) != CLDN_HIP_OK) return rc;
+    uint64_t kept_total = 0;
+    if ((rc = viz_filter_batch(c, d_points, cloud_points, n_clouds, step, xyz_offset, resolution, (uint8_t*)c->d_viz_out.p,
+                               kept_points, &kept_total)) != CLDN_HIP_OK)
+      return rc;
+  }
+  // (a batch without a point never allocated d_viz_out: NULL on a fresh codec, which the encode accepts for a batch whose
+  // clouds are all empty -- it asks for `points` only when there are points)
+  return encode_stage1_impl(c, c->d_viz_out.p, CLDN_HIP_DEVICE, nullptr, kept_points, n_clouds, out, out_capacity, out_loc,
+                            stream_offsets, chunk_sizes, modes);
+}
+
+extern "C" {
+
+int cldn_hip_viz_preprocess(cldn_hip_codec_t* c, const void* points, int points_loc, uint64_t n_points,
+                            uint32_t point_step, uint32_t xyz_offset, float resolution, void* out, uint64_t out_capacity,
+                            int out_loc, uint64_t* kept_points) {
+  if (!c || !kept_points) return fail(CLDN_HIP_ERR_ARG, "viz_preprocess: NULL argument");
+  return cldn_hip_viz_preprocess_batch(c, points, points_loc, &n_points, 1u, point_step, xyz_offset, resolution, out, out_capacity,
+                                       out_loc, kept_points);
+}
+
+int cldn_hip_viz_preprocess_batch(cldn_hip_codec_t* c, const void* points, int points_loc, const uint64_t* cloud_points,
+                                  uint32_t n_clouds, uint32_t point_step, uint32_t xyz_offset, float resolution, void* out,
+                                  uint64_t out_capacity, int out_loc, uint64_t* kept_points) {
+  if (!c || (n_clouds && (!cloud_points || !kept_points))) return fail(CLDN_HIP_ERR_ARG, "viz_preprocess: NULL argument");
+  for (uint32_t k = 0; k < n_clouds; ++k) kept_points[k] = 0;
+  int rc;
+  if ((rc = viz_check_args(points_loc, out_loc, point_step, xyz_offset, resolution)) != CLDN_HIP_OK) return rc;
+  uint64_t n_points = 0;
+  if ((rc = viz_batch_points(cloud_points, n_clouds, &n_points)) != CLDN_HIP_OK) return rc;
   if (n_points == 0) return CLDN_HIP_OK;
   if (!points || !out) return fail(CLDN_HIP_ERR_ARG, "viz_preprocess: NULL buffer");
   const uint64_t bytes = n_points * point_step;
@@ -1344,11 +1523,9 @@ int cldn_hip_viz_preprocess(cldn_hip_codec_t* c, const void* points, int points_
     return fail(CLDN_HIP_ERR_CAPACITY, "viz_preprocess: output needs room for every input point (%llu < %llu)",
                 (unsigned long long)out_capacity, (unsigned long long)bytes);
   ENTER_DEVICE(c->device);
-  int rc;
   const uint8_t* d_points = (const uint8_t*)points;
   if (points_loc == CLDN_HIP_HOST) {
-    if ((rc = c->d_in.ensure((size_t)bytes)) != CLDN_HIP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_in.p, points, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage_host_input(c, points, nullptr, cloud_points, n_clouds, point_step, bytes)) != CLDN_HIP_OK) return rc;
     d_points = (const uint8_t*)c->d_in.p;
   }
   uint8_t* d_out = (uint8_t*)out;
@@ -1357,32 +1534,29 @@ int cldn_hip_viz_preprocess(cldn_hip_codec_t* c, const void* points, int points_
     if ((rc = c->d_out.ensure((size_t)bytes)) != CLDN_HIP_OK) return rc;
     d_out = (uint8_t*)c->d_out.p;
   }
-  const uint64_t cap = viz_table_capacity(n_points);
-  if ((rc = c->d_viz_keys.ensure((size_t)cap * 16u)) != CLDN_HIP_OK) return rc;  // {key, first index, pad} per slot
-  if ((rc = c->d_viz_slot.ensure((size_t)n_points * 4u)) != CLDN_HIP_OK) return rc;
-  if ((rc = c->d_viz_blocks.ensure((size_t)((n_points + 1023u) / 1024u) * 4u + 16u)) != CLDN_HIP_OK) return rc;
-  if ((rc = c->d_viz_total.ensure(16)) != CLDN_HIP_OK) return rc;
-  VizLaunch L;
-  L.stream = c->stream;
-  L.points = d_points;
-  L.n_points = n_points;
-  L.point_step = point_step;
-  L.xyz_offset = xyz_offset;
-  L.inv_res = 1.0f / resolution;  // const float inv_res = 1.0f / xyz_res (ros_msg_utils.cpp:272)
-  L.keys = (unsigned long long*)c->d_viz_keys.p;
-  L.first = nullptr;  // (round 5: inside the table's entries)
-  L.slot_of = (uint32_t*)c->d_viz_slot.p;
-  L.block_count = (uint32_t*)c->d_viz_blocks.p;
-  L.total = (unsigned long long*)c->d_viz_total.p;
-  L.out = d_out;
-  if ((rc = viz_launch(L)) != CLDN_HIP_OK) return rc;
-  unsigned long long kept = 0;
-  HIP_TRY(hipMemcpyAsync(&kept, c->d_viz_total.p, sizeof(kept), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (out_loc == CLDN_HIP_HOST && kept)
-    HIP_TRY(hipMemcpy(out, d_out, (size_t)(kept * point_step), hipMemcpyDeviceToHost));
-  *kept_points = kept;
+  uint64_t kept_total = 0;
+  if ((rc = viz_filter_batch(c, d_points, cloud_points, n_clouds, point_step, xyz_offset, resolution, d_out, kept_points,
+                             &kept_total)) != CLDN_HIP_OK)
+    return rc;
+  if (out_loc == CLDN_HIP_HOST && kept_total)
+    HIP_TRY(hipMemcpy(out, d_out, (size_t)(kept_total * point_step), hipMemcpyDeviceToHost));
   return CLDN_HIP_OK;
+}
+
+int cldn_hip_encode_stage1_viz(cldn_hip_codec_t* c, const void* points, int points_loc, const uint64_t* cloud_points,
+                               uint32_t n_clouds, uint32_t xyz_offset, float resolution, uint64_t* kept_points, void* out,
+                               uint64_t out_capacity, int out_loc, uint64_t* stream_offsets, uint32_t* chunk_sizes, uint8_t* modes) {
+  return encode_stage1_viz_impl(c, points, points_loc, nullptr, cloud_points, n_clouds, xyz_offset, resolution, kept_points, out,
+                                out_capacity, out_loc, stream_offsets, chunk_sizes, modes);
+}
+
+int cldn_hip_encode_stage1_viz_gather(cldn_hip_codec_t* c, const void* const* cloud_ptrs, const uint64_t* cloud_points,
+                                      uint32_t n_clouds, uint32_t xyz_offset, float resolution, uint64_t* kept_points, void* out,
+                                      uint64_t out_capacity, int out_loc, uint64_t* stream_offsets, uint32_t* chunk_sizes,
+                                      uint8_t* modes) {
+  if (n_clouds && !cloud_ptrs) return fail(CLDN_HIP_ERR_ARG, "cloud_ptrs is NULL");
+  return encode_stage1_viz_impl(c, nullptr, CLDN_HIP_HOST, cloud_ptrs, cloud_points, n_clouds, xyz_offset, resolution, kept_points,
+                                out, out_capacity, out_loc, stream_offsets, chunk_sizes, modes);
 }
 
 int cldn_hip_codec_set_decode_fill(cldn_hip_codec_t* c, int fill) {

@@ -55,6 +55,9 @@ struct Parsed {
   Cloudini::EncodingInfo info;
   std::string key;
   uint64_t points = 0;
+  bool viz = false;                // passes the gate of the viz pre-filter and has points: filtered inside the run's GPU call
+  uint32_t viz_xyz_offset = 0;
+  float viz_resolution = 0.0f;
 };
 
 template <typename T>
@@ -254,6 +257,10 @@ struct Batch {
 };
 
 // the front of the reference's loop message by message (mcap_converter.cpp:187-203), then one GPU call per schema run
+// viz_lossy: applyVizLossyPreprocessing is split (host_internal.hpp). What does not depend on the data -- the gate, the
+// FLOAT64 rule -- happens here message by message, so that the runs form on the schema the message has BEHIND the filter; the
+// data path of a whole run is one filter + encode call on the device (encodeStage1BatchViz), and the message's geometry
+// (width = survivors, height = 1) follows from the counts it returns.
 void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
   const size_t n = b.in.size();
   b.parsed.assign(n, Parsed());
@@ -262,14 +269,20 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     Parsed& p = b.parsed[i];
     p.pc = cloudini_ros::getDeserializedPointCloudMessage(Cloudini::ConstBufferView(b.in[i].bytes.data(), b.in[i].bytes.size()));
     cloudini_ros::applyResolutionProfile(opt.profile, p.pc.fields, opt.default_resolution);
-    if (opt.viz_lossy) cloudini_ros::applyVizLossyPreprocessing(p.pc);
+    if (opt.viz_lossy && Cloudini::amd_detail::vizLossyGate(p.pc.fields, p.pc.point_step, &p.viz_xyz_offset, &p.viz_resolution) &&
+        p.pc.data.size() / p.pc.point_step != 0) {
+      p.viz = true;  // (an empty cloud passes through the reference's function untouched)
+      Cloudini::amd_detail::vizLossyStampRule(p.pc.fields);
+    }
     p.info = cloudini_ros::toEncodingInfo(p.pc);
     p.info.compression_opt = opt.compression;
     // the reference's order, message by message (src/ros_msg_utils.cpp:178-190, src/cloudini.cpp:525-531): an empty
     // cloud becomes an empty message whatever its schema says; otherwise point_step 0 and a data size that is not a
     // multiple of point_step are errors (never a silently shortened cloud)
     p.points = 0;
-    if (!p.pc.data.empty()) {
+    if (p.viz) {
+      p.points = p.pc.data.size() / p.info.point_step;  // the filter reads whole points; what it keeps is a multiple
+    } else if (!p.pc.data.empty()) {
       if (p.info.point_step == 0) throw std::runtime_error("convertPointCloud2ToCompressedCloud: point_step cannot be 0");
       if (p.pc.data.size() % p.info.point_step != 0)
         throw std::runtime_error("Input cloud_data size is not a multiple of point_step");
@@ -278,13 +291,15 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     p.key = p.pc.data.empty() ? std::string() : schemaKey(p.info);  // empty clouds: a run of their own, no GPU call
     if (stats) {
       stats->messages += 1;
-      stats->points += p.points;
+      if (!p.viz) stats->points += p.points;  // (filtered messages: their survivors, behind the GPU call)
       stats->input_bytes += b.in[i].bytes.size();
     }
   }
   size_t n_runs = 0;
+  std::vector<uint64_t> kept;
   for (size_t r0 = 0; r0 < n;) {
     size_t r1 = r0 + 1;
+    // (the gate reads the schema only: the non-empty messages of one key all pass it, or none does)
     while (r1 < n && b.parsed[r1].key == b.parsed[r0].key) ++r1;
     if (b.runs.size() <= n_runs) b.runs.emplace_back();  // recycled batches keep their page-locked staging
     Run& run = b.runs[n_runs++];
@@ -303,14 +318,30 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       ptrs[k] = b.parsed[r0 + k].pc.data.data();
       pts[k] = b.parsed[r0 + k].points;
     }
+    auto grow = [&](uint64_t bytes) {  // the exact size, not the 50-bytes-per-point bound; recycled batches keep the capacity
+      if (run.stage1.size() < bytes) run.stage1.resize(bytes + bytes / 8);
+      return run.stage1.data();
+    };
     const auto t_gpu = Clock::now();
-    Cloudini::amd_detail::encodeStage1Batch(
-        info0, ptrs.data(), pts.data(), run.count,
-        [&](uint64_t bytes) {  // the exact size, not the 50-bytes-per-point bound; recycled batches keep the capacity
-          if (run.stage1.size() < bytes) run.stage1.resize(bytes + bytes / 8);
-          return run.stage1.data();
-        },
-        run.offsets, run.chunk_sizes);
+    if (b.parsed[r0].viz) {
+      Cloudini::amd_detail::encodeStage1BatchViz(info0, ptrs.data(), pts.data(), run.count, b.parsed[r0].viz_xyz_offset,
+                                                 b.parsed[r0].viz_resolution, grow, run.offsets, run.chunk_sizes, kept);
+      for (uint32_t k = 0; k < run.count; ++k) {  // what the reference's function leaves behind (src/ros_msg_utils.cpp:326-335)
+        Parsed& p = b.parsed[r0 + k];
+        p.points = kept[k];
+        p.pc.width = static_cast<uint32_t>(kept[k]);
+        p.pc.height = 1;
+        p.pc.row_step = p.pc.point_step * p.pc.width;
+        // the survivors never come to the host: from here on only the SIZE of `data` is read (stage2Phase: 0 = the
+        // reference's empty message without a Cloudini header, :178-183)
+        p.pc.data = Cloudini::ConstBufferView(p.pc.data.data(), static_cast<size_t>(kept[k]) * p.pc.point_step);
+        p.info.width = p.pc.width;
+        p.info.height = 1;
+        if (stats) stats->points += kept[k];
+      }
+    } else {
+      Cloudini::amd_detail::encodeStage1Batch(info0, ptrs.data(), pts.data(), run.count, grow, run.offsets, run.chunk_sizes);
+    }
     if (stats) {
       stats->seconds_gpu += since(t_gpu);
       stats->gpu_batches += 1;

@@ -1054,6 +1054,33 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
   chunk_sizes.resize((size_t)n_chunks);
 }
 
+void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
+                          uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
+                          std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
+                          std::vector<uint64_t>& kept_points) {
+  PlanHandle plan(info);
+  uint64_t n_chunks = 0;  // of the input: an upper bound of what the filtered clouds have
+  for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
+  stream_offsets.assign((size_t)n_clouds + 1, 0);
+  chunk_sizes.assign((size_t)std::max<uint64_t>(1, n_chunks), 0);
+  kept_points.assign((size_t)std::max<uint32_t>(1, n_clouds), 0);
+  cldn_hip_codec_t* codec = pool().acquire(info, plan);
+  int rc = cldn_hip_encode_stage1_viz_gather(codec, reinterpret_cast<const void* const*>(cloud_ptrs), cloud_points, n_clouds,
+                                             xyz_offset, resolution, kept_points.data(), nullptr, 0, CLDN_HIP_HOST,
+                                             stream_offsets.data(), chunk_sizes.data(), nullptr);
+  if (rc == CLDN_HIP_OK) {
+    const uint64_t total = stream_offsets[n_clouds];
+    rc = cldn_hip_codec_fetch_output(codec, total ? grow(total) : nullptr, total);
+  }
+  const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
+  pool().release(info, codec);
+  if (rc != CLDN_HIP_OK) throw std::runtime_error(err);
+  kept_points.resize(n_clouds);
+  n_chunks = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (kept_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
+  chunk_sizes.resize((size_t)n_chunks);
+}
+
 uint32_t compressChunkTo(CompressionOption opt, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_cap) {
   return compressChunk(opt, src, src_size, dst, dst_cap);
 }

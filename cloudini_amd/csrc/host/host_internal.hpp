@@ -10,7 +10,13 @@
 namespace Cloudini {
 namespace amd_detail {
 
-// cldn_hip_viz_preprocess on host buffers through a pooled codec; throws std::runtime_error on failure.
+// cloudini_ros::applyVizLossyPreprocessing in two parts (src/ros_msg_utils.cpp:249-341). The part that does not look at the
+// data: the gate (:250-279 -- a FLOAT32 triple in front, consecutive offsets, one positive finite resolution), which yields
+// where the triple sits and the voxel size, and the rule behind the filter (:336-340: a FLOAT64 field without a resolution
+// gets 1 us). The data path: cldn_hip_viz_preprocess on host buffers through a pooled codec (throws std::runtime_error), or
+// encodeStage1BatchViz below for a whole schema run.
+bool vizLossyGate(const std::vector<Cloudini::PointField>& fields, uint32_t point_step, uint32_t* xyz_offset, float* resolution);
+void vizLossyStampRule(std::vector<Cloudini::PointField>& fields);
 uint64_t vizPreprocessOnDevice(const uint8_t* points, size_t n_points, uint32_t point_step, uint32_t xyz_offset,
                                float resolution, uint8_t* out, size_t out_capacity);
 
@@ -23,6 +29,13 @@ uint64_t vizPreprocessOnDevice(const uint8_t* points, size_t n_points, uint32_t 
 void encodeStage1Batch(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
                        std::vector<uint32_t>& chunk_sizes);
+// The same behind the viz pre-filter (cldn_hip_encode_stage1_viz_gather): every cloud is filtered on its own, the survivors
+// are encoded without leaving the device. kept_points gets n_clouds survivor counts; stream_offsets and chunk_sizes describe
+// the filtered clouds (a cloud that loses every point has an empty stream and no chunk).
+void encodeStage1BatchViz(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
+                          uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
+                          std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
+                          std::vector<uint64_t>& kept_points);
 // detail::CompressChunk (src/codec_common.cpp:220-258) and its worst-case output size
 uint32_t compressChunkTo(Cloudini::CompressionOption opt, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_cap);
 size_t compressedChunkBound(Cloudini::CompressionOption opt, size_t stage1_bytes);

@@ -244,20 +244,42 @@ int lz4_launch_decompress(const Lz4DecompressLaunch& L);
 int lz4_launch_decode_chunks(hipStream_t stream, const uint8_t* streams, DecChunk* chunks, uint32_t n_chunks, uint8_t* slots,
                              uint64_t slot_stride, uint32_t capacity, uint32_t* status);
 
-// applyVizLossyPreprocessing (viz_kernels.hip)
+// applyVizLossyPreprocessing for a ragged batch of clouds (viz_kernels.hip)
+constexpr uint32_t kVizBlockPoints = 1024;  // points per workgroup; blocks are cut per cloud, a cloud's last one may be partial
+struct VizCloud {                 // per cloud, built on the host with the batch shape
+  uint64_t first_point;           // of the cloud in the batch
+  uint64_t n_points;              // < 2^32 - 1
+  uint64_t tab_base;              // first slot of the cloud's table region, counted from the start of its group's tables
+  uint64_t cap_mask;              // viz_table_capacity(n_points) - 1
+  uint32_t first_block;           // the cloud's blocks are [first_block, next cloud's first_block)
+  uint32_t reserved;
+};
+struct VizBlock {
+  uint32_t cloud;
+  uint32_t first;                 // cloud-local index of the block's first point
+};
+struct VizGroup {                 // consecutive clouds whose tables share the table memory
+  uint32_t first_block, n_blocks;
+  uint64_t table_slots;           // sum of the group's table capacities
+};
 struct VizLaunch {
   hipStream_t stream;
-  const uint8_t* points;          // device AoS
-  uint64_t n_points;              // < 2^32
+  const uint8_t* points;          // device AoS, clouds back to back
+  uint32_t n_clouds;
+  uint32_t n_blocks;              // of the whole batch
   uint32_t point_step;
   uint32_t xyz_offset;
   float inv_res;
-  unsigned long long* keys;       // device [viz_table_capacity(n_points)]
-  uint32_t* first;                // device [capacity]
-  uint32_t* slot_of;              // device [n_points]
-  uint32_t* block_count;          // device [ceil(n_points / 1024)]
-  unsigned long long* total;      // device: surviving points
-  uint8_t* out;                   // device [n_points * point_step]
+  const VizCloud* clouds;         // device [n_clouds]
+  const VizBlock* blocks;         // device [n_blocks]
+  const VizGroup* groups;         // HOST [n_groups]
+  uint32_t n_groups;
+  unsigned long long* keys;       // device: {key, first index, pad} per slot, room for the largest group
+  uint32_t* slot_of;              // device [points of the batch]
+  unsigned long long* keep_bits;  // device [16 n_blocks]: one bit per point
+  uint32_t* block_count;          // device [n_blocks]: survivors per block, then the block's output position
+  unsigned long long* kept;       // device [n_clouds + 1]: surviving points per cloud, total
+  uint8_t* out;                   // device: survivors of all clouds back to back
 };
 uint64_t viz_table_capacity(uint64_t n_points);
 int viz_launch(const VizLaunch& L);

@@ -1,14 +1,23 @@
 // viz_kernels.hip -- cloudini_ros::applyVizLossyPreprocessing on the GPU (reference:
-// cloudini_lib/src/ros_msg_utils.cpp:249-341, voxel key packVoxelKey21 :42-49).
+// cloudini_lib/src/ros_msg_utils.cpp:249-341, voxel key packVoxelKey21 :42-49), for a ragged batch of clouds.
 //
 // The reference walks the points once, keeps a hash set of voxel keys and copies every point whose key is new:
 // "first occurrence wins, survivors keep their order". The same result without the serial walk:
 //   k_viz_insert   every finite point inserts its key into an open-addressing table in HBM (64-bit CAS on the key)
 //                  and lowers the slot's first-occurrence index with atomicMin -- the primitive of the Palette
 //                  section encoder, at cloud scale (round 5: behind a per-workgroup LDS table, 16-byte entries)
-//   k_viz_count    a point survives iff it is the first occurrence of its slot; survivors per 1024-point block
-//   k_viz_offsets  exclusive scan of the block counts (one workgroup) -> output position of every block, total
-//   k_viz_gather   block-local ranks (ballot + popcount) and the copy of the surviving points, order preserved
+//   k_viz_count    a point survives iff it is the first occurrence of its slot; one keep bit per point, survivors per
+//                  1024-point block
+//   k_viz_offsets  exclusive scan of the block counts (one workgroup) -> output position of every block, survivors
+//                  per cloud (differences at the cloud boundaries), total
+//   k_viz_gather   block-local ranks (popcounts of the keep bits, summed across 16 lanes) and the copy of the surviving points, order preserved
+//
+// A batch: the clouds lie back to back, share step / triple offset / resolution, and are filtered each on its own. The
+// 64-bit table entry has no room for a cloud id, so every cloud owns a table region (VizCloud::tab_base, cap_mask); the
+// 1024-point blocks are cut per cloud (VizBlock: cloud, first point), so a workgroup -- and the LDS table of k_viz_insert --
+// never sees two clouds. First-occurrence indexes are cloud-local. One scan over all blocks of the batch puts the
+// survivors of cloud k right behind those of cloud k - 1. Table memory is bounded by filtering consecutive cloud groups:
+// clear + insert + count per group (the keep bits outlive the group's table), scan and gather once.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -48,9 +57,11 @@ __device__ __forceinline__ bool viz_finite(float f) { return (__float_as_uint(f)
 constexpr int kVizInsertThreads = 1024;
 constexpr uint32_t kVizLocalSlots = 2048;  // LDS: 16 KiB of keys + 8 KiB of first indexes
 
-__global__ __launch_bounds__(kVizInsertThreads) void k_viz_insert(const uint8_t* __restrict__ points, uint64_t n, uint32_t step,
-                                                                  uint32_t xyz_off, float inv_res, unsigned long long* tab,
-                                                                  uint64_t cap_mask, uint32_t* __restrict__ slot_of) {
+__global__ __launch_bounds__(kVizInsertThreads) void k_viz_insert(const uint8_t* __restrict__ points,
+                                                                  const VizCloud* __restrict__ clouds,
+                                                                  const VizBlock* __restrict__ blocks, uint32_t block_lo,
+                                                                  uint32_t step, uint32_t xyz_off, float inv_res,
+                                                                  unsigned long long* tab_all, uint32_t* __restrict__ slot_of) {
   __shared__ unsigned long long lkeys[kVizLocalSlots];
   __shared__ uint32_t lfirst[kVizLocalSlots];
   const uint32_t tid = threadIdx.x;
@@ -59,11 +70,14 @@ __global__ __launch_bounds__(kVizInsertThreads) void k_viz_insert(const uint8_t*
     lfirst[k] = 0xffffffffu;
   }
   __syncthreads();
-  const uint64_t i = (uint64_t)blockIdx.x * kVizInsertThreads + tid;
-  bool valid = i < n;
+  const VizBlock bd = blocks[block_lo + blockIdx.x];
+  const VizCloud cd = clouds[bd.cloud];
+  const uint64_t i = (uint64_t)bd.first + tid;  // cloud-local: what the table's first-occurrence indexes hold
+  const uint64_t g = cd.first_point + i;        // in the batch
+  bool valid = i < cd.n_points;
   uint64_t key = 0;
   if (valid) {
-    const uint8_t* p = points + i * step + xyz_off;
+    const uint8_t* p = points + g * step + xyz_off;
     const float fx = viz_load_f32(p), fy = viz_load_f32(p + 4), fz = viz_load_f32(p + 8);
     valid = viz_finite(fx) && viz_finite(fy) && viz_finite(fz);
     if (valid) key = viz_key(fx, fy, fz, inv_res);
@@ -81,14 +95,15 @@ __global__ __launch_bounds__(kVizInsertThreads) void k_viz_insert(const uint8_t*
     atomicMin(&lfirst[ls], tid);
   }
   __syncthreads();
-  if (i >= n) return;
+  if (i >= cd.n_points) return;
   if (!valid || lfirst[ls] != tid) {
-    slot_of[i] = 0xffffffffu;  // dropped: not finite, or not the workgroup's first point of its voxel
+    slot_of[g] = 0xffffffffu;  // dropped: not finite, or not the workgroup's first point of its voxel
     return;
   }
+  unsigned long long* tab = tab_all + 2u * cd.tab_base;  // the cloud's own region: at least 2 n_points slots, never full
   uint64_t h = hash >> 20;
   for (;;) {
-    h &= cap_mask;
+    h &= cd.cap_mask;
     unsigned long long k = tab[2u * h];
     if (k == kVizFree) k = atomicCAS(&tab[2u * h], kVizFree, (unsigned long long)key);
     if (k == kVizFree || k == key) break;
@@ -96,34 +111,42 @@ __global__ __launch_bounds__(kVizInsertThreads) void k_viz_insert(const uint8_t*
   }
   uint32_t* first = reinterpret_cast<uint32_t*>(&tab[2u * h + 1u]);
   if (*first > (uint32_t)i) atomicMin(first, (uint32_t)i);
-  slot_of[i] = (uint32_t)h;
+  slot_of[g] = (uint32_t)h;
 }
 
-// (`first` = the table as 32-bit words: slot s keeps its first-occurrence index in word 4 s + 2)
-__device__ __forceinline__ bool viz_survives(uint64_t i, uint64_t n, const uint32_t* slot_of, const uint32_t* first) {
-  if (i >= n) return false;
-  const uint32_t s = slot_of[i];
-  return s != 0xffffffffu && first[4u * (size_t)s + 2u] == (uint32_t)i;
-}
-
-__global__ __launch_bounds__(kVizBlock) void k_viz_count(uint64_t n, const uint32_t* __restrict__ slot_of,
+// (`first` = the group's tables as 32-bit words: slot s of a cloud keeps its first-occurrence index in word 4 (tab_base + s) + 2)
+// keep_bits: one 64-bit word per wave, 16 per block -- what the gather needs of the table, so that the next group may clear it
+__global__ __launch_bounds__(kVizBlock) void k_viz_count(const VizCloud* __restrict__ clouds, const VizBlock* __restrict__ blocks,
+                                                         uint32_t block_lo, const uint32_t* __restrict__ slot_of,
                                                          const uint32_t* __restrict__ first,
+                                                         unsigned long long* __restrict__ keep_bits,
                                                          uint32_t* __restrict__ block_count) {
   __shared__ uint32_t wcnt[kVizBlock / 64];
-  const uint64_t i = (uint64_t)blockIdx.x * kVizBlock + threadIdx.x;
-  const unsigned long long b = __ballot(viz_survives(i, n, slot_of, first));
-  if ((threadIdx.x & 63u) == 0u) wcnt[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+  const uint32_t b = block_lo + blockIdx.x;
+  const VizBlock bd = blocks[b];
+  const VizCloud cd = clouds[bd.cloud];
+  const uint64_t i = (uint64_t)bd.first + threadIdx.x;
+  bool keep = false;
+  if (i < cd.n_points) {
+    const uint32_t s = slot_of[cd.first_point + i];
+    keep = s != 0xffffffffu && first[4u * (size_t)(cd.tab_base + s) + 2u] == (uint32_t)i;
+  }
+  const unsigned long long bits = __ballot(keep);
+  if ((threadIdx.x & 63u) == 0u) {
+    keep_bits[(size_t)b * (kVizBlock / 64) + (threadIdx.x >> 6)] = bits;
+    wcnt[threadIdx.x >> 6] = (uint32_t)__popcll(bits);
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     uint32_t c = 0;
     for (int w = 0; w < kVizBlock / 64; ++w) c += wcnt[w];
-    block_count[blockIdx.x] = c;
+    block_count[b] = c;
   }
 }
 
-// one workgroup: exclusive scan of n_blocks counts (in place) and the total
-__global__ __launch_bounds__(1024) void k_viz_offsets(uint32_t* __restrict__ block_count, uint32_t n_blocks,
-                                                      unsigned long long* __restrict__ total_out) {
+// one workgroup: exclusive scan of n_blocks counts (in place), the survivors of every cloud, the total (kept[n_clouds])
+__global__ __launch_bounds__(1024) void k_viz_offsets(uint32_t* block_count, uint32_t n_blocks, const VizCloud* __restrict__ clouds,
+                                                      uint32_t n_clouds, unsigned long long* __restrict__ kept) {
   __shared__ uint32_t wsum[16];
   __shared__ uint32_t carry_s;
   if (threadIdx.x == 0) carry_s = 0u;
@@ -146,25 +169,33 @@ __global__ __launch_bounds__(1024) void k_viz_offsets(uint32_t* __restrict__ blo
     if (threadIdx.x == 1023u) carry_s = before + incl;
     __syncthreads();
   }
-  if (threadIdx.x == 0) *total_out = carry_s;
+  // (the offsets were written by this workgroup in front of a barrier: they are visible to all of its threads)
+  const uint32_t total = carry_s;
+  for (uint32_t k = threadIdx.x; k < n_clouds; k += 1024u) {
+    const uint32_t lo = clouds[k].first_block, hi = k + 1u < n_clouds ? clouds[k + 1u].first_block : n_blocks;
+    const uint32_t a = lo < n_blocks ? block_count[lo] : total, e = hi < n_blocks ? block_count[hi] : total;
+    kept[k] = e - a;
+  }
+  if (threadIdx.x == 0) kept[n_clouds] = total;
 }
 
-__global__ __launch_bounds__(kVizBlock) void k_viz_gather(const uint8_t* __restrict__ points, uint64_t n, uint32_t step,
-                                                          const uint32_t* __restrict__ slot_of,
-                                                          const uint32_t* __restrict__ first,
-                                                          const uint32_t* __restrict__ block_off,
-                                                          uint8_t* __restrict__ out) {
-  __shared__ uint32_t wcnt[kVizBlock / 64];
-  const uint64_t i = (uint64_t)blockIdx.x * kVizBlock + threadIdx.x;
-  const bool keep = viz_survives(i, n, slot_of, first);
-  const unsigned long long b = __ballot(keep);
+__global__ __launch_bounds__(kVizBlock) void k_viz_gather(const uint8_t* __restrict__ points, const VizCloud* __restrict__ clouds,
+                                                          const VizBlock* __restrict__ blocks, uint32_t step,
+                                                          const unsigned long long* __restrict__ keep_bits,
+                                                          const uint32_t* __restrict__ block_off, uint8_t* __restrict__ out) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (lane == 0u) wcnt[wave] = (uint32_t)__popcll(b);
-  __syncthreads();
-  if (!keep) return;
-  uint32_t rank = block_off[blockIdx.x] + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-  for (uint32_t w = 0; w < wave; ++w) rank += wcnt[w];
-  const uint8_t* src = points + i * step;
+  const unsigned long long* bits = keep_bits + (size_t)blockIdx.x * (kVizBlock / 64);
+  const unsigned long long mine = bits[wave];
+  // survivors of the waves in front of mine: lane w < wave counts the bits of wave w, the 16 lanes are summed with four
+  // exchanges (one load per lane instead of up to 15 dependent ones; all 64 lanes take part, so this comes before the exit)
+  uint32_t before = lane < wave ? (uint32_t)__popcll(bits[lane]) : 0u;
+#pragma unroll
+  for (int d = 1; d < 16; d <<= 1) before += (uint32_t)__shfl_xor((int)before, d);
+  before = (uint32_t)__shfl((int)before, 0);
+  if (((mine >> lane) & 1ull) == 0ull) return;
+  const uint32_t rank = block_off[blockIdx.x] + before + (uint32_t)__popcll(mine & ((1ull << lane) - 1ull));
+  const VizBlock bd = blocks[blockIdx.x];
+  const uint8_t* src = points + (clouds[bd.cloud].first_point + bd.first + threadIdx.x) * step;
   uint8_t* dst = out + (size_t)rank * step;
   if ((step & 15u) == 0u && ((((uintptr_t)src) | ((uintptr_t)dst)) & 15u) == 0u) {
     for (uint32_t k = 0; k < step; k += 16u) *reinterpret_cast<uint4*>(dst + k) = *reinterpret_cast<const uint4*>(src + k);
@@ -186,25 +217,25 @@ uint64_t viz_table_capacity(uint64_t n_points) {
 
 int viz_launch(const VizLaunch& L) {
   hipError_t e;
-  if (L.n_points == 0) {
-    if ((e = hipMemsetAsync(L.total, 0, sizeof(unsigned long long), L.stream)) != hipSuccess) return viz_fail(e, "hipMemsetAsync(viz total)");
-    return 0;
-  }
-  const uint64_t cap = viz_table_capacity(L.n_points);
-  if ((e = hipMemsetAsync(L.keys, 0xff, cap * 16u, L.stream)) != hipSuccess) return viz_fail(e, "hipMemsetAsync(viz table)");
-  const uint32_t n_blocks = (uint32_t)((L.n_points + kVizBlock - 1) / kVizBlock);
-  static_assert(kVizInsertThreads == kVizBlock, "one grid shape");
+  static_assert(kVizInsertThreads == kVizBlock && kVizBlock == (int)kVizBlockPoints, "one grid shape");
   const uint32_t* first_words = reinterpret_cast<const uint32_t*>(L.keys);
-  hipLaunchKernelGGL(k_viz_insert, dim3(n_blocks), dim3(kVizInsertThreads), 0, L.stream, L.points, L.n_points, L.point_step,
-                     L.xyz_offset, L.inv_res, L.keys, cap - 1, L.slot_of);
-  if ((e = hipGetLastError()) != hipSuccess) return viz_fail(e, "k_viz_insert");
-  hipLaunchKernelGGL(k_viz_count, dim3(n_blocks), dim3(kVizBlock), 0, L.stream, L.n_points, L.slot_of, first_words,
-                     L.block_count);
-  if ((e = hipGetLastError()) != hipSuccess) return viz_fail(e, "k_viz_count");
-  hipLaunchKernelGGL(k_viz_offsets, dim3(1), dim3(1024), 0, L.stream, L.block_count, n_blocks, L.total);
+  for (uint32_t g = 0; g < L.n_groups; ++g) {
+    const VizGroup& G = L.groups[g];
+    if (G.n_blocks == 0) continue;
+    if ((e = hipMemsetAsync(L.keys, 0xff, (size_t)G.table_slots * 16u, L.stream)) != hipSuccess) return viz_fail(e, "hipMemsetAsync(viz table)");
+    hipLaunchKernelGGL(k_viz_insert, dim3(G.n_blocks), dim3(kVizInsertThreads), 0, L.stream, L.points, L.clouds, L.blocks,
+                       G.first_block, L.point_step, L.xyz_offset, L.inv_res, L.keys, L.slot_of);
+    if ((e = hipGetLastError()) != hipSuccess) return viz_fail(e, "k_viz_insert");
+    hipLaunchKernelGGL(k_viz_count, dim3(G.n_blocks), dim3(kVizBlock), 0, L.stream, L.clouds, L.blocks, G.first_block, L.slot_of,
+                       first_words, L.keep_bits, L.block_count);
+    if ((e = hipGetLastError()) != hipSuccess) return viz_fail(e, "k_viz_count");
+  }
+  // (a batch without a point still takes the scan: it writes the zero counts)
+  hipLaunchKernelGGL(k_viz_offsets, dim3(1), dim3(1024), 0, L.stream, L.block_count, L.n_blocks, L.clouds, L.n_clouds, L.kept);
   if ((e = hipGetLastError()) != hipSuccess) return viz_fail(e, "k_viz_offsets");
-  hipLaunchKernelGGL(k_viz_gather, dim3(n_blocks), dim3(kVizBlock), 0, L.stream, L.points, L.n_points, L.point_step,
-                     L.slot_of, first_words, L.block_count, L.out);
+  if (L.n_blocks == 0) return 0;
+  hipLaunchKernelGGL(k_viz_gather, dim3(L.n_blocks), dim3(kVizBlock), 0, L.stream, L.points, L.clouds, L.blocks, L.point_step,
+                     L.keep_bits, L.block_count, L.out);
   if ((e = hipGetLastError()) != hipSuccess) return viz_fail(e, "k_viz_gather");
   return 0;
 }

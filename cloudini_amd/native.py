@@ -106,6 +106,17 @@ def lib() -> C.CDLL:
     L.cldn_hip_viz_preprocess.restype = C.c_int
     L.cldn_hip_viz_preprocess.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, vp, C.c_uint64,
                                           C.c_int, u64p]
+    L.cldn_hip_viz_preprocess_batch.restype = C.c_int
+    L.cldn_hip_viz_preprocess_batch.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp,
+                                                C.c_uint64, C.c_int, u64p]
+    L.cldn_hip_encode_stage1_viz.restype = C.c_int
+    L.cldn_hip_encode_stage1_viz.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, C.c_uint32, C.c_float, u64p, vp, C.c_uint64,
+                                             C.c_int, vp, vp, vp]
+    L.cldn_hip_encode_stage1_viz_gather.restype = C.c_int
+    L.cldn_hip_encode_stage1_viz_gather.argtypes = [vp, C.POINTER(vp), u64p, C.c_uint32, C.c_uint32, C.c_float, u64p, vp,
+                                                    C.c_uint64, C.c_int, vp, vp, vp]
+    L.cldn_hip_debug_viz_group_slots.restype = C.c_int
+    L.cldn_hip_debug_viz_group_slots.argtypes = [vp, C.c_uint64]
     L.cldn_hip_codec_set_decode_fill.argtypes = [vp, C.c_int]
     L.cldn_hip_codec_set_decode_fill.restype = C.c_int
     L.cldn_hip_codec_decode_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -237,6 +248,81 @@ class Codec:
         _check(lib().cldn_hip_viz_preprocess(self._h, C.c_void_p(points_ptr), DEVICE, n_points, point_step, xyz_offset,
                                              resolution, C.c_void_p(out_ptr), out_capacity, DEVICE, C.byref(kept)))
         return int(kept.value)
+
+    def viz_group_slots(self, slots: int):
+        """Test hook (cldn_hip_debug_viz_group_slots): table slots per cloud group of the batched pre-filter, 0 = default."""
+        _check(lib().cldn_hip_debug_viz_group_slots(self._h, int(slots)))
+
+    def viz_preprocess_batch_host(self, clouds: Sequence[np.ndarray], point_step: int, xyz_offset: int, resolution: float,
+                                  guard: int = 0):
+        """cldn_hip_viz_preprocess_batch on host buffers. Returns (survivors per cloud, kept_points, tail): `tail` is the output
+        buffer behind the last survivor, `guard` bytes of it beyond the capacity handed to the call (filled with 0xA5)."""
+        arrs = [np.ascontiguousarray(c).view(np.uint8).reshape(-1) for c in clouds]
+        npts = np.array([a.size // point_step for a in arrs], dtype=np.uint64)
+        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        cap = int(npts.sum()) * point_step
+        out = np.full(cap + guard + 1, 0xA5, dtype=np.uint8)
+        kept = np.zeros(max(1, len(arrs)), dtype=np.uint64)
+        _check(lib().cldn_hip_viz_preprocess_batch(
+            self._h, data.ctypes.data_as(C.c_void_p), HOST, npts.ctypes.data_as(C.POINTER(C.c_uint64)), len(arrs), point_step,
+            xyz_offset, resolution, out.ctypes.data_as(C.c_void_p), cap, HOST, kept.ctypes.data_as(C.POINTER(C.c_uint64))))
+        kept = kept[: len(arrs)]
+        ends = np.concatenate([[0], np.cumsum(kept.astype(np.int64) * point_step)])
+        return [out[int(ends[k]):int(ends[k + 1])].copy() for k in range(len(arrs))], kept, out[int(ends[-1]):cap + guard]
+
+    def viz_preprocess_batch_device(self, points_ptr: int, cloud_points, point_step: int, xyz_offset: int, resolution: float,
+                                    out_ptr: int, out_capacity: int) -> np.ndarray:
+        """The same on device buffers; returns kept_points (the call has synchronised)."""
+        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
+        kept = np.zeros(max(1, cp.size), dtype=np.uint64)
+        _check(lib().cldn_hip_viz_preprocess_batch(
+            self._h, C.c_void_p(points_ptr), DEVICE, cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, point_step, xyz_offset,
+            resolution, C.c_void_p(out_ptr), int(out_capacity), DEVICE, kept.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return kept[: cp.size]
+
+    def encode_viz(self, clouds: Sequence[np.ndarray], xyz_offset: int, resolution: float, gather: bool = False,
+                   two_step: bool = False):
+        """cldn_hip_encode_stage1_viz (or _gather: one host buffer per cloud) with host outputs, sized by the INPUT counts;
+        two_step: out = NULL, then cldn_hip_codec_fetch_output. Returns (streams, chunk_sizes, modes, kept_points) of the
+        filtered clouds, shaped like encode_host's."""
+        step = self.plan.point_step
+        arrs = [np.ascontiguousarray(c).view(np.uint8).reshape(-1) for c in clouds]
+        npts = np.array([a.size // step for a in arrs], dtype=np.uint64)
+        n = len(arrs)
+        cap = int(sum(self.plan.stage2_bound(int(p), getattr(self, "_stage2", 0)) for p in npts))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        chunk_sizes = np.zeros(max(1, int(sum((int(p) + 32767) // 32768 for p in npts))), dtype=np.uint32)
+        na = self.plan.adaptive_fields
+        modes = np.full(max(1, n * max(1, na)), 0xEE, dtype=np.uint8)
+        kept = np.zeros(max(1, n), dtype=np.uint64)
+        tail = (None if two_step else out.ctypes.data_as(C.c_void_p), 0 if two_step else cap, HOST,
+                offs.ctypes.data_as(C.c_void_p), chunk_sizes.ctypes.data_as(C.c_void_p), modes.ctypes.data_as(C.c_void_p))
+        cp, kp = npts.ctypes.data_as(C.POINTER(C.c_uint64)), kept.ctypes.data_as(C.POINTER(C.c_uint64))
+        if gather:
+            ptrs = (C.c_void_p * max(1, n))(*[a.ctypes.data if a.size else None for a in arrs])
+            _check(lib().cldn_hip_encode_stage1_viz_gather(self._h, ptrs, cp, n, xyz_offset, resolution, kp, *tail))
+        else:
+            data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+            _check(lib().cldn_hip_encode_stage1_viz(self._h, data.ctypes.data_as(C.c_void_p), HOST, cp, n, xyz_offset, resolution,
+                                                    kp, *tail))
+        if two_step:
+            _check(lib().cldn_hip_codec_fetch_output(self._h, out.ctypes.data_as(C.c_void_p), int(offs[n])))
+        kept = kept[:n]
+        n_chunks = int(sum((int(p) + 32767) // 32768 for p in kept))
+        streams = [out[int(offs[k]):int(offs[k + 1])].copy() for k in range(n)]
+        return streams, chunk_sizes[:n_chunks].copy(), modes[: n * na].reshape(n, na).copy(), kept
+
+    def encode_viz_device(self, points_ptr: int, cloud_points, xyz_offset: int, resolution: float, out_ptr: int,
+                          out_capacity: int, stream_offsets_ptr: int = 0, chunk_sizes_ptr: int = 0, modes_ptr: int = 0):
+        """cldn_hip_encode_stage1_viz on device-resident points with device outputs; returns kept_points."""
+        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
+        kept = np.zeros(max(1, cp.size), dtype=np.uint64)
+        _check(lib().cldn_hip_encode_stage1_viz(
+            self._h, C.c_void_p(points_ptr), DEVICE, cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, xyz_offset, resolution,
+            kept.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(out_ptr), int(out_capacity), DEVICE,
+            C.c_void_p(stream_offsets_ptr), C.c_void_p(chunk_sizes_ptr), C.c_void_p(modes_ptr)))
+        return kept[: cp.size]
 
     def set_decode_fill(self, zero: bool):
         """cldn_hip_codec_set_decode_fill: True = bytes no field covers may be written as 0 (no round trip of a host buffer)."""

@@ -153,7 +153,9 @@ struct TranscodeOptions {
 
 struct TranscodeStats {
   uint64_t messages = 0, points = 0, input_bytes = 0, output_bytes = 0, gpu_batches = 0;
-  double seconds_total = 0, seconds_gpu = 0, seconds_stage2 = 0;  // seconds_gpu: summed over the GPU stages
+  // seconds_gpu: summed over the GPU stages. With viz_lossy it covers the fused filter + encode call of every schema run, the
+  // filter included.
+  double seconds_total = 0, seconds_gpu = 0, seconds_stage2 = 0;
   uint64_t gpu_workers = 0;
 };
 

@@ -275,6 +275,46 @@ int cldn_hip_viz_preprocess(cldn_hip_codec_t* codec, const void* points, int poi
                             uint32_t point_step, uint32_t xyz_offset, float resolution, void* out,
                             uint64_t out_capacity, int out_loc, uint64_t* kept_points);
 
+/* The same for a ragged batch: cloud k (cloud_points[k] points, clouds back to back in `points`, all with this point_step,
+ * xyz_offset and resolution) is filtered on its own -- a voxel is never shared between clouds, two identical clouds each keep
+ * what they would keep alone. The survivors of all clouds land back to back in `out`, batch order: the `points` layout of
+ * cldn_hip_encode_stage1 with cloud_points = kept_points. kept_points: HOST [n_clouds]. `out` must hold every input point
+ * (sum of cloud_points[k] * point_step bytes) and must not overlap `points`; buffers may have any byte alignment. A cloud is
+ * limited to 2^32 - 2 points, and so is the batch. The launch count does not depend on n_clouds: one table clear, four
+ * kernels, one copy of n_clouds + 1 counts, ONE synchronisation per call. cldn_hip_viz_preprocess is the n_clouds == 1 case.
+ *
+ * Workspace (grow-only, the codec's): 16 bytes per table slot, cloud k taking the smallest power of two >= 2 * cloud_points[k]
+ * slots (at least 1024; none for a zero-point cloud) -- 32 x 1 M points = 1 GiB; 4 bytes + 1 bit per input point; 8 bytes per
+ * 1024-point block; 40 bytes per cloud. The table memory is bounded: consecutive clouds form a group while their tables fit
+ * CLDN_HIP_VIZ_GROUP_SLOTS slots (a single larger cloud is a group of its own), every group takes its own clear + two kernels
+ * on the same table memory, the scan and the gather run once per call. */
+#define CLDN_HIP_VIZ_GROUP_SLOTS (1ull << 26) /* 1 GiB of table per cloud group */
+int cldn_hip_viz_preprocess_batch(cldn_hip_codec_t* codec, const void* points, int points_loc, const uint64_t* cloud_points,
+                                  uint32_t n_clouds, uint32_t point_step, uint32_t xyz_offset, float resolution, void* out,
+                                  uint64_t out_capacity, int out_loc, uint64_t* kept_points);
+
+/* Filter, then encode, without the survivors leaving the device: cldn_hip_encode_stage1 / _gather of the clouds that
+ * cldn_hip_viz_preprocess_batch would have produced, byte for byte. point_step is the plan's. kept_points: HOST [n_clouds].
+ * stream_offsets, chunk_sizes, modes and the streams describe the FILTERED clouds (chunk c of the call is the c-th chunk of
+ * the clouds with kept_points[k] points each); stage 2 on the device and forced modes apply as to any encode call. The
+ * caller sizes out_capacity (sum of cldn_hip_stage2_bound over the INPUT counts) and chunk_sizes (chunks of the INPUT
+ * counts) before it knows the survivors: an upper bound, a filtered cloud never has more points or chunks than its input.
+ * The two-step host output works as for the plain calls: out == NULL with CLDN_HIP_HOST, then cldn_hip_codec_fetch_output
+ * of stream_offsets[n_clouds] bytes. A cloud that loses every point takes part as a zero-point cloud: kept_points[k] == 0,
+ * stream_offsets[k + 1] == stream_offsets[k], no chunk, mode 0 for every adaptive field (unless modes are forced) -- what
+ * cldn_hip_encode_stage1 does with a zero-point cloud inside a batch. On top of the filter's workspace the codec keeps the
+ * survivors in a buffer of its own (as large as the input), because the encode writes its output buffer. One synchronisation
+ * for the counts, then the encode call's own. */
+int cldn_hip_encode_stage1_viz(cldn_hip_codec_t* codec, const void* points, int points_loc, const uint64_t* cloud_points,
+                               uint32_t n_clouds, uint32_t xyz_offset, float resolution, uint64_t* kept_points, void* out,
+                               uint64_t out_capacity, int out_loc, uint64_t* stream_offsets, uint32_t* chunk_sizes,
+                               uint8_t* modes);
+/* cloud_ptrs: one HOST buffer per cloud, as cldn_hip_encode_stage1_gather */
+int cldn_hip_encode_stage1_viz_gather(cldn_hip_codec_t* codec, const void* const* cloud_ptrs, const uint64_t* cloud_points,
+                                      uint32_t n_clouds, uint32_t xyz_offset, float resolution, uint64_t* kept_points,
+                                      void* out, uint64_t out_capacity, int out_loc, uint64_t* stream_offsets,
+                                      uint32_t* chunk_sizes, uint8_t* modes);
+
 /* What a decode call may do to the bytes of a point that no field covers. CLDN_HIP_FILL_KEEP (default): they keep the
  * content of points_out (src/field_decoder.cpp:72-76 writes fields only) -- for a HOST buffer of a layout with such bytes
  * that means bringing the buffer to the device first. CLDN_HIP_FILL_ZERO: the caller hands over a buffer whose content
