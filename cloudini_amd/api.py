@@ -69,6 +69,10 @@ def lib() -> C.CDLL:
     L.cldn_amd_decode_directory_on.restype = C.c_int64
     L.cldn_amd_decode_directory_on.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_int32), C.c_uint32,
                                                C.POINTER(C.c_double)]
+    L.cldn_amd_transcode_directory_audit.restype = C.c_int64
+    L.cldn_amd_transcode_directory_audit.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32,
+                                                     C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
+                                                     C.c_uint32, C.POINTER(C.c_double), C.c_char_p, C.c_uint64]
     L.cldn_amd_transcode_directory.restype = C.c_int64
     L.cldn_amd_transcode_directory.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32, C.POINTER(C.c_double)]
     L.cldn_amd_decode_directory.restype = C.c_int64
@@ -164,16 +168,32 @@ def _device_list(devices):
 
 
 def transcode_directory(in_dir: str, out_dir: str, resolution: float = 0.001, compression_opt: int = 2,
-                        viz_lossy: bool = False, batch_messages: int = 64, devices=None) -> dict:
+                        viz_lossy: bool = False, batch_messages: int = 64, devices=None, audit: bool = False,
+                        audit_limits=None) -> dict:
     """Batch transcoder (include/cloudini_amd/batch_transcoder.hpp): every CDR PointCloud2 file of in_dir ->
     CompressedPointCloud2 file of the same name in out_dir. `devices`: GPUs to spread the batches over (one GPU stage per
-    entry; None = the current device). Returns the statistics."""
+    entry; None = the current device). Returns the statistics. audit=True: every encode call is audited on the device
+    (cldn_hip_audit_last_encode) and the per-field summary comes back under "audit" -- a list of dicts (name, is_float,
+    n_bitwise_diff, n_class_diff, n_over_limit, max_abs_err, first_bad_message); audit_limits: {field name: limit} for the
+    fields that should not be held to their resolution."""
     st = (C.c_double * 8)()
     dv, nd = _device_list(devices)
-    _check(lib().cldn_amd_transcode_directory_on(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
-                                                 1 if viz_lossy else 0, batch_messages, dv, nd, st))
     keys = ("messages", "points", "input_bytes", "output_bytes", "gpu_batches", "seconds_total", "seconds_gpu", "seconds_stage2")
-    return dict(zip(keys, [float(x) for x in st]))
+    if not audit:
+        _check(lib().cldn_amd_transcode_directory_on(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
+                                                     1 if viz_lossy else 0, batch_messages, dv, nd, st))
+        return dict(zip(keys, [float(x) for x in st]))
+    import json
+    limits = dict(audit_limits or {})
+    names = (C.c_char_p * max(1, len(limits)))(*[k.encode() for k in limits])
+    values = (C.c_double * max(1, len(limits)))(*[float(v) for v in limits.values()])
+    text = C.create_string_buffer(1 << 20)
+    _check(lib().cldn_amd_transcode_directory_audit(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
+                                                    1 if viz_lossy else 0, batch_messages, dv, nd, names, values, len(limits), st,
+                                                    text, len(text)))
+    out = dict(zip(keys, [float(x) for x in st]))
+    out["audit"] = json.loads(text.value.decode())
+    return out
 
 
 def decode_directory(in_dir: str, out_dir: str, batch_messages: int = 64, devices=None) -> dict:

@@ -244,6 +244,23 @@ struct cldn_hip_codec {
   uint64_t call_index = 0;
   // modes committed elsewhere (continuation of a cloud from a chunk boundary); empty = probe
   std::vector<uint8_t> forced_modes;
+  // audit (audit_kernels.hip): d_audit takes host buffers of an audit call and the decode of an audited stream, d_audit_tab the
+  // cloud / block / field tables, d_audit_rep the report of a call with a HOST report
+  DevBuf d_audit, d_audit_tab, d_audit_rep;
+  PinnedBuf h_audit;              // upload of the tables, guarded by ev_audit
+  hipEvent_t ev_audit = nullptr;
+  // what cldn_hip_audit_last_encode audits: where the last encode call's points and streams lie on the device
+  struct LastEncode {
+    bool valid = false;
+    bool await_frame = false;        // cldn_hip_encode_stage1_chunks: complete once cldn_hip_frame_chunks has run
+    const uint8_t* points = nullptr;
+    const uint8_t* streams = nullptr;
+    const uint64_t* d_offsets = nullptr;  // device [n_clouds + 1], read back when `offsets` is empty
+    std::vector<uint64_t> offsets;        // host copy (calls with host outputs have read them anyway)
+    std::vector<uint64_t> cloud_points;
+    int kind = CLDN_HIP_STAGE2_NONE;
+    void drop() { valid = await_frame = false; }
+  } enc;
 };
 
 extern "C" {
@@ -604,7 +621,7 @@ void cldn_hip_codec_destroy(cldn_hip_codec_t* c) {
                     &c->d_lz_matches, &c->d_lz_counts, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables,
                     &c->d_payload, &c->d_dst, &c->d_offsets, &c->d_modes, &c->d_status, &c->d_dec_meta, &c->d_pre_ptrs, &c->d_dec_cols[0], &c->d_dec_cols[1], &c->d_dec_cols[2], &c->d_dec_cols[3], &c->d_dec_cols[4], &c->d_dec_cols[5], &c->d_dec_cols[6], &c->d_dec_cols[7],
                     &c->d_viz_keys, &c->d_viz_slot, &c->d_viz_blocks, &c->d_viz_bits, &c->d_viz_tables, &c->d_viz_kept, &c->d_viz_out,
-                    &c->d_pieces};
+                    &c->d_pieces, &c->d_audit, &c->d_audit_tab, &c->d_audit_rep};
   for (DevBuf* b : bufs) b->release();
   for (int a = 0; a < kMaxAdaptive; ++a) {
     c->d_cols[a].release();
@@ -617,6 +634,8 @@ void cldn_hip_codec_destroy(cldn_hip_codec_t* c) {
   for (DevBuf& b : c->d_wide_pre) b.release();
   c->h_stage.release();
   c->h_viz.release();
+  c->h_audit.release();
+  if (c->ev_audit) (void)hipEventDestroy(c->ev_audit);
   for (int k = 0; k < cldn_hip_codec::kDecStageRing; ++k) {
     c->h_dec_stage[k].release();
     if (c->dec_stage_ev[k]) (void)hipEventDestroy(c->dec_stage_ev[k]);
@@ -873,6 +892,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
   ENTER_DEVICE(c->device);
   c->ct_valid = false;  // (the workspace is about to be rewritten)
+  c->enc.drop();
   const DevPlan& plan = c->plan.dev;
   const uint32_t step = plan.point_step;
 
@@ -1185,13 +1205,25 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
     c->ct_segs_off = z_segs;
     c->ct_anchor_off = z_anchor;
     c->ct_need = need;
+    c->enc.points = d_points;
+    c->enc.cloud_points.assign(cloud_points, cloud_points + n_clouds);
+    c->enc.kind = CLDN_HIP_STAGE2_NONE;
+    c->enc.await_frame = true;
     if (modes && (size_t)n_clouds * n_adaptive)
       HIP_TRY(hipMemcpyAsync(modes, c->d_modes.p, (size_t)n_clouds * n_adaptive, hipMemcpyDeviceToDevice, c->stream));
     return CLDN_HIP_OK;
   }
 
   const size_t modes_bytes = (size_t)n_clouds * n_adaptive;
+  // cldn_hip_audit_last_encode: where this call's points and streams lie
+  c->enc.points = d_points;
+  c->enc.streams = d_outp;
+  c->enc.cloud_points.assign(cloud_points, cloud_points + n_clouds);
+  c->enc.kind = lz4 ? CLDN_HIP_STAGE2_LZ4 : CLDN_HIP_STAGE2_NONE;
+  c->enc.d_offsets = direct_offsets ? stream_offsets : (const uint64_t*)c->d_offsets.p;
+  c->enc.offsets.clear();
   if (out_loc == CLDN_HIP_DEVICE) {
+    c->enc.valid = true;
     if (stream_offsets && !direct_offsets)
       HIP_TRY(hipMemcpyAsync(stream_offsets, c->d_offsets.p, (size_t)(n_clouds + 1) * sizeof(uint64_t),
                              hipMemcpyDeviceToDevice, c->stream));
@@ -1237,6 +1269,8 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   if (modes && modes_bytes) HIP_TRY(hipMemcpyAsync(modes, c->d_modes.p, modes_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (stream_offsets) memcpy(stream_offsets, h_off, (size_t)(n_clouds + 1) * sizeof(uint64_t));
+  c->enc.offsets.assign(h_off, h_off + n_clouds + 1);
+  c->enc.valid = true;
   return CLDN_HIP_OK;
 }
 
@@ -1289,6 +1323,8 @@ int cldn_hip_frame_chunks(cldn_hip_codec_t* c, void* out, uint64_t out_capacity,
   if (c->ct_need && !out) return fail(CLDN_HIP_ERR_ARG, "out is NULL");
   ENTER_DEVICE(c->device);
   int rc;
+  const bool framed_encode = c->enc.await_frame;  // the table is this codec's last encode call: framing completes it for the audit
+  c->enc.valid = false;
   const uint32_t n_chunks = c->ct_n_chunks, n_clouds = c->ct_n_clouds;
   uint8_t* d_outp = (uint8_t*)out;
   if (out_loc == CLDN_HIP_HOST) {
@@ -1322,7 +1358,11 @@ int cldn_hip_frame_chunks(cldn_hip_codec_t* c, void* out, uint64_t out_capacity,
   F.out_capacity = out_capacity;
   F.status = (uint32_t*)c->d_status.p;
   if ((rc = stage1_launch_frame(F)) != CLDN_HIP_OK) return rc;
+  c->enc.streams = d_outp;
+  c->enc.d_offsets = (const uint64_t*)c->d_offsets.p;
+  c->enc.offsets.clear();
   if (out_loc == CLDN_HIP_DEVICE) {
+    c->enc.valid = framed_encode;
     if (stream_offsets)
       HIP_TRY(hipMemcpyAsync(stream_offsets, c->d_offsets.p, (size_t)(n_clouds + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
     if (chunk_sizes && n_chunks)
@@ -1343,6 +1383,8 @@ int cldn_hip_frame_chunks(cldn_hip_codec_t* c, void* out, uint64_t out_capacity,
     HIP_TRY(hipMemcpyAsync(chunk_sizes, c->d_payload.p, (size_t)n_chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (stream_offsets) memcpy(stream_offsets, h_off, (size_t)(n_clouds + 1) * sizeof(uint64_t));
+  c->enc.offsets.assign(h_off, h_off + n_clouds + 1);
+  c->enc.valid = framed_encode;
   return CLDN_HIP_OK;
 }
 
@@ -1511,6 +1553,7 @@ int cldn_hip_viz_preprocess_batch(cldn_hip_codec_t* c, const void* points, int p
                                   uint32_t n_clouds, uint32_t point_step, uint32_t xyz_offset, float resolution, void* out,
                                   uint64_t out_capacity, int out_loc, uint64_t* kept_points) {
   if (!c || (n_clouds && (!cloud_points || !kept_points))) return fail(CLDN_HIP_ERR_ARG, "viz_preprocess: NULL argument");
+  c->enc.drop();
   for (uint32_t k = 0; k < n_clouds; ++k) kept_points[k] = 0;
   int rc;
   if ((rc = viz_check_args(points_loc, out_loc, point_step, xyz_offset, resolution)) != CLDN_HIP_OK) return rc;
@@ -1622,6 +1665,13 @@ int cldn_hip_decode_stage1(cldn_hip_codec_t* c, const void* streams, int streams
                                       points_out, out_capacity, out_loc);
 }
 
+// what the status word of a framed decode call means to its caller
+static int decode_verdict(uint32_t st) {
+  if (st & ST_LZ4_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed");
+  if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "malformed stage-1 stream (truncated, bad chunk size, bad mode or trailing bytes)");
+  return CLDN_HIP_OK;
+}
+
 // the framed decode calls. lz4: every chunk of `streams` is [u32 block size][LZ4 block] (cldn_hip_decode_lz4)
 static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                          const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
@@ -1644,6 +1694,7 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
                          const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
                          void* points_out, uint64_t out_capacity, int out_loc, bool lz4) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
   if (chunk_sizes && chunk_sizes_loc != CLDN_HIP_HOST && chunk_sizes_loc != CLDN_HIP_DEVICE)
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
   if (n_clouds && (!cloud_points || !stream_offsets)) return fail(CLDN_HIP_ERR_ARG, "NULL offsets / cloud_points");
@@ -1868,8 +1919,7 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   uint32_t st = 0;
   HIP_TRY(hipMemcpyAsync(&st, c->d_status.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (st & ST_LZ4_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed");
-  if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "malformed stage-1 stream (truncated, bad chunk size, bad mode or trailing bytes)");
+  if ((rc = decode_verdict(st)) != CLDN_HIP_OK) return rc;
   if (need) HIP_TRY(hipMemcpy(points_out, d_outp, (size_t)need, hipMemcpyDeviceToHost));
   return CLDN_HIP_OK;
 }
@@ -1877,6 +1927,7 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
 int cldn_hip_lz4_decompress(cldn_hip_codec_t* c, const void* blocks, int blocks_loc, const uint64_t* block_offsets, uint32_t n_blocks,
                             void* out, int out_loc, const uint64_t* out_offsets, uint32_t* sizes) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
   if ((blocks_loc != CLDN_HIP_HOST && blocks_loc != CLDN_HIP_DEVICE) || (out_loc != CLDN_HIP_HOST && out_loc != CLDN_HIP_DEVICE))
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
   if (n_blocks == 0) return CLDN_HIP_OK;
@@ -1951,6 +2002,7 @@ int cldn_hip_lz4_decompress(cldn_hip_codec_t* c, const void* blocks, int blocks_
 int cldn_hip_decode_stage1_unframed(cldn_hip_codec_t* c, const void* payload, uint64_t size, int payload_loc,
                                     void* points_out, uint64_t out_capacity, int out_loc) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
   if ((payload_loc != CLDN_HIP_HOST && payload_loc != CLDN_HIP_DEVICE) || (out_loc != CLDN_HIP_HOST && out_loc != CLDN_HIP_DEVICE))
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
   if (c->plan.uses_v5) return fail(CLDN_HIP_ERR_ARG, "unframed streams (wire version 2) never use the V5 codec");
@@ -1992,6 +2044,246 @@ int cldn_hip_decode_stage1_unframed(cldn_hip_codec_t* c, const void* payload, ui
   if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "malformed stage-1 stream (truncated point, or more points than the output holds)");
   if (out_bytes) HIP_TRY(hipMemcpy(points_out, d_outp, (size_t)out_bytes, hipMemcpyDeviceToHost));
   return CLDN_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- audit: per-field error report (audit_kernels.hip) ----
+
+// the schema's fields as the kernel wants them; limit == NULL: a field's resolution, else 0
+static int audit_fields(const cldn_hip_plan& P, const double* limit, std::vector<AuditField>* out) {
+  out->resize(P.fields.size());
+  for (size_t i = 0; i < P.fields.size(); ++i) {
+    const cldn_hip_field_t& f = P.fields[i];
+    const int sz = size_of_type(f.type);
+    if (f.offset == 0xffffffffu) return fail(CLDN_HIP_ERR_ARG, "audit: field %zu is decoded but not stored (kDecodeButSkipStore)", i);
+    if (sz == 0 || (uint64_t)f.offset + (uint64_t)sz > P.point_step)
+      return fail(CLDN_HIP_ERR_ARG, "audit: field %zu (offset %u, %d bytes) exceeds point_step %u", i, f.offset, sz, P.point_step);
+    const double lim = limit ? limit[i] : (f.has_resolution ? (double)f.resolution : 0.0);
+    if (!(lim >= 0.0)) return fail(CLDN_HIP_ERR_ARG, "audit: limit of field %zu must be >= 0 and not NaN", i);
+    AuditField& a = (*out)[i];
+    memset(&a, 0, sizeof(a));
+    a.offset = f.offset;
+    a.size = (uint8_t)sz;
+    a.is_float = (f.type == 7 || f.type == 8) ? 1 : 0;
+    a.limit = lim;
+  }
+  return CLDN_HIP_OK;
+}
+
+static int audit_check_report(const cldn_hip_plan& P, uint32_t n_clouds, const void* report, int report_loc) {
+  if (report_loc != CLDN_HIP_HOST && report_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  if (n_clouds && !P.fields.empty() && !report) return fail(CLDN_HIP_ERR_ARG, "audit: report is NULL");
+  if (report_loc == CLDN_HIP_DEVICE && ((uintptr_t)report & 7u)) return fail(CLDN_HIP_ERR_ARG, "audit: a device report must be 8-byte aligned");
+  return CLDN_HIP_OK;
+}
+
+// two device buffers -> report: tables up, one clear, one kernel; HOST report: one copy, one synchronisation
+static int audit_device(cldn_hip_codec* c, const uint8_t* d_a, const uint8_t* d_b, const uint64_t* cloud_points, uint32_t n_clouds,
+                        const std::vector<AuditField>& fields, cldn_hip_audit_field_t* report, int report_loc) {
+  static_assert(sizeof(cldn_hip_audit_field_t) == 40, "five 64-bit words");
+  const uint32_t n_fields = (uint32_t)fields.size();
+  const size_t rep_bytes = (size_t)n_clouds * n_fields * sizeof(cldn_hip_audit_field_t);
+  if (rep_bytes == 0) return CLDN_HIP_OK;
+  int rc;
+  uint64_t n_blocks64 = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) n_blocks64 += (cloud_points[k] + kAuditBlockPoints - 1u) / kAuditBlockPoints;
+  if (n_blocks64 > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "audit: more than 2^31 blocks of 1024 points");
+  const uint32_t n_blocks = (uint32_t)n_blocks64;
+  const bool dev_fields = n_fields > kAuditArgFields;
+  const size_t clouds_b = ((size_t)n_clouds * sizeof(AuditCloud) + 63u) & ~size_t(63);
+  const size_t blocks_b = ((size_t)n_blocks * sizeof(AuditBlock) + 63u) & ~size_t(63);
+  const size_t fields_b = dev_fields ? ((size_t)n_fields * sizeof(AuditField) + 63u) & ~size_t(63) : 0u;
+  if (c->ev_audit) HIP_TRY(hipEventSynchronize(c->ev_audit));  // the previous call's upload has left the staging buffer
+  else HIP_TRY(hipEventCreateWithFlags(&c->ev_audit, hipEventDisableTiming));
+  if ((rc = c->h_audit.ensure(clouds_b + blocks_b + fields_b)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_audit_tab.ensure(clouds_b + blocks_b + fields_b)) != CLDN_HIP_OK) return rc;
+  AuditCloud* hc = (AuditCloud*)c->h_audit.p;
+  AuditBlock* hb = (AuditBlock*)((uint8_t*)c->h_audit.p + clouds_b);
+  uint64_t first = 0;
+  uint32_t bi = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) {
+    hc[k].first_point = first;
+    hc[k].n_points = cloud_points[k];
+    const uint32_t nb = (uint32_t)((cloud_points[k] + kAuditBlockPoints - 1u) / kAuditBlockPoints);
+    for (uint32_t j = 0; j < nb; ++j) {
+      hb[bi].cloud = k;
+      hb[bi].block = j;
+      ++bi;
+    }
+    first += cloud_points[k];
+  }
+  if (dev_fields) memcpy((uint8_t*)c->h_audit.p + clouds_b + blocks_b, fields.data(), (size_t)n_fields * sizeof(AuditField));
+  HIP_TRY(hipMemcpyAsync(c->d_audit_tab.p, c->h_audit.p, clouds_b + blocks_b + fields_b, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->ev_audit, c->stream));
+  unsigned long long* d_rep = (unsigned long long*)report;
+  if (report_loc == CLDN_HIP_HOST) {
+    if ((rc = c->d_audit_rep.ensure(rep_bytes)) != CLDN_HIP_OK) return rc;
+    d_rep = (unsigned long long*)c->d_audit_rep.p;
+  }
+  AuditLaunch L;
+  L.stream = c->stream;
+  L.a = d_a;
+  L.b = d_b;
+  L.point_step = c->plan.point_step;
+  L.n_clouds = n_clouds;
+  L.n_blocks = n_blocks;
+  L.n_fields = n_fields;
+  L.fields = fields.data();
+  L.dev_fields = dev_fields ? (const AuditField*)((const uint8_t*)c->d_audit_tab.p + clouds_b + blocks_b) : nullptr;
+  L.clouds = (const AuditCloud*)c->d_audit_tab.p;
+  L.blocks = (const AuditBlock*)((const uint8_t*)c->d_audit_tab.p + clouds_b);
+  L.report = d_rep;
+  if ((rc = audit_launch(L)) != CLDN_HIP_OK) return rc;
+  if (report_loc == CLDN_HIP_HOST) {
+    HIP_TRY(hipMemcpyAsync(report, d_rep, rep_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return CLDN_HIP_OK;
+}
+
+static int audit_batch_points(const uint64_t* cloud_points, uint32_t n_clouds, uint64_t* total) {
+  if (n_clouds && !cloud_points) return fail(CLDN_HIP_ERR_ARG, "cloud_points is NULL");
+  uint64_t n = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) n += cloud_points[k];
+  *total = n;
+  return CLDN_HIP_OK;
+}
+
+// `points` against the decode of `streams`. d_audit: [host points | decode, zero-filled | host streams]
+static int audit_streams_impl(cldn_hip_codec* c, const void* points, int points_loc, const void* streams, int streams_loc,
+                              const uint64_t* stream_offsets, const uint64_t* cloud_points, uint32_t n_clouds, int stream_kind,
+                              const double* limit, cldn_hip_audit_field_t* report, int report_loc) {
+  if ((points_loc != CLDN_HIP_HOST && points_loc != CLDN_HIP_DEVICE) || (streams_loc != CLDN_HIP_HOST && streams_loc != CLDN_HIP_DEVICE))
+    return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  if (stream_kind != CLDN_HIP_STAGE2_NONE && stream_kind != CLDN_HIP_STAGE2_LZ4)
+    return fail(CLDN_HIP_ERR_ARG, "audit_streams: stream_kind %d is neither framed stage-1 streams (0) nor LZ4 chunks (1)", stream_kind);
+  int rc;
+  if ((rc = audit_check_report(c->plan, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  std::vector<AuditField> fields;
+  if ((rc = audit_fields(c->plan, limit, &fields)) != CLDN_HIP_OK) return rc;
+  uint64_t n_points = 0;
+  if ((rc = audit_batch_points(cloud_points, n_clouds, &n_points)) != CLDN_HIP_OK) return rc;
+  if (n_clouds == 0) return CLDN_HIP_OK;
+  if (!stream_offsets) return fail(CLDN_HIP_ERR_ARG, "NULL offsets / cloud_points");
+  for (uint32_t k = 0; k < n_clouds; ++k)
+    if (stream_offsets[k + 1] < stream_offsets[k]) return fail(CLDN_HIP_ERR_ARG, "stream_offsets must be ascending");
+  if (n_points && !points) return fail(CLDN_HIP_ERR_ARG, "points is NULL");
+  const uint64_t s0 = stream_offsets[0], s_bytes = stream_offsets[n_clouds] - s0;
+  if (s_bytes && !streams) return fail(CLDN_HIP_ERR_ARG, "streams is NULL");
+  ENTER_DEVICE(c->device);
+  const uint64_t bytes = n_points * c->plan.point_step;
+  const size_t pts_b = points_loc == CLDN_HIP_HOST ? ((size_t)bytes + 255u) & ~size_t(255) : 0u;
+  const size_t dec_b = ((size_t)bytes + 255u) & ~size_t(255);
+  const size_t str_b = streams_loc == CLDN_HIP_HOST ? (size_t)s_bytes : 0u;
+  if ((rc = c->d_audit.ensure(std::max<size_t>(256, pts_b + dec_b + str_b))) != CLDN_HIP_OK) return rc;
+  uint8_t* base = (uint8_t*)c->d_audit.p;
+  const uint8_t* d_points = (const uint8_t*)points;
+  if (points_loc == CLDN_HIP_HOST) {
+    if (bytes) HIP_TRY(hipMemcpyAsync(base, points, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    d_points = base;
+  }
+  uint8_t* d_dec = base + pts_b;
+  if (bytes) HIP_TRY(hipMemsetAsync(d_dec, 0, (size_t)bytes, c->stream));
+  std::vector<uint64_t> rel(stream_offsets, stream_offsets + n_clouds + 1);
+  for (uint64_t& o : rel) o -= s0;
+  const uint8_t* d_streams = (const uint8_t*)streams + s0;
+  if (streams_loc == CLDN_HIP_HOST) {
+    if (s_bytes) HIP_TRY(hipMemcpyAsync(base + pts_b + dec_b, (const uint8_t*)streams + s0, (size_t)s_bytes, hipMemcpyHostToDevice, c->stream));
+    d_streams = base + pts_b + dec_b;
+  }
+  if ((rc = decode_framed(c, d_streams, CLDN_HIP_DEVICE, rel.data(), cloud_points, n_clouds, nullptr, CLDN_HIP_HOST, d_dec, bytes,
+                          CLDN_HIP_DEVICE, stream_kind == CLDN_HIP_STAGE2_LZ4)) != CLDN_HIP_OK)
+    return rc;
+  // the decode's verdict before the report is touched (also: the host buffers of this call have been read)
+  uint32_t st = 0;
+  HIP_TRY(hipMemcpyAsync(&st, c->d_status.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if ((rc = decode_verdict(st)) != CLDN_HIP_OK) return rc;
+  return audit_device(c, d_points, d_dec, cloud_points, n_clouds, fields, report, report_loc);
+}
+
+extern "C" {
+
+int cldn_hip_audit_clouds(cldn_hip_codec_t* c, const void* a, int a_loc, const void* b, int b_loc, const uint64_t* cloud_points,
+                          uint32_t n_clouds, const double* limit, cldn_hip_audit_field_t* report, int report_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
+  if ((a_loc != CLDN_HIP_HOST && a_loc != CLDN_HIP_DEVICE) || (b_loc != CLDN_HIP_HOST && b_loc != CLDN_HIP_DEVICE))
+    return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  int rc;
+  if ((rc = audit_check_report(c->plan, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  std::vector<AuditField> fields;
+  if ((rc = audit_fields(c->plan, limit, &fields)) != CLDN_HIP_OK) return rc;
+  uint64_t n_points = 0;
+  if ((rc = audit_batch_points(cloud_points, n_clouds, &n_points)) != CLDN_HIP_OK) return rc;
+  if (n_points && (!a || !b)) return fail(CLDN_HIP_ERR_ARG, "audit_clouds: NULL buffer");
+  ENTER_DEVICE(c->device);
+  const uint64_t bytes = n_points * c->plan.point_step;
+  const size_t one = ((size_t)bytes + 255u) & ~size_t(255);
+  const uint8_t* d_a = (const uint8_t*)a;
+  const uint8_t* d_b = (const uint8_t*)b;
+  const bool up_a = a_loc == CLDN_HIP_HOST && bytes, up_b = b_loc == CLDN_HIP_HOST && bytes;
+  if (up_a || up_b) {
+    if ((rc = c->d_audit.ensure(one * ((up_a ? 1u : 0u) + (up_b ? 1u : 0u)))) != CLDN_HIP_OK) return rc;
+    uint8_t* at = (uint8_t*)c->d_audit.p;
+    if (up_a) {
+      HIP_TRY(hipMemcpyAsync(at, a, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+      d_a = at;
+      at += one;
+    }
+    if (up_b) {
+      HIP_TRY(hipMemcpyAsync(at, b, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+      d_b = at;
+    }
+  }
+  rc = audit_device(c, d_a, d_b, cloud_points, n_clouds, fields, report, report_loc);
+  // (pageable host buffers: the call does not return while a copy may still read them)
+  if (rc == CLDN_HIP_OK && (up_a || up_b) && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
+  return rc;
+}
+
+int cldn_hip_audit_streams(cldn_hip_codec_t* c, const void* points, int points_loc, const void* streams, int streams_loc,
+                           const uint64_t* stream_offsets, const uint64_t* cloud_points, uint32_t n_clouds, int stream_kind,
+                           const double* limit, cldn_hip_audit_field_t* report, int report_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
+  return audit_streams_impl(c, points, points_loc, streams, streams_loc, stream_offsets, cloud_points, n_clouds, stream_kind, limit,
+                            report, report_loc);
+}
+
+int64_t cldn_hip_audit_last_encode_clouds(const cldn_hip_codec_t* c) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (!c->enc.valid)
+    return fail(CLDN_HIP_ERR_ARG, "audit_last_encode: no encode call to audit (an encode call must be this codec's last call that touched buffers; "
+                                  "a chunk table must have been framed)");
+  return (int64_t)c->enc.cloud_points.size();
+}
+
+int cldn_hip_audit_last_encode(cldn_hip_codec_t* c, const double* limit, cldn_hip_audit_field_t* report, int report_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (cldn_hip_audit_last_encode_clouds(c) < 0) return CLDN_HIP_ERR_ARG;
+  cldn_hip_codec::LastEncode E = c->enc;  // (the decode below drops the codec's copy)
+  const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
+  if (n_clouds == 0) return CLDN_HIP_OK;
+  uint64_t n_points = 0;
+  for (uint64_t n : E.cloud_points) n_points += n;
+  if (n_points == 0) {  // nothing was launched and nothing written: empty streams
+    E.streams = nullptr;
+    E.offsets.assign((size_t)n_clouds + 1, 0);
+  }
+  if (E.offsets.empty()) {  // DEVICE outputs: the encode call has not read its offsets
+    ENTER_DEVICE(c->device);
+    E.offsets.resize((size_t)n_clouds + 1);
+    HIP_TRY(hipMemcpyAsync(E.offsets.data(), E.d_offsets, ((size_t)n_clouds + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < n_clouds; ++k)
+      if (E.offsets[k + 1] < E.offsets[k]) return fail(CLDN_HIP_ERR_DEVICE, "audit_last_encode: the encode call left no valid stream offsets (see cldn_hip_codec_status)");
+  }
+  const int rc = audit_streams_impl(c, E.points, CLDN_HIP_DEVICE, E.streams, CLDN_HIP_DEVICE, E.offsets.data(), E.cloud_points.data(),
+                                    n_clouds, E.kind, limit, report, report_loc);
+  c->enc = E;
+  return rc;
 }
 
 }  // extern "C"

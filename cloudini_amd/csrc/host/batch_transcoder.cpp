@@ -322,10 +322,20 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       if (run.stage1.size() < bytes) run.stage1.resize(bytes + bytes / 8);
       return run.stage1.data();
     };
+    Cloudini::amd_detail::AuditRequest audit;
+    std::vector<double> audit_limit;
+    if (opt.audit) {
+      for (const Cloudini::PointField& f : info0.fields) {
+        const auto named = opt.audit_limits.find(f.name);
+        audit_limit.push_back(named != opt.audit_limits.end() ? named->second : (f.resolution ? (double)*f.resolution : 0.0));
+      }
+      audit.limit = audit_limit.data();
+    }
+    Cloudini::amd_detail::AuditRequest* const audit_p = opt.audit ? &audit : nullptr;
     const auto t_gpu = Clock::now();
     if (b.parsed[r0].viz) {
       Cloudini::amd_detail::encodeStage1BatchViz(info0, ptrs.data(), pts.data(), run.count, b.parsed[r0].viz_xyz_offset,
-                                                 b.parsed[r0].viz_resolution, grow, run.offsets, run.chunk_sizes, kept);
+                                                 b.parsed[r0].viz_resolution, grow, run.offsets, run.chunk_sizes, kept, audit_p);
       for (uint32_t k = 0; k < run.count; ++k) {  // what the reference's function leaves behind (src/ros_msg_utils.cpp:326-335)
         Parsed& p = b.parsed[r0 + k];
         p.points = kept[k];
@@ -340,7 +350,31 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
         if (stats) stats->points += kept[k];
       }
     } else {
-      Cloudini::amd_detail::encodeStage1Batch(info0, ptrs.data(), pts.data(), run.count, grow, run.offsets, run.chunk_sizes);
+      Cloudini::amd_detail::encodeStage1Batch(info0, ptrs.data(), pts.data(), run.count, grow, run.offsets, run.chunk_sizes, audit_p);
+    }
+    if (opt.audit && stats) {  // the run's report, message by message, into the per-name summary
+      const size_t nf = info0.fields.size();
+      std::vector<AuditFieldSummary> part(nf);
+      for (size_t f = 0; f < nf; ++f) {
+        part[f].name = info0.fields[f].name;
+        part[f].is_float = info0.fields[f].type == Cloudini::FieldType::FLOAT32 || info0.fields[f].type == Cloudini::FieldType::FLOAT64;
+      }
+      for (uint32_t k = 0; k < run.count; ++k)
+        for (size_t f = 0; f < nf; ++f) {
+          const cldn_hip_audit_field_t& rec = audit.report[(size_t)k * nf + f];
+          AuditFieldSummary one = part[f];
+          one.n_bitwise_diff = rec.n_bitwise_diff;
+          one.n_class_diff = rec.n_class_diff;
+          one.n_over_limit = rec.n_over_limit;
+          one.max_abs_err = rec.max_abs_err;
+          one.first_bad_message.clear();
+          one.first_bad_order = UINT64_MAX;
+          if (one.bad()) {
+            one.first_bad_message = b.in[r0 + k].name;
+            one.first_bad_order = (b.seq << 32) | (uint64_t)(r0 + k);
+          }
+          stats->mergeAudit({one});
+        }
     }
     if (stats) {
       stats->seconds_gpu += since(t_gpu);
@@ -588,6 +622,27 @@ void decodeWrapPhase(Batch& b, TranscodeStats* stats) {
 
 }  // namespace
 
+void TranscodeStats::mergeAudit(const std::vector<AuditFieldSummary>& other) {
+  for (const AuditFieldSummary& o : other) {
+    AuditFieldSummary* mine = nullptr;
+    for (AuditFieldSummary& f : audit)
+      if (f.name == o.name) mine = &f;
+    if (!mine) {
+      audit.push_back(o);
+      continue;
+    }
+    mine->is_float = mine->is_float || o.is_float;
+    mine->n_bitwise_diff += o.n_bitwise_diff;
+    mine->n_class_diff += o.n_class_diff;
+    mine->n_over_limit += o.n_over_limit;
+    mine->max_abs_err = std::max(mine->max_abs_err, o.max_abs_err);
+    if (o.first_bad_order < mine->first_bad_order) {
+      mine->first_bad_order = o.first_bad_order;
+      mine->first_bad_message = o.first_bad_message;
+    }
+  }
+}
+
 void transcodeBatch(const std::vector<Message>& in, const TranscodeOptions& opt, std::vector<std::vector<uint8_t>>& out,
                     TranscodeStats* stats) {
   Batch b;
@@ -762,6 +817,7 @@ TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, co
         stats.input_bytes += mine.input_bytes;
         stats.gpu_batches += mine.gpu_batches;
         stats.seconds_gpu += mine.seconds_gpu;
+        stats.mergeAudit(mine.audit);
       }
       if (gpu_workers_left.fetch_sub(1) == 1) to_stage2.close();
     });

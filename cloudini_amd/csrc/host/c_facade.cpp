@@ -113,6 +113,61 @@ CLDN_EXPORT int64_t cldn_amd_transcode_directory_on(const char* in_dir, const ch
   });
 }
 
+// the audit summary as one line of JSON (a list of objects, one per field name)
+static std::string auditJson(const cloudini_amd::TranscodeStats& st) {
+  auto quoted = [](const std::string& s) {
+    std::string q = "\"";
+    for (char ch : s) {
+      if (ch == '"' || ch == '\\') q += '\\';
+      q += (unsigned char)ch < 0x20 ? ' ' : ch;
+    }
+    return q + "\"";
+  };
+  std::string out = "[";
+  for (size_t i = 0; i < st.audit.size(); ++i) {
+    const cloudini_amd::AuditFieldSummary& f = st.audit[i];
+    char num[256];
+    std::snprintf(num, sizeof num, "\"is_float\": %s, \"n_bitwise_diff\": %llu, \"n_class_diff\": %llu, \"n_over_limit\": %llu, ",
+                  f.is_float ? "true" : "false", (unsigned long long)f.n_bitwise_diff, (unsigned long long)f.n_class_diff,
+                  (unsigned long long)f.n_over_limit);
+    char err[64];
+    if (f.max_abs_err > 1.7976931348623157e308) std::snprintf(err, sizeof err, "Infinity");
+    else std::snprintf(err, sizeof err, "%.17g", f.max_abs_err);
+    out += std::string(i ? ", " : "") + "{\"name\": " + quoted(f.name) + ", " + num + "\"max_abs_err\": " + err +
+           ", \"first_bad_message\": " + (f.first_bad_message.empty() ? std::string("null") : quoted(f.first_bad_message)) + "}";
+  }
+  return out + "]";
+}
+
+CLDN_EXPORT int64_t cldn_amd_transcode_directory_audit(const char* in_dir, const char* out_dir, float resolution,
+                                                       uint8_t compression_opt, int viz_lossy, uint32_t batch_messages,
+                                                       const int32_t* devices, uint32_t n_devices, const char* const* limit_names,
+                                                       const double* limit_values, uint32_t n_limits, double* stats_out,
+                                                       char* audit_json, uint64_t audit_capacity) {
+  return guarded([&] {
+    cloudini_amd::DirectorySource source(in_dir);
+    cloudini_amd::DirectorySink sink(out_dir);
+    cloudini_amd::TranscodeOptions opt;
+    opt.default_resolution = resolution;
+    opt.compression = static_cast<Cloudini::CompressionOption>(compression_opt);
+    opt.viz_lossy = viz_lossy != 0;
+    if (batch_messages) opt.batch_messages = batch_messages;
+    if (devices) opt.devices.assign(devices, devices + n_devices);
+    opt.audit = true;
+    for (uint32_t i = 0; i < n_limits; ++i) opt.audit_limits[limit_names[i]] = limit_values[i];
+    const cloudini_amd::TranscodeStats st = cloudini_amd::transcodePointClouds(source, sink, opt);
+    if (stats_out) {
+      const double v[8] = {(double)st.messages,    (double)st.points,  (double)st.input_bytes, (double)st.output_bytes,
+                           (double)st.gpu_batches, st.seconds_total, st.seconds_gpu,         st.seconds_stage2};
+      for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
+    }
+    const std::string json = auditJson(st);
+    if (json.size() + 1 > audit_capacity) throw std::runtime_error("transcode_directory_audit: the summary needs " + std::to_string(json.size() + 1) + " bytes");
+    std::memcpy(audit_json, json.c_str(), json.size() + 1);
+    return (int64_t)st.messages;
+  });
+}
+
 CLDN_EXPORT int64_t cldn_amd_transcode_directory(const char* in_dir, const char* out_dir, float resolution,
                                                  uint8_t compression_opt, int viz_lossy, uint32_t batch_messages,
                                                  double* stats_out) {

@@ -1032,9 +1032,16 @@ std::atomic<bool> g_device_lz4_decode{false};
 bool deviceLz4Decode() { return g_device_lz4_decode.load(); }
 void setDeviceLz4Decode(bool on) { g_device_lz4_decode.store(on); }
 
+// the encode call the codec has just made, audited where its points and streams lie (include/cloudini_hip.h)
+static int auditLastEncode(cldn_hip_codec_t* codec, const EncodingInfo& info, uint32_t n_clouds, AuditRequest* audit) {
+  audit->report.assign((size_t)n_clouds * info.fields.size(), cldn_hip_audit_field_t{});
+  if (audit->report.empty()) return CLDN_HIP_OK;
+  return cldn_hip_audit_last_encode(codec, audit->limit, audit->report.data(), CLDN_HIP_HOST);
+}
+
 void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
-                       std::vector<uint32_t>& chunk_sizes) {
+                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1048,6 +1055,7 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
     const uint64_t total = stream_offsets[n_clouds];
     rc = cldn_hip_codec_fetch_output(codec, total ? grow(total) : nullptr, total);
   }
+  if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
   pool().release(info, codec);
   if (rc != CLDN_HIP_OK) throw std::runtime_error(err);
@@ -1057,7 +1065,7 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
 void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
-                          std::vector<uint64_t>& kept_points) {
+                          std::vector<uint64_t>& kept_points, AuditRequest* audit) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;  // of the input: an upper bound of what the filtered clouds have
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1072,6 +1080,7 @@ void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_
     const uint64_t total = stream_offsets[n_clouds];
     rc = cldn_hip_codec_fetch_output(codec, total ? grow(total) : nullptr, total);
   }
+  if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
   pool().release(info, codec);
   if (rc != CLDN_HIP_OK) throw std::runtime_error(err);

@@ -5,6 +5,7 @@
 #include <functional>
 #include <vector>
 
+#include "cloudini_hip.h"
 #include "cloudini_lib/cloudini.hpp"
 
 namespace Cloudini {
@@ -26,16 +27,23 @@ uint64_t vizPreprocessOnDevice(const uint8_t* points, size_t n_points, uint32_t 
 // chunk_sizes one payload size per chunk in batch order. Throws std::runtime_error.
 // `grow(bytes)` is called once with the exact size of the batch's streams and returns where they go (page-locked memory
 // makes the copy back fast).
+// `audit` (optional): behind the encode call the codec audits it on the device (cldn_hip_audit_last_encode: the points it
+// staged against the decode of the streams it wrote); limit = NULL or info.fields.size() doubles, report receives
+// n_clouds * info.fields.size() records.
+struct AuditRequest {
+  const double* limit = nullptr;
+  std::vector<cldn_hip_audit_field_t> report;
+};
 void encodeStage1Batch(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
-                       std::vector<uint32_t>& chunk_sizes);
+                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit = nullptr);
 // The same behind the viz pre-filter (cldn_hip_encode_stage1_viz_gather): every cloud is filtered on its own, the survivors
 // are encoded without leaving the device. kept_points gets n_clouds survivor counts; stream_offsets and chunk_sizes describe
 // the filtered clouds (a cloud that loses every point has an empty stream and no chunk).
 void encodeStage1BatchViz(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
-                          std::vector<uint64_t>& kept_points);
+                          std::vector<uint64_t>& kept_points, AuditRequest* audit = nullptr);
 // detail::CompressChunk (src/codec_common.cpp:220-258) and its worst-case output size
 uint32_t compressChunkTo(Cloudini::CompressionOption opt, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_cap);
 size_t compressedChunkBound(Cloudini::CompressionOption opt, size_t stage1_bytes);

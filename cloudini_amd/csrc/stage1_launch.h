@@ -284,4 +284,42 @@ struct VizLaunch {
 uint64_t viz_table_capacity(uint64_t n_points);
 int viz_launch(const VizLaunch& L);
 
+// ---- per-field error report of two point buffers (audit_kernels.hip; record: cldn_hip_audit_field_t, five 64-bit words) ----
+constexpr uint32_t kAuditBlockPoints = 1024;  // points per workgroup; blocks are cut per cloud, a cloud's last one may be partial
+constexpr uint32_t kAuditStagedStep = 127;    // widest point that goes through LDS (at least 256 points per stage), wider ones are read in place
+constexpr uint32_t kAuditLdsBytes = 65536 - 256;  // dynamic LDS of the staged route: both buffers' stage, next to the reduction records
+constexpr uint32_t kAuditArgFields = 128;     // field table as a kernel argument (kMaxOps + kMaxAdaptive: every ordinary plan), else device memory
+struct AuditField {
+  uint32_t offset;
+  uint8_t size;      // 1, 2, 4, 8
+  uint8_t is_float;  // FLOAT32 / FLOAT64: compared as numbers as well as bytes
+  uint8_t pad[2];
+  double limit;      // >= 0
+};
+static_assert(sizeof(AuditField) == 16, "128 of them are a kernel argument");
+struct AuditCloud {
+  uint64_t first_point;  // of the cloud in the batch
+  uint64_t n_points;
+};
+struct AuditBlock {
+  uint32_t cloud;
+  uint32_t block;        // of the cloud: its first point is block * kAuditBlockPoints (cloud-local)
+};
+struct AuditLaunch {
+  hipStream_t stream;
+  const uint8_t* a;              // device AoS, clouds back to back, any alignment
+  const uint8_t* b;
+  uint32_t point_step;
+  uint32_t n_clouds;
+  uint32_t n_blocks;
+  uint32_t n_fields;
+  const AuditField* fields;      // HOST [n_fields]
+  const AuditField* dev_fields;  // device copy of it, or NULL when n_fields <= kAuditArgFields
+  const AuditCloud* clouds;      // device [n_clouds]
+  const AuditBlock* blocks;      // device [n_blocks]
+  unsigned long long* report;    // device [n_clouds * n_fields * 5], 8-byte aligned: cleared, then filled
+};
+uint32_t audit_stage_points(uint32_t point_step);  // points per LDS stage, 0 = the direct route
+int audit_launch(const AuditLaunch& L);            // one clear + one kernel
+
 }  // namespace cldn

@@ -151,6 +151,14 @@ def lib() -> C.CDLL:
     L.cldn_hip_lz4_decompress.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int, u64p, vp]
     L.cldn_hip_decode_lz4.restype = C.c_int
     L.cldn_hip_decode_lz4.argtypes = [vp, vp, C.c_int, u64p, u64p, C.c_uint32, vp, C.c_uint64, C.c_int]
+    L.cldn_hip_audit_clouds.restype = C.c_int
+    L.cldn_hip_audit_clouds.argtypes = [vp, vp, C.c_int, vp, C.c_int, u64p, C.c_uint32, vp, vp, C.c_int]
+    L.cldn_hip_audit_streams.restype = C.c_int
+    L.cldn_hip_audit_streams.argtypes = [vp, vp, C.c_int, vp, C.c_int, u64p, u64p, C.c_uint32, C.c_int, vp, vp, C.c_int]
+    L.cldn_hip_audit_last_encode.restype = C.c_int
+    L.cldn_hip_audit_last_encode.argtypes = [vp, vp, vp, C.c_int]
+    L.cldn_hip_audit_last_encode_clouds.restype = C.c_int64
+    L.cldn_hip_audit_last_encode_clouds.argtypes = [vp]
     _lib = L
     return L
 
@@ -176,6 +184,22 @@ def _fields_array(info):
     return arr
 
 
+# cldn_hip_audit_field_t: one record per (cloud, field)
+AUDIT_DTYPE = np.dtype([("n_bitwise_diff", "<u8"), ("n_class_diff", "<u8"), ("n_over_limit", "<u8"), ("first_bad_point", "<u8"),
+                        ("max_abs_err", "<f8")])
+AUDIT_NONE = 0xFFFFFFFFFFFFFFFF
+
+
+def _limit_ptr(limit, n_fields: int):
+    """(keep-alive array, pointer) of an audit call's `limit`: None = the defaults (a field's resolution, else 0)."""
+    if limit is None:
+        return None, None
+    lim = np.ascontiguousarray(limit, dtype=np.float64)
+    if lim.size != n_fields:
+        raise ValueError(f"limit has {lim.size} entries, the schema has {n_fields} fields")
+    return lim, lim.ctypes.data_as(C.c_void_p)
+
+
 class Plan:
     """cldn_hip_plan_t: the encoder/decoder selection for an EncodingInfo."""
 
@@ -185,6 +209,7 @@ class Plan:
         _check(lib().cldn_hip_plan_create(arr, len(info.fields), int(info.point_step), int(info.version),
                                           int(info.encoding_opt), C.byref(self._h)))
         self.point_step = int(info.point_step)
+        self.n_fields = len(info.fields)
 
     def __del__(self):
         if getattr(self, "_h", None) and self._h.value and _lib is not None:
@@ -519,3 +544,80 @@ class Codec:
         _check(lib().cldn_hip_decode_lz4(
             self._h, C.c_void_p(streams_ptr), DEVICE, so.ctypes.data_as(C.POINTER(C.c_uint64)),
             cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, C.c_void_p(out_ptr), int(out_capacity), DEVICE))
+
+    # ---- audit: per-field error reports (cldn_hip_audit_*) -----------------------------------------------------------
+    def _audit_report(self, n_clouds: int) -> np.ndarray:
+        rep = np.zeros((int(n_clouds), self.plan.n_fields), dtype=AUDIT_DTYPE)
+        rep.view(np.uint8)[...] = 0xEE  # (a call that fails leaves it as it was)
+        return rep
+
+    def audit_clouds_host(self, a: Sequence[np.ndarray], b: Sequence[np.ndarray], limit=None, report: Optional[np.ndarray] = None):
+        """cldn_hip_audit_clouds on host buffers: clouds a[k] against b[k]. Returns the (n_clouds, n_fields) report."""
+        step = self.plan.point_step
+        aa = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in a]
+        bb = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in b]
+        if [x.size for x in aa] != [x.size for x in bb] or any(x.size % step for x in aa):
+            raise ValueError("the two batches must have the same whole number of points per cloud")
+        cp = np.array([x.size // step for x in aa], dtype=np.uint64)
+        da, db = np.concatenate(aa + [np.zeros(1, np.uint8)]), np.concatenate(bb + [np.zeros(1, np.uint8)])
+        rep = self._audit_report(len(aa)) if report is None else report
+        lim, lp = _limit_ptr(limit, self.plan.n_fields)
+        _check(lib().cldn_hip_audit_clouds(self._h, da.ctypes.data_as(C.c_void_p), HOST, db.ctypes.data_as(C.c_void_p), HOST,
+                                           cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, lp, rep.ctypes.data_as(C.c_void_p), HOST))
+        return rep
+
+    def audit_clouds_device(self, a_ptr: int, b_ptr: int, cloud_points, limit=None, report_ptr: int = 0, a_loc: int = DEVICE,
+                            b_loc: int = DEVICE):
+        """cldn_hip_audit_clouds on raw pointers. report_ptr: device array of n_clouds * n_fields records (the call only
+        enqueues work when both buffers are on the device; returns None), 0 = host report (returned)."""
+        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
+        lim, lp = _limit_ptr(limit, self.plan.n_fields)
+        rep = None if report_ptr else self._audit_report(cp.size)
+        _check(lib().cldn_hip_audit_clouds(self._h, C.c_void_p(a_ptr), a_loc, C.c_void_p(b_ptr), b_loc,
+                                           cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, lp,
+                                           C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                           DEVICE if report_ptr else HOST))
+        return rep
+
+    def audit_streams_host(self, clouds: Sequence[np.ndarray], streams: Sequence[np.ndarray], stream_kind: int = 0, limit=None,
+                           report: Optional[np.ndarray] = None):
+        """cldn_hip_audit_streams on host buffers: clouds[k] against the decode of streams[k] (stream_kind 0: framed stage-1
+        streams, 1: [u32 size][LZ4 block] per chunk)."""
+        step = self.plan.point_step
+        pts = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in clouds]
+        ss = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in streams]
+        cp = np.array([x.size // step for x in pts], dtype=np.uint64)
+        offs = np.zeros(len(ss) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([x.size for x in ss])
+        dp, ds = np.concatenate(pts + [np.zeros(1, np.uint8)]), np.concatenate(ss + [np.zeros(1, np.uint8)])
+        rep = self._audit_report(len(pts)) if report is None else report
+        lim, lp = _limit_ptr(limit, self.plan.n_fields)
+        _check(lib().cldn_hip_audit_streams(self._h, dp.ctypes.data_as(C.c_void_p), HOST, ds.ctypes.data_as(C.c_void_p), HOST,
+                                            offs.ctypes.data_as(C.POINTER(C.c_uint64)), cp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                            cp.size, int(stream_kind), lp, rep.ctypes.data_as(C.c_void_p), HOST))
+        return rep
+
+    def audit_streams_device(self, points_ptr: int, streams_ptr: int, stream_offsets, cloud_points, stream_kind: int = 0,
+                             limit=None, report_ptr: int = 0):
+        """The same on device buffers; report_ptr as in audit_clouds_device."""
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
+        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
+        lim, lp = _limit_ptr(limit, self.plan.n_fields)
+        rep = None if report_ptr else self._audit_report(cp.size)
+        _check(lib().cldn_hip_audit_streams(self._h, C.c_void_p(points_ptr), DEVICE, C.c_void_p(streams_ptr), DEVICE,
+                                            so.ctypes.data_as(C.POINTER(C.c_uint64)), cp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                            cp.size, int(stream_kind), lp,
+                                            C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                            DEVICE if report_ptr else HOST))
+        return rep
+
+    def audit_last_encode(self, limit=None, report_ptr: int = 0):
+        """cldn_hip_audit_last_encode: this codec's most recent encode call against the decode of what it wrote; one row per
+        cloud of that call (the filtered clouds of a viz call). Raises CloudiniHipError (ARG) when another call came between."""
+        n = int(lib().cldn_hip_audit_last_encode_clouds(self._h))
+        _check(n)
+        lim, lp = _limit_ptr(limit, self.plan.n_fields)
+        rep = None if report_ptr else self._audit_report(n)
+        _check(lib().cldn_hip_audit_last_encode(self._h, lp, C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                                DEVICE if report_ptr else HOST))
+        return rep

@@ -22,6 +22,7 @@
 #include <cstdint>
 #include <new>
 #include <functional>
+#include <map>
 #include <optional>
 #include <string>
 #include <utility>
@@ -144,11 +145,29 @@ struct TranscodeOptions {
   // ordered writer; batches go to whichever GPU stage is free. Empty = the calling thread's current device. The same
   // device may be listed more than once (two batches in flight on one GPU).
   std::vector<int> devices;
+  // Audit (include/cloudini_hip.h, cldn_hip_audit_last_encode): behind the encode call of every schema run the GPU stage
+  // compares the points it encoded (with viz_lossy: the survivors) with the decode of the streams it wrote, on the device, and
+  // adds the per-field report to TranscodeStats::audit. The output is what it is without the audit. A field's limit is its
+  // resolution (0 for a field without one) unless audit_limits names the field.
+  bool audit = false;
+  std::map<std::string, double> audit_limits;
   // Test hook (tests/cpp/transcoder_order.cpp, runs without a GPU): when set, `test_workers` stage threads call it instead of
   // the GPU stage and stage 2 passes the batch on untouched -- what remains is the pipeline itself: batches handed to
   // whichever stage is free, the writer putting them back into input order, an error on any stage stopping all of them.
   std::function<void(size_t worker, const std::vector<Message>& in, std::vector<std::vector<uint8_t>>& out)> test_stage;
   size_t test_workers = 0;
+};
+
+// One field name over all messages of a run of the transcoder: sums of the report's counters, the largest error, and the first
+// message (input order) with a finding -- a class difference, an error over the limit, or an integer field that changed.
+struct AuditFieldSummary {
+  std::string name;
+  bool is_float = false;
+  uint64_t n_bitwise_diff = 0, n_class_diff = 0, n_over_limit = 0;
+  double max_abs_err = 0;
+  std::string first_bad_message;         // empty = none
+  uint64_t first_bad_order = UINT64_MAX; // position of that message in the input (batch number << 32 | index in the batch)
+  bool bad() const { return n_class_diff != 0 || n_over_limit != 0 || (!is_float && n_bitwise_diff != 0); }
 };
 
 struct TranscodeStats {
@@ -157,6 +176,13 @@ struct TranscodeStats {
   // filter included.
   double seconds_total = 0, seconds_gpu = 0, seconds_stage2 = 0;
   uint64_t gpu_workers = 0;
+  std::vector<AuditFieldSummary> audit;  // TranscodeOptions::audit: one entry per field name, in order of first appearance
+  bool auditClean() const {
+    for (const AuditFieldSummary& f : audit)
+      if (f.bad()) return false;
+    return true;
+  }
+  void mergeAudit(const std::vector<AuditFieldSummary>& other);
 };
 
 template <typename T>

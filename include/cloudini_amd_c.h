@@ -88,6 +88,17 @@ int64_t cldn_amd_transcode_directory_on(const char* in_dir, const char* out_dir,
 int64_t cldn_amd_decode_directory_on(const char* in_dir, const char* out_dir, uint32_t batch_messages, const int32_t* devices,
                                      uint32_t n_devices, double* stats_out);
 
+/* cldn_amd_transcode_directory_on with the audit of every encode call (TranscodeOptions::audit; include/cloudini_hip.h,
+ * cldn_hip_audit_last_encode): the files are the same, audit_json receives the per-field summary as one line of JSON -- a
+ * list of {"name", "is_float", "n_bitwise_diff", "n_class_diff", "n_over_limit", "max_abs_err", "first_bad_message"}, sums
+ * over all messages per field name, first_bad_message = the first message (input order) with a class difference, an error
+ * over the limit or a changed integer field, or null. A field's limit is its resolution (0 without one) unless
+ * limit_names[i] names it: then limit_values[i]. An audit_capacity that is too small is an error (-1). */
+int64_t cldn_amd_transcode_directory_audit(const char* in_dir, const char* out_dir, float resolution, uint8_t compression_opt,
+                                           int viz_lossy, uint32_t batch_messages, const int32_t* devices, uint32_t n_devices,
+                                           const char* const* limit_names, const double* limit_values, uint32_t n_limits,
+                                           double* stats_out, char* audit_json, uint64_t audit_capacity);
+
 /* Stage-2 (LZ4 / ZSTD) threads a single encode()/decode() call with use_threads may occupy, the caller included.
  * The reference's flag means one extra worker (cloudini_lib/src/cloudini.cpp:453-499); here the pool is bounded:
  * default min(4, hardware threads), overridden by the environment variable CLOUDINI_AMD_STAGE2_THREADS (read once)

@@ -315,6 +315,66 @@ int cldn_hip_encode_stage1_viz_gather(cldn_hip_codec_t* codec, const void* const
                                       void* out, uint64_t out_capacity, int out_loc, uint64_t* stream_offsets,
                                       uint32_t* chunk_sizes, uint8_t* modes);
 
+/* Audit of a lossy round trip: what did the codec change, field by field? The report is defined on the SCHEMA (the fields
+ * the plan was created with, in their order), not on the codec's ops; tests/audit_model.py restates it in numpy.
+ * For every cloud k and field f there is one record, report[k * n_fields + f]. a = the first buffer (the original points),
+ * b = the second (the decode). Integer fields are compared as bytes; float fields as bytes AND as numbers, both widened to
+ * double (exact). Bytes of a point that no field covers are never looked at. Two NaNs never disagree as numbers, whatever their
+ * payloads (they do count in n_bitwise_diff when the bits differ). Every quantity is a sum, a min or a max of integers (a
+ * non-negative double orders like its bit pattern): the report is deterministic to the bit. */
+typedef struct cldn_hip_audit_field {
+  uint64_t n_bitwise_diff;  /* points whose field bytes differ */
+  uint64_t n_class_diff;    /* float fields: exactly one side NaN, or either side +-inf and the two bit patterns differ */
+  uint64_t n_over_limit;    /* float fields, both sides finite: |double(a) - double(b)| > limit[f] */
+  uint64_t first_bad_point; /* smallest cloud-local index counted in n_class_diff or n_over_limit, or (non-float fields, and
+                               float fields with limit[f] == 0) in n_bitwise_diff; UINT64_MAX = none */
+  double max_abs_err;       /* max of |double(a) - double(b)| over points with both sides finite; 0 if none */
+} cldn_hip_audit_field_t;   /* 40 bytes */
+
+/* limit: HOST array [n_fields] of doubles (>= 0, not NaN), or NULL for the defaults: a field that has a resolution gets
+ * (double)resolution -- the bound the reference's own message test asserts (test_ros_msg.cpp:80-83) -- every other field 0.
+ * report: [n_clouds * n_fields] records, HOST or DEVICE per report_loc (DEVICE: 8-byte aligned). A field whose offset is
+ * kDecodeButSkipStore, or that reaches beyond point_step, is CLDN_HIP_ERR_ARG. Per call: one clear of the report and ONE kernel,
+ * whatever n_clouds (blocks of <= 1024 points, cut per cloud on the host; one upload of that table, and of the field table
+ * for plans of more than 128 fields); for a HOST report one copy of it and one synchronisation on top. Workspace (grow-only,
+ * the audit's own, d_audit): 8 bytes per 1024-point block + 16 per cloud + the report; host buffers and decodes as said below.
+ *
+ * cldn_hip_audit_clouds: two point buffers of the codec's schema, cloud_points[k] points per cloud, back to back, any byte
+ * alignment. HOST buffers are uploaded into the audit's workspace. With DEVICE buffers and a DEVICE report the call only
+ * enqueues work.
+ *
+ * cldn_hip_audit_streams: `points` against the decode of `streams`. stream_kind = CLDN_HIP_STAGE2_NONE: framed stage-1 streams
+ * (the contract of cldn_hip_decode_stage1); CLDN_HIP_STAGE2_LZ4: [u32 size][LZ4 block] per chunk (cldn_hip_decode_lz4).
+ * stream_offsets: HOST [n_clouds + 1]. The existing decoders write into the audit's workspace, which is filled with zeros
+ * first (the decode fill setting has no part in the verdict); no decoded byte leaves the device. The call reads the decode's
+ * 4-byte status word back and synchronises before it touches the report: a malformed stream returns what the decode call
+ * returns (CLDN_HIP_ERR_CORRUPT) and leaves the report as it was. The codec's input staging and output buffer (what
+ * cldn_hip_codec_fetch_output reads, what cldn_hip_audit_last_encode looks at) are not disturbed.
+ *
+ * cldn_hip_audit_last_encode: the most recent encode call of this codec against the decode of what it wrote --
+ * cldn_hip_encode_stage1, _gather, _viz, _viz_gather, and cldn_hip_encode_stage1_chunks once cldn_hip_frame_chunks has framed
+ * it. The report has one row per cloud of that call. The points are read where they already lie on the device: the codec's
+ * staging for host or gather inputs; the survivors for the viz calls (the filter is intended loss: the audit judges the encode
+ * of the survivors, kept_points[k] points per cloud); for DEVICE inputs the caller's pointer, whose content must be UNCHANGED
+ * SINCE THE ENCODE CALL. The streams are read where the encode left them: the codec's output buffer for host outputs (fetched
+ * or not: cldn_hip_codec_fetch_output before or after makes no difference), the caller's `out` for DEVICE outputs (unchanged
+ * since the call as well). With stage 2 on the device the streams take the LZ4 route. For host outputs the call knows the stream
+ * offsets already; for DEVICE outputs it reads the n_clouds + 1 offsets back (the encode call has not synchronised). Beyond
+ * that, the decode's status word and the report, nothing crosses the bus in either direction but the audit's tables.
+ * The state is dropped by every other call on the codec that encodes, decodes, filters, decompresses or audits buffers
+ * (cldn_hip_audit_last_encode itself may be repeated, e.g. with other limits); calls that only query or set
+ * (cldn_hip_codec_synchronize, _status, _fetch_output, _kernel_ms, _set_*, ...) leave it. Without such a state the call is
+ * CLDN_HIP_ERR_ARG ("audit_last_encode: no encode call to audit ..."). */
+int cldn_hip_audit_clouds(cldn_hip_codec_t* codec, const void* a, int a_loc, const void* b, int b_loc,
+                          const uint64_t* cloud_points, uint32_t n_clouds, const double* limit,
+                          cldn_hip_audit_field_t* report, int report_loc);
+int cldn_hip_audit_streams(cldn_hip_codec_t* codec, const void* points, int points_loc, const void* streams, int streams_loc,
+                           const uint64_t* stream_offsets, const uint64_t* cloud_points, uint32_t n_clouds, int stream_kind,
+                           const double* limit, cldn_hip_audit_field_t* report, int report_loc);
+int cldn_hip_audit_last_encode(cldn_hip_codec_t* codec, const double* limit, cldn_hip_audit_field_t* report, int report_loc);
+/* clouds of the call cldn_hip_audit_last_encode would audit (the rows its report needs), or CLDN_HIP_ERR_ARG */
+int64_t cldn_hip_audit_last_encode_clouds(const cldn_hip_codec_t* codec);
+
 /* What a decode call may do to the bytes of a point that no field covers. CLDN_HIP_FILL_KEEP (default): they keep the
  * content of points_out (src/field_decoder.cpp:72-76 writes fields only) -- for a HOST buffer of a layout with such bytes
  * that means bringing the buffer to the device first. CLDN_HIP_FILL_ZERO: the caller hands over a buffer whose content

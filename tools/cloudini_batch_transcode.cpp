@@ -4,6 +4,10 @@
 // plain directories.
 //   cloudini_batch_transcode <in_dir> <out_dir> [--resolution 0.001] [--compression none|lz4|zstd] [--viz] [--batch 64]
 //   cloudini_batch_transcode <in_dir> <out_dir> --decode [--batch 64]      (CompressedPointCloud2 -> PointCloud2)
+//   ... --audit [--audit-limit name:value ...]   every encode call is audited on the device (the points it encoded against the
+//       decode of what it wrote): one table line per field in front of the JSON line; exit status 3 when a float field changed
+//       class (NaN / inf) or exceeded its limit (its resolution unless --audit-limit names it), or an integer field changed.
+//       The files are written either way, and are the files of a run without --audit.
 //   ... --devices 0,1,2,3   spreads the batches over these GPUs (one GPU stage per entry; "0,0" = two stages on GPU 0)
 //   cloudini_batch_transcode <in.mcap> <out.mcap> [...same options] [--mcap-compression none|lz4|zstd]
 //       a bag: point-cloud messages converted, everything else copied (McapConverter, tools/src/mcap_converter.cpp:141-300);
@@ -16,6 +20,16 @@
 
 #include "cloudini_amd/batch_transcoder.hpp"
 #include "cloudini_amd/mcap_io.hpp"
+
+// one line per field; returns false when the audit has a finding
+static bool printAudit(const cloudini_amd::TranscodeStats& st) {
+  std::printf("audit %-24s %14s %12s %12s %24s  %s\n", "field", "bitwise_diff", "class_diff", "over_limit", "max_abs_err", "first_bad_message");
+  for (const cloudini_amd::AuditFieldSummary& f : st.audit)
+    std::printf("audit %-24s %14llu %12llu %12llu %24.17g  %s\n", f.name.c_str(), (unsigned long long)f.n_bitwise_diff,
+                (unsigned long long)f.n_class_diff, (unsigned long long)f.n_over_limit, f.max_abs_err,
+                f.first_bad_message.empty() ? "-" : f.first_bad_message.c_str());
+  return st.auditClean();
+}
 
 int main(int argc, char** argv) {
   if (argc < 3) {
@@ -35,6 +49,19 @@ int main(int argc, char** argv) {
       mcap_comp = v == "none" ? cloudini_amd::McapCompression::None : (v == "lz4" ? cloudini_amd::McapCompression::Lz4 : cloudini_amd::McapCompression::Zstd);
     }
     else if (a == "--decode") opt.decode = true;
+    else if (a == "--audit") opt.audit = true;
+    else if (a == "--audit-limit" && i + 1 < argc) {
+      const std::string v = argv[++i];
+      const size_t colon = v.rfind(':');
+      char* end = nullptr;
+      const double lim = colon == std::string::npos ? -1.0 : std::strtod(v.c_str() + colon + 1, &end);
+      if (colon == std::string::npos || colon == 0 || end == v.c_str() + colon + 1 || *end || !(lim >= 0.0)) {
+        std::fprintf(stderr, "--audit-limit wants name:value with a value >= 0\n");
+        return 2;
+      }
+      opt.audit_limits[v.substr(0, colon)] = lim;
+      opt.audit = true;
+    }
     else if (a == "--batch" && i + 1 < argc) opt.batch_messages = (size_t)std::strtoul(argv[++i], nullptr, 10);
     else if (a == "--devices" && i + 1 < argc) {
       for (const char* p = argv[++i]; *p;) {
@@ -56,6 +83,7 @@ int main(int argc, char** argv) {
     const std::string in_path = argv[1];
     if (in_path.size() > 5 && in_path.compare(in_path.size() - 5, 5, ".mcap") == 0) {
       const cloudini_amd::McapTranscodeStats ms = cloudini_amd::transcodeMcap(in_path, argv[2], opt, mcap_comp);
+      const bool clean = !opt.audit || printAudit(ms.pipeline);
       std::printf("{\"messages\": %llu, \"converted\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"points\": %llu, "
                   "\"seconds_total\": %.6f, \"gpu_batches\": %llu, \"peak_held_bytes\": %llu}\n",
                   (unsigned long long)ms.messages, (unsigned long long)ms.converted, (unsigned long long)ms.input_bytes,
@@ -69,16 +97,18 @@ int main(int argc, char** argv) {
           std::fclose(f);
         }
       }
-      return 0;
+      return clean ? 0 : 3;
     }
     cloudini_amd::DirectorySource source(argv[1]);
     cloudini_amd::DirectorySink sink(argv[2]);
     const cloudini_amd::TranscodeStats st = cloudini_amd::transcodePointClouds(source, sink, opt);
+    const bool clean = !opt.audit || printAudit(st);
     std::printf("{\"messages\": %llu, \"points\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"gpu_batches\": %llu, "
                 "\"seconds_total\": %.6f, \"seconds_gpu\": %.6f, \"seconds_stage2\": %.6f, \"gpu_stages\": %llu, \"Mpoints_per_s\": %.1f}\n",
                 (unsigned long long)st.messages, (unsigned long long)st.points, (unsigned long long)st.input_bytes,
                 (unsigned long long)st.output_bytes, (unsigned long long)st.gpu_batches, st.seconds_total, st.seconds_gpu,
                 st.seconds_stage2, (unsigned long long)st.gpu_workers, st.seconds_total > 0 ? st.points / st.seconds_total / 1e6 : 0.0);
+    if (!clean) return 3;
   } catch (const std::exception& e) {
     std::fprintf(stderr, "cloudini_batch_transcode: %s\n", e.what());
     return 1;
