@@ -73,6 +73,10 @@ def lib() -> C.CDLL:
     L.cldn_amd_transcode_directory_audit.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32,
                                                      C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                                      C.c_uint32, C.POINTER(C.c_double), C.c_char_p, C.c_uint64]
+    L.cldn_amd_transcode_directory_sweep.restype = C.c_int64
+    L.cldn_amd_transcode_directory_sweep.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32,
+                                                     C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32),
+                                                     C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_double), C.c_char_p, C.c_uint64]
     L.cldn_amd_transcode_directory.restype = C.c_int64
     L.cldn_amd_transcode_directory.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32, C.POINTER(C.c_double)]
     L.cldn_amd_decode_directory.restype = C.c_int64
@@ -169,16 +173,35 @@ def _device_list(devices):
 
 def transcode_directory(in_dir: str, out_dir: str, resolution: float = 0.001, compression_opt: int = 2,
                         viz_lossy: bool = False, batch_messages: int = 64, devices=None, audit: bool = False,
-                        audit_limits=None) -> dict:
+                        audit_limits=None, sweep=None) -> dict:
     """Batch transcoder (include/cloudini_amd/batch_transcoder.hpp): every CDR PointCloud2 file of in_dir ->
     CompressedPointCloud2 file of the same name in out_dir. `devices`: GPUs to spread the batches over (one GPU stage per
     entry; None = the current device). Returns the statistics. audit=True: every encode call is audited on the device
     (cldn_hip_audit_last_encode) and the per-field summary comes back under "audit" -- a list of dicts (name, is_float,
     n_bitwise_diff, n_class_diff, n_over_limit, max_abs_err, first_bad_message); audit_limits: {field name: limit} for the
-    fields that should not be held to their resolution."""
+    fields that should not be held to their resolution. sweep={field name: [resolutions]} ("xyz" names x, y and z; at most 16
+    per name): the points of every encode call are swept on the device (cldn_hip_sweep_last_encode) and "sweep" holds, per
+    field name and resolution, a dict (name, resolution, bytes, points, n_class_diff, n_over_limit, max_abs_err) -- what the
+    field would cost in stage-1 bytes and lose at that resolution. The files are those of a run without it. One of audit and
+    sweep per call."""
     st = (C.c_double * 8)()
     dv, nd = _device_list(devices)
     keys = ("messages", "points", "input_bytes", "output_bytes", "gpu_batches", "seconds_total", "seconds_gpu", "seconds_stage2")
+    if sweep:
+        if audit:
+            raise ValueError("transcode_directory: audit and sweep are separate calls")
+        import json
+        names = (C.c_char_p * len(sweep))(*[k.encode() for k in sweep])
+        sizes = (C.c_uint32 * len(sweep))(*[len(v) for v in sweep.values()])
+        flat = [float(r) for v in sweep.values() for r in v]
+        values = (C.c_float * max(1, len(flat)))(*flat)
+        text = C.create_string_buffer(1 << 20)
+        _check(lib().cldn_amd_transcode_directory_sweep(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
+                                                        1 if viz_lossy else 0, batch_messages, dv, nd, names, sizes, values,
+                                                        len(sweep), st, text, len(text)))
+        out = dict(zip(keys, [float(x) for x in st]))
+        out["sweep"] = json.loads(text.value.decode())
+        return out
     if not audit:
         _check(lib().cldn_amd_transcode_directory_on(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
                                                      1 if viz_lossy else 0, batch_messages, dv, nd, st))

@@ -137,6 +137,22 @@ int launch_fail(hipError_t e, const char* what) {
 }
 }  // namespace cldn
 
+// The multiplier and the decoder's factor of a lossy float op for one resolution: what the plan builder puts into its ops and what
+// the sweep (sweep_kernels.hip) puts into its ladders. kind: OP_QF32 (FieldEncoderFloatN_Lossy, field_encoder.cpp:24-40),
+// OP_LOSSY_F32 / OP_LOSSY_F64 (FieldEncoderFloat_Lossy<T>, field_encoder.hpp:101-102).
+static void lossy_float_scale(uint32_t kind, float resolution, DevOp* op) {
+  if (kind == OP_QF32) {
+    op->mult_f = 1.0F / resolution;
+    op->res_f = resolution;
+  } else if (kind == OP_LOSSY_F32) {
+    op->mult_f = (float)(1.0 / (double)resolution);
+    op->res_f = resolution;
+  } else {
+    op->mult_d = 1.0 / (double)resolution;
+    op->res_d = (double)resolution;
+  }
+}
+
 struct cldn_hip_plan {
   DevPlan dev;
   std::vector<cldn_hip_field_t> fields;
@@ -146,6 +162,7 @@ struct cldn_hip_plan {
   bool uses_v5 = false;
   uint32_t ref_max_point_bytes = 0;  // detail::MaxSerializedPointSize
   bool has_padding = false;          // some byte of a point is not covered by any field
+  uint32_t floatn_lanes = 0;         // LeadingLossyFloatFieldCount: the first 3 or 4 fields form the FloatN group, else 0
   // WIDE route (stage1_wide.h): the schema does not fit the launch-argument plan (more than kMaxOps regular tokens,
   // kMaxAdaptive adaptive fields or kMaxPointStep bytes per point). `dev` then keeps only its scalar members (n_ops,
   // n_adaptive and n_gorilla are 0: nothing on the host walks its arrays), the entries are here
@@ -358,6 +375,7 @@ int cldn_hip_plan_create(const cldn_hip_field_t* fields, uint32_t n_fields, uint
     }
     if (lead != 3 && lead != 4) lead = 0;
   }
+  plan->floatn_lanes = lead;
   // UsesV5Codec (v5_codec.cpp:883-892)
   plan->uses_v5 = false;
   if (version >= 5 && lossy) {
@@ -390,8 +408,7 @@ int cldn_hip_plan_create(const cldn_hip_field_t* fields, uint32_t n_fields, uint
     }
     if (i < lead) {  // FieldEncoderFloatN_Lossy lane, field_encoder.cpp:24-40
       op.kind = OP_QF32;
-      op.mult_f = 1.0F / f.resolution;
-      op.res_f = f.resolution;
+      lossy_float_scale(OP_QF32, f.resolution, &op);
       op.max_bytes = 5;
       if (!(op.mult_f > 0.0f)) {
         rc = fail(CLDN_HIP_ERR_ARG, "FieldEncoderFloatN_Lossy requires a resolution with value > 0.0");
@@ -418,8 +435,7 @@ int cldn_hip_plan_create(const cldn_hip_field_t* fields, uint32_t n_fields, uint
             break;
           }
           op.kind = OP_LOSSY_F32;
-          op.mult_f = (float)(1.0 / (double)f.resolution);  // field_encoder.hpp:101-102
-          op.res_f = f.resolution;
+          lossy_float_scale(OP_LOSSY_F32, f.resolution, &op);
           op.max_bytes = 10;
           d.min_regular_bytes += 1;
         } else if (encoding_opt == 2) {
@@ -441,8 +457,7 @@ int cldn_hip_plan_create(const cldn_hip_field_t* fields, uint32_t n_fields, uint
             break;
           }
           op.kind = OP_LOSSY_F64;
-          op.mult_d = 1.0 / (double)f.resolution;
-          op.res_d = (double)f.resolution;
+          lossy_float_scale(OP_LOSSY_F64, f.resolution, &op);
           op.max_bytes = 10;
           d.min_regular_bytes += 1;
         } else if (!f.has_resolution && version >= 4) {
@@ -2071,35 +2086,22 @@ static int audit_fields(const cldn_hip_plan& P, const double* limit, std::vector
   return CLDN_HIP_OK;
 }
 
-static int audit_check_report(const cldn_hip_plan& P, uint32_t n_clouds, const void* report, int report_loc) {
+static int audit_check_report(const cldn_hip_plan& P, uint32_t n_clouds, const void* report, int report_loc, const char* who = "audit") {
   if (report_loc != CLDN_HIP_HOST && report_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
-  if (n_clouds && !P.fields.empty() && !report) return fail(CLDN_HIP_ERR_ARG, "audit: report is NULL");
-  if (report_loc == CLDN_HIP_DEVICE && ((uintptr_t)report & 7u)) return fail(CLDN_HIP_ERR_ARG, "audit: a device report must be 8-byte aligned");
+  if (n_clouds && !P.fields.empty() && !report) return fail(CLDN_HIP_ERR_ARG, "%s: report is NULL", who);
+  if (report_loc == CLDN_HIP_DEVICE && ((uintptr_t)report & 7u)) return fail(CLDN_HIP_ERR_ARG, "%s: a device report must be 8-byte aligned", who);
   return CLDN_HIP_OK;
 }
 
-// two device buffers -> report: tables up, one clear, one kernel; HOST report: one copy, one synchronisation
-static int audit_device(cldn_hip_codec* c, const uint8_t* d_a, const uint8_t* d_b, const uint64_t* cloud_points, uint32_t n_clouds,
-                        const std::vector<AuditField>& fields, cldn_hip_audit_field_t* report, int report_loc) {
-  static_assert(sizeof(cldn_hip_audit_field_t) == 40, "five 64-bit words");
-  const uint32_t n_fields = (uint32_t)fields.size();
-  const size_t rep_bytes = (size_t)n_clouds * n_fields * sizeof(cldn_hip_audit_field_t);
-  if (rep_bytes == 0) return CLDN_HIP_OK;
-  int rc;
-  uint64_t n_blocks64 = 0;
-  for (uint32_t k = 0; k < n_clouds; ++k) n_blocks64 += (cloud_points[k] + kAuditBlockPoints - 1u) / kAuditBlockPoints;
-  if (n_blocks64 > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "audit: more than 2^31 blocks of 1024 points");
-  const uint32_t n_blocks = (uint32_t)n_blocks64;
-  const bool dev_fields = n_fields > kAuditArgFields;
-  const size_t clouds_b = ((size_t)n_clouds * sizeof(AuditCloud) + 63u) & ~size_t(63);
-  const size_t blocks_b = ((size_t)n_blocks * sizeof(AuditBlock) + 63u) & ~size_t(63);
-  const size_t fields_b = dev_fields ? ((size_t)n_fields * sizeof(AuditField) + 63u) & ~size_t(63) : 0u;
-  if (c->ev_audit) HIP_TRY(hipEventSynchronize(c->ev_audit));  // the previous call's upload has left the staging buffer
-  else HIP_TRY(hipEventCreateWithFlags(&c->ev_audit, hipEventDisableTiming));
-  if ((rc = c->h_audit.ensure(clouds_b + blocks_b + fields_b)) != CLDN_HIP_OK) return rc;
-  if ((rc = c->d_audit_tab.ensure(clouds_b + blocks_b + fields_b)) != CLDN_HIP_OK) return rc;
-  AuditCloud* hc = (AuditCloud*)c->h_audit.p;
-  AuditBlock* hb = (AuditBlock*)((uint8_t*)c->h_audit.p + clouds_b);
+// The cloud and block tables of a batch, as the audit and the sweep kernels read them: blocks of kAuditBlockPoints points, cut per cloud.
+static int count_point_blocks(const uint64_t* cloud_points, uint32_t n_clouds, const char* who, uint32_t* n_blocks) {
+  uint64_t n = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) n += (cloud_points[k] + kAuditBlockPoints - 1u) / kAuditBlockPoints;
+  if (n > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "%s: more than 2^31 blocks of 1024 points", who);
+  *n_blocks = (uint32_t)n;
+  return CLDN_HIP_OK;
+}
+static void fill_point_blocks(const uint64_t* cloud_points, uint32_t n_clouds, AuditCloud* hc, AuditBlock* hb) {
   uint64_t first = 0;
   uint32_t bi = 0;
   for (uint32_t k = 0; k < n_clouds; ++k) {
@@ -2113,6 +2115,27 @@ static int audit_device(cldn_hip_codec* c, const uint8_t* d_a, const uint8_t* d_
     }
     first += cloud_points[k];
   }
+}
+
+// two device buffers -> report: tables up, one clear, one kernel; HOST report: one copy, one synchronisation
+static int audit_device(cldn_hip_codec* c, const uint8_t* d_a, const uint8_t* d_b, const uint64_t* cloud_points, uint32_t n_clouds,
+                        const std::vector<AuditField>& fields, cldn_hip_audit_field_t* report, int report_loc) {
+  static_assert(sizeof(cldn_hip_audit_field_t) == 40, "five 64-bit words");
+  const uint32_t n_fields = (uint32_t)fields.size();
+  const size_t rep_bytes = (size_t)n_clouds * n_fields * sizeof(cldn_hip_audit_field_t);
+  if (rep_bytes == 0) return CLDN_HIP_OK;
+  int rc;
+  uint32_t n_blocks = 0;
+  if ((rc = count_point_blocks(cloud_points, n_clouds, "audit", &n_blocks)) != CLDN_HIP_OK) return rc;
+  const bool dev_fields = n_fields > kAuditArgFields;
+  const size_t clouds_b = ((size_t)n_clouds * sizeof(AuditCloud) + 63u) & ~size_t(63);
+  const size_t blocks_b = ((size_t)n_blocks * sizeof(AuditBlock) + 63u) & ~size_t(63);
+  const size_t fields_b = dev_fields ? ((size_t)n_fields * sizeof(AuditField) + 63u) & ~size_t(63) : 0u;
+  if (c->ev_audit) HIP_TRY(hipEventSynchronize(c->ev_audit));  // the previous call's upload has left the staging buffer
+  else HIP_TRY(hipEventCreateWithFlags(&c->ev_audit, hipEventDisableTiming));
+  if ((rc = c->h_audit.ensure(clouds_b + blocks_b + fields_b)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_audit_tab.ensure(clouds_b + blocks_b + fields_b)) != CLDN_HIP_OK) return rc;
+  fill_point_blocks(cloud_points, n_clouds, (AuditCloud*)c->h_audit.p, (AuditBlock*)((uint8_t*)c->h_audit.p + clouds_b));
   if (dev_fields) memcpy((uint8_t*)c->h_audit.p + clouds_b + blocks_b, fields.data(), (size_t)n_fields * sizeof(AuditField));
   HIP_TRY(hipMemcpyAsync(c->d_audit_tab.p, c->h_audit.p, clouds_b + blocks_b + fields_b, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->ev_audit, c->stream));
@@ -2140,6 +2163,11 @@ static int audit_device(cldn_hip_codec* c, const uint8_t* d_a, const uint8_t* d_
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   return CLDN_HIP_OK;
+}
+
+static int no_last_encode(const char* who) {
+  return fail(CLDN_HIP_ERR_ARG, "%s: no encode call to audit (an encode call must be this codec's last call that touched buffers; "
+                                "a chunk table must have been framed)", who);
 }
 
 static int audit_batch_points(const uint64_t* cloud_points, uint32_t n_clouds, uint64_t* total) {
@@ -2254,9 +2282,7 @@ int cldn_hip_audit_streams(cldn_hip_codec_t* c, const void* points, int points_l
 
 int64_t cldn_hip_audit_last_encode_clouds(const cldn_hip_codec_t* c) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
-  if (!c->enc.valid)
-    return fail(CLDN_HIP_ERR_ARG, "audit_last_encode: no encode call to audit (an encode call must be this codec's last call that touched buffers; "
-                                  "a chunk table must have been framed)");
+  if (!c->enc.valid) return no_last_encode("audit_last_encode");
   return (int64_t)c->enc.cloud_points.size();
 }
 
@@ -2284,6 +2310,154 @@ int cldn_hip_audit_last_encode(cldn_hip_codec_t* c, const double* limit, cldn_hi
                                     n_clouds, E.kind, limit, report, report_loc);
   c->enc = E;
   return rc;
+}
+
+}  // extern "C"
+
+// ---- resolution sweep: size and error per field and candidate (sweep_kernels.hip) ----
+
+// the schema's fields and their ladders as the kernel wants them
+static int sweep_tables(const cldn_hip_plan& P, const float* resolutions, uint32_t n_candidates, std::vector<SweepField>* fields,
+                        std::vector<SweepCand>* cands) {
+  if (n_candidates == 0 || n_candidates > CLDN_HIP_SWEEP_MAX_CANDIDATES)
+    return fail(CLDN_HIP_ERR_ARG, "sweep: n_candidates is %u, must be 1..%u", n_candidates, CLDN_HIP_SWEEP_MAX_CANDIDATES);
+  if (!P.fields.empty() && !resolutions) return fail(CLDN_HIP_ERR_ARG, "sweep: resolutions is NULL");
+  fields->resize(P.fields.size());
+  cands->assign(P.fields.size() * n_candidates, SweepCand{0.0, 0.0});
+  for (size_t i = 0; i < P.fields.size(); ++i) {
+    const cldn_hip_field_t& f = P.fields[i];
+    SweepField& s = (*fields)[i];
+    memset(&s, 0, sizeof(s));
+    s.offset = f.offset;
+    s.kind = SWEEP_NONE;
+    if (P.encoding_opt != 1 || !f.has_resolution || (f.type != 7 && f.type != 8)) continue;
+    const uint32_t op_kind = i < P.floatn_lanes ? OP_QF32 : (f.type == 7 ? OP_LOSSY_F32 : OP_LOSSY_F64);
+    s.kind = op_kind == OP_QF32 ? SWEEP_QF32 : (op_kind == OP_LOSSY_F32 ? SWEEP_F32 : SWEEP_F64);
+    if (f.offset == 0xffffffffu) return fail(CLDN_HIP_ERR_ARG, "sweep: field %zu is decoded but not stored (kDecodeButSkipStore)", i);
+    for (uint32_t k = 0; k < n_candidates; ++k) {
+      const float r = resolutions[i * n_candidates + k];
+      if (r == 0.0f) continue;  // skip
+      const float recip = 1.0F / r;
+      if (!(r > 0.0f) || std::isinf(r) || recip == 0.0f || std::isinf(recip))
+        return fail(CLDN_HIP_ERR_ARG, "sweep: resolution %u of field %zu (%g) must be 0 (skip) or positive and finite with a finite, non-zero float32 reciprocal",
+                    k, i, (double)r);
+      DevOp op;
+      memset(&op, 0, sizeof(op));
+      lossy_float_scale(op_kind, r, &op);
+      SweepCand& C = (*cands)[i * n_candidates + k];
+      C.m = op_kind == OP_LOSSY_F64 ? op.mult_d : (double)op.mult_f;
+      C.r = op_kind == OP_LOSSY_F64 ? op.res_d : (double)op.res_f;
+      if (!(C.m > 0.0) || std::isinf(C.m))
+        return fail(CLDN_HIP_ERR_ARG, "sweep: resolution %u of field %zu (%g) has no usable multiplier", k, i, (double)r);
+    }
+  }
+  return CLDN_HIP_OK;
+}
+
+// device points -> report: tables up, one clear, one kernel; HOST report: one copy, one synchronisation
+static int sweep_device(cldn_hip_codec* c, const uint8_t* d_points, const uint64_t* cloud_points, uint32_t n_clouds,
+                        const std::vector<SweepField>& fields, const std::vector<SweepCand>& cands, uint32_t n_candidates,
+                        cldn_hip_sweep_cell_t* report, int report_loc) {
+  static_assert(sizeof(cldn_hip_sweep_cell_t) == 32, "four 64-bit words");
+  const uint32_t n_fields = (uint32_t)fields.size();
+  const size_t rep_bytes = (size_t)n_clouds * n_fields * n_candidates * sizeof(cldn_hip_sweep_cell_t);
+  if (rep_bytes == 0) return CLDN_HIP_OK;
+  int rc;
+  uint32_t n_blocks = 0;
+  if ((rc = count_point_blocks(cloud_points, n_clouds, "sweep", &n_blocks)) != CLDN_HIP_OK) return rc;
+  const bool dev_fields = n_fields > kAuditArgFields;
+  const size_t clouds_b = ((size_t)n_clouds * sizeof(AuditCloud) + 63u) & ~size_t(63);
+  const size_t blocks_b = ((size_t)n_blocks * sizeof(AuditBlock) + 63u) & ~size_t(63);
+  const size_t cands_b = (cands.size() * sizeof(SweepCand) + 63u) & ~size_t(63);
+  const size_t fields_b = dev_fields ? ((size_t)n_fields * sizeof(SweepField) + 63u) & ~size_t(63) : 0u;
+  const size_t tab_b = clouds_b + blocks_b + cands_b + fields_b;
+  if (c->ev_audit) HIP_TRY(hipEventSynchronize(c->ev_audit));  // the previous call's upload has left the staging buffer
+  else HIP_TRY(hipEventCreateWithFlags(&c->ev_audit, hipEventDisableTiming));
+  if ((rc = c->h_audit.ensure(tab_b)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_audit_tab.ensure(tab_b)) != CLDN_HIP_OK) return rc;
+  uint8_t* h = (uint8_t*)c->h_audit.p;
+  fill_point_blocks(cloud_points, n_clouds, (AuditCloud*)h, (AuditBlock*)(h + clouds_b));
+  memcpy(h + clouds_b + blocks_b, cands.data(), cands.size() * sizeof(SweepCand));
+  if (dev_fields) memcpy(h + clouds_b + blocks_b + cands_b, fields.data(), (size_t)n_fields * sizeof(SweepField));
+  HIP_TRY(hipMemcpyAsync(c->d_audit_tab.p, h, tab_b, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->ev_audit, c->stream));
+  unsigned long long* d_rep = (unsigned long long*)report;
+  if (report_loc == CLDN_HIP_HOST) {
+    if ((rc = c->d_audit_rep.ensure(rep_bytes)) != CLDN_HIP_OK) return rc;
+    d_rep = (unsigned long long*)c->d_audit_rep.p;
+  }
+  const uint8_t* d_tab = (const uint8_t*)c->d_audit_tab.p;
+  SweepLaunch L;
+  L.stream = c->stream;
+  L.points = d_points;
+  L.point_step = c->plan.point_step;
+  L.n_clouds = n_clouds;
+  L.n_blocks = n_blocks;
+  L.n_fields = n_fields;
+  L.n_candidates = n_candidates;
+  L.fields = fields.data();
+  L.dev_fields = dev_fields ? (const SweepField*)(d_tab + clouds_b + blocks_b + cands_b) : nullptr;
+  L.cands = (const SweepCand*)(d_tab + clouds_b + blocks_b);
+  L.clouds = (const AuditCloud*)d_tab;
+  L.blocks = (const AuditBlock*)(d_tab + clouds_b);
+  L.report = d_rep;
+  if ((rc = sweep_launch(L)) != CLDN_HIP_OK) return rc;
+  if (report_loc == CLDN_HIP_HOST) {
+    HIP_TRY(hipMemcpyAsync(report, d_rep, rep_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return CLDN_HIP_OK;
+}
+
+extern "C" {
+
+int cldn_hip_sweep_clouds(cldn_hip_codec_t* c, const void* points, int points_loc, const uint64_t* cloud_points, uint32_t n_clouds,
+                          const float* resolutions, uint32_t n_candidates, cldn_hip_sweep_cell_t* report, int report_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
+  if (points_loc != CLDN_HIP_HOST && points_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  int rc;
+  if ((rc = audit_check_report(c->plan, n_clouds, report, report_loc, "sweep")) != CLDN_HIP_OK) return rc;
+  std::vector<SweepField> fields;
+  std::vector<SweepCand> cands;
+  if ((rc = sweep_tables(c->plan, resolutions, n_candidates, &fields, &cands)) != CLDN_HIP_OK) return rc;
+  uint64_t n_points = 0;
+  if ((rc = audit_batch_points(cloud_points, n_clouds, &n_points)) != CLDN_HIP_OK) return rc;
+  if (n_points && !points) return fail(CLDN_HIP_ERR_ARG, "sweep_clouds: points is NULL");
+  ENTER_DEVICE(c->device);
+  const uint64_t bytes = n_points * c->plan.point_step;
+  const uint8_t* d_points = (const uint8_t*)points;
+  const bool up = points_loc == CLDN_HIP_HOST && bytes;
+  if (up) {
+    if ((rc = c->d_audit.ensure((size_t)bytes)) != CLDN_HIP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_audit.p, points, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    d_points = (const uint8_t*)c->d_audit.p;
+  }
+  rc = sweep_device(c, d_points, cloud_points, n_clouds, fields, cands, n_candidates, report, report_loc);
+  // (pageable host buffers: the call does not return while a copy may still read them)
+  if (rc == CLDN_HIP_OK && up && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
+  return rc;
+}
+
+int64_t cldn_hip_sweep_last_encode_clouds(const cldn_hip_codec_t* c) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (!c->enc.valid && !c->enc.await_frame) return no_last_encode("sweep_last_encode");  // (the points are there before the framing)
+  return (int64_t)c->enc.cloud_points.size();
+}
+
+int cldn_hip_sweep_last_encode(cldn_hip_codec_t* c, const float* resolutions, uint32_t n_candidates, cldn_hip_sweep_cell_t* report,
+                               int report_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (cldn_hip_sweep_last_encode_clouds(c) < 0) return CLDN_HIP_ERR_ARG;
+  const cldn_hip_codec::LastEncode& E = c->enc;  // read only: the state stays as it is
+  const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
+  int rc;
+  if ((rc = audit_check_report(c->plan, n_clouds, report, report_loc, "sweep")) != CLDN_HIP_OK) return rc;
+  std::vector<SweepField> fields;
+  std::vector<SweepCand> cands;
+  if ((rc = sweep_tables(c->plan, resolutions, n_candidates, &fields, &cands)) != CLDN_HIP_OK) return rc;
+  ENTER_DEVICE(c->device);
+  return sweep_device(c, E.points, E.cloud_points.data(), n_clouds, fields, cands, n_candidates, report, report_loc);
 }
 
 }  // extern "C"

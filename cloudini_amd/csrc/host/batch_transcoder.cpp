@@ -10,7 +10,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <cctype>
 #include <cerrno>
+#include <cmath>
 #include <dirent.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -332,10 +334,31 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       audit.limit = audit_limit.data();
     }
     Cloudini::amd_detail::AuditRequest* const audit_p = opt.audit ? &audit : nullptr;
+    // the ladders of this run's schema: one row per field, padded with 0 (skip) to the longest ladder
+    Cloudini::amd_detail::SweepRequest sweep;
+    std::vector<const std::vector<float>*> sweep_ladder(info0.fields.size(), nullptr);
+    std::vector<float> sweep_res;
+    if (!opt.sweep.empty() && info0.encoding_opt == Cloudini::EncodingOptions::LOSSY) {
+      for (size_t f = 0; f < info0.fields.size(); ++f) {
+        const Cloudini::PointField& fd = info0.fields[f];
+        if (!fd.resolution || (fd.type != Cloudini::FieldType::FLOAT32 && fd.type != Cloudini::FieldType::FLOAT64)) continue;
+        auto named = opt.sweep.find(fd.name);
+        if (named == opt.sweep.end() && (fd.name == "x" || fd.name == "y" || fd.name == "z")) named = opt.sweep.find("xyz");
+        if (named == opt.sweep.end() || named->second.empty()) continue;
+        sweep_ladder[f] = &named->second;
+        sweep.n_candidates = std::max<uint32_t>(sweep.n_candidates, (uint32_t)named->second.size());
+      }
+      sweep_res.assign(info0.fields.size() * sweep.n_candidates, 0.0f);
+      for (size_t f = 0; f < info0.fields.size(); ++f)
+        if (sweep_ladder[f]) std::copy(sweep_ladder[f]->begin(), sweep_ladder[f]->end(), sweep_res.begin() + f * sweep.n_candidates);
+      sweep.resolutions = sweep_res.data();
+    }
+    Cloudini::amd_detail::SweepRequest* const sweep_p = sweep.n_candidates ? &sweep : nullptr;
     const auto t_gpu = Clock::now();
     if (b.parsed[r0].viz) {
       Cloudini::amd_detail::encodeStage1BatchViz(info0, ptrs.data(), pts.data(), run.count, b.parsed[r0].viz_xyz_offset,
-                                                 b.parsed[r0].viz_resolution, grow, run.offsets, run.chunk_sizes, kept, audit_p);
+                                                 b.parsed[r0].viz_resolution, grow, run.offsets, run.chunk_sizes, kept, audit_p,
+                                                 sweep_p);
       for (uint32_t k = 0; k < run.count; ++k) {  // what the reference's function leaves behind (src/ros_msg_utils.cpp:326-335)
         Parsed& p = b.parsed[r0 + k];
         p.points = kept[k];
@@ -350,7 +373,32 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
         if (stats) stats->points += kept[k];
       }
     } else {
-      Cloudini::amd_detail::encodeStage1Batch(info0, ptrs.data(), pts.data(), run.count, grow, run.offsets, run.chunk_sizes, audit_p);
+      Cloudini::amd_detail::encodeStage1Batch(info0, ptrs.data(), pts.data(), run.count, grow, run.offsets, run.chunk_sizes, audit_p,
+                                              sweep_p);
+    }
+    if (sweep_p && stats) {  // the run's cells, summed over its messages, into the per-name-and-resolution summary
+      const size_t nf = info0.fields.size(), nc = sweep.n_candidates;
+      std::vector<SweepCellSummary> part;
+      for (size_t f = 0; f < nf; ++f) {
+        if (!sweep_ladder[f]) continue;
+        const std::vector<float>& ladder = *sweep_ladder[f];
+        for (size_t c = 0; c < ladder.size(); ++c) {
+          if (std::find(ladder.begin(), ladder.begin() + c, ladder[c]) != ladder.begin() + c) continue;  // a rung given twice counts once
+          SweepCellSummary one;
+          one.name = info0.fields[f].name;
+          one.resolution = ladder[c];
+          for (uint32_t k = 0; k < run.count; ++k) {
+            const cldn_hip_sweep_cell_t& cell = sweep.report[((size_t)k * nf + f) * nc + c];
+            one.bytes += cell.bytes;
+            one.points += b.parsed[r0 + k].points;
+            one.n_class_diff += cell.n_class_diff;
+            one.n_over_limit += cell.n_over_limit;
+            one.max_abs_err = std::max(one.max_abs_err, cell.max_abs_err);
+          }
+          part.push_back(one);
+        }
+      }
+      stats->mergeSweep(part);
     }
     if (opt.audit && stats) {  // the run's report, message by message, into the per-name summary
       const size_t nf = info0.fields.size();
@@ -643,8 +691,97 @@ void TranscodeStats::mergeAudit(const std::vector<AuditFieldSummary>& other) {
   }
 }
 
+void TranscodeStats::mergeSweep(const std::vector<SweepCellSummary>& other) {
+  for (const SweepCellSummary& o : other) {
+    SweepCellSummary* mine = nullptr;
+    for (SweepCellSummary& s : sweep)
+      if (s.name == o.name && s.resolution == o.resolution) mine = &s;
+    if (!mine) {
+      sweep.push_back(o);
+      continue;
+    }
+    mine->bytes += o.bytes;
+    mine->points += o.points;
+    mine->n_class_diff += o.n_class_diff;
+    mine->n_over_limit += o.n_over_limit;
+    mine->max_abs_err = std::max(mine->max_abs_err, o.max_abs_err);
+  }
+}
+
+namespace {
+std::string trimmed(const std::string& s) {
+  size_t a = 0, z = s.size();
+  while (a < z && std::isspace((unsigned char)s[a])) ++a;
+  while (z > a && std::isspace((unsigned char)s[z - 1])) --z;
+  return s.substr(a, z - a);
+}
+
+// "name:value; name:value" -> (name, value text) pairs; what does not have that shape throws
+std::vector<std::pair<std::string, std::string>> namedEntries(const std::string& text, const char* what) {
+  std::vector<std::pair<std::string, std::string>> out;
+  size_t at = 0;
+  while (at <= text.size()) {
+    const size_t semi = std::min(text.find(';', at), text.size());
+    const std::string entry = trimmed(text.substr(at, semi - at));
+    const bool last = semi == text.size();
+    at = semi + 1;
+    if (entry.empty() && last && !out.empty()) break;  // a trailing ';'
+    const size_t colon = entry.find(':');
+    if (colon == std::string::npos || entry.find(':', colon + 1) != std::string::npos)
+      throw std::invalid_argument(std::string(what) + ": \"" + entry + "\" is not name:value");
+    const std::string name = trimmed(entry.substr(0, colon)), value = trimmed(entry.substr(colon + 1));
+    if (name.empty() || value.empty()) throw std::invalid_argument(std::string(what) + ": \"" + entry + "\" is not name:value");
+    out.emplace_back(name, value);
+  }
+  return out;
+}
+
+float resolutionValue(const std::string& value, bool zero_allowed, const char* what) {
+  char* end = nullptr;
+  const float r = std::strtof(value.c_str(), &end);
+  if (end == value.c_str() || *end || !std::isfinite(r) || r < 0.0f || (r == 0.0f && !zero_allowed))
+    throw std::invalid_argument(std::string(what) + ": \"" + value + "\" is not a resolution");
+  return r;
+}
+
+void checkOptions(const TranscodeOptions& opt) {
+  if (opt.decode && !opt.sweep.empty()) throw std::invalid_argument("TranscodeOptions: sweep is not available together with decode");
+  for (const auto& named : opt.sweep)
+    if (named.second.size() > CLDN_HIP_SWEEP_MAX_CANDIDATES)
+      throw std::invalid_argument("TranscodeOptions: the sweep ladder of " + named.first + " has more than 16 resolutions");
+}
+}  // namespace
+
+cloudini_ros::ResolutionProfile parseProfileString(const std::string& text) {
+  cloudini_ros::ResolutionProfile profile;
+  for (const auto& entry : namedEntries(text, "profile")) {
+    const float r = entry.second == "remove" ? 0.0f : resolutionValue(entry.second, true, "profile");
+    if (entry.first == "xyz") profile["x"] = profile["y"] = profile["z"] = r;
+    else profile[entry.first] = r;
+  }
+  return profile;
+}
+
+std::map<std::string, std::vector<float>> parseSweepString(const std::string& text) {
+  std::map<std::string, std::vector<float>> sweep;
+  for (const auto& entry : namedEntries(text, "sweep")) {
+    std::vector<float> ladder;
+    size_t at = 0;
+    while (at <= entry.second.size()) {
+      const size_t comma = std::min(entry.second.find(',', at), entry.second.size());
+      ladder.push_back(resolutionValue(trimmed(entry.second.substr(at, comma - at)), false, "sweep"));
+      at = comma + 1;
+    }
+    if (ladder.size() > CLDN_HIP_SWEEP_MAX_CANDIDATES)
+      throw std::invalid_argument("sweep: " + entry.first + " has more than 16 resolutions");
+    sweep[entry.first] = ladder;
+  }
+  return sweep;
+}
+
 void transcodeBatch(const std::vector<Message>& in, const TranscodeOptions& opt, std::vector<std::vector<uint8_t>>& out,
                     TranscodeStats* stats) {
+  checkOptions(opt);
   Batch b;
   b.in.resize(in.size());
   for (size_t i = 0; i < in.size(); ++i) {
@@ -694,6 +831,7 @@ void parallelFor(size_t n, unsigned threads, Fn&& fn) {
 // ---- the pipeline: reader -> GPU (this thread) -> stage 2 -> writer; batches circulate (page-locked buffers are reused) ---
 
 TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, const TranscodeOptions& opt) {
+  checkOptions(opt);
   TranscodeStats stats, stats2;
   const auto t0 = Clock::now();
   // GPU workers: one thread per entry of options.devices (the same device may appear more than once), each with its own
@@ -818,6 +956,7 @@ TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, co
         stats.gpu_batches += mine.gpu_batches;
         stats.seconds_gpu += mine.seconds_gpu;
         stats.mergeAudit(mine.audit);
+        stats.mergeSweep(mine.sweep);
       }
       if (gpu_workers_left.fetch_sub(1) == 1) to_stage2.close();
     });

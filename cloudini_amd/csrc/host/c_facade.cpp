@@ -168,6 +168,56 @@ CLDN_EXPORT int64_t cldn_amd_transcode_directory_audit(const char* in_dir, const
   });
 }
 
+// the sweep summary as one line of JSON (a list of objects, one per field name and resolution)
+static std::string sweepJson(const cloudini_amd::TranscodeStats& st) {
+  std::string out = "[";
+  for (size_t i = 0; i < st.sweep.size(); ++i) {
+    const cloudini_amd::SweepCellSummary& s = st.sweep[i];
+    std::string name = "\"";
+    for (char ch : s.name) {
+      if (ch == '"' || ch == '\\') name += '\\';
+      name += (unsigned char)ch < 0x20 ? ' ' : ch;
+    }
+    char num[320];
+    std::snprintf(num, sizeof num, "\"resolution\": %.9g, \"bytes\": %llu, \"points\": %llu, \"n_class_diff\": %llu, \"n_over_limit\": %llu, "
+                  "\"max_abs_err\": %.17g", (double)s.resolution, (unsigned long long)s.bytes, (unsigned long long)s.points,
+                  (unsigned long long)s.n_class_diff, (unsigned long long)s.n_over_limit, s.max_abs_err);  // (never inf: both sides finite)
+    out += std::string(i ? ", " : "") + "{\"name\": " + name + "\", " + num + "}";
+  }
+  return out + "]";
+}
+
+CLDN_EXPORT int64_t cldn_amd_transcode_directory_sweep(const char* in_dir, const char* out_dir, float resolution,
+                                                       uint8_t compression_opt, int viz_lossy, uint32_t batch_messages,
+                                                       const int32_t* devices, uint32_t n_devices, const char* const* sweep_names,
+                                                       const uint32_t* ladder_sizes, const float* ladders, uint32_t n_names,
+                                                       double* stats_out, char* sweep_json, uint64_t sweep_capacity) {
+  return guarded([&] {
+    cloudini_amd::DirectorySource source(in_dir);
+    cloudini_amd::DirectorySink sink(out_dir);
+    cloudini_amd::TranscodeOptions opt;
+    opt.default_resolution = resolution;
+    opt.compression = static_cast<Cloudini::CompressionOption>(compression_opt);
+    opt.viz_lossy = viz_lossy != 0;
+    if (batch_messages) opt.batch_messages = batch_messages;
+    if (devices) opt.devices.assign(devices, devices + n_devices);
+    for (uint32_t i = 0; i < n_names; ++i) {
+      opt.sweep[sweep_names[i]].assign(ladders, ladders + ladder_sizes[i]);
+      ladders += ladder_sizes[i];
+    }
+    const cloudini_amd::TranscodeStats st = cloudini_amd::transcodePointClouds(source, sink, opt);
+    if (stats_out) {
+      const double v[8] = {(double)st.messages,    (double)st.points,  (double)st.input_bytes, (double)st.output_bytes,
+                           (double)st.gpu_batches, st.seconds_total, st.seconds_gpu,         st.seconds_stage2};
+      for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
+    }
+    const std::string json = sweepJson(st);
+    if (json.size() + 1 > sweep_capacity) throw std::runtime_error("transcode_directory_sweep: the summary needs " + std::to_string(json.size() + 1) + " bytes");
+    std::memcpy(sweep_json, json.c_str(), json.size() + 1);
+    return (int64_t)st.messages;
+  });
+}
+
 CLDN_EXPORT int64_t cldn_amd_transcode_directory(const char* in_dir, const char* out_dir, float resolution,
                                                  uint8_t compression_opt, int viz_lossy, uint32_t batch_messages,
                                                  double* stats_out) {

@@ -1039,9 +1039,16 @@ static int auditLastEncode(cldn_hip_codec_t* codec, const EncodingInfo& info, ui
   return cldn_hip_audit_last_encode(codec, audit->limit, audit->report.data(), CLDN_HIP_HOST);
 }
 
+// the points of that encode call, swept where they lie (the audit before it leaves the codec's note of the call in place)
+static int sweepLastEncode(cldn_hip_codec_t* codec, const EncodingInfo& info, uint32_t n_clouds, SweepRequest* sweep) {
+  sweep->report.assign((size_t)n_clouds * info.fields.size() * sweep->n_candidates, cldn_hip_sweep_cell_t{});
+  if (sweep->report.empty()) return CLDN_HIP_OK;
+  return cldn_hip_sweep_last_encode(codec, sweep->resolutions, sweep->n_candidates, sweep->report.data(), CLDN_HIP_HOST);
+}
+
 void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
-                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit) {
+                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit, SweepRequest* sweep) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1056,6 +1063,7 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
     rc = cldn_hip_codec_fetch_output(codec, total ? grow(total) : nullptr, total);
   }
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
+  if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
   pool().release(info, codec);
   if (rc != CLDN_HIP_OK) throw std::runtime_error(err);
@@ -1065,7 +1073,7 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
 void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
-                          std::vector<uint64_t>& kept_points, AuditRequest* audit) {
+                          std::vector<uint64_t>& kept_points, AuditRequest* audit, SweepRequest* sweep) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;  // of the input: an upper bound of what the filtered clouds have
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1081,6 +1089,7 @@ void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_
     rc = cldn_hip_codec_fetch_output(codec, total ? grow(total) : nullptr, total);
   }
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
+  if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
   pool().release(info, codec);
   if (rc != CLDN_HIP_OK) throw std::runtime_error(err);

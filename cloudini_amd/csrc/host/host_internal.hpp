@@ -34,16 +34,24 @@ struct AuditRequest {
   const double* limit = nullptr;
   std::vector<cldn_hip_audit_field_t> report;
 };
+// `sweep` (optional): behind the encode call (and behind the audit, if both are asked for) the codec sweeps the points it
+// encoded (cldn_hip_sweep_last_encode; behind the viz filter: the survivors); resolutions = info.fields.size() * n_candidates
+// float32, one ladder per field (0 = skip), report receives n_clouds * info.fields.size() * n_candidates cells.
+struct SweepRequest {
+  const float* resolutions = nullptr;
+  uint32_t n_candidates = 0;
+  std::vector<cldn_hip_sweep_cell_t> report;
+};
 void encodeStage1Batch(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
-                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit = nullptr);
+                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr);
 // The same behind the viz pre-filter (cldn_hip_encode_stage1_viz_gather): every cloud is filtered on its own, the survivors
 // are encoded without leaving the device. kept_points gets n_clouds survivor counts; stream_offsets and chunk_sizes describe
 // the filtered clouds (a cloud that loses every point has an empty stream and no chunk).
 void encodeStage1BatchViz(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
-                          std::vector<uint64_t>& kept_points, AuditRequest* audit = nullptr);
+                          std::vector<uint64_t>& kept_points, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr);
 // detail::CompressChunk (src/codec_common.cpp:220-258) and its worst-case output size
 uint32_t compressChunkTo(Cloudini::CompressionOption opt, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_cap);
 size_t compressedChunkBound(Cloudini::CompressionOption opt, size_t stage1_bytes);

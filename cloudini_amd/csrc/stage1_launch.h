@@ -322,4 +322,37 @@ struct AuditLaunch {
 uint32_t audit_stage_points(uint32_t point_step);  // points per LDS stage, 0 = the direct route
 int audit_launch(const AuditLaunch& L);            // one clear + one kernel
 
+// ---- resolution sweep of the lossy float fields (sweep_kernels.hip; record: cldn_hip_sweep_cell_t, four 64-bit words) ----
+// Blocks and clouds are the audit's (AuditBlock / AuditCloud, kAuditBlockPoints: 1024 divides 32768, a block never straddles a chunk).
+constexpr uint32_t kSweepMaxCandidates = 16;      // CLDN_HIP_SWEEP_MAX_CANDIDATES
+constexpr uint32_t kSweepLdsBytes = 40960;        // dynamic LDS of the staged route: one predecessor point + the stage's points
+enum SweepKind : uint8_t { SWEEP_NONE = 0, SWEEP_QF32 = 1, SWEEP_F32 = 2, SWEEP_F64 = 3 };  // the field's encoder: OP_QF32 / OP_LOSSY_F32 / OP_LOSSY_F64
+struct SweepField {
+  uint32_t offset;
+  uint8_t kind;      // SweepKind
+  uint8_t pad[3];
+};
+static_assert(sizeof(SweepField) == 8, "128 of them are a kernel argument");
+struct SweepCand {   // one rung of a field's ladder; m == 0: skip
+  double m;          // the encoder's multiplier (a float32 value for the FLOAT32 kinds: exact in a double)
+  double r;          // (double)resolution: the decoder's factor (a float32 value for the FLOAT32 kinds) and the limit
+};
+struct SweepLaunch {
+  hipStream_t stream;
+  const uint8_t* points;         // device AoS, clouds back to back, any alignment
+  uint32_t point_step;
+  uint32_t n_clouds;
+  uint32_t n_blocks;
+  uint32_t n_fields;
+  uint32_t n_candidates;         // 1..kSweepMaxCandidates
+  const SweepField* fields;      // HOST [n_fields]
+  const SweepField* dev_fields;  // device copy of it, or NULL when n_fields <= kAuditArgFields
+  const SweepCand* cands;        // device [n_fields * n_candidates]
+  const AuditCloud* clouds;      // device [n_clouds]
+  const AuditBlock* blocks;      // device [n_blocks]
+  unsigned long long* report;    // device [n_clouds * n_fields * n_candidates * 4], 8-byte aligned: cleared, then filled
+};
+uint32_t sweep_stage_points(uint32_t point_step);  // points per LDS stage, 0 = the direct route
+int sweep_launch(const SweepLaunch& L);            // one clear + one kernel
+
 }  // namespace cldn

@@ -159,6 +159,12 @@ def lib() -> C.CDLL:
     L.cldn_hip_audit_last_encode.argtypes = [vp, vp, vp, C.c_int]
     L.cldn_hip_audit_last_encode_clouds.restype = C.c_int64
     L.cldn_hip_audit_last_encode_clouds.argtypes = [vp]
+    L.cldn_hip_sweep_clouds.restype = C.c_int
+    L.cldn_hip_sweep_clouds.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_uint32, vp, C.c_int]
+    L.cldn_hip_sweep_last_encode.restype = C.c_int
+    L.cldn_hip_sweep_last_encode.argtypes = [vp, vp, C.c_uint32, vp, C.c_int]
+    L.cldn_hip_sweep_last_encode_clouds.restype = C.c_int64
+    L.cldn_hip_sweep_last_encode_clouds.argtypes = [vp]
     _lib = L
     return L
 
@@ -198,6 +204,19 @@ def _limit_ptr(limit, n_fields: int):
     if lim.size != n_fields:
         raise ValueError(f"limit has {lim.size} entries, the schema has {n_fields} fields")
     return lim, lim.ctypes.data_as(C.c_void_p)
+
+
+# cldn_hip_sweep_cell_t: one cell per (cloud, field, candidate resolution)
+SWEEP_DTYPE = np.dtype([("bytes", "<u8"), ("n_class_diff", "<u8"), ("n_over_limit", "<u8"), ("max_abs_err", "<f8")])
+SWEEP_MAX_CANDIDATES = 16
+
+
+def _ladders(resolutions, n_fields: int) -> np.ndarray:
+    """A sweep call's `resolutions` as the (n_fields, n_candidates) float32 array the C side reads."""
+    res = np.ascontiguousarray(resolutions, dtype=np.float32)
+    if res.ndim != 2 or res.shape[0] != n_fields:
+        raise ValueError(f"resolutions must have shape (n_fields = {n_fields}, n_candidates), not {res.shape}")
+    return res
 
 
 class Plan:
@@ -619,5 +638,47 @@ class Codec:
         lim, lp = _limit_ptr(limit, self.plan.n_fields)
         rep = None if report_ptr else self._audit_report(n)
         _check(lib().cldn_hip_audit_last_encode(self._h, lp, C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                                DEVICE if report_ptr else HOST))
+        return rep
+
+    # ---- resolution sweep: size and error per field and candidate (cldn_hip_sweep_*) ---------------------------------
+    def _sweep_report(self, n_clouds: int, n_candidates: int) -> np.ndarray:
+        rep = np.zeros((int(n_clouds), self.plan.n_fields, int(n_candidates)), dtype=SWEEP_DTYPE)
+        rep.view(np.uint8)[...] = 0xEE  # (a call that fails leaves it as it was)
+        return rep
+
+    def sweep_clouds_host(self, clouds: Sequence[np.ndarray], resolutions) -> np.ndarray:
+        """cldn_hip_sweep_clouds on host buffers. resolutions: (n_fields, n_candidates), one ladder per field, 0 = skip.
+        Returns the (n_clouds, n_fields, n_candidates) report."""
+        step = self.plan.point_step
+        arrs = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in clouds]
+        if any(x.size % step for x in arrs):
+            raise ValueError("Input cloud_data size is not a multiple of point_step")
+        cp = np.array([x.size // step for x in arrs], dtype=np.uint64)
+        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        return self.sweep_clouds_device(data.ctypes.data, cp, resolutions, points_loc=HOST)
+
+    def sweep_clouds_device(self, points_ptr: int, cloud_points, resolutions, report_ptr: int = 0, points_loc: int = DEVICE):
+        """cldn_hip_sweep_clouds on a raw pointer. report_ptr: device array of n_clouds * n_fields * n_candidates cells (the call
+        only enqueues work when the points are on the device; returns None), 0 = host report (returned)."""
+        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
+        res = _ladders(resolutions, self.plan.n_fields)
+        rep = None if report_ptr else self._sweep_report(cp.size, res.shape[1])
+        _check(lib().cldn_hip_sweep_clouds(self._h, C.c_void_p(points_ptr), points_loc, cp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           cp.size, res.ctypes.data_as(C.c_void_p), res.shape[1],
+                                           C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                           DEVICE if report_ptr else HOST))
+        return rep
+
+    def sweep_last_encode(self, resolutions, report_ptr: int = 0):
+        """cldn_hip_sweep_last_encode: the points of this codec's most recent encode call (the survivors of a viz call), one row
+        per cloud of that call. Valid from the encode call on (a chunk table need not be framed); leaves the state for
+        audit_last_encode as it found it. Raises CloudiniHipError (ARG) when another call came between."""
+        n = int(lib().cldn_hip_sweep_last_encode_clouds(self._h))
+        _check(n)
+        res = _ladders(resolutions, self.plan.n_fields)
+        rep = None if report_ptr else self._sweep_report(n, res.shape[1])
+        _check(lib().cldn_hip_sweep_last_encode(self._h, res.ctypes.data_as(C.c_void_p), res.shape[1],
+                                                C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
                                                 DEVICE if report_ptr else HOST))
         return rep

@@ -151,6 +151,14 @@ struct TranscodeOptions {
   // resolution (0 for a field without one) unless audit_limits names the field.
   bool audit = false;
   std::map<std::string, double> audit_limits;
+  // Resolution sweep (include/cloudini_hip.h, cldn_hip_sweep_last_encode): field name -> ladder of candidate resolutions (at
+  // most 16, each > 0). Behind the encode call of every schema run (and behind its audit) the GPU stage sweeps the points it
+  // encoded (with viz_lossy: the survivors, chosen at the CURRENT xyz resolution) and adds, per field name and resolution, what
+  // the field would cost and lose at that resolution to TranscodeStats::sweep. "xyz" stands for the fields x, y and z that have
+  // no entry of their own, as in the reference's profile strings. A name that a message's schema lacks, or whose field the
+  // codec does not encode with a lossy float encoder there, is ignored for that message. The output is what it is without the
+  // sweep. Not available together with `decode`.
+  std::map<std::string, std::vector<float>> sweep;
   // Test hook (tests/cpp/transcoder_order.cpp, runs without a GPU): when set, `test_workers` stage threads call it instead of
   // the GPU stage and stage 2 passes the batch on untouched -- what remains is the pipeline itself: batches handed to
   // whichever stage is free, the writer putting them back into input order, an error on any stage stopping all of them.
@@ -170,6 +178,16 @@ struct AuditFieldSummary {
   bool bad() const { return n_class_diff != 0 || n_over_limit != 0 || (!is_float && n_bitwise_diff != 0); }
 };
 
+// One field name at one candidate resolution over all messages of a run of the transcoder (cldn_hip_sweep_cell_t summed).
+struct SweepCellSummary {
+  std::string name;
+  float resolution = 0;
+  uint64_t bytes = 0;          // stage-1 bytes of the field's tokens at this resolution
+  uint64_t points = 0;         // points of the messages that were swept for it
+  uint64_t n_class_diff = 0, n_over_limit = 0;
+  double max_abs_err = 0;
+};
+
 struct TranscodeStats {
   uint64_t messages = 0, points = 0, input_bytes = 0, output_bytes = 0, gpu_batches = 0;
   // seconds_gpu: summed over the GPU stages. With viz_lossy it covers the fused filter + encode call of every schema run, the
@@ -183,7 +201,18 @@ struct TranscodeStats {
     return true;
   }
   void mergeAudit(const std::vector<AuditFieldSummary>& other);
+  std::vector<SweepCellSummary> sweep;   // TranscodeOptions::sweep: one entry per field name and resolution, in order of first appearance
+  void mergeSweep(const std::vector<SweepCellSummary>& other);
 };
+
+// The reference's profile strings (McapConverter::addProfile, tools/src/mcap_converter.cpp:325-353):
+// "xyz:0.001; intensity:0.1; ring:remove" -- `name:resolution` entries separated by ';', "remove" = resolution 0 (the field is
+// dropped), "xyz" = x, y and z. A trailing ';' is allowed. Throws std::invalid_argument for anything else (no ':', an empty
+// name, a value that is not a finite number >= 0).
+cloudini_ros::ResolutionProfile parseProfileString(const std::string& text);
+// The sweep's counterpart: "xyz:0.0005,0.001,0.002; intensity:0.05,0.1,1" -- 1 to 16 finite resolutions > 0 per name. "xyz" is
+// kept as a name (TranscodeOptions::sweep resolves it).
+std::map<std::string, std::vector<float>> parseSweepString(const std::string& text);
 
 template <typename T>
 T* PinnedAllocator<T>::allocate(size_t n) {

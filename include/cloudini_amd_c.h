@@ -99,6 +99,16 @@ int64_t cldn_amd_transcode_directory_audit(const char* in_dir, const char* out_d
                                            const char* const* limit_names, const double* limit_values, uint32_t n_limits,
                                            double* stats_out, char* audit_json, uint64_t audit_capacity);
 
+/* cldn_amd_transcode_directory_on with a resolution sweep behind every encode call (TranscodeOptions::sweep;
+ * include/cloudini_hip.h, cldn_hip_sweep_last_encode): the files are the same, sweep_json receives one line of JSON -- a list of
+ * {"name", "resolution", "bytes", "points", "n_class_diff", "n_over_limit", "max_abs_err"}, sums over all messages per field
+ * name and candidate resolution (max_abs_err: the largest). sweep_names[i] has ladder_sizes[i] (1..16) resolutions; the
+ * ladders lie back to back in `ladders`. "xyz" names x, y and z. A sweep_capacity that is too small is an error (-1). */
+int64_t cldn_amd_transcode_directory_sweep(const char* in_dir, const char* out_dir, float resolution, uint8_t compression_opt,
+                                           int viz_lossy, uint32_t batch_messages, const int32_t* devices, uint32_t n_devices,
+                                           const char* const* sweep_names, const uint32_t* ladder_sizes, const float* ladders,
+                                           uint32_t n_names, double* stats_out, char* sweep_json, uint64_t sweep_capacity);
+
 /* Stage-2 (LZ4 / ZSTD) threads a single encode()/decode() call with use_threads may occupy, the caller included.
  * The reference's flag means one extra worker (cloudini_lib/src/cloudini.cpp:453-499); here the pool is bounded:
  * default min(4, hardware threads), overridden by the environment variable CLOUDINI_AMD_STAGE2_THREADS (read once)

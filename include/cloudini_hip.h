@@ -375,6 +375,61 @@ int cldn_hip_audit_last_encode(cldn_hip_codec_t* codec, const double* limit, cld
 /* clouds of the call cldn_hip_audit_last_encode would audit (the rows its report needs), or CLDN_HIP_ERR_ARG */
 int64_t cldn_hip_audit_last_encode_clouds(const cldn_hip_codec_t* codec);
 
+/* Resolution sweep: what would each candidate resolution of each lossy float field cost and buy, BEFORE one is chosen? One read
+ * of the points gives, per cloud k, field f and candidate c, the exact stage-1 byte count of the field's tokens and the exact
+ * figures cldn_hip_audit_* would report for a round trip at that resolution: report[(k * n_fields + f) * n_candidates + c].
+ * tests/sweep_model.py restates the record in numpy.
+ *
+ * The format makes this exact: a lossy float field's token at point i depends only on that field's value at i and at i - 1
+ * (the reference is 0 at cloud-local indexes that are multiples of 32768 and behind a NaN); which arithmetic a field gets
+ * (the FloatN group of 3 or 4 leading FLOAT32 fields with a resolution, or the scalar lossy encoder) depends on WHETHER fields
+ * have a resolution, not on its value; the integer sections never look at float resolutions. Hence both identities:
+ *   - for a cloud of n points whose fields are all sweepable, the sum over the fields of `bytes` at the plan's own resolutions
+ *     plus 4 * ceil(n / 32768) is the size of the stream cldn_hip_encode_stage1 writes for it;
+ *   - in general, changing field f from resolution r to r' changes that size by bytes_f(r') - bytes_f(r).
+ * `bytes` covers stage 1 only: LZ4 / ZSTD behind it (on the host or on the device) are not predicted.
+ *
+ * A field is SWEEPABLE when the plan encodes it with a lossy float encoder: FLOAT32 or FLOAT64 with a resolution under
+ * encoding_opt LOSSY. The arithmetic is the encoder's and the decoder's own: a FloatN field quantises with m = 1.0f / r, rounds
+ * half to even into int32 (0x80000000 out of range) and takes int32 wrap-around deltas; every other lossy float quantises with
+ * m = T(1.0 / double(T(r))), rounds half away from zero into int64 (INT64_MIN out of range) and takes int64 deltas; a NaN costs
+ * one byte. The decoded value is float(q) * r (FLOAT64: double(q) * double(r)); the error is taken in double after widening. */
+#define CLDN_HIP_SWEEP_MAX_CANDIDATES 16u
+typedef struct cldn_hip_sweep_cell {
+  uint64_t bytes;        /* bytes of this field's tokens in the cloud's regular streams if the field had this resolution */
+  uint64_t n_class_diff; /* as cldn_hip_audit_field_t, for a round trip at this resolution */
+  uint64_t n_over_limit; /* both sides finite, |double(v) - double(decoded)| > (double)resolution */
+  double max_abs_err;    /* as cldn_hip_audit_field_t */
+} cldn_hip_sweep_cell_t; /* 32 bytes */
+
+/* resolutions: HOST array [n_fields * n_candidates] of float32, one ladder per field of the plan's schema (fields have different
+ * scales): resolutions[f * n_candidates + c]. The ladder of a field that is not sweepable is ignored and its cells are zero. In
+ * a sweepable field an entry of 0 means "skip" (its cell is zero); an entry that is negative, NaN or inf, or whose float32
+ * reciprocal 1.0f / r is 0 or inf, is CLDN_HIP_ERR_ARG, and so is n_candidates == 0 or > CLDN_HIP_SWEEP_MAX_CANDIDATES.
+ * report: [n_clouds * n_fields * n_candidates] cells, HOST or DEVICE per report_loc (DEVICE: 8-byte aligned). Every quantity is
+ * an integer sum or a max of non-negative doubles (ordered like their bits): the report is deterministic to the bit.
+ * Per call, whatever n_clouds: one clear of the report, one kernel (blocks of <= 1024 points, cut per cloud on the host) and one
+ * upload of the block / cloud / field / ladder tables; for a HOST report one copy of it and one synchronisation on top. The
+ * tables and a HOST report use the audit's workspace.
+ *
+ * cldn_hip_sweep_clouds: `points` holds cloud_points[k] points per cloud, back to back, at any byte alignment. HOST points are
+ * uploaded into the audit's workspace (never into the codec's input staging or output buffer). With DEVICE points and a DEVICE
+ * report the call only enqueues work. Like every call that takes buffers it drops the state cldn_hip_audit_last_encode needs.
+ *
+ * cldn_hip_sweep_last_encode: the points of this codec's most recent encode call, read where they lie on the device (see
+ * cldn_hip_audit_last_encode). It needs the points only, so it is also valid between cldn_hip_encode_stage1_chunks and
+ * cldn_hip_frame_chunks. It leaves the state as it found it: it may be repeated, and cldn_hip_audit_last_encode may follow.
+ * After a viz encode the points are the SURVIVORS, kept_points[k] per cloud -- and those survivors were chosen by the filter at
+ * the resolution of THAT call: a sweep over them says what other xyz resolutions do to the same survivors, not which points
+ * another resolution would have let through. Without such a state the call is CLDN_HIP_ERR_ARG in the audit's wording.
+ * cldn_hip_sweep_last_encode_clouds: the clouds (report rows) of that call, or CLDN_HIP_ERR_ARG. */
+int cldn_hip_sweep_clouds(cldn_hip_codec_t* codec, const void* points, int points_loc, const uint64_t* cloud_points,
+                          uint32_t n_clouds, const float* resolutions, uint32_t n_candidates, cldn_hip_sweep_cell_t* report,
+                          int report_loc);
+int cldn_hip_sweep_last_encode(cldn_hip_codec_t* codec, const float* resolutions, uint32_t n_candidates,
+                               cldn_hip_sweep_cell_t* report, int report_loc);
+int64_t cldn_hip_sweep_last_encode_clouds(const cldn_hip_codec_t* codec);
+
 /* What a decode call may do to the bytes of a point that no field covers. CLDN_HIP_FILL_KEEP (default): they keep the
  * content of points_out (src/field_decoder.cpp:72-76 writes fields only) -- for a HOST buffer of a layout with such bytes
  * that means bringing the buffer to the device first. CLDN_HIP_FILL_ZERO: the caller hands over a buffer whose content

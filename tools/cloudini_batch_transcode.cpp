@@ -8,6 +8,12 @@
 //       decode of what it wrote): one table line per field in front of the JSON line; exit status 3 when a float field changed
 //       class (NaN / inf) or exceeded its limit (its resolution unless --audit-limit names it), or an integer field changed.
 //       The files are written either way, and are the files of a run without --audit.
+//   ... --profile "xyz:0.001; intensity:0.1; ring:remove"   the reference's profile string (tools/src/mcap_converter.cpp:325-353):
+//       a resolution per field name, "remove" drops the field, "xyz" names x, y and z; fields it does not name keep --resolution.
+//   ... --sweep "xyz:0.0005,0.001,0.002,0.005; intensity:0.05,0.1,1"   what would each of these resolutions cost and lose? Every
+//       encode call's points are swept on the device (cldn_hip_sweep_last_encode): one `sweep` table line per field and
+//       resolution in front of the JSON line -- stage-1 bytes, bytes per point, class_diff, over_limit, max_abs_err. The files
+//       are the files of a run without --sweep. Not available with --decode. Malformed strings: exit status 2.
 //   ... --devices 0,1,2,3   spreads the batches over these GPUs (one GPU stage per entry; "0,0" = two stages on GPU 0)
 //   cloudini_batch_transcode <in.mcap> <out.mcap> [...same options] [--mcap-compression none|lz4|zstd]
 //       a bag: point-cloud messages converted, everything else copied (McapConverter, tools/src/mcap_converter.cpp:141-300);
@@ -16,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
 #include <string>
 
 #include "cloudini_amd/batch_transcoder.hpp"
@@ -29,6 +36,15 @@ static bool printAudit(const cloudini_amd::TranscodeStats& st) {
                 (unsigned long long)f.n_class_diff, (unsigned long long)f.n_over_limit, f.max_abs_err,
                 f.first_bad_message.empty() ? "-" : f.first_bad_message.c_str());
   return st.auditClean();
+}
+
+// one line per field and candidate resolution
+static void printSweep(const cloudini_amd::TranscodeStats& st) {
+  std::printf("sweep %-24s %14s %16s %12s %12s %12s %24s\n", "field", "resolution", "bytes", "bytes/point", "class_diff", "over_limit", "max_abs_err");
+  for (const cloudini_amd::SweepCellSummary& s : st.sweep)
+    std::printf("sweep %-24s %14.9g %16llu %12.4f %12llu %12llu %24.17g\n", s.name.c_str(), (double)s.resolution,
+                (unsigned long long)s.bytes, s.points ? (double)s.bytes / (double)s.points : 0.0, (unsigned long long)s.n_class_diff,
+                (unsigned long long)s.n_over_limit, s.max_abs_err);
 }
 
 int main(int argc, char** argv) {
@@ -62,6 +78,15 @@ int main(int argc, char** argv) {
       opt.audit_limits[v.substr(0, colon)] = lim;
       opt.audit = true;
     }
+    else if ((a == "--profile" || a == "--sweep") && i + 1 < argc) {
+      try {
+        if (a == "--profile") opt.profile = cloudini_amd::parseProfileString(argv[++i]);
+        else opt.sweep = cloudini_amd::parseSweepString(argv[++i]);
+      } catch (const std::invalid_argument& e) {
+        std::fprintf(stderr, "%s: %s\n", a.c_str(), e.what());
+        return 2;
+      }
+    }
     else if (a == "--batch" && i + 1 < argc) opt.batch_messages = (size_t)std::strtoul(argv[++i], nullptr, 10);
     else if (a == "--devices" && i + 1 < argc) {
       for (const char* p = argv[++i]; *p;) {
@@ -79,11 +104,16 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (opt.decode && !opt.sweep.empty()) {
+    std::fprintf(stderr, "--sweep is not available with --decode\n");
+    return 2;
+  }
   try {
     const std::string in_path = argv[1];
     if (in_path.size() > 5 && in_path.compare(in_path.size() - 5, 5, ".mcap") == 0) {
       const cloudini_amd::McapTranscodeStats ms = cloudini_amd::transcodeMcap(in_path, argv[2], opt, mcap_comp);
       const bool clean = !opt.audit || printAudit(ms.pipeline);
+      if (!opt.sweep.empty()) printSweep(ms.pipeline);
       std::printf("{\"messages\": %llu, \"converted\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"points\": %llu, "
                   "\"seconds_total\": %.6f, \"gpu_batches\": %llu, \"peak_held_bytes\": %llu}\n",
                   (unsigned long long)ms.messages, (unsigned long long)ms.converted, (unsigned long long)ms.input_bytes,
@@ -103,6 +133,7 @@ int main(int argc, char** argv) {
     cloudini_amd::DirectorySink sink(argv[2]);
     const cloudini_amd::TranscodeStats st = cloudini_amd::transcodePointClouds(source, sink, opt);
     const bool clean = !opt.audit || printAudit(st);
+    if (!opt.sweep.empty()) printSweep(st);
     std::printf("{\"messages\": %llu, \"points\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"gpu_batches\": %llu, "
                 "\"seconds_total\": %.6f, \"seconds_gpu\": %.6f, \"seconds_stage2\": %.6f, \"gpu_stages\": %llu, \"Mpoints_per_s\": %.1f}\n",
                 (unsigned long long)st.messages, (unsigned long long)st.points, (unsigned long long)st.input_bytes,
