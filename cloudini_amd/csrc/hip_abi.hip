@@ -181,7 +181,8 @@ struct cldn_hip_codec {
   bool own_stream = false;
   // workspace (grow-only)
   DevBuf d_in, d_out, d_slots, d_chunks, d_cloud_first, d_payload, d_dst, d_offsets, d_modes;
-  // zeroed once per encode call: [status block 256 B | k_finish anchors | section-handled flags | segment table]
+  // zeroed once per encode call (by a memset, or by the piece kernel where it is the call's first launch):
+  // [status block 256 B | k_finish anchors | section-handled flags | segment table]
   DevBuf d_status;
   DevBuf d_cols[kMaxAdaptive];
   DevBuf d_ranks[kMaxAdaptive];
@@ -963,17 +964,24 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   const uint64_t wide_slot = (((uint64_t)kPointsPerChunk * ((uint64_t)plan.max_regular_bytes + 11ull * n_adaptive) + 16ull * n_adaptive + 64ull) + 255ull) & ~255ull;
   const uint64_t slot_stride = wide ? wide_slot : reg_stride + (uint64_t)n_adaptive * kSectionStride;
 
-  // one zero-filled block per call (one memset launch instead of three)
+  // one zero-filled block per call (one memset launch instead of three; none where the piece kernel clears it, see below)
   const size_t z_anchor = 256;
   const size_t z_anchor2 = z_anchor + (((size_t)(n_chunks / 1024u + 1u) * 8u + 63u) & ~size_t(63));  // framing of the LZ4 blocks
   const size_t z_flags = z_anchor2 + (((size_t)(n_chunks / 1024u + 1u) * 8u + 63u) & ~size_t(63));
   const size_t z_segs = (z_flags + (size_t)n_chunks * std::max(1u, n_adaptive) + 63u) & ~size_t(63);
   const size_t z_bytes = z_segs + std::max<size_t>(16, (size_t)n_chunks * segs_per_chunk * sizeof(Seg));
+  const size_t status_cap_before = c->d_status.cap;
   if ((rc = c->d_status.ensure(z_bytes)) != CLDN_HIP_OK) return rc;
   if ((rc = c->d_offsets.ensure((size_t)(n_clouds + 1) * sizeof(uint64_t))) != CLDN_HIP_OK) return rc;
   if ((rc = c->d_modes.ensure(std::max<size_t>(1, (size_t)n_clouds * std::max(1u, n_adaptive)))) != CLDN_HIP_OK)
     return rc;
-  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, z_bytes, c->stream));
+  // Framed calls whose first launch is the piece kernel: that launch zeroes what the call needs zeroed of the block (FusedArgs::clear:
+  // status block, anchors, flags, the segment entries its workgroups do not write) -- the memset was a launch and a dependent
+  // boundary on the stream in front of every call. Every other path keeps it: the generic, fixed and WIDE kernels, chunk tables
+  // (intra placement), LZ4 calls (second anchor array), a Gorilla pre-pass in front of the piece kernel, n_chunks == 0, and the
+  // one call that got a new allocation.
+  const bool kernel_clears = pieces && !intra && !table && !lz4 && plan.n_gorilla == 0u && c->d_status.cap == status_cap_before;
+  if (!kernel_clears) HIP_TRY(hipMemsetAsync(c->d_status.p, 0, z_bytes, c->stream));
   // a batch without a single point launches no probe: its clouds commit mode 0 (DeltaVarint), like an encode() call of
   // the reference that never reaches the analysis (src/v5_codec.cpp:934-949)
   if (n_chunks == 0 && n_clouds && n_adaptive) HIP_TRY(hipMemsetAsync(c->d_modes.p, 0, (size_t)n_clouds * n_adaptive, c->stream));
@@ -1106,6 +1114,10 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
     L.modes_forced = true;
   }
   L.fallback_flags = (uint8_t*)c->d_status.p + z_flags;
+  L.kernel_clears = kernel_clears;
+  // device-resident outputs: the probe workgroups of the piece kernel write the caller's modes array as well (a byte store
+  // fits any address); where another kernel decides the modes, or the caller forced them, the copy behind the call stays
+  L.caller_modes = (out_loc == CLDN_HIP_DEVICE && !lz4 && !table && !L.modes_forced) ? modes : nullptr;
   L.fin_rec = (unsigned long long*)c->d_finrec.p;
   L.fin_rec2 = L.fin_rec + n_chunks;
   L.fin_anchor = (unsigned long long*)((uint8_t*)c->d_status.p + z_anchor);
@@ -1128,7 +1140,8 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   const size_t n_slots = c->slot_valid.size();
   const size_t slot = n_slots ? (size_t)(c->call_index % n_slots) : 0;
   L.events = n_slots ? &c->events[slot * 5] : nullptr;
-  rc = stage1_launch_encode(L);
+  bool modes_in_place = false;  // the kernels wrote the caller's modes array
+  rc = stage1_launch_encode(L, &modes_in_place);
   if (rc != CLDN_HIP_OK) return rc;
   const void* d_sizes = c->d_payload.p;  // what chunk_sizes reports
   if (lz4 && n_chunks) {
@@ -1245,7 +1258,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
     if (chunk_sizes && n_chunks && !direct_sizes)
       HIP_TRY(hipMemcpyAsync(chunk_sizes, d_sizes, (size_t)n_chunks * sizeof(uint32_t),
                              hipMemcpyDeviceToDevice, c->stream));
-    if (modes && modes_bytes)
+    if (modes && modes_bytes && !modes_in_place)
       HIP_TRY(hipMemcpyAsync(modes, c->d_modes.p, modes_bytes, hipMemcpyDeviceToDevice, c->stream));
     return CLDN_HIP_OK;
   }

@@ -206,6 +206,17 @@ struct FusedArgs {
   uint32_t epoch;
   unsigned long long* wgrec;     // [n_chunks * 32]
   uint32_t* status;
+  // clear != 0 (never with intra): the launch zeroes what the call's later launches expect zeroed, so that no memset runs in
+  // front of it (a launch and a dependent boundary on the stream per call). Per chunk, by the workgroup of its quad 0: the
+  // segment entries [P/4, segs_per_chunk) -- the regular entries a short chunk does not use and the two per adaptive field --
+  // and the chunk's n_adaptive fallback flags. Once, by the first piece workgroup: the 256-byte status block (status word,
+  // counters, k_finish's ticket, contiguity flag) and k_finish's anchors. No workgroup of this launch reads or writes any of
+  // these (the status word is touched by the intra branch only); every reader runs in a later launch of the stream.
+  uint32_t clear;
+  uint32_t n_anchor;             // words of `anchor`
+  unsigned long long* anchor;
+  uint8_t* flags;                // [n_chunks * n_adaptive]
+  uint8_t* modes_out;            // the caller's modes array (any address) or NULL: the probe workgroups store there as well
 };
 
 // UNAL / L3 / LOADW: see kFusedKernels (stage1_kernels.hip), the layouts the kernel is instantiated for.
@@ -233,9 +244,10 @@ __device__ __forceinline__ void fused_body(const DevPlan& plan, const FusedArgs&
   if (blockIdx.x < A.n_probe) {  // uniform: a mode-probe workgroup
     const uint32_t cloud = blockIdx.x / na, a = blockIdx.x - cloud * na;
     uint8_t* mode_out = A.modes + (size_t)cloud * na + a;
+    uint8_t* mode_out2 = A.modes_out ? A.modes_out + (size_t)cloud * na + a : mode_out;  // (the same byte twice: no branch at the stores)
     const uint32_t fc = A.cloud_first_chunk[cloud];
     if (fc == A.cloud_first_chunk[cloud + 1u]) {  // empty cloud
-      if (tid == 0u) *mode_out = 0u;
+      if (tid == 0u) *mode_out = *mode_out2 = 0u;
       return;
     }
     const ChunkDesc cd = A.chunks[fc];
@@ -253,7 +265,7 @@ __device__ __forceinline__ void fused_body(const DevPlan& plan, const FusedArgs&
     else
       mode = probe_mode_t<uint32_t, (int)kFusedThreads>([&](uint32_t i) { return (uint32_t)aos_field(fp + (size_t)i * pstep, 4u); }, n, f_type,
                                                         smem, slots, wtot);
-    if (tid == 0u) *mode_out = mode;
+    if (tid == 0u) *mode_out = *mode_out2 = mode;
     return;
   }
   const uint32_t g = (blockIdx.x - A.n_probe) * kFusedWaves + wave;  // my piece
@@ -662,6 +674,20 @@ __device__ __forceinline__ void fused_body(const DevPlan& plan, const FusedArgs&
     sg.off = seg_off;
     sg.size = total;
     A.segs[(size_t)pd.chunk * A.segs_per_chunk + quad] = sg;
+  }
+  // FusedArgs::clear -- behind the piece's work, where nothing of it is live any more
+  if (A.clear) {
+    if (quad == 0u) {  // uniform: pd.chunk, pd.P and quad are the same for the four pieces of a workgroup
+      Seg* cs = A.segs + (size_t)pd.chunk * A.segs_per_chunk;
+      Seg zero;
+      zero.off = zero.size = 0u;
+      for (uint32_t i = (pd.P >> 2) + tid; i < A.segs_per_chunk; i += kFusedThreads) cs[i] = zero;
+      if (tid < na) A.flags[(size_t)pd.chunk * na + tid] = 0u;
+    }
+    if (blockIdx.x == A.n_probe) {  // the first piece workgroup, with or without probe workgroups in front of it
+      if (tid < 64u) A.status[tid] = 0u;
+      for (uint32_t i = tid; i < A.n_anchor; i += kFusedThreads) A.anchor[i] = 0ull;
+    }
   }
 }
 

@@ -1552,6 +1552,10 @@ static int launch_fused(const EncodeLaunch& L, hipStream_t stream, uint32_t piec
   A.epoch = L.fin_epoch;
   A.wgrec = L.wgrec;
   A.status = L.status;
+  A.clear = (L.kernel_clears && !L.intra && piece0 == 0u && piece1 == L.n_pieces) ? 1u : 0u;
+  A.n_anchor = L.n_chunks / 1024u + 1u;
+  A.anchor = L.fin_anchor;
+  A.flags = L.fallback_flags;
   A.tail_kind = 0u;
   A.tail_rel = 0u;
   A.tail_size = 0u;
@@ -1573,6 +1577,7 @@ static int launch_fused(const EncodeLaunch& L, hipStream_t stream, uint32_t piec
     if (wide) lds = std::max(lds, 6144u * 4u + 272u);
   }
   A.probe_lds = lds;
+  A.modes_out = A.n_probe ? L.caller_modes : nullptr;
   if (probed) *probed = A.n_probe != 0u;
   const dim3 grid(A.n_probe + (piece1 - piece0) / kFusedWaves), block(kFusedThreads);
   hipLaunchKernelGGL(v.k->kernel, grid, block, lds, stream, *L.plan, A);
@@ -1742,8 +1747,9 @@ static int launch_encode_wide(const EncodeLaunch& L) {
   return CLDN_HIP_OK;
 }
 
-int stage1_launch_encode(const EncodeLaunch& L) {
+int stage1_launch_encode(const EncodeLaunch& L, bool* wrote_caller_modes) {
   hipError_t e;
+  if (wrote_caller_modes) *wrote_caller_modes = false;
   if (L.wide) return launch_encode_wide(L);
   // the field whose Palette sections k_finish builds itself: the first 2- or 4-byte adaptive field that may commit Palette
   uint32_t fused_field = kNoFusedField;
@@ -1770,6 +1776,7 @@ int stage1_launch_encode(const EncodeLaunch& L) {
   if (L.n_chunks && L.pieces) {  // slot pipeline, regular stream by the barrier-free piece kernel
     const int rc = launch_fused(L, L.stream, 0u, L.n_pieces, &modes_probed);
     if (rc != CLDN_HIP_OK) return rc;
+    if (wrote_caller_modes) *wrote_caller_modes = modes_probed && L.caller_modes != nullptr;
   } else if (L.n_chunks && fixed_point_bytes(*L.plan) != 0u) {
     // every per-point encoder writes a fixed number of bytes (lossless floats, raw copies): one thread per point, which also
     // splits the integer fields off into their columns

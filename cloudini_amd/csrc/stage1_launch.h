@@ -60,6 +60,13 @@ struct EncodeLaunch {
   uint32_t n_pieces;          // multiple of 4
   bool intra;                 // the piece kernel's workgroups place a chunk's regular stream contiguously (subs == 1)
   unsigned long long* wgrec;  // device [n_chunks * 32]: their look-back records, tagged with fin_epoch
+  // The piece kernel's launch zeroes what the call's kernels expect zeroed -- the status block, fin_anchor, every chunk's
+  // fallback_flags and the segment entries its own workgroups do not write -- so the caller enqueued no memset for them.
+  // Only with `pieces`, without `intra` / `chunks_only` and without a Gorilla pre-pass (the piece kernel is the call's first launch).
+  bool kernel_clears;
+  // the caller's device array [n_clouds * n_adaptive] or NULL: the piece kernel's probe workgroups store every mode there as
+  // well as to `modes`. stage1_launch_encode reports through its out flag whether they did (else the caller copies `modes`).
+  uint8_t* caller_modes;
   // WIDE route (stage1_wide.h): schemas beyond the launch-argument plan. wide != NULL: `plan` holds only the scalar members,
   // subs == 1 and segs_per_chunk == 1 (one segment per chunk), the slots take a chunk's whole payload.
   const WidePlan* wide;       // host copy of the descriptor (its arrays are device memory), or NULL
@@ -148,7 +155,7 @@ inline hipError_t allow_lds(Kernel* kernel, uint32_t lds) {
 
 int stage1_configure_kernels();
 int stage1_configure_decode();   // decode TU (stage1_decode.hip); called by stage1_configure_kernels
-int stage1_launch_encode(const EncodeLaunch& L);
+int stage1_launch_encode(const EncodeLaunch& L, bool* wrote_caller_modes = nullptr);  // (the flag: see EncodeLaunch::caller_modes)
 int stage1_launch_decode(const DecodeLaunch& L);
 int stage1_launch_decode_unframed(const DevPlan& plan, hipStream_t stream, const uint8_t* payload, uint32_t size,
                                   uint32_t capacity_points, void* chunk_slot, uint8_t* out, uint32_t* status,

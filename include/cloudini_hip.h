@@ -116,7 +116,9 @@ int cldn_hip_codec_device(const cldn_hip_codec_t* codec); /* device the codec wa
  * stream_offsets / chunk_sizes / modes live where `out` lives (out_loc).
  * Alignment: `points` and `out` may have ANY byte alignment, host or device (a stream often follows a header of odd length;
  * tests/test_gpu_encode.py::test_device_buffers_at_any_address). Device-resident stream_offsets (8-byte aligned) and chunk_sizes
- * (4-byte aligned) are written by the kernels in place; at other alignments they are filled by a copy behind the kernels. */
+ * (4-byte aligned) are written by the kernels in place; at other alignments they are filled by a copy behind the kernels.
+ * A device-resident `modes` array (any address) is, like stream_offsets and chunk_sizes, written in place by the kernels of
+ * the call where they decide the modes, and its content is undefined unless the call's status (cldn_hip_codec_status) is OK. */
 int cldn_hip_encode_stage1(cldn_hip_codec_t* codec, const void* points, int points_loc,
                            const uint64_t* cloud_points, uint32_t n_clouds, void* out, uint64_t out_capacity,
                            int out_loc, uint64_t* stream_offsets, uint32_t* chunk_sizes, uint8_t* modes);
