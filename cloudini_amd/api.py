@@ -77,6 +77,10 @@ def lib() -> C.CDLL:
     L.cldn_amd_transcode_directory_sweep.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32,
                                                      C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32),
                                                      C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_double), C.c_char_p, C.c_uint64]
+    L.cldn_amd_transcode_directory_modes.restype = C.c_int64
+    L.cldn_amd_transcode_directory_modes.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32,
+                                                     C.POINTER(C.c_int32), C.c_uint32, C.c_int, C.POINTER(C.c_double), C.c_char_p,
+                                                     C.c_uint64]
     L.cldn_amd_transcode_directory.restype = C.c_int64
     L.cldn_amd_transcode_directory.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32, C.POINTER(C.c_double)]
     L.cldn_amd_decode_directory.restype = C.c_int64
@@ -173,7 +177,7 @@ def _device_list(devices):
 
 def transcode_directory(in_dir: str, out_dir: str, resolution: float = 0.001, compression_opt: int = 2,
                         viz_lossy: bool = False, batch_messages: int = 64, devices=None, audit: bool = False,
-                        audit_limits=None, sweep=None) -> dict:
+                        audit_limits=None, sweep=None, modes=None) -> dict:
     """Batch transcoder (include/cloudini_amd/batch_transcoder.hpp): every CDR PointCloud2 file of in_dir ->
     CompressedPointCloud2 file of the same name in out_dir. `devices`: GPUs to spread the batches over (one GPU stage per
     entry; None = the current device). Returns the statistics. audit=True: every encode call is audited on the device
@@ -182,11 +186,29 @@ def transcode_directory(in_dir: str, out_dir: str, resolution: float = 0.001, co
     fields that should not be held to their resolution. sweep={field name: [resolutions]} ("xyz" names x, y and z; at most 16
     per name): the points of every encode call are swept on the device (cldn_hip_sweep_last_encode) and "sweep" holds, per
     field name and resolution, a dict (name, resolution, bytes, points, n_class_diff, n_over_limit, max_abs_err) -- what the
-    field would cost in stage-1 bytes and lose at that resolution. The files are those of a run without it. One of audit and
-    sweep per call."""
+    field would cost in stage-1 bytes and lose at that resolution. The files are those of a run without it.
+    modes="report": the adaptive integer modes of every encode call's points are swept on the device
+    (cldn_hip_sweep_modes_last_encode) and "modes" holds {"reencoded_runs", "fields": [per integer field name: clouds, bytes
+    under DeltaVarint / Palette / Rle / DeltaRle, clouds probed into and best in each mode, saved_bytes]}; the files are those
+    of a run without it. modes="best": a schema run in which a cloud's best mode differs from the probed one is encoded again
+    with the best modes forced -- those messages are NOT the reference encoder's bytes, but valid streams that every Cloudini
+    decoder decodes to the same points. One of audit, sweep and modes per call."""
     st = (C.c_double * 8)()
     dv, nd = _device_list(devices)
     keys = ("messages", "points", "input_bytes", "output_bytes", "gpu_batches", "seconds_total", "seconds_gpu", "seconds_stage2")
+    if modes not in (None, "off", "report", "best"):
+        raise ValueError("transcode_directory: modes is 'off', 'report' or 'best'")
+    if modes in ("report", "best"):
+        if audit or sweep:
+            raise ValueError("transcode_directory: audit, sweep and modes are separate calls")
+        import json
+        text = C.create_string_buffer(1 << 20)
+        _check(lib().cldn_amd_transcode_directory_modes(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
+                                                        1 if viz_lossy else 0, batch_messages, dv, nd, 1 if modes == "best" else 0,
+                                                        st, text, len(text)))
+        out = dict(zip(keys, [float(x) for x in st]))
+        out["modes"] = json.loads(text.value.decode())
+        return out
     if sweep:
         if audit:
             raise ValueError("transcode_directory: audit and sweep are separate calls")
@@ -350,3 +372,21 @@ def applyVizLossyPreprocessing(info, cloud):
     n = _check(lib().cldn_amd_viz_preprocess(C.byref(ci), _ptr(data) if data.size else None, data.size, _ptr(out),
                                              out.size, res, C.byref(w), C.byref(h)))
     return out[:n].copy(), [None if x != x else float(x) for x in list(res)[: len(info.fields)]], int(w.value), int(h.value)
+
+
+# ---- adaptive integer modes on raw clouds (cldn_hip_sweep_modes_*, cldn_hip_codec_force_modes_per_cloud) -----------------
+
+def sweep_modes(info, clouds):
+    """Per cloud and adaptive integer field of `info`'s schema: the section bytes under each of the four V5 modes, the mode the
+    reference's probe commits and the best mode over the whole cloud (native.MODE_DTYPE, shape (n_clouds, adaptive fields))."""
+    from . import native
+    return native.Codec(native.Plan(info)).sweep_modes_host(clouds)
+
+
+def encode_stage1_with_modes(info, clouds, modes):
+    """Framed stage-1 streams of `clouds` with the adaptive integer modes forced per cloud (modes: (n_clouds, adaptive fields),
+    e.g. sweep_modes(...)["best_mode"]). Valid Cloudini streams, not the reference encoder's bytes where a mode differs."""
+    from . import native
+    codec = native.Codec(native.Plan(info))
+    codec.force_modes_per_cloud(modes)
+    return codec.encode_host(clouds)[0]

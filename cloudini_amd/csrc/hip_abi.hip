@@ -170,6 +170,7 @@ struct cldn_hip_plan {
   std::vector<DevOp> ops_all;
   std::vector<uint32_t> op_aux;          // OP_GORILLA64: index of the op's token buffer
   std::vector<DevAdaptive> adaptive_all;
+  std::vector<uint32_t> adaptive_field;  // index of each adaptive field among the schema's fields
   uint32_t n_gorilla_all = 0;
   uint32_t n_adaptive_total() const { return wide ? (uint32_t)adaptive_all.size() : dev.n_adaptive; }
 };
@@ -262,6 +263,9 @@ struct cldn_hip_codec {
   uint64_t call_index = 0;
   // modes committed elsewhere (continuation of a cloud from a chunk boundary); empty = probe
   std::vector<uint8_t> forced_modes;
+  // cldn_hip_codec_force_modes_per_cloud: [forced_clouds * adaptive fields], one row per cloud; the two setters replace each other
+  std::vector<uint8_t> forced_cloud_modes;
+  uint32_t forced_clouds = 0;
   // audit (audit_kernels.hip): d_audit takes host buffers of an audit call and the decode of an audited stream, d_audit_tab the
   // cloud / block / field tables, d_audit_rep the report of a call with a HOST report
   DevBuf d_audit, d_audit_tab, d_audit_rep;
@@ -426,6 +430,7 @@ int cldn_hip_plan_create(const cldn_hip_field_t* fields, uint32_t n_fields, uint
       a.type = f.type;
       a.bpv = op.size;
       plan->adaptive_all.push_back(a);
+      plan->adaptive_field.push_back(i);
       continue;
     }
     switch (f.type) {  // CreateCompatibleEncoder, codec_common.cpp:116-153
@@ -525,6 +530,9 @@ int cldn_hip_plan_create(const cldn_hip_field_t* fields, uint32_t n_fields, uint
 void cldn_hip_plan_destroy(cldn_hip_plan_t* plan) { delete plan; }
 int cldn_hip_plan_uses_v5(const cldn_hip_plan_t* plan) { return plan && plan->uses_v5 ? 1 : 0; }
 uint32_t cldn_hip_plan_adaptive_fields(const cldn_hip_plan_t* plan) { return plan ? plan->n_adaptive_total() : 0; }
+uint32_t cldn_hip_plan_adaptive_field_index(const cldn_hip_plan_t* plan, uint32_t a) {
+  return plan && a < plan->adaptive_field.size() ? plan->adaptive_field[a] : 0xffffffffu;
+}
 uint32_t cldn_hip_plan_max_point_bytes(const cldn_hip_plan_t* plan) { return plan ? plan->ref_max_point_bytes : 0; }
 
 uint64_t cldn_hip_stage1_bound(const cldn_hip_plan_t* plan, uint64_t n_points) {  // cloudini.cpp:249-292 (NONE)
@@ -591,6 +599,7 @@ int cldn_hip_codec_create(const cldn_hip_plan_t* plan, int device, void* hip_str
   }
   int rc = stage1_configure_kernels();
   if (rc == CLDN_HIP_OK) rc = lz4_configure_decode();
+  if (rc == CLDN_HIP_OK) rc = modes_configure();
   if (rc == CLDN_HIP_OK && c->plan.wide) {
     // WIDE route: [ops | op_aux | adaptive] in one device buffer, the descriptor that points into it
     const cldn_hip_plan& P = c->plan;
@@ -906,6 +915,9 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   if ((points_loc != CLDN_HIP_HOST && points_loc != CLDN_HIP_DEVICE) ||
       (out_loc != CLDN_HIP_HOST && out_loc != CLDN_HIP_DEVICE))
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  if (c->forced_clouds && c->forced_clouds != n_clouds)
+    return fail(CLDN_HIP_ERR_ARG, "modes are forced for %u clouds (cldn_hip_codec_force_modes_per_cloud), the call has %u",
+                c->forced_clouds, n_clouds);
   ENTER_DEVICE(c->device);
   c->ct_valid = false;  // (the workspace is about to be rewritten)
   c->enc.drop();
@@ -1103,11 +1115,17 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
     c->last_modes_count = 0;
   }
   for (uint32_t a = 0; a < (uint32_t)kMaxAdaptive; ++a) L.mode_hint[a] = c->hint_valid ? c->hint_cache[a] : (uint8_t)0xF;
-  if (!c->forced_modes.empty() && n_adaptive && n_clouds) {
-    for (uint32_t a = 0; a < plan.n_adaptive; ++a) L.mode_hint[a] = (uint8_t)(1u << c->forced_modes[a]);
+  const bool per_cloud = c->forced_clouds != 0u;  // (then forced_clouds == n_clouds)
+  if ((!c->forced_modes.empty() || per_cloud) && n_adaptive && n_clouds) {
+    for (uint32_t a = 0; a < plan.n_adaptive; ++a) {
+      uint8_t hint = per_cloud ? (uint8_t)0 : (uint8_t)(1u << c->forced_modes[a]);
+      for (uint32_t k = 0; per_cloud && k < n_clouds; ++k) hint |= (uint8_t)(1u << c->forced_cloud_modes[(size_t)k * n_adaptive + a]);
+      L.mode_hint[a] = hint;
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));  // the previous call's upload from h_modes has to be over
     if ((rc = c->h_modes.ensure((size_t)n_clouds * n_adaptive)) != CLDN_HIP_OK) return rc;
-    for (uint32_t k = 0; k < n_clouds; ++k)
+    if (per_cloud) memcpy(c->h_modes.p, c->forced_cloud_modes.data(), (size_t)n_clouds * n_adaptive);
+    for (uint32_t k = 0; !per_cloud && k < n_clouds; ++k)
       memcpy((uint8_t*)c->h_modes.p + (size_t)k * n_adaptive, c->forced_modes.data(), n_adaptive);
     HIP_TRY(hipMemcpyAsync(c->d_modes.p, c->h_modes.p, (size_t)n_clouds * n_adaptive, hipMemcpyHostToDevice,
                            c->stream));
@@ -1529,6 +1547,9 @@ static int encode_stage1_viz_impl(cldn_hip_codec_t* c, const void* points, int p
                                   uint32_t* chunk_sizes, uint8_t* modes) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   if (n_clouds && (!cloud_points || !kept_points)) return fail(CLDN_HIP_ERR_ARG, "viz_preprocess: NULL argument");
+  if (c->forced_clouds && c->forced_clouds != n_clouds)  // (before the filter runs: the call does nothing)
+    return fail(CLDN_HIP_ERR_ARG, "modes are forced for %u clouds (cldn_hip_codec_force_modes_per_cloud), the call has %u",
+                c->forced_clouds, n_clouds);
   const uint32_t step = c->plan.point_step;
   int rc;
   if ((rc = viz_check_args(points_loc, out_loc, step, xyz_offset, resolution)) != CLDN_HIP_OK) return rc;
@@ -1675,6 +1696,8 @@ int cldn_hip_codec_force_modes(cldn_hip_codec_t* c, const uint8_t* modes, uint32
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   if (!modes || n_modes == 0) {
     c->forced_modes.clear();
+    c->forced_cloud_modes.clear();
+    c->forced_clouds = 0;
     return CLDN_HIP_OK;
   }
   if (n_modes != c->plan.n_adaptive_total())
@@ -1683,6 +1706,23 @@ int cldn_hip_codec_force_modes(cldn_hip_codec_t* c, const uint8_t* modes, uint32
   for (uint32_t a = 0; a < n_modes; ++a)
     if (modes[a] > 3u) return fail(CLDN_HIP_ERR_ARG, "force_modes: invalid adaptive-int mode %u", modes[a]);
   c->forced_modes.assign(modes, modes + n_modes);
+  c->forced_cloud_modes.clear();
+  c->forced_clouds = 0;
+  return CLDN_HIP_OK;
+}
+
+int cldn_hip_codec_force_modes_per_cloud(cldn_hip_codec_t* c, const uint8_t* modes, uint32_t n_clouds) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  const uint32_t n_adaptive = c->plan.n_adaptive_total();
+  const size_t n = (size_t)n_clouds * n_adaptive;
+  for (size_t i = 0; modes && i < n; ++i)
+    if (modes[i] > 3u) return fail(CLDN_HIP_ERR_ARG, "force_modes_per_cloud: invalid adaptive-int mode %u", modes[i]);
+  c->forced_modes.clear();
+  c->forced_cloud_modes.clear();
+  c->forced_clouds = 0;
+  if (!modes || n_clouds == 0) return CLDN_HIP_OK;  // back to probing
+  c->forced_cloud_modes.assign(modes, modes + n);
+  c->forced_clouds = n_clouds;  // (a plan without adaptive fields: nothing to force, the cloud count is still checked)
   return CLDN_HIP_OK;
 }
 
@@ -2471,6 +2511,140 @@ int cldn_hip_sweep_last_encode(cldn_hip_codec_t* c, const float* resolutions, ui
   if ((rc = sweep_tables(c->plan, resolutions, n_candidates, &fields, &cands)) != CLDN_HIP_OK) return rc;
   ENTER_DEVICE(c->device);
   return sweep_device(c, E.points, E.cloud_points.data(), n_clouds, fields, cands, n_candidates, report, report_loc);
+}
+
+}  // extern "C"
+
+// ---- sweep of the adaptive integer modes: section bytes per mode, probed and best mode (mode_kernels.hip) ----
+
+static int modes_check_report(const cldn_hip_plan& P, uint32_t n_clouds, const void* report, int report_loc) {
+  if (report_loc != CLDN_HIP_HOST && report_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  if (n_clouds && P.n_adaptive_total() && !report) return fail(CLDN_HIP_ERR_ARG, "sweep_modes: report is NULL");
+  if (report_loc == CLDN_HIP_DEVICE && ((uintptr_t)report & 7u)) return fail(CLDN_HIP_ERR_ARG, "sweep_modes: a device report must be 8-byte aligned");
+  return CLDN_HIP_OK;
+}
+
+static int modes_fields(const cldn_hip_plan& P, std::vector<ModeField>* out) {
+  out->assign(P.adaptive_all.size(), ModeField{});
+  for (size_t a = 0; a < P.adaptive_all.size(); ++a) {
+    const DevAdaptive& d = P.adaptive_all[a];
+    if ((d.bpv != 2u && d.bpv != 4u && d.bpv != 8u) || (uint64_t)d.offset + d.bpv > P.point_step)
+      return fail(CLDN_HIP_ERR_ARG, "sweep_modes: adaptive field %zu (offset %u, %u bytes) exceeds point_step %u", a, d.offset,
+                  (unsigned)d.bpv, P.point_step);
+    ModeField& m = (*out)[a];
+    m.offset = d.offset;
+    m.type = d.type;
+    m.bpv = d.bpv;
+  }
+  return CLDN_HIP_OK;
+}
+
+// device points -> report: tables up, one clear, one kernel; HOST report: one copy, one synchronisation
+static int modes_device(cldn_hip_codec* c, const uint8_t* d_points, const uint64_t* cloud_points, uint32_t n_clouds,
+                        const std::vector<ModeField>& fields, cldn_hip_mode_cell_t* report, int report_loc) {
+  static_assert(sizeof(cldn_hip_mode_cell_t) == 40, "five 64-bit words");
+  const uint32_t n_fields = (uint32_t)fields.size();
+  const size_t rep_bytes = (size_t)n_clouds * n_fields * sizeof(cldn_hip_mode_cell_t);
+  if (rep_bytes == 0) return CLDN_HIP_OK;
+  int rc;
+  uint64_t sections = 0;  // per field: the chunks of every cloud and one probe per cloud that has points
+  for (uint32_t k = 0; k < n_clouds; ++k)
+    sections += (cloud_points[k] + kPointsPerChunk - 1u) / kPointsPerChunk + (cloud_points[k] ? 1u : 0u);
+  if (sections * n_fields > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "sweep_modes: more than 2^31 sections");
+  const uint32_t n_units = (uint32_t)(sections * n_fields);
+  const bool dev_fields = n_fields > kAuditArgFields;
+  const size_t clouds_b = ((size_t)n_clouds * sizeof(AuditCloud) + 63u) & ~size_t(63);
+  const size_t units_b = ((size_t)n_units * sizeof(ModeUnit) + 63u) & ~size_t(63);
+  const size_t fields_b = dev_fields ? ((size_t)n_fields * sizeof(ModeField) + 63u) & ~size_t(63) : 0u;
+  const size_t tab_b = clouds_b + units_b + fields_b;
+  if (c->ev_audit) HIP_TRY(hipEventSynchronize(c->ev_audit));  // the previous call's upload has left the staging buffer
+  else HIP_TRY(hipEventCreateWithFlags(&c->ev_audit, hipEventDisableTiming));
+  if ((rc = c->h_audit.ensure(tab_b)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_audit_tab.ensure(tab_b)) != CLDN_HIP_OK) return rc;
+  uint8_t* h = (uint8_t*)c->h_audit.p;
+  AuditCloud* hc = (AuditCloud*)h;
+  ModeUnit* hu = (ModeUnit*)(h + clouds_b);
+  uint64_t first = 0;
+  uint32_t ui = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) {  // chunks first, field inner: the units of a chunk read the same points
+    hc[k].first_point = first;
+    hc[k].n_points = cloud_points[k];
+    first += cloud_points[k];
+    const uint32_t nc = (uint32_t)((cloud_points[k] + kPointsPerChunk - 1u) / kPointsPerChunk);
+    for (uint32_t j = 0; j < nc + (nc ? 1u : 0u); ++j)
+      for (uint32_t a = 0; a < n_fields; ++a) hu[ui++] = ModeUnit{k, j < nc ? j : kModeProbeUnit, a, 0u};
+  }
+  if (dev_fields) memcpy(h + clouds_b + units_b, fields.data(), (size_t)n_fields * sizeof(ModeField));
+  HIP_TRY(hipMemcpyAsync(c->d_audit_tab.p, h, tab_b, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->ev_audit, c->stream));
+  unsigned long long* d_rep = (unsigned long long*)report;
+  if (report_loc == CLDN_HIP_HOST) {
+    if ((rc = c->d_audit_rep.ensure(rep_bytes)) != CLDN_HIP_OK) return rc;
+    d_rep = (unsigned long long*)c->d_audit_rep.p;
+  }
+  const uint8_t* d_tab = (const uint8_t*)c->d_audit_tab.p;
+  ModeLaunch L;
+  L.stream = c->stream;
+  L.points = d_points;
+  L.point_step = c->plan.point_step;
+  L.n_clouds = n_clouds;
+  L.n_units = n_units;
+  L.n_fields = n_fields;
+  L.fields = fields.data();
+  L.dev_fields = dev_fields ? (const ModeField*)(d_tab + clouds_b + units_b) : nullptr;
+  L.clouds = (const AuditCloud*)d_tab;
+  L.units = (const ModeUnit*)(d_tab + clouds_b);
+  L.report = d_rep;
+  if ((rc = modes_launch(L)) != CLDN_HIP_OK) return rc;
+  if (report_loc == CLDN_HIP_HOST) {
+    HIP_TRY(hipMemcpyAsync(report, d_rep, rep_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return CLDN_HIP_OK;
+}
+
+extern "C" {
+
+int cldn_hip_sweep_modes_clouds(cldn_hip_codec_t* c, const void* points, int points_loc, const uint64_t* cloud_points,
+                                uint32_t n_clouds, cldn_hip_mode_cell_t* report, int report_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
+  if (points_loc != CLDN_HIP_HOST && points_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  int rc;
+  if ((rc = modes_check_report(c->plan, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  std::vector<ModeField> fields;
+  if ((rc = modes_fields(c->plan, &fields)) != CLDN_HIP_OK) return rc;
+  uint64_t n_points = 0;
+  if ((rc = audit_batch_points(cloud_points, n_clouds, &n_points)) != CLDN_HIP_OK) return rc;
+  if (fields.empty()) return CLDN_HIP_OK;  // nothing to report
+  if (n_points && !points) return fail(CLDN_HIP_ERR_ARG, "sweep_modes_clouds: points is NULL");
+  ENTER_DEVICE(c->device);
+  const uint64_t bytes = n_points * c->plan.point_step;
+  const uint8_t* d_points = (const uint8_t*)points;
+  const bool up = points_loc == CLDN_HIP_HOST && bytes;
+  if (up) {
+    if ((rc = c->d_audit.ensure((size_t)bytes)) != CLDN_HIP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_audit.p, points, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    d_points = (const uint8_t*)c->d_audit.p;
+  }
+  rc = modes_device(c, d_points, cloud_points, n_clouds, fields, report, report_loc);
+  // (pageable host buffers: the call does not return while a copy may still read them)
+  if (rc == CLDN_HIP_OK && up && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
+  return rc;
+}
+
+int cldn_hip_sweep_modes_last_encode(cldn_hip_codec_t* c, cldn_hip_mode_cell_t* report, int report_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (!c->enc.valid && !c->enc.await_frame) return no_last_encode("sweep_modes_last_encode");  // (the points are there before the framing)
+  const cldn_hip_codec::LastEncode& E = c->enc;  // read only: the state stays as it is
+  const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
+  int rc;
+  if ((rc = modes_check_report(c->plan, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  std::vector<ModeField> fields;
+  if ((rc = modes_fields(c->plan, &fields)) != CLDN_HIP_OK) return rc;
+  if (fields.empty()) return CLDN_HIP_OK;
+  ENTER_DEVICE(c->device);
+  return modes_device(c, E.points, E.cloud_points.data(), n_clouds, fields, report, report_loc);
 }
 
 }  // extern "C"

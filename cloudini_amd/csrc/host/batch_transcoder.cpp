@@ -354,11 +354,14 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       sweep.resolutions = sweep_res.data();
     }
     Cloudini::amd_detail::SweepRequest* const sweep_p = sweep.n_candidates ? &sweep : nullptr;
+    Cloudini::amd_detail::ModesRequest modes;
+    modes.apply_best = opt.modes == TranscodeOptions::Modes::Best;
+    Cloudini::amd_detail::ModesRequest* const modes_p = opt.modes != TranscodeOptions::Modes::Off ? &modes : nullptr;
     const auto t_gpu = Clock::now();
     if (b.parsed[r0].viz) {
       Cloudini::amd_detail::encodeStage1BatchViz(info0, ptrs.data(), pts.data(), run.count, b.parsed[r0].viz_xyz_offset,
                                                  b.parsed[r0].viz_resolution, grow, run.offsets, run.chunk_sizes, kept, audit_p,
-                                                 sweep_p);
+                                                 sweep_p, modes_p);
       for (uint32_t k = 0; k < run.count; ++k) {  // what the reference's function leaves behind (src/ros_msg_utils.cpp:326-335)
         Parsed& p = b.parsed[r0 + k];
         p.points = kept[k];
@@ -374,7 +377,24 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       }
     } else {
       Cloudini::amd_detail::encodeStage1Batch(info0, ptrs.data(), pts.data(), run.count, grow, run.offsets, run.chunk_sizes, audit_p,
-                                              sweep_p);
+                                              sweep_p, modes_p);
+    }
+    if (modes_p && stats && modes.adaptive_fields) {  // the run's cells, summed over its messages, into the per-name summary
+      std::vector<ModeFieldSummary> part(modes.adaptive_fields);  // names from the plan's own list of adaptive fields
+      for (size_t a = 0; a < part.size(); ++a) part[a].name = info0.fields.at(modes.field_index[a]).name;
+      for (uint32_t k = 0; k < run.count; ++k) {
+        if (b.parsed[r0 + k].points == 0) continue;
+        for (size_t a = 0; a < part.size(); ++a) {
+          const cldn_hip_mode_cell_t& cell = modes.report[(size_t)k * part.size() + a];
+          part[a].clouds += 1;
+          for (int m = 0; m < 4; ++m) part[a].bytes[m] += cell.bytes[m];
+          part[a].probed[cell.probe_mode & 3u] += 1;
+          part[a].best[cell.best_mode & 3u] += 1;
+          part[a].saved_bytes += cell.bytes[cell.probe_mode & 3u] - cell.bytes[cell.best_mode & 3u];
+        }
+      }
+      stats->mergeModes(part);
+      if (modes.reencoded) stats->mode_reencoded_runs += 1;
     }
     if (sweep_p && stats) {  // the run's cells, summed over its messages, into the per-name-and-resolution summary
       const size_t nf = info0.fields.size(), nc = sweep.n_candidates;
@@ -708,6 +728,25 @@ void TranscodeStats::mergeSweep(const std::vector<SweepCellSummary>& other) {
   }
 }
 
+void TranscodeStats::mergeModes(const std::vector<ModeFieldSummary>& other) {
+  for (const ModeFieldSummary& o : other) {
+    ModeFieldSummary* mine = nullptr;
+    for (ModeFieldSummary& s : modes)
+      if (s.name == o.name) mine = &s;
+    if (!mine) {
+      modes.push_back(o);
+      continue;
+    }
+    mine->clouds += o.clouds;
+    mine->saved_bytes += o.saved_bytes;
+    for (int m = 0; m < 4; ++m) {
+      mine->bytes[m] += o.bytes[m];
+      mine->probed[m] += o.probed[m];
+      mine->best[m] += o.best[m];
+    }
+  }
+}
+
 namespace {
 std::string trimmed(const std::string& s) {
   size_t a = 0, z = s.size();
@@ -746,6 +785,8 @@ float resolutionValue(const std::string& value, bool zero_allowed, const char* w
 
 void checkOptions(const TranscodeOptions& opt) {
   if (opt.decode && !opt.sweep.empty()) throw std::invalid_argument("TranscodeOptions: sweep is not available together with decode");
+  if (opt.decode && opt.modes != TranscodeOptions::Modes::Off)
+    throw std::invalid_argument("TranscodeOptions: modes is not available together with decode");
   for (const auto& named : opt.sweep)
     if (named.second.size() > CLDN_HIP_SWEEP_MAX_CANDIDATES)
       throw std::invalid_argument("TranscodeOptions: the sweep ladder of " + named.first + " has more than 16 resolutions");
@@ -957,6 +998,8 @@ TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, co
         stats.seconds_gpu += mine.seconds_gpu;
         stats.mergeAudit(mine.audit);
         stats.mergeSweep(mine.sweep);
+        stats.mergeModes(mine.modes);
+        stats.mode_reencoded_runs += mine.mode_reencoded_runs;
       }
       if (gpu_workers_left.fetch_sub(1) == 1) to_stage2.close();
     });

@@ -218,6 +218,52 @@ CLDN_EXPORT int64_t cldn_amd_transcode_directory_sweep(const char* in_dir, const
   });
 }
 
+// the mode summary as one line of JSON: {"reencoded_runs": n, "fields": [one object per integer field name]}
+static std::string modesJson(const cloudini_amd::TranscodeStats& st) {
+  std::string out = "{\"reencoded_runs\": " + std::to_string(st.mode_reencoded_runs) + ", \"fields\": [";
+  for (size_t i = 0; i < st.modes.size(); ++i) {
+    const cloudini_amd::ModeFieldSummary& f = st.modes[i];
+    std::string name = "\"";
+    for (char ch : f.name) {
+      if (ch == '"' || ch == '\\') name += '\\';
+      name += (unsigned char)ch < 0x20 ? ' ' : ch;
+    }
+    const auto four = [](const uint64_t (&v)[4]) {
+      return "[" + std::to_string(v[0]) + ", " + std::to_string(v[1]) + ", " + std::to_string(v[2]) + ", " + std::to_string(v[3]) + "]";
+    };
+    out += std::string(i ? ", " : "") + "{\"name\": " + name + "\", \"clouds\": " + std::to_string(f.clouds) + ", \"bytes\": " + four(f.bytes) +
+           ", \"probed\": " + four(f.probed) + ", \"best\": " + four(f.best) + ", \"saved_bytes\": " + std::to_string(f.saved_bytes) + "}";
+  }
+  return out + "]}";
+}
+
+CLDN_EXPORT int64_t cldn_amd_transcode_directory_modes(const char* in_dir, const char* out_dir, float resolution,
+                                                       uint8_t compression_opt, int viz_lossy, uint32_t batch_messages,
+                                                       const int32_t* devices, uint32_t n_devices, int apply_best, double* stats_out,
+                                                       char* modes_json, uint64_t modes_capacity) {
+  return guarded([&] {
+    cloudini_amd::DirectorySource source(in_dir);
+    cloudini_amd::DirectorySink sink(out_dir);
+    cloudini_amd::TranscodeOptions opt;
+    opt.default_resolution = resolution;
+    opt.compression = static_cast<Cloudini::CompressionOption>(compression_opt);
+    opt.viz_lossy = viz_lossy != 0;
+    if (batch_messages) opt.batch_messages = batch_messages;
+    if (devices) opt.devices.assign(devices, devices + n_devices);
+    opt.modes = apply_best ? cloudini_amd::TranscodeOptions::Modes::Best : cloudini_amd::TranscodeOptions::Modes::Report;
+    const cloudini_amd::TranscodeStats st = cloudini_amd::transcodePointClouds(source, sink, opt);
+    if (stats_out) {
+      const double v[8] = {(double)st.messages,    (double)st.points,  (double)st.input_bytes, (double)st.output_bytes,
+                           (double)st.gpu_batches, st.seconds_total, st.seconds_gpu,         st.seconds_stage2};
+      for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
+    }
+    const std::string json = modesJson(st);
+    if (json.size() + 1 > modes_capacity) throw std::runtime_error("transcode_directory_modes: the summary needs " + std::to_string(json.size() + 1) + " bytes");
+    std::memcpy(modes_json, json.c_str(), json.size() + 1);
+    return (int64_t)st.messages;
+  });
+}
+
 CLDN_EXPORT int64_t cldn_amd_transcode_directory(const char* in_dir, const char* out_dir, float resolution,
                                                  uint8_t compression_opt, int viz_lossy, uint32_t batch_messages,
                                                  double* stats_out) {

@@ -1046,9 +1046,36 @@ static int sweepLastEncode(cldn_hip_codec_t* codec, const EncodingInfo& info, ui
   return cldn_hip_sweep_last_encode(codec, sweep->resolutions, sweep->n_candidates, sweep->report.data(), CLDN_HIP_HOST);
 }
 
+// The adaptive integer modes of that encode call's points; with apply_best and a cloud whose best mode is not the probed one,
+// `encode` (the call and the fetch of its output) runs once more with the best modes forced per cloud.
+static int modesLastEncode(cldn_hip_codec_t* codec, const cldn_hip_plan_t* plan, uint32_t n_clouds, ModesRequest* modes,
+                           const std::function<int()>& encode) {
+  modes->adaptive_fields = cldn_hip_plan_adaptive_fields(plan);
+  modes->field_index.resize(modes->adaptive_fields);
+  for (uint32_t a = 0; a < modes->adaptive_fields; ++a) modes->field_index[a] = cldn_hip_plan_adaptive_field_index(plan, a);
+  modes->reencoded = false;
+  modes->report.assign((size_t)n_clouds * modes->adaptive_fields, cldn_hip_mode_cell_t{});
+  if (modes->report.empty()) return CLDN_HIP_OK;
+  int rc = cldn_hip_sweep_modes_last_encode(codec, modes->report.data(), CLDN_HIP_HOST);
+  if (rc != CLDN_HIP_OK || !modes->apply_best) return rc;
+  std::vector<uint8_t> best(modes->report.size());
+  bool differs = false;
+  for (size_t i = 0; i < best.size(); ++i) {
+    best[i] = static_cast<uint8_t>(modes->report[i].best_mode);
+    differs = differs || modes->report[i].best_mode != modes->report[i].probe_mode;
+  }
+  if (!differs) return CLDN_HIP_OK;
+  if ((rc = cldn_hip_codec_force_modes_per_cloud(codec, best.data(), n_clouds)) != CLDN_HIP_OK) return rc;
+  rc = encode();
+  cldn_hip_codec_force_modes_per_cloud(codec, nullptr, 0);  // (the codec goes back to the pool: it probes again; a successful
+                                                            // call leaves cldn_hip_last_error as the encode set it)
+  modes->reencoded = rc == CLDN_HIP_OK;
+  return rc;
+}
+
 void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
-                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit, SweepRequest* sweep) {
+                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit, SweepRequest* sweep, ModesRequest* modes) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1056,12 +1083,17 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
   chunk_sizes.assign((size_t)std::max<uint64_t>(1, n_chunks), 0);
   cldn_hip_codec_t* codec = pool().acquire(info, plan);
   // two-step host output: sizes first, then exactly the bytes that were produced
-  int rc = cldn_hip_encode_stage1_gather(codec, reinterpret_cast<const void* const*>(cloud_ptrs), cloud_points, n_clouds, nullptr,
-                                         0, CLDN_HIP_HOST, stream_offsets.data(), chunk_sizes.data(), nullptr);
-  if (rc == CLDN_HIP_OK) {
-    const uint64_t total = stream_offsets[n_clouds];
-    rc = cldn_hip_codec_fetch_output(codec, total ? grow(total) : nullptr, total);
-  }
+  const auto encode = [&]() {
+    int rc = cldn_hip_encode_stage1_gather(codec, reinterpret_cast<const void* const*>(cloud_ptrs), cloud_points, n_clouds, nullptr,
+                                           0, CLDN_HIP_HOST, stream_offsets.data(), chunk_sizes.data(), nullptr);
+    if (rc == CLDN_HIP_OK) {
+      const uint64_t total = stream_offsets[n_clouds];
+      rc = cldn_hip_codec_fetch_output(codec, total ? grow(total) : nullptr, total);
+    }
+    return rc;
+  };
+  int rc = encode();
+  if (rc == CLDN_HIP_OK && modes) rc = modesLastEncode(codec, plan.plan, n_clouds, modes, encode);
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
@@ -1073,7 +1105,7 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
 void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
-                          std::vector<uint64_t>& kept_points, AuditRequest* audit, SweepRequest* sweep) {
+                          std::vector<uint64_t>& kept_points, AuditRequest* audit, SweepRequest* sweep, ModesRequest* modes) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;  // of the input: an upper bound of what the filtered clouds have
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1081,13 +1113,18 @@ void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_
   chunk_sizes.assign((size_t)std::max<uint64_t>(1, n_chunks), 0);
   kept_points.assign((size_t)std::max<uint32_t>(1, n_clouds), 0);
   cldn_hip_codec_t* codec = pool().acquire(info, plan);
-  int rc = cldn_hip_encode_stage1_viz_gather(codec, reinterpret_cast<const void* const*>(cloud_ptrs), cloud_points, n_clouds,
-                                             xyz_offset, resolution, kept_points.data(), nullptr, 0, CLDN_HIP_HOST,
-                                             stream_offsets.data(), chunk_sizes.data(), nullptr);
-  if (rc == CLDN_HIP_OK) {
-    const uint64_t total = stream_offsets[n_clouds];
-    rc = cldn_hip_codec_fetch_output(codec, total ? grow(total) : nullptr, total);
-  }
+  const auto encode = [&]() {
+    int rc = cldn_hip_encode_stage1_viz_gather(codec, reinterpret_cast<const void* const*>(cloud_ptrs), cloud_points, n_clouds,
+                                               xyz_offset, resolution, kept_points.data(), nullptr, 0, CLDN_HIP_HOST,
+                                               stream_offsets.data(), chunk_sizes.data(), nullptr);
+    if (rc == CLDN_HIP_OK) {
+      const uint64_t total = stream_offsets[n_clouds];
+      rc = cldn_hip_codec_fetch_output(codec, total ? grow(total) : nullptr, total);
+    }
+    return rc;
+  };
+  int rc = encode();  // (a second encode filters again: the same survivors)
+  if (rc == CLDN_HIP_OK && modes) rc = modesLastEncode(codec, plan.plan, n_clouds, modes, encode);
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";

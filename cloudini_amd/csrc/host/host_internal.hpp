@@ -42,16 +42,30 @@ struct SweepRequest {
   uint32_t n_candidates = 0;
   std::vector<cldn_hip_sweep_cell_t> report;
 };
+// `modes` (optional): right behind the encode call the codec sweeps the adaptive integer modes of the points it encoded
+// (cldn_hip_sweep_modes_last_encode; behind the viz filter: the survivors): report receives n_clouds * adaptive_fields cells.
+// With apply_best, when some cloud's best mode differs from the probed one, the encode call is repeated ONCE from the same host
+// buffers with cldn_hip_codec_force_modes_per_cloud(best modes) and the forcing is cleared again (reencoded = true): the streams
+// are then not the reference encoder's bytes, and the audit and the resolution sweep behind it see the second encode.
+struct ModesRequest {
+  bool apply_best = false;
+  uint32_t adaptive_fields = 0;
+  std::vector<uint32_t> field_index;  // of each adaptive field among info.fields (cldn_hip_plan_adaptive_field_index)
+  bool reencoded = false;
+  std::vector<cldn_hip_mode_cell_t> report;
+};
 void encodeStage1Batch(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
-                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr);
+                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr,
+                       ModesRequest* modes = nullptr);
 // The same behind the viz pre-filter (cldn_hip_encode_stage1_viz_gather): every cloud is filtered on its own, the survivors
 // are encoded without leaving the device. kept_points gets n_clouds survivor counts; stream_offsets and chunk_sizes describe
 // the filtered clouds (a cloud that loses every point has an empty stream and no chunk).
 void encodeStage1BatchViz(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
-                          std::vector<uint64_t>& kept_points, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr);
+                          std::vector<uint64_t>& kept_points, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr,
+                          ModesRequest* modes = nullptr);
 // detail::CompressChunk (src/codec_common.cpp:220-258) and its worst-case output size
 uint32_t compressChunkTo(Cloudini::CompressionOption opt, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_cap);
 size_t compressedChunkBound(Cloudini::CompressionOption opt, size_t stage1_bytes);

@@ -362,4 +362,36 @@ struct SweepLaunch {
 uint32_t sweep_stage_points(uint32_t point_step);  // points per LDS stage, 0 = the direct route
 int sweep_launch(const SweepLaunch& L);            // one clear + one kernel
 
+// ---- sweep of the V5 adaptive integer modes (mode_kernels.hip; record: cldn_hip_mode_cell_t, five 64-bit words) ----
+constexpr uint32_t kModeProbeUnit = 0xffffffffu;  // ModeUnit::chunk of the unit that probes a cloud's first kProbePoints values
+struct ModeField {
+  uint32_t offset;
+  uint8_t type;      // Cloudini::FieldType of the adaptive field
+  uint8_t bpv;       // 2, 4, 8
+  uint8_t pad[2];
+};
+static_assert(sizeof(ModeField) == 8, "128 of them are a kernel argument");
+struct ModeUnit {    // one workgroup: one section of one adaptive field
+  uint32_t cloud;
+  uint32_t chunk;    // of the cloud, or kModeProbeUnit
+  uint32_t field;    // index among the plan's adaptive fields
+  uint32_t pad;
+};
+struct ModeLaunch {
+  hipStream_t stream;
+  const uint8_t* points;         // device AoS, clouds back to back, any alignment
+  uint32_t point_step;
+  uint32_t n_clouds;
+  uint32_t n_units;
+  uint32_t n_fields;             // adaptive fields of the plan
+  const ModeField* fields;       // HOST [n_fields]
+  const ModeField* dev_fields;   // device copy of it, or NULL when n_fields <= kAuditArgFields
+  const AuditCloud* clouds;      // device [n_clouds]
+  const ModeUnit* units;         // device [n_units]
+  unsigned long long* report;    // device [n_clouds * n_fields * 5], 8-byte aligned: cleared, then filled
+};
+uint32_t modes_stage_points(uint32_t point_step);  // values per LDS stage of phase A, 0 = the direct route
+int modes_configure();
+int modes_launch(const ModeLaunch& L);             // one clear + one kernel
+
 }  // namespace cldn

@@ -165,6 +165,12 @@ def lib() -> C.CDLL:
     L.cldn_hip_sweep_last_encode.argtypes = [vp, vp, C.c_uint32, vp, C.c_int]
     L.cldn_hip_sweep_last_encode_clouds.restype = C.c_int64
     L.cldn_hip_sweep_last_encode_clouds.argtypes = [vp]
+    L.cldn_hip_sweep_modes_clouds.restype = C.c_int
+    L.cldn_hip_sweep_modes_clouds.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int]
+    L.cldn_hip_sweep_modes_last_encode.restype = C.c_int
+    L.cldn_hip_sweep_modes_last_encode.argtypes = [vp, vp, C.c_int]
+    L.cldn_hip_codec_force_modes_per_cloud.restype = C.c_int
+    L.cldn_hip_codec_force_modes_per_cloud.argtypes = [vp, C.POINTER(C.c_uint8), C.c_uint32]
     _lib = L
     return L
 
@@ -211,6 +217,10 @@ SWEEP_DTYPE = np.dtype([("bytes", "<u8"), ("n_class_diff", "<u8"), ("n_over_limi
 SWEEP_MAX_CANDIDATES = 16
 
 
+# cldn_hip_mode_cell_t: one cell per (cloud, adaptive integer field)
+MODE_DTYPE = np.dtype([("bytes", "<u8", (4,)), ("probe_mode", "<u4"), ("best_mode", "<u4")])
+
+
 def _ladders(resolutions, n_fields: int) -> np.ndarray:
     """A sweep call's `resolutions` as the (n_fields, n_candidates) float32 array the C side reads."""
     res = np.ascontiguousarray(resolutions, dtype=np.float32)
@@ -246,6 +256,12 @@ class Plan:
     @property
     def max_point_bytes(self) -> int:
         return int(lib().cldn_hip_plan_max_point_bytes(self._h))
+
+    def adaptive_field_index(self, a: int) -> int:
+        """Index among the schema's fields of adaptive field a (cldn_hip_plan_adaptive_field_index)."""
+        f = lib().cldn_hip_plan_adaptive_field_index
+        f.restype, f.argtypes = C.c_uint32, [C.c_void_p, C.c_uint32]
+        return int(f(self._h, int(a)))
 
     def stage1_bound(self, n_points: int) -> int:
         return int(lib().cldn_hip_stage1_bound(self._h, int(n_points)))
@@ -389,6 +405,18 @@ class Codec:
             return
         m = np.ascontiguousarray(modes, dtype=np.uint8)
         _check(lib().cldn_hip_codec_force_modes(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), m.size))
+
+    def force_modes_per_cloud(self, modes=None):
+        """One mode set per cloud of the following encode calls (cldn_hip_codec_force_modes_per_cloud): modes has shape
+        (n_clouds, adaptive fields), e.g. the best_mode column of sweep_modes_*; None / empty returns to probing. The streams
+        are then valid Cloudini streams, but not the reference encoder's bytes."""
+        if modes is None or len(modes) == 0:
+            _check(lib().cldn_hip_codec_force_modes_per_cloud(self._h, None, 0))
+            return
+        m = np.ascontiguousarray(modes, dtype=np.uint8)
+        if m.ndim != 2 or m.shape[1] != self.plan.adaptive_fields:
+            raise ValueError(f"modes must have shape (n_clouds, adaptive fields = {self.plan.adaptive_fields}), not {m.shape}")
+        _check(lib().cldn_hip_codec_force_modes_per_cloud(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), m.shape[0]))
 
     def set_stage2(self, stage2: int):
         """0 = stage-1 streams (default), 1 = [u32 size][LZ4 block] per chunk, compressed on the device, 2 = the same with the
@@ -681,4 +709,40 @@ class Codec:
         _check(lib().cldn_hip_sweep_last_encode(self._h, res.ctypes.data_as(C.c_void_p), res.shape[1],
                                                 C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
                                                 DEVICE if report_ptr else HOST))
+        return rep
+
+    # ---- adaptive integer modes: section bytes per mode, probed and best mode (cldn_hip_sweep_modes_*) ---------------
+    def _mode_report(self, n_clouds: int) -> np.ndarray:
+        rep = np.zeros((int(n_clouds), self.plan.adaptive_fields), dtype=MODE_DTYPE)
+        rep.view(np.uint8)[...] = 0xEE  # (a call that fails leaves it as it was)
+        return rep
+
+    def sweep_modes_host(self, clouds: Sequence[np.ndarray]) -> np.ndarray:
+        """cldn_hip_sweep_modes_clouds on host buffers. Returns the (n_clouds, adaptive fields) report."""
+        step = self.plan.point_step
+        arrs = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in clouds]
+        if any(x.size % step for x in arrs):
+            raise ValueError("Input cloud_data size is not a multiple of point_step")
+        cp = np.array([x.size // step for x in arrs], dtype=np.uint64)
+        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        return self.sweep_modes_device(data.ctypes.data, cp, points_loc=HOST)
+
+    def sweep_modes_device(self, points_ptr: int, cloud_points, report_ptr: int = 0, points_loc: int = DEVICE):
+        """cldn_hip_sweep_modes_clouds on a raw pointer. report_ptr: device array of n_clouds * adaptive fields cells (the call
+        only enqueues work when the points are on the device; returns None), 0 = host report (returned)."""
+        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
+        rep = None if report_ptr else self._mode_report(cp.size)
+        _check(lib().cldn_hip_sweep_modes_clouds(self._h, C.c_void_p(points_ptr), points_loc, cp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 cp.size, C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                                 DEVICE if report_ptr else HOST))
+        return rep
+
+    def sweep_modes_last_encode(self, report_ptr: int = 0):
+        """cldn_hip_sweep_modes_last_encode: the points of this codec's most recent encode call (the survivors of a viz call),
+        one row per cloud of that call; leaves the state for audit_last_encode and sweep_last_encode as it found it."""
+        n = int(lib().cldn_hip_sweep_last_encode_clouds(self._h))
+        _check(n)
+        rep = None if report_ptr else self._mode_report(n)
+        _check(lib().cldn_hip_sweep_modes_last_encode(self._h, C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                                      DEVICE if report_ptr else HOST))
         return rep

@@ -159,6 +159,19 @@ struct TranscodeOptions {
   // codec does not encode with a lossy float encoder there, is ignored for that message. The output is what it is without the
   // sweep. Not available together with `decode`.
   std::map<std::string, std::vector<float>> sweep;
+  // Adaptive integer modes (include/cloudini_hip.h, cldn_hip_sweep_modes_last_encode). The reference commits one mode per cloud
+  // and integer field (ring, rgba, integer intensity, stamps ...) from the first 4096 values only.
+  //   Report  behind the encode call of every schema run the GPU stage measures, on the device, what each integer section costs
+  //           under each of the four modes over the WHOLE cloud and adds it per field name to TranscodeStats::modes. The output is
+  //           what it is without the option.
+  //   Best    the same, and a run in which some cloud's best mode differs from the probed one is encoded a second time, from
+  //           the host messages again, with the best modes forced per cloud (TranscodeStats::mode_reencoded_runs counts them; a
+  //           single-pass route is not built). Messages of such a run are NOT the reference encoder's bytes: they are valid
+  //           streams -- every Cloudini decoder reads the mode byte of each section -- that decode to the same points. Messages
+  //           whose modes did not change are byte-identical to a run without the option.
+  // Not available together with `decode`.
+  enum class Modes { Off, Report, Best };
+  Modes modes = Modes::Off;
   // Test hook (tests/cpp/transcoder_order.cpp, runs without a GPU): when set, `test_workers` stage threads call it instead of
   // the GPU stage and stage 2 passes the batch on untouched -- what remains is the pipeline itself: batches handed to
   // whichever stage is free, the writer putting them back into input order, an error on any stage stopping all of them.
@@ -188,6 +201,16 @@ struct SweepCellSummary {
   double max_abs_err = 0;
 };
 
+// One adaptive integer field name over all messages of a run of the transcoder (cldn_hip_mode_cell_t summed).
+struct ModeFieldSummary {
+  std::string name;
+  uint64_t clouds = 0;              // non-empty clouds that have the field
+  uint64_t bytes[4] = {0, 0, 0, 0}; // section bytes under DeltaVarint, Palette, Rle, DeltaRle
+  uint64_t probed[4] = {0, 0, 0, 0};  // clouds whose probe commits each mode
+  uint64_t best[4] = {0, 0, 0, 0};    // clouds whose best mode over the whole cloud is each mode
+  uint64_t saved_bytes = 0;         // sum over clouds of bytes[probe_mode] - bytes[best_mode]: what Modes::Best saves (stage 1)
+};
+
 struct TranscodeStats {
   uint64_t messages = 0, points = 0, input_bytes = 0, output_bytes = 0, gpu_batches = 0;
   // seconds_gpu: summed over the GPU stages. With viz_lossy it covers the fused filter + encode call of every schema run, the
@@ -203,6 +226,9 @@ struct TranscodeStats {
   void mergeAudit(const std::vector<AuditFieldSummary>& other);
   std::vector<SweepCellSummary> sweep;   // TranscodeOptions::sweep: one entry per field name and resolution, in order of first appearance
   void mergeSweep(const std::vector<SweepCellSummary>& other);
+  std::vector<ModeFieldSummary> modes;   // TranscodeOptions::modes: one entry per field name, in order of first appearance
+  uint64_t mode_reencoded_runs = 0;      // Modes::Best: schema runs that were encoded a second time
+  void mergeModes(const std::vector<ModeFieldSummary>& other);
 };
 
 // The reference's profile strings (McapConverter::addProfile, tools/src/mcap_converter.cpp:325-353):

@@ -109,6 +109,18 @@ int64_t cldn_amd_transcode_directory_sweep(const char* in_dir, const char* out_d
                                            const char* const* sweep_names, const uint32_t* ladder_sizes, const float* ladders,
                                            uint32_t n_names, double* stats_out, char* sweep_json, uint64_t sweep_capacity);
 
+/* cldn_amd_transcode_directory_on with the adaptive integer mode sweep behind every encode call (TranscodeOptions::modes;
+ * include/cloudini_hip.h, cldn_hip_sweep_modes_last_encode). apply_best == 0 ("report"): the files are the same; != 0 ("best"): a
+ * schema run in which some cloud's best mode differs from the probed one is encoded a second time with the best modes forced per
+ * cloud -- those messages are NOT the reference encoder's bytes, they are valid streams that every Cloudini decoder decodes to
+ * the same points. modes_json receives one line of JSON: {"reencoded_runs": n, "fields": [{"name", "clouds", "bytes": [4],
+ * "probed": [4], "best": [4], "saved_bytes"}, ...]} -- per integer field name the section bytes under DeltaVarint, Palette, Rle and
+ * DeltaRle, the clouds the probe put in each mode, the clouds whose best mode is each, and the stage-1 bytes "best" saves. A
+ * modes_capacity that is too small is an error (-1). */
+int64_t cldn_amd_transcode_directory_modes(const char* in_dir, const char* out_dir, float resolution, uint8_t compression_opt,
+                                           int viz_lossy, uint32_t batch_messages, const int32_t* devices, uint32_t n_devices,
+                                           int apply_best, double* stats_out, char* modes_json, uint64_t modes_capacity);
+
 /* Stage-2 (LZ4 / ZSTD) threads a single encode()/decode() call with use_threads may occupy, the caller included.
  * The reference's flag means one extra worker (cloudini_lib/src/cloudini.cpp:453-499); here the pool is bounded:
  * default min(4, hardware threads), overridden by the environment variable CLOUDINI_AMD_STAGE2_THREADS (read once)

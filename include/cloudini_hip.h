@@ -90,6 +90,8 @@ int cldn_hip_plan_create(const cldn_hip_field_t* fields, uint32_t n_fields, uint
 void cldn_hip_plan_destroy(cldn_hip_plan_t* plan);
 int cldn_hip_plan_uses_v5(const cldn_hip_plan_t* plan);                 /* detail::UsesV5Codec */
 uint32_t cldn_hip_plan_adaptive_fields(const cldn_hip_plan_t* plan);    /* number of V5 adaptive-int fields */
+/* index among the schema's fields of adaptive field a (the order of the encode calls' `modes`), or UINT32_MAX */
+uint32_t cldn_hip_plan_adaptive_field_index(const cldn_hip_plan_t* plan, uint32_t a);
 uint32_t cldn_hip_plan_max_point_bytes(const cldn_hip_plan_t* plan);    /* detail::MaxSerializedPointSize */
 /* MaxCompressedSize(info, n_points, include_header=false) for CompressionOption::NONE
  * (src/cloudini.cpp:249-292): the capacity the framed stage-1 stream of one cloud must be given. */
@@ -190,6 +192,15 @@ uint64_t cldn_hip_stage2_bound(const cldn_hip_plan_t* plan, uint64_t n_points, i
  *   modes   HOST array [adaptive_fields] with values 0..3; NULL / n_modes = 0 returns to probing.
  * The setting stays until changed and applies to every cloud of the following encode calls. */
 int cldn_hip_codec_force_modes(cldn_hip_codec_t* codec, const uint8_t* modes, uint32_t n_modes);
+
+/* The same with one mode set PER CLOUD of the following encode calls (plain, gather, chunks, viz, with or without stage 2 on
+ * the device): modes is a HOST array [n_clouds * adaptive_fields], row k for cloud k, in the layout of the encode calls'
+ * `modes` output -- e.g. the best_mode column of cldn_hip_sweep_modes_*. Sticky like cldn_hip_codec_force_modes; the two
+ * setters replace each other; NULL or n_clouds == 0 returns to probing. While it is set, an encode call with another
+ * n_clouds returns CLDN_HIP_ERR_ARG and encodes nothing. A stream encoded with modes other than the probed ones is NOT the
+ * reference encoder's bytes: it is a valid stream (every Cloudini decoder reads the mode byte of each section) that decodes
+ * to the same points. */
+int cldn_hip_codec_force_modes_per_cloud(cldn_hip_codec_t* codec, const uint8_t* modes, uint32_t n_clouds);
 
 /* Encoder pipelines (both produce identical bytes; for A/B runs and tests):
  *   1  generic kernel + slots  every schema: the op interpreter, workgroup tiles with barriers (k_encode_regular)
@@ -431,6 +442,42 @@ int cldn_hip_sweep_clouds(cldn_hip_codec_t* codec, const void* points, int point
 int cldn_hip_sweep_last_encode(cldn_hip_codec_t* codec, const float* resolutions, uint32_t n_candidates,
                                cldn_hip_sweep_cell_t* report, int report_loc);
 int64_t cldn_hip_sweep_last_encode_clouds(const cldn_hip_codec_t* codec);
+
+/* Sweep of the adaptive integer modes: what does each V5 integer section (ring, rgba, integer intensity, stamps ...) cost
+ * under each of the four modes, which mode does the reference's probe commit, and which one would the same rule pick if it
+ * saw the whole cloud? The reference decides per cloud and field on the first min(n, 4096) values only
+ * (src/v5_codec.cpp:387-421, 934-949); a prefix that is constant or has few distinct values commits Rle or Palette for the
+ * whole cloud. One record per cloud k and adaptive field a (the order of the encode calls' `modes`):
+ * report[k * adaptive_fields + a]. tests/mode_model.py restates it in numpy.
+ * Per chunk of <= 32768 values (nothing crosses a chunk edge: prev = 0 at its start, runs are cut at its end), mode byte included:
+ *   DeltaVarint  1 + sum varint64len(v[i] - v[i-1])                              (int64 wrap-around)
+ *   Palette      3 + U * bpv + ceil(bitsForPaletteIndex(U) * n / 8)              (U = the chunk's exact distinct count)
+ *   Rle          5 + sum over runs of equal values (bpv + uvarintlen(run length))
+ *   DeltaRle     5 + sum over runs of equal deltas (varint64len(delta) + uvarintlen(run length))
+ * Hence: forcing field a of cloud k from mode m to m' (cldn_hip_codec_force_modes_per_cloud) changes the size of the cloud's
+ * stage-1 stream by bytes[m'] - bytes[m], exactly. Stage 2 (LZ4 / ZSTD) behind it is not predicted. */
+typedef struct cldn_hip_mode_cell {
+  uint64_t bytes[4];   /* exact section bytes of this cloud's field under mode 0..3, summed over the cloud's chunks */
+  uint32_t probe_mode; /* the mode the reference commits (and cldn_hip_encode_stage1 reports in `modes`): the selection rule on
+                          the first min(n, 4096) values as one section */
+  uint32_t best_mode;  /* the same rule (DeltaVarint, Palette, Rle, DeltaRle in this order, strict <) on bytes[] */
+} cldn_hip_mode_cell_t; /* 40 bytes */
+
+/* report: [n_clouds * adaptive_fields] records, HOST or DEVICE per report_loc (DEVICE: 8-byte aligned). A zero-point cloud has
+ * all-zero cells; a plan without adaptive fields returns CLDN_HIP_OK and writes nothing. Every plan is served (the field table
+ * is a kernel argument up to 128 adaptive fields, device memory beyond). Per call, whatever n_clouds: one clear of the report,
+ * ONE kernel (one workgroup per chunk and field, and one per cloud and field for the probe) and one upload of its tables; for a
+ * HOST report one copy of it and one synchronisation on top. Tables, HOST points and a HOST report use the audit's workspace,
+ * never the codec's input staging or output buffer.
+ * cldn_hip_sweep_modes_clouds: cloud_points[k] points per cloud, back to back, any byte alignment; like every call that takes
+ * buffers it drops the state the *_last_encode calls need.
+ * cldn_hip_sweep_modes_last_encode: the points of this codec's most recent encode call, read where they lie on the device (see
+ * cldn_hip_audit_last_encode); valid from cldn_hip_encode_stage1_chunks on; after a viz encode the points are the survivors.
+ * It leaves the state as it found it: cldn_hip_audit_last_encode and cldn_hip_sweep_last_encode may follow in any order.
+ * The rows are those of cldn_hip_sweep_last_encode_clouds. */
+int cldn_hip_sweep_modes_clouds(cldn_hip_codec_t* codec, const void* points, int points_loc, const uint64_t* cloud_points,
+                                uint32_t n_clouds, cldn_hip_mode_cell_t* report, int report_loc);
+int cldn_hip_sweep_modes_last_encode(cldn_hip_codec_t* codec, cldn_hip_mode_cell_t* report, int report_loc);
 
 /* What a decode call may do to the bytes of a point that no field covers. CLDN_HIP_FILL_KEEP (default): they keep the
  * content of points_out (src/field_decoder.cpp:72-76 writes fields only) -- for a HOST buffer of a layout with such bytes

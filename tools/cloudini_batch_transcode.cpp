@@ -14,6 +14,12 @@
 //       encode call's points are swept on the device (cldn_hip_sweep_last_encode): one `sweep` table line per field and
 //       resolution in front of the JSON line -- stage-1 bytes, bytes per point, class_diff, over_limit, max_abs_err. The files
 //       are the files of a run without --sweep. Not available with --decode. Malformed strings: exit status 2.
+//   ... --modes report|best   the V5 integer sections (ring, rgba, stamps ...): the reference commits one of four modes per cloud
+//       and field from the first 4096 values only. `report` measures on the device what every mode costs over the whole cloud
+//       (cldn_hip_sweep_modes_last_encode): one `modes` table line per field in front of the JSON line; the files are the files
+//       of a run without --modes. `best` also encodes a schema run a second time with the best modes forced wherever a cloud's
+//       best mode is not the probed one: those messages are NOT the reference encoder's bytes -- they are valid streams that
+//       every Cloudini decoder decodes to the same points. Not available with --decode (exit status 2).
 //   ... --devices 0,1,2,3   spreads the batches over these GPUs (one GPU stage per entry; "0,0" = two stages on GPU 0)
 //   cloudini_batch_transcode <in.mcap> <out.mcap> [...same options] [--mcap-compression none|lz4|zstd]
 //       a bag: point-cloud messages converted, everything else copied (McapConverter, tools/src/mcap_converter.cpp:141-300);
@@ -47,9 +53,34 @@ static void printSweep(const cloudini_amd::TranscodeStats& st) {
                 (unsigned long long)s.n_over_limit, s.max_abs_err);
 }
 
+// one line per integer field name
+static void printModes(const cloudini_amd::TranscodeStats& st) {
+  std::printf("modes %-20s %8s %14s %14s %14s %14s  %-19s %-19s %14s\n", "field", "clouds", "DeltaVarint", "Palette", "Rle", "DeltaRle",
+              "probed", "best", "saved_bytes");
+  for (const cloudini_amd::ModeFieldSummary& f : st.modes) {
+    char probed[64], best[64];
+    std::snprintf(probed, sizeof probed, "%llu/%llu/%llu/%llu", (unsigned long long)f.probed[0], (unsigned long long)f.probed[1],
+                  (unsigned long long)f.probed[2], (unsigned long long)f.probed[3]);
+    std::snprintf(best, sizeof best, "%llu/%llu/%llu/%llu", (unsigned long long)f.best[0], (unsigned long long)f.best[1],
+                  (unsigned long long)f.best[2], (unsigned long long)f.best[3]);
+    std::printf("modes %-20s %8llu %14llu %14llu %14llu %14llu  %-19s %-19s %14llu\n", f.name.c_str(), (unsigned long long)f.clouds,
+                (unsigned long long)f.bytes[0], (unsigned long long)f.bytes[1], (unsigned long long)f.bytes[2],
+                (unsigned long long)f.bytes[3], probed, best, (unsigned long long)f.saved_bytes);
+  }
+  std::printf("modes reencoded_runs %llu\n", (unsigned long long)st.mode_reencoded_runs);
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::fprintf(stderr, "usage: %s <in_dir> <out_dir> [--resolution r] [--compression none|lz4|zstd] [--viz] [--batch n] [--devices 0,1,...] | --decode [--batch n] [--devices ...]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <in_dir> <out_dir> [--resolution r] [--compression none|lz4|zstd] [--viz] [--batch n] [--devices 0,1,...] | --decode [--batch n] [--devices ...]\n"
+                 "  --audit [--audit-limit name:value]   audit every encode call on the device; exit status 3 on a finding\n"
+                 "  --profile \"xyz:0.001; ring:remove\"    resolution per field name\n"
+                 "  --sweep \"xyz:0.001,0.002; ...\"        what would each resolution cost and lose (files unchanged)\n"
+                 "  --modes report                        what does each V5 integer mode cost per field over whole clouds (files unchanged)\n"
+                 "  --modes best                          also re-encode with the best mode per cloud where the 4096-value probe chose another:\n"
+                 "                                        those messages are NOT the reference encoder's bytes; they are valid streams that\n"
+                 "                                        every Cloudini decoder decodes to the same points\n"
+                 "  --sweep and --modes are not available with --decode\n", argv[0]);
     return 2;
   }
   cloudini_amd::TranscodeOptions opt;
@@ -87,6 +118,14 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--modes" && i + 1 < argc) {
+      const std::string v = argv[++i];
+      if (v != "report" && v != "best") {
+        std::fprintf(stderr, "--modes wants report or best\n");
+        return 2;
+      }
+      opt.modes = v == "best" ? cloudini_amd::TranscodeOptions::Modes::Best : cloudini_amd::TranscodeOptions::Modes::Report;
+    }
     else if (a == "--batch" && i + 1 < argc) opt.batch_messages = (size_t)std::strtoul(argv[++i], nullptr, 10);
     else if (a == "--devices" && i + 1 < argc) {
       for (const char* p = argv[++i]; *p;) {
@@ -108,12 +147,18 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--sweep is not available with --decode\n");
     return 2;
   }
+  if (opt.decode && opt.modes != cloudini_amd::TranscodeOptions::Modes::Off) {
+    std::fprintf(stderr, "--modes is not available with --decode\n");
+    return 2;
+  }
+  const bool modes = opt.modes != cloudini_amd::TranscodeOptions::Modes::Off;
   try {
     const std::string in_path = argv[1];
     if (in_path.size() > 5 && in_path.compare(in_path.size() - 5, 5, ".mcap") == 0) {
       const cloudini_amd::McapTranscodeStats ms = cloudini_amd::transcodeMcap(in_path, argv[2], opt, mcap_comp);
       const bool clean = !opt.audit || printAudit(ms.pipeline);
       if (!opt.sweep.empty()) printSweep(ms.pipeline);
+      if (modes) printModes(ms.pipeline);
       std::printf("{\"messages\": %llu, \"converted\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"points\": %llu, "
                   "\"seconds_total\": %.6f, \"gpu_batches\": %llu, \"peak_held_bytes\": %llu}\n",
                   (unsigned long long)ms.messages, (unsigned long long)ms.converted, (unsigned long long)ms.input_bytes,
@@ -134,6 +179,7 @@ int main(int argc, char** argv) {
     const cloudini_amd::TranscodeStats st = cloudini_amd::transcodePointClouds(source, sink, opt);
     const bool clean = !opt.audit || printAudit(st);
     if (!opt.sweep.empty()) printSweep(st);
+    if (modes) printModes(st);
     std::printf("{\"messages\": %llu, \"points\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"gpu_batches\": %llu, "
                 "\"seconds_total\": %.6f, \"seconds_gpu\": %.6f, \"seconds_stage2\": %.6f, \"gpu_stages\": %llu, \"Mpoints_per_s\": %.1f}\n",
                 (unsigned long long)st.messages, (unsigned long long)st.points, (unsigned long long)st.input_bytes,
