@@ -2139,35 +2139,117 @@ static int audit_fields(const cldn_hip_plan& P, const double* limit, std::vector
   return CLDN_HIP_OK;
 }
 
-static int audit_check_report(const cldn_hip_plan& P, uint32_t n_clouds, const void* report, int report_loc, const char* who = "audit") {
+// ---- what the three report calls share: argument checks, tables up, the report's place, host points up ----
+
+// `anything`: the plan has something to report
+static int report_check(const char* who, bool anything, uint32_t n_clouds, const void* report, int report_loc) {
   if (report_loc != CLDN_HIP_HOST && report_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
-  if (n_clouds && !P.fields.empty() && !report) return fail(CLDN_HIP_ERR_ARG, "%s: report is NULL", who);
+  if (n_clouds && anything && !report) return fail(CLDN_HIP_ERR_ARG, "%s: report is NULL", who);
   if (report_loc == CLDN_HIP_DEVICE && ((uintptr_t)report & 7u)) return fail(CLDN_HIP_ERR_ARG, "%s: a device report must be 8-byte aligned", who);
   return CLDN_HIP_OK;
 }
 
-// The cloud and block tables of a batch, as the audit and the sweep kernels read them: blocks of kAuditBlockPoints points, cut per cloud.
-static int count_point_blocks(const uint64_t* cloud_points, uint32_t n_clouds, const char* who, uint32_t* n_blocks) {
-  uint64_t n = 0;
-  for (uint32_t k = 0; k < n_clouds; ++k) n += (cloud_points[k] + kAuditBlockPoints - 1u) / kAuditBlockPoints;
-  if (n > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "%s: more than 2^31 blocks of 1024 points", who);
-  *n_blocks = (uint32_t)n;
+// What the host-built tables of a call are cut from
+struct ReportBatch {
+  const uint64_t* cloud_points;
+  uint32_t n_clouds, n_fields;
+};
+// One section of the tables of a call: `bytes` copied from `src`, or written in place by `fill` when src is NULL. A section of
+// 0 bytes is left out and its `dev` stays NULL.
+struct TableSection {
+  size_t bytes;
+  const void* src;
+  void (*fill)(const ReportBatch& B, void* h);
+  const uint8_t* dev;  // out: the section in d_audit_tab
+};
+// the field table goes to the device only when it does not fit the kernel arguments
+template <class F>
+static TableSection field_section(const std::vector<F>& fields) {
+  return TableSection{fields.size() > kReportArgFields ? fields.size() * sizeof(F) : 0u, fields.data(), nullptr, nullptr};
+}
+
+// Tables up: the sections back to back, each rounded up to 64 bytes, through the pinned h_audit into d_audit_tab in one copy
+static int upload_tables(cldn_hip_codec* c, const ReportBatch& B, TableSection* sec, size_t n_sections) {
+  if (c->ev_audit) HIP_TRY(hipEventSynchronize(c->ev_audit));  // the previous call's upload has left the staging buffer
+  else HIP_TRY(hipEventCreateWithFlags(&c->ev_audit, hipEventDisableTiming));
+  size_t total = 0;
+  for (size_t i = 0; i < n_sections; ++i) total += (sec[i].bytes + 63u) & ~size_t(63);
+  int rc;
+  if ((rc = c->h_audit.ensure(total)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_audit_tab.ensure(total)) != CLDN_HIP_OK) return rc;
+  size_t at = 0;
+  for (size_t i = 0; i < n_sections; ++i) {
+    if (sec[i].bytes == 0) continue;
+    uint8_t* h = (uint8_t*)c->h_audit.p + at;
+    if (sec[i].src) memcpy(h, sec[i].src, sec[i].bytes);
+    else sec[i].fill(B, h);
+    sec[i].dev = (const uint8_t*)c->d_audit_tab.p + at;
+    at += (sec[i].bytes + 63u) & ~size_t(63);
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_audit_tab.p, c->h_audit.p, total, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->ev_audit, c->stream));
   return CLDN_HIP_OK;
 }
-static void fill_point_blocks(const uint64_t* cloud_points, uint32_t n_clouds, AuditCloud* hc, AuditBlock* hb) {
+
+// The cloud table of a batch, as the three kernels read it
+static void fill_clouds(const ReportBatch& B, void* h) {
+  ReportCloud* hc = (ReportCloud*)h;
   uint64_t first = 0;
-  uint32_t bi = 0;
-  for (uint32_t k = 0; k < n_clouds; ++k) {
-    hc[k].first_point = first;
-    hc[k].n_points = cloud_points[k];
-    const uint32_t nb = (uint32_t)((cloud_points[k] + kAuditBlockPoints - 1u) / kAuditBlockPoints);
-    for (uint32_t j = 0; j < nb; ++j) {
-      hb[bi].cloud = k;
-      hb[bi].block = j;
-      ++bi;
-    }
-    first += cloud_points[k];
+  for (uint32_t k = 0; k < B.n_clouds; ++k) {
+    hc[k] = ReportCloud{first, B.cloud_points[k]};
+    first += B.cloud_points[k];
   }
+}
+static TableSection cloud_section(const ReportBatch& B) {
+  return TableSection{(size_t)B.n_clouds * sizeof(ReportCloud), nullptr, fill_clouds, nullptr};
+}
+
+// The audit's and the sweep's workgroups: blocks of kReportBlockPoints points, cut per cloud
+static void fill_blocks(const ReportBatch& B, void* h) {
+  ReportBlock* hb = (ReportBlock*)h;
+  for (uint32_t k = 0; k < B.n_clouds; ++k) {
+    const uint32_t nb = (uint32_t)((B.cloud_points[k] + kReportBlockPoints - 1u) / kReportBlockPoints);
+    for (uint32_t j = 0; j < nb; ++j) *hb++ = ReportBlock{k, j};
+  }
+}
+static int block_section(const ReportBatch& B, const char* who, uint32_t* n_blocks, TableSection* out) {
+  uint64_t n = 0;
+  for (uint32_t k = 0; k < B.n_clouds; ++k) n += (B.cloud_points[k] + kReportBlockPoints - 1u) / kReportBlockPoints;
+  if (n > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "%s: more than 2^31 blocks of 1024 points", who);
+  *n_blocks = (uint32_t)n;
+  *out = TableSection{(size_t)n * sizeof(ReportBlock), nullptr, fill_blocks, nullptr};
+  return CLDN_HIP_OK;
+}
+
+// where the kernel writes the report: the caller's device report, or d_audit_rep for a HOST report ...
+static int report_place(cldn_hip_codec* c, void* report, int report_loc, size_t rep_bytes, unsigned long long** d_rep) {
+  *d_rep = (unsigned long long*)report;
+  if (report_loc != CLDN_HIP_HOST) return CLDN_HIP_OK;
+  const int rc = c->d_audit_rep.ensure(rep_bytes);
+  *d_rep = (unsigned long long*)c->d_audit_rep.p;
+  return rc;
+}
+// ... which then comes back: one copy, one synchronisation
+static int report_fetch(cldn_hip_codec* c, void* report, int report_loc, const void* d_rep, size_t rep_bytes) {
+  if (report_loc != CLDN_HIP_HOST) return CLDN_HIP_OK;
+  HIP_TRY(hipMemcpyAsync(report, d_rep, rep_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return CLDN_HIP_OK;
+}
+
+// Host points of a *_clouds call go to d_audit at byte `at`; *d_ptr: where the kernel reads them. `room` is all that the call
+// stages there (at + bytes <= room), the same in each of its uploads: the first sizes d_audit, a later one finds it large enough
+// and moves nothing.
+// (Pageable host buffers: a call with a DEVICE report synchronises before it returns, so that no copy still reads them; a HOST
+// report has synchronised already.)
+static int stage_host_points(cldn_hip_codec* c, const void* ptr, int loc, uint64_t bytes, size_t at, size_t room, const uint8_t** d_ptr) {
+  *d_ptr = (const uint8_t*)ptr;
+  if (loc != CLDN_HIP_HOST || bytes == 0) return CLDN_HIP_OK;
+  const int rc = c->d_audit.ensure(room);
+  if (rc != CLDN_HIP_OK) return rc;
+  HIP_TRY(hipMemcpyAsync((uint8_t*)c->d_audit.p + at, ptr, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+  *d_ptr = (const uint8_t*)c->d_audit.p + at;
+  return CLDN_HIP_OK;
 }
 
 // two device buffers -> report: tables up, one clear, one kernel; HOST report: one copy, one synchronisation
@@ -2178,44 +2260,24 @@ static int audit_device(cldn_hip_codec* c, const uint8_t* d_a, const uint8_t* d_
   const size_t rep_bytes = (size_t)n_clouds * n_fields * sizeof(cldn_hip_audit_field_t);
   if (rep_bytes == 0) return CLDN_HIP_OK;
   int rc;
-  uint32_t n_blocks = 0;
-  if ((rc = count_point_blocks(cloud_points, n_clouds, "audit", &n_blocks)) != CLDN_HIP_OK) return rc;
-  const bool dev_fields = n_fields > kAuditArgFields;
-  const size_t clouds_b = ((size_t)n_clouds * sizeof(AuditCloud) + 63u) & ~size_t(63);
-  const size_t blocks_b = ((size_t)n_blocks * sizeof(AuditBlock) + 63u) & ~size_t(63);
-  const size_t fields_b = dev_fields ? ((size_t)n_fields * sizeof(AuditField) + 63u) & ~size_t(63) : 0u;
-  if (c->ev_audit) HIP_TRY(hipEventSynchronize(c->ev_audit));  // the previous call's upload has left the staging buffer
-  else HIP_TRY(hipEventCreateWithFlags(&c->ev_audit, hipEventDisableTiming));
-  if ((rc = c->h_audit.ensure(clouds_b + blocks_b + fields_b)) != CLDN_HIP_OK) return rc;
-  if ((rc = c->d_audit_tab.ensure(clouds_b + blocks_b + fields_b)) != CLDN_HIP_OK) return rc;
-  fill_point_blocks(cloud_points, n_clouds, (AuditCloud*)c->h_audit.p, (AuditBlock*)((uint8_t*)c->h_audit.p + clouds_b));
-  if (dev_fields) memcpy((uint8_t*)c->h_audit.p + clouds_b + blocks_b, fields.data(), (size_t)n_fields * sizeof(AuditField));
-  HIP_TRY(hipMemcpyAsync(c->d_audit_tab.p, c->h_audit.p, clouds_b + blocks_b + fields_b, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(c->ev_audit, c->stream));
-  unsigned long long* d_rep = (unsigned long long*)report;
-  if (report_loc == CLDN_HIP_HOST) {
-    if ((rc = c->d_audit_rep.ensure(rep_bytes)) != CLDN_HIP_OK) return rc;
-    d_rep = (unsigned long long*)c->d_audit_rep.p;
-  }
   AuditLaunch L;
+  const ReportBatch B = {cloud_points, n_clouds, n_fields};
+  TableSection sec[3] = {cloud_section(B), {}, field_section(fields)};
+  if ((rc = block_section(B, "audit", &L.n_blocks, &sec[1])) != CLDN_HIP_OK) return rc;
+  if ((rc = upload_tables(c, B, sec, 3)) != CLDN_HIP_OK) return rc;
+  if ((rc = report_place(c, report, report_loc, rep_bytes, &L.report)) != CLDN_HIP_OK) return rc;
   L.stream = c->stream;
   L.a = d_a;
   L.b = d_b;
   L.point_step = c->plan.point_step;
   L.n_clouds = n_clouds;
-  L.n_blocks = n_blocks;
   L.n_fields = n_fields;
   L.fields = fields.data();
-  L.dev_fields = dev_fields ? (const AuditField*)((const uint8_t*)c->d_audit_tab.p + clouds_b + blocks_b) : nullptr;
-  L.clouds = (const AuditCloud*)c->d_audit_tab.p;
-  L.blocks = (const AuditBlock*)((const uint8_t*)c->d_audit_tab.p + clouds_b);
-  L.report = d_rep;
+  L.dev_fields = (const AuditField*)sec[2].dev;
+  L.clouds = (const ReportCloud*)sec[0].dev;
+  L.blocks = (const ReportBlock*)sec[1].dev;
   if ((rc = audit_launch(L)) != CLDN_HIP_OK) return rc;
-  if (report_loc == CLDN_HIP_HOST) {
-    HIP_TRY(hipMemcpyAsync(report, d_rep, rep_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return CLDN_HIP_OK;
+  return report_fetch(c, report, report_loc, L.report, rep_bytes);
 }
 
 static int no_last_encode(const char* who) {
@@ -2240,7 +2302,7 @@ static int audit_streams_impl(cldn_hip_codec* c, const void* points, int points_
   if (stream_kind != CLDN_HIP_STAGE2_NONE && stream_kind != CLDN_HIP_STAGE2_LZ4)
     return fail(CLDN_HIP_ERR_ARG, "audit_streams: stream_kind %d is neither framed stage-1 streams (0) nor LZ4 chunks (1)", stream_kind);
   int rc;
-  if ((rc = audit_check_report(c->plan, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  if ((rc = report_check("audit", !c->plan.fields.empty(), n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
   std::vector<AuditField> fields;
   if ((rc = audit_fields(c->plan, limit, &fields)) != CLDN_HIP_OK) return rc;
   uint64_t n_points = 0;
@@ -2293,7 +2355,7 @@ int cldn_hip_audit_clouds(cldn_hip_codec_t* c, const void* a, int a_loc, const v
   if ((a_loc != CLDN_HIP_HOST && a_loc != CLDN_HIP_DEVICE) || (b_loc != CLDN_HIP_HOST && b_loc != CLDN_HIP_DEVICE))
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
   int rc;
-  if ((rc = audit_check_report(c->plan, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  if ((rc = report_check("audit", !c->plan.fields.empty(), n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
   std::vector<AuditField> fields;
   if ((rc = audit_fields(c->plan, limit, &fields)) != CLDN_HIP_OK) return rc;
   uint64_t n_points = 0;
@@ -2302,24 +2364,12 @@ int cldn_hip_audit_clouds(cldn_hip_codec_t* c, const void* a, int a_loc, const v
   ENTER_DEVICE(c->device);
   const uint64_t bytes = n_points * c->plan.point_step;
   const size_t one = ((size_t)bytes + 255u) & ~size_t(255);
-  const uint8_t* d_a = (const uint8_t*)a;
-  const uint8_t* d_b = (const uint8_t*)b;
+  const uint8_t *d_a, *d_b;
   const bool up_a = a_loc == CLDN_HIP_HOST && bytes, up_b = b_loc == CLDN_HIP_HOST && bytes;
-  if (up_a || up_b) {
-    if ((rc = c->d_audit.ensure(one * ((up_a ? 1u : 0u) + (up_b ? 1u : 0u)))) != CLDN_HIP_OK) return rc;
-    uint8_t* at = (uint8_t*)c->d_audit.p;
-    if (up_a) {
-      HIP_TRY(hipMemcpyAsync(at, a, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-      d_a = at;
-      at += one;
-    }
-    if (up_b) {
-      HIP_TRY(hipMemcpyAsync(at, b, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-      d_b = at;
-    }
-  }
+  const size_t room = one * ((up_a ? 1u : 0u) + (up_b ? 1u : 0u));
+  if ((rc = stage_host_points(c, a, a_loc, bytes, 0u, room, &d_a)) != CLDN_HIP_OK) return rc;
+  if ((rc = stage_host_points(c, b, b_loc, bytes, up_a ? one : 0u, room, &d_b)) != CLDN_HIP_OK) return rc;
   rc = audit_device(c, d_a, d_b, cloud_points, n_clouds, fields, report, report_loc);
-  // (pageable host buffers: the call does not return while a copy may still read them)
   if (rc == CLDN_HIP_OK && (up_a || up_b) && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
   return rc;
 }
@@ -2416,50 +2466,26 @@ static int sweep_device(cldn_hip_codec* c, const uint8_t* d_points, const uint64
   const size_t rep_bytes = (size_t)n_clouds * n_fields * n_candidates * sizeof(cldn_hip_sweep_cell_t);
   if (rep_bytes == 0) return CLDN_HIP_OK;
   int rc;
-  uint32_t n_blocks = 0;
-  if ((rc = count_point_blocks(cloud_points, n_clouds, "sweep", &n_blocks)) != CLDN_HIP_OK) return rc;
-  const bool dev_fields = n_fields > kAuditArgFields;
-  const size_t clouds_b = ((size_t)n_clouds * sizeof(AuditCloud) + 63u) & ~size_t(63);
-  const size_t blocks_b = ((size_t)n_blocks * sizeof(AuditBlock) + 63u) & ~size_t(63);
-  const size_t cands_b = (cands.size() * sizeof(SweepCand) + 63u) & ~size_t(63);
-  const size_t fields_b = dev_fields ? ((size_t)n_fields * sizeof(SweepField) + 63u) & ~size_t(63) : 0u;
-  const size_t tab_b = clouds_b + blocks_b + cands_b + fields_b;
-  if (c->ev_audit) HIP_TRY(hipEventSynchronize(c->ev_audit));  // the previous call's upload has left the staging buffer
-  else HIP_TRY(hipEventCreateWithFlags(&c->ev_audit, hipEventDisableTiming));
-  if ((rc = c->h_audit.ensure(tab_b)) != CLDN_HIP_OK) return rc;
-  if ((rc = c->d_audit_tab.ensure(tab_b)) != CLDN_HIP_OK) return rc;
-  uint8_t* h = (uint8_t*)c->h_audit.p;
-  fill_point_blocks(cloud_points, n_clouds, (AuditCloud*)h, (AuditBlock*)(h + clouds_b));
-  memcpy(h + clouds_b + blocks_b, cands.data(), cands.size() * sizeof(SweepCand));
-  if (dev_fields) memcpy(h + clouds_b + blocks_b + cands_b, fields.data(), (size_t)n_fields * sizeof(SweepField));
-  HIP_TRY(hipMemcpyAsync(c->d_audit_tab.p, h, tab_b, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(c->ev_audit, c->stream));
-  unsigned long long* d_rep = (unsigned long long*)report;
-  if (report_loc == CLDN_HIP_HOST) {
-    if ((rc = c->d_audit_rep.ensure(rep_bytes)) != CLDN_HIP_OK) return rc;
-    d_rep = (unsigned long long*)c->d_audit_rep.p;
-  }
-  const uint8_t* d_tab = (const uint8_t*)c->d_audit_tab.p;
   SweepLaunch L;
+  const ReportBatch B = {cloud_points, n_clouds, n_fields};
+  TableSection sec[4] = {cloud_section(B), {},
+                         TableSection{cands.size() * sizeof(SweepCand), cands.data(), nullptr, nullptr}, field_section(fields)};
+  if ((rc = block_section(B, "sweep", &L.n_blocks, &sec[1])) != CLDN_HIP_OK) return rc;
+  if ((rc = upload_tables(c, B, sec, 4)) != CLDN_HIP_OK) return rc;
+  if ((rc = report_place(c, report, report_loc, rep_bytes, &L.report)) != CLDN_HIP_OK) return rc;
   L.stream = c->stream;
   L.points = d_points;
   L.point_step = c->plan.point_step;
   L.n_clouds = n_clouds;
-  L.n_blocks = n_blocks;
   L.n_fields = n_fields;
   L.n_candidates = n_candidates;
   L.fields = fields.data();
-  L.dev_fields = dev_fields ? (const SweepField*)(d_tab + clouds_b + blocks_b + cands_b) : nullptr;
-  L.cands = (const SweepCand*)(d_tab + clouds_b + blocks_b);
-  L.clouds = (const AuditCloud*)d_tab;
-  L.blocks = (const AuditBlock*)(d_tab + clouds_b);
-  L.report = d_rep;
+  L.dev_fields = (const SweepField*)sec[3].dev;
+  L.cands = (const SweepCand*)sec[2].dev;
+  L.clouds = (const ReportCloud*)sec[0].dev;
+  L.blocks = (const ReportBlock*)sec[1].dev;
   if ((rc = sweep_launch(L)) != CLDN_HIP_OK) return rc;
-  if (report_loc == CLDN_HIP_HOST) {
-    HIP_TRY(hipMemcpyAsync(report, d_rep, rep_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return CLDN_HIP_OK;
+  return report_fetch(c, report, report_loc, L.report, rep_bytes);
 }
 
 extern "C" {
@@ -2470,7 +2496,7 @@ int cldn_hip_sweep_clouds(cldn_hip_codec_t* c, const void* points, int points_lo
   c->enc.drop();
   if (points_loc != CLDN_HIP_HOST && points_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
   int rc;
-  if ((rc = audit_check_report(c->plan, n_clouds, report, report_loc, "sweep")) != CLDN_HIP_OK) return rc;
+  if ((rc = report_check("sweep", !c->plan.fields.empty(), n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
   std::vector<SweepField> fields;
   std::vector<SweepCand> cands;
   if ((rc = sweep_tables(c->plan, resolutions, n_candidates, &fields, &cands)) != CLDN_HIP_OK) return rc;
@@ -2479,16 +2505,10 @@ int cldn_hip_sweep_clouds(cldn_hip_codec_t* c, const void* points, int points_lo
   if (n_points && !points) return fail(CLDN_HIP_ERR_ARG, "sweep_clouds: points is NULL");
   ENTER_DEVICE(c->device);
   const uint64_t bytes = n_points * c->plan.point_step;
-  const uint8_t* d_points = (const uint8_t*)points;
-  const bool up = points_loc == CLDN_HIP_HOST && bytes;
-  if (up) {
-    if ((rc = c->d_audit.ensure((size_t)bytes)) != CLDN_HIP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_audit.p, points, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-    d_points = (const uint8_t*)c->d_audit.p;
-  }
+  const uint8_t* d_points;
+  if ((rc = stage_host_points(c, points, points_loc, bytes, 0u, (size_t)bytes, &d_points)) != CLDN_HIP_OK) return rc;
   rc = sweep_device(c, d_points, cloud_points, n_clouds, fields, cands, n_candidates, report, report_loc);
-  // (pageable host buffers: the call does not return while a copy may still read them)
-  if (rc == CLDN_HIP_OK && up && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
+  if (rc == CLDN_HIP_OK && points_loc == CLDN_HIP_HOST && bytes && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
   return rc;
 }
 
@@ -2505,7 +2525,7 @@ int cldn_hip_sweep_last_encode(cldn_hip_codec_t* c, const float* resolutions, ui
   const cldn_hip_codec::LastEncode& E = c->enc;  // read only: the state stays as it is
   const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
   int rc;
-  if ((rc = audit_check_report(c->plan, n_clouds, report, report_loc, "sweep")) != CLDN_HIP_OK) return rc;
+  if ((rc = report_check("sweep", !c->plan.fields.empty(), n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
   std::vector<SweepField> fields;
   std::vector<SweepCand> cands;
   if ((rc = sweep_tables(c->plan, resolutions, n_candidates, &fields, &cands)) != CLDN_HIP_OK) return rc;
@@ -2516,13 +2536,6 @@ int cldn_hip_sweep_last_encode(cldn_hip_codec_t* c, const float* resolutions, ui
 }  // extern "C"
 
 // ---- sweep of the adaptive integer modes: section bytes per mode, probed and best mode (mode_kernels.hip) ----
-
-static int modes_check_report(const cldn_hip_plan& P, uint32_t n_clouds, const void* report, int report_loc) {
-  if (report_loc != CLDN_HIP_HOST && report_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
-  if (n_clouds && P.n_adaptive_total() && !report) return fail(CLDN_HIP_ERR_ARG, "sweep_modes: report is NULL");
-  if (report_loc == CLDN_HIP_DEVICE && ((uintptr_t)report & 7u)) return fail(CLDN_HIP_ERR_ARG, "sweep_modes: a device report must be 8-byte aligned");
-  return CLDN_HIP_OK;
-}
 
 static int modes_fields(const cldn_hip_plan& P, std::vector<ModeField>* out) {
   out->assign(P.adaptive_all.size(), ModeField{});
@@ -2539,6 +2552,16 @@ static int modes_fields(const cldn_hip_plan& P, std::vector<ModeField>* out) {
   return CLDN_HIP_OK;
 }
 
+// The mode kernel's workgroups: chunks first, the probe last, field inner: the units of a chunk read the same points
+static void fill_units(const ReportBatch& B, void* h) {
+  ModeUnit* hu = (ModeUnit*)h;
+  for (uint32_t k = 0; k < B.n_clouds; ++k) {
+    const uint32_t nc = (uint32_t)((B.cloud_points[k] + kPointsPerChunk - 1u) / kPointsPerChunk);
+    for (uint32_t j = 0; j < nc + (nc ? 1u : 0u); ++j)
+      for (uint32_t a = 0; a < B.n_fields; ++a) *hu++ = ModeUnit{k, j < nc ? j : kModeProbeUnit, a, 0u};
+  }
+}
+
 // device points -> report: tables up, one clear, one kernel; HOST report: one copy, one synchronisation
 static int modes_device(cldn_hip_codec* c, const uint8_t* d_points, const uint64_t* cloud_points, uint32_t n_clouds,
                         const std::vector<ModeField>& fields, cldn_hip_mode_cell_t* report, int report_loc) {
@@ -2551,56 +2574,24 @@ static int modes_device(cldn_hip_codec* c, const uint8_t* d_points, const uint64
   for (uint32_t k = 0; k < n_clouds; ++k)
     sections += (cloud_points[k] + kPointsPerChunk - 1u) / kPointsPerChunk + (cloud_points[k] ? 1u : 0u);
   if (sections * n_fields > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "sweep_modes: more than 2^31 sections");
-  const uint32_t n_units = (uint32_t)(sections * n_fields);
-  const bool dev_fields = n_fields > kAuditArgFields;
-  const size_t clouds_b = ((size_t)n_clouds * sizeof(AuditCloud) + 63u) & ~size_t(63);
-  const size_t units_b = ((size_t)n_units * sizeof(ModeUnit) + 63u) & ~size_t(63);
-  const size_t fields_b = dev_fields ? ((size_t)n_fields * sizeof(ModeField) + 63u) & ~size_t(63) : 0u;
-  const size_t tab_b = clouds_b + units_b + fields_b;
-  if (c->ev_audit) HIP_TRY(hipEventSynchronize(c->ev_audit));  // the previous call's upload has left the staging buffer
-  else HIP_TRY(hipEventCreateWithFlags(&c->ev_audit, hipEventDisableTiming));
-  if ((rc = c->h_audit.ensure(tab_b)) != CLDN_HIP_OK) return rc;
-  if ((rc = c->d_audit_tab.ensure(tab_b)) != CLDN_HIP_OK) return rc;
-  uint8_t* h = (uint8_t*)c->h_audit.p;
-  AuditCloud* hc = (AuditCloud*)h;
-  ModeUnit* hu = (ModeUnit*)(h + clouds_b);
-  uint64_t first = 0;
-  uint32_t ui = 0;
-  for (uint32_t k = 0; k < n_clouds; ++k) {  // chunks first, field inner: the units of a chunk read the same points
-    hc[k].first_point = first;
-    hc[k].n_points = cloud_points[k];
-    first += cloud_points[k];
-    const uint32_t nc = (uint32_t)((cloud_points[k] + kPointsPerChunk - 1u) / kPointsPerChunk);
-    for (uint32_t j = 0; j < nc + (nc ? 1u : 0u); ++j)
-      for (uint32_t a = 0; a < n_fields; ++a) hu[ui++] = ModeUnit{k, j < nc ? j : kModeProbeUnit, a, 0u};
-  }
-  if (dev_fields) memcpy(h + clouds_b + units_b, fields.data(), (size_t)n_fields * sizeof(ModeField));
-  HIP_TRY(hipMemcpyAsync(c->d_audit_tab.p, h, tab_b, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(c->ev_audit, c->stream));
-  unsigned long long* d_rep = (unsigned long long*)report;
-  if (report_loc == CLDN_HIP_HOST) {
-    if ((rc = c->d_audit_rep.ensure(rep_bytes)) != CLDN_HIP_OK) return rc;
-    d_rep = (unsigned long long*)c->d_audit_rep.p;
-  }
-  const uint8_t* d_tab = (const uint8_t*)c->d_audit_tab.p;
   ModeLaunch L;
+  L.n_units = (uint32_t)(sections * n_fields);
+  const ReportBatch B = {cloud_points, n_clouds, n_fields};
+  TableSection sec[3] = {cloud_section(B), TableSection{(size_t)L.n_units * sizeof(ModeUnit), nullptr, fill_units, nullptr},
+                         field_section(fields)};
+  if ((rc = upload_tables(c, B, sec, 3)) != CLDN_HIP_OK) return rc;
+  if ((rc = report_place(c, report, report_loc, rep_bytes, &L.report)) != CLDN_HIP_OK) return rc;
   L.stream = c->stream;
   L.points = d_points;
   L.point_step = c->plan.point_step;
   L.n_clouds = n_clouds;
-  L.n_units = n_units;
   L.n_fields = n_fields;
   L.fields = fields.data();
-  L.dev_fields = dev_fields ? (const ModeField*)(d_tab + clouds_b + units_b) : nullptr;
-  L.clouds = (const AuditCloud*)d_tab;
-  L.units = (const ModeUnit*)(d_tab + clouds_b);
-  L.report = d_rep;
+  L.dev_fields = (const ModeField*)sec[2].dev;
+  L.clouds = (const ReportCloud*)sec[0].dev;
+  L.units = (const ModeUnit*)sec[1].dev;
   if ((rc = modes_launch(L)) != CLDN_HIP_OK) return rc;
-  if (report_loc == CLDN_HIP_HOST) {
-    HIP_TRY(hipMemcpyAsync(report, d_rep, rep_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return CLDN_HIP_OK;
+  return report_fetch(c, report, report_loc, L.report, rep_bytes);
 }
 
 extern "C" {
@@ -2611,7 +2602,7 @@ int cldn_hip_sweep_modes_clouds(cldn_hip_codec_t* c, const void* points, int poi
   c->enc.drop();
   if (points_loc != CLDN_HIP_HOST && points_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
   int rc;
-  if ((rc = modes_check_report(c->plan, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  if ((rc = report_check("sweep_modes", c->plan.n_adaptive_total() != 0, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
   std::vector<ModeField> fields;
   if ((rc = modes_fields(c->plan, &fields)) != CLDN_HIP_OK) return rc;
   uint64_t n_points = 0;
@@ -2620,16 +2611,10 @@ int cldn_hip_sweep_modes_clouds(cldn_hip_codec_t* c, const void* points, int poi
   if (n_points && !points) return fail(CLDN_HIP_ERR_ARG, "sweep_modes_clouds: points is NULL");
   ENTER_DEVICE(c->device);
   const uint64_t bytes = n_points * c->plan.point_step;
-  const uint8_t* d_points = (const uint8_t*)points;
-  const bool up = points_loc == CLDN_HIP_HOST && bytes;
-  if (up) {
-    if ((rc = c->d_audit.ensure((size_t)bytes)) != CLDN_HIP_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_audit.p, points, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-    d_points = (const uint8_t*)c->d_audit.p;
-  }
+  const uint8_t* d_points;
+  if ((rc = stage_host_points(c, points, points_loc, bytes, 0u, (size_t)bytes, &d_points)) != CLDN_HIP_OK) return rc;
   rc = modes_device(c, d_points, cloud_points, n_clouds, fields, report, report_loc);
-  // (pageable host buffers: the call does not return while a copy may still read them)
-  if (rc == CLDN_HIP_OK && up && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
+  if (rc == CLDN_HIP_OK && points_loc == CLDN_HIP_HOST && bytes && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
   return rc;
 }
 
@@ -2639,7 +2624,7 @@ int cldn_hip_sweep_modes_last_encode(cldn_hip_codec_t* c, cldn_hip_mode_cell_t* 
   const cldn_hip_codec::LastEncode& E = c->enc;  // read only: the state stays as it is
   const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
   int rc;
-  if ((rc = modes_check_report(c->plan, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  if ((rc = report_check("sweep_modes", c->plan.n_adaptive_total() != 0, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
   std::vector<ModeField> fields;
   if ((rc = modes_fields(c->plan, &fields)) != CLDN_HIP_OK) return rc;
   if (fields.empty()) return CLDN_HIP_OK;

@@ -11,8 +11,8 @@
 //               from v' - v''. Run lengths come from the run-start flags: a lane that starts a run closes the one in front of
 //               it, whose start is the nearest flag below it -- in its wave's ballot, else in the per-wave records of the stage,
 //               else the start carried over from earlier stages (a run may span the whole chunk). The last run is closed at n.
-//   STAGED      point_step <= kAuditStagedStep: whole 16-byte units through LDS at any pointer residue, as k_sweep does
-//   DIRECT      wider points: a lane reads its three values from global memory
+//   STAGED      the stage's points and the two in front of them go through LDS, DIRECT: a lane reads its three values in
+//               place (stage1_report.h)
 //   Palette     the exact distinct count U of the unit. 16-bit fields: a 65536-bit bitmap in LDS, filled in phase A. Wider
 //               fields, phase B: a 64 KiB LDS table of keys as wide as the field (16384 of 32 bits, 8192 of 64 bits compared on
 //               all 64 bits; 0 = empty: a zero value is counted by a flag) takes the keys of ONE hash partition per pass over
@@ -26,12 +26,10 @@
 //               Only counts are kept.
 //   report      at most one 64-bit atomic per quantity and workgroup; the unit that arrives last at its cell (a counter kept
 //               in the cell's best_mode word, release / acquire at agent scope) applies the selection rule to the sums
-//   tables      fields as a kernel argument (up to kAuditArgFields), else in device memory
+//   tables      fields as a kernel argument or in device memory (stage1_report.h)
 // Every quantity is a sum of integers: the report does not depend on the order of the atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <cstring>
 
 #include "stage1_launch.h"
 #include "stage1_math.h"
@@ -57,22 +55,6 @@ struct ModeSmall {
 };
 constexpr uint32_t kModeLdsBytes = kModeSmallOff + (uint32_t)sizeof(ModeSmall);
 static_assert(sizeof(ModeSmall) % 16 == 0 && kModeBitmapOff + 8192u <= kModeSmallOff, "LDS carve");
-
-struct ModeArgTable {
-  ModeField f[kAuditArgFields];
-};
-
-// little-endian 2, 4 or 8 bytes at any alignment (LDS or global)
-__device__ __forceinline__ uint32_t mode_ld32(const uint8_t* p) {
-  if ((((uintptr_t)p) & 3u) == 0u) return *reinterpret_cast<const uint32_t*>(p);
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-__device__ __forceinline__ unsigned long long mode_ld(const uint8_t* p, uint32_t bpv) {
-  if (bpv == 2u) return (uint32_t)p[0] | ((uint32_t)p[1] << 8);
-  unsigned long long v = mode_ld32(p);
-  if (bpv == 8u) v |= (unsigned long long)mode_ld32(p + 4) << 32;
-  return v;
-}
 
 // hashPaletteValue's mixer kept at 64 bits: a bijection, so distinct keys differ in some bit of it
 __device__ __forceinline__ unsigned long long mode_mix(unsigned long long v) {
@@ -118,7 +100,7 @@ __device__ __forceinline__ uint32_t mode_unique(const uint8_t* __restrict__ col,
       __syncthreads();
       for (uint32_t j = t; j < n; j += kModeThreads) {
         if (*(volatile uint32_t*)&S.pal_count > kCap) break;  // the partition does not fit
-        const unsigned long long r = mode_ld(col + (size_t)j * step, (uint32_t)sizeof(K));
+        const unsigned long long r = report_ld(col + (size_t)j * step, (uint32_t)sizeof(K));
         if (r == 0ull) {
           if (p == 0u) S.pal_zero = 1u;
           continue;
@@ -155,9 +137,9 @@ __device__ __forceinline__ uint32_t mode_unique(const uint8_t* __restrict__ col,
   __syncthreads();
   uint32_t firsts = 0u;
   for (uint32_t j = t; j < n; j += kModeThreads) {
-    const unsigned long long r = mode_ld(col + (size_t)j * step, (uint32_t)sizeof(K));
+    const unsigned long long r = report_ld(col + (size_t)j * step, (uint32_t)sizeof(K));
     bool seen = false;
-    for (uint32_t i = 0; i < j && !seen; ++i) seen = mode_ld(col + (size_t)i * step, (uint32_t)sizeof(K)) == r;
+    for (uint32_t i = 0; i < j && !seen; ++i) seen = report_ld(col + (size_t)i * step, (uint32_t)sizeof(K)) == r;
     if (!seen) ++firsts;
   }
   if (firsts) atomicAdd(&S.pal_count, firsts);
@@ -172,7 +154,7 @@ __device__ __forceinline__ void mode_section_sizes(const uint8_t* __restrict__ b
   ModeSmall& S = *reinterpret_cast<ModeSmall*>(lds + kModeSmallOff);
   uint32_t* const bitmap = reinterpret_cast<uint32_t*>(lds + kModeBitmapOff);
   const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-  const uint32_t bpv = F.bpv;
+  const uint32_t bpv = F.bpv == 2u ? 2u : (F.bpv == 8u ? 8u : 4u);  // (spelled out: report_ld's 1-byte case is not this kernel's)
   uint32_t acc[Q_COUNT];
 #pragma unroll
   for (uint32_t q = 0; q < Q_COUNT; ++q) acc[q] = 0u;
@@ -188,17 +170,9 @@ __device__ __forceinline__ void mode_section_sizes(const uint8_t* __restrict__ b
     const uint32_t lead = s0 ? 2u : 0u;  // the two values in front of the stage (stage_points >= 64: they exist)
     const uint8_t* p0 = base + (size_t)s0 * step;
     if (kStaged) {
-      // whole 16-byte units from the boundary at or below the first needed byte: the bytes in front of it and behind the last
-      // one share an aligned unit (and a page) with bytes of the range and are never looked at
-      const uint8_t* g0 = p0 - lead * step;
-      const uint32_t head = (uint32_t)(((uintptr_t)g0) & 15u);
-      const uint32_t units = (head + (pts + lead) * step + 15u) >> 4;
-      const uint4* g = reinterpret_cast<const uint4*>(g0 - head);
-      uint4* stage = reinterpret_cast<uint4*>(lds);
       if (s0) __syncthreads();  // the previous stage's readers are done
-      for (uint32_t u = t; u < units; u += kModeThreads) stage[u] = g[u];
+      p0 = report_stage(p0 - lead * step, (pts + lead) * step, reinterpret_cast<uint4*>(lds), kModeThreads) + lead * step;
       __syncthreads();
-      p0 = lds + head + lead * step;
     }
     const bool active = t < pts;
     const uint32_t j = s0 + t;  // index in the section
@@ -206,10 +180,10 @@ __device__ __forceinline__ void mode_section_sizes(const uint8_t* __restrict__ b
     bool rs = false, ds = false;
     if (active) {
       const uint8_t* at = p0 + (size_t)t * step + F.offset;
-      const unsigned long long r = mode_ld(at, bpv);
+      const unsigned long long r = report_ld(at, bpv);
       const unsigned long long v = (unsigned long long)int_field_as_i64(r, F.type);
-      const unsigned long long v1 = j >= 1u ? (unsigned long long)int_field_as_i64(mode_ld(at - step, bpv), F.type) : 0ull;
-      const unsigned long long v2 = j >= 2u ? (unsigned long long)int_field_as_i64(mode_ld(at - 2u * step, bpv), F.type) : 0ull;
+      const unsigned long long v1 = j >= 1u ? (unsigned long long)int_field_as_i64(report_ld(at - step, bpv), F.type) : 0ull;
+      const unsigned long long v2 = j >= 2u ? (unsigned long long)int_field_as_i64(report_ld(at - 2u * step, bpv), F.type) : 0ull;
       d = v - v1;  // int64 wrap-around
       rs = j == 0u || v != v1;
       ds = j == 0u || d != v1 - v2;
@@ -257,9 +231,7 @@ __device__ __forceinline__ void mode_section_sizes(const uint8_t* __restrict__ b
     for (uint32_t u = t; u < 2048u; u += kModeThreads) acc[Q_UNIQUE] += (uint32_t)__popc(bitmap[u]);
 #pragma unroll
   for (uint32_t q = 0; q < Q_COUNT; ++q) {
-    uint32_t x = acc[q];
-#pragma unroll
-    for (int dd = 1; dd < 64; dd <<= 1) x += (uint32_t)__shfl_xor((int)x, dd);
+    const uint32_t x = wave_sum_u32(acc[q]);
     if (lane == 0u) S.red[q][wave] = x;
   }
   __syncthreads();  // also: every reader of the stage is done, phase B may take the LDS
@@ -285,13 +257,13 @@ __device__ __forceinline__ void mode_section_sizes(const uint8_t* __restrict__ b
 
 // kStaged: phase A goes through dynamic LDS. kArgs: the field table is the kernel argument `tab`, else `dev_fields`.
 template <bool kStaged, bool kArgs>
-__global__ __launch_bounds__(kModeThreads) void k_modes(const uint8_t* __restrict__ points, const AuditCloud* __restrict__ clouds,
+__global__ __launch_bounds__(kModeThreads) void k_modes(const uint8_t* __restrict__ points, const ReportCloud* __restrict__ clouds,
                                                         const ModeUnit* __restrict__ units, uint32_t step, uint32_t n_fields,
                                                         uint32_t stage_points, const ModeField* __restrict__ dev_fields,
-                                                        unsigned long long* report, const ModeArgTable tab) {
+                                                        unsigned long long* report, const ReportArgTable<ModeField> tab) {
   extern __shared__ __attribute__((aligned(16))) uint8_t mode_lds[];
   const ModeUnit ud = units[blockIdx.x];
-  const AuditCloud cd = clouds[ud.cloud];
+  const ReportCloud cd = clouds[ud.cloud];
   const ModeField F = kArgs ? tab.f[ud.field] : dev_fields[ud.field];
   const bool probe = ud.chunk == kModeProbeUnit;
   const unsigned long long first = probe ? 0ull : (unsigned long long)ud.chunk * kPointsPerChunk;  // cloud-local
@@ -319,19 +291,13 @@ __global__ __launch_bounds__(kModeThreads) void k_modes(const uint8_t* __restric
 }
 }  // namespace
 
-uint32_t modes_stage_points(uint32_t point_step) {
-  if (point_step == 0u || point_step > kAuditStagedStep) return 0u;
-  const uint32_t fit = (kModeStageBytes - 32u) / point_step - 2u;  // two of them are the predecessors
-  return fit >= kModeThreads ? kModeThreads : (fit / 64u) * 64u;
-}
-
 int modes_configure() {
-  hipError_t e;
-  if ((e = allow_lds(&k_modes<true, true>, kModeLdsBytes)) != hipSuccess) return launch_fail(e, "hipFuncSetAttribute(k_modes)");
-  if ((e = allow_lds(&k_modes<true, false>, kModeLdsBytes)) != hipSuccess) return launch_fail(e, "hipFuncSetAttribute(k_modes)");
-  if ((e = allow_lds(&k_modes<false, true>, kModeLdsBytes)) != hipSuccess) return launch_fail(e, "hipFuncSetAttribute(k_modes)");
-  if ((e = allow_lds(&k_modes<false, false>, kModeLdsBytes)) != hipSuccess) return launch_fail(e, "hipFuncSetAttribute(k_modes)");
-  return 0;
+  hipError_t e = hipSuccess;
+  for (uint32_t v = 0; v < 4u && e == hipSuccess; ++v)  // v enumerates (staged, args): all four instantiations
+    report_dispatch((v & 2u) != 0u, (v & 1u) != 0u, [&](auto staged, auto in_args) {
+      e = allow_lds(&k_modes<decltype(staged)::value, decltype(in_args)::value>, kModeLdsBytes);
+    });
+  return e == hipSuccess ? 0 : launch_fail(e, "hipFuncSetAttribute(k_modes)");
 }
 
 int modes_launch(const ModeLaunch& L) {
@@ -341,27 +307,14 @@ int modes_launch(const ModeLaunch& L) {
   if ((e = hipMemsetAsync(L.report, 0, rep_bytes, L.stream)) != hipSuccess) return launch_fail(e, "modes: clearing the report");
   if (L.n_units == 0) return 0;
   const bool args = L.dev_fields == nullptr;
-  ModeArgTable tab;
-  memset(&tab, 0, sizeof(tab));
-  if (args)
-    for (uint32_t f = 0; f < L.n_fields; ++f) tab.f[f] = L.fields[f];
-  const uint32_t sp = modes_stage_points(L.point_step);
-  const dim3 grid(L.n_units), block(kModeThreads);
-  if (sp) {
-    if (args)
-      hipLaunchKernelGGL((k_modes<true, true>), grid, block, kModeLdsBytes, L.stream, L.points, L.clouds, L.units, L.point_step,
-                         L.n_fields, sp, L.dev_fields, L.report, tab);
-    else
-      hipLaunchKernelGGL((k_modes<true, false>), grid, block, kModeLdsBytes, L.stream, L.points, L.clouds, L.units, L.point_step,
-                         L.n_fields, sp, L.dev_fields, L.report, tab);
-  } else {
-    if (args)
-      hipLaunchKernelGGL((k_modes<false, true>), grid, block, kModeLdsBytes, L.stream, L.points, L.clouds, L.units, L.point_step,
-                         L.n_fields, kModeThreads, L.dev_fields, L.report, tab);
-    else
-      hipLaunchKernelGGL((k_modes<false, false>), grid, block, kModeLdsBytes, L.stream, L.points, L.clouds, L.units, L.point_step,
-                         L.n_fields, kModeThreads, L.dev_fields, L.report, tab);
-  }
+  const ReportArgTable<ModeField> tab = report_arg_table(L.fields, L.n_fields, args);
+  // phase A's stage: one value per lane in whole waves, and their two predecessors
+  const uint32_t sp = report_stage_points(L.point_step, kModeStageBytes - 32u, 2u, kModeThreads, 64u);
+  report_dispatch(sp != 0u, args, [&](auto staged, auto in_args) {
+    hipLaunchKernelGGL((k_modes<decltype(staged)::value, decltype(in_args)::value>), dim3(L.n_units), dim3(kModeThreads),
+                       kModeLdsBytes, L.stream, L.points, L.clouds, L.units, L.point_step, L.n_fields, sp ? sp : kModeThreads,
+                       L.dev_fields, L.report, tab);
+  });
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_modes");
   return 0;
 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "stage1_device.h"
+#include "stage1_report.h"
 
 namespace cldn {
 
@@ -292,10 +293,8 @@ uint64_t viz_table_capacity(uint64_t n_points);
 int viz_launch(const VizLaunch& L);
 
 // ---- per-field error report of two point buffers (audit_kernels.hip; record: cldn_hip_audit_field_t, five 64-bit words) ----
-constexpr uint32_t kAuditBlockPoints = 1024;  // points per workgroup; blocks are cut per cloud, a cloud's last one may be partial
-constexpr uint32_t kAuditStagedStep = 127;    // widest point that goes through LDS (at least 256 points per stage), wider ones are read in place
+// Clouds, blocks, the staged route and the field table as a kernel argument are stage1_report.h's, for all three report kernels.
 constexpr uint32_t kAuditLdsBytes = 65536 - 256;  // dynamic LDS of the staged route: both buffers' stage, next to the reduction records
-constexpr uint32_t kAuditArgFields = 128;     // field table as a kernel argument (kMaxOps + kMaxAdaptive: every ordinary plan), else device memory
 struct AuditField {
   uint32_t offset;
   uint8_t size;      // 1, 2, 4, 8
@@ -304,14 +303,6 @@ struct AuditField {
   double limit;      // >= 0
 };
 static_assert(sizeof(AuditField) == 16, "128 of them are a kernel argument");
-struct AuditCloud {
-  uint64_t first_point;  // of the cloud in the batch
-  uint64_t n_points;
-};
-struct AuditBlock {
-  uint32_t cloud;
-  uint32_t block;        // of the cloud: its first point is block * kAuditBlockPoints (cloud-local)
-};
 struct AuditLaunch {
   hipStream_t stream;
   const uint8_t* a;              // device AoS, clouds back to back, any alignment
@@ -321,16 +312,15 @@ struct AuditLaunch {
   uint32_t n_blocks;
   uint32_t n_fields;
   const AuditField* fields;      // HOST [n_fields]
-  const AuditField* dev_fields;  // device copy of it, or NULL when n_fields <= kAuditArgFields
-  const AuditCloud* clouds;      // device [n_clouds]
-  const AuditBlock* blocks;      // device [n_blocks]
+  const AuditField* dev_fields;  // device copy of it, or NULL when n_fields <= kReportArgFields
+  const ReportCloud* clouds;     // device [n_clouds]
+  const ReportBlock* blocks;     // device [n_blocks]
   unsigned long long* report;    // device [n_clouds * n_fields * 5], 8-byte aligned: cleared, then filled
 };
-uint32_t audit_stage_points(uint32_t point_step);  // points per LDS stage, 0 = the direct route
 int audit_launch(const AuditLaunch& L);            // one clear + one kernel
 
 // ---- resolution sweep of the lossy float fields (sweep_kernels.hip; record: cldn_hip_sweep_cell_t, four 64-bit words) ----
-// Blocks and clouds are the audit's (AuditBlock / AuditCloud, kAuditBlockPoints: 1024 divides 32768, a block never straddles a chunk).
+// kReportBlockPoints = 1024 divides 32768: a block never straddles a chunk.
 constexpr uint32_t kSweepMaxCandidates = 16;      // CLDN_HIP_SWEEP_MAX_CANDIDATES
 constexpr uint32_t kSweepLdsBytes = 40960;        // dynamic LDS of the staged route: one predecessor point + the stage's points
 enum SweepKind : uint8_t { SWEEP_NONE = 0, SWEEP_QF32 = 1, SWEEP_F32 = 2, SWEEP_F64 = 3 };  // the field's encoder: OP_QF32 / OP_LOSSY_F32 / OP_LOSSY_F64
@@ -353,13 +343,12 @@ struct SweepLaunch {
   uint32_t n_fields;
   uint32_t n_candidates;         // 1..kSweepMaxCandidates
   const SweepField* fields;      // HOST [n_fields]
-  const SweepField* dev_fields;  // device copy of it, or NULL when n_fields <= kAuditArgFields
+  const SweepField* dev_fields;  // device copy of it, or NULL when n_fields <= kReportArgFields
   const SweepCand* cands;        // device [n_fields * n_candidates]
-  const AuditCloud* clouds;      // device [n_clouds]
-  const AuditBlock* blocks;      // device [n_blocks]
+  const ReportCloud* clouds;     // device [n_clouds]
+  const ReportBlock* blocks;     // device [n_blocks]
   unsigned long long* report;    // device [n_clouds * n_fields * n_candidates * 4], 8-byte aligned: cleared, then filled
 };
-uint32_t sweep_stage_points(uint32_t point_step);  // points per LDS stage, 0 = the direct route
 int sweep_launch(const SweepLaunch& L);            // one clear + one kernel
 
 // ---- sweep of the V5 adaptive integer modes (mode_kernels.hip; record: cldn_hip_mode_cell_t, five 64-bit words) ----
@@ -385,12 +374,11 @@ struct ModeLaunch {
   uint32_t n_units;
   uint32_t n_fields;             // adaptive fields of the plan
   const ModeField* fields;       // HOST [n_fields]
-  const ModeField* dev_fields;   // device copy of it, or NULL when n_fields <= kAuditArgFields
-  const AuditCloud* clouds;      // device [n_clouds]
+  const ModeField* dev_fields;   // device copy of it, or NULL when n_fields <= kReportArgFields
+  const ReportCloud* clouds;     // device [n_clouds]
   const ModeUnit* units;         // device [n_units]
   unsigned long long* report;    // device [n_clouds * n_fields * 5], 8-byte aligned: cleared, then filled
 };
-uint32_t modes_stage_points(uint32_t point_step);  // values per LDS stage of phase A, 0 = the direct route
 int modes_configure();
 int modes_launch(const ModeLaunch& L);             // one clear + one kernel
 

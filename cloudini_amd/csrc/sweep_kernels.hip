@@ -4,25 +4,22 @@
 // and the decoder's (stage1_math.h; eval_op in stage1_kernels.hip, the OP_QF32 / OP_LOSSY_* cases of stage1_decode.h).
 //
 // Shaped like k_audit (audit_kernels.hip), but bound by vector issue, not by HBM: every point is looked at once per candidate.
-//   blocks      at most 1024 points of ONE cloud per workgroup (the audit's AuditBlock table). 1024 divides 32768: a block
+//   blocks      at most 1024 points of ONE cloud per workgroup (the audit's ReportBlock table). 1024 divides 32768: a block
 //               never straddles a chunk, and the delta reference is 0 exactly when the block (or a later stage of it, never)
 //               starts a chunk; otherwise the point in front of the stage is staged with it
-//   STAGED      point_step <= kAuditStagedStep: whole 16-byte units through LDS, from the 16-byte boundary at or below the
-//               first needed byte -- coalesced at every pointer residue
-//   DIRECT      wider points: a lane reads its field (and the predecessor's) from global memory
+//   STAGED      the stage's points and the one in front of them go through LDS, DIRECT: a lane reads its field (and the
+//               predecessor's) in place (stage1_report.h)
 //   loop order  field outer, candidate inner: a lane takes the values of its (at most 4) points and of their predecessors out
 //               of LDS once per field and evaluates every candidate on registers. The predecessor's quantised value is
 //               recomputed, not exchanged between lanes.
 //   reduction   per candidate one packed 32-bit sum (bytes | class << 12 | over << 22: a wave has at most 256 points of at
 //               most 10 bytes) and one 64-bit max by cross-lane exchanges, one LDS record per wave and candidate; per field
 //               ONE barrier, then at most one global atomic per quantity and candidate, none where there is nothing to add
-//   tables      fields as a kernel argument (up to kAuditArgFields), else in device memory; ladders always in device memory
+//   tables      fields as a kernel argument or in device memory (stage1_report.h); ladders always in device memory
 //               (16 rungs of 128 fields do not fit an argument block): uniform loads, one per field and candidate
 // Every quantity is a sum or a max of integers: the report does not depend on the order of the atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <cstring>
 
 #include "stage1_launch.h"
 #include "stage1_math.h"
@@ -32,23 +29,8 @@ namespace cldn {
 namespace {
 constexpr uint32_t kSweepThreads = 256;
 constexpr uint32_t kSweepWaves = kSweepThreads / 64;
-constexpr uint32_t kSweepLanePoints = kAuditBlockPoints / kSweepThreads;  // points of a stage per lane
+constexpr uint32_t kSweepLanePoints = kReportBlockPoints / kSweepThreads;  // points of a stage per lane
 constexpr uint32_t kClassShift = 12, kOverShift = 22;
-
-struct SweepArgTable {
-  SweepField f[kAuditArgFields];
-};
-
-// little-endian 4 or 8 bytes at any alignment (LDS or global)
-__device__ __forceinline__ uint32_t sweep_ld32(const uint8_t* p) {
-  if ((((uintptr_t)p) & 3u) == 0u) return *reinterpret_cast<const uint32_t*>(p);
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-__device__ __forceinline__ unsigned long long sweep_ld(const uint8_t* p, bool wide) {
-  unsigned long long v = sweep_ld32(p);
-  if (wide) v |= (unsigned long long)sweep_ld32(p + 4) << 32;
-  return v;
-}
 
 // the audit's verdict on (original, decoded), both widened to double; the original is not a NaN
 __device__ __forceinline__ void sweep_err(uint32_t& sums, unsigned long long& max_bits, double da, double db, bool differ,
@@ -126,12 +108,8 @@ __device__ __forceinline__ void sweep_field(const unsigned long long (&cur)[kSwe
 #pragma unroll
       for (uint32_t i = 0; i < kSweepLanePoints; ++i)
         if ((valid >> i) & 1u) sweep_point<KIND>(sums, max_bits, cur[i], prv[i], ((has_prev >> i) & 1u) != 0u, C);
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        sums += (uint32_t)__shfl_xor((int)sums, d);
-        const unsigned long long o = (unsigned long long)__shfl_xor((long long)max_bits, d);
-        max_bits = o > max_bits ? o : max_bits;
-      }
+      sums = wave_sum_u32(sums);
+      max_bits = wave_max_u64(max_bits);
     }
     if (lane == 0u) {
       red.sums[slot][c][wave] = sums;
@@ -143,19 +121,20 @@ __device__ __forceinline__ void sweep_field(const unsigned long long (&cur)[kSwe
 // kStaged: stage_points points (and the one in front of them) at a time through dynamic LDS.
 // kArgs: the field table is the kernel argument `tab`, else `dev_fields`.
 template <bool kStaged, bool kArgs>
-__global__ __launch_bounds__(kSweepThreads) void k_sweep(const uint8_t* __restrict__ points, const AuditCloud* __restrict__ clouds,
-                                                         const AuditBlock* __restrict__ blocks, uint32_t step, uint32_t n_fields,
+__global__ __launch_bounds__(kSweepThreads) void k_sweep(const uint8_t* __restrict__ points, const ReportCloud* __restrict__ clouds,
+                                                         const ReportBlock* __restrict__ blocks, uint32_t step, uint32_t n_fields,
                                                          uint32_t n_candidates, uint32_t stage_points,
                                                          const SweepField* __restrict__ dev_fields,
                                                          const SweepCand* __restrict__ cands,
-                                                         unsigned long long* __restrict__ report, const SweepArgTable tab) {
+                                                         unsigned long long* __restrict__ report,
+                                                         const ReportArgTable<SweepField> tab) {
   extern __shared__ uint4 sweep_lds[];
   __shared__ SweepRed red;
-  const AuditBlock bd = blocks[blockIdx.x];
-  const AuditCloud cd = clouds[bd.cloud];
-  const unsigned long long first = (unsigned long long)bd.block * kAuditBlockPoints;  // cloud-local
+  const ReportBlock bd = blocks[blockIdx.x];
+  const ReportCloud cd = clouds[bd.cloud];
+  const unsigned long long first = (unsigned long long)bd.block * kReportBlockPoints;  // cloud-local
   const unsigned long long left = cd.n_points - first;
-  const uint32_t n = left < kAuditBlockPoints ? (uint32_t)left : kAuditBlockPoints;
+  const uint32_t n = left < kReportBlockPoints ? (uint32_t)left : kReportBlockPoints;
   unsigned long long* const rec0 = report + (size_t)bd.cloud * n_fields * n_candidates * 4u;
   const size_t byte0 = (size_t)(cd.first_point + first) * step;
   uint32_t slot = 0u;
@@ -165,22 +144,15 @@ __global__ __launch_bounds__(kSweepThreads) void k_sweep(const uint8_t* __restri
     const bool lead = ((first + s0) & (unsigned long long)(kPointsPerChunk - 1u)) != 0ull;
     const uint8_t* p0 = points + byte0 + (size_t)s0 * step;  // the stage's first point; p0 - step is readable when `lead`
     if (kStaged) {
-      // whole 16-byte units from the boundary at or below the first needed byte: the bytes in front of it and behind the last
-      // one share an aligned unit (and a page) with bytes of the range and are never looked at
-      const uint8_t* g0 = p0 - (lead ? step : 0u);
-      const uint32_t head = (uint32_t)(((uintptr_t)g0) & 15u);
-      const uint32_t len = (pts + (lead ? 1u : 0u)) * step;
-      const uint32_t units = (head + len + 15u) >> 4;
-      const uint4* g = reinterpret_cast<const uint4*>(g0 - head);
+      const uint32_t before = lead ? step : 0u;
       if (s0) __syncthreads();  // the previous stage's readers are done
-      for (uint32_t u = threadIdx.x; u < units; u += kSweepThreads) sweep_lds[u] = g[u];
+      p0 = report_stage(p0 - before, pts * step + before, sweep_lds, kSweepThreads) + before;
       __syncthreads();
-      p0 = reinterpret_cast<const uint8_t*>(sweep_lds) + head + (lead ? step : 0u);
     }
     for (uint32_t f = 0; f < n_fields; ++f) {
       const SweepField F = kArgs ? tab.f[f] : dev_fields[f];
       if (F.kind == SWEEP_NONE) continue;  // (uniform)
-      const bool wide = F.kind == SWEEP_F64;
+      const uint32_t size = F.kind == SWEEP_F64 ? 8u : 4u;
       unsigned long long cur[kSweepLanePoints], prv[kSweepLanePoints];
       uint32_t valid = 0u, has_prev = 0u;
 #pragma unroll
@@ -190,10 +162,10 @@ __global__ __launch_bounds__(kSweepThreads) void k_sweep(const uint8_t* __restri
         if (j < pts) {
           const uint8_t* at = p0 + (size_t)j * step + F.offset;
           valid |= 1u << i;
-          cur[i] = sweep_ld(at, wide);
+          cur[i] = report_ld(at, size);
           if (j != 0u || lead) {
-            prv[i] = sweep_ld(at - step, wide);
-            const bool nan = wide ? (prv[i] & 0x7fffffffffffffffull) > 0x7ff0000000000000ull
+            prv[i] = report_ld(at - step, size);
+            const bool nan = size == 8u ? (prv[i] & 0x7fffffffffffffffull) > 0x7ff0000000000000ull
                                   : ((uint32_t)prv[i] & 0x7fffffffu) > 0x7f800000u;
             if (!nan) has_prev |= 1u << i;  // behind a NaN the reference is 0
           }
@@ -225,12 +197,6 @@ __global__ __launch_bounds__(kSweepThreads) void k_sweep(const uint8_t* __restri
 }
 }  // namespace
 
-uint32_t sweep_stage_points(uint32_t point_step) {
-  if (point_step == 0u || point_step > kAuditStagedStep) return 0u;
-  const uint32_t fit = (kSweepLdsBytes - 32u) / point_step - 1u;  // one of them is the predecessor
-  return fit >= kAuditBlockPoints ? kAuditBlockPoints : (fit / kSweepThreads) * kSweepThreads;
-}
-
 int sweep_launch(const SweepLaunch& L) {
   hipError_t e;
   const size_t rep_bytes = (size_t)L.n_clouds * L.n_fields * L.n_candidates * 4u * sizeof(unsigned long long);
@@ -240,28 +206,15 @@ int sweep_launch(const SweepLaunch& L) {
   for (uint32_t f = 0; f < L.n_fields; ++f) any = any || L.fields[f].kind != SWEEP_NONE;
   if (L.n_blocks == 0 || !any) return 0;
   const bool args = L.dev_fields == nullptr;
-  SweepArgTable tab;
-  memset(&tab, 0, sizeof(tab));
-  if (args)
-    for (uint32_t f = 0; f < L.n_fields; ++f) tab.f[f] = L.fields[f];
-  const uint32_t sp = sweep_stage_points(L.point_step);
-  if (sp) {
-    // the predecessor, up to 15 bytes in front, the last unit's rest behind
-    const uint32_t lds = ((sp + 1u) * L.point_step + 32u + 15u) & ~15u;
-    if (args)
-      hipLaunchKernelGGL((k_sweep<true, true>), dim3(L.n_blocks), dim3(kSweepThreads), lds, L.stream, L.points, L.clouds, L.blocks,
-                         L.point_step, L.n_fields, L.n_candidates, sp, L.dev_fields, L.cands, L.report, tab);
-    else
-      hipLaunchKernelGGL((k_sweep<true, false>), dim3(L.n_blocks), dim3(kSweepThreads), lds, L.stream, L.points, L.clouds, L.blocks,
-                         L.point_step, L.n_fields, L.n_candidates, sp, L.dev_fields, L.cands, L.report, tab);
-  } else {
-    if (args)
-      hipLaunchKernelGGL((k_sweep<false, true>), dim3(L.n_blocks), dim3(kSweepThreads), 0, L.stream, L.points, L.clouds, L.blocks,
-                         L.point_step, L.n_fields, L.n_candidates, kAuditBlockPoints, L.dev_fields, L.cands, L.report, tab);
-    else
-      hipLaunchKernelGGL((k_sweep<false, false>), dim3(L.n_blocks), dim3(kSweepThreads), 0, L.stream, L.points, L.clouds, L.blocks,
-                         L.point_step, L.n_fields, L.n_candidates, kAuditBlockPoints, L.dev_fields, L.cands, L.report, tab);
-  }
+  const ReportArgTable<SweepField> tab = report_arg_table(L.fields, L.n_fields, args);
+  // the stage: its points and their predecessor, up to 15 bytes in front, the last unit's rest behind
+  const uint32_t sp = report_stage_points(L.point_step, kSweepLdsBytes - 32u, 1u, kReportBlockPoints, kSweepThreads);
+  const uint32_t lds = sp ? ((sp + 1u) * L.point_step + 32u + 15u) & ~15u : 0u;
+  report_dispatch(sp != 0u, args, [&](auto staged, auto in_args) {
+    hipLaunchKernelGGL((k_sweep<decltype(staged)::value, decltype(in_args)::value>), dim3(L.n_blocks), dim3(kSweepThreads), lds,
+                       L.stream, L.points, L.clouds, L.blocks, L.point_step, L.n_fields, L.n_candidates,
+                       sp ? sp : kReportBlockPoints, L.dev_fields, L.cands, L.report, tab);
+  });
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_sweep");
   return 0;
 }

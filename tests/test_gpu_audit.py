@@ -57,6 +57,7 @@ def _dev_report(n_clouds, n_fields):
     nbytes = n_clouds * n_fields * 40
     t = torch.full((256 + GUARD + nbytes + GUARD,), 0xEE, dtype=torch.uint8, device=dev)
     base = (-t.data_ptr()) % 256 + GUARD
+    torch.cuda.synchronize()  # the codec works on a stream of its own: the fill lands before a call writes the report
 
     def read():
         torch.cuda.synchronize()
@@ -239,6 +240,65 @@ def test_32_clouds_of_a_million_points_with_differences_at_block_and_cloud_bound
             hits = [k * n + int(want[k, f]["first_bad_point"]) for k in range(n_clouds) if want[k, f]["first_bad_point"] != M.NONE]
             hits = [h - lo for h in hits if lo <= h < hi]
             assert int(got[j, f]["first_bad_point"]) == (min(hits) if hits else M.NONE), (j, f)
+
+
+def _dev_cells(nbytes):
+    """A pre-filled device span of `nbytes` between guard spans; returns (read, pointer): read() checks the guards and returns
+    the bytes. It does not synchronise."""
+    import torch
+    t = torch.full((256 + GUARD + nbytes + GUARD,), 0xEE, dtype=torch.uint8, device=torch.device("cuda", 0))
+    base = (-t.data_ptr()) % 256 + GUARD
+
+    def read():
+        h = t.cpu().numpy()
+        assert (h[:base] == 0xEE).all() and (h[base + nbytes:] == 0xEE).all(), "a call wrote outside its report"
+        return h[base:base + nbytes].copy()
+    return read, t.data_ptr() + base
+
+
+@pytest.mark.parametrize("schema", ["step19_odd", "step200"])
+def test_audit_sweep_and_modes_interleaved_on_one_codec(schema):
+    """The three report calls share one table staging buffer, one device table and one event. Audit, sweep, mode sweep and
+    the first audit again on one codec, device inputs at address residue 7, device reports, nothing between the calls: the
+    tables grow, shrink and grow again (3 clouds / 4 blocks, 1 cloud / 1 block, 5 clouds / 8 units per field, then the first),
+    and the shapes cross a block edge (1024), the probe edge (4096) and a chunk edge (32768) by one point."""
+    import torch
+    import mode_model as MM
+    import sweep_model as SM
+    info, data = [(i, d) for nm, i, d in cases.stride_variants() if nm == schema][0]
+    step, nf, na = info.point_step, len(info.fields), len(MM.adaptive_fields(info))
+    assert na == 1
+    audit_sizes, sweep_sizes, mode_sizes = [0, 1025, 2049], [1], [1, 0, 4097, 32769, 63]
+    a = data[:sum(audit_sizes) * step].copy()
+    b = _perturbed(np.random.RandomState(12), info, a, 60)
+    pts = data[:sum(mode_sizes) * step].copy()
+    ladders = SM.default_ladders(info, (1.0, 0.5))
+    want_audit = M.audit(info, a, b, audit_sizes)
+    want_sweep = SM.sweep(info, pts[:step], sweep_sizes, ladders)
+    want_modes = MM.sweep(info, pts, mode_sizes)
+    _ta, pa, check_a = _dev(a, 7)
+    _tb, pb, check_b = _dev(b, 7)
+    _tp, pp, check_p = _dev(pts, 7)
+    read_a1, pr_a1 = _dev_cells(want_audit.nbytes)
+    read_s, pr_s = _dev_cells(want_sweep.nbytes)
+    read_m, pr_m = _dev_cells(want_modes.nbytes)
+    read_a2, pr_a2 = _dev_cells(want_audit.nbytes)
+    codec = _codec(info)
+    torch.cuda.synchronize()
+    assert codec.audit_clouds_device(pa, pb, audit_sizes, report_ptr=pr_a1) is None
+    assert codec.sweep_clouds_device(pp, sweep_sizes, ladders, report_ptr=pr_s) is None
+    assert codec.sweep_modes_device(pp, mode_sizes, report_ptr=pr_m) is None
+    assert codec.audit_clouds_device(pa, pb, audit_sizes, report_ptr=pr_a2) is None
+    torch.cuda.synchronize()
+    first = read_a1().view(M.DTYPE).reshape(want_audit.shape)
+    _same(first, want_audit, schema + " audit")
+    assert SM.same(read_s().view(SM.DTYPE).reshape(want_sweep.shape), want_sweep), schema + " sweep"
+    assert read_m().tobytes() == np.ascontiguousarray(want_modes).tobytes(), schema + " modes"
+    _same(read_a2().view(M.DTYPE).reshape(want_audit.shape), first, schema + " audit again")
+    assert want_audit["n_bitwise_diff"].sum() > 0
+    check_a()
+    check_b()
+    check_p()
 
 
 # ---- audit_streams -----------------------------------------------------------------------------------------------------

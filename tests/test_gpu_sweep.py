@@ -62,6 +62,7 @@ def _dev_report(n_clouds, n_fields, n_candidates):
     nbytes = n_clouds * n_fields * n_candidates * CELL
     t = torch.full((256 + GUARD + nbytes + GUARD,), 0xEE, dtype=torch.uint8, device=dev)
     base = (-t.data_ptr()) % 256 + GUARD
+    torch.cuda.synchronize()  # the codec works on a stream of its own: the fill lands before a call writes the report
 
     def read():
         torch.cuda.synchronize()
