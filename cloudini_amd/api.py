@@ -73,6 +73,11 @@ def lib() -> C.CDLL:
     L.cldn_amd_transcode_directory_audit.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32,
                                                      C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                                      C.c_uint32, C.POINTER(C.c_double), C.c_char_p, C.c_uint64]
+    L.cldn_amd_transcode_directory_estimate.restype = C.c_int64
+    L.cldn_amd_transcode_directory_estimate.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32,
+                                                        C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_char_p),
+                                                        C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32,
+                                                        C.POINTER(C.c_double), C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
     L.cldn_amd_transcode_directory_sweep.restype = C.c_int64
     L.cldn_amd_transcode_directory_sweep.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32,
                                                      C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32),
@@ -177,7 +182,7 @@ def _device_list(devices):
 
 def transcode_directory(in_dir: str, out_dir: str, resolution: float = 0.001, compression_opt: int = 2,
                         viz_lossy: bool = False, batch_messages: int = 64, devices=None, audit: bool = False,
-                        audit_limits=None, sweep=None, modes=None) -> dict:
+                        audit_limits=None, sweep=None, modes=None, estimate: bool = False) -> dict:
     """Batch transcoder (include/cloudini_amd/batch_transcoder.hpp): every CDR PointCloud2 file of in_dir ->
     CompressedPointCloud2 file of the same name in out_dir. `devices`: GPUs to spread the batches over (one GPU stage per
     entry; None = the current device). Returns the statistics. audit=True: every encode call is audited on the device
@@ -187,12 +192,17 @@ def transcode_directory(in_dir: str, out_dir: str, resolution: float = 0.001, co
     per name): the points of every encode call are swept on the device (cldn_hip_sweep_last_encode) and "sweep" holds, per
     field name and resolution, a dict (name, resolution, bytes, points, n_class_diff, n_over_limit, max_abs_err) -- what the
     field would cost in stage-1 bytes and lose at that resolution. The files are those of a run without it.
+    estimate=True (needs sweep): "estimate" holds {"own_bytes", "stage1_bytes", "actual_bytes", "fields": [name, resolution,
+    bytes]} -- per field name and resolution the order-0 entropy of the messages' streams if that field alone had that
+    resolution (cldn_hip_sweep_hist_last_encode, cldn_hip_stream_hist_last_encode): what ZSTD level 1 makes of them.
     modes="report": the adaptive integer modes of every encode call's points are swept on the device
     (cldn_hip_sweep_modes_last_encode) and "modes" holds {"reencoded_runs", "fields": [per integer field name: clouds, bytes
     under DeltaVarint / Palette / Rle / DeltaRle, clouds probed into and best in each mode, saved_bytes]}; the files are those
     of a run without it. modes="best": a schema run in which a cloud's best mode differs from the probed one is encoded again
     with the best modes forced -- those messages are NOT the reference encoder's bytes, but valid streams that every Cloudini
     decoder decodes to the same points. One of audit, sweep and modes per call."""
+    if estimate and not sweep:
+        raise ValueError("transcode_directory: estimate needs sweep")
     st = (C.c_double * 8)()
     dv, nd = _device_list(devices)
     keys = ("messages", "points", "input_bytes", "output_bytes", "gpu_batches", "seconds_total", "seconds_gpu", "seconds_stage2")
@@ -218,11 +228,19 @@ def transcode_directory(in_dir: str, out_dir: str, resolution: float = 0.001, co
         flat = [float(r) for v in sweep.values() for r in v]
         values = (C.c_float * max(1, len(flat)))(*flat)
         text = C.create_string_buffer(1 << 20)
-        _check(lib().cldn_amd_transcode_directory_sweep(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
-                                                        1 if viz_lossy else 0, batch_messages, dv, nd, names, sizes, values,
-                                                        len(sweep), st, text, len(text)))
+        if estimate:
+            text2 = C.create_string_buffer(1 << 20)
+            _check(lib().cldn_amd_transcode_directory_estimate(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
+                                                               1 if viz_lossy else 0, batch_messages, dv, nd, names, sizes, values,
+                                                               len(sweep), st, text, len(text), text2, len(text2)))
+        else:
+            _check(lib().cldn_amd_transcode_directory_sweep(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
+                                                            1 if viz_lossy else 0, batch_messages, dv, nd, names, sizes, values,
+                                                            len(sweep), st, text, len(text)))
         out = dict(zip(keys, [float(x) for x in st]))
         out["sweep"] = json.loads(text.value.decode())
+        if estimate:
+            out["estimate"] = json.loads(text2.value.decode())
         return out
     if not audit:
         _check(lib().cldn_amd_transcode_directory_on(in_dir.encode(), out_dir.encode(), resolution, compression_opt,
@@ -390,3 +408,26 @@ def encode_stage1_with_modes(info, clouds, modes):
     codec = native.Codec(native.Plan(info))
     codec.force_modes_per_cloud(modes)
     return codec.encode_host(clouds)[0]
+
+
+# ---- byte histograms for the stage-2 estimate (cldn_hip_sweep_hist_*, cldn_hip_stream_hist, cldn_hip_hist_entropy_bytes) --
+
+def sweep_hist(info, clouds, resolutions):
+    """Per cloud, field and candidate resolution (resolutions: (n_fields, n_candidates), 0 = skip): the 256-bin histogram of the
+    bytes of the field's tokens at that resolution; uint64, shape (n_clouds, n_fields, n_candidates, 256). Zero for fields
+    without a lossy float encoder."""
+    from . import native
+    return native.Codec(native.Plan(info)).sweep_hist_clouds_host(clouds, resolutions)
+
+
+def stream_hist(info, streams):
+    """The 256-bin histogram of the bytes of each stream (uint64, shape (n_streams, 256)), counted on the device."""
+    from . import native
+    return native.Codec(native.Plan(info)).stream_hist_host(streams)
+
+
+def hist_entropy_bytes(hist) -> float:
+    """Order-0 entropy, in bytes, of the bytes a 256-bin histogram counts: what ZSTD level 1 makes of them while literals
+    dominate. With stream_hist - sweep_hist[f][own] + sweep_hist[f][candidate]: the estimate for field f at the candidate."""
+    from . import native
+    return native.hist_entropy_bytes(hist)

@@ -221,6 +221,7 @@ struct cldn_hip_codec {
   DevBuf d_viz_keys, d_viz_slot, d_viz_blocks, d_viz_bits, d_viz_tables, d_viz_kept, d_viz_out;
   PinnedBuf h_viz;                // upload of the cloud / block tables, readback of the counts
   uint64_t viz_group_slots = 0;   // cldn_hip_debug_viz_group_slots: 0 = kVizGroupSlots
+  uint32_t hist_walk = 0;         // cldn_hip_debug_hist_walk: 0 = kHistWalkBlocks
   DevBuf d_pre[kMaxGorilla];
   // WIDE route: the plan's arrays in device memory (uploaded by cldn_hip_codec_create), per-chunk scratch of the encoder,
   // per-op state of the serial decoder, Gorilla token buffers
@@ -2457,13 +2458,15 @@ static int sweep_tables(const cldn_hip_plan& P, const float* resolutions, uint32
   return CLDN_HIP_OK;
 }
 
-// device points -> report: tables up, one clear, one kernel; HOST report: one copy, one synchronisation
+// device points -> report: tables up, one clear, one kernel; HOST report: one copy, one synchronisation.
+// hist: the report holds cldn_hip_hist_t (k_sweep_hist), else cldn_hip_sweep_cell_t (k_sweep)
 static int sweep_device(cldn_hip_codec* c, const uint8_t* d_points, const uint64_t* cloud_points, uint32_t n_clouds,
                         const std::vector<SweepField>& fields, const std::vector<SweepCand>& cands, uint32_t n_candidates,
-                        cldn_hip_sweep_cell_t* report, int report_loc) {
+                        void* report, int report_loc, bool hist) {
   static_assert(sizeof(cldn_hip_sweep_cell_t) == 32, "four 64-bit words");
+  static_assert(sizeof(cldn_hip_hist_t) == 2048, "256 64-bit words");
   const uint32_t n_fields = (uint32_t)fields.size();
-  const size_t rep_bytes = (size_t)n_clouds * n_fields * n_candidates * sizeof(cldn_hip_sweep_cell_t);
+  const size_t rep_bytes = (size_t)n_clouds * n_fields * n_candidates * (hist ? sizeof(cldn_hip_hist_t) : sizeof(cldn_hip_sweep_cell_t));
   if (rep_bytes == 0) return CLDN_HIP_OK;
   int rc;
   SweepLaunch L;
@@ -2484,14 +2487,13 @@ static int sweep_device(cldn_hip_codec* c, const uint8_t* d_points, const uint64
   L.cands = (const SweepCand*)sec[2].dev;
   L.clouds = (const ReportCloud*)sec[0].dev;
   L.blocks = (const ReportBlock*)sec[1].dev;
-  if ((rc = sweep_launch(L)) != CLDN_HIP_OK) return rc;
+  if ((rc = hist ? sweep_hist_launch(L, c->hist_walk) : sweep_launch(L)) != CLDN_HIP_OK) return rc;
   return report_fetch(c, report, report_loc, L.report, rep_bytes);
 }
 
-extern "C" {
-
-int cldn_hip_sweep_clouds(cldn_hip_codec_t* c, const void* points, int points_loc, const uint64_t* cloud_points, uint32_t n_clouds,
-                          const float* resolutions, uint32_t n_candidates, cldn_hip_sweep_cell_t* report, int report_loc) {
+// cldn_hip_sweep_clouds / cldn_hip_sweep_hist_clouds
+static int sweep_clouds_impl(cldn_hip_codec_t* c, const void* points, int points_loc, const uint64_t* cloud_points, uint32_t n_clouds,
+                             const float* resolutions, uint32_t n_candidates, void* report, int report_loc, bool hist) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   c->enc.drop();
   if (points_loc != CLDN_HIP_HOST && points_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
@@ -2507,19 +2509,14 @@ int cldn_hip_sweep_clouds(cldn_hip_codec_t* c, const void* points, int points_lo
   const uint64_t bytes = n_points * c->plan.point_step;
   const uint8_t* d_points;
   if ((rc = stage_host_points(c, points, points_loc, bytes, 0u, (size_t)bytes, &d_points)) != CLDN_HIP_OK) return rc;
-  rc = sweep_device(c, d_points, cloud_points, n_clouds, fields, cands, n_candidates, report, report_loc);
+  rc = sweep_device(c, d_points, cloud_points, n_clouds, fields, cands, n_candidates, report, report_loc, hist);
   if (rc == CLDN_HIP_OK && points_loc == CLDN_HIP_HOST && bytes && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
   return rc;
 }
 
-int64_t cldn_hip_sweep_last_encode_clouds(const cldn_hip_codec_t* c) {
-  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
-  if (!c->enc.valid && !c->enc.await_frame) return no_last_encode("sweep_last_encode");  // (the points are there before the framing)
-  return (int64_t)c->enc.cloud_points.size();
-}
-
-int cldn_hip_sweep_last_encode(cldn_hip_codec_t* c, const float* resolutions, uint32_t n_candidates, cldn_hip_sweep_cell_t* report,
-                               int report_loc) {
+// cldn_hip_sweep_last_encode / cldn_hip_sweep_hist_last_encode
+static int sweep_last_encode_impl(cldn_hip_codec_t* c, const float* resolutions, uint32_t n_candidates, void* report, int report_loc,
+                                  bool hist) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   if (cldn_hip_sweep_last_encode_clouds(c) < 0) return CLDN_HIP_ERR_ARG;
   const cldn_hip_codec::LastEncode& E = c->enc;  // read only: the state stays as it is
@@ -2530,7 +2527,137 @@ int cldn_hip_sweep_last_encode(cldn_hip_codec_t* c, const float* resolutions, ui
   std::vector<SweepCand> cands;
   if ((rc = sweep_tables(c->plan, resolutions, n_candidates, &fields, &cands)) != CLDN_HIP_OK) return rc;
   ENTER_DEVICE(c->device);
-  return sweep_device(c, E.points, E.cloud_points.data(), n_clouds, fields, cands, n_candidates, report, report_loc);
+  return sweep_device(c, E.points, E.cloud_points.data(), n_clouds, fields, cands, n_candidates, report, report_loc, hist);
+}
+
+extern "C" {
+
+int cldn_hip_sweep_clouds(cldn_hip_codec_t* c, const void* points, int points_loc, const uint64_t* cloud_points, uint32_t n_clouds,
+                          const float* resolutions, uint32_t n_candidates, cldn_hip_sweep_cell_t* report, int report_loc) {
+  return sweep_clouds_impl(c, points, points_loc, cloud_points, n_clouds, resolutions, n_candidates, report, report_loc, false);
+}
+
+int64_t cldn_hip_sweep_last_encode_clouds(const cldn_hip_codec_t* c) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (!c->enc.valid && !c->enc.await_frame) return no_last_encode("sweep_last_encode");  // (the points are there before the framing)
+  return (int64_t)c->enc.cloud_points.size();
+}
+
+int cldn_hip_sweep_last_encode(cldn_hip_codec_t* c, const float* resolutions, uint32_t n_candidates, cldn_hip_sweep_cell_t* report,
+                               int report_loc) {
+  return sweep_last_encode_impl(c, resolutions, n_candidates, report, report_loc, false);
+}
+
+int cldn_hip_sweep_hist_clouds(cldn_hip_codec_t* c, const void* points, int points_loc, const uint64_t* cloud_points, uint32_t n_clouds,
+                               const float* resolutions, uint32_t n_candidates, cldn_hip_hist_t* report, int report_loc) {
+  return sweep_clouds_impl(c, points, points_loc, cloud_points, n_clouds, resolutions, n_candidates, report, report_loc, true);
+}
+
+int cldn_hip_sweep_hist_last_encode(cldn_hip_codec_t* c, const float* resolutions, uint32_t n_candidates, cldn_hip_hist_t* report,
+                                    int report_loc) {
+  return sweep_last_encode_impl(c, resolutions, n_candidates, report, report_loc, true);
+}
+
+// Test and measurement hook, not part of the header: block-table entries a workgroup of k_sweep_hist walks (0 = kHistWalkBlocks).
+// Reports never depend on it.
+__attribute__((visibility("default"))) int cldn_hip_debug_hist_walk(cldn_hip_codec_t* c, uint32_t blocks) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->hist_walk = blocks;
+  return CLDN_HIP_OK;
+}
+
+}  // extern "C"
+
+// ---- histogram of the bytes of each cloud's stream (hist_kernels.hip) ----
+
+// device streams -> report: the item table up, one clear, one kernel; HOST report: one copy, one synchronisation.
+// offsets: HOST [n_clouds + 1], ascending, in bytes of d_streams
+static int stream_hist_device(cldn_hip_codec* c, const uint8_t* d_streams, const uint64_t* offsets, uint32_t n_clouds,
+                              cldn_hip_hist_t* report, int report_loc) {
+  const size_t rep_bytes = (size_t)n_clouds * sizeof(cldn_hip_hist_t);
+  if (rep_bytes == 0) return CLDN_HIP_OK;
+  std::vector<StreamHistItem> items;
+  for (uint32_t k = 0; k < n_clouds; ++k)
+    for (uint64_t at = offsets[k]; at < offsets[k + 1]; at += kStreamHistItemBytes)
+      items.push_back(StreamHistItem{at, std::min<uint64_t>(at + kStreamHistItemBytes, offsets[k + 1]), k, 0u});
+  if (items.size() > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "stream_hist: more than 2^31 pieces of 128 KiB");
+  int rc;
+  StreamHistLaunch L;
+  const ReportBatch B = {nullptr, n_clouds, 0u};
+  TableSection sec[1] = {TableSection{items.size() * sizeof(StreamHistItem), items.data(), nullptr, nullptr}};
+  if (!items.empty() && (rc = upload_tables(c, B, sec, 1)) != CLDN_HIP_OK) return rc;
+  if ((rc = report_place(c, report, report_loc, rep_bytes, &L.report)) != CLDN_HIP_OK) return rc;
+  L.stream = c->stream;
+  L.streams = d_streams;
+  L.n_clouds = n_clouds;
+  L.n_items = (uint32_t)items.size();
+  L.items = (const StreamHistItem*)sec[0].dev;
+  if ((rc = stream_hist_launch(L)) != CLDN_HIP_OK) return rc;
+  return report_fetch(c, report, report_loc, L.report, rep_bytes);
+}
+
+extern "C" {
+
+int cldn_hip_stream_hist(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets, uint32_t n_clouds,
+                         cldn_hip_hist_t* report, int report_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
+  if (streams_loc != CLDN_HIP_HOST && streams_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  int rc;
+  if ((rc = report_check("stream_hist", true, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  if (n_clouds == 0) return CLDN_HIP_OK;
+  if (!stream_offsets) return fail(CLDN_HIP_ERR_ARG, "stream_hist: stream_offsets is NULL");
+  for (uint32_t k = 0; k < n_clouds; ++k)
+    if (stream_offsets[k + 1] < stream_offsets[k]) return fail(CLDN_HIP_ERR_ARG, "stream_offsets must be ascending");
+  const uint64_t s0 = stream_offsets[0], s_bytes = stream_offsets[n_clouds] - s0;
+  if (s_bytes && !streams) return fail(CLDN_HIP_ERR_ARG, "stream_hist: streams is NULL");
+  ENTER_DEVICE(c->device);
+  std::vector<uint64_t> rel(stream_offsets, stream_offsets + n_clouds + 1);
+  for (uint64_t& o : rel) o -= s0;
+  const uint8_t* d_streams;
+  if ((rc = stage_host_points(c, (const uint8_t*)streams + s0, streams_loc, s_bytes, 0u, (size_t)s_bytes, &d_streams)) != CLDN_HIP_OK)
+    return rc;
+  rc = stream_hist_device(c, d_streams, rel.data(), n_clouds, report, report_loc);
+  if (rc == CLDN_HIP_OK && streams_loc == CLDN_HIP_HOST && s_bytes && report_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
+  return rc;
+}
+
+int cldn_hip_stream_hist_last_encode(cldn_hip_codec_t* c, cldn_hip_hist_t* report, int report_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (!c->enc.valid) return no_last_encode("stream_hist_last_encode");  // (a chunk table has no streams before its framing)
+  cldn_hip_codec::LastEncode& E = c->enc;
+  const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
+  int rc;
+  if ((rc = report_check("stream_hist", true, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+  if (n_clouds == 0) return CLDN_HIP_OK;
+  ENTER_DEVICE(c->device);
+  uint64_t n_points = 0;
+  for (uint64_t n : E.cloud_points) n_points += n;
+  if (n_points == 0) {  // nothing was launched and nothing written: empty streams
+    const std::vector<uint64_t> none((size_t)n_clouds + 1, 0);
+    return stream_hist_device(c, nullptr, none.data(), n_clouds, report, report_loc);
+  }
+  if (E.offsets.empty()) {  // DEVICE outputs: the encode call has not read its offsets. Kept: the state describes the same call
+    std::vector<uint64_t> offs((size_t)n_clouds + 1);
+    HIP_TRY(hipMemcpyAsync(offs.data(), E.d_offsets, offs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < n_clouds; ++k)
+      if (offs[k + 1] < offs[k]) return fail(CLDN_HIP_ERR_DEVICE, "stream_hist_last_encode: the encode call left no valid stream offsets (see cldn_hip_codec_status)");
+    E.offsets = offs;
+  }
+  return stream_hist_device(c, E.streams, E.offsets.data(), n_clouds, report, report_loc);
+}
+
+double cldn_hip_hist_entropy_bytes(const cldn_hip_hist_t* h) {
+  if (!h) return 0.0;
+  uint64_t n = 0;
+  for (uint64_t v : h->bin) n += v;
+  if (n == 0) return 0.0;
+  double bits = 0.0;
+  for (uint64_t v : h->bin)
+    if (v) bits += (double)v * std::log2((double)n / (double)v);
+  const double bytes = bits / 8.0;
+  return bytes < (double)n ? bytes : (double)n;
 }
 
 }  // extern "C"

@@ -246,6 +246,7 @@ struct Run {                       // messages [first, first + count) share a sc
   PinnedBytes stage1;              // framed stage-1 streams of the run, page-locked (the GPU copies into it)
   std::vector<uint64_t> offsets;   // count + 1
   std::vector<uint32_t> chunk_sizes;
+  bool estimated = false;          // TranscodeOptions::estimate took this run's histograms: stage 2 reports its actual size
   PinnedBytes decoded;             // decode direction: the points of the run's clouds, back to back
   std::vector<uint64_t> out_at;    // decode direction: where every message's points start in `decoded`
 };
@@ -305,6 +306,7 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     while (r1 < n && b.parsed[r1].key == b.parsed[r0].key) ++r1;
     if (b.runs.size() <= n_runs) b.runs.emplace_back();  // recycled batches keep their page-locked staging
     Run& run = b.runs[n_runs++];
+    run.estimated = false;
     run.first = r0;
     run.count = static_cast<uint32_t>(r1 - r0);
     const Cloudini::EncodingInfo& info0 = b.parsed[r0].info;
@@ -337,7 +339,7 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     // the ladders of this run's schema: one row per field, padded with 0 (skip) to the longest ladder
     Cloudini::amd_detail::SweepRequest sweep;
     std::vector<const std::vector<float>*> sweep_ladder(info0.fields.size(), nullptr);
-    std::vector<float> sweep_res;
+    std::vector<float> sweep_res, own_res;
     if (!opt.sweep.empty() && info0.encoding_opt == Cloudini::EncodingOptions::LOSSY) {
       for (size_t f = 0; f < info0.fields.size(); ++f) {
         const Cloudini::PointField& fd = info0.fields[f];
@@ -352,6 +354,13 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       for (size_t f = 0; f < info0.fields.size(); ++f)
         if (sweep_ladder[f]) std::copy(sweep_ladder[f]->begin(), sweep_ladder[f]->end(), sweep_res.begin() + f * sweep.n_candidates);
       sweep.resolutions = sweep_res.data();
+      if (opt.estimate && sweep.n_candidates) {
+        own_res.assign(info0.fields.size(), 0.0f);
+        for (size_t f = 0; f < info0.fields.size(); ++f)
+          if (sweep_ladder[f]) own_res[f] = *info0.fields[f].resolution;
+        sweep.estimate = run.estimated = true;
+        sweep.own_resolutions = own_res.data();
+      }
     }
     Cloudini::amd_detail::SweepRequest* const sweep_p = sweep.n_candidates ? &sweep : nullptr;
     Cloudini::amd_detail::ModesRequest modes;
@@ -420,6 +429,31 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       }
       stats->mergeSweep(part);
     }
+    if (sweep_p && sweep.estimate && stats) {  // per name and rung: the entropy of stream - own + candidate, summed over the clouds
+      const size_t nf = info0.fields.size(), nc = sweep.n_candidates;
+      const auto moved = [&](uint32_t k, const cldn_hip_hist_t* own, const cldn_hip_hist_t* cand) {
+        cldn_hip_hist_t h = sweep.stream_hist[k];
+        for (int i = 0; own && i < 256; ++i) h.bin[i] = h.bin[i] + cand->bin[i] > own->bin[i] ? h.bin[i] + cand->bin[i] - own->bin[i] : 0u;
+        return cldn_hip_hist_entropy_bytes(&h);
+      };
+      std::vector<EstimateSummary> part;
+      for (size_t f = 0; f < nf; ++f) {
+        if (!sweep_ladder[f]) continue;
+        const std::vector<float>& ladder = *sweep_ladder[f];
+        for (size_t c = 0; c < ladder.size(); ++c) {
+          if (std::find(ladder.begin(), ladder.begin() + c, ladder[c]) != ladder.begin() + c) continue;
+          EstimateSummary one;
+          one.name = info0.fields[f].name;
+          one.resolution = ladder[c];
+          for (uint32_t k = 0; k < run.count; ++k)
+            one.bytes += moved(k, &sweep.own_hist[(size_t)k * nf + f], &sweep.hist[((size_t)k * nf + f) * nc + c]);
+          part.push_back(one);
+        }
+      }
+      stats->mergeEstimate(part);
+      for (uint32_t k = 0; k < run.count; ++k) stats->estimate_own_bytes += moved(k, nullptr, nullptr);
+      stats->estimate_stage1_bytes += run.offsets[run.count] - run.offsets[0];
+    }
     if (opt.audit && stats) {  // the run's report, message by message, into the per-name summary
       const size_t nf = info0.fields.size();
       std::vector<AuditFieldSummary> part(nf);
@@ -463,6 +497,7 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     uint32_t src_size;
     size_t slot;         // offset of the job's worst-case slot inside the message's scratch area
     uint32_t packed = 0;
+    bool estimated = false;  // the run's histograms were taken and the output is ZSTD: its size goes next to the estimate
   };
   const size_t n = b.in.size();
   std::vector<Job> jobs;
@@ -492,6 +527,7 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
         j.src = s + 4;
         j.src_size = size;
         j.slot = slot;
+        j.estimated = run.estimated && opt.compression == Cloudini::CompressionOption::ZSTD;
         jobs.push_back(j);
         slot += 4 + Cloudini::amd_detail::compressedChunkBound(opt.compression, size);
         s += 4 + size;
@@ -524,6 +560,7 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       end = scratch_at[i];
       for (size_t ji = first_job[i]; ji < first_job[i + 1]; ++ji) {
         const Job& j = jobs[ji];
+        if (stats && j.estimated) stats->estimate_actual_bytes += 4u + j.packed;
         uint8_t* from = msg.data() + scratch_at[i] + j.slot;
         if (from != msg.data() + end) std::memmove(msg.data() + end, from, 4u + j.packed);
         end += 4u + j.packed;
@@ -605,6 +642,7 @@ void decodeGpuPhase(Batch& b, TranscodeStats* stats) {
     }
     if (b.runs.size() <= n_runs) b.runs.emplace_back();
     Run& run = b.runs[n_runs++];
+    run.estimated = false;
     run.first = r0;
     run.count = static_cast<uint32_t>(r1 - r0);
     const auto t_gpu = Clock::now();
@@ -711,6 +749,16 @@ void TranscodeStats::mergeAudit(const std::vector<AuditFieldSummary>& other) {
   }
 }
 
+void TranscodeStats::mergeEstimate(const std::vector<EstimateSummary>& other) {
+  for (const EstimateSummary& o : other) {
+    EstimateSummary* mine = nullptr;
+    for (EstimateSummary& s : estimate)
+      if (s.name == o.name && s.resolution == o.resolution) mine = &s;
+    if (mine) mine->bytes += o.bytes;
+    else estimate.push_back(o);
+  }
+}
+
 void TranscodeStats::mergeSweep(const std::vector<SweepCellSummary>& other) {
   for (const SweepCellSummary& o : other) {
     SweepCellSummary* mine = nullptr;
@@ -785,6 +833,7 @@ float resolutionValue(const std::string& value, bool zero_allowed, const char* w
 
 void checkOptions(const TranscodeOptions& opt) {
   if (opt.decode && !opt.sweep.empty()) throw std::invalid_argument("TranscodeOptions: sweep is not available together with decode");
+  if (opt.estimate && opt.sweep.empty()) throw std::invalid_argument("TranscodeOptions: estimate needs sweep");
   if (opt.decode && opt.modes != TranscodeOptions::Modes::Off)
     throw std::invalid_argument("TranscodeOptions: modes is not available together with decode");
   for (const auto& named : opt.sweep)
@@ -998,6 +1047,9 @@ TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, co
         stats.seconds_gpu += mine.seconds_gpu;
         stats.mergeAudit(mine.audit);
         stats.mergeSweep(mine.sweep);
+        stats.mergeEstimate(mine.estimate);
+        stats.estimate_own_bytes += mine.estimate_own_bytes;
+        stats.estimate_stage1_bytes += mine.estimate_stage1_bytes;
         stats.mergeModes(mine.modes);
         stats.mode_reencoded_runs += mine.mode_reencoded_runs;
       }
@@ -1074,6 +1126,7 @@ TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, co
   if (reader_error) std::rethrow_exception(reader_error);
   if (writer_error) std::rethrow_exception(writer_error);
   stats.output_bytes = stats2.output_bytes;
+  stats.estimate_actual_bytes = stats2.estimate_actual_bytes;
   stats.seconds_stage2 = stats2.seconds_stage2;
   stats.seconds_total = since(t0);
   stats.gpu_workers = n_workers;

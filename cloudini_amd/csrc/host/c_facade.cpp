@@ -187,11 +187,31 @@ static std::string sweepJson(const cloudini_amd::TranscodeStats& st) {
   return out + "]";
 }
 
-CLDN_EXPORT int64_t cldn_amd_transcode_directory_sweep(const char* in_dir, const char* out_dir, float resolution,
-                                                       uint8_t compression_opt, int viz_lossy, uint32_t batch_messages,
-                                                       const int32_t* devices, uint32_t n_devices, const char* const* sweep_names,
-                                                       const uint32_t* ladder_sizes, const float* ladders, uint32_t n_names,
-                                                       double* stats_out, char* sweep_json, uint64_t sweep_capacity) {
+// the estimate as one line of JSON: {"own_bytes", "stage1_bytes", "actual_bytes", "fields": [{"name", "resolution", "bytes"}]}
+static std::string estimateJson(const cloudini_amd::TranscodeStats& st) {
+  char num[320];
+  std::snprintf(num, sizeof num, "{\"own_bytes\": %.17g, \"stage1_bytes\": %llu, \"actual_bytes\": %llu, \"fields\": [", st.estimate_own_bytes,
+                (unsigned long long)st.estimate_stage1_bytes, (unsigned long long)st.estimate_actual_bytes);
+  std::string out = num;
+  for (size_t i = 0; i < st.estimate.size(); ++i) {
+    const cloudini_amd::EstimateSummary& e = st.estimate[i];
+    std::string name = "\"";
+    for (char ch : e.name) {
+      if (ch == '"' || ch == '\\') name += '\\';
+      name += (unsigned char)ch < 0x20 ? ' ' : ch;
+    }
+    std::snprintf(num, sizeof num, "\"resolution\": %.9g, \"bytes\": %.17g", (double)e.resolution, e.bytes);
+    out += std::string(i ? ", " : "") + "{\"name\": " + name + "\", " + num + "}";
+  }
+  return out + "]}";
+}
+
+// cldn_amd_transcode_directory_sweep, and _estimate (estimate_json != NULL: TranscodeOptions::estimate on top)
+static int64_t transcodeDirectorySweep(const char* in_dir, const char* out_dir, float resolution, uint8_t compression_opt, int viz_lossy,
+                                       uint32_t batch_messages, const int32_t* devices, uint32_t n_devices,
+                                       const char* const* sweep_names, const uint32_t* ladder_sizes, const float* ladders,
+                                       uint32_t n_names, double* stats_out, char* sweep_json, uint64_t sweep_capacity,
+                                       char* estimate_json, uint64_t estimate_capacity) {
   return guarded([&] {
     cloudini_amd::DirectorySource source(in_dir);
     cloudini_amd::DirectorySink sink(out_dir);
@@ -199,6 +219,7 @@ CLDN_EXPORT int64_t cldn_amd_transcode_directory_sweep(const char* in_dir, const
     opt.default_resolution = resolution;
     opt.compression = static_cast<Cloudini::CompressionOption>(compression_opt);
     opt.viz_lossy = viz_lossy != 0;
+    opt.estimate = estimate_json != nullptr;
     if (batch_messages) opt.batch_messages = batch_messages;
     if (devices) opt.devices.assign(devices, devices + n_devices);
     for (uint32_t i = 0; i < n_names; ++i) {
@@ -214,8 +235,33 @@ CLDN_EXPORT int64_t cldn_amd_transcode_directory_sweep(const char* in_dir, const
     const std::string json = sweepJson(st);
     if (json.size() + 1 > sweep_capacity) throw std::runtime_error("transcode_directory_sweep: the summary needs " + std::to_string(json.size() + 1) + " bytes");
     std::memcpy(sweep_json, json.c_str(), json.size() + 1);
+    if (estimate_json) {
+      const std::string est = estimateJson(st);
+      if (est.size() + 1 > estimate_capacity) throw std::runtime_error("transcode_directory_estimate: the summary needs " + std::to_string(est.size() + 1) + " bytes");
+      std::memcpy(estimate_json, est.c_str(), est.size() + 1);
+    }
     return (int64_t)st.messages;
   });
+}
+
+CLDN_EXPORT int64_t cldn_amd_transcode_directory_sweep(const char* in_dir, const char* out_dir, float resolution,
+                                                       uint8_t compression_opt, int viz_lossy, uint32_t batch_messages,
+                                                       const int32_t* devices, uint32_t n_devices, const char* const* sweep_names,
+                                                       const uint32_t* ladder_sizes, const float* ladders, uint32_t n_names,
+                                                       double* stats_out, char* sweep_json, uint64_t sweep_capacity) {
+  return transcodeDirectorySweep(in_dir, out_dir, resolution, compression_opt, viz_lossy, batch_messages, devices, n_devices, sweep_names,
+                                 ladder_sizes, ladders, n_names, stats_out, sweep_json, sweep_capacity, nullptr, 0);
+}
+
+CLDN_EXPORT int64_t cldn_amd_transcode_directory_estimate(const char* in_dir, const char* out_dir, float resolution,
+                                                          uint8_t compression_opt, int viz_lossy, uint32_t batch_messages,
+                                                          const int32_t* devices, uint32_t n_devices, const char* const* sweep_names,
+                                                          const uint32_t* ladder_sizes, const float* ladders, uint32_t n_names,
+                                                          double* stats_out, char* sweep_json, uint64_t sweep_capacity,
+                                                          char* estimate_json, uint64_t estimate_capacity) {
+  if (!estimate_json) return guarded([&]() -> int64_t { throw std::invalid_argument("transcode_directory_estimate: estimate_json is NULL"); });
+  return transcodeDirectorySweep(in_dir, out_dir, resolution, compression_opt, viz_lossy, batch_messages, devices, n_devices, sweep_names,
+                                 ladder_sizes, ladders, n_names, stats_out, sweep_json, sweep_capacity, estimate_json, estimate_capacity);
 }
 
 // the mode summary as one line of JSON: {"reencoded_runs": n, "fields": [one object per integer field name]}

@@ -1043,7 +1043,16 @@ static int auditLastEncode(cldn_hip_codec_t* codec, const EncodingInfo& info, ui
 static int sweepLastEncode(cldn_hip_codec_t* codec, const EncodingInfo& info, uint32_t n_clouds, SweepRequest* sweep) {
   sweep->report.assign((size_t)n_clouds * info.fields.size() * sweep->n_candidates, cldn_hip_sweep_cell_t{});
   if (sweep->report.empty()) return CLDN_HIP_OK;
-  return cldn_hip_sweep_last_encode(codec, sweep->resolutions, sweep->n_candidates, sweep->report.data(), CLDN_HIP_HOST);
+  int rc = cldn_hip_sweep_last_encode(codec, sweep->resolutions, sweep->n_candidates, sweep->report.data(), CLDN_HIP_HOST);
+  if (rc != CLDN_HIP_OK || !sweep->estimate) return rc;
+  const size_t cells = (size_t)n_clouds * info.fields.size();
+  sweep->hist.assign(cells * sweep->n_candidates, cldn_hip_hist_t{});
+  sweep->own_hist.assign(cells, cldn_hip_hist_t{});
+  sweep->stream_hist.assign(n_clouds, cldn_hip_hist_t{});
+  if ((rc = cldn_hip_sweep_hist_last_encode(codec, sweep->resolutions, sweep->n_candidates, sweep->hist.data(), CLDN_HIP_HOST)) != CLDN_HIP_OK)
+    return rc;
+  if ((rc = cldn_hip_sweep_hist_last_encode(codec, sweep->own_resolutions, 1, sweep->own_hist.data(), CLDN_HIP_HOST)) != CLDN_HIP_OK) return rc;
+  return cldn_hip_stream_hist_last_encode(codec, sweep->stream_hist.data(), CLDN_HIP_HOST);
 }
 
 // The adaptive integer modes of that encode call's points; with apply_best and a cloud whose best mode is not the probed one,

@@ -37,10 +37,16 @@ struct AuditRequest {
 // `sweep` (optional): behind the encode call (and behind the audit, if both are asked for) the codec sweeps the points it
 // encoded (cldn_hip_sweep_last_encode; behind the viz filter: the survivors); resolutions = info.fields.size() * n_candidates
 // float32, one ladder per field (0 = skip), report receives n_clouds * info.fields.size() * n_candidates cells.
+// `estimate`: behind the sweep, the byte histograms for the stage-2 estimate (cldn_hip_sweep_hist_last_encode with the same
+// ladders, again with the one-rung ladder own_resolutions -- info.fields.size() float32, 0 = skip --, and
+// cldn_hip_stream_hist_last_encode): hist as report, own_hist one per cloud and field, stream_hist one per cloud.
 struct SweepRequest {
   const float* resolutions = nullptr;
   uint32_t n_candidates = 0;
   std::vector<cldn_hip_sweep_cell_t> report;
+  bool estimate = false;
+  const float* own_resolutions = nullptr;
+  std::vector<cldn_hip_hist_t> hist, own_hist, stream_hist;
 };
 // `modes` (optional): right behind the encode call the codec sweeps the adaptive integer modes of the points it encoded
 // (cldn_hip_sweep_modes_last_encode; behind the viz filter: the survivors): report receives n_clouds * adaptive_fields cells.

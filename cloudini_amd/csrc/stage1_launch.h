@@ -351,6 +351,27 @@ struct SweepLaunch {
 };
 int sweep_launch(const SweepLaunch& L);            // one clear + one kernel
 
+// ---- byte histograms for the stage-2 estimate (hist_kernels.hip; record: cldn_hip_hist_t, 256 64-bit words) ----
+// k_sweep_hist takes a SweepLaunch whose report holds [n_clouds * n_fields * n_candidates * 256] words. A workgroup walks
+// `walk` consecutive entries of the block table and flushes once per (cloud, field, candidate); 0 = kHistWalkBlocks.
+constexpr uint32_t kHistWalkBlocks = 4;           // measured: DESIGN.md 4f (1 .. 32 tried; 2 .. 8 within 4 %, 4 the best of both sets)
+constexpr uint32_t kStreamHistItemBytes = 131072; // bytes of a stream per workgroup of k_stream_hist (32 KiB: clearing and summing the 32 copies was a third of the LDS work)
+struct StreamHistItem {
+  uint64_t begin, end;           // bytes of `streams`
+  uint32_t cloud;
+  uint32_t pad;
+};
+struct StreamHistLaunch {
+  hipStream_t stream;
+  const uint8_t* streams;        // device, any alignment
+  uint32_t n_clouds;
+  uint32_t n_items;
+  const StreamHistItem* items;   // device [n_items]: no item is empty
+  unsigned long long* report;    // device [n_clouds * 256], 8-byte aligned: cleared, then filled
+};
+int sweep_hist_launch(const SweepLaunch& L, uint32_t walk);  // one clear + one kernel
+int stream_hist_launch(const StreamHistLaunch& L);           // one clear + one kernel
+
 // ---- sweep of the V5 adaptive integer modes (mode_kernels.hip; record: cldn_hip_mode_cell_t, five 64-bit words) ----
 constexpr uint32_t kModeProbeUnit = 0xffffffffu;  // ModeUnit::chunk of the unit that probes a cloud's first kProbePoints values
 struct ModeField {

@@ -165,6 +165,18 @@ def lib() -> C.CDLL:
     L.cldn_hip_sweep_last_encode.argtypes = [vp, vp, C.c_uint32, vp, C.c_int]
     L.cldn_hip_sweep_last_encode_clouds.restype = C.c_int64
     L.cldn_hip_sweep_last_encode_clouds.argtypes = [vp]
+    L.cldn_hip_sweep_hist_clouds.restype = C.c_int
+    L.cldn_hip_sweep_hist_clouds.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_uint32, vp, C.c_int]
+    L.cldn_hip_sweep_hist_last_encode.restype = C.c_int
+    L.cldn_hip_sweep_hist_last_encode.argtypes = [vp, vp, C.c_uint32, vp, C.c_int]
+    L.cldn_hip_stream_hist.restype = C.c_int
+    L.cldn_hip_stream_hist.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int]
+    L.cldn_hip_stream_hist_last_encode.restype = C.c_int
+    L.cldn_hip_stream_hist_last_encode.argtypes = [vp, vp, C.c_int]
+    L.cldn_hip_hist_entropy_bytes.restype = C.c_double
+    L.cldn_hip_hist_entropy_bytes.argtypes = [vp]
+    L.cldn_hip_debug_hist_walk.restype = C.c_int
+    L.cldn_hip_debug_hist_walk.argtypes = [vp, C.c_uint32]
     L.cldn_hip_sweep_modes_clouds.restype = C.c_int
     L.cldn_hip_sweep_modes_clouds.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int]
     L.cldn_hip_sweep_modes_last_encode.restype = C.c_int
@@ -219,6 +231,14 @@ SWEEP_MAX_CANDIDATES = 16
 
 # cldn_hip_mode_cell_t: one cell per (cloud, adaptive integer field)
 MODE_DTYPE = np.dtype([("bytes", "<u8", (4,)), ("probe_mode", "<u4"), ("best_mode", "<u4")])
+
+
+def hist_entropy_bytes(hist) -> float:
+    """cldn_hip_hist_entropy_bytes (host only): the order-0 entropy, in bytes, of the bytes a 256-bin histogram counts."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    if h.size != 256:
+        raise ValueError(f"a histogram has 256 bins, not {h.size}")
+    return float(lib().cldn_hip_hist_entropy_bytes(h.ctypes.data_as(C.c_void_p)))
 
 
 def _ladders(resolutions, n_fields: int) -> np.ndarray:
@@ -709,6 +729,77 @@ class Codec:
         _check(lib().cldn_hip_sweep_last_encode(self._h, res.ctypes.data_as(C.c_void_p), res.shape[1],
                                                 C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
                                                 DEVICE if report_ptr else HOST))
+        return rep
+
+    # ---- byte histograms for the stage-2 estimate (cldn_hip_sweep_hist_*, cldn_hip_stream_hist*) ---------------------
+    def _hist_report(self, *shape) -> np.ndarray:
+        rep = np.zeros(tuple(int(n) for n in shape) + (256,), dtype=np.uint64)
+        rep.view(np.uint8)[...] = 0xEE  # (a call that fails leaves it as it was)
+        return rep
+
+    def hist_walk(self, blocks: int):
+        """Test and measurement hook (cldn_hip_debug_hist_walk): 1024-point blocks per workgroup of k_sweep_hist, 0 = default."""
+        _check(lib().cldn_hip_debug_hist_walk(self._h, int(blocks)))
+
+    def sweep_hist_clouds_host(self, clouds: Sequence[np.ndarray], resolutions) -> np.ndarray:
+        """cldn_hip_sweep_hist_clouds on host buffers; arguments as sweep_clouds_host. Returns the
+        (n_clouds, n_fields, n_candidates, 256) uint64 report."""
+        step = self.plan.point_step
+        arrs = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in clouds]
+        if any(x.size % step for x in arrs):
+            raise ValueError("Input cloud_data size is not a multiple of point_step")
+        cp = np.array([x.size // step for x in arrs], dtype=np.uint64)
+        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        return self.sweep_hist_clouds_device(data.ctypes.data, cp, resolutions, points_loc=HOST)
+
+    def sweep_hist_clouds_device(self, points_ptr: int, cloud_points, resolutions, report_ptr: int = 0, points_loc: int = DEVICE):
+        """cldn_hip_sweep_hist_clouds on a raw pointer; report_ptr as in sweep_clouds_device (2048 bytes per histogram)."""
+        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
+        res = _ladders(resolutions, self.plan.n_fields)
+        rep = None if report_ptr else self._hist_report(cp.size, self.plan.n_fields, res.shape[1])
+        _check(lib().cldn_hip_sweep_hist_clouds(self._h, C.c_void_p(points_ptr), points_loc, cp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                cp.size, res.ctypes.data_as(C.c_void_p), res.shape[1],
+                                                C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                                DEVICE if report_ptr else HOST))
+        return rep
+
+    def sweep_hist_last_encode(self, resolutions, report_ptr: int = 0):
+        """cldn_hip_sweep_hist_last_encode: the points of this codec's most recent encode call; state rules as sweep_last_encode."""
+        n = int(lib().cldn_hip_sweep_last_encode_clouds(self._h))
+        _check(n)
+        res = _ladders(resolutions, self.plan.n_fields)
+        rep = None if report_ptr else self._hist_report(n, self.plan.n_fields, res.shape[1])
+        _check(lib().cldn_hip_sweep_hist_last_encode(self._h, res.ctypes.data_as(C.c_void_p), res.shape[1],
+                                                     C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                                     DEVICE if report_ptr else HOST))
+        return rep
+
+    def stream_hist_host(self, streams: Sequence[np.ndarray]) -> np.ndarray:
+        """cldn_hip_stream_hist on host buffers: one (256,) uint64 histogram per stream."""
+        ss = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in streams]
+        offs = np.zeros(len(ss) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([x.size for x in ss])
+        data = np.concatenate(ss + [np.zeros(1, np.uint8)])
+        return self.stream_hist_device(data.ctypes.data, offs, streams_loc=HOST)
+
+    def stream_hist_device(self, streams_ptr: int, stream_offsets, report_ptr: int = 0, streams_loc: int = DEVICE):
+        """cldn_hip_stream_hist on a raw pointer. stream_offsets: host [n_clouds + 1]; report_ptr: device array of n_clouds
+        histograms (returns None), 0 = host report (returned)."""
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
+        n = max(0, so.size - 1)
+        rep = None if report_ptr else self._hist_report(n)
+        _check(lib().cldn_hip_stream_hist(self._h, C.c_void_p(streams_ptr), streams_loc, so.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                          C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                          DEVICE if report_ptr else HOST))
+        return rep
+
+    def stream_hist_last_encode(self, report_ptr: int = 0):
+        """cldn_hip_stream_hist_last_encode: the streams this codec's most recent framed encode call wrote, one row per cloud."""
+        n = int(lib().cldn_hip_audit_last_encode_clouds(self._h))
+        _check(n)
+        rep = None if report_ptr else self._hist_report(n)
+        _check(lib().cldn_hip_stream_hist_last_encode(self._h, C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
+                                                      DEVICE if report_ptr else HOST))
         return rep
 
     # ---- adaptive integer modes: section bytes per mode, probed and best mode (cldn_hip_sweep_modes_*) ---------------

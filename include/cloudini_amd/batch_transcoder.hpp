@@ -159,6 +159,13 @@ struct TranscodeOptions {
   // codec does not encode with a lossy float encoder there, is ignored for that message. The output is what it is without the
   // sweep. Not available together with `decode`.
   std::map<std::string, std::vector<float>> sweep;
+  // Stage-2 estimate (include/cloudini_hip.h, cldn_hip_sweep_hist_last_encode, cldn_hip_stream_hist_last_encode); needs `sweep`.
+  // Behind the sweep of every schema run the GPU stage takes the byte histograms of the run's streams and of every swept
+  // field's tokens at its own resolution and at every rung, and adds to TranscodeStats::estimate, per field name and rung, the
+  // order-0 entropy of the streams if THAT FIELD ALONE moved to that rung (stream - own + candidate, summed over the run's
+  // clouds) -- what ZSTD level 1 makes of them while literals dominate, whatever `compression` is -- and to
+  // estimate_own_bytes the same figure for the streams as they are. The output is what it is without the option.
+  bool estimate = false;
   // Adaptive integer modes (include/cloudini_hip.h, cldn_hip_sweep_modes_last_encode). The reference commits one mode per cloud
   // and integer field (ring, rgba, integer intensity, stamps ...) from the first 4096 values only.
   //   Report  behind the encode call of every schema run the GPU stage measures, on the device, what each integer section costs
@@ -201,6 +208,13 @@ struct SweepCellSummary {
   double max_abs_err = 0;
 };
 
+// One field name at one candidate resolution over all messages of a run of the transcoder (TranscodeOptions::estimate).
+struct EstimateSummary {
+  std::string name;
+  float resolution = 0;
+  double bytes = 0;            // estimated stage-2 bytes of the estimated clouds' streams if this field alone had this resolution
+};
+
 // One adaptive integer field name over all messages of a run of the transcoder (cldn_hip_mode_cell_t summed).
 struct ModeFieldSummary {
   std::string name;
@@ -226,6 +240,11 @@ struct TranscodeStats {
   void mergeAudit(const std::vector<AuditFieldSummary>& other);
   std::vector<SweepCellSummary> sweep;   // TranscodeOptions::sweep: one entry per field name and resolution, in order of first appearance
   void mergeSweep(const std::vector<SweepCellSummary>& other);
+  std::vector<EstimateSummary> estimate; // TranscodeOptions::estimate: one entry per field name and resolution, as `sweep`
+  double estimate_own_bytes = 0;         // the same estimate at the resolutions the messages were encoded with
+  uint64_t estimate_stage1_bytes = 0;    // stage-1 bytes of the estimated streams, [u32] prefixes included
+  uint64_t estimate_actual_bytes = 0;    // compression == ZSTD: what stage 2 made of those streams, [u32] prefixes included
+  void mergeEstimate(const std::vector<EstimateSummary>& other);
   std::vector<ModeFieldSummary> modes;   // TranscodeOptions::modes: one entry per field name, in order of first appearance
   uint64_t mode_reencoded_runs = 0;      // Modes::Best: schema runs that were encoded a second time
   void mergeModes(const std::vector<ModeFieldSummary>& other);

@@ -109,6 +109,17 @@ int64_t cldn_amd_transcode_directory_sweep(const char* in_dir, const char* out_d
                                            const char* const* sweep_names, const uint32_t* ladder_sizes, const float* ladders,
                                            uint32_t n_names, double* stats_out, char* sweep_json, uint64_t sweep_capacity);
 
+/* The same with the stage-2 estimate on top (TranscodeOptions::estimate; include/cloudini_hip.h, cldn_hip_sweep_hist_last_encode,
+ * cldn_hip_stream_hist_last_encode): estimate_json receives one line of JSON -- {"own_bytes", "stage1_bytes", "actual_bytes",
+ * "fields": [{"name", "resolution", "bytes"}]}: per field name and candidate resolution the order-0 entropy, in bytes, of the
+ * messages' streams if that field alone had that resolution; own_bytes the same for the streams as encoded, stage1_bytes their
+ * size, actual_bytes what stage 2 made of them when compression_opt is ZSTD (else 0). */
+int64_t cldn_amd_transcode_directory_estimate(const char* in_dir, const char* out_dir, float resolution, uint8_t compression_opt,
+                                              int viz_lossy, uint32_t batch_messages, const int32_t* devices, uint32_t n_devices,
+                                              const char* const* sweep_names, const uint32_t* ladder_sizes, const float* ladders,
+                                              uint32_t n_names, double* stats_out, char* sweep_json, uint64_t sweep_capacity,
+                                              char* estimate_json, uint64_t estimate_capacity);
+
 /* cldn_amd_transcode_directory_on with the adaptive integer mode sweep behind every encode call (TranscodeOptions::modes;
  * include/cloudini_hip.h, cldn_hip_sweep_modes_last_encode). apply_best == 0 ("report"): the files are the same; != 0 ("best"): a
  * schema run in which some cloud's best mode differs from the probed one is encoded a second time with the best modes forced per

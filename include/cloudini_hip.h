@@ -400,7 +400,7 @@ int64_t cldn_hip_audit_last_encode_clouds(const cldn_hip_codec_t* codec);
  *   - for a cloud of n points whose fields are all sweepable, the sum over the fields of `bytes` at the plan's own resolutions
  *     plus 4 * ceil(n / 32768) is the size of the stream cldn_hip_encode_stage1 writes for it;
  *   - in general, changing field f from resolution r to r' changes that size by bytes_f(r') - bytes_f(r).
- * `bytes` covers stage 1 only: LZ4 / ZSTD behind it (on the host or on the device) are not predicted.
+ * `bytes` covers stage 1 only; for what ZSTD behind it makes of a candidate see the byte histograms below (cldn_hip_sweep_hist_*).
  *
  * A field is SWEEPABLE when the plan encodes it with a lossy float encoder: FLOAT32 or FLOAT64 with a resolution under
  * encoding_opt LOSSY. The arithmetic is the encoder's and the decoder's own: a FloatN field quantises with m = 1.0f / r, rounds
@@ -442,6 +442,57 @@ int cldn_hip_sweep_clouds(cldn_hip_codec_t* codec, const void* points, int point
 int cldn_hip_sweep_last_encode(cldn_hip_codec_t* codec, const float* resolutions, uint32_t n_candidates,
                                cldn_hip_sweep_cell_t* report, int report_loc);
 int64_t cldn_hip_sweep_last_encode_clouds(const cldn_hip_codec_t* codec);
+
+/* Byte histograms: what stage 2 would make of a candidate resolution. `bytes` above hardly moves with the resolution (a token
+ * has at least one byte); the file behind ZSTD does. The order-0 entropy of a stream's bytes, cldn_hip_hist_entropy_bytes of
+ * its 256-bin histogram, follows ZSTD level 1 closely while literals dominate (DESIGN.md 4f has the measured ratios); it says
+ * nothing about LZ4, where matches dominate. tests/hist_model.py restates both reports in numpy.
+ *
+ * A histogram ignores position, so the histogram of an interleaved stream is the sum of the histograms of its parts. With
+ * sweep_hist[k][f][c] the histogram of the bytes of field f's tokens at candidate c (the bytes the encoder would write: the
+ * zig-zag(+1) LEB128 groups, 0x00 for a NaN) and stream_hist[k] the histogram of cloud k's framed stream, both identities of
+ * the sweep hold bin for bin:
+ *   - for a cloud whose fields are all sweepable, stream_hist[k] is the sum over the fields of sweep_hist[k][f] at the plan's
+ *     own resolutions plus the histogram of the bytes of the [u32] chunk prefixes;
+ *   - in general, moving field f from resolution r to r' changes the histogram of the stream's PAYLOAD bytes by
+ *     sweep_hist[k][f][r'] - sweep_hist[k][f][r]. The four prefix bytes per chunk are the exception: they spell the payload
+ *     sizes, which move with the field (take the prefix bytes out of both stream histograms and the identity is exact).
+ * Hence the estimate for "field f at r', everything else as encoded": the entropy of stream - own_f + candidate_f, with four
+ * stale bytes per 32768 points in it. */
+typedef struct cldn_hip_hist {
+  uint64_t bin[256];
+} cldn_hip_hist_t; /* 2048 bytes */
+
+/* cldn_hip_sweep_hist_clouds, cldn_hip_sweep_hist_last_encode: report[(k * n_fields + f) * n_candidates + c]. Ladders, the skip
+ * rule (0), argument errors, workspace, state rules and the survivors of a viz encode are exactly cldn_hip_sweep_clouds' and
+ * cldn_hip_sweep_last_encode's (valid from cldn_hip_encode_stage1_chunks on); the histograms of a field that is not sweepable
+ * and of a skipped rung are all zero. Per call: one clear of the report, one kernel, one upload of the tables; a workgroup
+ * takes several consecutive 1024-point blocks and adds to the report once per cloud, field and candidate, only where a bin is
+ * not zero. Every bin is an integer sum: the report is deterministic to the bit. */
+int cldn_hip_sweep_hist_clouds(cldn_hip_codec_t* codec, const void* points, int points_loc, const uint64_t* cloud_points,
+                               uint32_t n_clouds, const float* resolutions, uint32_t n_candidates, cldn_hip_hist_t* report,
+                               int report_loc);
+int cldn_hip_sweep_hist_last_encode(cldn_hip_codec_t* codec, const float* resolutions, uint32_t n_candidates,
+                                    cldn_hip_hist_t* report, int report_loc);
+
+/* One histogram per cloud over the bytes [stream_offsets[k], stream_offsets[k + 1]) of `streams`, as they lie there: the [u32]
+ * prefixes are counted, any byte alignment is served, a cloud without bytes has an all-zero histogram. stream_offsets: HOST
+ * [n_clouds + 1], ascending. report: [n_clouds], HOST or DEVICE per report_loc (DEVICE: 8-byte aligned). HOST streams are
+ * uploaded into the audit's workspace. Per call: one clear, one kernel (128 KiB of a stream per workgroup), one upload of its
+ * table. Like every call that takes buffers, cldn_hip_stream_hist drops the state the *_last_encode calls need.
+ * cldn_hip_stream_hist_last_encode: the streams this codec's most recent FRAMED encode call wrote, read where they lie (see
+ * cldn_hip_audit_last_encode; rows: cldn_hip_audit_last_encode_clouds). Between cldn_hip_encode_stage1_chunks and
+ * cldn_hip_frame_chunks there are no streams: CLDN_HIP_ERR_ARG in the audit's wording, as without any state. With stage 2 on
+ * the device (CLDN_HIP_STAGE2_LZ4) the streams hold LZ4 blocks and the histogram is of the LZ4 BYTES: it no longer composes
+ * with cldn_hip_sweep_hist_*. For DEVICE outputs the call reads the n_clouds + 1 offsets back once. The state stays as it was:
+ * the call may be repeated and mixed in any order with cldn_hip_audit_last_encode and the sweeps. */
+int cldn_hip_stream_hist(cldn_hip_codec_t* codec, const void* streams, int streams_loc, const uint64_t* stream_offsets,
+                         uint32_t n_clouds, cldn_hip_hist_t* report, int report_loc);
+int cldn_hip_stream_hist_last_encode(cldn_hip_codec_t* codec, cldn_hip_hist_t* report, int report_loc);
+
+/* Host only, no device: min(N, sum over the non-zero bins of c * log2(N / c) / 8) with N = the sum of the bins; 0 for an empty
+ * histogram. Histograms may be added and subtracted bin by bin before the call (the identities above). */
+double cldn_hip_hist_entropy_bytes(const cldn_hip_hist_t* h);
 
 /* Sweep of the adaptive integer modes: what does each V5 integer section (ring, rgba, integer intensity, stamps ...) cost
  * under each of the four modes, which mode does the reference's probe commit, and which one would the same rule pick if it

@@ -14,6 +14,10 @@
 //       encode call's points are swept on the device (cldn_hip_sweep_last_encode): one `sweep` table line per field and
 //       resolution in front of the JSON line -- stage-1 bytes, bytes per point, class_diff, over_limit, max_abs_err. The files
 //       are the files of a run without --sweep. Not available with --decode. Malformed strings: exit status 2.
+//   ... --sweep "..." --estimate   behind the `sweep` lines (unchanged), one `estimate` line per field and resolution: the order-0
+//       entropy of the streams if that field alone had that resolution (cldn_hip_sweep_hist_last_encode,
+//       cldn_hip_stream_hist_last_encode) -- what ZSTD level 1 makes of them --, and an `own` line for the streams as encoded,
+//       next to the real size when the output is ZSTD. Without --sweep, or with --decode: exit status 2.
 //   ... --modes report|best   the V5 integer sections (ring, rgba, stamps ...): the reference commits one of four modes per cloud
 //       and field from the first 4096 values only. `report` measures on the device what every mode costs over the whole cloud
 //       (cldn_hip_sweep_modes_last_encode): one `modes` table line per field in front of the JSON line; the files are the files
@@ -45,6 +49,19 @@ static bool printAudit(const cloudini_amd::TranscodeStats& st) {
 }
 
 // one line per field and candidate resolution
+// one line per field name and rung: what the estimated streams would be behind ZSTD level 1 if that field alone moved there;
+// `own`: as they were encoded, with stage 1's size and -- when the output is ZSTD -- what stage 2 really made of them
+static void printEstimate(const cloudini_amd::TranscodeStats& st) {
+  std::printf("estimate %-24s %14s %16s\n", "field", "resolution", "stage2_bytes");
+  for (const cloudini_amd::EstimateSummary& e : st.estimate)
+    std::printf("estimate %-24s %14.9g %16.3f\n", e.name.c_str(), (double)e.resolution, e.bytes);
+  std::printf("estimate %-24s %14s %16.3f stage1_bytes %llu", "own", "-", st.estimate_own_bytes, (unsigned long long)st.estimate_stage1_bytes);
+  if (st.estimate_actual_bytes)
+    std::printf(" actual_bytes %llu estimate/actual %.4f", (unsigned long long)st.estimate_actual_bytes,
+                st.estimate_own_bytes / (double)st.estimate_actual_bytes);
+  std::printf("\n");
+}
+
 static void printSweep(const cloudini_amd::TranscodeStats& st) {
   std::printf("sweep %-24s %14s %16s %12s %12s %12s %24s\n", "field", "resolution", "bytes", "bytes/point", "class_diff", "over_limit", "max_abs_err");
   for (const cloudini_amd::SweepCellSummary& s : st.sweep)
@@ -80,6 +97,7 @@ int main(int argc, char** argv) {
                  "  --modes best                          also re-encode with the best mode per cloud where the 4096-value probe chose another:\n"
                  "                                        those messages are NOT the reference encoder's bytes; they are valid streams that\n"
                  "                                        every Cloudini decoder decodes to the same points\n"
+                 "  --estimate                             with --sweep: estimated ZSTD bytes per field and rung (files unchanged)\n"
                  "  --sweep and --modes are not available with --decode\n", argv[0]);
     return 2;
   }
@@ -118,6 +136,7 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--estimate") opt.estimate = true;
     else if (a == "--modes" && i + 1 < argc) {
       const std::string v = argv[++i];
       if (v != "report" && v != "best") {
@@ -147,6 +166,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--sweep is not available with --decode\n");
     return 2;
   }
+  if (opt.estimate && (opt.decode || opt.sweep.empty())) {
+    std::fprintf(stderr, "--estimate needs --sweep and is not available with --decode\n");
+    return 2;
+  }
   if (opt.decode && opt.modes != cloudini_amd::TranscodeOptions::Modes::Off) {
     std::fprintf(stderr, "--modes is not available with --decode\n");
     return 2;
@@ -158,6 +181,7 @@ int main(int argc, char** argv) {
       const cloudini_amd::McapTranscodeStats ms = cloudini_amd::transcodeMcap(in_path, argv[2], opt, mcap_comp);
       const bool clean = !opt.audit || printAudit(ms.pipeline);
       if (!opt.sweep.empty()) printSweep(ms.pipeline);
+      if (opt.estimate) printEstimate(ms.pipeline);
       if (modes) printModes(ms.pipeline);
       std::printf("{\"messages\": %llu, \"converted\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"points\": %llu, "
                   "\"seconds_total\": %.6f, \"gpu_batches\": %llu, \"peak_held_bytes\": %llu}\n",
@@ -179,6 +203,7 @@ int main(int argc, char** argv) {
     const cloudini_amd::TranscodeStats st = cloudini_amd::transcodePointClouds(source, sink, opt);
     const bool clean = !opt.audit || printAudit(st);
     if (!opt.sweep.empty()) printSweep(st);
+    if (opt.estimate) printEstimate(st);
     if (modes) printModes(st);
     std::printf("{\"messages\": %llu, \"points\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"gpu_batches\": %llu, "
                 "\"seconds_total\": %.6f, \"seconds_gpu\": %.6f, \"seconds_stage2\": %.6f, \"gpu_stages\": %llu, \"Mpoints_per_s\": %.1f}\n",
