@@ -1828,10 +1828,10 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   h_so[n_clouds] = stream_bytes - base_off;
   h_fp[n_clouds] = fp;
   h_fc[n_clouds] = fc;
-  const size_t chunk_table_bytes = ((size_t)std::max(1u, n_chunks) * kDecChunkBytes + 63) & ~size_t(63);
+  const size_t chunk_table_bytes = ((size_t)std::max(1u, n_chunks) * sizeof(DecChunk) + 63) & ~size_t(63);
   if ((rc = c->d_dec_meta.ensure(((table_bytes + 63) & ~size_t(63)) + chunk_table_bytes + (size_t)std::max(1u, n_chunks) * 18u + 64u)) != CLDN_HIP_OK)
     return rc;
-  const bool dec_cols = c->plan.uses_v5 && plan.n_adaptive >= 1u && plan.n_adaptive <= 8u;
+  const bool dec_cols = c->plan.uses_v5 && plan.n_adaptive >= 1u && plan.n_adaptive <= kSoMaxFields;
   for (uint32_t a = 0; a < 8u; ++a)
     if (dec_cols && a < plan.n_adaptive && plan.adaptive[a].bpv <= 4u &&
         (rc = c->d_dec_cols[a].ensure((size_t)n_points * plan.adaptive[a].bpv + 64)) != CLDN_HIP_OK)
@@ -1878,7 +1878,7 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   }
   L.n_clouds = n_clouds;
   L.n_chunks = n_chunks;
-  L.chunks = meta + ((table_bytes + 63) & ~size_t(63));
+  L.chunks = (DecChunk*)(meta + ((table_bytes + 63) & ~size_t(63)));
   L.reg_end = (uint32_t*)(meta + ((table_bytes + 63) & ~size_t(63)) + chunk_table_bytes);
   L.reg_end_pre = L.reg_end + std::max(1u, n_chunks);
   L.sec_done = (uint8_t*)(L.reg_end_pre + std::max(1u, n_chunks));
@@ -1909,10 +1909,10 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   L.dsec = nullptr;
   L.secs_ok = nullptr;
   L.done_cnt = nullptr;
-  if (c->plan.uses_v5 && plan.n_adaptive >= 1u && plan.n_adaptive <= 8u && n_chunks) {  // sections side by side (stage1_decode_sections_w.h)
-    const size_t rows = (size_t)plan.n_adaptive * n_chunks * kDecChunkBytes;
+  if (c->plan.uses_v5 && plan.n_adaptive >= 1u && plan.n_adaptive <= kSoMaxFields && n_chunks) {  // sections side by side (stage1_decode_sections_w.h)
+    const size_t rows = (size_t)plan.n_adaptive * n_chunks * sizeof(DecChunk);
     if ((rc = c->d_dec_secs.ensure(rows + (size_t)n_chunks * 8u + 256u)) != CLDN_HIP_OK) return rc;
-    L.dsec = c->d_dec_secs.p;
+    L.dsec = (DecChunk*)c->d_dec_secs.p;
     L.done_cnt = (uint32_t*)((uint8_t*)c->d_dec_secs.p + ((rows + 63u) & ~size_t(63)));
     L.secs_ok = (uint8_t*)(L.done_cnt + n_chunks);
   }

@@ -14,6 +14,8 @@
 //                        final values).
 #pragma once
 
+#include "stage1_decode_route.h"
+
 namespace cldn {
 
 // decode statistics behind the status word (uint32 indexes into the codec's status buffer): chunks whose regular

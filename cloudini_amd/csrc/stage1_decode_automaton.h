@@ -23,23 +23,14 @@
 // grid = n_chunks, kMaWaves * 64 threads.
 #pragma once
 
+#include "stage1_decode_route.h"
+
 namespace cldn {
 
 constexpr uint32_t kMaWaves = 8u;
 constexpr uint32_t kMaPiece = 2048u;  // payload bytes per piece: 32 per lane
 constexpr uint32_t kMaRing = 64u;
-constexpr uint32_t kMaMaxStates = 16u;
 constexpr uint32_t kMaSpinLimit = 1u << 20;
-
-// states of the form (0 when it has more than kMaMaxStates)
-inline uint32_t automaton_states(const DevPlan& P) {
-  uint32_t s = 0u;
-  for (uint32_t o = 0; o < P.n_ops; ++o) {
-    const uint32_t kd = P.ops[o].kind;
-    s += (kd == OP_COPY || kd == OP_XOR32 || kd == OP_XOR64) ? P.ops[o].size : 1u;
-  }
-  return s <= kMaMaxStates ? s : 0u;
-}
 
 // (a o b)(s) = a(b(s)): b first. Fields beyond S are never looked at.
 __device__ __forceinline__ uint64_t ma_compose(uint64_t a, uint64_t b, uint32_t S) {

@@ -16,10 +16,11 @@
 // its palette): reg_end[c] = kDecRedo hands it to k_decode_varint, which keeps the reference's error reporting.
 #pragma once
 
+#include "stage1_decode_route.h"
+
 namespace cldn {
 
 constexpr uint32_t kFastPalEntries = 1024;
-constexpr uint32_t kFastPalFields = 2;
 
 // 16 payload bytes at payload offset `o` (any alignment of the stream); bytes behind the payload read as 0xff
 // (continuation bytes: no token ends there)
@@ -413,7 +414,6 @@ __global__ __launch_bounds__(NW * 64) void k_locate_sections(const DevPlan plan,
 constexpr uint32_t kScfThreads = 256;
 constexpr uint32_t kScfTileBytes = kScfThreads * 16u;
 constexpr uint32_t kScfMaxRuns = 1024;  // (three tables of this many entries share the value buffer)
-constexpr uint32_t kScfMaxParts = 16;   // workgroups per chunk (DeltaVarint slices round robin; runs: the first one): at most
 constexpr uint32_t kScfMaxSlices = 48;  // 32768 tokens of 5 bytes are 40 slices
 constexpr uint32_t kScfSpinLimit = 1u << 22;
 

@@ -14,10 +14,11 @@
 // (decodeV5AdaptiveIntSection, src/v5_codec.cpp:764-879.)
 #pragma once
 
+#include "stage1_decode_route.h"
+
 namespace cldn {
 
 constexpr uint32_t kSoThreads = 256;
-constexpr uint32_t kSoMaxFields = 8;
 constexpr uint32_t kSoRleStage = 4096;   // bytes of an Rle section one lane parses from LDS
 constexpr uint32_t kSwsThreads = 256;
 constexpr uint32_t kSwsMaxRuns = 1024;

@@ -15,12 +15,12 @@
 // a loop iteration, whatever the number of ops. Per-op state (running value, aggregate) lives in LANE o of a register.
 #pragma once
 
+#include "stage1_decode_route.h"
+
 namespace cldn {
 
 constexpr uint32_t kSwPiece = 1024u;
 constexpr uint32_t kSwHalo = 96u;           // a point has at most kSwMaxPointBytes bytes behind its first
-constexpr uint32_t kSwMaxPointBytes = 88u;
-constexpr uint32_t kSwMaxOps = 8u;
 constexpr uint32_t kSwRing = 32u;
 constexpr uint32_t kSwListEntries = 1032u;  // points a piece can own (one op of one byte: one per byte) + slack
 constexpr uint32_t kSwSpinLimit = 1u << 18;
@@ -1270,7 +1270,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MODE ? 
 // with one store per field. The stream kernel decoded these streams with its token machinery at 1.35 TB/s.
 // At most kFxMaxOps fields; anything else (or a payload shorter than n * P) leaves the chunk to the kernels behind (kDecRedo).
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kFxMaxOps = 8;
 constexpr uint32_t kFxThreads = 1024;
 
 __global__ __launch_bounds__(kFxThreads) void k_decode_fixed(const DevPlan plan, const uint8_t* __restrict__ streams,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "stage1_decode_route.h"
 #include "stage1_device.h"
 #include "stage1_report.h"
 
@@ -94,19 +95,19 @@ struct DecodeLaunch {
   uint32_t n_clouds;
   uint32_t n_chunks;
   uint32_t dv_hint;                   // what the codec's earlier calls saw: 1 = no chunk had a lone DeltaVarint section, 2 = every chunk had, 0 = unknown / mixed
-  void* chunks;                       // device [n_chunks] DecChunk (48 bytes each)
+  DecChunk* chunks;                   // device [n_chunks]: the table k_build_chunks / k_walk_chunks fill
   uint32_t* reg_end;                  // device [n_chunks]: end of the regular stream per chunk (fast path)
-  uint8_t* sec_done;                  // device [n_chunks]: 1 = sections decoded by k_decode_sections
+  uint8_t* sec_done;                  // device [n_chunks]: 1 = the chunk's sections are decoded (k_decode_general skips them)
   uint8_t* cols[8];                   // device: dense columns of the first adaptive fields (n_points * bpv each), or NULL
-  uint32_t* reg_end_pre;              // device [n_chunks]: k_decode_sections_cols: where the regular stream ends
+  uint32_t* reg_end_pre;              // device [n_chunks]: where k_locate_sections found the regular stream's end (read by the column kernels and the decoder behind them)
   uint8_t* sec_cols;                  // device [n_chunks]: 1 = the columns hold the chunk's integer fields
   const uint32_t* chunk_sizes;        // device [n_chunks] or NULL: the payload sizes, if the caller knows them (no serial walk)
-  uint32_t* token_ends;           // k_mark_token_ends: one bit per stream byte (+ a word per chunk), or NULL
+  uint32_t* token_ends;           // the marker kernels' bitmap (k_mark_token_ends, k_mark_ends_automaton): one bit per stream byte (+ a word per chunk), or NULL
   uint32_t fill_zero;             // CLDN_HIP_FILL_ZERO: bytes of a point that no field covers may be written as 0
   uint32_t* slices_done;          // [n_chunks] DeltaVarint slices of a chunk that k_sections_cols_fast finished
   unsigned long long* slice_rec;  // [n_chunks * 48 * 2] (count, sum) records of the slices, tagged with slice_epoch
   uint32_t slice_epoch;           // != 0, different from every earlier launch on slice_rec since it was cleared
-  void* dsec;                     // [n_adaptive * n_chunks] DecChunk: the sections k_section_offsets sized (stage1_decode_sections_w.h), or NULL
+  DecChunk* dsec;                 // [n_adaptive * n_chunks]: the sections k_section_offsets sized (stage1_decode_sections_w.h), or NULL
   uint8_t* secs_ok;               // [n_chunks]
   uint32_t* done_cnt;             // [n_chunks]
   uint8_t* out;                       // device: decoded AoS points
@@ -131,18 +132,6 @@ struct DecodeLaunch {
 };
 // bytes of the SPLIT workspace: per piece t0 (4) + aggregates (5 x 4) + carries (4 x 4), per chunk 4 flag words
 inline size_t wp_split_bytes(uint32_t n_chunks, uint32_t maxp) { return (size_t)n_chunks * maxp * 40u + (size_t)n_chunks * 16u + 256u; }
-// workgroups per chunk of a SPLIT launch (1 = the chained launch). Measured (device-resident decode, n x 1 M XYZI points /
-// 130 k-point Velodyne clouds): a split launch costs about 1.5 x the arithmetic, three more launches and a prologue per
-// workgroup -- it wins up to about 64 chunks (one cloud 0.093 -> 0.072 ms, one Velodyne cloud 0.153 -> 0.088) and loses
-// from about 100 on (124 chunks 0.095 -> 0.111, 496 chunks 0.16 -> 0.39 ms)
-inline uint32_t wp_split_parts(uint32_t n_chunks) {
-  if (n_chunks == 0u || n_chunks > 64u) return 1u;
-  const uint32_t parts = 256u / n_chunks;
-  return parts > 16u ? 16u : (parts < 2u ? 2u : parts);
-}
-
-constexpr size_t kDecChunkBytes = 48;
-
 // Launch errors go to the ABI's thread-local error string (cldn_hip_last_error), implemented in hip_abi.hip.
 int launch_fail(hipError_t e, const char* what);
 
