@@ -258,6 +258,13 @@ struct cldn_hip_codec {
   bool dec_stats_seen = false;       // one copy of the counters has landed
   uint32_t dec_dv_hint = 0;          // 1: the last counters showed no DeltaVarint section decoded by k_section_dv_w, 2: every chunk's (stage1_launch.h)
   uint32_t dec_call_index = 0;
+  // cldn_hip_debug_decode_trace: the per-chunk arrays of the last decode call (inside d_dec_meta)
+  struct DecTrace {
+    uint32_t n_chunks = 0;
+    const void* meta = nullptr;  // d_dec_meta.p of that call: a later call may have moved the workspace
+    const uint32_t *reg_end = nullptr, *reg_end_pre = nullptr, *slices_done = nullptr;
+    const uint8_t *sec_done = nullptr, *sec_cols = nullptr;
+  } dec_trace;
   hipEvent_t dec_events[4] = {nullptr, nullptr, nullptr, nullptr};  // the last decode call's (timing enabled)
   bool dec_events_valid = false;
   std::vector<uint8_t> slot_valid;
@@ -727,6 +734,34 @@ __attribute__((visibility("default"))) int cldn_hip_debug_decode_split(cldn_hip_
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   if (parts > 16u) return fail(CLDN_HIP_ERR_ARG, "at most 16 workgroups per chunk");
   c->test_split_parts = parts;
+  return CLDN_HIP_OK;
+}
+
+// Test hook, outside the boundary like the ones above: what the codec's last decode call decided, read from its workspace behind a
+// stream synchronise (tests/test_gpu_locate.py holds it against tests/locate_model.py). words: status words 8..15 (kStatFastRegular
+// .. kStatDvGuess, stage1_decode.h). Per chunk, `capacity` entries each (any may be NULL): reg_end_pre / slices_done / sec_cols as the
+// kernels in front of the point kernel left them, reg_end / sec_done as the call left them. Arrays no kernel of the call's route
+// writes hold stale bytes, and any later call of the codec reuses the status block: ask straight after the decode call.
+// *n_chunks: chunks of that call (0: no decode call yet); more than `capacity` is an error.
+__attribute__((visibility("default"))) int cldn_hip_debug_decode_trace(cldn_hip_codec_t* c, uint32_t words[8], uint32_t capacity,
+                                                                       uint32_t* n_chunks, uint32_t* reg_end_pre, uint32_t* slices_done,
+                                                                       uint8_t* sec_cols, uint32_t* reg_end, uint8_t* sec_done) {
+  if (!c || !words || !n_chunks) return fail(CLDN_HIP_ERR_ARG, "decode_trace: NULL argument");
+  memset(words, 0, 8 * sizeof(uint32_t));
+  const cldn_hip_codec::DecTrace& t = c->dec_trace;
+  *n_chunks = t.n_chunks;
+  if (!c->d_status.p) return CLDN_HIP_OK;
+  if (t.n_chunks && t.meta != c->d_dec_meta.p) return fail(CLDN_HIP_ERR_ARG, "decode_trace: the last decode call's workspace is gone");
+  if (t.n_chunks > capacity) return fail(CLDN_HIP_ERR_CAPACITY, "decode_trace: %u chunks, room for %u", t.n_chunks, capacity);
+  ENTER_DEVICE(c->device);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(words, (const uint32_t*)c->d_status.p + 8, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  const size_t n = t.n_chunks;
+  if (n && reg_end_pre) HIP_TRY(hipMemcpy(reg_end_pre, t.reg_end_pre, n * 4u, hipMemcpyDeviceToHost));
+  if (n && slices_done) HIP_TRY(hipMemcpy(slices_done, t.slices_done, n * 4u, hipMemcpyDeviceToHost));
+  if (n && sec_cols) HIP_TRY(hipMemcpy(sec_cols, t.sec_cols, n, hipMemcpyDeviceToHost));
+  if (n && reg_end) HIP_TRY(hipMemcpy(reg_end, t.reg_end, n * 4u, hipMemcpyDeviceToHost));
+  if (n && sec_done) HIP_TRY(hipMemcpy(sec_done, t.sec_done, n, hipMemcpyDeviceToHost));
   return CLDN_HIP_OK;
 }
 
@@ -1970,6 +2005,7 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
     (void)hipEventRecord(L.events[2], c->stream);
   }
   ++c->dec_call_index;
+  c->dec_trace = {n_chunks, meta, L.reg_end, L.reg_end_pre, L.slices_done, L.sec_done, L.sec_cols};
   if ((rc = stage1_launch_decode(L)) != CLDN_HIP_OK) return rc;
   if (L.events) {
     (void)hipEventRecord(L.events[3], c->stream);

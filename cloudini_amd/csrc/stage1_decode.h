@@ -31,6 +31,9 @@ constexpr uint32_t kStatFoldedByGuess = 12;
 // front of k_decode_sections_cols, which decodes whatever is left whichever was launched (hip_abi.hip: dec_dv_hint)
 constexpr uint32_t kStatDvChunks = 13;
 constexpr uint32_t kStatDvMode = 14;  // chunks whose section k_locate_sections found to begin with mode byte 0 (whoever decodes it)
+// chunks k_locate_sections located by its DeltaVarint guess from the payload's end. Read by tests only (cldn_hip_debug_decode_trace):
+// a guess that was right leaves the same offset, mode byte and kStatDvMode as the count from the front
+constexpr uint32_t kStatDvGuess = 15;
 
 // (struct DecChunk: stage1_device.h -- the LZ4 block decoder of lz4_decode.hip fills the same table)
 

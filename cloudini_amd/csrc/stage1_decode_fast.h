@@ -296,6 +296,7 @@ __global__ __launch_bounds__(NW * 64) void k_locate_sections(const DevPlan plan,
           reg_end_pre[c] = at;
           slices_done[c] = 0u;  // (mode byte 0 in the top byte, no slice done)
           atomicAdd(&status[kStatDvMode], 1u);
+          atomicAdd(&status[kStatDvGuess], 1u);
         }
         return;
       }

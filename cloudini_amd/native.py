@@ -121,6 +121,8 @@ def lib() -> C.CDLL:
     L.cldn_hip_codec_set_decode_fill.restype = C.c_int
     L.cldn_hip_codec_decode_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cldn_hip_codec_decode_stats.restype = C.c_int
+    L.cldn_hip_debug_decode_trace.restype = C.c_int
+    L.cldn_hip_debug_decode_trace.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), vp, vp, vp, vp, vp]
     L.cldn_hip_codec_finish_retries.argtypes = [vp]
     L.cldn_hip_codec_finish_retries.restype = C.c_uint32
     L.cldn_hip_codec_force_modes.argtypes = [vp, C.POINTER(C.c_uint8), C.c_uint32]
@@ -413,6 +415,23 @@ class Codec:
         v = (C.c_uint32 * 4)()
         _check(lib().cldn_hip_codec_decode_stats(self._h, v))
         return tuple(int(x) for x in v)
+
+    def decode_trace(self, max_chunks: int = 4096):
+        """Test hook (cldn_hip_debug_decode_trace): what the last decode call decided, after a stream synchronise. Returns a dict:
+        `words` = status words 8..15 (fast regular, fast sections, serial chunks, serial sections, folded by the Palette guess,
+        k_section_dv_w chunks, sections with mode byte 0, DeltaVarint guesses from the end) and per chunk reg_end_pre,
+        slices_done, sec_cols, reg_end, sec_done."""
+        words = (C.c_uint32 * 8)()
+        n = C.c_uint32(0)
+        u32 = [np.zeros(max(1, max_chunks), dtype=np.uint32) for _ in range(3)]
+        u8 = [np.zeros(max(1, max_chunks), dtype=np.uint8) for _ in range(2)]
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(lib().cldn_hip_debug_decode_trace(self._h, words, max_chunks, C.byref(n), p(u32[0]), p(u32[1]), p(u8[0]), p(u32[2]),
+                                                 p(u8[1])))
+        k = int(n.value)
+        return {"words": tuple(int(x) for x in words), "n_chunks": k, "reg_end_pre": u32[0][:k].copy(),
+                "slices_done": u32[1][:k].copy(), "sec_cols": u8[0][:k].copy(), "reg_end": u32[2][:k].copy(),
+                "sec_done": u8[1][:k].copy()}
 
     def finish_retries(self) -> int:
         """Calls redone through k_finish's ticket order after ST_FINISH_TIMEOUT (cldn_hip_codec_finish_retries)."""

@@ -260,7 +260,7 @@ def test_marker_inside_integer_token_stream_is_rejected(oracle):
     codec.close()
 
 
-def _stats_after_decode(oracle, info, data):
+def _stats_after_decode(oracle, info, data, words=None):
     from cloudini_amd import native
     codec = native.Codec(native.Plan(info))
     step = info.point_step
@@ -271,6 +271,8 @@ def _stats_after_decode(oracle, info, data):
     want = oracle.decode_stage1(info, stream, n, fill=0x3C)
     assert np.array_equal(got, want)
     stats = codec.decode_stats()
+    if words is not None:
+        words.append(codec.decode_trace()["words"])   # status words 8..15
     codec.close()
     return stats, modes.tolist(), (n + 32767) // 32768
 
@@ -391,8 +393,11 @@ def test_section_guess_with_a_false_hit_in_the_token_stream(oracle, field):
     # the 257-entry guess really lands on 01 01 01 inside the token stream
     guess = len(payload) - (3 + 257 * 2 + (9 * n + 7) // 8)
     assert 3 < guess < 3 * n - 3 and bytes(payload[guess:guess + 3]) == b"\x01\x01\x01"
-    stats, _modes, n_chunks = _stats_after_decode(oracle, info, data)
+    folded = []
+    stats, _modes, n_chunks = _stats_after_decode(oracle, info, data, words=folded)
     assert stats == (n_chunks, n_chunks, 0, 0)
+    # word 12 (kStatFoldedByGuess): the real Palette is folded by the point kernel's own guess; the false hit alone folds nothing
+    assert folded[0][4] == (n_chunks if field == "palette3" else 0)
 
 
 def test_epoch_time_stamps_stay_on_the_parallel_decoder(oracle):
@@ -647,31 +652,48 @@ def test_chained_and_split_launches_of_the_point_kernel_agree(oracle, parts):
         codec.close()
 
 
+def _wrong_dv_guess_cloud(n):
+    """lidar_xyzi with every x NaN (a marker byte per point) and runs of 100 equal values in the integer field (Rle / DeltaRle)"""
+    info, data = synth.lidar_xyzi(n, seed=n)
+    a = data.reshape(n, info.point_step).copy()
+    a[:, 0:4] = np.frombuffer(np.float32(np.nan).tobytes(), np.uint8)
+    a[:, 12:14] = np.repeat((np.arange((n + 99) // 100) % 7 * 1000).astype(np.uint16), 100)[:n].view(np.uint8).reshape(n, 2)
+    return info, a.reshape(-1)
+
+
 def test_a_wrong_delta_varint_guess_from_the_end_is_found_out(oracle):
     """k_locate_sections guesses a lone DeltaVarint section from the payload's end (round 6): the (n + 1)-th byte with a clear MSB
     counted from the end is taken for the mode byte if it is 0. Here that byte IS 0 -- a NaN marker of the regular stream -- while
-    the section is a short Rle one: k_section_dv_w decodes n "tokens" of regular stream into the column, the point kernel finds
-    the regular stream ending elsewhere, and the chunk's sections must be redone from the right place."""
+    the section is a short run-length one. Chunks of 32000 points and more: the payload has over 65552 bytes, so the one tile of
+    k_locate_sections<16> is really read (smaller payloads never reach the guess), and every third size (32003, 32006, 32009)
+    puts an x marker on the guessed place. The trace (cldn_hip_debug_decode_trace) must show that the guess fired and was refuted: more
+    markers follow the false mode byte, so k_section_dv_w hands the chunk back, the point kernel finds the regular stream's real
+    end and k_decode_tail redoes the section from there. (tests/test_gpu_locate.py has the guess's other outcomes, among them the
+    garbage column that k_section_dv_w completes.)"""
+    import locate_model
     from cloudini_amd import native
     hits = 0
-    for n in range(3000, 3400):
-        info, data = synth.lidar_xyzi(n, seed=n)
-        a = data.reshape(n, info.point_step).copy()
-        a[:, 0:4] = np.frombuffer(np.float32(np.nan).tobytes(), np.uint8)          # every x is NaN: a marker byte per point
-        a[:, 12:14] = np.repeat(np.arange((n + 99) // 100, dtype=np.uint16), 100)[:n].view(np.uint8).reshape(n, 2) * 0 + \
-            np.repeat((np.arange((n + 99) // 100) % 7 * 1000).astype(np.uint16), 100)[:n].view(np.uint8).reshape(n, 2)  # runs of 100: Rle / DeltaRle
-        cloud = a.reshape(-1)
+    for n in range(32000, 32010):
+        info, cloud = _wrong_dv_guess_cloud(n)
         stream, modes = oracle.encode_stage1(info, cloud, return_modes=True)
         payload = stream[4:]
+        assert len(payload) > 65552
+        loc = locate_model.locate(payload, n, 3, [2], 16)
         ends = np.nonzero((payload & 0x80) == 0)[0]
-        if len(ends) < n + 1 or payload[ends[-(n + 1)]] != 0 or ends[-(n + 1)] < 3 * n:
-            continue   # the guess would not fire for this cloud
-        hits += 1
+        fires = not (len(ends) < n + 1 or payload[ends[-(n + 1)]] != 0 or ends[-(n + 1)] < 3 * n)
+        assert fires == (loc.branch == "dv_end")
         codec = native.Codec(native.Plan(info))
         out = np.full(cloud.size, 0x5A, dtype=np.uint8)
         got = codec.decode_host([stream], [n], out=out)[0]
         assert np.array_equal(got, oracle.decode_stage1(info, stream, n, fill=0x5A)), (n, list(modes))
+        tr = codec.decode_trace()
         codec.close()
-        if hits >= 6:
-            break
+        assert tr["words"][7] == (1 if fires else 0), (n, tr)           # the guess fired on the device exactly when the model says
+        assert tr["words"][:4] == (1, 1, 0, 0), (n, tr)
+        if fires:
+            hits += 1
+            assert not loc.right and int(tr["reg_end_pre"][0]) == ends[-(n + 1)] and int(tr["slices_done"][0]) >> 24 == 0
+            # refuted: no column, the point pass ended elsewhere, the section was redone behind it (sec_done 1, not 2 = folded)
+            assert int(tr["reg_end"][0]) == loc.truth != int(tr["reg_end_pre"][0])
+            assert (int(tr["sec_cols"][0]), int(tr["sec_done"][0]), tr["words"][5], tr["words"][6]) == (0, 1, 0, 1), (n, tr)
     assert hits >= 3
