@@ -812,22 +812,12 @@ int cldn_hip_codec_status(cldn_hip_codec_t* c) {
   return CLDN_HIP_OK;
 }
 
-// Build (or reuse) the chunk table of a batch. Returns the number of chunks and total points.
+// Build (or reuse) the chunk table of a batch of n_chunks chunks (the caller counted them: at most 0x3fffffff).
 // piece_pts != 0: also the piece table of the single-pass encoder (pieces of piece_pts points, per chunk padded to 4)
 // quad_major: the piece table lists workgroup 0 (pieces 0..3) of every chunk, then workgroup 1 of every chunk, ... so
 // that the workgroups of ONE chunk start far apart in time (intra-chunk placement of the piece kernel)
-static int upload_batch_shape(cldn_hip_codec* c, const uint64_t* cloud_points, uint32_t n_clouds, uint32_t piece_pts,
-                              bool quad_major, uint32_t* n_chunks_out, uint64_t* n_points_out) {
-  uint64_t total_points = 0;
-  uint64_t n_chunks64 = 0;
-  for (uint32_t k = 0; k < n_clouds; ++k) {
-    total_points += cloud_points[k];
-    n_chunks64 += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
-  }
-  if (n_chunks64 > 0x3fffffffull) return fail(CLDN_HIP_ERR_ARG, "batch too large");
-  const uint32_t n_chunks = (uint32_t)n_chunks64;
-  *n_chunks_out = n_chunks;
-  *n_points_out = total_points;
+static int upload_batch_shape(cldn_hip_codec* c, const uint64_t* cloud_points, uint32_t n_clouds, uint32_t n_chunks, uint32_t piece_pts,
+                              bool quad_major) {
   int rc;
   const bool same = c->last_cloud_points.size() == n_clouds && c->last_n_chunks == n_chunks &&
                     c->last_piece_pts == piece_pts && c->last_quad_major == quad_major &&
@@ -960,57 +950,84 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   const DevPlan& plan = c->plan.dev;
   const uint32_t step = plan.point_step;
 
-  uint32_t n_chunks = 0;
-  uint64_t n_points = 0;
-  // device-resident inputs decide the kernel variant by their address; host inputs are staged into an aligned buffer
-  const uint8_t* variant_ptr = points_loc == CLDN_HIP_DEVICE ? (const uint8_t*)points : nullptr;
   const bool wide = c->plan.wide;  // stage1_wide.h: the plan's arrays live in device memory, one segment per chunk
-  const uint32_t piece_pts = (c->pipeline == 1 || wide) ? 0u : stage1_piece_points(plan, variant_ptr);
-  const bool intra_env = table != nullptr;  // chunk tables want one regular segment per chunk
-  int rc = upload_batch_shape(c, cloud_points, n_clouds, piece_pts, piece_pts != 0u && intra_env, &n_chunks, &n_points);
+  const bool lz4 = c->stage2 == CLDN_HIP_STAGE2_LZ4 || c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST;
+  const bool lz4_fast = c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST;
+  const uint32_t n_adaptive = c->plan.n_adaptive_total();
+  // capacity contract of PointcloudEncoder::encode (cloudini.cpp:531-534)
+  uint64_t need = 0, need_s1 = 0, n_chunks64 = 0, n_points = 0;
+  for (uint32_t k = 0; k < n_clouds; ++k) {
+    need_s1 += cldn_hip_stage1_bound(&c->plan, cloud_points[k]);
+    need += cldn_hip_stage2_bound(&c->plan, cloud_points[k], c->stage2);
+    n_points += cloud_points[k];
+    n_chunks64 += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
+  }
+  if (n_chunks64 > 0x3fffffffull) return fail(CLDN_HIP_ERR_ARG, "batch too large");
+  const uint32_t n_chunks = (uint32_t)n_chunks64;  // the route's geometry and every buffer size below rest on this one count
+  // two-step host output (cldn_hip_codec_fetch_output): no caller buffer yet, the codec's own device buffer takes the bound
+  const bool deferred = out == nullptr && out_loc == CLDN_HIP_HOST && !table;
+  if (deferred || table) out_capacity = need;
+
+  // The call's route (stage1_encode_route.h), once: which kernels run, and the geometry of slots and segment table that the
+  // buffers below are sized from. Its facts first: the mode hints, whether the modes are forced, where the modes may go.
+  // (The hint refresh used to sit behind the argument checks and the sizing. Up here a call that then fails with ARG or
+  // CAPACITY has already taken the landed copy into hint_cache, and the event is queried a little earlier: the hints only
+  // steer which section kernels are launched, never a byte.)
+  if (!wide && c->last_modes_count && c->ev_last_modes && hipEventQuery(c->ev_last_modes) == hipSuccess) {
+    // a copy of an earlier call's modes has landed: it becomes the hint until a newer one lands
+    const uint8_t* lm = (const uint8_t*)c->h_last_modes.p;
+    const uint32_t nf = c->last_modes_fields;
+    for (uint32_t a = 0; a < (uint32_t)kMaxAdaptive; ++a) c->hint_cache[a] = 0;
+    for (size_t k = 0; k < c->last_modes_count; ++k) {
+      const uint8_t m = lm[k];
+      c->hint_cache[k % nf] |= (m <= 3u) ? (uint8_t)(1u << m) : (uint8_t)0xF;
+    }
+    c->hint_valid = true;
+    c->last_modes_count = 0;
+  }
+  EncodeFacts F = {};
+  F.n_chunks = n_chunks;
+  F.n_clouds = n_clouds;
+  F.n_points = n_points;
+  F.pipeline = (uint8_t)c->pipeline;
+  F.wide = wide;
+  F.chunks_only = table != nullptr;
+  F.lz4 = lz4;
+  // device-resident inputs decide the kernel variant by their address; host inputs are staged into d_in (checked where it is filled)
+  F.points_misaligned = points_loc == CLDN_HIP_DEVICE ? (uint8_t)((uintptr_t)points & 3u) : (uint8_t)0;
+  for (uint32_t a = 0; a < (uint32_t)kMaxAdaptive; ++a) F.mode_hint[a] = c->hint_valid ? c->hint_cache[a] : (uint8_t)0xF;
+  const bool per_cloud = c->forced_clouds != 0u;  // (then forced_clouds == n_clouds)
+  F.modes_forced = (!c->forced_modes.empty() || per_cloud) && n_adaptive && n_clouds;
+  for (uint32_t a = 0; a < plan.n_adaptive && F.modes_forced; ++a) {
+    uint8_t hint = per_cloud ? (uint8_t)0 : (uint8_t)(1u << c->forced_modes[a]);
+    for (uint32_t k = 0; per_cloud && k < n_clouds; ++k) hint |= (uint8_t)(1u << c->forced_cloud_modes[(size_t)k * n_adaptive + a]);
+    F.mode_hint[a] = hint;
+  }
+  // device-resident outputs: the probe workgroups of the piece kernel write the caller's modes array as well (a byte store
+  // fits any address); where another kernel decides the modes, or the caller forced them, the copy behind the call stays
+  uint8_t* const caller_modes = (out_loc == CLDN_HIP_DEVICE && !lz4 && !table && !F.modes_forced) ? modes : nullptr;
+  F.caller_modes = caller_modes != nullptr;
+  F.zero_block_reused = true;  // (known once the block is sized, see below)
+  F.out_capacity = lz4 ? need_s1 : out_capacity;
+  F.wide_adaptive = n_adaptive;
+  F.wide_gorilla = wide ? c->wide_desc.n_gorilla : 0u;
+  EncodeRoute R = encode_route(plan, F);
+
+  int rc = upload_batch_shape(c, cloud_points, n_clouds, n_chunks, R.piece_pts, R.piece_pts != 0u && table != nullptr);
   if (rc != CLDN_HIP_OK) return rc;
   if (n_points && !points && !cloud_ptrs) return fail(CLDN_HIP_ERR_ARG, "points is NULL");
   if (cloud_ptrs)
     for (uint32_t k = 0; k < n_clouds; ++k)
       if (cloud_points[k] && !cloud_ptrs[k]) return fail(CLDN_HIP_ERR_ARG, "cloud %u: NULL buffer", k);
 
-  // capacity contract of PointcloudEncoder::encode (cloudini.cpp:531-534)
-  uint64_t need = 0, need_s1 = 0;
-  for (uint32_t k = 0; k < n_clouds; ++k) {
-    need_s1 += cldn_hip_stage1_bound(&c->plan, cloud_points[k]);
-    need += cldn_hip_stage2_bound(&c->plan, cloud_points[k], c->stage2);
-  }
-  const bool lz4 = c->stage2 == CLDN_HIP_STAGE2_LZ4 || c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST;
-  const bool lz4_fast = c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST;
-  // two-step host output (cldn_hip_codec_fetch_output): no caller buffer yet, the codec's own device buffer takes the bound
-  const bool deferred = out == nullptr && out_loc == CLDN_HIP_HOST && !table;
-  if (deferred || table) out_capacity = need;
   if (out_capacity < need)
     return fail(CLDN_HIP_ERR_CAPACITY, "Output buffer too small for worst-case compressed size (%llu < %llu)",
                 (unsigned long long)out_capacity, (unsigned long long)need);
   if (need && !out && !deferred && !table) return fail(CLDN_HIP_ERR_ARG, "out is NULL");
   c->pending_total = 0;
 
-  const uint32_t n_adaptive = c->plan.n_adaptive_total();
-  // Sub-chunks: the regular stream of a chunk is produced as `subs` independent sub-streams (one workgroup each)
-  // that the compaction kernel concatenates; this multiplies the parallelism of small batches at no extra work.
-  uint32_t subs = 1;
-  while (subs < 32u && (uint64_t)n_chunks * subs < 6000u) subs *= 2u;
-  if (wide) subs = 1u;
-  const bool pieces = piece_pts != 0u && n_chunks != 0u;   // regular stream by the piece kernel
-  const bool intra = pieces && intra_env;
-  const uint32_t piece_wgs = ((((kPointsPerChunk + piece_pts - 1u) / std::max(1u, piece_pts)) + 3u) & ~3u) / 4u;  // workgroups (4 pieces) per full chunk
-  if (pieces) subs = intra ? 1u : piece_wgs;  // one segment per workgroup, or one per chunk
-  const uint32_t sub_points = pieces ? piece_pts : kPointsPerChunk / subs;
-  // (intra: the slot still reserves the worst case of every workgroup, the streams are packed at its start)
-  const uint32_t sub_stride = pieces ? 4u * stage1_piece_slot_stride(plan, variant_ptr) * (intra ? piece_wgs : 1u)
-                                     : (uint32_t)((((uint64_t)sub_points * plan.max_regular_bytes + 64u) + 255u) & ~uint64_t(255));
-  const uint32_t segs_per_chunk = wide ? 1u : subs + 2u * n_adaptive;
-  const uint64_t reg_stride = (uint64_t)subs * sub_stride;
-  // WIDE: the slot takes the chunk's whole payload as one run -- the regular stream's worst case and, per adaptive field,
-  // the largest section any mode can write (DeltaRle: 5 + 11 bytes per value)
-  const uint64_t wide_slot = (((uint64_t)kPointsPerChunk * ((uint64_t)plan.max_regular_bytes + 11ull * n_adaptive) + 16ull * n_adaptive + 64ull) + 255ull) & ~255ull;
-  const uint64_t slot_stride = wide ? wide_slot : reg_stride + (uint64_t)n_adaptive * kSectionStride;
+  const uint32_t segs_per_chunk = R.segs_per_chunk;
+  const uint64_t slot_stride = R.slot_stride;
 
   // one zero-filled block per call (one memset launch instead of three; none where the piece kernel clears it, see below)
   const size_t z_anchor = 256;
@@ -1023,13 +1040,11 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   if ((rc = c->d_offsets.ensure((size_t)(n_clouds + 1) * sizeof(uint64_t))) != CLDN_HIP_OK) return rc;
   if ((rc = c->d_modes.ensure(std::max<size_t>(1, (size_t)n_clouds * std::max(1u, n_adaptive)))) != CLDN_HIP_OK)
     return rc;
-  // Framed calls whose first launch is the piece kernel: that launch zeroes what the call needs zeroed of the block (FusedArgs::clear:
-  // status block, anchors, flags, the segment entries its workgroups do not write) -- the memset was a launch and a dependent
-  // boundary on the stream in front of every call. Every other path keeps it: the generic, fixed and WIDE kernels, chunk tables
-  // (intra placement), LZ4 calls (second anchor array), a Gorilla pre-pass in front of the piece kernel, n_chunks == 0, and the
-  // one call that got a new allocation.
-  const bool kernel_clears = pieces && !intra && !table && !lz4 && plan.n_gorilla == 0u && c->d_status.cap == status_cap_before;
-  if (!kernel_clears) HIP_TRY(hipMemsetAsync(c->d_status.p, 0, z_bytes, c->stream));
+  // Framed calls whose first launch is the piece kernel: that launch zeroes what the call needs zeroed of the block (FusedArgs::clear)
+  // -- the memset was a launch and a dependent boundary on the stream in front of every call. The route says which calls those
+  // are; the one that got a new allocation (known only here: the block's size follows from the route) keeps the memset too.
+  R.kernel_clears = R.kernel_clears && c->d_status.cap == status_cap_before;
+  if (!R.kernel_clears) HIP_TRY(hipMemsetAsync(c->d_status.p, 0, z_bytes, c->stream));
   // a batch without a single point launches no probe: its clouds commit mode 0 (DeltaVarint), like an encode() call of
   // the reference that never reaches the analysis (src/v5_codec.cpp:934-949)
   if (n_chunks == 0 && n_clouds && n_adaptive) HIP_TRY(hipMemsetAsync(c->d_modes.p, 0, (size_t)n_clouds * n_adaptive, c->stream));
@@ -1085,6 +1100,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
       // (gather: every cloud straight from its own buffer to its place in the batch)
       if ((rc = stage_host_input(c, points, cloud_ptrs, cloud_points, n_clouds, step, n_points * step)) != CLDN_HIP_OK) return rc;
       d_points = (const uint8_t*)c->d_in.p;
+      if ((uintptr_t)d_points & 3u) return fail(CLDN_HIP_ERR_DEVICE, "staging buffer is not 4-byte aligned");  // the route assumed it is
     }
     if (out_loc == CLDN_HIP_HOST && !table) {
       if ((rc = c->d_out.ensure((size_t)need)) != CLDN_HIP_OK) return rc;
@@ -1100,6 +1116,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   EncodeLaunch L;
   memset(&L, 0, sizeof(L));
   L.plan = &plan;
+  L.route = &R;
   L.stream = c->stream;
   L.points = d_points;
   L.points_end = d_points + (size_t)n_points * step;
@@ -1108,13 +1125,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   L.n_clouds = n_clouds;
   L.cloud_first_chunk = (const uint32_t*)c->d_cloud_first.p;
   L.slots = (uint8_t*)c->d_slots.p;
-  L.slot_stride = slot_stride;
-  L.reg_stride = reg_stride;
-  L.subs = subs;
-  L.sub_points = sub_points;
-  L.sub_stride = sub_stride;
   L.segs = (Seg*)((uint8_t*)c->d_status.p + z_segs);
-  L.segs_per_chunk = segs_per_chunk;
   for (uint32_t a = 0; a < plan.n_adaptive; ++a) {
     L.cols.p[a] = (uint8_t*)c->d_cols[a].p;
     L.ranks[a] = (uint16_t*)c->d_ranks[a].p;
@@ -1137,27 +1148,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   if (direct_offsets) L.stream_offsets = stream_offsets;
   if (direct_sizes) L.chunk_payload = chunk_sizes;
   L.modes = (uint8_t*)c->d_modes.p;
-  L.modes_forced = false;
-  if (!wide && c->last_modes_count && c->ev_last_modes && hipEventQuery(c->ev_last_modes) == hipSuccess) {
-    // a copy of an earlier call's modes has landed: it becomes the hint until a newer one lands
-    const uint8_t* lm = (const uint8_t*)c->h_last_modes.p;
-    const uint32_t nf = c->last_modes_fields;
-    for (uint32_t a = 0; a < (uint32_t)kMaxAdaptive; ++a) c->hint_cache[a] = 0;
-    for (size_t k = 0; k < c->last_modes_count; ++k) {
-      const uint8_t m = lm[k];
-      c->hint_cache[k % nf] |= (m <= 3u) ? (uint8_t)(1u << m) : (uint8_t)0xF;
-    }
-    c->hint_valid = true;
-    c->last_modes_count = 0;
-  }
-  for (uint32_t a = 0; a < (uint32_t)kMaxAdaptive; ++a) L.mode_hint[a] = c->hint_valid ? c->hint_cache[a] : (uint8_t)0xF;
-  const bool per_cloud = c->forced_clouds != 0u;  // (then forced_clouds == n_clouds)
-  if ((!c->forced_modes.empty() || per_cloud) && n_adaptive && n_clouds) {
-    for (uint32_t a = 0; a < plan.n_adaptive; ++a) {
-      uint8_t hint = per_cloud ? (uint8_t)0 : (uint8_t)(1u << c->forced_modes[a]);
-      for (uint32_t k = 0; per_cloud && k < n_clouds; ++k) hint |= (uint8_t)(1u << c->forced_cloud_modes[(size_t)k * n_adaptive + a]);
-      L.mode_hint[a] = hint;
-    }
+  if (F.modes_forced) {
     HIP_TRY(hipStreamSynchronize(c->stream));  // the previous call's upload from h_modes has to be over
     if ((rc = c->h_modes.ensure((size_t)n_clouds * n_adaptive)) != CLDN_HIP_OK) return rc;
     if (per_cloud) memcpy(c->h_modes.p, c->forced_cloud_modes.data(), (size_t)n_clouds * n_adaptive);
@@ -1165,13 +1156,9 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
       memcpy((uint8_t*)c->h_modes.p + (size_t)k * n_adaptive, c->forced_modes.data(), n_adaptive);
     HIP_TRY(hipMemcpyAsync(c->d_modes.p, c->h_modes.p, (size_t)n_clouds * n_adaptive, hipMemcpyHostToDevice,
                            c->stream));
-    L.modes_forced = true;
   }
   L.fallback_flags = (uint8_t*)c->d_status.p + z_flags;
-  L.kernel_clears = kernel_clears;
-  // device-resident outputs: the probe workgroups of the piece kernel write the caller's modes array as well (a byte store
-  // fits any address); where another kernel decides the modes, or the caller forced them, the copy behind the call stays
-  L.caller_modes = (out_loc == CLDN_HIP_DEVICE && !lz4 && !table && !L.modes_forced) ? modes : nullptr;
+  L.caller_modes = caller_modes;
   L.fin_rec = (unsigned long long*)c->d_finrec.p;
   L.fin_rec2 = L.fin_rec + n_chunks;
   L.fin_anchor = (unsigned long long*)((uint8_t*)c->d_status.p + z_anchor);
@@ -1180,12 +1167,10 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   L.use_ticket = c->force_ticket ? 1u : 0u;
   L.test_timeout = c->test_timeout_once ? 1u : 0u;  // test hook (cldn_hip_debug_finish_timeout_once): this attempt reports a timeout
   c->test_timeout_once = false;
-  L.chunks_only = table != nullptr;
   L.contiguous_flag = (uint32_t*)c->d_status.p + 42;
-  if (pieces) {
+  if (R.regular == ER_PIECES) {
     L.pieces = (const PieceDesc*)c->d_pieces.p;
     L.n_pieces = c->n_pieces;
-    L.intra = intra;
     L.wgrec = L.fin_rec2 + n_chunks;
   }
   L.out = lz4 ? (uint8_t*)c->d_s1.p : d_outp;
@@ -1194,8 +1179,8 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   const size_t n_slots = c->slot_valid.size();
   const size_t slot = n_slots ? (size_t)(c->call_index % n_slots) : 0;
   L.events = n_slots ? &c->events[slot * 5] : nullptr;
-  bool modes_in_place = false;  // the kernels wrote the caller's modes array
-  rc = stage1_launch_encode(L, &modes_in_place);
+  const bool modes_in_place = R.writes_caller_modes;  // the kernels write the caller's modes array
+  rc = stage1_launch_encode(L);
   if (rc != CLDN_HIP_OK) return rc;
   const void* d_sizes = c->d_payload.p;  // what chunk_sizes reports
   if (lz4 && n_chunks) {
@@ -1724,8 +1709,11 @@ int cldn_hip_codec_pipeline(cldn_hip_codec_t* c, int mode, const void* points) {
   if (mode < 0 || mode > 2) return fail(CLDN_HIP_ERR_ARG, "pipeline mode %d out of range", mode);
   c->pipeline = mode;
   const uint8_t* p = (const uint8_t*)points;
-  if (mode == 1 || stage1_piece_points(c->plan.dev, p) == 0u) return 1;
-  return 2;
+  EncodeFacts F = {};
+  F.pipeline = (uint8_t)mode;
+  F.wide = c->plan.wide;
+  F.points_misaligned = (uint8_t)((uintptr_t)p & 3u);
+  return encode_route(c->plan.dev, F).piece_pts ? 2 : 1;
 }
 
 int cldn_hip_codec_force_modes(cldn_hip_codec_t* c, const uint8_t* modes, uint32_t n_modes) {

@@ -28,18 +28,6 @@ namespace cldn {
 namespace {
 int hip_fail(hipError_t e, const char* what) { return launch_fail(e, what); }
 
-// one launch, checked: the error text names the kernel
-template <class Kernel, class... Args>
-int launch(const char* name, Kernel kernel, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream, const Args&... args) {
-  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CLDN_HIP_OK : launch_fail(e, name);
-}
-#define TRY_LAUNCH(...)                                      \
-  do {                                                       \
-    if (const int rc_ = launch(__VA_ARGS__)) return rc_;     \
-  } while (0)
-
 // k_decode_points_w, one entry per kPointsVariants[] (stage1_decode_route.h): the kernels of the chained launch (pass[0]) and
 // of the two SPLIT passes around `carry` (pass[1], pass[2]). lds: every pass's dynamic LDS
 using PointsKernel = void (*)(DevPlan, const uint8_t*, const DecChunk*, uint8_t*, uint32_t*, uint8_t*, uint32_t, uint32_t*,

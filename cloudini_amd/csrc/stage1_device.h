@@ -3,7 +3,14 @@
 
 #include <stdint.h>
 
+#if defined(__HIPCC__) || __has_include(<hip/hip_runtime.h>)
 #include <hip/hip_runtime.h>
+#else
+// A host-only build of the route headers without the HIP headers (tests/test_encode_route.py): the token buffers are only
+// pointed at. Under HIP uint4 is a typedef, not a struct: this declaration must never meet the HIP headers in one translation
+// unit -- whoever includes them does so in front of this header, or has them on the include path.
+struct uint4;
+#endif
 
 namespace cldn {
 

@@ -15,30 +15,15 @@
 // results).
 #pragma once
 
+#include "stage1_encode_route.h"
+
 namespace cldn {
 
-constexpr uint32_t kRowPts = 63;          // new points per wave row (lane 0 holds the point before them)
-constexpr uint32_t kFusedWaves = 4;       // pieces per workgroup (all of one chunk: piece counts are padded to 4)
-constexpr uint32_t kFusedThreads = kFusedWaves * 64;
-
-__host__ __device__ constexpr uint32_t fused_piece_rows(int lanes) { return lanes == 3 ? 8u : 6u; }
-__host__ __device__ constexpr uint32_t fused_piece_points(int lanes) { return fused_piece_rows(lanes) * kRowPts; }
-// LDS bytes of one wave's stream region: worst case 5 bytes per token + slack for the aligned 16-byte reads of the
-// copy-out
+// (kRowPts, kFusedWaves, kFusedThreads, fused_piece_points, the small / TAIL region sizes: stage1_encode_route.h)
+// LDS bytes of one wave's stream region sized for the worst case, 5 bytes per token, + slack for the aligned 16-byte reads of
+// the copy-out
 __host__ __device__ constexpr uint32_t fused_region_bytes(int lanes) {
   return ((fused_piece_points(lanes) * 5u * (uint32_t)lanes + 15u) & ~15u) + 32u;
-}
-// Round 5: the instantiations without a TAIL op size the region for 3 bytes per token (18.3 KB per workgroup instead of 30.4:
-// more workgroups per CU). A piece whose tokens do not fit -- deltas of 2^20 ticks and more on average, i.e. noise over
-// kilometres at 1 mm -- is written by fused_slow_piece straight from the input instead (same bytes, slowly).
-__host__ __device__ constexpr uint32_t fused_region_cap_small(int lanes) {
-  return (fused_piece_points(lanes) * 3u * (uint32_t)lanes + 15u) & ~15u;
-}
-__host__ __device__ constexpr uint32_t fused_region_bytes_small(int lanes) { return fused_region_cap_small(lanes) + 32u; }
-// ... with one more token of up to kTailMaxBytes behind the FloatN tokens of every point (TAIL instantiations)
-constexpr uint32_t kTailMaxBytes = 10;  // varint of an int64 delta, Gorilla token (13 + 64 bits), raw 8 bytes
-__host__ __device__ constexpr uint32_t fused_region_bytes_tail(int lanes) {
-  return ((fused_piece_points(lanes) * (5u * (uint32_t)lanes + kTailMaxBytes) + 15u) & ~15u) + 32u;
 }
 
 // ceil(bits / 7) for bits < 2^16 on the full-rate 24-bit multiply-add (groups7's 32-bit product becomes a v_mad_u64_u32,

@@ -18,9 +18,12 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <array>
 #include <type_traits>
+#include <utility>
 
 #include "stage1_device.h"
+#include "stage1_encode_route.h"
 #include "stage1_math.h"
 #include "stage1_prims.h"
 
@@ -1264,7 +1267,6 @@ __device__ __forceinline__ SecLds sec_lds_carve(uint8_t* smem) {
 // that take the (chunk, field) pairs round robin (round 6: the kernel's 119 KB of LDS allow one workgroup per CU anyway, and
 // with the fused Palette nearly every pair is a check and nothing else: a thousand 1024-thread workgroups that return at
 // once cost 8 us of dispatch on the 32-cloud batch)
-constexpr uint32_t kSecGrid = 256;
 __global__ __launch_bounds__(kSecThreads) void k_encode_sections(const DevPlan plan, const ChunkDesc* __restrict__ chunks,
                                                                  const ColumnPtrs cols, const uint8_t* __restrict__ modes,
                                                                  uint8_t* __restrict__ slots, uint64_t slot_stride,
@@ -1345,120 +1347,39 @@ struct RegularKernel {
 const RegularKernel kRegularKernels[] = {{regular_lds(kWidePointStep), k_encode_regular<kRegularThreads, false>},
                                          {kRegularLdsMax, k_encode_regular<kRegularThreads, true>}};
 
-// k_encode_fused, the piece kernel (stage1_fused.h), one entry per layout it takes. LANES: fused float lanes; LOADW: dwords
-// loaded per point; UNAL: points that are not 4-byte aligned (odd point_step / offset / base, e.g. packed 18-byte points):
-// every lane loads LOADW + 1 dwords from the aligned address below its point and realigns them with v_alignbyte; L3: dword
-// (behind the first lane) of the fourth lane -- 3 for x y z w back to back, 4 for the PCL / Ouster layout
-// "x y z <pad> intensity" (the fused encoder takes any four offsets, src/field_encoder.cpp:24-40); TAIL: one more op behind
-// the lanes. lds: the four piece regions (a launch that also probes 32-bit fields raises it to the probe's hash table)
-struct FusedKernel {
-  int lanes, loadw;
-  bool unal;
-  int l3;
-  bool tail;
-  uint32_t lds;
-  void (*kernel)(DevPlan, FusedArgs);
-};
+// k_encode_fused, the piece kernel (stage1_fused.h): the instantiation of every kFusedVariants[] entry, at its position
+// (stage1_encode_route.h describes the layouts and picks one)
+using FusedKernel = void (*)(DevPlan, FusedArgs);
 template <int LANES, int LOADW, bool UNAL, int L3, bool TAIL = false>
 constexpr FusedKernel fused_kernel() {
-  const uint32_t lds = 16u + kFusedWaves * (TAIL ? fused_region_bytes_tail(LANES) : fused_region_bytes_small(LANES));
   // instantiations without a TAIL op that prefetch at most 5 dwords per point: the 64-VGPR kernel (8 waves per SIMD)
-  if constexpr (!TAIL && LOADW <= 5) return {LANES, LOADW, UNAL, L3, TAIL, lds, k_encode_fused_w8<LANES, LOADW, UNAL, L3>};
-  else return {LANES, LOADW, UNAL, L3, TAIL, lds, k_encode_fused<LANES, LOADW, UNAL, L3, TAIL>};
+  if constexpr (!TAIL && LOADW <= 5) return k_encode_fused_w8<LANES, LOADW, UNAL, L3>;
+  else return k_encode_fused<LANES, LOADW, UNAL, L3, TAIL>;
 }
-const FusedKernel kFusedKernels[] = {
-    fused_kernel<3, 3, false, 3>(),       fused_kernel<3, 4, false, 3>(),       fused_kernel<3, 8, false, 3>(),
-    fused_kernel<4, 4, false, 3>(),       fused_kernel<4, 8, false, 3>(),       fused_kernel<4, 8, false, 4>(),
-    fused_kernel<3, 4, true, 3>(),        fused_kernel<3, 8, true, 3>(),        fused_kernel<4, 5, true, 3>(),
-    fused_kernel<4, 8, true, 3>(),        fused_kernel<3, 4, false, 3, true>(), fused_kernel<3, 8, false, 3, true>(),
-    fused_kernel<4, 8, false, 3, true>(), fused_kernel<4, 8, false, 4, true>(), fused_kernel<3, 4, true, 3, true>(),
-    fused_kernel<3, 8, true, 3, true>(),  fused_kernel<4, 8, true, 3, true>()};
+template <int V>
+constexpr FusedKernel fused_kernel_at() {
+  constexpr FusedVariant v = kFusedVariants[V];
+  return fused_kernel<v.lanes, v.loadw, v.unal, v.l3, v.tail>();
+}
+template <int... V>
+constexpr std::array<FusedKernel, sizeof...(V)> fused_kernels(std::integer_sequence<int, V...>) {
+  return {fused_kernel_at<V>()...};
+}
+const auto kFusedKernels = fused_kernels(std::make_integer_sequence<int, kFusedVariantCount>{});
 
-// k_finish (stage1_finish.h): `threads` per workgroup; bpv 0 (framing only), 2 or 4 (also the Palette section of one
-// 16- or 32-bit field, in the LDS of a Pal32)
-struct FinishKernel {
-  uint32_t threads, bpv, lds;
-  void (*kernel)(FinishArgs);
-};
-template <int T, int FUSE_BPV>
-constexpr FinishKernel finish_kernel() {
-  return {T, FUSE_BPV, FUSE_BPV == 0 ? 0u : (FUSE_BPV == 2 ? Pal32<uint16_t>::kLds : Pal32<uint32_t>::kLds), k_finish<T, FUSE_BPV>};
+// k_finish (stage1_finish.h): the instantiation of every kFinishVariants[] entry, at its position
+template <int V>
+constexpr auto finish_kernel_at() {
+  return k_finish<(int)kFinishVariants[V].threads, (int)kFinishVariants[V].bpv>;
 }
-const FinishKernel kFinishKernels[] = {finish_kernel<256, 0>(), finish_kernel<512, 2>(), finish_kernel<512, 4>(),
-                                       finish_kernel<1024, 2>(), finish_kernel<1024, 4>()};
-const FinishKernel* finish_variant(uint32_t threads, uint32_t bpv) {
-  for (const FinishKernel& k : kFinishKernels)
-    if (k.threads == threads && k.bpv == bpv) return &k;
-  return nullptr;
+template <int... V>
+constexpr std::array<void (*)(FinishArgs), sizeof...(V)> finish_kernels(std::integer_sequence<int, V...>) {
+  return {finish_kernel_at<V>()...};
 }
-
-// The piece kernel's layouts: the regular stream is one fused 3/4-lane float encoder, optionally followed by one more op.
-// Lanes of the fused FloatN encoder (0 = none); *l3 = dword of the fourth lane; *tail: index of ONE more regular op behind
-// the lanes that the piece kernel can append to every point (raw copy, scalar lossy float, Gorilla token), -1 if there is
-// none
-int floatn_lanes(const DevPlan& p, int* l3, int* tail) {
-  *l3 = 3;
-  *tail = -1;
-  uint32_t lanes = 0;
-  while (lanes < p.n_ops && lanes < 4u && p.ops[lanes].kind == OP_QF32) ++lanes;
-  if (lanes != 3u && lanes != 4u) return 0;
-  if (p.n_ops != lanes) {
-    if (p.n_ops != lanes + 1u) return 0;
-    const uint32_t k = p.ops[lanes].kind;
-    // (XOR fields only exist in lossless schemas, which have no FloatN lanes)
-    if (k != OP_COPY && k != OP_LOSSY_F32 && k != OP_LOSSY_F64 && k != OP_GORILLA64) return 0;
-    if (p.ops[lanes].size > 8u || p.ops[lanes].offset < p.ops[0].offset) return 0;
-    *tail = (int)lanes;
-  }
-  for (uint32_t k = 0; k < lanes; ++k) {
-    if (k < 3u && p.ops[k].offset != p.ops[0].offset + 4u * k) return 0;
-  }
-  if (lanes == 4u) {
-    if (p.ops[3].offset == p.ops[0].offset + 16u) *l3 = 4;
-    else if (p.ops[3].offset != p.ops[0].offset + 12u) return 0;
-  }
-  return (int)lanes;
-}
-
-bool floatn_unaligned(const DevPlan& p, const uint8_t* points) {
-  return (p.point_step & 3u) || (p.ops[0].offset & 3u) || ((uintptr_t)points & 3u);
-}
-
-// dwords to load per point so that every adaptive-int field (and the tail op's field) is covered by the point load
-// (0 = not possible)
-int floatn_loadw(const DevPlan& p, int lanes, bool unal, int l3, int tail) {
-  const uint32_t off0 = p.ops[0].offset;
-  // bytes behind off0 the tail needs; an unaligned 8-byte field is read from three dwords
-  uint32_t tail_need = 0;
-  if (tail >= 0) {
-    const uint32_t rel = p.ops[tail].offset - off0;
-    tail_need = ((rel >> 2) + (p.ops[tail].size > 4u || (rel & 3u) + p.ops[tail].size > 4u ? ((rel & 3u) ? 3u : 2u) : 1u)) * 4u;
-  }
-  if (l3 == 4) return (!unal && off0 + 32u <= p.point_step && tail_need <= 32u) ? 8 : 0;  // one variant: aligned, 8 dwords
-  if (p.n_adaptive == 0 && tail < 0) return unal && lanes == 3 ? 4 : lanes;
-  uint32_t need = std::max((uint32_t)lanes * 4u, tail_need);
-  for (uint32_t a = 0; a < p.n_adaptive; ++a) {
-    const DevAdaptive& f = p.adaptive[a];
-    // fields the point load cannot deliver: the aligned kernels then read every field directly (loadw == lanes);
-    // the unaligned instantiations have no such mode -> 0 = generic kernel
-    if (f.offset < off0) return (unal || tail >= 0) ? 0 : lanes;
-    if (f.bpv == 8u && ((f.offset - off0) & 3u)) return (unal || tail >= 0) ? 0 : lanes;
-    need = std::max(need, f.offset - off0 + f.bpv);
-  }
-  const int w = (int)((need + 3u) / 4u);
-  if (tail >= 0) {  // TAIL instantiations: (3: 4, 8), (4: 8), aligned and unaligned
-    if (w > 8) return 0;
-    return (lanes == 3 && w <= 4) ? 4 : 8;  // (an aligned layout whose point is shorter takes the guarded UNAL variant)
-  }
-  if (unal) {  // realigned dword loads may reach into the next point; variants: (3: 4, 8), (4: 5, 8)
-    if (w > 8) return 0;
-    if (lanes == 3) return w <= 4 ? 4 : 8;
-    return w <= 5 ? 5 : 8;
-  }
-  const int loadw = w <= lanes ? lanes : (w <= 4 ? 4 : (w <= 8 ? 8 : 0));
-  if (loadw == 0 || off0 + (uint32_t)loadw * 4u > p.point_step) return lanes;  // would read past the point
-  return loadw;
-}
+const auto kFinishKernels = finish_kernels(std::make_integer_sequence<int, kFinishVariantCount>{});
+// the LDS sizes the route header carries as plain numbers
+static_assert(kPal16Lds == Pal32<uint16_t>::kLds && kPal32Lds == Pal32<uint32_t>::kLds, "kFinishVariants[].lds, k_section_palette32");
+static_assert(kProbeLdsBytes == kProbeLds, "k_probe_fast, k_wide_probe");
 
 int hip_fail(hipError_t e, const char* what) { return launch_fail(e, what); }
 }  // namespace
@@ -1467,10 +1388,10 @@ int stage1_configure_kernels() {
   hipError_t e;
   for (const RegularKernel& k : kRegularKernels)
     if ((e = allow_lds(k.kernel, k.lds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_regular)");
-  for (const FusedKernel& k : kFusedKernels)
-    if ((e = allow_lds(k.kernel, k.lds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_fused)");
-  for (const FinishKernel& k : kFinishKernels)
-    if ((e = allow_lds(k.kernel, k.lds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_finish)");
+  for (int v = 0; v < kFusedVariantCount; ++v)
+    if ((e = allow_lds(kFusedKernels[v], fused_launch_lds(kFusedVariants[v]))) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_fused)");
+  for (int v = 0; v < kFinishVariantCount; ++v)
+    if ((e = allow_lds(kFinishKernels[v], kFinishVariants[v].lds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_finish)");
   if ((e = allow_lds(&k_encode_sections, kSecLdsTotal)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_encode_sections)");
   if ((e = allow_lds(&k_probe_fast, kProbeLds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_probe_fast)");
   if ((e = allow_lds(&k_wide_probe, kProbeLds)) != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(k_wide_probe)");
@@ -1479,429 +1400,27 @@ int stage1_configure_kernels() {
   return stage1_configure_decode();
 }
 
-// ---- single-pass encoder ----
-namespace {
-struct FusedVariant {
-  const FusedKernel* k;
-  int tail;  // index of the op appended behind the lanes, -1 = none
-};
-// the piece kernel takes the plan when kFusedKernels holds an instantiation for its layout
-bool fused_variant(const DevPlan& p, const uint8_t* points, FusedVariant* v) {
-  int l3 = 3, tail = -1;
-  const int lanes = floatn_lanes(p, &l3, &tail);
-  if (!lanes) return false;
-  bool unal = floatn_unaligned(p, points);
-  const int loadw = floatn_loadw(p, lanes, unal, l3, tail);
-  if (loadw == 0) return false;
-  // TAIL on an aligned layout whose loaded dwords reach into the next point: the UNAL instantiation (aligned dwords +
-  // realignment, here by 0 bytes) has the guard for the last points of the batch
-  if (tail >= 0 && !unal && l3 != 4 && p.ops[0].offset + (uint32_t)loadw * 4u > p.point_step) unal = true;
-  for (const FusedKernel& k : kFusedKernels) {
-    if (k.lanes == lanes && k.loadw == loadw && k.unal == unal && k.l3 == l3 && k.tail == (tail >= 0)) {
-      v->k = &k;
-      v->tail = tail;
-      return true;
-    }
-  }
-  return false;
-}
-}  // namespace
-
-uint32_t stage1_piece_points(const DevPlan& plan, const uint8_t* points) {
-  FusedVariant v;
-  if (!fused_variant(plan, points, &v)) return 0u;
-  return fused_piece_points(v.k->lanes);
-}
-
-// the piece kernel takes this plan and its tail op is the Gorilla field: points per piece, else 0
-uint32_t stage1_gorilla_inline_piece_points(const DevPlan& plan, const uint8_t* points) {
-  FusedVariant v;
-  if (!fused_variant(plan, points, &v) || v.tail < 0 || plan.ops[v.tail].kind != OP_GORILLA64) return 0u;
-  return fused_piece_points(v.k->lanes);
-}
-
-uint32_t stage1_piece_slot_stride(const DevPlan& plan, const uint8_t* points) {
-  FusedVariant v;
-  if (!fused_variant(plan, points, &v)) return 0u;
-  const uint32_t per_point = 5u * (uint32_t)v.k->lanes + (v.tail >= 0 ? kTailMaxBytes : 0u);  // worst case, 5 bytes per token
-  return (fused_piece_points(v.k->lanes) * per_point + 255u) & ~255u;
-}
-
-static int launch_fused(const EncodeLaunch& L, hipStream_t stream, uint32_t piece0, uint32_t piece1, bool* probed) {
-  FusedVariant v;
-  if (!fused_variant(*L.plan, L.points, &v)) return launch_fail(hipErrorInvalidValue, "k_encode_fused (no variant)");
-  FusedArgs A;
-  A.points = L.points;
-  A.points_end = L.points_end;
-  A.pieces = L.pieces + piece0;
-  A.cols = L.cols;
-  A.slots = L.slots;
-  A.slot_stride = L.slot_stride;
-  A.piece_stride = L.sub_stride / kFusedWaves;  // sub_stride = one workgroup's range (4 pieces)
-  A.segs = L.segs;
-  A.segs_per_chunk = L.segs_per_chunk;
-  // mode probe next to the pieces: fields of 2 and 4 bytes (the distinct-value structure has to fit the launch's LDS)
-  bool probe_here = piece0 == 0u && L.plan->n_adaptive != 0u && !L.modes_forced && L.n_clouds != 0u &&
-                    (uint64_t)L.n_clouds * L.plan->n_adaptive < (1u << 20);
-  for (uint32_t a = 0; a < L.plan->n_adaptive && probe_here; ++a) probe_here = L.plan->adaptive[a].bpv <= 4u;
-  A.n_probe = probe_here ? L.n_clouds * L.plan->n_adaptive : 0u;
-  A.chunks = L.chunks;
-  A.cloud_first_chunk = L.cloud_first_chunk;
-  A.modes = L.modes;
-  A.intra = L.intra ? 1u : 0u;
-  A.epoch = L.fin_epoch;
-  A.wgrec = L.wgrec;
-  A.status = L.status;
-  A.clear = (L.kernel_clears && !L.intra && piece0 == 0u && piece1 == L.n_pieces) ? 1u : 0u;
-  A.n_anchor = L.n_chunks / 1024u + 1u;
-  A.anchor = L.fin_anchor;
-  A.flags = L.fallback_flags;
-  A.tail_kind = 0u;
-  A.tail_rel = 0u;
-  A.tail_size = 0u;
-  A.tail_windows = nullptr;
-  if (v.tail >= 0) {
-    const DevOp& top = L.plan->ops[v.tail];
-    A.tail_kind = top.kind;
-    A.tail_rel = top.offset - L.plan->ops[0].offset;
-    A.tail_size = top.size;
-    if (top.kind == OP_GORILLA64) A.tail_windows = reinterpret_cast<const uint16_t*>(L.pre.p[top.type]);
-  }
-  uint32_t lds = v.k->lds;
-  // the probe workgroups of the launch share its LDS size: a 16-bit field needs its 8 KiB value bitmap, a 32-bit field a
-  // hash table of 6144 slots (24.8 KB: above the 18.3 KB of four 3-byte-per-token regions -- such launches keep 6
-  // workgroups per CU instead of 8)
-  if (A.n_probe) {
-    bool wide = false;
-    for (uint32_t a = 0; a < L.plan->n_adaptive; ++a) wide = wide || L.plan->adaptive[a].bpv == 4u;
-    if (wide) lds = std::max(lds, 6144u * 4u + 272u);
-  }
-  A.probe_lds = lds;
-  A.modes_out = A.n_probe ? L.caller_modes : nullptr;
-  if (probed) *probed = A.n_probe != 0u;
-  const dim3 grid(A.n_probe + (piece1 - piece0) / kFusedWaves), block(kFusedThreads);
-  hipLaunchKernelGGL(v.k->kernel, grid, block, lds, stream, *L.plan, A);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "k_encode_fused");
-  return CLDN_HIP_OK;
-}
-
-// section kernels of chunks [c0, c1) on `stream` (per-chunk tables are passed shifted to c0; columns, modes and the
-// chunk descriptors' point indexes are batch-global)
-static int launch_sections(const EncodeLaunch& L, hipStream_t stream, uint32_t c0, uint32_t c1, uint32_t fused_field) {
-  hipError_t e;
-  const uint32_t na = L.plan->n_adaptive;
-  const uint32_t nch = c1 - c0;
-  if (!na || !nch) return CLDN_HIP_OK;
-  const ChunkDesc* chunks = L.chunks + c0;
-  uint8_t* slots = L.slots + (size_t)c0 * L.slot_stride;
-  Seg* segs = L.segs + (size_t)c0 * L.segs_per_chunk;
-  uint8_t* flags = L.fallback_flags + (size_t)c0 * na;
-  ColumnPtrs rank_cols;
-  for (int a = 0; a < kMaxAdaptive; ++a) rank_cols.p[a] = reinterpret_cast<uint8_t*>(L.ranks[a]);
-  // One launch per kernel type covers all the fields of that type (grid.y): the fields are independent and every one of
-  // these kernels is latency-bound at one workgroup per chunk, so a schema with five integer channels gets five times
-  // the workgroups in flight instead of five launches in a row.
-  SectionFields run16, run32, pal16, pal32, pal64;
-  run16.n = run32.n = pal16.n = pal32.n = pal64.n = 0u;
-  for (uint32_t a = 0; a < na; ++a) {
-    const uint32_t bpv = L.plan->adaptive[a].bpv;
-    const uint32_t hint = L.mode_hint[a];
-    if (hint & 0xDu) {  // DeltaVarint / Rle / DeltaRle expected somewhere
-      if (bpv == 2u) run16.a[run16.n++] = (uint8_t)a;
-      else if (bpv == 4u) run32.a[run32.n++] = (uint8_t)a;
-    }
-    if ((hint & 0x2u) && a != fused_field) {
-      if (bpv == 2u) pal16.a[pal16.n++] = (uint8_t)a;
-      else if (bpv == 4u) pal32.a[pal32.n++] = (uint8_t)a;
-      else pal64.a[pal64.n++] = (uint8_t)a;
-    }
-  }
-  // one adaptive field + one regular segment per chunk (intra-chunk placement): the section goes right behind the regular
-  // stream, so that the chunk's payload is one contiguous run of its slot
-  const uint32_t append = (L.intra && na == 1u && L.subs == 1u) ? 1u : 0u;
-#define SEC_ARGS(FL) *L.plan, FL, chunks, L.cols, L.modes, slots, L.slot_stride, L.reg_stride, segs, L.segs_per_chunk, L.subs, flags, append
-  {
-    SectionFields runs;  // every 2- and 4-byte field that may be DeltaVarint / Rle / DeltaRle somewhere: one launch
-    runs.n = 0u;
-    for (uint32_t k = 0; k < run16.n; ++k) runs.a[runs.n++] = run16.a[k];
-    for (uint32_t k = 0; k < run32.n; ++k) runs.a[runs.n++] = run32.a[k];
-    if (runs.n) hipLaunchKernelGGL(k_section_fast, dim3(nch, runs.n), dim3(kS2Threads), kD32Lds, stream, SEC_ARGS(runs));
-  }
-  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_section_fast");
-  // 512-thread workgroups (two bitmap words and two groups of 32 values per thread): four of them fit a CU, so a batch of
-  // up to 1024 chunks is one generation (C2: sections 0.066 ms with 1024 threads, 0.062 ms with 512)
-  if (pal16.n)
-    hipLaunchKernelGGL((k_section_palette32<uint16_t, 512>), dim3(nch, pal16.n), dim3(512), Pal32<uint16_t>::kLds, stream, SEC_ARGS(pal16), rank_cols, L.status);
-  if (pal32.n)
-    hipLaunchKernelGGL((k_section_palette32<uint32_t, 512>), dim3(nch, pal32.n), dim3(512), Pal32<uint32_t>::kLds, stream, SEC_ARGS(pal32), rank_cols, L.status);
-  if (pal64.n)
-    hipLaunchKernelGGL(k_section_palette<uint64_t>, dim3(nch, pal64.n), dim3(kS2Threads), kS2PalLds, stream, SEC_ARGS(pal64));
-#undef SEC_ARGS
-  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_section_palette");
-  hipLaunchKernelGGL(k_encode_sections, dim3(std::min<uint32_t>(nch * na, kSecGrid)), dim3(kSecThreads), kSecLdsTotal, stream, *L.plan, chunks, L.cols,
-                     L.modes, slots, L.slot_stride, L.reg_stride, segs, L.segs_per_chunk, rank_cols, L.subs, flags, fused_field, nch);
-  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_encode_sections");
-  return CLDN_HIP_OK;
-}
-
-constexpr uint32_t kNoFusedField = 0xffffffffu;
-
-// bytes per point of a regular stream made of fixed-size encoders only (XOR-coded floats, raw copies), 0 otherwise
-static uint32_t fixed_point_bytes(const DevPlan& P) {
-  if (P.n_ops == 0u || P.n_gorilla != 0u) return 0u;
-  uint32_t bytes = 0u;
-  for (uint32_t k = 0; k < P.n_ops; ++k) {
-    const uint32_t kd = P.ops[k].kind;
-    if (kd != OP_COPY && kd != OP_XOR32 && kd != OP_XOR64) return 0u;
-    bytes += P.ops[k].size;
-  }
-  return bytes;
-}
-
 size_t stage1_wide_scratch_bytes() { return kWideScratchBytes; }
 
-// WIDE route (stage1_wide.h): Gorilla pre-pass in groups, mode probe, one workgroup per chunk, framing
-static int launch_encode_wide(const EncodeLaunch& L) {
-  hipError_t e;
-  const WidePlan& W = *L.wide;
-  if (L.events) {
-    (void)hipEventRecord(L.events[0], L.stream);
-    (void)hipEventRecord(L.events[1], L.stream);
-  }
-  if (L.n_chunks) {
-    if (W.n_gorilla) {
-      // k_gorilla_tokens finds "the blockIdx.y-th Gorilla op of the plan": a plan of at most kMaxOps such ops per launch
-      DevPlan mini;
-      mini = DevPlan{};
-      mini.point_step = W.point_step;
-      uint32_t g0 = 0u;
-      for (uint32_t k = 0; k <= W.n_ops; ++k) {
-        if (k < W.n_ops && L.wide_ops_host[k].kind == OP_GORILLA64) mini.ops[mini.n_ops++] = L.wide_ops_host[k];
-        if (mini.n_ops == (uint32_t)kMaxOps || (k == W.n_ops && mini.n_ops != 0u)) {
-          mini.n_gorilla = mini.n_ops;
-          hipLaunchKernelGGL(k_gorilla_tokens, dim3(L.n_chunks, mini.n_ops), dim3(kGorThreads), 0, L.stream, mini, L.points, L.points_end,
-                             L.chunks, L.pre_out + g0);
-          if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_gorilla_tokens (wide)");
-          g0 += mini.n_ops;
-          mini.n_ops = 0u;
-        }
-      }
-    }
-    WideEncodeArgs A;
-    A.plan = W;
-    A.points = L.points;
-    A.points_end = L.points_end;
-    A.chunks = L.chunks;
-    A.cloud_first_chunk = L.cloud_first_chunk;
-    A.modes = L.modes;
-    A.slots = L.slots;
-    A.slot_stride = L.slot_stride;
-    A.segs = L.segs;
-    A.scratch = L.wide_scratch;
-    A.pre = L.wide_pre;
-    if (W.n_adaptive && !L.modes_forced) {
-      hipLaunchKernelGGL(k_wide_probe, dim3(L.n_clouds * W.n_adaptive), dim3(kS2Threads), kProbeLds, L.stream, A, L.n_clouds);
-      if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_wide_probe");
-    }
-    hipLaunchKernelGGL(k_wide_encode, dim3(L.n_chunks), dim3(kWideThreads), kSecLdsTotal, L.stream, A);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_wide_encode");
-  }
-  if (L.events) {
-    (void)hipEventRecord(L.events[2], L.stream);
-    (void)hipEventRecord(L.events[3], L.stream);
-  }
-  if (L.chunks_only) {
-    if (L.n_chunks) {
-      hipLaunchKernelGGL(k_chunk_sizes, dim3((L.n_chunks + 255u) / 256u), dim3(256), 0, L.stream, L.segs, 1u, L.n_chunks, L.chunk_payload,
-                         L.contiguous_flag);
-      if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_chunk_sizes (wide)");
-    }
-  } else {
-    FrameLaunch F;
-    F.stream = L.stream;
-    F.chunks = L.chunks;
-    F.n_chunks = L.n_chunks;
-    F.cloud_first_chunk = L.cloud_first_chunk;
-    F.n_clouds = L.n_clouds;
-    F.slots = L.slots;
-    F.slot_stride = L.slot_stride;
-    F.segs = L.segs;
-    F.segs_per_chunk = 1u;
-    F.rec = L.fin_rec;
-    F.anchor = L.fin_anchor;
-    F.epoch = L.fin_epoch;
-    F.ticket = L.fin_ticket;
-    F.use_ticket = L.use_ticket;
-    F.test_timeout = L.test_timeout;
-    F.chunk_payload = L.chunk_payload;
-    F.chunk_dst = L.chunk_dst;
-    F.stream_offsets = L.stream_offsets;
-    F.out = L.out;
-    F.out_capacity = L.out_capacity;
-    F.status = L.status;
-    const int rc = stage1_launch_frame(F);
-    if (rc != CLDN_HIP_OK) return rc;
-  }
-  if (L.events) (void)hipEventRecord(L.events[4], L.stream);
-  return CLDN_HIP_OK;
-}
-
-int stage1_launch_encode(const EncodeLaunch& L, bool* wrote_caller_modes) {
-  hipError_t e;
-  if (wrote_caller_modes) *wrote_caller_modes = false;
-  if (L.wide) return launch_encode_wide(L);
-  // the field whose Palette sections k_finish builds itself: the first 2- or 4-byte adaptive field that may commit Palette
-  uint32_t fused_field = kNoFusedField;
-  if (L.n_chunks && !L.chunks_only) {
-    for (uint32_t a = 0; a < L.plan->n_adaptive && fused_field == kNoFusedField; ++a)
-      if ((L.plan->adaptive[a].bpv == 2u || L.plan->adaptive[a].bpv == 4u) && (L.mode_hint[a] & 0x2u)) fused_field = a;
-  }
-  if (L.events) (void)hipEventRecord(L.events[0], L.stream);
-  uint32_t gor_piece_pts = 0u;  // the piece kernel encodes the Gorilla field itself: points per piece
-  bool modes_probed = false;    // the piece kernel's launch decided the adaptive-int modes
-  if (L.events) (void)hipEventRecord(L.events[1], L.stream);
-  gor_piece_pts = (L.n_chunks && L.pieces) ? stage1_gorilla_inline_piece_points(*L.plan, L.points) : 0u;
-  if (gor_piece_pts) {
-    const uint32_t opi = L.plan->n_ops - 1u;  // the tail op
-    hipLaunchKernelGGL(k_gorilla_windows, dim3(L.n_chunks), dim3(kGorThreads), 0, L.stream, *L.plan, opi, gor_piece_pts,
-                       L.points, L.points_end, L.chunks,
-                       reinterpret_cast<uint16_t*>(const_cast<uint4*>(L.pre.p[L.plan->ops[opi].type])));
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_gorilla_windows");
-  } else if (L.n_chunks && L.plan->n_gorilla) {
-    hipLaunchKernelGGL(k_gorilla_tokens, dim3(L.n_chunks, L.plan->n_gorilla), dim3(kGorThreads), 0, L.stream, *L.plan,
-                       L.points, L.points_end, L.chunks, L.pre_out);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_gorilla_tokens");
-  }
-  if (L.n_chunks && L.pieces) {  // slot pipeline, regular stream by the barrier-free piece kernel
-    const int rc = launch_fused(L, L.stream, 0u, L.n_pieces, &modes_probed);
-    if (rc != CLDN_HIP_OK) return rc;
-    if (wrote_caller_modes) *wrote_caller_modes = modes_probed && L.caller_modes != nullptr;
-  } else if (L.n_chunks && fixed_point_bytes(*L.plan) != 0u) {
-    // every per-point encoder writes a fixed number of bytes (lossless floats, raw copies): one thread per point, which also
-    // splits the integer fields off into their columns
-    const uint32_t pb = fixed_point_bytes(*L.plan);
-    const uint64_t total_points = (uint64_t)(L.points_end - L.points) / L.plan->point_step;
-    const uint64_t total = 4ull * L.n_chunks + (uint64_t)pb * total_points;
-    // without integer columns every size is known here: the kernel writes the framed streams themselves (an output that is too
-    // small takes the slot path, whose k_finish reports it)
-    const bool direct = !L.chunks_only && L.plan->n_adaptive == 0u && total <= L.out_capacity;
-    hipLaunchKernelGGL(k_encode_fixed, dim3(L.n_chunks, kPointsPerChunk / 256u), dim3(256), 0, L.stream, *L.plan, L.points, L.chunks,
-                       L.slots, L.slot_stride, L.segs, L.segs_per_chunk, L.subs, L.sub_points, L.sub_stride, pb, L.cols,
-                       direct ? L.out : (uint8_t*)nullptr, L.chunk_payload, L.chunk_dst);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_encode_fixed");
-    if (direct) {
-      hipLaunchKernelGGL(k_fixed_offsets, dim3((L.n_clouds + 256u) / 256u), dim3(256), 0, L.stream, L.chunks, L.cloud_first_chunk, L.n_clouds,
-                         L.n_chunks, pb, total, L.stream_offsets);
-      if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_fixed_offsets");
-      if (L.events) {
-        (void)hipEventRecord(L.events[2], L.stream);
-        (void)hipEventRecord(L.events[3], L.stream);
-        (void)hipEventRecord(L.events[4], L.stream);
-      }
-      return CLDN_HIP_OK;
-    }
-  } else if (L.n_chunks) {  // the generic op interpreter
-    const RegularKernel& k = kRegularKernels[L.plan->point_step <= kWidePointStep ? 0 : 1];
-    hipLaunchKernelGGL(k.kernel, dim3(L.n_chunks * L.subs), dim3(kRegularThreads), regular_lds(L.plan->point_step), L.stream, *L.plan,
-                       L.points, L.points_end, L.chunks, L.slots, L.slot_stride, L.segs, L.segs_per_chunk, L.cols, L.subs, L.sub_points,
-                       L.sub_stride, L.pre);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_encode_regular");
-  }
-  if (L.events) (void)hipEventRecord(L.events[2], L.stream);
-  const uint32_t na = L.plan->n_adaptive;
-  if (na && L.n_chunks) {
-    if (!L.modes_forced && !modes_probed) {
-      hipLaunchKernelGGL(k_probe_fast, dim3(L.n_clouds, na), dim3(kS2Threads), kProbeLds, L.stream, *L.plan, L.chunks,
-                         L.cloud_first_chunk, L.cols, L.modes);
-      if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_probe_fast");
-    }
-    const int rc_sec = launch_sections(L, L.stream, 0u, L.n_chunks, fused_field);
-    if (rc_sec != CLDN_HIP_OK) return rc_sec;
-  }
-  if (L.events) (void)hipEventRecord(L.events[3], L.stream);
-  if (L.chunks_only) {
-    if (L.n_chunks) {
-      hipLaunchKernelGGL(k_chunk_sizes, dim3((L.n_chunks + 255u) / 256u), dim3(256), 0, L.stream, L.segs, L.segs_per_chunk, L.n_chunks,
-                         L.chunk_payload, L.contiguous_flag);
-      if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_chunk_sizes");
-    }
-    if (L.events) (void)hipEventRecord(L.events[4], L.stream);
-    return CLDN_HIP_OK;
-  }
-  if (L.n_chunks == 0u) {  // no chunk, no workgroup: every cloud's stream is empty
-    if ((e = hipMemsetAsync(L.stream_offsets, 0, (size_t)(L.n_clouds + 1u) * sizeof(uint64_t), L.stream)) != hipSuccess)
-      return hip_fail(e, "hipMemsetAsync(stream_offsets)");
-  } else {
-    FinishArgs F;
-    F.chunks = L.chunks;
-    F.n_chunks = L.n_chunks;
-    F.cloud_first_chunk = L.cloud_first_chunk;
-    F.n_clouds = L.n_clouds;
-    F.slots = L.slots;
-    F.slot_stride = L.slot_stride;
-    F.segs = L.segs;
-    F.segs_per_chunk = L.segs_per_chunk;
-    F.subs = L.subs;
-    F.rec = L.fin_rec;
-    F.rec2 = L.fin_rec2;
-    F.anchor = L.fin_anchor;
-    F.epoch = L.fin_epoch;
-    F.ticket = L.fin_ticket;
-    F.use_ticket = L.use_ticket ? 1u : 0u;
-    F.test_timeout = L.test_timeout;
-    F.chunk_payload = L.chunk_payload;
-    F.chunk_dst = L.chunk_dst;
-    F.stream_offsets = L.stream_offsets;
-    F.out = L.out;
-    F.out_capacity = L.out_capacity;
-    F.status = L.status;
-    F.modes = L.modes;
-    F.n_adaptive = na;
-    F.fuse_field = fused_field;
-    F.fuse_col = nullptr;
-    F.fuse_first = nullptr;
-    const FinishKernel* fk;
-    if (fused_field != kNoFusedField) {
-      F.fuse_col = L.cols.p[fused_field];
-      F.fuse_first = L.ranks[fused_field];
-      // small batches: 1024-thread workgroups (a chunk's Palette section is latency-bound: twice the threads, 0.6x the time)
-      const bool big = L.n_chunks < 200u;
-      F.splits = big ? 4u : (L.n_chunks >= 512u ? 1u : 2u);
-      const bool u16 = L.plan->adaptive[fused_field].bpv == 2u;
-      fk = finish_variant(big ? 1024u : 512u, u16 ? 2u : 4u);
-    } else {
-      F.splits = L.n_chunks >= 1024u ? 1u : (L.n_chunks >= 256u ? 4u : 16u);
-      fk = finish_variant(256u, 0u);
-    }
-    if (!fk) return hip_fail(hipErrorInvalidValue, "k_finish (no variant)");
-    hipLaunchKernelGGL(fk->kernel, dim3(L.n_chunks * F.splits), dim3(fk->threads), fk->lds, L.stream, F);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_finish");
-  }
-  if (L.events) (void)hipEventRecord(L.events[4], L.stream);
-  return CLDN_HIP_OK;
-}
-
-int stage1_launch_frame(const FrameLaunch& L) {
-  hipError_t e;
-  if (L.n_chunks == 0u) {
-    if ((e = hipMemsetAsync(L.stream_offsets, 0, (size_t)(L.n_clouds + 1u) * sizeof(uint64_t), L.stream)) != hipSuccess)
-      return hip_fail(e, "hipMemsetAsync(stream_offsets)");
-    return CLDN_HIP_OK;
-  }
+// ---- the encode launchers: what encode_route() decided (stage1_encode_route.h), launched ----
+namespace {
+// k_finish<256, 0> and its fused variants: the framing members come from a FrameLaunch, the encoder adds its sections'
+int launch_finish(const FrameLaunch& L, uint32_t subs, int variant, uint32_t splits, unsigned long long* rec2, const uint8_t* modes,
+                  uint32_t n_adaptive, uint32_t fuse_field, const uint8_t* fuse_col, uint16_t* fuse_first) {
   FinishArgs F;
   F = FinishArgs{};
   F.chunks = L.chunks;
   F.n_chunks = L.n_chunks;
+  F.splits = splits;
   F.cloud_first_chunk = L.cloud_first_chunk;
   F.n_clouds = L.n_clouds;
   F.slots = L.slots;
   F.slot_stride = L.slot_stride;
   F.segs = L.segs;
   F.segs_per_chunk = L.segs_per_chunk;
-  F.subs = L.segs_per_chunk;
+  F.subs = subs;
   F.rec = L.rec;
-  F.rec2 = nullptr;
+  F.rec2 = rec2;
   F.anchor = L.anchor;
   F.epoch = L.epoch;
   F.ticket = L.ticket;
@@ -1913,13 +1432,225 @@ int stage1_launch_frame(const FrameLaunch& L) {
   F.out = L.out;
   F.out_capacity = L.out_capacity;
   F.status = L.status;
-  F.fuse_field = kNoFusedField;
-  F.splits = L.n_chunks >= 1024u ? 1u : (L.n_chunks >= 256u ? 4u : 16u);
-  const FinishKernel* fk = finish_variant(256u, 0u);
-  if (!fk) return hip_fail(hipErrorInvalidValue, "k_finish (no variant)");
-  hipLaunchKernelGGL(fk->kernel, dim3(L.n_chunks * F.splits), dim3(fk->threads), fk->lds, L.stream, F);
-  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_finish (frame)");
+  F.modes = modes;
+  F.n_adaptive = n_adaptive;
+  F.fuse_field = fuse_field;
+  F.fuse_col = fuse_col;
+  F.fuse_first = fuse_first;
+  if (variant < 0 || variant >= kFinishVariantCount) return hip_fail(hipErrorInvalidValue, "k_finish (no variant)");
+  return launch("k_finish", kFinishKernels[variant], dim3(L.n_chunks * splits), dim3(kFinishVariants[variant].threads), kFinishVariants[variant].lds,
+                L.stream, F);
+}
+
+// every cloud's stream is empty
+int clear_offsets(hipStream_t stream, uint64_t* stream_offsets, uint32_t n_clouds) {
+  const hipError_t e = hipMemsetAsync(stream_offsets, 0, (size_t)(n_clouds + 1u) * sizeof(uint64_t), stream);
+  return e == hipSuccess ? CLDN_HIP_OK : hip_fail(e, "hipMemsetAsync(stream_offsets)");
+}
+
+// the framing members of an encode call
+FrameLaunch frame_of(const EncodeLaunch& L) {
+  const EncodeRoute& R = *L.route;
+  FrameLaunch F;
+  F.stream = L.stream;
+  F.chunks = L.chunks;
+  F.n_chunks = L.n_chunks;
+  F.cloud_first_chunk = L.cloud_first_chunk;
+  F.n_clouds = L.n_clouds;
+  F.slots = L.slots;
+  F.slot_stride = R.slot_stride;
+  F.segs = L.segs;
+  F.segs_per_chunk = R.segs_per_chunk;
+  F.rec = L.fin_rec;
+  F.anchor = L.fin_anchor;
+  F.epoch = L.fin_epoch;
+  F.ticket = L.fin_ticket;
+  F.use_ticket = L.use_ticket;
+  F.test_timeout = L.test_timeout;
+  F.chunk_payload = L.chunk_payload;
+  F.chunk_dst = L.chunk_dst;
+  F.stream_offsets = L.stream_offsets;
+  F.out = L.out;
+  F.out_capacity = L.out_capacity;
+  F.status = L.status;
+  return F;
+}
+
+int launch_fused(const EncodeLaunch& L) {
+  const EncodeRoute& R = *L.route;
+  FusedArgs A;
+  A.points = L.points;
+  A.points_end = L.points_end;
+  A.pieces = L.pieces;
+  A.cols = L.cols;
+  A.slots = L.slots;
+  A.slot_stride = R.slot_stride;
+  A.piece_stride = R.wave_stride;
+  A.segs = L.segs;
+  A.segs_per_chunk = R.segs_per_chunk;
+  A.n_probe = R.n_probe;
+  A.chunks = L.chunks;
+  A.cloud_first_chunk = L.cloud_first_chunk;
+  A.modes = L.modes;
+  A.intra = R.intra ? 1u : 0u;
+  A.epoch = L.fin_epoch;
+  A.wgrec = L.wgrec;
+  A.status = L.status;
+  A.clear = R.kernel_clears ? 1u : 0u;
+  A.n_anchor = L.n_chunks / 1024u + 1u;
+  A.anchor = L.fin_anchor;
+  A.flags = L.fallback_flags;
+  A.tail_kind = 0u;
+  A.tail_rel = 0u;
+  A.tail_size = 0u;
+  A.tail_windows = nullptr;
+  if (R.tail_op >= 0) {
+    const DevOp& top = L.plan->ops[R.tail_op];
+    A.tail_kind = top.kind;
+    A.tail_rel = top.offset - L.plan->ops[0].offset;
+    A.tail_size = top.size;
+    if (top.kind == OP_GORILLA64) A.tail_windows = reinterpret_cast<const uint16_t*>(L.pre.p[top.type]);
+  }
+  A.probe_lds = R.pieces_lds;
+  A.modes_out = R.writes_caller_modes ? L.caller_modes : nullptr;
+  return launch("k_encode_fused", kFusedKernels[R.variant], dim3(R.n_probe + L.n_pieces / kFusedWaves), dim3(kFusedThreads), R.pieces_lds,
+                L.stream, *L.plan, A);
+}
+
+// the Gorilla pre-pass of a WIDE plan. k_gorilla_tokens finds "the blockIdx.y-th Gorilla op of the plan": a plan of at most
+// kMaxOps such ops per launch
+int launch_wide_gorilla(const EncodeLaunch& L) {
+  const WidePlan& W = *L.wide;
+  DevPlan mini;
+  mini = DevPlan{};
+  mini.point_step = W.point_step;
+  uint32_t g0 = 0u;
+  for (uint32_t k = 0; k <= W.n_ops; ++k) {
+    if (k < W.n_ops && L.wide_ops_host[k].kind == OP_GORILLA64) mini.ops[mini.n_ops++] = L.wide_ops_host[k];
+    if (mini.n_ops == (uint32_t)kMaxOps || (k == W.n_ops && mini.n_ops != 0u)) {
+      mini.n_gorilla = mini.n_ops;
+      TRY_LAUNCH("k_gorilla_tokens (wide)", k_gorilla_tokens, dim3(L.n_chunks, mini.n_ops), dim3(kGorThreads), 0, L.stream, mini, L.points,
+                 L.points_end, L.chunks, L.pre_out + g0);
+      g0 += mini.n_ops;
+      mini.n_ops = 0u;
+    }
+  }
   return CLDN_HIP_OK;
+}
+
+// mode probe and the chunks' payloads of a WIDE plan
+int launch_wide(const EncodeLaunch& L) {
+  const EncodeRoute& R = *L.route;
+  WideEncodeArgs A;
+  A.plan = *L.wide;
+  A.points = L.points;
+  A.points_end = L.points_end;
+  A.chunks = L.chunks;
+  A.cloud_first_chunk = L.cloud_first_chunk;
+  A.modes = L.modes;
+  A.slots = L.slots;
+  A.slot_stride = R.slot_stride;
+  A.segs = L.segs;
+  A.scratch = L.wide_scratch;
+  A.pre = L.wide_pre;
+  if (R.probe == EB_WIDE)
+    TRY_LAUNCH("k_wide_probe", k_wide_probe, dim3(L.n_clouds * A.plan.n_adaptive), dim3(kS2Threads), kProbeLds, L.stream, A, L.n_clouds);
+  return launch("k_wide_encode", k_wide_encode, dim3(L.n_chunks), dim3(kWideThreads), kSecLdsTotal, L.stream, A);
+}
+
+// section kernels of every chunk
+int launch_sections(const EncodeLaunch& L) {
+  const EncodeRoute& R = *L.route;
+  const uint32_t nch = L.n_chunks;
+  ColumnPtrs rank_cols;
+  for (int a = 0; a < kMaxAdaptive; ++a) rank_cols.p[a] = reinterpret_cast<uint8_t*>(L.ranks[a]);
+#define SEC_ARGS(FL) \
+  *L.plan, FL, L.chunks, L.cols, L.modes, L.slots, R.slot_stride, R.reg_stride, L.segs, R.segs_per_chunk, R.subs, L.fallback_flags, R.append
+  if (R.runs.n) TRY_LAUNCH("k_section_fast", k_section_fast, dim3(nch, R.runs.n), dim3(kS2Threads), kD32Lds, L.stream, SEC_ARGS(R.runs));
+  // 512-thread workgroups (two bitmap words and two groups of 32 values per thread): four of them fit a CU, so a batch of
+  // up to 1024 chunks is one generation (C2: sections 0.066 ms with 1024 threads, 0.062 ms with 512)
+  if (R.pal16.n)
+    TRY_LAUNCH("k_section_palette", (k_section_palette32<uint16_t, 512>), dim3(nch, R.pal16.n), dim3(512), kPal16Lds, L.stream, SEC_ARGS(R.pal16),
+               rank_cols, L.status);
+  if (R.pal32.n)
+    TRY_LAUNCH("k_section_palette", (k_section_palette32<uint32_t, 512>), dim3(nch, R.pal32.n), dim3(512), kPal32Lds, L.stream, SEC_ARGS(R.pal32),
+               rank_cols, L.status);
+  if (R.pal64.n)
+    TRY_LAUNCH("k_section_palette", k_section_palette<uint64_t>, dim3(nch, R.pal64.n), dim3(kS2Threads), kS2PalLds, L.stream, SEC_ARGS(R.pal64));
+#undef SEC_ARGS
+  return launch("k_encode_sections", k_encode_sections, dim3(R.sec_grid), dim3(kSecThreads), kSecLdsTotal, L.stream, *L.plan, L.chunks, L.cols,
+                L.modes, L.slots, R.slot_stride, R.reg_stride, L.segs, R.segs_per_chunk, rank_cols, R.subs, L.fallback_flags, R.fused_field, nch);
+}
+}  // namespace
+
+int stage1_launch_encode(const EncodeLaunch& L) {
+  const EncodeRoute& R = *L.route;
+  const DevPlan& P = *L.plan;
+  int rc = CLDN_HIP_OK;
+  auto event = [&](int k) {
+    if (L.events) (void)hipEventRecord(L.events[k], L.stream);
+  };
+  event(0);
+  event(1);
+  if (R.prepass == EP_GORILLA_WINDOWS) {
+    const uint32_t opi = (uint32_t)R.tail_op;
+    TRY_LAUNCH("k_gorilla_windows", k_gorilla_windows, dim3(L.n_chunks), dim3(kGorThreads), 0, L.stream, P, opi, R.piece_pts, L.points,
+               L.points_end, L.chunks, reinterpret_cast<uint16_t*>(const_cast<uint4*>(L.pre.p[P.ops[opi].type])));
+  } else if (R.prepass == EP_GORILLA_TOKENS) {
+    TRY_LAUNCH("k_gorilla_tokens", k_gorilla_tokens, dim3(L.n_chunks, P.n_gorilla), dim3(kGorThreads), 0, L.stream, P, L.points, L.points_end,
+               L.chunks, L.pre_out);
+  } else if (R.prepass == EP_WIDE_GROUPS) {
+    rc = launch_wide_gorilla(L);
+  }
+  if (rc != CLDN_HIP_OK) return rc;
+  switch (R.regular) {
+    case ER_WIDE: rc = launch_wide(L); break;
+    case ER_PIECES: rc = launch_fused(L); break;
+    case ER_FIXED:
+    case ER_FIXED_DIRECT: {
+      const bool direct = R.regular == ER_FIXED_DIRECT;
+      rc = launch("k_encode_fixed", k_encode_fixed, dim3(L.n_chunks, kPointsPerChunk / 256u), dim3(256), 0, L.stream, P, L.points, L.chunks,
+                  L.slots, R.slot_stride, L.segs, R.segs_per_chunk, R.subs, R.sub_points, R.sub_stride, R.fixed_bytes, L.cols,
+                  direct ? L.out : (uint8_t*)nullptr, L.chunk_payload, L.chunk_dst);
+      if (rc == CLDN_HIP_OK && direct)
+        rc = launch("k_fixed_offsets", k_fixed_offsets, dim3((L.n_clouds + 256u) / 256u), dim3(256), 0, L.stream, L.chunks, L.cloud_first_chunk,
+                    L.n_clouds, L.n_chunks, R.fixed_bytes, R.fixed_total, L.stream_offsets);
+      break;
+    }
+    case ER_GENERIC:
+      rc = launch("k_encode_regular", kRegularKernels[R.generic_kernel].kernel, dim3(L.n_chunks * R.subs), dim3(kRegularThreads),
+                  regular_lds(P.point_step), L.stream, P, L.points, L.points_end, L.chunks, L.slots, R.slot_stride, L.segs, R.segs_per_chunk,
+                  L.cols, R.subs, R.sub_points, R.sub_stride, L.pre);
+      break;
+    default: break;
+  }
+  if (rc != CLDN_HIP_OK) return rc;
+  event(2);
+  if (R.probe == EB_FAST)
+    TRY_LAUNCH("k_probe_fast", k_probe_fast, dim3(L.n_clouds, P.n_adaptive), dim3(kS2Threads), kProbeLds, L.stream, P, L.chunks,
+               L.cloud_first_chunk, L.cols, L.modes);
+  if (R.sections && (rc = launch_sections(L)) != CLDN_HIP_OK) return rc;
+  event(3);
+  if (R.close == EC_CHUNK_SIZES) {
+    rc = launch("k_chunk_sizes", k_chunk_sizes, dim3((L.n_chunks + 255u) / 256u), dim3(256), 0, L.stream, L.segs, R.segs_per_chunk, L.n_chunks,
+                L.chunk_payload, L.contiguous_flag);
+  } else if (R.close == EC_OFFSETS_MEMSET) {
+    rc = clear_offsets(L.stream, L.stream_offsets, L.n_clouds);
+  } else if (R.close == EC_FINISH) {
+    const bool fused = R.fused_field != kNoFusedField;
+    // (WIDE: framing alone, one segment per chunk)
+    rc = launch_finish(frame_of(L), R.subs, R.finish, R.splits, R.regular == ER_WIDE ? nullptr : L.fin_rec2,
+                       R.regular == ER_WIDE ? nullptr : L.modes, P.n_adaptive, R.fused_field, fused ? L.cols.p[R.fused_field] : nullptr,
+                       fused ? L.ranks[R.fused_field] : nullptr);
+  }
+  if (rc != CLDN_HIP_OK) return rc;
+  event(4);
+  return CLDN_HIP_OK;
+}
+
+int stage1_launch_frame(const FrameLaunch& L) {
+  if (L.n_chunks == 0u) return clear_offsets(L.stream, L.stream_offsets, L.n_clouds);
+  return launch_finish(L, L.segs_per_chunk, 0, finish_splits_plain(L.n_chunks), nullptr, nullptr, 0u, kNoFusedField, nullptr, nullptr);
 }
 
 }  // namespace cldn

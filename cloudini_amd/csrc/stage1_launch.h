@@ -1,4 +1,6 @@
-// stage1_launch.h -- host-callable launchers implemented next to the kernels (stage1_kernels.hip).
+// stage1_launch.h -- host-callable launchers implemented next to the kernels (stage1_kernels.hip, stage1_decode.hip). The two
+// stage-1 launchers decide nothing: EncodeLaunch / DecodeLaunch carry the call's buffers, which kernels run is the route's
+// (stage1_encode_route.h: the ABI computes it once per call and sizes its buffers from it; stage1_decode_route.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -6,12 +8,14 @@
 
 #include "stage1_decode_route.h"
 #include "stage1_device.h"
+#include "stage1_encode_route.h"
 #include "stage1_report.h"
 
 namespace cldn {
 
 struct EncodeLaunch {
   const DevPlan* plan;
+  const EncodeRoute* route;   // encode_route() of the call: the kernels, and the geometry of slots and segment table
   hipStream_t stream;
   const uint8_t* points;      // device, batch AoS
   const uint8_t* points_end;
@@ -19,14 +23,8 @@ struct EncodeLaunch {
   uint32_t n_chunks;
   uint32_t n_clouds;
   const uint32_t* cloud_first_chunk;  // device [n_clouds + 1]
-  uint8_t* slots;             // device [n_chunks * slot_stride]
-  uint64_t slot_stride;
-  uint64_t reg_stride;        // = subs * sub_stride
-  uint32_t subs;              // sub-chunks (independent regular sub-streams) per chunk, power of two
-  uint32_t sub_points;        // 32768 / subs
-  uint32_t sub_stride;        // bytes reserved per sub-stream
-  Seg* segs;                  // device [n_chunks * segs_per_chunk]
-  uint32_t segs_per_chunk;
+  uint8_t* slots;             // device [n_chunks * route->slot_stride]
+  Seg* segs;                  // device [n_chunks * route->segs_per_chunk]
   ColumnPtrs cols;
   PreTokenPtrs pre;           // Gorilla token buffers (read side, by value into the kernels)
   uint4* const* pre_out;      // device array [n_gorilla] of the same buffers (write side of k_gorilla_tokens)
@@ -35,14 +33,8 @@ struct EncodeLaunch {
   uint64_t* chunk_dst;        // device [n_chunks]
   uint64_t* stream_offsets;   // device [n_clouds + 1]
   uint8_t* modes;             // device [n_clouds * n_adaptive]
-  bool modes_forced;          // modes were uploaded by the caller: no probe kernels
-  // per adaptive field: bit m set = mode m may occur (modes of the previous call, or forced); 0xF = unknown.
-  // Only a launch hint: a fast section kernel that is not launched leaves its chunks to k_encode_sections.
-  uint8_t mode_hint[kMaxAdaptive];
   uint8_t* fallback_flags;    // device [n_chunks * n_adaptive], zeroed per call: 1 = section written by a fast path
-  // chunk-table output: no framing -- the call ends with the chunks' payloads in their slots (segment table) and
-  // k_chunk_sizes (payload sizes, contiguity flag)
-  bool chunks_only;
+  // chunk-table output (no framing): the call ends with the chunks' payloads in their slots (segment table) and k_chunk_sizes
   uint32_t* contiguous_flag;       // device word, 0 at launch: set to 1 when a chunk's payload is not one run of its slot
   // k_finish (stage1_finish.h)
   unsigned long long* fin_rec;     // device [n_chunks]: look-back records, tagged with fin_epoch
@@ -56,30 +48,20 @@ struct EncodeLaunch {
   uint64_t out_capacity;
   uint32_t* status;           // device status word
   hipEvent_t* events;         // 5 events (start, before regular, after regular, after sections, end) or NULL
-  // piece kernel (stage1_fused.h). pieces != NULL: the regular stream is encoded one wave per piece, every workgroup
-  // leaves one segment in the chunk's slot
-  const PieceDesc* pieces;    // device [n_pieces] or NULL
+  // piece kernel (stage1_fused.h): one wave per piece, every workgroup leaves one segment in the chunk's slot
+  const PieceDesc* pieces;    // device [n_pieces] (ER_PIECES)
   uint32_t n_pieces;          // multiple of 4
-  bool intra;                 // the piece kernel's workgroups place a chunk's regular stream contiguously (subs == 1)
-  unsigned long long* wgrec;  // device [n_chunks * 32]: their look-back records, tagged with fin_epoch
-  // The piece kernel's launch zeroes what the call's kernels expect zeroed -- the status block, fin_anchor, every chunk's
-  // fallback_flags and the segment entries its own workgroups do not write -- so the caller enqueued no memset for them.
-  // Only with `pieces`, without `intra` / `chunks_only` and without a Gorilla pre-pass (the piece kernel is the call's first launch).
-  bool kernel_clears;
-  // the caller's device array [n_clouds * n_adaptive] or NULL: the piece kernel's probe workgroups store every mode there as
-  // well as to `modes`. stage1_launch_encode reports through its out flag whether they did (else the caller copies `modes`).
+  unsigned long long* wgrec;  // device [n_chunks * 32]: the workgroups' look-back records (intra), tagged with fin_epoch
+  // the caller's device array [n_clouds * n_adaptive] or NULL: where route->writes_caller_modes, the piece kernel's probe
+  // workgroups store every mode there as well as to `modes` (else the caller copies `modes`)
   uint8_t* caller_modes;
-  // WIDE route (stage1_wide.h): schemas beyond the launch-argument plan. wide != NULL: `plan` holds only the scalar members,
-  // subs == 1 and segs_per_chunk == 1 (one segment per chunk), the slots take a chunk's whole payload.
+  // WIDE route (stage1_wide.h): schemas beyond the launch-argument plan; `plan` holds only the scalar members
   const WidePlan* wide;       // host copy of the descriptor (its arrays are device memory), or NULL
   const DevOp* wide_ops_host; // host copy of the regular ops (the Gorilla pre-pass is launched per group of them)
   uint8_t* wide_scratch;      // device [n_chunks * stage1_wide_scratch_bytes()]
   const uint4* const* wide_pre;  // device [n_gorilla] token buffers (same array as pre_out)
 };
 size_t stage1_wide_scratch_bytes();  // per chunk
-
-uint32_t stage1_piece_points(const DevPlan& plan, const uint8_t* points);        // piece kernel applies: points per piece, else 0
-uint32_t stage1_piece_slot_stride(const DevPlan& plan, const uint8_t* points);   // bytes a piece may produce, 256-aligned
 
 struct DecodeLaunch {
   const DevPlan* plan;
@@ -135,6 +117,18 @@ inline size_t wp_split_bytes(uint32_t n_chunks, uint32_t maxp) { return (size_t)
 // Launch errors go to the ABI's thread-local error string (cldn_hip_last_error), implemented in hip_abi.hip.
 int launch_fail(hipError_t e, const char* what);
 
+// one launch, checked: the error text names the kernel
+template <class Kernel, class... Args>
+int launch(const char* name, Kernel kernel, dim3 grid, dim3 block, uint32_t lds, hipStream_t stream, const Args&... args) {
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : launch_fail(e, name);
+}
+#define TRY_LAUNCH(...)                                      \
+  do {                                                       \
+    if (const int rc_ = launch(__VA_ARGS__)) return rc_;     \
+  } while (0)
+
 // A launch with more than the 64 KiB of dynamic LDS a runtime grants by default needs hipFuncAttributeMaxDynamicSharedMemorySize:
 // stage1_configure_kernels / _decode pass their kernels through here with the most dynamic LDS a launch of each takes.
 template <class Kernel>
@@ -145,7 +139,7 @@ inline hipError_t allow_lds(Kernel* kernel, uint32_t lds) {
 
 int stage1_configure_kernels();
 int stage1_configure_decode();   // decode TU (stage1_decode.hip); called by stage1_configure_kernels
-int stage1_launch_encode(const EncodeLaunch& L, bool* wrote_caller_modes = nullptr);  // (the flag: see EncodeLaunch::caller_modes)
+int stage1_launch_encode(const EncodeLaunch& L);
 int stage1_launch_decode(const DecodeLaunch& L);
 int stage1_launch_decode_unframed(const DevPlan& plan, hipStream_t stream, const uint8_t* payload, uint32_t size,
                                   uint32_t capacity_points, void* chunk_slot, uint8_t* out, uint32_t* status,

@@ -16,12 +16,7 @@ namespace cldn {
 // palette-coded field has)
 constexpr uint32_t kPalSeed = 2048u;
 
-// the adaptive fields one section-kernel launch covers: blockIdx.y indexes the list
-struct SectionFields {
-  uint32_t n;
-  uint8_t a[kMaxAdaptive];
-};
-
+// (SectionFields, the adaptive fields one section-kernel launch covers: stage1_encode_route.h; blockIdx.y indexes the list)
 constexpr int kS2Threads = 1024;
 constexpr uint32_t kS2PalSlots = 4096;
 constexpr uint32_t kS2PalCapacity = 3072;  // load factor 0.75
