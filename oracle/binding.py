@@ -62,6 +62,28 @@ class OracleError(RuntimeError):
     pass
 
 
+# orc_lz4_sub (oracle/lz4_model.c)
+_LZ4_SUB = np.dtype([(k, np.uint32) for k in ("s", "e", "count", "full", "first_match", "n_steps")] + [("first_step", np.uint64)] +
+                    [(k, np.uint32) for k in ("anchor_in", "sub_size", "before", "next_pos", "last_end", "w0", "span", "gap",
+                                              "skip0", "lit0")], align=True)
+
+
+class Lz4Trace:
+    """Oracle.lz4_trace: `size` (the block size the layout gives), `subs` (one orc_lz4_sub record per sub-range), `matches`
+    (rows pos, len, off, in order) and `steps` (rows first position, matches taken, cursor advance `cur`)."""
+
+    def __init__(self, size, n, subs, matches, steps):
+        self.size, self.n, self.subs, self.matches, self.steps = size, n, subs, matches, steps
+
+    def sub_matches(self, k: int) -> np.ndarray:
+        r = self.subs[k]
+        return self.matches[int(r["first_match"]): int(r["first_match"]) + int(r["count"])]
+
+    def sub_steps(self, k: int) -> np.ndarray:
+        r = self.subs[k]
+        return self.steps[int(r["first_step"]): int(r["first_step"]) + int(r["n_steps"])]
+
+
 class Oracle:
     """Plain-C restatement (stage 1 only; framed [u32 size][payload] chunks, no header)."""
 
@@ -186,6 +208,27 @@ class Oracle:
         if n < 0:
             raise RuntimeError("orc_lz4_compress failed")
         return out[:n].copy()
+
+    def lz4_trace(self, payload, sub_bytes: int = 8192, hash_bits: int = 11, max_matches: int = 1024) -> "Lz4Trace":
+        """What the device's kernels compute per sub-range of `payload`, from the model's own parser (orc_lz4_trace). A trace
+        shows which branch a payload reaches; expected bytes come from lz4_model."""
+        a = _as_u8(payload)
+        L = self.lib
+        L.orc_lz4_trace.restype = C.c_int64
+        L.orc_lz4_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                    C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        n_subs = (a.size + sub_bytes - 1) // sub_bytes
+        subs = np.zeros(max(1, n_subs), dtype=_LZ4_SUB)
+        # (a match has 4 bytes or more, a step moves the cursor by 64 or more)
+        matches = np.zeros((max(1, min(a.size // 4 + 1, n_subs * max_matches)), 3), dtype=np.uint32)
+        steps = np.zeros((max(1, a.size // 64 + n_subs + 1), 3), dtype=np.uint32)
+        totals = np.zeros(3, dtype=np.uint64)
+        size = L.orc_lz4_trace(a.ctypes.data if a.size else None, a.size, sub_bytes, hash_bits, max_matches, subs.ctypes.data,
+                               subs.shape[0], matches.ctypes.data, matches.shape[0], steps.ctypes.data, steps.shape[0],
+                               totals.ctypes.data)
+        if size < 0 or int(totals[1]) > matches.shape[0] or int(totals[2]) > steps.shape[0]:
+            raise RuntimeError("orc_lz4_trace failed")
+        return Lz4Trace(int(size), a.size, subs[: int(totals[0])], matches[: int(totals[1])], steps[: int(totals[2])])
 
     def encode_varint64(self, v: int) -> bytes:
         buf = (C.c_uint8 * 16)()

@@ -28,6 +28,14 @@ typedef struct {
   uint32_t pos, len, off;
 } lz4m_match;
 
+/* what a trace keeps of the parser's steps (orc_lz4_trace; orc_lz4_compress passes none): per step its first position, the
+ * matches it took and the lanes its cursor moved over, and whether the list ran full with positions left to parse */
+typedef struct {
+  uint32_t* steps; /* 3 per step: pos, taken, cur */
+  uint64_t n_steps, cap;
+  uint32_t full;
+} lz4m_steplog;
+
 static uint32_t rd32(const uint8_t* p) {
   uint32_t v;
   memcpy(&v, p, 4);
@@ -48,8 +56,9 @@ static uint8_t* put_ext(uint8_t* o, uint32_t x) { /* x >= 15: the part above 15 
 
 /* matches of sub-range [s, e) of the n-byte block, appended to m[] (capacity max_matches); returns their number */
 static uint32_t lz4m_parse(const uint8_t* in, uint32_t n, uint32_t s, uint32_t e, uint32_t hash_bits, uint32_t max_matches,
-                           uint16_t* table, lz4m_match* m) {
+                           uint16_t* table, lz4m_match* m, lz4m_steplog* log) {
   memset(table, 0, sizeof(uint16_t) << hash_bits);
+  if (log) log->full = 0u;
   if (n < 13u || e - s < 4u) return 0u;
   const int64_t last_start = (int64_t)(e - 4u) < (int64_t)n - 12 ? (int64_t)(e - 4u) : (int64_t)n - 12;
   const uint32_t end_limit = e < n - 5u ? e : n - 5u; /* a match ends here at the latest */
@@ -78,17 +87,28 @@ static uint32_t lz4m_parse(const uint8_t* in, uint32_t n, uint32_t s, uint32_t e
       const uint32_t h = (rd32(in + p) * 2654435761u) >> (32u - hash_bits);
       table[h] = (uint16_t)(p - s + 1);
     }
-    uint32_t cur = 0u;
+    uint32_t cur = 0u, taken = 0u;
     for (uint32_t l = 0; l < 64u; ++l) {
       if (l < cur || len[l] == 0u) continue;
       m[count].pos = (uint32_t)(i + l);
       m[count].len = len[l];
       m[count].off = (uint32_t)(i + l) - cf[l];
       ++count;
+      ++taken;
       cur = l + len[l];
+    }
+    if (log) {
+      if (log->n_steps < log->cap) {
+        uint32_t* r = log->steps + 3u * log->n_steps;
+        r[0] = (uint32_t)i;
+        r[1] = taken;
+        r[2] = cur;
+      }
+      ++log->n_steps;
     }
     i += cur > 64u ? cur : 64u;
   }
+  if (log) log->full = i <= last_start;
   return count;
 }
 
@@ -111,7 +131,7 @@ int64_t orc_lz4_compress(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t c
   uint32_t anchor = 0u;
   for (uint32_t s = 0u; s < n; s += sub_bytes) {
     const uint32_t e = n - s < sub_bytes ? n : s + sub_bytes;
-    const uint32_t cnt = lz4m_parse(in, n, s, e, hash_bits, max_matches, table, m);
+    const uint32_t cnt = lz4m_parse(in, n, s, e, hash_bits, max_matches, table, m, NULL);
     for (uint32_t k = 0; k < cnt; ++k) {
       const uint32_t lit = m[k].pos - anchor, ml = m[k].len - 4u;
       *o++ = (uint8_t)(((lit < 15u ? lit : 15u) << 4) | (ml < 15u ? ml : 15u));
@@ -133,6 +153,112 @@ int64_t orc_lz4_compress(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t c
   }
   free(table);
   free(m);
-  (void)ext_bytes;
   return (int64_t)(o - out);
+}
+
+/* One record per sub-range of what the device's kernels compute for it, from the same lz4m_parse (a trace only shows which
+ * branch a payload reaches; expected bytes come from orc_lz4_compress). The names are the kernels' own:
+ *   anchor_in, sub_size (k_lz4_sizes), before, next_pos (k_lz4_layout), last_end (k_lz4_match; 0 = no match);
+ *   w0, span = W1 - W0, gap = G1 - G0 and skip0 as the header comment of k_lz4_emit_lds defines them (block offsets; the
+ *   kernel takes lz_emit_direct when span + (address of W0 mod 16) exceeds its image). */
+typedef struct {
+  uint32_t s, e, count, full, first_match, n_steps;
+  uint64_t first_step;
+  uint32_t anchor_in, sub_size, before, next_pos, last_end, w0, span, gap, skip0, lit0;
+} orc_lz4_sub;
+
+/* returns the block size as the layout gives it (before + sub_size of the last sub-range + the last sequence), or -1.
+ * subs[subs_cap], matches[3 * matches_cap] (pos, len, off), steps[3 * steps_cap] (pos, taken, cur); totals[3] = the numbers
+ * of sub-ranges, matches and steps there are (records beyond a capacity are not written) */
+int64_t orc_lz4_trace(const uint8_t* in, uint32_t n, uint32_t sub_bytes, uint32_t hash_bits, uint32_t max_matches, orc_lz4_sub* subs,
+                      uint64_t subs_cap, uint32_t* matches, uint64_t matches_cap, uint32_t* steps, uint64_t steps_cap,
+                      uint64_t* totals) {
+  if (sub_bytes < 64u || sub_bytes > 65535u || hash_bits < 4u || hash_bits > 16u || max_matches == 0u) return -1;
+  const uint64_t n_subs = ((uint64_t)n + sub_bytes - 1u) / sub_bytes;
+  if (n_subs > subs_cap) return -1;
+  uint16_t* table = (uint16_t*)malloc(sizeof(uint16_t) << hash_bits);
+  lz4m_match* m = (lz4m_match*)malloc(sizeof(lz4m_match) * (size_t)max_matches);
+  uint32_t* first_pos = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(n_subs + 1u));
+  if (!table || !m || !first_pos) {
+    free(table);
+    free(m);
+    free(first_pos);
+    return -1;
+  }
+  lz4m_steplog log;
+  log.steps = steps;
+  log.n_steps = 0u;
+  log.cap = steps_cap;
+  uint64_t n_matches = 0u;
+  uint32_t anchor = 0u, run = 0u, k = 0u;
+  for (uint32_t s = 0u; s < n; s += sub_bytes, ++k) {
+    const uint32_t e = n - s < sub_bytes ? n : s + sub_bytes;
+    const uint64_t step0 = log.n_steps;
+    const uint32_t cnt = lz4m_parse(in, n, s, e, hash_bits, max_matches, table, m, &log);
+    orc_lz4_sub* r = subs + k;
+    memset(r, 0, sizeof *r);
+    r->s = s;
+    r->e = e;
+    r->count = cnt;
+    r->full = log.full;
+    r->first_match = (uint32_t)n_matches;
+    r->first_step = step0;
+    r->n_steps = (uint32_t)(log.n_steps - step0);
+    r->anchor_in = anchor;
+    r->before = run;
+    uint32_t a = anchor, size = 0u;
+    for (uint32_t j = 0; j < cnt; ++j) {
+      const uint32_t lit = m[j].pos - a, ml = m[j].len - 4u;
+      size += 1u + ext_bytes(lit) + lit + 2u + ext_bytes(ml);
+      a = m[j].pos + m[j].len;
+      if (n_matches < matches_cap) {
+        matches[3u * n_matches] = m[j].pos;
+        matches[3u * n_matches + 1u] = m[j].len;
+        matches[3u * n_matches + 2u] = m[j].off;
+      }
+      ++n_matches;
+    }
+    r->sub_size = size;
+    r->last_end = cnt ? a : 0u;
+    first_pos[k] = cnt ? m[0].pos : 0xffffffffu;
+    if (cnt) {
+      r->lit0 = m[0].pos - anchor;
+      r->skip0 = anchor < s ? (r->lit0 < s - anchor ? r->lit0 : s - anchor) : 0u;
+    }
+    anchor = a;
+    run += size;
+  }
+  /* next_pos: the first match behind each sub-range (none: the payload size); then the spans */
+  uint32_t carry = n;
+  for (uint32_t j = k; j-- > 0u;) {
+    orc_lz4_sub* r = subs + j;
+    r->next_pos = carry;
+    if (first_pos[j] != 0xffffffffu) carry = first_pos[j];
+    const uint32_t t0 = r->count ? r->last_end : r->s;
+    const uint32_t a2 = r->count ? t0 : r->anchor_in;
+    const uint32_t c_at = r->before + r->sub_size + 1u + ext_bytes(r->next_pos - a2) + (t0 - a2);
+    uint32_t w0, w1, gap = 0u;
+    if (r->count) {
+      w0 = r->before + 1u + ext_bytes(r->lit0) + r->skip0;
+      w1 = r->before + r->sub_size;
+      if (t0 < r->e) {
+        gap = c_at - w1;
+        w1 = c_at + (r->e - t0);
+      }
+    } else {
+      w0 = c_at;
+      w1 = c_at + (r->e - t0);
+    }
+    r->w0 = w0;
+    r->span = w1 - w0;
+    r->gap = gap;
+  }
+  totals[0] = k;
+  totals[1] = n_matches;
+  totals[2] = log.n_steps;
+  const uint32_t lit = n - anchor;
+  free(table);
+  free(m);
+  free(first_pos);
+  return (int64_t)run + 1 + ext_bytes(lit) + lit;
 }
