@@ -96,6 +96,9 @@ def lib() -> C.CDLL:
     L.cldn_amd_device_lz4_decode.restype = C.c_int
     L.cldn_amd_set_device_lz4_decode.restype = C.c_int
     L.cldn_amd_set_device_lz4_decode.argtypes = [C.c_int]
+    L.cldn_amd_device_zstd.restype = C.c_int
+    L.cldn_amd_set_device_zstd.restype = C.c_int
+    L.cldn_amd_set_device_zstd.argtypes = [C.c_int]
     for name in ("cldn_GetHeaderAsYAML", "cldn_GetHeaderAsYAMLFromDDS", "cldn_ConvertCompressedMsgToPointCloud2Msg",
                  "cldn_DecodeCompressedData", "cldn_DecodeCompressedMessage"):
         getattr(L, name).restype = C.c_uint32
@@ -171,6 +174,16 @@ def set_device_lz4_decode(on) -> bool:
     """PointcloudDecoder.decode of LZ4 messages (wire version >= 3) with stage 2 undone on the GPU (cldn_hip_decode_lz4) instead
     of liblz4 on the host pool. Off by default. Returns the value in effect."""
     return bool(lib().cldn_amd_set_device_lz4_decode(1 if on else 0))
+
+
+def device_zstd() -> bool:
+    return bool(lib().cldn_amd_device_zstd())
+
+
+def set_device_zstd(on) -> bool:
+    """ZSTD streams with stage 2 on the GPU: PointcloudEncoder.encode writes frames of literal-only blocks (valid ZSTD frames
+    that any decoder reads, not libzstd's bytes; larger where ZSTD finds matches). Off by default. Returns the value in effect."""
+    return bool(lib().cldn_amd_set_device_zstd(1 if on else 0))
 
 
 def _device_list(devices):

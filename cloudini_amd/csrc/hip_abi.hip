@@ -289,6 +289,8 @@ struct cldn_hip_codec {
     std::vector<uint64_t> offsets;        // host copy (calls with host outputs have read them anyway)
     std::vector<uint64_t> cloud_points;
     int kind = CLDN_HIP_STAGE2_NONE;
+    const uint8_t* s1_streams = nullptr;      // kind == CLDN_HIP_STAGE2_ZSTD: the framed stage-1 streams behind the frames
+    const uint64_t* d_s1_offsets = nullptr;   // ... and their offsets, device [n_clouds + 1]
     void drop() { valid = await_frame = false; }
   } enc;
 };
@@ -557,6 +559,9 @@ uint64_t cldn_hip_stage1_bound(const cldn_hip_plan_t* plan, uint64_t n_points) {
 }
 
 static uint64_t lz4_block_bound(uint64_t n) { return n + n / 255u + 16u; }  // LZ4_COMPRESSBOUND, lz4.h
+// ZSTD_COMPRESSBOUND, zstd.h (what MaxCompressedSize uses). A frame of zstd_kernels.hip never exceeds it: 9 bytes of frame
+// header and 3 per 128 KiB block over the payload
+static uint64_t zstd_frame_bound(uint64_t n) { return n + (n >> 8) + (n < 131072u ? (131072u - n) >> 11 : 0u); }
 
 uint64_t cldn_hip_stage2_bound(const cldn_hip_plan_t* plan, uint64_t n_points, int stage2) {  // cloudini.cpp:249-292
   if (!plan) return 0;
@@ -567,14 +572,15 @@ uint64_t cldn_hip_stage2_bound(const cldn_hip_plan_t* plan, uint64_t n_points, i
     left -= in_chunk;
     uint64_t chunk = in_chunk * plan->ref_max_point_bytes;
     if (plan->uses_v5) chunk += (uint64_t)plan->fields.size() * 32u + 1024u;
-    total += 4 + lz4_block_bound(chunk);
+    total += 4 + (stage2 == CLDN_HIP_STAGE2_ZSTD ? zstd_frame_bound(chunk) : lz4_block_bound(chunk));
   }
   return total;
 }
 
 int cldn_hip_codec_set_stage2(cldn_hip_codec_t* c, int stage2) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
-  if (stage2 != CLDN_HIP_STAGE2_NONE && stage2 != CLDN_HIP_STAGE2_LZ4 && stage2 != CLDN_HIP_STAGE2_LZ4_FAST)
+  if (stage2 != CLDN_HIP_STAGE2_NONE && stage2 != CLDN_HIP_STAGE2_LZ4 && stage2 != CLDN_HIP_STAGE2_LZ4_FAST &&
+      stage2 != CLDN_HIP_STAGE2_ZSTD)
     return fail(CLDN_HIP_ERR_ARG, "invalid stage-2 mode %d", stage2);
   c->stage2 = stage2;
   return CLDN_HIP_OK;
@@ -951,7 +957,10 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   const uint32_t step = plan.point_step;
 
   const bool wide = c->plan.wide;  // stage1_wide.h: the plan's arrays live in device memory, one segment per chunk
-  const bool lz4 = c->stage2 == CLDN_HIP_STAGE2_LZ4 || c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST;
+  // `lz4`: stage 2 runs on the device, of either kind -- the stage-1 streams go to d_s1, the call's output is written by the
+  // stage-2 kernels. `zstd`: those are zstd_kernels.hip's
+  const bool zstd = c->stage2 == CLDN_HIP_STAGE2_ZSTD;
+  const bool lz4 = c->stage2 == CLDN_HIP_STAGE2_LZ4 || c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST || zstd;
   const bool lz4_fast = c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST;
   const uint32_t n_adaptive = c->plan.n_adaptive_total();
   // capacity contract of PointcloudEncoder::encode (cloudini.cpp:531-534)
@@ -1183,7 +1192,41 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   rc = stage1_launch_encode(L);
   if (rc != CLDN_HIP_OK) return rc;
   const void* d_sizes = c->d_payload.p;  // what chunk_sizes reports
-  if (lz4 && n_chunks) {
+  if (zstd && n_chunks) {
+    // stage 2 on the device: a ZSTD frame of literal-only blocks per chunk payload (zstd_kernels.hip), written straight into the
+    // framed streams. Every chunk has ceil(payload / 128 KiB) blocks, one at least; the payloads are bounded by need_s1
+    const uint64_t max_blocks = need_s1 / kZsBlockBytes + n_chunks;
+    const size_t o_codes = ((size_t)max_blocks * sizeof(ZsBlock) + 63u) & ~size_t(63);
+    const size_t o_descs = o_codes + (size_t)max_blocks * 256u * sizeof(uint32_t);
+    const size_t o_dst = (o_descs + (size_t)max_blocks * kZsDescBytes + 63u) & ~size_t(63);
+    const size_t o_first = o_dst + (size_t)(max_blocks + 1u) * sizeof(uint64_t);
+    const size_t o_state = o_first + (size_t)(n_chunks + 1u) * sizeof(uint32_t);
+    if ((rc = c->d_lz_counts.ensure(o_state + (size_t)n_chunks * sizeof(uint32_t))) != CLDN_HIP_OK) return rc;
+    uint8_t* ws = (uint8_t*)c->d_lz_counts.p;
+    ZstdLaunch Z;
+    Z.stream = c->stream;
+    Z.stage1 = (const uint8_t*)c->d_s1.p;
+    Z.stage1_capacity = need_s1;
+    Z.chunk_dst = (const uint64_t*)c->d_dst.p;
+    Z.chunk_payload = (const uint32_t*)c->d_payload.p;
+    Z.n_chunks = n_chunks;
+    Z.max_blocks = max_blocks;
+    Z.blocks = (ZsBlock*)ws;
+    Z.codes = (uint32_t*)(ws + o_codes);
+    Z.descs = ws + o_descs;
+    Z.block_dst = (uint64_t*)(ws + o_dst);
+    Z.blk_first = (uint32_t*)(ws + o_first);
+    Z.chunk_state = (uint32_t*)(ws + o_state);
+    Z.cloud_first_chunk = (const uint32_t*)c->d_cloud_first.p;
+    Z.n_clouds = n_clouds;
+    Z.frame_sizes_out = (uint32_t*)c->d_payload2.p;
+    Z.stream_offsets = (uint64_t*)c->d_offsets.p;
+    Z.out = d_outp;
+    Z.out_capacity = out_capacity;
+    Z.status = (uint32_t*)c->d_status.p;
+    if ((rc = zstd_launch(Z)) != CLDN_HIP_OK) return rc;
+    d_sizes = c->d_payload2.p;
+  } else if (lz4 && n_chunks) {
     // stage 2 on the device: an LZ4 block per chunk payload (lz4_kernels.hip), written straight into the framed streams
     // every chunk has ceil(payload / 16 KiB) sub-ranges; the payloads of the batch are bounded by need_s1
     const uint32_t lz_sub = lz4_fast ? kLzFastSubBytes : kLzSubBytes, lz_mm = lz4_fast ? kLzFastMaxMatches : kLzMaxMatches;
@@ -1286,9 +1329,12 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   c->enc.points = d_points;
   c->enc.streams = d_outp;
   c->enc.cloud_points.assign(cloud_points, cloud_points + n_clouds);
-  c->enc.kind = lz4 ? CLDN_HIP_STAGE2_LZ4 : CLDN_HIP_STAGE2_NONE;
+  c->enc.kind = zstd ? CLDN_HIP_STAGE2_ZSTD : lz4 ? CLDN_HIP_STAGE2_LZ4 : CLDN_HIP_STAGE2_NONE;
   c->enc.d_offsets = direct_offsets ? stream_offsets : (const uint64_t*)c->d_offsets.p;
   c->enc.offsets.clear();
+  // (no device decoder reads the ZSTD frames: the audit of such a call decodes the stage-1 streams they were made from)
+  c->enc.s1_streams = zstd ? (const uint8_t*)c->d_s1.p : nullptr;
+  c->enc.d_s1_offsets = zstd ? (const uint64_t*)c->d_s1_offsets.p : nullptr;
   if (out_loc == CLDN_HIP_DEVICE) {
     c->enc.valid = true;
     if (stream_offsets && !direct_offsets)
@@ -2418,6 +2464,13 @@ int cldn_hip_audit_last_encode(cldn_hip_codec_t* c, const double* limit, cldn_hi
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   if (cldn_hip_audit_last_encode_clouds(c) < 0) return CLDN_HIP_ERR_ARG;
   cldn_hip_codec::LastEncode E = c->enc;  // (the decode below drops the codec's copy)
+  const cldn_hip_codec::LastEncode kept = c->enc;
+  if (E.kind == CLDN_HIP_STAGE2_ZSTD) {  // the stage-1 streams of the call, still in the codec's workspace
+    E.streams = E.s1_streams;
+    E.d_offsets = E.d_s1_offsets;
+    E.offsets.clear();
+    E.kind = CLDN_HIP_STAGE2_NONE;
+  }
   const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
   if (n_clouds == 0) return CLDN_HIP_OK;
   uint64_t n_points = 0;
@@ -2436,7 +2489,7 @@ int cldn_hip_audit_last_encode(cldn_hip_codec_t* c, const double* limit, cldn_hi
   }
   const int rc = audit_streams_impl(c, E.points, CLDN_HIP_DEVICE, E.streams, CLDN_HIP_DEVICE, E.offsets.data(), E.cloud_points.data(),
                                     n_clouds, E.kind, limit, report, report_loc);
-  c->enc = E;
+  c->enc = kept.kind == CLDN_HIP_STAGE2_ZSTD ? kept : E;
   return rc;
 }
 
@@ -2649,6 +2702,25 @@ int cldn_hip_stream_hist(cldn_hip_codec_t* c, const void* streams, int streams_l
 int cldn_hip_stream_hist_last_encode(cldn_hip_codec_t* c, cldn_hip_hist_t* report, int report_loc) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   if (!c->enc.valid) return no_last_encode("stream_hist_last_encode");  // (a chunk table has no streams before its framing)
+  if (c->enc.kind == CLDN_HIP_STAGE2_ZSTD) {
+    // the stage-1 streams behind the frames, as the audit reads them: the histogram a ZSTD size is estimated from, and what
+    // composes with cldn_hip_sweep_hist_*. (The offsets are read back per call: the kept ones describe the frames.)
+    cldn_hip_codec::LastEncode E = c->enc;
+    const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
+    int rc;
+    if ((rc = report_check("stream_hist", true, n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
+    if (n_clouds == 0) return CLDN_HIP_OK;
+    ENTER_DEVICE(c->device);
+    uint64_t n_points = 0;
+    for (uint64_t n : E.cloud_points) n_points += n;
+    std::vector<uint64_t> offs((size_t)n_clouds + 1, 0);
+    if (n_points == 0) return stream_hist_device(c, nullptr, offs.data(), n_clouds, report, report_loc);
+    HIP_TRY(hipMemcpyAsync(offs.data(), E.d_s1_offsets, offs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < n_clouds; ++k)
+      if (offs[k + 1] < offs[k]) return fail(CLDN_HIP_ERR_DEVICE, "stream_hist_last_encode: the encode call left no valid stream offsets (see cldn_hip_codec_status)");
+    return stream_hist_device(c, E.s1_streams, offs.data(), n_clouds, report, report_loc);
+  }
   cldn_hip_codec::LastEncode& E = c->enc;
   const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
   int rc;

@@ -247,6 +247,7 @@ struct Run {                       // messages [first, first + count) share a sc
   std::vector<uint64_t> offsets;   // count + 1
   std::vector<uint32_t> chunk_sizes;
   bool estimated = false;          // TranscodeOptions::estimate took this run's histograms: stage 2 reports its actual size
+  bool packed = false;             // TranscodeOptions::device_zstd: `stage1` holds finished [u32 size][ZSTD frame] chunks
   PinnedBytes decoded;             // decode direction: the points of the run's clouds, back to back
   std::vector<uint64_t> out_at;    // decode direction: where every message's points start in `decoded`
 };
@@ -307,6 +308,8 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     if (b.runs.size() <= n_runs) b.runs.emplace_back();  // recycled batches keep their page-locked staging
     Run& run = b.runs[n_runs++];
     run.estimated = false;
+    run.packed = opt.device_zstd && opt.compression == Cloudini::CompressionOption::ZSTD;
+    const int stage2_mode = run.packed ? CLDN_HIP_STAGE2_ZSTD : CLDN_HIP_STAGE2_NONE;
     run.first = r0;
     run.count = static_cast<uint32_t>(r1 - r0);
     const Cloudini::EncodingInfo& info0 = b.parsed[r0].info;
@@ -370,7 +373,7 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     if (b.parsed[r0].viz) {
       Cloudini::amd_detail::encodeStage1BatchViz(info0, ptrs.data(), pts.data(), run.count, b.parsed[r0].viz_xyz_offset,
                                                  b.parsed[r0].viz_resolution, grow, run.offsets, run.chunk_sizes, kept, audit_p,
-                                                 sweep_p, modes_p);
+                                                 sweep_p, modes_p, stage2_mode);
       for (uint32_t k = 0; k < run.count; ++k) {  // what the reference's function leaves behind (src/ros_msg_utils.cpp:326-335)
         Parsed& p = b.parsed[r0 + k];
         p.points = kept[k];
@@ -386,7 +389,7 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       }
     } else {
       Cloudini::amd_detail::encodeStage1Batch(info0, ptrs.data(), pts.data(), run.count, grow, run.offsets, run.chunk_sizes, audit_p,
-                                              sweep_p, modes_p);
+                                              sweep_p, modes_p, stage2_mode);
     }
     if (modes_p && stats && modes.adaptive_fields) {  // the run's cells, summed over its messages, into the per-name summary
       std::vector<ModeFieldSummary> part(modes.adaptive_fields);  // names from the plan's own list of adaptive fields
@@ -452,7 +455,12 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       }
       stats->mergeEstimate(part);
       for (uint32_t k = 0; k < run.count; ++k) stats->estimate_own_bytes += moved(k, nullptr, nullptr);
-      stats->estimate_stage1_bytes += run.offsets[run.count] - run.offsets[0];
+      if (run.packed) {  // the offsets describe the frames; the stream histograms are of the stage-1 streams behind them
+        for (uint32_t k = 0; k < run.count; ++k)
+          for (int i = 0; i < 256; ++i) stats->estimate_stage1_bytes += sweep.stream_hist[k].bin[i];
+      } else {
+        stats->estimate_stage1_bytes += run.offsets[run.count] - run.offsets[0];
+      }
     }
     if (opt.audit && stats) {  // the run's report, message by message, into the per-name summary
       const size_t nf = info0.fields.size();
@@ -498,6 +506,7 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     size_t slot;         // offset of the job's worst-case slot inside the message's scratch area
     uint32_t packed = 0;
     bool estimated = false;  // the run's histograms were taken and the output is ZSTD: its size goes next to the estimate
+    bool finished = false;   // the GPU stage wrote the chunk's ZSTD frame already: it is copied
   };
   const size_t n = b.in.size();
   std::vector<Job> jobs;
@@ -528,6 +537,7 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
         j.src_size = size;
         j.slot = slot;
         j.estimated = run.estimated && opt.compression == Cloudini::CompressionOption::ZSTD;
+        j.finished = run.packed;
         jobs.push_back(j);
         slot += 4 + Cloudini::amd_detail::compressedChunkBound(opt.compression, size);
         s += 4 + size;
@@ -542,7 +552,7 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
   Cloudini::amd_detail::runOnStage2Pool(jobs.size(), [&](size_t ji) {
     Job& j = jobs[ji];
     uint8_t* dst = b.out[j.msg].data() + scratch_at[j.msg] + j.slot;
-    if (direct) {
+    if (direct || j.finished) {
       std::memcpy(dst + 4, j.src, j.src_size);
       j.packed = j.src_size;
     } else {
@@ -836,6 +846,7 @@ void checkOptions(const TranscodeOptions& opt) {
   if (opt.estimate && opt.sweep.empty()) throw std::invalid_argument("TranscodeOptions: estimate needs sweep");
   if (opt.decode && opt.modes != TranscodeOptions::Modes::Off)
     throw std::invalid_argument("TranscodeOptions: modes is not available together with decode");
+  if (opt.decode && opt.device_zstd) throw std::invalid_argument("TranscodeOptions: device_zstd is not available together with decode");
   for (const auto& named : opt.sweep)
     if (named.second.size() > CLDN_HIP_SWEEP_MAX_CANDIDATES)
       throw std::invalid_argument("TranscodeOptions: the sweep ladder of " + named.first + " has more than 16 resolutions");

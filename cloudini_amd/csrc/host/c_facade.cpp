@@ -347,6 +347,12 @@ CLDN_EXPORT int cldn_amd_set_device_lz4(int on) {
   return Cloudini::amd_detail::deviceLz4Level();
 }
 
+CLDN_EXPORT int cldn_amd_device_zstd(void) { return Cloudini::amd_detail::deviceZstd() ? 1 : 0; }
+CLDN_EXPORT int cldn_amd_set_device_zstd(int on) {
+  Cloudini::amd_detail::setDeviceZstd(on != 0);
+  return Cloudini::amd_detail::deviceZstd() ? 1 : 0;
+}
+
 CLDN_EXPORT int cldn_amd_device_lz4_decode(void) { return Cloudini::amd_detail::deviceLz4Decode() ? 1 : 0; }
 CLDN_EXPORT int cldn_amd_set_device_lz4_decode(int on) {
   Cloudini::amd_detail::setDeviceLz4Decode(on != 0);

@@ -780,14 +780,17 @@ size_t PointcloudEncoder::encode(ConstBufferView cloud_data, BufferView& output,
     }
   } trim{tl_stage1, tl_stage2};
   impl_->chunk_sizes.resize(n_chunks);
-  if (info_.compression_opt == CompressionOption::LZ4 && amd_detail::deviceLz4()) {
+  const bool device_lz4 = info_.compression_opt == CompressionOption::LZ4 && amd_detail::deviceLz4();
+  const bool device_zstd = info_.compression_opt == CompressionOption::ZSTD && amd_detail::deviceZstd();
+  if (device_lz4 || device_zstd) {
     // stage 2 on the device as well: the codec writes [u32 size][LZ4 block] per chunk straight
     // into the caller's buffer. Valid LZ4 blocks (the reference's decoder reads them), not lz4's own bytes.
+    // ZSTD (amd_detail::setDeviceZstd): [u32 size][frame of literal-only blocks] per chunk -- valid frames, not libzstd's bytes.
     struct Reset {
       cldn_hip_codec_t* codec;
       ~Reset() { (void)cldn_hip_codec_set_stage2(codec, CLDN_HIP_STAGE2_NONE); }  // the codec goes back to the pool
     } reset{impl_->codec};
-    const int lz_mode = amd_detail::deviceLz4Level() >= 2 ? CLDN_HIP_STAGE2_LZ4_FAST : CLDN_HIP_STAGE2_LZ4;
+    const int lz_mode = device_zstd ? CLDN_HIP_STAGE2_ZSTD : amd_detail::deviceLz4Level() >= 2 ? CLDN_HIP_STAGE2_LZ4_FAST : CLDN_HIP_STAGE2_LZ4;
     if (cldn_hip_codec_set_stage2(impl_->codec, lz_mode) != CLDN_HIP_OK) throw std::runtime_error(cldn_hip_last_error());
     uint64_t offsets[2] = {0, 0};
     if (cldn_hip_encode_stage1(impl_->codec, cloud_data.data(), CLDN_HIP_HOST, &points, 1, dst + written, output.size() - written,
@@ -1026,6 +1029,14 @@ bool deviceLz4() { return deviceLz4Level() != 0; }
 void setDeviceLz4(bool on) { g_device_lz4.store(on ? 1 : 0); }
 void setDeviceLz4Level(int level) { g_device_lz4.store(level >= 2 ? 2 : (level == 1 ? 1 : 0)); }
 
+// ZSTD frames written by the device (CLDN_HIP_STAGE2_ZSTD: literal-only blocks). Off unless a caller turns it on: there is no
+// environment switch
+namespace {
+std::atomic<bool> g_device_zstd{false};
+}
+bool deviceZstd() { return g_device_zstd.load(); }
+void setDeviceZstd(bool on) { g_device_zstd.store(on); }
+
 namespace {
 std::atomic<bool> g_device_lz4_decode{false};
 }
@@ -1084,7 +1095,8 @@ static int modesLastEncode(cldn_hip_codec_t* codec, const cldn_hip_plan_t* plan,
 
 void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
-                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit, SweepRequest* sweep, ModesRequest* modes) {
+                       std::vector<uint32_t>& chunk_sizes, AuditRequest* audit, SweepRequest* sweep, ModesRequest* modes,
+                       int stage2) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1101,11 +1113,13 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
     }
     return rc;
   };
-  int rc = encode();
+  int rc = cldn_hip_codec_set_stage2(codec, stage2);
+  if (rc == CLDN_HIP_OK) rc = encode();
   if (rc == CLDN_HIP_OK && modes) rc = modesLastEncode(codec, plan.plan, n_clouds, modes, encode);
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
+  (void)cldn_hip_codec_set_stage2(codec, CLDN_HIP_STAGE2_NONE);  // the codec goes back to the pool
   pool().release(info, codec);
   if (rc != CLDN_HIP_OK) throw std::runtime_error(err);
   chunk_sizes.resize((size_t)n_chunks);
@@ -1114,7 +1128,8 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
 void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
-                          std::vector<uint64_t>& kept_points, AuditRequest* audit, SweepRequest* sweep, ModesRequest* modes) {
+                          std::vector<uint64_t>& kept_points, AuditRequest* audit, SweepRequest* sweep, ModesRequest* modes,
+                          int stage2) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;  // of the input: an upper bound of what the filtered clouds have
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1132,11 +1147,13 @@ void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_
     }
     return rc;
   };
-  int rc = encode();  // (a second encode filters again: the same survivors)
+  int rc = cldn_hip_codec_set_stage2(codec, stage2);
+  if (rc == CLDN_HIP_OK) rc = encode();  // (a second encode filters again: the same survivors)
   if (rc == CLDN_HIP_OK && modes) rc = modesLastEncode(codec, plan.plan, n_clouds, modes, encode);
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
+  (void)cldn_hip_codec_set_stage2(codec, CLDN_HIP_STAGE2_NONE);  // the codec goes back to the pool
   pool().release(info, codec);
   if (rc != CLDN_HIP_OK) throw std::runtime_error(err);
   kept_points.resize(n_clouds);

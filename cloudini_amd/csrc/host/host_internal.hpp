@@ -63,7 +63,10 @@ struct ModesRequest {
 void encodeStage1Batch(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
                        std::vector<uint32_t>& chunk_sizes, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr,
-                       ModesRequest* modes = nullptr);
+                       ModesRequest* modes = nullptr, int stage2 = 0);
+// `stage2` (both calls): the codec's stage-2 mode for the call (cldn_hip_codec_set_stage2; 0 = CLDN_HIP_STAGE2_NONE). With
+// CLDN_HIP_STAGE2_ZSTD the streams are [u32 size][ZSTD frame] per chunk and chunk_sizes the frame sizes: finished chunks of
+// a ZSTD message, nothing is left for the host's stage 2.
 // The same behind the viz pre-filter (cldn_hip_encode_stage1_viz_gather): every cloud is filtered on its own, the survivors
 // are encoded without leaving the device. kept_points gets n_clouds survivor counts; stream_offsets and chunk_sizes describe
 // the filtered clouds (a cloud that loses every point has an empty stream and no chunk).
@@ -71,7 +74,7 @@ void encodeStage1BatchViz(const Cloudini::EncodingInfo& info, const uint8_t* con
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
                           std::vector<uint64_t>& kept_points, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr,
-                          ModesRequest* modes = nullptr);
+                          ModesRequest* modes = nullptr, int stage2 = 0);
 // detail::CompressChunk (src/codec_common.cpp:220-258) and its worst-case output size
 uint32_t compressChunkTo(Cloudini::CompressionOption opt, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_cap);
 size_t compressedChunkBound(Cloudini::CompressionOption opt, size_t stage1_bytes);
@@ -92,6 +95,8 @@ void setDeviceLz4Level(int level);
 // The way back: PointcloudDecoder::decode of an LZ4 message (wire version >= 3) uploads the compressed body and lets
 // cldn_hip_decode_lz4 undo stage 2 on the device instead of LZ4_decompress_safe on the host pool. Off by default, no
 // environment variable; with it off every path is what it was.
+bool deviceZstd();               // PointcloudEncoder::encode with CompressionOption::ZSTD writes the device's literal-only frames
+void setDeviceZstd(bool on);     // (default off; valid ZSTD frames, not libzstd's bytes)
 bool deviceLz4Decode();
 void setDeviceLz4Decode(bool on);
 

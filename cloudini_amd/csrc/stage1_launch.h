@@ -216,6 +216,46 @@ struct Lz4Launch {
 };
 int lz4_launch(const Lz4Launch& L);
 
+// ---- stage 2 on the device: ZSTD frame of literal-only blocks per chunk (zstd_kernels.hip; restated in tests/zstd_lit_model.py) ----
+constexpr uint32_t kZsBlockBytes = 131072;  // a frame's blocks: consecutive pieces of the payload
+constexpr uint32_t kZsMinHuf = 64;          // a block below this is Raw
+constexpr uint32_t kZsFourStreams = 256;    // one Huffman stream below, four from here on
+constexpr uint32_t kZsDescBytes = 128;      // a tree description: its head byte and at most 127 more
+constexpr uint32_t kZsRaw = 0, kZsRle = 1, kZsHuf = 2;  // (the block types of the format)
+struct ZsBlock {
+  uint32_t chunk, off, n;   // the block is [off, off + n) of the chunk's payload
+  uint32_t kind;
+  uint32_t body;            // bytes behind the 3-byte block header
+  uint32_t form, hdr_bytes; // literals section header: size format and bytes
+  uint32_t desc_bytes;      // tree description
+  uint32_t comp;            // tree description + jump table + streams
+  uint32_t stream[4];       // bytes of the streams
+  uint32_t rle;             // the byte of an RLE block
+};
+struct ZstdLaunch {
+  hipStream_t stream;
+  const uint8_t* stage1;          // framed stage-1 streams (the payload of chunk c starts at chunk_dst[c] + 4)
+  uint64_t stage1_capacity;       // bytes of that buffer: a payload that does not lie inside is not read
+  const uint64_t* chunk_dst;
+  const uint32_t* chunk_payload;
+  uint32_t n_chunks;
+  uint64_t max_blocks;            // upper bound of the blocks of the batch (payload bound / block bytes + n_chunks)
+  uint32_t* blk_first;            // [n_chunks + 1]: compact block numbering
+  uint32_t* chunk_state;          // [n_chunks]
+  ZsBlock* blocks;                // [max_blocks]
+  uint32_t* codes;                // [max_blocks * 256]: length << 16 | code value
+  uint8_t* descs;                 // [max_blocks * kZsDescBytes]
+  uint64_t* block_dst;            // [max_blocks + 1]: where a block's header goes in `out` (a chunk's first: its [u32] prefix)
+  const uint32_t* cloud_first_chunk;  // [n_clouds + 1]
+  uint32_t n_clouds;
+  uint32_t* frame_sizes_out;      // [n_chunks]: what chunk_sizes reports
+  uint64_t* stream_offsets;       // [n_clouds + 1]
+  uint8_t* out;
+  uint64_t out_capacity;
+  uint32_t* status;
+};
+int zstd_launch(const ZstdLaunch& L);
+
 // ---- LZ4 blocks back into bytes on the device (lz4_decode.hip) ----
 constexpr uint32_t kLz4Rejected = 0xffffffffu;  // sizes[k] of a block the strict rules refuse
 struct Lz4DecompressLaunch {

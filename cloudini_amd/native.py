@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_SO = os.environ.get("CLDN_HIP_LIB_OVERRIDE") or os.path.join(HERE, "lib", "libcloudini_hip.so")  # override: A/B builds
 
 HOST, DEVICE = 0, 1
+STAGE2_NONE, STAGE2_LZ4, STAGE2_LZ4_FAST, STAGE2_ZSTD = 0, 1, 2, 3   # cldn_hip_codec_set_stage2
 
 ERRORS = {-1: "ARG", -2: "CAPACITY", -3: "UNSUPPORTED", -4: "DEVICE", -5: "NO_DEVICE", -6: "CORRUPT", -7: "NOMEM"}
 
@@ -459,7 +460,8 @@ class Codec:
 
     def set_stage2(self, stage2: int):
         """0 = stage-1 streams (default), 1 = [u32 size][LZ4 block] per chunk, compressed on the device, 2 = the same with the
-        FAST parameters (4 KiB sub-ranges: ~1.5 x the speed, blocks ~3 % larger)."""
+        FAST parameters (4 KiB sub-ranges: ~1.5 x the speed, blocks ~3 % larger), 3 (STAGE2_ZSTD) = [u32 size][ZSTD frame of
+        literal-only blocks] per chunk: valid frames for any ZSTD decoder, not libzstd's bytes."""
         _check(lib().cldn_hip_codec_set_stage2(self._h, int(stage2)))
         self._stage2 = int(stage2)
 

@@ -179,6 +179,13 @@ struct TranscodeOptions {
   // Not available together with `decode`.
   enum class Modes { Off, Report, Best };
   Modes modes = Modes::Off;
+  // ZSTD on the device (include/cloudini_hip.h, CLDN_HIP_STAGE2_ZSTD). With `compression` == ZSTD the GPU stage writes every
+  // chunk as a finished [u32 size][ZSTD frame] and stage 2 passes it on: no libzstd call on the host. The frames hold
+  // literal-only blocks (Huffman-coded literals, no sequences): every ZSTD decoder reads them and the messages decode to the
+  // same points, but they are NOT libzstd's bytes, and schemas whose streams repeat (lossless float64 stamps) come out larger.
+  // `estimate`'s estimate_actual_bytes still adds up what was written. Other compressions ignore the option. Not available
+  // together with `decode`.
+  bool device_zstd = false;
   // Test hook (tests/cpp/transcoder_order.cpp, runs without a GPU): when set, `test_workers` stage threads call it instead of
   // the GPU stage and stage 2 passes the batch on untouched -- what remains is the pipeline itself: batches handed to
   // whichever stage is free, the writer putting them back into input order, an error on any stage stopping all of them.

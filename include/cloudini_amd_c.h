@@ -152,6 +152,13 @@ uint32_t cldn_amd_set_stage2_threads(uint32_t n);
  * messages and ZSTD keep the host route. Off by default, no environment variable. Both return the value in effect (0, 1). */
 int cldn_amd_device_lz4_decode(void);
 int cldn_amd_set_device_lz4_decode(int on);
+/* Stage 2 of ZSTD streams on the GPU (include/cloudini_hip.h, CLDN_HIP_STAGE2_ZSTD): PointcloudEncoder::encode with
+ * compression_opt == ZSTD then receives [u32 size][ZSTD frame] per chunk from the device. The frames are valid ZSTD frames of
+ * literal-only blocks (Huffman-coded literals, no sequences) that the reference's decoder and this library's read; they are
+ * not libzstd's bytes, and where ZSTD finds matches (lossless float64 fields) they are larger. Off by default, no environment
+ * variable. Both return the value in effect (0, 1). */
+int cldn_amd_device_zstd(void);
+int cldn_amd_set_device_zstd(int on);
 
 #ifdef __cplusplus
 }

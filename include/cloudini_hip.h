@@ -176,10 +176,25 @@ int cldn_hip_encode_stage1_gather(cldn_hip_codec_t* codec, const void* const* cl
  * (= MaxCompressedSize for LZ4, src/cloudini.cpp:249-292). The blocks are valid LZ4 blocks that LZ4_decompress_safe
  * (the reference's DecompressChunk, src/codec_common.cpp:260-299) turns back into the exact stage-1 payloads; they are
  * NOT the bytes lz4's own compressor would write (a different, data-parallel parse: cloudini_amd/csrc/lz4_kernels.hip,
- * restated serially in oracle/lz4_model.c). The setting stays until changed. Default: CLDN_HIP_STAGE2_NONE. */
+ * restated serially in oracle/lz4_model.c). The setting stays until changed. Default: CLDN_HIP_STAGE2_NONE.
+ *
+ * CLDN_HIP_STAGE2_ZSTD: every chunk is [u32 LE frame size][ZSTD frame of the chunk's stage-1 payload] -- the bytes a stream
+ * with compression_opt == ZSTD holds behind its header. chunk_sizes reports the frame sizes; the capacity is
+ * sum_k cldn_hip_stage2_bound(plan, cloud_points[k], CLDN_HIP_STAGE2_ZSTD) (= MaxCompressedSize for ZSTD: 4 + ZSTD_COMPRESSBOUND
+ * per chunk). What the frames ARE: valid single-segment ZSTD frames with a 4-byte content size, no checksum and no dictionary,
+ * made of blocks of up to 128 KiB that are Raw, RLE, or Compressed with Huffman-coded literals and "0 sequences"; any ZSTD
+ * decoder -- the reference's ZSTD_decompress in DecompressChunk -- returns the exact stage-1 payload. What they are NOT:
+ * libzstd's bytes, or its ratio where ZSTD finds matches: the writer searches none (cloudini_amd/csrc/zstd_kernels.hip,
+ * restated serially in tests/zstd_lit_model.py). On the token streams of lossy stage 1 that costs about a tenth of a percent
+ * up to a percent against level 1; lossless float64 streams can come out up to about twice as large.
+ * There is no device decoder for this mode: behind such a call cldn_hip_audit_last_encode decodes, and
+ * cldn_hip_stream_hist_last_encode counts, the stage-1 streams the frames were made from (they stay in the codec's workspace),
+ * so both report what they report behind a CLDN_HIP_STAGE2_NONE call and the histogram still composes with
+ * cldn_hip_sweep_hist_*. cldn_hip_encode_stage1_chunks refuses the mode as it refuses LZ4. */
 enum { CLDN_HIP_STAGE2_NONE = 0, CLDN_HIP_STAGE2_LZ4 = 1,
-       CLDN_HIP_STAGE2_LZ4_FAST = 2 /* round 5: the same parser on 4 KiB sub-ranges (1024-entry table): twice the resident
-                                       waves, ~1.5 x the speed, blocks ~3 % larger; same bound, same decoder */ };
+       CLDN_HIP_STAGE2_LZ4_FAST = 2, /* round 5: the same parser on 4 KiB sub-ranges (1024-entry table): twice the resident
+                                        waves, ~1.5 x the speed, blocks ~3 % larger; same bound, same decoder */
+       CLDN_HIP_STAGE2_ZSTD = 3 };
 int cldn_hip_codec_set_stage2(cldn_hip_codec_t* codec, int stage2);
 uint64_t cldn_hip_stage2_bound(const cldn_hip_plan_t* plan, uint64_t n_points, int stage2);
 

@@ -98,7 +98,9 @@ int main(int argc, char** argv) {
                  "                                        those messages are NOT the reference encoder's bytes; they are valid streams that\n"
                  "                                        every Cloudini decoder decodes to the same points\n"
                  "  --estimate                             with --sweep: estimated ZSTD bytes per field and rung (files unchanged)\n"
-                 "  --sweep and --modes are not available with --decode\n", argv[0]);
+                 "  --device-zstd                          with --compression zstd: the GPU writes the ZSTD frames (literal-only blocks:\n"
+                 "                                        valid frames every ZSTD decoder reads, not libzstd's bytes); other compressions ignore it\n"
+                 "  --sweep, --modes and --device-zstd are not available with --decode\n", argv[0]);
     return 2;
   }
   cloudini_amd::TranscodeOptions opt;
@@ -137,6 +139,7 @@ int main(int argc, char** argv) {
       }
     }
     else if (a == "--estimate") opt.estimate = true;
+    else if (a == "--device-zstd") opt.device_zstd = true;
     else if (a == "--modes" && i + 1 < argc) {
       const std::string v = argv[++i];
       if (v != "report" && v != "best") {
@@ -168,6 +171,10 @@ int main(int argc, char** argv) {
   }
   if (opt.estimate && (opt.decode || opt.sweep.empty())) {
     std::fprintf(stderr, "--estimate needs --sweep and is not available with --decode\n");
+    return 2;
+  }
+  if (opt.decode && opt.device_zstd) {
+    std::fprintf(stderr, "--device-zstd is not available with --decode\n");
     return 2;
   }
   if (opt.decode && opt.modes != cloudini_amd::TranscodeOptions::Modes::Off) {
