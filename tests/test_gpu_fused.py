@@ -251,8 +251,8 @@ def test_tail_op_behind_the_floatn_lanes(oracle, kind):
     step = info.point_step
     parts = [data[: 40000 * step], data[40000 * step: 40100 * step], data[:0], data[40100 * step:]]
     check_encode(oracle, info, parts)
-    # and the way back (these layouts decode through k_decode_varint<8> or, with raw / Gorilla bytes in the point stream,
-    # through the serial decoder): bit for bit the oracle's decode, untouched bytes included
+    # and the way back (on the parallel decoders too: a Gorilla-coded double in the point stream takes k_decode_stream_w's MODE 2,
+    # tests/test_gpu_gorilla.py asserts which chunks stay there): bit for bit the oracle's decode, untouched bytes included
     n = data.size // step
     codec = native.Codec(native.Plan(info))
     out = np.full(data.size, 0x5D, dtype=np.uint8)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import cases
+import gorilla_cases
 from cloudini_amd.schema import CompressionOption
 
 
@@ -38,6 +39,17 @@ def test_decode_matches_reference(oracle, reflib, name, info, data):
     stream = reflib.encode_stage1(info, data)
     got = oracle.decode_stage1(info, stream, n, fill=0x5A)
     assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("row", gorilla_cases.EXPRESSIBLE, ids=[r.name for r in gorilla_cases.EXPRESSIBLE])
+def test_constructed_gorilla_rows_match_reference(oracle, reflib, row):
+    """The rows of tests/gorilla_cases.py an encoder can write (Gorilla tokens chosen one by one: every length, the clamp of the
+    stored leading count, openers at chosen points): the oracle against the compiled reference, both ways."""
+    info, data = row.info(), row.cloud()
+    want = reflib.encode_stage1(info, data)
+    assert np.array_equal(oracle.encode_stage1(info, data), want)
+    want_dec, _yaml = reflib.decode(reflib.encode(info, data), len(data), fill=0x5A)
+    assert np.array_equal(oracle.decode_stage1(info, want, row.n, fill=0x5A), want_dec)
 
 
 @pytest.mark.parametrize("seed", cases.VERY_WIDE_SEEDS)
