@@ -196,7 +196,7 @@ struct cldn_hip_codec {
   uint64_t ct_slot_stride = 0, ct_need = 0;
   size_t ct_segs_off = 0, ct_anchor_off = 0;
   int stage2 = 0;
-  DevBuf d_s1, d_s1_offsets, d_lz_matches, d_lz_counts, d_payload2, d_dst2, d_dec_split;
+  DevBuf d_s1, d_s1_offsets, d_lz_matches, d_stage2_ws, d_payload2, d_dst2, d_dec_split;
   // LZ4 blocks back into bytes (cldn_hip_decode_lz4 / cldn_hip_lz4_decompress): one worst-case slot per chunk, the offset tables
   DevBuf d_lzd_slots, d_lzd_tables;
   DevBuf d_finrec;            // k_finish look-back records (rec, rec2), cleared only when (re)allocated
@@ -657,7 +657,7 @@ void cldn_hip_codec_destroy(cldn_hip_codec_t* c) {
   (void)guard.enter(c->device);
   (void)hipStreamSynchronize(c->stream);
   DevBuf* bufs[] = {&c->d_in, &c->d_out, &c->d_slots, &c->d_chunks, &c->d_cloud_first, &c->d_finrec, &c->d_dec_rec, &c->d_dec_bits, &c->d_dec_secs, &c->d_s1, &c->d_s1_offsets,
-                    &c->d_lz_matches, &c->d_lz_counts, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables,
+                    &c->d_lz_matches, &c->d_stage2_ws, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables,
                     &c->d_payload, &c->d_dst, &c->d_offsets, &c->d_modes, &c->d_status, &c->d_dec_meta, &c->d_pre_ptrs, &c->d_dec_cols[0], &c->d_dec_cols[1], &c->d_dec_cols[2], &c->d_dec_cols[3], &c->d_dec_cols[4], &c->d_dec_cols[5], &c->d_dec_cols[6], &c->d_dec_cols[7],
                     &c->d_viz_keys, &c->d_viz_slot, &c->d_viz_blocks, &c->d_viz_bits, &c->d_viz_tables, &c->d_viz_kept, &c->d_viz_out,
                     &c->d_pieces, &c->d_audit, &c->d_audit_tab, &c->d_audit_rep};
@@ -933,6 +933,77 @@ static int stage_host_input(cldn_hip_codec* c, const void* points, const void* c
   return CLDN_HIP_OK;
 }
 
+// Stage 2 on the device, behind stage1_launch_encode of a call whose codec asks for it: the chunks' stage-1 payloads in d_s1 become
+// LZ4 blocks (lz4_kernels.hip) or ZSTD frames of literal-only blocks (zstd_kernels.hip), written straight into the framed streams
+// at `out`, with their sizes and the clouds' stream offsets (d_offsets). *d_sizes becomes the buffer chunk_sizes reports where a
+// writer ran. The payloads of the batch are bounded by need_s1, the size of d_s1.
+static int launch_device_stage2(cldn_hip_codec_t* c, uint32_t n_chunks, uint32_t n_clouds, uint64_t need_s1, uint8_t* out,
+                                uint64_t out_capacity, const void** d_sizes) {
+  int rc;
+  if (n_chunks == 0u) {
+    HIP_TRY(hipMemsetAsync(c->d_offsets.p, 0, (size_t)(n_clouds + 1) * sizeof(uint64_t), c->stream));
+    return CLDN_HIP_OK;
+  }
+  Stage2Io io;
+  io.stream = c->stream;
+  io.stage1 = (const uint8_t*)c->d_s1.p;
+  io.stage1_capacity = need_s1;
+  io.chunk_dst = (const uint64_t*)c->d_dst.p;
+  io.chunk_payload = (const uint32_t*)c->d_payload.p;
+  io.n_chunks = n_chunks;
+  io.cloud_first_chunk = (const uint32_t*)c->d_cloud_first.p;
+  io.n_clouds = n_clouds;
+  io.chunk_sizes = (uint32_t*)c->d_payload2.p;
+  io.stream_offsets = (uint64_t*)c->d_offsets.p;
+  io.out = out;
+  io.out_capacity = out_capacity;
+  io.status = (uint32_t*)c->d_status.p;
+  if (c->stage2 == CLDN_HIP_STAGE2_ZSTD) {
+    // every chunk has ceil(payload / 128 KiB) blocks, one at least
+    const uint64_t max_blocks = need_s1 / kZsBlockBytes + n_chunks;
+    if ((rc = c->d_stage2_ws.ensure(ZstdLaunch::workspace_bytes(max_blocks, n_chunks))) != CLDN_HIP_OK) return rc;
+    ZstdLaunch Z;
+    Z.io = io;
+    Z.carve(c->d_stage2_ws.p, max_blocks, n_chunks);
+    if ((rc = zstd_launch(Z)) != CLDN_HIP_OK) return rc;
+    *d_sizes = c->d_payload2.p;
+    return CLDN_HIP_OK;
+  }
+  // every chunk has ceil(payload / sub-range bytes) sub-ranges
+  const bool lz4_fast = c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST;
+  const uint32_t lz_sub = lz4_fast ? kLzFastSubBytes : kLzSubBytes, lz_mm = lz4_fast ? kLzFastMaxMatches : kLzMaxMatches;
+  uint64_t max_subs = need_s1 / lz_sub + n_chunks;
+  // the match lists take as many bytes as the payloads they describe: sized from the worst-case stage-1 bound that is
+  // gigabytes for a large batch (32 x 1 M XYZI points: 1.3 GB for 207 MB of payload). Beyond 256 MB the call waits for
+  // stage 1 and sizes them from the bytes it really wrote (one 8-byte read; the wait is ~5 % of what the LZ4 stage takes)
+  bool stage1_failed = false;
+  if (max_subs * lz_mm * sizeof(LzMatch) > (256ull << 20)) {
+    uint64_t total_s1 = 0;
+    uint32_t st1 = 0;  // the status word travels with the total: behind a stage 1 that gave up (ST_FINISH_TIMEOUT: k_finish
+                       // returned before it wrote offsets, payload sizes and positions) the total is a stale number
+    HIP_TRY(hipMemcpyAsync(&total_s1, (const uint64_t*)c->d_s1_offsets.p + n_clouds, sizeof(total_s1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&st1, c->d_status.p, sizeof(st1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    stage1_failed = st1 != 0u;
+    if (!stage1_failed && total_s1 <= need_s1) max_subs = total_s1 / lz_sub + n_chunks;  // (every chunk's last sub-range may be partial)
+  }
+  if (stage1_failed) {  // no LZ4 stage over stale sizes: the status handling of the caller (ticket retry / error) takes it from here
+    HIP_TRY(hipMemsetAsync(c->d_offsets.p, 0, (size_t)(n_clouds + 1) * sizeof(uint64_t), c->stream));
+    return CLDN_HIP_OK;
+  }
+  if ((rc = c->d_lz_matches.ensure((size_t)max_subs * lz_mm * sizeof(LzMatch))) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_stage2_ws.ensure(Lz4Launch::workspace_bytes(max_subs, n_chunks))) != CLDN_HIP_OK) return rc;
+  Lz4Launch Z;
+  Z.io = io;
+  Z.fast = lz4_fast ? 1u : 0u;
+  Z.matches = (LzMatch*)c->d_lz_matches.p;
+  Z.block_dst = (uint64_t*)c->d_dst2.p;
+  Z.carve(c->d_stage2_ws.p, max_subs, n_chunks);
+  if ((rc = lz4_launch(Z)) != CLDN_HIP_OK) return rc;
+  *d_sizes = c->d_payload2.p;
+  return CLDN_HIP_OK;
+}
+
 static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int points_loc, const void* const* cloud_ptrs,
                               const uint64_t* cloud_points, uint32_t n_clouds, void* out, uint64_t out_capacity, int out_loc,
                               uint64_t* stream_offsets, uint32_t* chunk_sizes, uint8_t* modes,
@@ -957,11 +1028,10 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   const uint32_t step = plan.point_step;
 
   const bool wide = c->plan.wide;  // stage1_wide.h: the plan's arrays live in device memory, one segment per chunk
-  // `lz4`: stage 2 runs on the device, of either kind -- the stage-1 streams go to d_s1, the call's output is written by the
-  // stage-2 kernels. `zstd`: those are zstd_kernels.hip's
+  // stage 2 runs on the device (launch_device_stage2): the stage-1 streams go to d_s1, the call's output is written by the
+  // stage-2 kernels. `zstd`: those are zstd_kernels.hip's, else lz4_kernels.hip's
+  const bool device_stage2 = c->stage2 != CLDN_HIP_STAGE2_NONE;
   const bool zstd = c->stage2 == CLDN_HIP_STAGE2_ZSTD;
-  const bool lz4 = c->stage2 == CLDN_HIP_STAGE2_LZ4 || c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST || zstd;
-  const bool lz4_fast = c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST;
   const uint32_t n_adaptive = c->plan.n_adaptive_total();
   // capacity contract of PointcloudEncoder::encode (cloudini.cpp:531-534)
   uint64_t need = 0, need_s1 = 0, n_chunks64 = 0, n_points = 0;
@@ -1001,7 +1071,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   F.pipeline = (uint8_t)c->pipeline;
   F.wide = wide;
   F.chunks_only = table != nullptr;
-  F.lz4 = lz4;
+  F.lz4 = device_stage2;  // (of either kind)
   // device-resident inputs decide the kernel variant by their address; host inputs are staged into d_in (checked where it is filled)
   F.points_misaligned = points_loc == CLDN_HIP_DEVICE ? (uint8_t)((uintptr_t)points & 3u) : (uint8_t)0;
   for (uint32_t a = 0; a < (uint32_t)kMaxAdaptive; ++a) F.mode_hint[a] = c->hint_valid ? c->hint_cache[a] : (uint8_t)0xF;
@@ -1014,10 +1084,10 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   }
   // device-resident outputs: the probe workgroups of the piece kernel write the caller's modes array as well (a byte store
   // fits any address); where another kernel decides the modes, or the caller forced them, the copy behind the call stays
-  uint8_t* const caller_modes = (out_loc == CLDN_HIP_DEVICE && !lz4 && !table && !F.modes_forced) ? modes : nullptr;
+  uint8_t* const caller_modes = (out_loc == CLDN_HIP_DEVICE && !device_stage2 && !table && !F.modes_forced) ? modes : nullptr;
   F.caller_modes = caller_modes != nullptr;
   F.zero_block_reused = true;  // (known once the block is sized, see below)
-  F.out_capacity = lz4 ? need_s1 : out_capacity;
+  F.out_capacity = device_stage2 ? need_s1 : out_capacity;
   F.wide_adaptive = n_adaptive;
   F.wide_gorilla = wide ? c->wide_desc.n_gorilla : 0u;
   EncodeRoute R = encode_route(plan, F);
@@ -1115,7 +1185,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
       if ((rc = c->d_out.ensure((size_t)need)) != CLDN_HIP_OK) return rc;
       d_outp = (uint8_t*)c->d_out.p;
     }
-    if (lz4) {
+    if (device_stage2) {
       if ((rc = c->d_s1.ensure((size_t)need_s1)) != CLDN_HIP_OK) return rc;
       if ((rc = c->d_s1_offsets.ensure((size_t)(n_clouds + 1) * sizeof(uint64_t))) != CLDN_HIP_OK) return rc;
       if ((rc = c->d_payload2.ensure((size_t)n_chunks * sizeof(uint32_t))) != CLDN_HIP_OK) return rc;
@@ -1149,11 +1219,11 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   L.pre_out = (uint4* const*)c->d_pre_ptrs.p;
   L.chunk_payload = (uint32_t*)c->d_payload.p;
   L.chunk_dst = (uint64_t*)c->d_dst.p;
-  L.stream_offsets = lz4 ? (uint64_t*)c->d_s1_offsets.p : (uint64_t*)c->d_offsets.p;
+  L.stream_offsets = device_stage2 ? (uint64_t*)c->d_s1_offsets.p : (uint64_t*)c->d_offsets.p;
   // device-resident outputs: the kernels write the caller's stream_offsets / chunk_sizes arrays themselves (no copy behind
   // the call: a device-to-device copy of a few bytes costs a launch, 3-5 us of a 50 us call)
-  const bool direct_offsets = out_loc == CLDN_HIP_DEVICE && !lz4 && !table && stream_offsets != nullptr && ((uintptr_t)stream_offsets & 7u) == 0u;
-  const bool direct_sizes = out_loc == CLDN_HIP_DEVICE && !lz4 && !table && chunk_sizes != nullptr && ((uintptr_t)chunk_sizes & 3u) == 0u;
+  const bool direct_offsets = out_loc == CLDN_HIP_DEVICE && !device_stage2 && !table && stream_offsets != nullptr && ((uintptr_t)stream_offsets & 7u) == 0u;
+  const bool direct_sizes = out_loc == CLDN_HIP_DEVICE && !device_stage2 && !table && chunk_sizes != nullptr && ((uintptr_t)chunk_sizes & 3u) == 0u;
   if (direct_offsets) L.stream_offsets = stream_offsets;
   if (direct_sizes) L.chunk_payload = chunk_sizes;
   L.modes = (uint8_t*)c->d_modes.p;
@@ -1182,8 +1252,8 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
     L.n_pieces = c->n_pieces;
     L.wgrec = L.fin_rec2 + n_chunks;
   }
-  L.out = lz4 ? (uint8_t*)c->d_s1.p : d_outp;
-  L.out_capacity = lz4 ? need_s1 : out_capacity;
+  L.out = device_stage2 ? (uint8_t*)c->d_s1.p : d_outp;
+  L.out_capacity = device_stage2 ? need_s1 : out_capacity;
   L.status = (uint32_t*)c->d_status.p;
   const size_t n_slots = c->slot_valid.size();
   const size_t slot = n_slots ? (size_t)(c->call_index % n_slots) : 0;
@@ -1191,98 +1261,9 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   const bool modes_in_place = R.writes_caller_modes;  // the kernels write the caller's modes array
   rc = stage1_launch_encode(L);
   if (rc != CLDN_HIP_OK) return rc;
+  // stage 2 on the device writes the call's output and its own chunk sizes
   const void* d_sizes = c->d_payload.p;  // what chunk_sizes reports
-  if (zstd && n_chunks) {
-    // stage 2 on the device: a ZSTD frame of literal-only blocks per chunk payload (zstd_kernels.hip), written straight into the
-    // framed streams. Every chunk has ceil(payload / 128 KiB) blocks, one at least; the payloads are bounded by need_s1
-    const uint64_t max_blocks = need_s1 / kZsBlockBytes + n_chunks;
-    const size_t o_codes = ((size_t)max_blocks * sizeof(ZsBlock) + 63u) & ~size_t(63);
-    const size_t o_descs = o_codes + (size_t)max_blocks * 256u * sizeof(uint32_t);
-    const size_t o_dst = (o_descs + (size_t)max_blocks * kZsDescBytes + 63u) & ~size_t(63);
-    const size_t o_first = o_dst + (size_t)(max_blocks + 1u) * sizeof(uint64_t);
-    const size_t o_state = o_first + (size_t)(n_chunks + 1u) * sizeof(uint32_t);
-    if ((rc = c->d_lz_counts.ensure(o_state + (size_t)n_chunks * sizeof(uint32_t))) != CLDN_HIP_OK) return rc;
-    uint8_t* ws = (uint8_t*)c->d_lz_counts.p;
-    ZstdLaunch Z;
-    Z.stream = c->stream;
-    Z.stage1 = (const uint8_t*)c->d_s1.p;
-    Z.stage1_capacity = need_s1;
-    Z.chunk_dst = (const uint64_t*)c->d_dst.p;
-    Z.chunk_payload = (const uint32_t*)c->d_payload.p;
-    Z.n_chunks = n_chunks;
-    Z.max_blocks = max_blocks;
-    Z.blocks = (ZsBlock*)ws;
-    Z.codes = (uint32_t*)(ws + o_codes);
-    Z.descs = ws + o_descs;
-    Z.block_dst = (uint64_t*)(ws + o_dst);
-    Z.blk_first = (uint32_t*)(ws + o_first);
-    Z.chunk_state = (uint32_t*)(ws + o_state);
-    Z.cloud_first_chunk = (const uint32_t*)c->d_cloud_first.p;
-    Z.n_clouds = n_clouds;
-    Z.frame_sizes_out = (uint32_t*)c->d_payload2.p;
-    Z.stream_offsets = (uint64_t*)c->d_offsets.p;
-    Z.out = d_outp;
-    Z.out_capacity = out_capacity;
-    Z.status = (uint32_t*)c->d_status.p;
-    if ((rc = zstd_launch(Z)) != CLDN_HIP_OK) return rc;
-    d_sizes = c->d_payload2.p;
-  } else if (lz4 && n_chunks) {
-    // stage 2 on the device: an LZ4 block per chunk payload (lz4_kernels.hip), written straight into the framed streams
-    // every chunk has ceil(payload / 16 KiB) sub-ranges; the payloads of the batch are bounded by need_s1
-    const uint32_t lz_sub = lz4_fast ? kLzFastSubBytes : kLzSubBytes, lz_mm = lz4_fast ? kLzFastMaxMatches : kLzMaxMatches;
-    uint64_t max_subs = need_s1 / lz_sub + n_chunks;
-    // the match lists take as many bytes as the payloads they describe: sized from the worst-case stage-1 bound that is
-    // gigabytes for a large batch (32 x 1 M XYZI points: 1.3 GB for 207 MB of payload). Beyond 256 MB the call waits for
-    // stage 1 and sizes them from the bytes it really wrote (one 8-byte read; the wait is ~5 % of what the LZ4 stage takes)
-    bool stage1_failed = false;
-    if (max_subs * lz_mm * sizeof(LzMatch) > (256ull << 20)) {
-      uint64_t total_s1 = 0;
-      uint32_t st1 = 0;  // the status word travels with the total: behind a stage 1 that gave up (ST_FINISH_TIMEOUT: k_finish
-                         // returned before it wrote offsets, payload sizes and positions) the total is a stale number
-      HIP_TRY(hipMemcpyAsync(&total_s1, (const uint64_t*)c->d_s1_offsets.p + n_clouds, sizeof(total_s1), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(&st1, c->d_status.p, sizeof(st1), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      stage1_failed = st1 != 0u;
-      if (!stage1_failed && total_s1 <= need_s1) max_subs = total_s1 / lz_sub + n_chunks;  // (every chunk's last sub-range may be partial)
-    }
-    if (stage1_failed) {  // no LZ4 stage over stale sizes: the status handling of the caller (ticket retry / error) takes it from here
-      HIP_TRY(hipMemsetAsync(c->d_offsets.p, 0, (size_t)(n_clouds + 1) * sizeof(uint64_t), c->stream));
-    } else {
-      if ((rc = c->d_lz_matches.ensure((size_t)max_subs * lz_mm * sizeof(LzMatch))) != CLDN_HIP_OK) return rc;
-      if ((rc = c->d_lz_counts.ensure((size_t)(max_subs * 7u + 2u * n_chunks + 1u) * sizeof(uint32_t))) != CLDN_HIP_OK) return rc;
-      Lz4Launch Z;
-      Z.stream = c->stream;
-      Z.stage1 = (const uint8_t*)c->d_s1.p;
-      Z.chunk_dst = (const uint64_t*)c->d_dst.p;
-      Z.chunk_payload = (const uint32_t*)c->d_payload.p;
-      Z.n_chunks = n_chunks;
-      Z.fast = lz4_fast ? 1u : 0u;
-      Z.max_subs = max_subs;
-      Z.matches = (LzMatch*)c->d_lz_matches.p;
-      Z.counts = (uint32_t*)c->d_lz_counts.p;
-      Z.last_end = Z.counts + max_subs;
-      Z.anchor_in = Z.last_end + max_subs;
-      Z.sub_size = Z.anchor_in + max_subs;
-      Z.sub_chunk = Z.sub_size + max_subs;
-      Z.before = Z.sub_chunk + max_subs;
-      Z.next_pos = Z.before + max_subs;
-      Z.block_size = Z.next_pos + max_subs;
-      Z.sub_first = Z.block_size + n_chunks;
-      // the blocks go straight into the framed streams: [u32 size][block] per chunk, positions from a scan of the block sizes
-      Z.cloud_first_chunk = (const uint32_t*)c->d_cloud_first.p;
-      Z.n_clouds = n_clouds;
-      Z.block_dst = (uint64_t*)c->d_dst2.p;
-      Z.block_sizes_out = (uint32_t*)c->d_payload2.p;
-      Z.stream_offsets = (uint64_t*)c->d_offsets.p;
-      Z.out = d_outp;
-      Z.out_capacity = out_capacity;
-      Z.status = (uint32_t*)c->d_status.p;
-      if ((rc = lz4_launch(Z)) != CLDN_HIP_OK) return rc;
-      d_sizes = c->d_payload2.p;
-    }
-  } else if (lz4) {
-    HIP_TRY(hipMemsetAsync(c->d_offsets.p, 0, (size_t)(n_clouds + 1) * sizeof(uint64_t), c->stream));
-  }
+  if (device_stage2 && (rc = launch_device_stage2(c, n_chunks, n_clouds, need_s1, d_outp, out_capacity, &d_sizes)) != CLDN_HIP_OK) return rc;
   // remember this call's modes for the next call's launch hint (no synchronisation: the copy is only looked at
   // once its event has fired)
   // (a hint that is in place is refreshed with every 16th call only: it decides the launch shape, never a byte)
@@ -1329,7 +1310,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   c->enc.points = d_points;
   c->enc.streams = d_outp;
   c->enc.cloud_points.assign(cloud_points, cloud_points + n_clouds);
-  c->enc.kind = zstd ? CLDN_HIP_STAGE2_ZSTD : lz4 ? CLDN_HIP_STAGE2_LZ4 : CLDN_HIP_STAGE2_NONE;
+  c->enc.kind = zstd ? CLDN_HIP_STAGE2_ZSTD : device_stage2 ? CLDN_HIP_STAGE2_LZ4 : CLDN_HIP_STAGE2_NONE;
   c->enc.d_offsets = direct_offsets ? stream_offsets : (const uint64_t*)c->d_offsets.p;
   c->enc.offsets.clear();
   // (no device decoder reads the ZSTD frames: the audit of such a call decodes the stage-1 streams they were made from)

@@ -8,7 +8,8 @@
 // only, the last 5 bytes literals, no match starting within the last 12 bytes.
 //
 // The algorithm is deterministic and restated serially in oracle/lz4_model.c (the GPU tests ask for byte equality):
-//   k_lz4_plan    sub-ranges per chunk -> compact numbering (one scan).
+//   k_lz4_plan    sub-ranges per chunk -> compact numbering (block_running_scan, stage1_prims.h; later kernels find a
+//                 sub-range's chunk with chunk_of).
 //   k_lz4_match   one wave per 8 KiB sub-range of a chunk's payload (CLDN_HIP_STAGE2_LZ4_FAST: 4 KiB): the sub-range is
 //                 staged in LDS next to a hash table of its own positions (2048 / 1024 entries, atomicMax = the most recent
 //                 position wins), so every byte the parser touches is an LDS access. Per step the 64 lanes look at 64
@@ -21,11 +22,12 @@
 //   k_lz4_sizes   per sub-range: bytes of its sequences (a sequence's literals start where the previous match ended,
 //                 whichever sub-range that was in).
 //   k_lz4_layout  per chunk: the sequence bytes in front of every sub-range, the first match behind it, the block's size.
-//   k_lz4_offsets one scan over the chunks: where every [u32 size][block] goes in the caller's output, the size headers, the
-//                 stream offsets of the clouds (what k_finish does for stage-1 payloads).
+//   k_lz4_offsets block_running_scan over the chunks: where every [u32 size][block] goes in the caller's output, the size
+//                 headers, the stream offsets of the clouds (cloud_stream_offsets; what k_finish does for stage-1 payloads).
 //   k_lz4_emit_lds  per sub-range: the sub-range staged in LDS, its sequences assembled in an LDS image of the output span it
 //                 owns, 16-byte stores STRAIGHT INTO THE FRAMED STREAMS (round 5: no block slots, no second framing pass).
 //                 Every literal byte is copied by the wave of the sub-range it lies in, however long a literal run is.
+//                 Wave scans, lds_u32_alignbyte and copy_bytes_16 are stage1_prims.h's.
 //                 lz_emit_direct (the round-3 emit without the LDS image) is the fallback for a span that does not fit
 //                 the image.
 #include <hip/hip_runtime.h>
@@ -37,23 +39,13 @@
 #include "cloudini_hip.h"
 #include "stage1_device.h"
 #include "stage1_launch.h"
+#include "stage1_prims.h"
 
 namespace cldn {
 
 namespace {
 
 constexpr uint32_t kLzHashMul = 2654435761u;
-
-__device__ __forceinline__ uint32_t lz_wave_excl_scan(uint32_t x, uint32_t lane, uint32_t* total) {
-  uint32_t incl = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-    if (lane >= (uint32_t)d) incl += o;
-  }
-  *total = (uint32_t)__shfl((int)incl, 63);
-  return incl - x;
-}
 
 __device__ __forceinline__ uint32_t lz_ext_bytes(uint32_t x) { return x >= 15u ? (x - 15u) / 255u + 1u : 0u; }
 
@@ -69,37 +61,7 @@ __device__ __forceinline__ uint32_t lz_put_ext(uint8_t* o, uint32_t x) {
   return k;
 }
 
-// 4 bytes at any byte offset of an LDS dword array
-__device__ __forceinline__ uint32_t lz_lds_u32(const uint32_t* base, uint32_t byte_off) {
-  const uint32_t i = byte_off >> 2;
-  const uint32_t lo = base[i], hi = base[i + 1u];
-  return __builtin_amdgcn_alignbyte(hi, lo, byte_off);  // (v_alignbyte_b32 uses the two low bits of the shift)
-}
-
 }  // namespace
-
-// n bytes, any alignment, by one wave: 16 bytes per lane and step through unaligned accesses
-__device__ __forceinline__ void lz_copy_wave(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint32_t n, uint32_t lane) {
-  const uint32_t n16 = n >> 4;
-  for (uint32_t i = lane; i < n16; i += 64u) {
-    uint4 w;
-    __builtin_memcpy(&w, src + 16u * i, 16);
-    __builtin_memcpy(dst + 16u * i, &w, 16);
-  }
-  const uint32_t done = n16 << 4;
-  if (lane < (n & 15u)) dst[done + lane] = src[done + lane];
-}
-
-// chunk of compact sub-range index `idx`: the last c with sub_first[c] <= idx
-__device__ __forceinline__ uint32_t lz_chunk_of(const uint32_t* __restrict__ sub_first, uint32_t n_chunks, uint32_t idx) {
-  uint32_t lo = 0u, hi = n_chunks;  // invariant: sub_first[lo] <= idx < sub_first[hi]
-  while (hi - lo > 1u) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (sub_first[mid] <= idx) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // one workgroup: sub_first[c] = sub-ranges of the chunks before c (sub_first[n_chunks] = all of them)
 // (a chunk without a byte of payload has no sub-range and no wave below: its block, the single token 0x00, is written by k_lz4_offsets)
@@ -110,23 +72,13 @@ __global__ __launch_bounds__(1024) void k_lz4_plan(const uint32_t* __restrict__ 
                                                    uint32_t* __restrict__ sub_first, uint32_t sub_bytes, uint32_t max_subs,
                                                    uint32_t* __restrict__ status) {
   __shared__ uint32_t wtot[16];
-  __shared__ uint32_t carry;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  if (tid == 0u) carry = 0u;
-  __syncthreads();
+  const uint32_t tid = threadIdx.x;
+  uint32_t carry = 0u;
   for (uint32_t base = 0; base < n_chunks; base += 1024u) {
     const uint32_t c = base + tid;
     const uint32_t mine = c < n_chunks ? (chunk_payload[c] + sub_bytes - 1u) / sub_bytes : 0u;
-    uint32_t wsum;
-    const uint32_t excl = lz_wave_excl_scan(mine, lane, &wsum);
-    if (lane == 0u) wtot[wave] = wsum;
-    __syncthreads();
-    uint32_t before = carry;
-    for (uint32_t w = 0; w < wave; ++w) before += wtot[w];
-    if (c < n_chunks) sub_first[c] = min(before + excl, max_subs);
-    __syncthreads();
-    if (tid == 1023u) carry = before + excl + mine;
-    __syncthreads();
+    const uint32_t before = block_running_scan(mine, wtot, carry);
+    if (c < n_chunks) sub_first[c] = min(before, max_subs);
   }
   if (tid == 0u) {
     sub_first[n_chunks] = min(carry, max_subs);
@@ -151,7 +103,7 @@ __global__ __launch_bounds__(64) void k_lz4_match(const uint8_t* __restrict__ st
   const uint32_t lane = threadIdx.x;
   const uint32_t total = sub_first[n_chunks];
   for (uint32_t idx = blockIdx.x; idx < total; idx += gridDim.x) {
-    const uint32_t c = lz_chunk_of(sub_first, n_chunks, idx);
+    const uint32_t c = chunk_of(sub_first, n_chunks, idx);
     const uint32_t k = idx - sub_first[c];
     const uint32_t n = chunk_payload[c];
     const uint32_t s = k * SUB;
@@ -200,11 +152,11 @@ __global__ __launch_bounds__(64) void k_lz4_match(const uint8_t* __restrict__ st
         const bool active = p <= last_start;
         // (a lane behind the last position repeats it: the same look-up, the same table entry written again -- no hit)
         const uint32_t pc = (uint32_t)min(p, last_start);
-        const uint32_t seq = lz_lds_u32(data, pc);
+        const uint32_t seq = lds_u32_alignbyte(data, pc);
         const uint32_t h = (seq * kLzHashMul) >> (32u - HASH_BITS);
         const uint32_t cand = table[h];
         const uint32_t cm1 = cand != 0u ? cand - 1u : 0u;
-        const uint32_t vseq = lz_lds_u32(data, cm1);  // (read by every lane: no exec-mask change)
+        const uint32_t vseq = lds_u32_alignbyte(data, cm1);  // (read by every lane: no exec-mask change)
         const bool ok = (int)active & (int)(cand != 0u) & (int)(vseq == seq);
         // every hit extends its own match, 4 bytes per round, up to kLaneRounds rounds
         constexpr uint32_t kLaneRounds = 3u;
@@ -213,7 +165,7 @@ __global__ __launch_bounds__(64) void k_lz4_match(const uint8_t* __restrict__ st
         bool going = ok && len < maxlen;
         for (uint32_t r = 0; r < kLaneRounds; ++r) {
           if (__ballot(going) == 0ull) break;
-          const uint32_t x = lz_lds_u32(data, pc + len) ^ lz_lds_u32(data, cm1 + len);
+          const uint32_t x = lds_u32_alignbyte(data, pc + len) ^ lds_u32_alignbyte(data, cm1 + len);
           const uint32_t adv = x ? (uint32_t)__builtin_ctz(x) >> 3 : 4u;
           const uint32_t nl = min(len + adv, maxlen);
           const bool on = going && x == 0u && nl < maxlen;
@@ -320,8 +272,7 @@ __global__ __launch_bounds__(64) void k_lz4_sizes(uint32_t n_chunks, const uint3
       lz_seq_fields(list, j, a, lit, ml, anchor, r);
       acc += 1u + lz_ext_bytes(lit) + lit + 2u + lz_ext_bytes(ml);
     }
-    uint32_t sum;
-    (void)lz_wave_excl_scan(acc, lane, &sum);
+    const uint32_t sum = wave_sum(acc);
     if (lane == 0u) {
       anchor_in[idx] = a;
       sub_size[idx] = sum;
@@ -404,8 +355,8 @@ __device__ __forceinline__ void lz_emit_direct(const LzEmitArgs& A, uint32_t idx
         lz_seq_fields(list, j, a_in, lit, ml, anchor, r);
         size = 1u + lz_ext_bytes(lit) + lit + 2u + lz_ext_bytes(ml);
       }
-      uint32_t tile_total;
-      const uint32_t at = run + lz_wave_excl_scan(size, lane, &tile_total);
+      const uint32_t incl = wave_inclusive_scan(size);
+      const uint32_t at = run + incl - size;
       uint32_t lit_at = at;
       if (j < m) {
         uint8_t* o = out + at;
@@ -448,9 +399,9 @@ __device__ __forceinline__ void lz_emit_direct(const LzEmitArgs& A, uint32_t idx
         const uint32_t ql = (uint32_t)__builtin_amdgcn_readlane((int)clit, q);
         const uint32_t qa = (uint32_t)__builtin_amdgcn_readlane((int)(anchor + skip), q);
         const uint32_t qo = (uint32_t)__builtin_amdgcn_readlane((int)(lit_at + skip), q);
-        lz_copy_wave(in + qa, out + qo, ql, lane);
+        copy_bytes_16(in + qa, out + qo, ql, lane, 64u);
       }
-      run += tile_total;
+      run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     }
 
     // ---- the bytes behind my last match (all of my bytes if I have none): literals of the chunk's NEXT sequence
@@ -472,7 +423,7 @@ __device__ __forceinline__ void lz_emit_direct(const LzEmitArgs& A, uint32_t idx
         a2 = tail_anchor;
         dst0 = all + 1u + lz_ext_bytes(n - a2);
       }
-      lz_copy_wave(in + t0, out + dst0 + (t0 - a2), e - t0, lane);
+      copy_bytes_16(in + t0, out + dst0 + (t0 - a2), e - t0, lane, 64u);
     }
 
     // ---- the last sub-range of the chunk also writes the header of the last sequence and the block's size
@@ -620,8 +571,8 @@ __global__ __launch_bounds__(64) void k_lz4_emit_lds(const LzEmitArgs A) {
         lz_seq_fields(list, j, a_in, lit, ml, anchor, r);
         size = 1u + lz_ext_bytes(lit) + lit + 2u + lz_ext_bytes(ml);
       }
-      uint32_t tile_total;
-      const uint32_t at = run + lz_wave_excl_scan(size, lane, &tile_total);
+      const uint32_t incl = wave_inclusive_scan(size);
+      const uint32_t at = run + incl - size;
       const uint32_t lit_at = at + 1u + lz_ext_bytes(lit);
       if (j < m) {
         const uint8_t token = (uint8_t)(((lit < 15u ? lit : 15u) << 4) | (ml < 15u ? ml : 15u));
@@ -652,7 +603,7 @@ __global__ __launch_bounds__(64) void k_lz4_emit_lds(const LzEmitArgs A) {
         copy_wave((uint32_t)__builtin_amdgcn_readlane((int)sb, q), (uint32_t)__builtin_amdgcn_readlane((int)db, q),
                   (uint32_t)__builtin_amdgcn_readlane((int)clit, q));
       }
-      run += tile_total;
+      run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     }
     // ---- region C
     if (t0 < e) copy_wave(t0 - s, c_at + ib, e - t0);
@@ -698,10 +649,9 @@ __global__ __launch_bounds__(64) void k_lz4_layout(const uint32_t* __restrict__ 
   for (uint32_t j0 = first; j0 < end; j0 += 64u) {
     const uint32_t j = j0 + lane;
     const uint32_t sz = j < end ? sub_size[j] : 0u;
-    uint32_t tot;
-    const uint32_t excl = lz_wave_excl_scan(sz, lane, &tot);
-    if (j < end) before[j] = run + excl;
-    run += tot;
+    const uint32_t incl = wave_inclusive_scan(sz);
+    if (j < end) before[j] = run + incl - sz;
+    run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     tail = max(tail, j < end ? last_end[j] : 0u);
   }
 #pragma unroll
@@ -735,24 +685,13 @@ __global__ __launch_bounds__(1024) void k_lz4_offsets(const uint32_t* __restrict
                                                      uint64_t* __restrict__ stream_offsets, uint8_t* __restrict__ out,
                                                      uint64_t out_capacity, uint32_t* __restrict__ status) {
   __shared__ unsigned long long wtot[16];
-  __shared__ unsigned long long carry;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  if (tid == 0u) carry = 0ull;
-  __syncthreads();
+  const uint32_t tid = threadIdx.x;
+  unsigned long long total = 0ull;
   for (uint32_t base = 0; base < n_chunks; base += 1024u) {
     const uint32_t c = base + tid;
     const uint32_t bs = c < n_chunks ? block_size[c] : 0u;
     const unsigned long long mine = c < n_chunks ? 4ull + bs : 0ull;
-    unsigned long long incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned long long o = (unsigned long long)__shfl_up((long long)incl, d);
-      if (lane >= (uint32_t)d) incl += o;
-    }
-    if (lane == 63u) wtot[wave] = incl;
-    __syncthreads();
-    unsigned long long dst = carry + incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) dst += wtot[w];
+    const unsigned long long dst = block_running_scan(mine, wtot, total);
     if (c < n_chunks) {
       block_dst[c] = dst;
       chunk_sizes[c] = bs;
@@ -767,52 +706,45 @@ __global__ __launch_bounds__(1024) void k_lz4_offsets(const uint32_t* __restrict
         if (sub_first[c] == sub_first[c + 1u]) o[4] = 0u;  // a chunk without a byte of payload: the single token 0x00
       }
     }
-    __syncthreads();
-    if (tid == 1023u) carry = dst + mine;
-    __syncthreads();
   }
   __threadfence_block();
   __syncthreads();
-  // stream offset of a cloud = where its first chunk goes; a cloud without chunks: where the next one's does
-  const unsigned long long total = carry;
-  for (uint32_t k = tid; k <= n_clouds; k += 1024u) {
-    const uint32_t fc = k < n_clouds ? cloud_first_chunk[k] : n_chunks;
-    stream_offsets[k] = fc < n_chunks ? block_dst[fc] : total;
-  }
+  cloud_stream_offsets(cloud_first_chunk, n_clouds, n_chunks, [&](uint32_t c) { return block_dst[c]; }, total, stream_offsets, tid, 1024u);
 }
 
 int lz4_launch(const Lz4Launch& L) {
-  if (L.n_chunks == 0u) return CLDN_HIP_OK;
+  const Stage2Io& io = L.io;
+  if (io.n_chunks == 0u) return CLDN_HIP_OK;
   hipError_t e;
   const uint32_t sub_bytes = L.fast ? kLzFastSubBytes : kLzSubBytes;
   const uint32_t max_matches = L.fast ? kLzFastMaxMatches : kLzMaxMatches;
-  hipLaunchKernelGGL(k_lz4_plan, dim3(1), dim3(1024), 0, L.stream, L.chunk_payload, L.n_chunks, L.sub_first, sub_bytes,
-                     (uint32_t)std::min<uint64_t>(L.max_subs, 0xffffffffu), L.status);
+  hipLaunchKernelGGL(k_lz4_plan, dim3(1), dim3(1024), 0, io.stream, io.chunk_payload, io.n_chunks, L.sub_first, sub_bytes,
+                     (uint32_t)std::min<uint64_t>(L.max_subs, 0xffffffffu), io.status);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_plan");
   // one wave per sub-range, at most `max_subs` of them: workgroups beyond the real number find nothing to do
   // (round 5: one workgroup per sub-range -- the dispatcher balances them; 8192 looping workgroups ran 1.68 rounds)
   const uint32_t grid = (uint32_t)std::min<uint64_t>(L.max_subs, 1u << 20);
   if (L.fast)
-    hipLaunchKernelGGL((k_lz4_match<kLzFastSubBytes, kLzFastHashBits, kLzFastMaxMatches>), dim3(grid), dim3(64), 0, L.stream, L.stage1,
-                       L.chunk_dst, L.chunk_payload, L.n_chunks, L.sub_first, L.matches, L.counts, L.last_end, L.sub_chunk);
+    hipLaunchKernelGGL((k_lz4_match<kLzFastSubBytes, kLzFastHashBits, kLzFastMaxMatches>), dim3(grid), dim3(64), 0, io.stream, io.stage1,
+                       io.chunk_dst, io.chunk_payload, io.n_chunks, L.sub_first, L.matches, L.counts, L.last_end, L.sub_chunk);
   else
-    hipLaunchKernelGGL((k_lz4_match<kLzSubBytes, kLzHashBits, kLzMaxMatches>), dim3(grid), dim3(64), 0, L.stream, L.stage1, L.chunk_dst,
-                       L.chunk_payload, L.n_chunks, L.sub_first, L.matches, L.counts, L.last_end, L.sub_chunk);
+    hipLaunchKernelGGL((k_lz4_match<kLzSubBytes, kLzHashBits, kLzMaxMatches>), dim3(grid), dim3(64), 0, io.stream, io.stage1, io.chunk_dst,
+                       io.chunk_payload, io.n_chunks, L.sub_first, L.matches, L.counts, L.last_end, L.sub_chunk);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_match");
-  hipLaunchKernelGGL(k_lz4_sizes, dim3(grid), dim3(64), 0, L.stream, L.n_chunks, L.sub_first, L.matches, L.counts, L.last_end,
+  hipLaunchKernelGGL(k_lz4_sizes, dim3(grid), dim3(64), 0, io.stream, io.n_chunks, L.sub_first, L.matches, L.counts, L.last_end,
                      L.anchor_in, L.sub_size, max_matches, L.sub_chunk);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_sizes");
-  hipLaunchKernelGGL(k_lz4_layout, dim3(L.n_chunks), dim3(64), 0, L.stream, L.chunk_payload, L.sub_first, L.matches, L.counts, L.last_end,
+  hipLaunchKernelGGL(k_lz4_layout, dim3(io.n_chunks), dim3(64), 0, io.stream, io.chunk_payload, L.sub_first, L.matches, L.counts, L.last_end,
                      L.sub_size, L.before, L.next_pos, L.block_size, max_matches);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_layout");
-  hipLaunchKernelGGL(k_lz4_offsets, dim3(1), dim3(1024), 0, L.stream, L.block_size, L.sub_first, L.n_chunks, L.cloud_first_chunk, L.n_clouds,
-                     L.block_dst, L.block_sizes_out, L.stream_offsets, L.out, L.out_capacity, L.status);
+  hipLaunchKernelGGL(k_lz4_offsets, dim3(1), dim3(1024), 0, io.stream, L.block_size, L.sub_first, io.n_chunks, io.cloud_first_chunk, io.n_clouds,
+                     L.block_dst, io.chunk_sizes, io.stream_offsets, io.out, io.out_capacity, io.status);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_offsets");
   LzEmitArgs A;
-  A.stream = L.stage1;
-  A.chunk_dst = L.chunk_dst;
-  A.chunk_payload = L.chunk_payload;
-  A.n_chunks = L.n_chunks;
+  A.stream = io.stage1;
+  A.chunk_dst = io.chunk_dst;
+  A.chunk_payload = io.chunk_payload;
+  A.n_chunks = io.n_chunks;
   A.sub_first = L.sub_first;
   A.matches = L.matches;
   A.counts = L.counts;
@@ -824,12 +756,12 @@ int lz4_launch(const Lz4Launch& L) {
   A.next_pos = L.next_pos;
   A.block_size = L.block_size;
   A.block_dst = L.block_dst;
-  A.out = L.out;
-  A.out_capacity = L.out_capacity;
+  A.out = io.out;
+  A.out_capacity = io.out_capacity;
   A.sub_bytes = sub_bytes;
   A.max_matches = max_matches;
-  if (L.fast) hipLaunchKernelGGL(k_lz4_emit_lds<kLzFastSubBytes>, dim3(grid), dim3(64), 0, L.stream, A);
-  else hipLaunchKernelGGL(k_lz4_emit_lds<kLzSubBytes>, dim3(grid), dim3(64), 0, L.stream, A);
+  if (L.fast) hipLaunchKernelGGL(k_lz4_emit_lds<kLzFastSubBytes>, dim3(grid), dim3(64), 0, io.stream, A);
+  else hipLaunchKernelGGL(k_lz4_emit_lds<kLzSubBytes>, dim3(grid), dim3(64), 0, io.stream, A);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_emit");
   return CLDN_HIP_OK;
 }

@@ -80,7 +80,7 @@ struct EncodeFacts {
   uint8_t pipeline;           // cldn_hip_codec_pipeline: 0 auto, 1 generic kernel + slots, 2 piece kernel + slots
   bool wide;                  // WIDE route: `plan` holds only the scalar members
   bool chunks_only;           // chunk-table output: no framing
-  bool lz4;                   // stage 2 on the device follows
+  bool lz4;                   // stage 2 on the device follows, LZ4 or ZSTD (the name is the one tests/encode_route_shim.cpp fills)
   uint8_t points_misaligned;  // low two bits of the points' device address; 0 for host input (its staging buffer is aligned)
   bool modes_forced;          // modes were uploaded by the caller: no probe
   bool caller_modes;          // the caller gave a device array for the modes, and the call could write it in place

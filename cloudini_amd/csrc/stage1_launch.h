@@ -172,7 +172,24 @@ struct FrameLaunch {
 };
 int stage1_launch_frame(const FrameLaunch& F);
 
-// ---- stage 2 on the device: LZ4 block per chunk (lz4_kernels.hip; parameters shared with oracle/lz4_model.c) ----
+// ---- stage 2 on the device (lz4_kernels.hip, zstd_kernels.hip): what either writer takes from the call and gives back ----
+struct Stage2Io {
+  hipStream_t stream;
+  const uint8_t* stage1;          // framed stage-1 streams (the payload of chunk c starts at chunk_dst[c] + 4)
+  uint64_t stage1_capacity;       // bytes of that buffer (ZSTD: a payload that does not lie inside is not read; LZ4 ignores it)
+  const uint64_t* chunk_dst;
+  const uint32_t* chunk_payload;
+  uint32_t n_chunks;
+  const uint32_t* cloud_first_chunk;  // [n_clouds + 1]
+  uint32_t n_clouds;
+  uint32_t* chunk_sizes;          // [n_chunks]: what chunk_sizes reports (LZ4 block / ZSTD frame of the chunk)
+  uint64_t* stream_offsets;       // [n_clouds + 1]
+  uint8_t* out;                   // the framed streams: [u32 size][block or frame] per chunk, written by the kernels themselves
+  uint64_t out_capacity;
+  uint32_t* status;
+};
+
+// ---- LZ4 block per chunk (lz4_kernels.hip; parameters shared with oracle/lz4_model.c) ----
 constexpr uint32_t kLzSubBytes = 8192;    // a wave parses this much of a payload with its own hash table
 constexpr uint32_t kLzHashBits = 11;
 constexpr uint32_t kLzMaxMatches = 1024;  // per sub-range (the rest of it leaves as literals)
@@ -187,36 +204,40 @@ struct LzMatch {
   uint16_t off;  // 1 .. kLzSubBytes - 1
 };
 struct Lz4Launch {
-  hipStream_t stream;
-  const uint8_t* stage1;          // framed stage-1 streams (the payload of chunk c starts at chunk_dst[c] + 4)
-  const uint64_t* chunk_dst;
-  const uint32_t* chunk_payload;
-  uint32_t n_chunks;
+  Stage2Io io;
   uint32_t fast;                  // 1 = the CLDN_HIP_STAGE2_LZ4_FAST parameters
   uint64_t max_subs;              // upper bound of the sub-ranges of the batch (payload bound / sub-range bytes + n_chunks)
-  uint32_t* sub_first;            // [n_chunks + 1]: compact sub-range numbering
-  LzMatch* matches;               // [max_subs * kLzMaxMatches] (fast: kLzFastMaxMatches)
-  uint32_t* counts;               // [max_subs] and the arrays behind it: last_end, anchor_in, sub_size, sub_chunk, before, next_pos
-  uint32_t* last_end;
-  uint32_t* anchor_in;
-  uint32_t* sub_size;
+  LzMatch* matches;               // [max_subs * kLzMaxMatches] (fast: kLzFastMaxMatches), a buffer of its own
+  uint64_t* block_dst;            // [n_chunks]: where [u32 size][block] of a chunk begins in io.out, a buffer of its own
+  // the workspace, in this order (carve)
+  uint32_t* counts;               // [max_subs]: matches of a sub-range
+  uint32_t* last_end;             // [max_subs]: where its last match ends (0 = no match)
+  uint32_t* anchor_in;            // [max_subs]: where the literals of its first sequence start
+  uint32_t* sub_size;             // [max_subs]: bytes of its sequences
   uint32_t* sub_chunk;            // [max_subs]: chunk of a sub-range
   uint32_t* before;               // [max_subs]: sequence bytes of the chunk's earlier sub-ranges
   uint32_t* next_pos;             // [max_subs]: the chunk's next match behind the sub-range
   uint32_t* block_size;           // [n_chunks]: bytes of the chunk's LZ4 block
-  // the blocks are written straight into the framed streams (round 5: no slots, no second framing pass)
-  const uint32_t* cloud_first_chunk;  // [n_clouds + 1]
-  uint32_t n_clouds;
-  uint64_t* block_dst;            // [n_chunks]: where [u32 size][block] of a chunk begins in `out`
-  uint32_t* block_sizes_out;      // [n_chunks]: what chunk_sizes reports
-  uint64_t* stream_offsets;       // [n_clouds + 1]
-  uint8_t* out;
-  uint64_t out_capacity;
-  uint32_t* status;
+  uint32_t* sub_first;            // [n_chunks + 1]: compact sub-range numbering
+  static size_t workspace_bytes(uint64_t max_subs, uint32_t n_chunks) {
+    return (size_t)(7u * max_subs + (uint64_t)n_chunks + ((uint64_t)n_chunks + 1u)) * sizeof(uint32_t);
+  }
+  void carve(void* ws, uint64_t max_subs_, uint32_t n_chunks) {
+    max_subs = max_subs_;
+    counts = (uint32_t*)ws;
+    last_end = counts + max_subs;
+    anchor_in = last_end + max_subs;
+    sub_size = anchor_in + max_subs;
+    sub_chunk = sub_size + max_subs;
+    before = sub_chunk + max_subs;
+    next_pos = before + max_subs;
+    block_size = next_pos + max_subs;
+    sub_first = block_size + n_chunks;
+  }
 };
 int lz4_launch(const Lz4Launch& L);
 
-// ---- stage 2 on the device: ZSTD frame of literal-only blocks per chunk (zstd_kernels.hip; restated in tests/zstd_lit_model.py) ----
+// ---- ZSTD frame of literal-only blocks per chunk (zstd_kernels.hip; restated in tests/zstd_lit_model.py) ----
 constexpr uint32_t kZsBlockBytes = 131072;  // a frame's blocks: consecutive pieces of the payload
 constexpr uint32_t kZsMinHuf = 64;          // a block below this is Raw
 constexpr uint32_t kZsFourStreams = 256;    // one Huffman stream below, four from here on
@@ -233,26 +254,40 @@ struct ZsBlock {
   uint32_t rle;             // the byte of an RLE block
 };
 struct ZstdLaunch {
-  hipStream_t stream;
-  const uint8_t* stage1;          // framed stage-1 streams (the payload of chunk c starts at chunk_dst[c] + 4)
-  uint64_t stage1_capacity;       // bytes of that buffer: a payload that does not lie inside is not read
-  const uint64_t* chunk_dst;
-  const uint32_t* chunk_payload;
-  uint32_t n_chunks;
+  Stage2Io io;
   uint64_t max_blocks;            // upper bound of the blocks of the batch (payload bound / block bytes + n_chunks)
-  uint32_t* blk_first;            // [n_chunks + 1]: compact block numbering
-  uint32_t* chunk_state;          // [n_chunks]
+  // the workspace, in this order (carve); codes and block_dst start at multiples of 64 bytes
   ZsBlock* blocks;                // [max_blocks]
   uint32_t* codes;                // [max_blocks * 256]: length << 16 | code value
   uint8_t* descs;                 // [max_blocks * kZsDescBytes]
-  uint64_t* block_dst;            // [max_blocks + 1]: where a block's header goes in `out` (a chunk's first: its [u32] prefix)
-  const uint32_t* cloud_first_chunk;  // [n_clouds + 1]
-  uint32_t n_clouds;
-  uint32_t* frame_sizes_out;      // [n_chunks]: what chunk_sizes reports
-  uint64_t* stream_offsets;       // [n_clouds + 1]
-  uint8_t* out;
-  uint64_t out_capacity;
-  uint32_t* status;
+  uint64_t* block_dst;            // [max_blocks + 1]: where a block's header goes in io.out (a chunk's first: its [u32] prefix)
+  uint32_t* blk_first;            // [n_chunks + 1]: compact block numbering
+  uint32_t* chunk_state;          // [n_chunks]
+  struct Layout {
+    size_t codes, descs, block_dst, blk_first, chunk_state, bytes;
+  };
+  static Layout layout(uint64_t max_blocks, uint32_t n_chunks) {
+    Layout o;
+    o.codes = ((size_t)max_blocks * sizeof(ZsBlock) + 63u) & ~size_t(63);
+    o.descs = o.codes + (size_t)max_blocks * 256u * sizeof(uint32_t);
+    o.block_dst = (o.descs + (size_t)max_blocks * kZsDescBytes + 63u) & ~size_t(63);
+    o.blk_first = o.block_dst + (size_t)(max_blocks + 1u) * sizeof(uint64_t);
+    o.chunk_state = o.blk_first + (size_t)(n_chunks + 1u) * sizeof(uint32_t);
+    o.bytes = o.chunk_state + (size_t)n_chunks * sizeof(uint32_t);
+    return o;
+  }
+  static size_t workspace_bytes(uint64_t max_blocks, uint32_t n_chunks) { return layout(max_blocks, n_chunks).bytes; }
+  void carve(void* ws, uint64_t max_blocks_, uint32_t n_chunks) {
+    const Layout o = layout(max_blocks_, n_chunks);
+    uint8_t* p = (uint8_t*)ws;
+    max_blocks = max_blocks_;
+    blocks = (ZsBlock*)p;
+    codes = (uint32_t*)(p + o.codes);
+    descs = p + o.descs;
+    block_dst = (uint64_t*)(p + o.block_dst);
+    blk_first = (uint32_t*)(p + o.blk_first);
+    chunk_state = (uint32_t*)(p + o.chunk_state);
+  }
 };
 int zstd_launch(const ZstdLaunch& L);
 

@@ -23,6 +23,7 @@
 
 #include "stage1_launch.h"
 #include "stage1_math.h"
+#include "stage1_prims.h"
 
 namespace cldn {
 
@@ -147,30 +148,15 @@ __global__ __launch_bounds__(kVizBlock) void k_viz_count(const VizCloud* __restr
 // one workgroup: exclusive scan of n_blocks counts (in place), the survivors of every cloud, the total (kept[n_clouds])
 __global__ __launch_bounds__(1024) void k_viz_offsets(uint32_t* block_count, uint32_t n_blocks, const VizCloud* __restrict__ clouds,
                                                       uint32_t n_clouds, unsigned long long* __restrict__ kept) {
-  __shared__ uint32_t wsum[16];
-  __shared__ uint32_t carry_s;
-  if (threadIdx.x == 0) carry_s = 0u;
-  __syncthreads();
+  __shared__ uint32_t wtot[16];
+  uint32_t total = 0u;
   for (uint32_t base = 0; base < n_blocks; base += 1024u) {
     const uint32_t i = base + threadIdx.x;
     const uint32_t x = i < n_blocks ? block_count[i] : 0u;
-    uint32_t incl = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
-      if ((threadIdx.x & 63u) >= (uint32_t)d) incl += o;
-    }
-    if ((threadIdx.x & 63u) == 63u) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    uint32_t before = carry_s;
-    for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) before += wsum[w];
-    if (i < n_blocks) block_count[i] = before + incl - x;
-    __syncthreads();
-    if (threadIdx.x == 1023u) carry_s = before + incl;
-    __syncthreads();
+    const uint32_t before = block_running_scan(x, wtot, total);
+    if (i < n_blocks) block_count[i] = before;
   }
-  // (the offsets were written by this workgroup in front of a barrier: they are visible to all of its threads)
-  const uint32_t total = carry_s;
+  __syncthreads();  // (the offsets were written by this workgroup in front of a barrier: they are visible to all of its threads)
   for (uint32_t k = threadIdx.x; k < n_clouds; k += 1024u) {
     const uint32_t lo = clouds[k].first_block, hi = k + 1u < n_clouds ? clouds[k + 1u].first_block : n_blocks;
     const uint32_t a = lo < n_blocks ? block_count[lo] : total, e = hi < n_blocks ? block_count[hi] : total;

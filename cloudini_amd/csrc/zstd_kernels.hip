@@ -7,18 +7,19 @@
 // (DESIGN.md section 4f / 4g). Where ZSTD does find matches these frames are larger.
 //
 // The writer is deterministic and restated serially in tests/zstd_lit_model.py (the GPU tests ask for byte equality):
-//   k_zstd_plan     blocks per chunk -> compact numbering (one scan). A chunk without payload has one empty Raw block.
+//   k_zstd_plan     blocks per chunk -> compact numbering (block_running_scan, stage1_prims.h; chunk_of finds a block's chunk).
+//                   A chunk without payload has one empty Raw block.
 //   k_zstd_code     one workgroup per block: a histogram per stream (a wave per stream, 8 copies per wave so that a skewed
 //                   stream does not put 64 lanes on one counter), the 256 keys count << 8 | symbol ranked, Huffman's two
 //                   queues and the Kraft repair in one lane, code values per symbol, the tree description (FSE, one lane),
 //                   the exact stream sizes from count x length, and with them the block's kind and size.
-//   k_zstd_offsets  one scan over the blocks: where everything goes; [u32] prefixes, frame / block / literals headers, tree
-//                   descriptions, jump tables; chunk sizes and stream offsets. A chunk that does not fit `out_capacity`
+//   k_zstd_offsets  block_running_scan over the blocks: where everything goes; [u32] prefixes, frame / block / literals headers,
+//                   tree descriptions, jump tables; chunk sizes and stream offsets (cloud_stream_offsets). A chunk that does not fit `out_capacity`
 //                   raises ST_OUT_OVERFLOW and is not written by this kernel or the next.
 //   k_zstd_emit     one workgroup per stream: code lengths from an LDS table, a suffix scan for the bit positions (the
 //                   stream's LAST symbol lies at bit 0), the codes ORed into an LDS image of the stream, the image drained
 //                   into the framed streams at any byte alignment in 16-byte units (single bytes at its two ends:
-//                   neighbouring streams never share a store). Raw blocks are copied and RLE bytes written here too.
+//                   neighbouring streams never share a store). Raw blocks are copied (copy_bytes_16) and RLE bytes written here too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -27,6 +28,7 @@
 #include "cloudini_hip.h"
 #include "stage1_device.h"
 #include "stage1_launch.h"
+#include "stage1_prims.h"
 
 namespace cldn {
 
@@ -36,32 +38,6 @@ constexpr uint32_t kZsMaxLen = 11u;
 constexpr uint32_t kZsChunkBad = 0u, kZsChunkPlanned = 1u, kZsChunkFits = 2u;
 // bytes of a stream's image: 32768 symbols of 11 bits, the closing bit, 15 bytes of alignment, whole 16-byte units
 constexpr uint32_t kZsImgBytes = ((kZsBlockBytes / 4u * kZsMaxLen / 8u + 1u + 15u + 15u) / 16u) * 16u;
-
-__device__ __forceinline__ uint32_t zs_wave_incl_scan(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_up((int)x, d);
-    if (lane >= (uint32_t)d) x += o;
-  }
-  return x;
-}
-
-__device__ __forceinline__ uint32_t zs_wave_sum(uint32_t x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d);
-  return x;
-}
-
-// chunk of compact block index `idx`: the last c with blk_first[c] <= idx
-__device__ __forceinline__ uint32_t zs_chunk_of(const uint32_t* __restrict__ blk_first, uint32_t n_chunks, uint32_t idx) {
-  uint32_t lo = 0u, hi = n_chunks;
-  while (hi - lo > 1u) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (blk_first[mid] <= idx) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // LE bit writer of one lane into LDS bytes
 struct ZsBits {
@@ -96,10 +72,8 @@ __global__ __launch_bounds__(1024) void k_zstd_plan(const uint32_t* __restrict__
                                                     uint32_t* __restrict__ chunk_state, uint32_t max_blocks,
                                                     uint32_t* __restrict__ status) {
   __shared__ uint32_t wtot[16];
-  __shared__ uint32_t carry;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  if (tid == 0u) carry = 0u;
-  __syncthreads();
+  const uint32_t tid = threadIdx.x;
+  uint32_t carry = 0u;
   bool bad = false;
   for (uint32_t base = 0; base < n_chunks; base += 1024u) {
     const uint32_t c = base + tid;
@@ -111,20 +85,13 @@ __global__ __launch_bounds__(1024) void k_zstd_plan(const uint32_t* __restrict__
       inside = at <= s1_capacity && 4ull + n <= s1_capacity - at;
       mine = inside ? max(1u, (n + kZsBlockBytes - 1u) / kZsBlockBytes) : 0u;
     }
-    const uint32_t incl = zs_wave_incl_scan(mine, lane);
-    if (lane == 63u) wtot[wave] = incl;
-    __syncthreads();
-    uint32_t before = carry + incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) before += wtot[w];
+    const uint32_t before = block_running_scan(mine, wtot, carry);
     if (c < n_chunks) {
       const bool ok = inside && before + mine <= max_blocks;
       blk_first[c] = min(before, max_blocks);
       chunk_state[c] = ok ? kZsChunkPlanned : kZsChunkBad;
       bad |= !ok;
     }
-    __syncthreads();
-    if (tid == 1023u) carry = before + mine;
-    __syncthreads();
   }
   if (tid == 0u) blk_first[n_chunks] = min(carry, max_blocks);
   if (bad) atomicOr(status, (uint32_t)ST_OUT_OVERFLOW);
@@ -151,7 +118,7 @@ __global__ __launch_bounds__(256) void k_zstd_code(const uint8_t* __restrict__ s
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t total = blk_first[n_chunks];
   for (uint32_t idx = blockIdx.x; idx < total; idx += gridDim.x) {
-    const uint32_t c = zs_chunk_of(blk_first, n_chunks, idx);
+    const uint32_t c = chunk_of(blk_first, n_chunks, idx);
     ZsBlock rec;
     rec.chunk = c;
     rec.off = (idx - blk_first[c]) * kZsBlockBytes;
@@ -295,7 +262,7 @@ __global__ __launch_bounds__(256) void k_zstd_code(const uint8_t* __restrict__ s
       // bits of every stream
 #pragma unroll
       for (uint32_t j = 0; j < 4u; ++j) {
-        const uint32_t b = zs_wave_sum(cnt[j][tid] * my_len);
+        const uint32_t b = wave_sum(cnt[j][tid] * my_len);
         if (lane == 0u) part[wave][j] = b;
       }
     }
@@ -452,11 +419,9 @@ __global__ __launch_bounds__(1024) void k_zstd_offsets(const ZsBlock* __restrict
                                                       uint32_t* __restrict__ chunk_sizes, uint64_t* __restrict__ stream_offsets,
                                                       uint8_t* __restrict__ out, uint64_t out_capacity, uint32_t* __restrict__ status) {
   __shared__ unsigned long long wtot[16];
-  __shared__ unsigned long long carry;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t tid = threadIdx.x;
   const uint32_t total_blocks = blk_first[n_chunks];
-  if (tid == 0u) carry = 0ull;
-  __syncthreads();
+  unsigned long long total = 0ull;
   for (uint32_t base = 0; base < total_blocks; base += 1024u) {
     const uint32_t b = base + tid;
     unsigned long long mine = 0ull;
@@ -464,22 +429,9 @@ __global__ __launch_bounds__(1024) void k_zstd_offsets(const ZsBlock* __restrict
       const ZsBlock r = blocks[b];
       if (chunk_state[r.chunk] != kZsChunkBad) mine = 3ull + r.body + (blk_first[r.chunk] == b ? 13ull : 0ull);
     }
-    unsigned long long incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned long long o = (unsigned long long)__shfl_up((long long)incl, d);
-      if (lane >= (uint32_t)d) incl += o;
-    }
-    if (lane == 63u) wtot[wave] = incl;
-    __syncthreads();
-    unsigned long long dst = carry + incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) dst += wtot[w];
+    const unsigned long long dst = block_running_scan(mine, wtot, total);
     if (b < total_blocks) block_dst[b] = dst;
-    __syncthreads();
-    if (tid == 1023u) carry = dst + mine;
-    __syncthreads();
   }
-  const unsigned long long total = carry;
   if (tid == 0u) block_dst[total_blocks] = total;
   __threadfence_block();
   __syncthreads();
@@ -506,11 +458,7 @@ __global__ __launch_bounds__(1024) void k_zstd_offsets(const ZsBlock* __restrict
     chunk_sizes[c] = fsize;
   }
   if (overflow) atomicOr(status, (uint32_t)ST_OUT_OVERFLOW);
-  // stream offset of a cloud = where its first chunk goes; a cloud without chunks: where the next one's does
-  for (uint32_t k = tid; k <= n_clouds; k += 1024u) {
-    const uint32_t fc = k < n_clouds ? cloud_first_chunk[k] : n_chunks;
-    stream_offsets[k] = fc < n_chunks ? block_dst[blk_first[fc]] : total;
-  }
+  cloud_stream_offsets(cloud_first_chunk, n_clouds, n_chunks, [&](uint32_t c) { return block_dst[blk_first[c]]; }, total, stream_offsets, tid, 1024u);
   __threadfence_block();
   __syncthreads();
   // blocks: header, literals header, tree description, jump table
@@ -569,14 +517,7 @@ __global__ __launch_bounds__(256) void k_zstd_emit(const uint8_t* __restrict__ s
     if (r.kind == kZsRaw) {
       const uint32_t q = ((r.n + 63u) / 64u) * 16u;  // a quarter, in whole 16-byte units
       const uint32_t s0 = min(r.n, j * q), s1 = min(r.n, s0 + q);
-      const uint32_t n16 = (s1 - s0) >> 4;
-      for (uint32_t i = tid; i < n16; i += 256u) {
-        uint4 w;
-        __builtin_memcpy(&w, in + s0 + 16u * i, 16);
-        __builtin_memcpy(o + s0 + 16u * i, &w, 16);
-      }
-      const uint32_t done = s0 + (n16 << 4);
-      if (tid < s1 - done) o[done + tid] = in[done + tid];
+      copy_bytes_16(in + s0, o + s0, s1 - s0, tid, 256u);
       continue;
     }
     const bool four = r.n >= kZsFourStreams;
@@ -640,7 +581,7 @@ __global__ __launch_bounds__(256) void k_zstd_emit(const uint8_t* __restrict__ s
         }
         bits += gb;
       }
-      const uint32_t incl = zs_wave_incl_scan(bits, lane);
+      const uint32_t incl = wave_inclusive_scan(bits);
       __syncthreads();  // (the previous tile's wave totals are read)
       if (lane == 63u) wtot[wave] = incl;
       __syncthreads();
@@ -676,22 +617,23 @@ __global__ __launch_bounds__(256) void k_zstd_emit(const uint8_t* __restrict__ s
 }
 
 int zstd_launch(const ZstdLaunch& L) {
-  if (L.n_chunks == 0u) return CLDN_HIP_OK;
+  const Stage2Io& io = L.io;
+  if (io.n_chunks == 0u) return CLDN_HIP_OK;
   hipError_t e;
   const uint32_t max_blocks = (uint32_t)std::min<uint64_t>(L.max_blocks, 1u << 20);
-  hipLaunchKernelGGL(k_zstd_plan, dim3(1), dim3(1024), 0, L.stream, L.chunk_payload, L.chunk_dst, L.n_chunks, L.stage1_capacity,
-                     L.blk_first, L.chunk_state, max_blocks, L.status);
+  hipLaunchKernelGGL(k_zstd_plan, dim3(1), dim3(1024), 0, io.stream, io.chunk_payload, io.chunk_dst, io.n_chunks, io.stage1_capacity,
+                     L.blk_first, L.chunk_state, max_blocks, io.status);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_zstd_plan");
   // one workgroup per block, at most `max_blocks` of them: workgroups beyond the real number find nothing to do
-  hipLaunchKernelGGL(k_zstd_code, dim3(max_blocks), dim3(256), 0, L.stream, L.stage1, L.chunk_dst, L.chunk_payload, L.n_chunks,
+  hipLaunchKernelGGL(k_zstd_code, dim3(max_blocks), dim3(256), 0, io.stream, io.stage1, io.chunk_dst, io.chunk_payload, io.n_chunks,
                      L.blk_first, L.chunk_state, L.blocks, L.codes, L.descs);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_zstd_code");
-  hipLaunchKernelGGL(k_zstd_offsets, dim3(1), dim3(1024), 0, L.stream, L.blocks, L.descs, L.blk_first, L.chunk_payload, L.n_chunks,
-                     L.cloud_first_chunk, L.n_clouds, L.chunk_state, L.block_dst, L.frame_sizes_out, L.stream_offsets, L.out,
-                     L.out_capacity, L.status);
+  hipLaunchKernelGGL(k_zstd_offsets, dim3(1), dim3(1024), 0, io.stream, L.blocks, L.descs, L.blk_first, io.chunk_payload, io.n_chunks,
+                     io.cloud_first_chunk, io.n_clouds, L.chunk_state, L.block_dst, io.chunk_sizes, io.stream_offsets, io.out,
+                     io.out_capacity, io.status);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_zstd_offsets");
-  hipLaunchKernelGGL(k_zstd_emit, dim3(4u * max_blocks), dim3(256), 0, L.stream, L.stage1, L.chunk_dst, L.n_chunks, L.blk_first,
-                     L.chunk_state, L.blocks, L.codes, L.block_dst, L.out);
+  hipLaunchKernelGGL(k_zstd_emit, dim3(4u * max_blocks), dim3(256), 0, io.stream, io.stage1, io.chunk_dst, io.n_chunks, L.blk_first,
+                     L.chunk_state, L.blocks, L.codes, L.block_dst, io.out);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_zstd_emit");
   return CLDN_HIP_OK;
 }

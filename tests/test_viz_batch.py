@@ -116,6 +116,29 @@ def test_cloud_groups_do_not_change_a_byte(oracle):
 
 
 @pytest.mark.gpu
+def test_more_blocks_than_one_round_of_the_scan(oracle):
+    """1100 clouds of 1 to 3 points are 1100 blocks: the one-workgroup scan of k_viz_offsets takes a second round of 1024, and
+    the survivors per cloud are differences of block positions on both sides of that boundary."""
+    rs = np.random.RandomState(77)
+    step, off, res = 16, 0, 0.5
+    clouds = []
+    for k in range(1100):
+        n = 1 + k % 3
+        pts = np.zeros((n, 4), np.float32)
+        pts[:, :3] = rs.randint(0, 2, (n, 3)) * (2 * res)    # two voxels per axis: points of a cloud often share one
+        if k % 7 == 0:
+            pts[0, 1] = np.nan
+        clouds.append(pts.view(np.uint8).reshape(-1))
+    want = [oracle.viz_preprocess(c, step, off, res) for c in clouds]
+    kept = [w.size // step for w in want]
+    assert len(clouds) == 1100 > 1024 and set(kept) == {0, 1, 2, 3}
+    assert any(k < c.size // step for k, c in zip(kept[1024:], clouds[1024:]))
+    codec = _codec()
+    _check_host(codec, clouds, step, off, res, want, "1100 clouds")
+    codec.close()
+
+
+@pytest.mark.gpu
 def test_batch_argument_checks():
     from cloudini_amd import native
     codec = _codec()

@@ -169,11 +169,12 @@ def _build():
              np.full(131072, 255, np.uint8), rs.randint(0, 256, 131072).astype(np.uint8), skewed(131072, 33, 0.4), distinct(131072, 256, 34)]
     out.append(Case("eight_blocks_mixed", "RAW32", [np.concatenate(parts)], _expect([[H3, RAWK, RLEK, H3, RLEK, RAWK, H3, H3]])))
 
-    # ---- 1100 clouds of 13..40 bytes: a second round of the one-workgroup scans
+    # ---- 1100 one-chunk clouds of 13..40 bytes, 1100 blocks: a second round of 1024 in both one-workgroup scans (k_zstd_plan over
+    # the chunks, k_zstd_offsets over the blocks)
     clouds = [skewed(13 + k % 28, 100 + k) for k in range(1100)]
 
     def cond_many(T):
-        assert len(T) == 1100 and all(len(c) == 1 and c[0]["kind"] == M.RAW for c in T)
+        assert len(T) == 1100 > 1024 and all(len(c) == 1 and c[0]["kind"] == M.RAW for c in T)
     out.append(Case("1100_clouds", "RAW1", clouds, cond_many))
 
     # ---- zero-point clouds inside a batch
