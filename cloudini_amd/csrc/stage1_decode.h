@@ -547,25 +547,27 @@ __global__ __launch_bounds__(64) void k_decode_general(const DevPlan plan, const
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// Parallel decode of varint token streams.
+// Parallel decode of varint token streams, one workgroup of kDvThreads threads per chunk.
 //
-//   dv_tokens_tile    one tile = 8 bytes per thread. End-of-token flags (MSB clear; the NaN marker 0x00 included) ->
-//                     one block scan gives every thread the index of its first token; the tokens ending inside a
-//                     thread's 8 bytes are consecutive, and the thread rebuilds each from the 8-byte window that ends
-//                     at the token's last byte (tokens of more than 7 bytes flag the chunk for the serial decoder; the
-//                     64-bit instantiation takes up to 10 from the history bytes: a chunk's first epoch stamp).
-//   dv_stream         regular stream / DeltaVarint section: token values staged in LDS in token order; every thread
-//                     then takes a run of whole points: local sums per op with NaN resets -> segmented block scan ->
-//                     second walk that adds the incoming value, converts and stores (FieldDecoderFloatN_Lossy::decode,
+//   the shared steps  dv_ends4 (MSB clear = a token ends; the NaN marker 0x00 included), dv_window (the 8-byte window that
+//                     ends at a token's last byte, and how many continuation bytes it holds), dv_pack7 (the window's
+//                     7-bit groups joined).
+//   dv_tokens_tile    one tile = 8 bytes per thread: end flags -> one block scan gives every thread the index of its
+//                     first token -> the values go to the caller's `store` in token order. DeltaRle's (diff, run) pairs;
+//                     tokens of more than 7 bytes flag the chunk for the serial decoder.
+//   dv_stream         the tile walker: regular stream / DeltaVarint section. The tokens that end in a thread's bytes
+//                     stay in its registers: partial sums per op with NaN resets -> segmented block scan -> second walk
+//                     that adds the incoming value, converts and stores (FieldDecoderFloatN_Lossy::decode,
 //                     src/field_decoder.cpp:43-86; FieldDecoderFloat_Lossy / FieldDecoderInt,
-//                     include/cloudini_lib/field_decoder.hpp:330-353, :79-106). Tokens of a point cut by the tile
-//                     edge wait at the front of the LDS buffer for the next tile.
-//   k_decode_varint   dv_stream over the regular stream of plans whose regular ops are all varint-coded (<= 8 per point)
+//                     include/cloudini_lib/field_decoder.hpp:330-353, :79-106). Nothing waits at a tile edge; its 64-bit
+//                     instantiations take tokens of up to 10 bytes from the 16 history bytes in front of the tile.
+//   k_decode_varint   dv_stream over the regular stream of plans whose regular ops are all varint-coded (<= 8 per point),
+//                     or varints and raw fields with the token ends from k_mark_token_ends' bitmap
 //   k_decode_sections the V5 adaptive-int sections of a chunk, field after field (decodeV5AdaptiveIntSection,
-//                     src/v5_codec.cpp:764-879): DeltaVarint = dv_stream with one integer op; Palette = 32 indexes per
-//                     thread; DeltaRle = (diff, run) token pairs -> run table in LDS (two block scans) -> every output
-//                     finds its run by binary search; Rle = one lane parses the runs from an LDS copy of the bytes,
-//                     then the same fill.
+//                     src/v5_codec.cpp:764-879): DeltaVarint = dv_stream with one 64-bit integer op; Palette = 32 indexes
+//                     per thread; DeltaRle = dv_tokens_tile -> run table in LDS (two block scans) -> every output finds
+//                     its run by binary search; Rle = one lane parses the runs from an LDS copy of the bytes, then the
+//                     same fill. k_decode_tail and k_decode_sections_cols run the same body (decode_sections_core).
 //
 // reg_end[c] = offset of the first byte behind the regular stream, or kDecRedo when anything looked irregular;
 // sec_done[c] = 1 when all sections were decoded here. k_decode_general redoes whatever is left (whole chunks or
@@ -575,11 +577,36 @@ constexpr uint32_t kDecRedo = 0xfffffffeu;
 constexpr int kDvThreads = 1024;
 constexpr uint32_t kDvTileBytes = kDvThreads * 8u;
 
+// bit j = byte j of the dword ends a token: its MSB is clear (the multiply gathers bits 0, 8, 16, 24 into 21..24)
+__device__ __forceinline__ uint32_t dv_ends4(uint32_t b) { return (((~b & 0x80808080u) >> 7) * 0x00204081u) >> 21 & 0xfu; }
+
+// The window [e - 7, e] of tileb's bytes (e = byte index of a token's last byte; tileb: [16 history bytes + tile]) -> lo, hi;
+// returns the number of continuation bytes right in front of the end byte, 0..7
+__device__ __forceinline__ uint32_t dv_window(const uint32_t* tileb, uint32_t e, uint32_t& lo, uint32_t& hi) {
+  const uint32_t w0 = e - 7u;
+  const uint32_t d0 = tileb[w0 >> 2], d1 = tileb[(w0 >> 2) + 1u], d2 = tileb[(w0 >> 2) + 2u];
+  const uint32_t sh = (w0 & 3u) * 8u;
+  lo = sh ? ((d0 >> sh) | (d1 << (32u - sh))) : d0;
+  hi = sh ? ((d1 >> sh) | (d2 << (32u - sh))) : d1;
+  const uint32_t c_lo = lo & 0x80808080u, c_hi = hi & 0x00808080u;
+  const uint32_t cm = (((c_lo >> 7) * 0x00204081u) >> 21 & 0xfu) | ((((c_hi >> 7) * 0x00204081u) >> 21 & 0x7u) << 4);
+  return (uint32_t)__builtin_clz(~(cm << 25));  // leading ones of the 7-bit mask
+}
+
+// the low 7 bits of each of 8 bytes, joined: 56 value bits
+__device__ __forceinline__ uint64_t dv_pack7(uint64_t x) {
+  x &= 0x7f7f7f7f7f7f7f7full;
+  x = (x & 0x007f007f007f007full) | ((x & 0x7f007f007f007f00ull) >> 1);
+  x = (x & 0x00003fff00003fffull) | ((x & 0x3fff00003fff0000ull) >> 2);
+  return (x & 0x000000000fffffffull) | ((x & 0x0fffffff00000000ull) >> 4);
+}
+
 // tokens ending in this thread's 8 bytes of the tile at payload offset `pos`. tileb: [16 history bytes + tile].
 // store(kl, x, end_off): kl = index behind the `left` waiting tokens, x = the token's 7-bit groups joined (< 2^49),
-// end_off = payload offset behind the token. Tokens with a global index >= `limit` are left alone. Returns the
-// number of tokens ending in the tile (block-uniform). Contains barriers.
-template <bool LONG_TOKENS = false, typename Store>
+// end_off = payload offset behind the token. Tokens with a global index >= `limit` are left alone; a token of more than
+// 7 bytes or an overlong zero sets misc[0] and is not stored. Returns the number of tokens ending in the tile
+// (block-uniform). Contains barriers.
+template <typename Store>
 __device__ __forceinline__ uint32_t dv_tokens_tile(const uint8_t* __restrict__ src, uint32_t src_size, uint32_t pos,
                                                    uint32_t* tileb, uint32_t* misc, uint32_t left, uint32_t seen,
                                                    uint32_t limit, Store store) {
@@ -604,53 +631,20 @@ __device__ __forceinline__ uint32_t dv_tokens_tile(const uint8_t* __restrict__ s
   }
   tileb[4u + tid * 2u] = b0;
   tileb[5u + tid * 2u] = b1;
-  const uint32_t e0 = ~b0 & 0x80808080u, e1 = ~b1 & 0x80808080u;
-  // bit j of `ends` = byte j ends a token (the multiply gathers bits 0, 8, 16, 24 into 21..24)
-  const uint32_t ends = (((e0 >> 7) * 0x00204081u) >> 21 & 0xfu) | ((((e1 >> 7) * 0x00204081u) >> 21 & 0xfu) << 4);
+  const uint32_t ends = dv_ends4(b0) | (dv_ends4(b1) << 4);
   uint32_t n_tile;
   const uint32_t tb = block_exclusive_scan<T>((uint32_t)__builtin_popcount(ends), misc + 2, &n_tile);  // has a barrier
   for (uint32_t m = ends, r = 0u; m; m &= m - 1u, ++r) {
     const uint32_t j = (uint32_t)__builtin_ctz(m);
     const uint32_t kl = left + tb + r;
     if (seen + kl >= limit) break;                   // bytes of whatever follows the token stream
-    const uint32_t e = 16u + tid * 8u + j;           // byte index of the token's last byte in tileb
-    const uint32_t w0 = e - 7u;                      // window [w0, e]
-    const uint32_t d0 = tileb[w0 >> 2], d1 = tileb[(w0 >> 2) + 1u], d2 = tileb[(w0 >> 2) + 2u];
-    const uint32_t sh = (w0 & 3u) * 8u;
-    const uint32_t lo = sh ? ((d0 >> sh) | (d1 << (32u - sh))) : d0;
-    const uint32_t hi = sh ? ((d1 >> sh) | (d2 << (32u - sh))) : d1;
-    // continuation bytes right before the end byte (window bytes 6, 5, ...)
-    const uint32_t c_lo = lo & 0x80808080u, c_hi = hi & 0x00808080u;
-    const uint32_t cm = (((c_lo >> 7) * 0x00204081u) >> 21 & 0xfu) | ((((c_hi >> 7) * 0x00204081u) >> 21 & 0x7u) << 4);
-    const uint32_t lencont = (uint32_t)__builtin_clz(~(cm << 25));  // leading ones of the 7-bit mask
-    if (lencont >= 7u && !LONG_TOKENS) {
+    uint32_t lo, hi;
+    const uint32_t lencont = dv_window(tileb, 16u + tid * 8u + j, lo, hi);
+    if (lencont >= 7u) {
       misc[0] = 1u;  // token of 8 or more bytes
       continue;
     }
-    uint64_t x = ((((uint64_t)hi) << 32) | lo) >> (8u * (7u - min(lencont, 7u)));
-    x &= 0x7f7f7f7f7f7f7f7full;
-    x = (x & 0x007f007f007f007full) | ((x & 0x7f007f007f007f00ull) >> 1);
-    x = (x & 0x00003fff00003fffull) | ((x & 0x3fff00003fff0000ull) >> 2);
-    x = (x & 0x000000000fffffffull) | ((x & 0x0fffffff00000000ull) >> 4);
-    if (LONG_TOKENS && lencont >= 7u) {
-      // The window is the token's LAST 8 bytes; an int64 varint has up to 10 (the first value of a chunk's epoch time
-      // stamp at 1 us has 8): up to two more bytes in front of the window, inside the 16 bytes of history. Arithmetic
-      // modulo 2^64 like decodeVarint's shifts; the tenth byte may carry one bit (rd_varint's check).
-      const uint32_t p8 = e - 8u, p9 = e - 9u, p10 = e - 10u;
-      const uint32_t B8 = (tileb[p8 >> 2] >> ((p8 & 3u) * 8u)) & 0xffu;
-      const uint32_t B9 = (tileb[p9 >> 2] >> ((p9 & 3u) * 8u)) & 0xffu;
-      const uint32_t B10 = (tileb[p10 >> 2] >> ((p10 & 3u) * 8u)) & 0xffu;
-      if ((B8 & 0x80u) == 0u) {
-        // exactly 8 bytes: x is complete
-      } else if ((B9 & 0x80u) == 0u) {
-        x = (uint64_t)(B8 & 0x7fu) | (x << 7);
-      } else if ((B10 & 0x80u) == 0u && ((hi >> 24) & 0x7fu) <= 1u) {
-        x = (uint64_t)(B9 & 0x7fu) | ((uint64_t)(B8 & 0x7fu) << 7) | (x << 14);
-      } else {
-        misc[0] = 1u;  // more than 10 bytes, or bits beyond 64: the serial decoder raises the error
-        continue;
-      }
-    }
+    const uint64_t x = dv_pack7(((((uint64_t)hi) << 32) | lo) >> (8u * (7u - lencont)));
     if (x == 0ull && lencont != 0u) {
       // an overlong zero (0x80 0x00, ...): decodeVarint (encoding_utils.hpp:139-141) rejects every zero it is handed -- only the
       // single byte 0x00 in front of it is the NaN marker (src/field_decoder.cpp:58-62). The serial decoder raises the error.
@@ -671,207 +665,6 @@ __device__ __forceinline__ void dv_roll_history(uint32_t* tileb) {
   if (threadIdx.x < 4u) tileb[threadIdx.x] = hist;
 }
 
-template <int NOPS, bool WIDE>
-struct DvLds {
-  using Acc = typename std::conditional<WIDE, long long, int>::type;
-  static constexpr uint32_t kBytesOff = 0;                                  // [16 history + tile] bytes
-  static constexpr uint32_t kValOff = 16u + kDvTileBytes + 16u;             // Acc [8 + tile tokens]
-  static constexpr uint32_t kMarkOff = kValOff + (8u + kDvTileBytes) * (uint32_t)sizeof(Acc);  // u8 [8 + tile tokens]
-  static constexpr uint32_t kScanOff = (kMarkOff + 8u + kDvTileBytes + 15u) & ~15u;  // per wave: Acc[NOPS] + flags
-  static constexpr uint32_t kWaveRec = NOPS * (uint32_t)sizeof(Acc) + 8u;
-  static constexpr uint32_t kMiscOff = kScanOff + 17u * kWaveRec;           // 16 waves + carry record
-  static constexpr uint32_t kTotal = kMiscOff + 256u;  // misc: [0] bad, [1] end offset, [2..34) block-scan scratch
-};
-
-// One token stream of n_points x n_ops varint tokens that starts at src + start. Results: misc[0] != 0 -> irregular,
-// misc[1] = payload offset behind the last token. op_at(o) -> const DevOp&. Ends with a barrier.
-template <int NOPS, bool WIDE, typename OpAt>
-__device__ __forceinline__ void dv_stream(OpAt op_at, uint32_t n_ops, const uint8_t* __restrict__ src,
-                                          uint32_t src_size, uint32_t start, uint32_t n_points, uint8_t* base,
-                                          uint32_t step, uint8_t* smem) {
-  using L = DvLds<NOPS, WIDE>;
-  using Acc = typename L::Acc;
-  using UAcc = typename std::make_unsigned<Acc>::type;
-  constexpr int T = kDvThreads;
-  uint32_t* tileb = reinterpret_cast<uint32_t*>(smem + L::kBytesOff);
-  Acc* val = reinterpret_cast<Acc*>(smem + L::kValOff);
-  uint8_t* mark = smem + L::kMarkOff;
-  uint8_t* scanrec = smem + L::kScanOff;
-  uint32_t* misc = reinterpret_cast<uint32_t*>(smem + L::kMiscOff);
-  const uint32_t tid = threadIdx.x;
-  const uint32_t lane = tid & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t target = n_points * n_ops;
-
-  __syncthreads();  // the caller may have used the LDS
-  if (tid < 4u) tileb[tid] = 0u;  // history before the stream: token ends
-  if (tid == 0) {
-    misc[0] = 0u;
-    misc[1] = target == 0u ? start : 0xffffffffu;
-  }
-  if (tid < (uint32_t)(NOPS * sizeof(Acc) + 8u) / 4u)
-    reinterpret_cast<uint32_t*>(scanrec + 16u * L::kWaveRec)[tid] = 0u;  // carry record: sums 0
-  __syncthreads();
-
-  uint32_t pos = start;     // payload offset of the current tile
-  uint32_t pts_done = 0u;   // points already written
-  uint32_t left = 0u;       // tokens of a cut point waiting at val[0..left)
-  while (pts_done * n_ops + left < target) {
-    if (pos >= src_size) {  // stream ends before all tokens
-      if (tid == 0) misc[0] = 1u;
-      break;
-    }
-    const uint32_t seen = pts_done * n_ops;  // tokens handed to points so far
-    const uint32_t n_tile = dv_tokens_tile<WIDE>(src, src_size, pos, tileb, misc, left, seen, target,
-                                           [&](uint32_t kl, uint64_t x, uint32_t end_off) {
-                                             const bool marker = (x == 0ull);
-                                             const uint64_t u1 = x - 1ull;
-                                             const uint64_t d = (u1 >> 1) ^ (0ull - (u1 & 1ull));
-                                             val[kl] = marker ? (Acc)0 : (Acc)(UAcc)d;
-                                             mark[kl] = marker ? 1u : 0u;
-                                             if (seen + kl + 1u == target) misc[1] = end_off;
-                                           });
-
-    // ---- whole points of this tile
-    const uint32_t avail = min(left + n_tile, target - seen);
-    const uint32_t npts = avail / n_ops;
-    const uint32_t per = (npts + T - 1u) / T;
-    const uint32_t p0 = min(npts, tid * per), p1 = min(npts, p0 + per);
-    Acc acc[NOPS];
-    uint32_t fl = 0u;
-#pragma unroll
-    for (int o = 0; o < NOPS; ++o) acc[o] = 0;
-    for (uint32_t i = p0; i < p1; ++i) {
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) {
-        if ((uint32_t)o < n_ops) {
-          const uint32_t idx = i * n_ops + (uint32_t)o;
-          if (mark[idx]) {
-            acc[o] = 0;
-            fl |= 1u << o;
-            if (op_at(o).kind == OP_INT) misc[0] = 1u;  // the marker is not a valid integer token
-          } else {
-            acc[o] = (Acc)((UAcc)acc[o] + (UAcc)val[idx]);
-          }
-        }
-      }
-    }
-    // segmented inclusive scan over the threads: (f1, v1) o (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2)
-    Acc inc[NOPS];
-    uint32_t fin = fl;
-#pragma unroll
-    for (int o = 0; o < NOPS; ++o) inc[o] = acc[o];
-#pragma unroll
-    for (int dlt = 1; dlt < 64; dlt <<= 1) {
-      const uint32_t of = (uint32_t)__shfl_up((int)fin, dlt);
-      Acc ov[NOPS];
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) {
-        if (WIDE) ov[o] = (Acc)__shfl_up((long long)inc[o], dlt);
-        else ov[o] = (Acc)__shfl_up((int)inc[o], dlt);
-      }
-      if (lane >= (uint32_t)dlt) {
-#pragma unroll
-        for (int o = 0; o < NOPS; ++o)
-          if (!(fin & (1u << o))) inc[o] = (Acc)((UAcc)inc[o] + (UAcc)ov[o]);
-        fin |= of;
-      }
-    }
-    if (lane == 63u) {
-      Acc* rec = reinterpret_cast<Acc*>(scanrec + wave * L::kWaveRec);
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) rec[o] = inc[o];
-      *reinterpret_cast<uint32_t*>(scanrec + wave * L::kWaveRec + NOPS * sizeof(Acc)) = fin;
-    }
-    __syncthreads();
-    // incoming state of this thread = carry o waves before o lanes before
-    Acc in[NOPS];
-    {
-      const Acc* crec = reinterpret_cast<const Acc*>(scanrec + 16u * L::kWaveRec);
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) in[o] = crec[o];
-      for (uint32_t w = 0; w < wave; ++w) {
-        const Acc* rec = reinterpret_cast<const Acc*>(scanrec + w * L::kWaveRec);
-        const uint32_t rf = *reinterpret_cast<const uint32_t*>(scanrec + w * L::kWaveRec + NOPS * sizeof(Acc));
-#pragma unroll
-        for (int o = 0; o < NOPS; ++o) in[o] = (rf & (1u << o)) ? rec[o] : (Acc)((UAcc)in[o] + (UAcc)rec[o]);
-      }
-      // exclusive within the wave: the inclusive state of the previous lane
-      const uint32_t pf = (uint32_t)__shfl_up((int)fin, 1);
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) {
-        Acc pv;
-        if (WIDE) pv = (Acc)__shfl_up((long long)inc[o], 1);
-        else pv = (Acc)__shfl_up((int)inc[o], 1);
-        if (lane > 0u) in[o] = (pf & (1u << o)) ? pv : (Acc)((UAcc)in[o] + (UAcc)pv);
-      }
-    }
-    // second walk: final values
-    for (uint32_t i = p0; i < p1; ++i) {
-      uint8_t* pt = base + (size_t)(pts_done + i) * step;
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) {
-        if ((uint32_t)o < n_ops) {
-          const DevOp& op = op_at(o);
-          const uint32_t idx = i * n_ops + (uint32_t)o;
-          const bool isnan = mark[idx] != 0u;
-          in[o] = isnan ? (Acc)0 : (Acc)((UAcc)in[o] + (UAcc)val[idx]);
-          if (op.offset != 0xffffffffu) {
-            if (op.kind == OP_QF32) {
-              const uint32_t bits = isnan ? 0x7fc00000u : __float_as_uint(__fmul_rn((float)(int32_t)in[o], op.res_f));
-              if ((op.offset & 3u) == 0u && (step & 3u) == 0u) *reinterpret_cast<uint32_t*>(pt + op.offset) = bits;
-              else st_raw(pt + op.offset, bits, 4);
-            } else if (op.kind == OP_LOSSY_F32) {
-              const uint32_t bits = isnan ? 0x7fc00000u : __float_as_uint(__fmul_rn((float)(long long)in[o], op.res_f));
-              st_raw(pt + op.offset, bits, 4);
-            } else if (op.kind == OP_LOSSY_F64) {
-              const uint64_t bits = isnan ? 0x7ff8000000000000ull
-                                          : (uint64_t)__double_as_longlong(__dmul_rn((double)(long long)in[o], op.res_d));
-              st_raw(pt + op.offset, bits, 8);
-            } else {
-              st_raw(pt + op.offset, (uint64_t)(long long)in[o], op.size);
-            }
-          }
-        }
-      }
-    }
-    // block state after this tile -> carry; the cut point's tokens and the last 16 bytes move to the front
-    const uint32_t used = npts * n_ops;
-    const uint32_t rest = avail - used;  // < n_ops <= 8
-    Acc mv = 0;
-    uint8_t mm = 0;
-    if (tid < rest) {
-      mv = val[used + tid];
-      mm = mark[used + tid];
-    }
-    dv_roll_history(tileb);  // barrier inside: every thread is done with val / mark / scanrec
-    if (tid == (uint32_t)T - 1u) {  // the last thread's inclusive state is the block total
-      Acc* crec = reinterpret_cast<Acc*>(scanrec + 16u * L::kWaveRec);
-#pragma unroll
-      for (int o = 0; o < NOPS; ++o) crec[o] = in[o];
-    }
-    if (tid < rest) {
-      val[tid] = mv;
-      mark[tid] = mm;
-    }
-    __syncthreads();
-    pos += kDvTileBytes;
-    pts_done += npts;
-    left = rest;
-    if (misc[0]) break;  // uniform after the barrier
-  }
-  __syncthreads();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// dv_stream2: the same job as dv_stream without staging token values in LDS. The tokens that end inside a thread's
-// BPT bytes are consecutive tokens of the stream, so the thread that decodes them also owns them: it keeps their
-// values in registers (indexed by the byte position of the token's last byte), folds them into one partial sum per
-// op (token g belongs to op g % n_ops), the segmented block scan hands it the running values in front of its first
-// token, and a second walk over the same registers produces and stores the final values -- consecutive tokens are
-// consecutive fields of consecutive points, so the stores of neighbouring threads are neighbours too. Nothing
-// waits at a tile edge: a point cut by it simply continues with the carried per-op state.
-// ---------------------------------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------------------------------
 // k_mark_token_ends: regular streams with raw fields between the varints (FieldEncoderCopy, field_encoder.hpp:342-357:
 // XYZ + a packed rgb float without resolution is the PCL PointXYZRGB layout). A raw byte may look like anything, so the
@@ -1068,8 +861,21 @@ __global__ __launch_bounds__(kMtThreads) void k_mark_token_ends(const DevPlan pl
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// dv_stream, the tile walker: one token stream of n_points x n_ops varint tokens that starts at src + start.
+// Results: misc[0] != 0 -> irregular (the stream ends early, a token of more than 10 bytes or with bits beyond 64 --
+// more than 7 bytes without WIDE --, an overlong zero, a 0x00 marker in an integer op), misc[1] = payload offset
+// behind the last token. op_at(o) -> const DevOp&. Ends with a barrier.
+// A tile is BPT bytes per thread. The tokens that end inside a thread's BPT bytes are consecutive tokens of the
+// stream, so the thread that decodes them also owns them: it keeps their values in registers (indexed by the byte
+// position of the token's last byte), folds them into one partial sum per op (token g belongs to op g % n_ops), the
+// segmented block scan hands it the running values in front of its first token, and a second walk over the same
+// registers produces and stores the final values -- consecutive tokens are consecutive fields of consecutive points,
+// so the stores of neighbouring threads are neighbours too. Nothing waits at a tile edge: a point cut by it simply
+// continues with the carried per-op state.
+// ---------------------------------------------------------------------------------------------------------------
 template <int NOPS, bool WIDE, int BPT>
-struct Dv2Lds {
+struct DvLds {
   using Acc = typename std::conditional<WIDE, long long, int>::type;
   static constexpr uint32_t kTileBytes = kDvThreads * BPT;
   static constexpr uint32_t kBytesOff = 0;                                 // [16 history + tile + 16] bytes
@@ -1083,10 +889,10 @@ struct Dv2Lds {
 // byte p ends a token) that k_mark_token_ends has laid out -- streams with raw (FieldEncoderCopy) fields between the
 // varints. A raw field is a token like any other there: its value is its bytes, it resets its op's running sum.
 template <int NOPS, bool WIDE, int BPT, typename OpAt>
-__device__ __forceinline__ void dv_stream2(OpAt op_at, uint32_t n_ops, const uint8_t* __restrict__ src,
-                                           uint32_t src_size, uint32_t start, uint32_t n_points, uint8_t* base,
-                                           uint32_t step, uint8_t* smem, const uint8_t* __restrict__ end_bits = nullptr) {
-  using L = Dv2Lds<NOPS, WIDE, BPT>;
+__device__ __forceinline__ void dv_stream(OpAt op_at, uint32_t n_ops, const uint8_t* __restrict__ src,
+                                          uint32_t src_size, uint32_t start, uint32_t n_points, uint8_t* base,
+                                          uint32_t step, uint8_t* smem, const uint8_t* __restrict__ end_bits = nullptr) {
+  using L = DvLds<NOPS, WIDE, BPT>;
   using Acc = typename L::Acc;
   using UAcc = typename std::make_unsigned<Acc>::type;
   constexpr int T = kDvThreads;
@@ -1147,7 +953,7 @@ __device__ __forceinline__ void dv_stream2(OpAt op_at, uint32_t n_ops, const uin
 #pragma unroll
     for (int k = 0; k < DW; ++k) {
       tileb[4u + tid * DW + k] = b[k];
-      ends |= ((((~b[k] & 0x80808080u) >> 7) * 0x00204081u) >> 21 & 0xfu) << (4 * k);
+      ends |= dv_ends4(b[k]) << (4 * k);
     }
     uint32_t ehist = 0u;  // bitmap mode: bit k = byte my - 16 + k ends a token (k < 16: in front of my bytes; the byte in front of the payload counts as an end)
     if (WIDE && BPT == 8 && end_bits != nullptr) {
@@ -1174,14 +980,8 @@ __device__ __forceinline__ void dv_stream2(OpAt op_at, uint32_t n_ops, const uin
         if ((ends >> j) & 1u) {
           if (g < target) {
             const uint32_t e = 16u + tid * BPT + (uint32_t)j;  // byte index of the token's last byte in tileb
-            const uint32_t w0 = e - 7u;                        // window [w0, e]
-            const uint32_t d0 = tileb[w0 >> 2], d1 = tileb[(w0 >> 2) + 1u], d2 = tileb[(w0 >> 2) + 2u];
-            const uint32_t sh = (w0 & 3u) * 8u;
-            const uint32_t lo = sh ? ((d0 >> sh) | (d1 << (32u - sh))) : d0;
-            const uint32_t hi = sh ? ((d1 >> sh) | (d2 << (32u - sh))) : d1;
-            const uint32_t c_lo = lo & 0x80808080u, c_hi = hi & 0x00808080u;
-            const uint32_t cm = (((c_lo >> 7) * 0x00204081u) >> 21 & 0xfu) | ((((c_hi >> 7) * 0x00204081u) >> 21 & 0x7u) << 4);
-            uint32_t lencont = (uint32_t)__builtin_clz(~(cm << 25));  // continuation bytes before the end byte
+            uint32_t lo, hi;
+            uint32_t lencont = dv_window(tileb, e, lo, hi);  // continuation bytes before the end byte
             bool from_bits = false;
             if (WIDE && BPT == 8 && end_bits != nullptr) {
               // with raw fields in the stream the bytes in front of a token say nothing about it: its length is the
@@ -1194,11 +994,7 @@ __device__ __forceinline__ void dv_stream2(OpAt op_at, uint32_t n_ops, const uin
               from_bits = true;
             }
             if (lencont >= 7u && !WIDE) misc[0] = 1u;                        // token of 8 or more bytes
-            uint64_t x = ((((uint64_t)hi) << 32) | lo) >> (8u * (7u - min(lencont, WIDE ? 7u : 6u)));
-            x &= 0x7f7f7f7f7f7f7f7full;
-            x = (x & 0x007f007f007f007full) | ((x & 0x7f007f007f007f00ull) >> 1);
-            x = (x & 0x00003fff00003fffull) | ((x & 0x3fff00003fff0000ull) >> 2);
-            x = (x & 0x000000000fffffffull) | ((x & 0x0fffffff00000000ull) >> 4);
+            uint64_t x = dv_pack7(((((uint64_t)hi) << 32) | lo) >> (8u * (7u - min(lencont, WIDE ? 7u : 6u))));
             if (WIDE && lencont >= 7u) {
               // The window is the token's LAST 8 bytes; an int64 varint has up to 10 (the first value of a chunk's epoch
               // time stamp at 1 us has 8): up to two more bytes in front of the window, inside the 16 bytes of history.
@@ -1410,7 +1206,7 @@ __device__ __forceinline__ void decode_varint_body(const DevPlan plan, const uin
                                                               uint32_t* __restrict__ status, uint32_t redo_only,
                                                               const uint32_t* __restrict__ token_ends = nullptr) {
   constexpr int BPT = WIDE ? 8 : 16;
-  using L = Dv2Lds<NOPS, WIDE, BPT>;
+  using L = DvLds<NOPS, WIDE, BPT>;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint32_t c = blockIdx.x;
   const DecChunk dc = chunks[c];
@@ -1422,7 +1218,7 @@ __device__ __forceinline__ void decode_varint_body(const DevPlan plan, const uin
     if (reg_end[c] == kDecRedo) return;  // k_mark_token_ends found the stream irregular: the serial decoder takes the chunk
     end_bits = reinterpret_cast<const uint8_t*>(token_ends + token_ends_word(dc.src_off, c));
   }
-  dv_stream2<NOPS, WIDE, BPT>([&](int o) -> const DevOp& { return plan.ops[o]; }, plan.n_ops, streams + dc.src_off,
+  dv_stream<NOPS, WIDE, BPT>([&](int o) -> const DevOp& { return plan.ops[o]; }, plan.n_ops, streams + dc.src_off,
                               dc.src_size, 0u, dc.n_points, base, plan.point_step, smem, end_bits);
   const uint32_t* misc = reinterpret_cast<const uint32_t*>(smem + L::kMiscOff);
   if (threadIdx.x == 0) {
@@ -1446,37 +1242,17 @@ __global__ __launch_bounds__(kDvThreads) __attribute__((amdgpu_waves_per_eu(WIDE
 constexpr uint32_t kRunTile = 4096;     // DeltaRle: runs per table tile (8192 tokens)
 constexpr uint32_t kRleRunTile = 2048;  // Rle: runs parsed per round
 constexpr uint32_t kRleStage = 16384;   // Rle: section bytes staged per round
-struct DecSecLds {  // the DvLds<1, true> layout (DeltaVarint uses it as is) + a run-start table behind it
-  using DL = DvLds<1, true>;
-  static constexpr uint32_t kRawOff = DL::kValOff;                      // u64 [8 + 8192]: token values, then run table
+// (The three kernels that run decode_sections_core -- k_decode_sections, k_decode_tail, k_decode_sections_cols -- carry
+// amdgpu_waves_per_eu(7): the walker's registers would otherwise put them at 73..76 VGPRs, one allocation step past 72.)
+struct DecSecLds {  // the walker's own layout in front (DeltaVarint uses it as is), the other modes' tables behind it
+  using DL = DvLds<1, true, 8>;                                         // history + tile, scan records, misc
+  static constexpr uint32_t kRawOff = DL::kTotal;                       // u64 [8 + 8192]: DeltaRle tokens, then run table; Palette
   static constexpr uint32_t kStageOff = kRawOff + 2u * kRleRunTile * 8u;  // Rle: staged bytes behind its run table
-  static constexpr uint32_t kStartOff = DL::kTotal;                     // u32 [kRunTile + 4]
+  static constexpr uint32_t kStartOff = kRawOff + (8u + kDvTileBytes) * 8u;  // u32 [kRunTile + 4]: run starts
   static constexpr uint32_t kTotal = kStartOff + (kRunTile + 4u) * 4u;
-  static_assert(kStageOff + kRleStage + 16u <= DL::kMarkOff + 8u + kDvTileBytes, "Rle staging fits the token area");
+  static_assert(DL::kTileBytes == kDvTileBytes && kRawOff % 16u == 0u, "dv_tokens_tile shares the walker's tile");
+  static_assert(kStageOff + kRleStage + 16u <= kStartOff, "Rle staging fits the token area");
 };
-
-template <int T>
-__device__ __forceinline__ uint64_t block_exclusive_scan_u64(uint64_t x, uint64_t* wtot, uint64_t* total) {
-  constexpr int NW = T / 64;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint64_t incl = x;
-#pragma unroll
-  for (int dlt = 1; dlt < 64; dlt <<= 1) {
-    const uint64_t o = (uint64_t)__shfl_up((long long)incl, dlt);
-    if (lane >= (uint32_t)dlt) incl += o;
-  }
-  if (lane == 63u) wtot[wave] = incl;
-  __syncthreads();
-  uint64_t basev = 0u, tot = 0u;
-  for (uint32_t w = 0; w < (uint32_t)NW; ++w) {
-    const uint64_t t = wtot[w];
-    if (w < wave) basev += t;
-    tot += t;
-  }
-  *total = tot;
-  return basev + incl - x;
-}
 
 // every output index of [s0, s1) finds its run r in start[0..n_runs] (start[n_runs] = s1) and stores
 // tab[2r] + tab[2r+1] * (i - start[r] + 1)   (DeltaRle, v5_codec.cpp:851-872; Rle has tab[2r+1] = 0)
@@ -1636,7 +1412,7 @@ __device__ __forceinline__ bool dec_palette(const uint8_t* __restrict__ src, uin
 
 // Chunks whose sections are all Palette with small palettes (the common case: intensity, ring, reflectivity ...) need
 // almost no LDS; this kernel takes them at two workgroups per CU and leaves every other chunk to k_decode_sections,
-// whose 100 KiB of LDS (token tiles, run tables) allow only one.
+// whose 89 KiB of LDS (token tile, run tables) allow only one.
 constexpr uint32_t kSmallPalEntries = 1024;
 constexpr uint32_t kSmallSecLds = kSmallPalEntries * 8u + 8192u * 4u + 256u;  // palette, transposition buffer, misc
 
@@ -1701,7 +1477,7 @@ struct SecFieldOut {
 template <typename FieldOut>
 __device__ __forceinline__ bool decode_sections_core(const DevPlan& plan, const uint8_t* __restrict__ src, uint32_t src_size,
                                                      uint32_t off, uint32_t n, FieldOut field_out, uint8_t* smem) {
-  using DL = DvLds<1, true>;
+  using DL = DecSecLds::DL;
   constexpr int T = kDvThreads;
   uint32_t* misc = reinterpret_cast<uint32_t*>(smem + DL::kMiscOff);  // [0] bad, [1] end, [2..34) scan, [40..48) handlers
   uint32_t* tileb = reinterpret_cast<uint32_t*>(smem + DL::kBytesOff);
@@ -1720,11 +1496,11 @@ __device__ __forceinline__ bool decode_sections_core(const DevPlan& plan, const 
     const uint32_t mode = src[off];
     ++off;
     if (mode == 0u) {  // ---- DeltaVarint: n integer tokens
-      DevOp op;
+      DevOp op = {};
       op.kind = OP_INT;
       op.size = (uint8_t)bpv;
       op.offset = field_off;
-      dv_stream<1, true>([&](int) -> const DevOp& { return op; }, 1u, src, src_size, off, n, base, step, smem);
+      dv_stream<1, true, 8>([&](int) -> const DevOp& { return op; }, 1u, src, src_size, off, n, base, step, smem);
       if (misc[0] || misc[1] == 0xffffffffu) bad = true;
       else off = misc[1];
       __syncthreads();
@@ -1908,7 +1684,7 @@ __device__ __forceinline__ void decode_sections_body(const DevPlan plan, const u
   }
 }
 
-__global__ __launch_bounds__(kDvThreads) void k_decode_sections(const DevPlan plan, const uint8_t* __restrict__ streams,
+__global__ __launch_bounds__(kDvThreads) __attribute__((amdgpu_waves_per_eu(7))) void k_decode_sections(const DevPlan plan, const uint8_t* __restrict__ streams,
                                                                 const DecChunk* __restrict__ chunks,
                                                                 uint8_t* __restrict__ out,
                                                                 const uint32_t* __restrict__ reg_end,
@@ -1922,7 +1698,7 @@ __global__ __launch_bounds__(kDvThreads) void k_decode_sections(const DevPlan pl
 // whatever those stepped away from -> the serial decoder on thread 0. The bodies are the kernels above; a barrier
 // between them orders what one leaves in reg_end / sec_done for the next. All early exits of the bodies are uniform
 // over the workgroup (they depend on the chunk table, reg_end, sec_done and LDS words read behind barriers).
-__global__ __launch_bounds__(kDvThreads) void k_decode_tail(const DevPlan plan, const uint8_t* __restrict__ streams,
+__global__ __launch_bounds__(kDvThreads) __attribute__((amdgpu_waves_per_eu(7))) void k_decode_tail(const DevPlan plan, const uint8_t* __restrict__ streams,
                                                             const DecChunk* __restrict__ chunks, uint8_t* __restrict__ out,
                                                             uint32_t* __restrict__ reg_end, uint8_t* __restrict__ sec_done,
                                                             uint32_t* __restrict__ status, uint32_t uses_v5,

@@ -49,7 +49,7 @@ const PointsKernels kPointsKernels[] = {points_kernels<0>(), points_kernels<1>()
                                         points_kernels<8>(), points_kernels<9>(), points_kernels<10>()};
 static_assert(sizeof(kPointsKernels) / sizeof(kPointsKernels[0]) == kPointsVariantCount, "one entry per kPointsVariants[]");
 
-constexpr uint32_t kTailLds = (uint32_t)Dv2Lds<4, false, 16>::kTotal;  // k_decode_tail without sections, and with them:
+constexpr uint32_t kTailLds = (uint32_t)DvLds<4, false, 16>::kTotal;  // k_decode_tail without sections, and with them:
 constexpr uint32_t kTailSectionsLds = std::max<uint32_t>(std::max<uint32_t>(kTailLds, kSmallSecLds), (uint32_t)DecSecLds::kTotal);
 
 // the plan the stream kernel decodes DeltaVarint SECTIONS with: op a = the integer field a as a stream of its own, stored
@@ -272,7 +272,7 @@ int stage1_launch_decode(const DecodeLaunch& L0) {
       TRY_LAUNCH("k_decode_stream_w (gorilla)", k_decode_stream_w<12, 2>, chunks, dim3(12 * 64), SwLds<12, 2>::kTotal, L.stream, P, L.streams,
                  L.chunks, L.out, L.reg_end, L.status, nullptr, 0u, DecColumns{}, nullptr, nullptr, nullptr);
     else if (R.regular == DR_MIXED_VARINT)
-      TRY_LAUNCH("k_decode_varint (mixed)", k_decode_varint<8, true>, chunks, dim3(kDvThreads), Dv2Lds<8, true, 8>::kTotal, L.stream, P,
+      TRY_LAUNCH("k_decode_varint (mixed)", k_decode_varint<8, true>, chunks, dim3(kDvThreads), DvLds<8, true, 8>::kTotal, L.stream, P,
                  L.streams, L.chunks, L.out, L.reg_end, L.status, 0u, L.token_ends);
     else  // DR_STREAM, DR_STREAM_COLS, DR_STREAM_BITMAP (chunks it finds irregular go to the kernels behind)
       TRY_LAUNCH("k_decode_stream_w", k_decode_stream_w<16, 0>, chunks, dim3(16 * 64), SwLds<16, 0>::kTotal, L.stream, P, L.streams, L.chunks,
@@ -286,10 +286,10 @@ int stage1_launch_decode(const DecodeLaunch& L0) {
     TRY_LAUNCH("k_decode_tail", k_decode_tail, chunks, dim3(kDvThreads), R.tail_sections ? kTailSectionsLds : kTailLds, L.stream, P, L.streams,
                L.chunks, L.out, L.reg_end, L.sec_done, L.status, L.uses_v5, R.tail_sections ? 1u : 0u);
   if (R.redo == DO_QF32)
-    TRY_LAUNCH("k_decode_varint", k_decode_varint<4, false>, chunks, dim3(kDvThreads), Dv2Lds<4, false, 16>::kTotal, L.stream, P, L.streams,
+    TRY_LAUNCH("k_decode_varint", k_decode_varint<4, false>, chunks, dim3(kDvThreads), DvLds<4, false, 16>::kTotal, L.stream, P, L.streams,
                L.chunks, L.out, L.reg_end, L.status, R.redo_only ? 1u : 0u, nullptr);
   if (R.redo == DO_ANY)
-    TRY_LAUNCH("k_decode_varint", k_decode_varint<8, true>, chunks, dim3(kDvThreads), Dv2Lds<8, true, 8>::kTotal, L.stream, P, L.streams,
+    TRY_LAUNCH("k_decode_varint", k_decode_varint<8, true>, chunks, dim3(kDvThreads), DvLds<8, true, 8>::kTotal, L.stream, P, L.streams,
                L.chunks, L.out, L.reg_end, L.status, R.redo_only ? 1u : 0u, nullptr);
   if (R.sections == DS_SIDE_BY_SIDE) {
     const dim3 grid(L.n_chunks, P.n_adaptive);

@@ -760,7 +760,7 @@ __global__ __launch_bounds__(kScfThreads) void k_sections_cols_fast(const DevPla
 // fields. Chunks k_locate_sections did not look at (a small Palette seen from the end) are left alone.
 // grid = n_chunks, kDvThreads threads, DecSecLds::kTotal bytes of LDS.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kDvThreads) void k_decode_sections_cols(const DevPlan plan, const uint8_t* __restrict__ streams,
+__global__ __launch_bounds__(kDvThreads) __attribute__((amdgpu_waves_per_eu(7))) void k_decode_sections_cols(const DevPlan plan, const uint8_t* __restrict__ streams,
                                                                      const DecChunk* __restrict__ chunks, uint32_t n_ops,
                                                                      uint8_t* __restrict__ col0, uint8_t* __restrict__ col1,
                                                                      const uint32_t* __restrict__ reg_end_pre,

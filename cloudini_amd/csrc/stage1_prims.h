@@ -54,6 +54,25 @@ __device__ __forceinline__ unsigned long long wave_inclusive_scan_u64(unsigned l
   return x;
 }
 
+// block_exclusive_scan for one uint64 per thread (sums modulo 2^64). `wtot` is an LDS array of T / 64 uint64. Contains one
+// __syncthreads(); the caller separates two calls (or other uses of wtot) by a barrier.
+template <int T>
+__device__ __forceinline__ uint64_t block_exclusive_scan_u64(uint64_t x, uint64_t* wtot, uint64_t* total) {
+  constexpr int NW = T / 64;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t incl = wave_inclusive_scan_u64(x);
+  if ((threadIdx.x & 63u) == 63u) wtot[wave] = incl;
+  __syncthreads();
+  uint64_t basev = 0u, tot = 0u;
+  for (uint32_t w = 0; w < (uint32_t)NW; ++w) {
+    const uint64_t t = wtot[w];
+    if (w < wave) basev += t;
+    tot += t;
+  }
+  *total = tot;
+  return basev + incl - x;
+}
+
 // Running exclusive prefix sum of ONE workgroup of 1024 threads over rounds of 1024 items (the stage-2 and viz kernels that
 // number chunks, blocks or bytes of a whole batch): every thread calls it once per round with its item's value (0 behind the
 // last item) and gets the sum of all values in front of its item, earlier rounds included. `carry` is a register of every
