@@ -96,6 +96,10 @@ def lib() -> C.CDLL:
     L.cldn_amd_device_lz4_decode.restype = C.c_int
     L.cldn_amd_set_device_lz4_decode.restype = C.c_int
     L.cldn_amd_set_device_lz4_decode.argtypes = [C.c_int]
+    L.cldn_amd_device_zstd_decode.restype = C.c_int
+    L.cldn_amd_set_device_zstd_decode.restype = C.c_int
+    L.cldn_amd_set_device_zstd_decode.argtypes = [C.c_int]
+    L.cldn_amd_device_zstd_decode_count.restype = C.c_uint64
     L.cldn_amd_device_zstd.restype = C.c_int
     L.cldn_amd_set_device_zstd.restype = C.c_int
     L.cldn_amd_set_device_zstd.argtypes = [C.c_int]
@@ -174,6 +178,24 @@ def set_device_lz4_decode(on) -> bool:
     """PointcloudDecoder.decode of LZ4 messages (wire version >= 3) with stage 2 undone on the GPU (cldn_hip_decode_lz4) instead
     of liblz4 on the host pool. Off by default. Returns the value in effect."""
     return bool(lib().cldn_amd_set_device_lz4_decode(1 if on else 0))
+
+
+def device_zstd_decode() -> bool:
+    return bool(lib().cldn_amd_device_zstd_decode())
+
+
+def set_device_zstd_decode(on) -> bool:
+    """PointcloudDecoder.decode of ZSTD messages (wire version >= 3) whose frames carry no sequences -- what set_device_zstd
+    writes -- with stage 2 undone on the GPU (cldn_hip_decode_zstd); every other message takes the host route as before.
+    Measured: a single message is 6 to 20 times slower this way than on 16 host threads; the device decoder pays for
+    device-resident batches (native.Codec.decode_zstd_device), not for single host messages. Off by default. Returns the value in
+    effect."""
+    return bool(lib().cldn_amd_set_device_zstd_decode(1 if on else 0))
+
+
+def device_zstd_decode_count() -> int:
+    """Messages that took the device route through set_device_zstd_decode since the library was loaded (fall-backs are silent)."""
+    return int(lib().cldn_amd_device_zstd_decode_count())
 
 
 def device_zstd() -> bool:

@@ -199,6 +199,7 @@ struct cldn_hip_codec {
   DevBuf d_s1, d_s1_offsets, d_lz_matches, d_stage2_ws, d_payload2, d_dst2, d_dec_split;
   // LZ4 blocks back into bytes (cldn_hip_decode_lz4 / cldn_hip_lz4_decompress): one worst-case slot per chunk, the offset tables
   DevBuf d_lzd_slots, d_lzd_tables;
+  DevBuf d_zsd_ws;  // ZSTD decode (zstd_decode.hip): block records, weights, frame tables
   DevBuf d_finrec;            // k_finish look-back records (rec, rec2), cleared only when (re)allocated
   int decode_fill = CLDN_HIP_FILL_KEEP;  // cldn_hip_codec_set_decode_fill
   DevBuf d_dec_bits;          // k_mark_token_ends: token-end bitmap of the streams of a decode call
@@ -657,7 +658,7 @@ void cldn_hip_codec_destroy(cldn_hip_codec_t* c) {
   (void)guard.enter(c->device);
   (void)hipStreamSynchronize(c->stream);
   DevBuf* bufs[] = {&c->d_in, &c->d_out, &c->d_slots, &c->d_chunks, &c->d_cloud_first, &c->d_finrec, &c->d_dec_rec, &c->d_dec_bits, &c->d_dec_secs, &c->d_s1, &c->d_s1_offsets,
-                    &c->d_lz_matches, &c->d_stage2_ws, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables,
+                    &c->d_lz_matches, &c->d_stage2_ws, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables, &c->d_zsd_ws,
                     &c->d_payload, &c->d_dst, &c->d_offsets, &c->d_modes, &c->d_status, &c->d_dec_meta, &c->d_pre_ptrs, &c->d_dec_cols[0], &c->d_dec_cols[1], &c->d_dec_cols[2], &c->d_dec_cols[3], &c->d_dec_cols[4], &c->d_dec_cols[5], &c->d_dec_cols[6], &c->d_dec_cols[7],
                     &c->d_viz_keys, &c->d_viz_slot, &c->d_viz_blocks, &c->d_viz_bits, &c->d_viz_tables, &c->d_viz_kept, &c->d_viz_out,
                     &c->d_pieces, &c->d_audit, &c->d_audit_tab, &c->d_audit_rep};
@@ -814,6 +815,8 @@ int cldn_hip_codec_status(cldn_hip_codec_t* c) {
   }
   if (st & ST_OUT_OVERFLOW) return fail(CLDN_HIP_ERR_CAPACITY, "Output buffer too small for the encoded stream");
   if (st & ST_LZ4_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed");
+  if (st & ST_ZSTD_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "ZSTD decompression failed");
+  if (st & ST_ZSTD_HOST) return fail(CLDN_HIP_ERR_UNSUPPORTED, "ZSTD frame carries sequences or options the device decoder does not take");
   if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "malformed stage-1 stream");
   return CLDN_HIP_OK;
 }
@@ -1787,31 +1790,40 @@ int cldn_hip_decode_stage1(cldn_hip_codec_t* c, const void* streams, int streams
 // what the status word of a framed decode call means to its caller
 static int decode_verdict(uint32_t st) {
   if (st & ST_LZ4_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed");
+  if (st & ST_ZSTD_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "ZSTD decompression failed");
+  if (st & ST_ZSTD_HOST) return fail(CLDN_HIP_ERR_UNSUPPORTED, "ZSTD frame carries sequences or options the device decoder does not take");
   if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "malformed stage-1 stream (truncated, bad chunk size, bad mode or trailing bytes)");
   return CLDN_HIP_OK;
 }
 
-// the framed decode calls. lz4: every chunk of `streams` is [u32 block size][LZ4 block] (cldn_hip_decode_lz4)
+// the framed decode calls. stage2 = CLDN_HIP_STAGE2_LZ4: every chunk of `streams` is [u32 block size][LZ4 block]
+// (cldn_hip_decode_lz4); CLDN_HIP_STAGE2_ZSTD: [u32 frame size][ZSTD frame] (cldn_hip_decode_zstd)
 static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                          const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
-                         void* points_out, uint64_t out_capacity, int out_loc, bool lz4);
+                         void* points_out, uint64_t out_capacity, int out_loc, int stage2);
 
 int cldn_hip_decode_stage1_sized(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                                  const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
                                  void* points_out, uint64_t out_capacity, int out_loc) {
   return decode_framed(c, streams, streams_loc, stream_offsets, cloud_points, n_clouds, chunk_sizes, chunk_sizes_loc, points_out,
-                       out_capacity, out_loc, false);
+                       out_capacity, out_loc, CLDN_HIP_STAGE2_NONE);
 }
 
 int cldn_hip_decode_lz4(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                         const uint64_t* cloud_points, uint32_t n_clouds, void* points_out, uint64_t out_capacity, int out_loc) {
   return decode_framed(c, streams, streams_loc, stream_offsets, cloud_points, n_clouds, nullptr, CLDN_HIP_HOST, points_out,
-                       out_capacity, out_loc, true);
+                       out_capacity, out_loc, CLDN_HIP_STAGE2_LZ4);
+}
+
+int cldn_hip_decode_zstd(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
+                         const uint64_t* cloud_points, uint32_t n_clouds, void* points_out, uint64_t out_capacity, int out_loc) {
+  return decode_framed(c, streams, streams_loc, stream_offsets, cloud_points, n_clouds, nullptr, CLDN_HIP_HOST, points_out,
+                       out_capacity, out_loc, CLDN_HIP_STAGE2_ZSTD);
 }
 
 static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                          const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
-                         void* points_out, uint64_t out_capacity, int out_loc, bool lz4) {
+                         void* points_out, uint64_t out_capacity, int out_loc, int stage2) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   c->enc.drop();
   if (chunk_sizes && chunk_sizes_loc != CLDN_HIP_HOST && chunk_sizes_loc != CLDN_HIP_DEVICE)
@@ -1969,15 +1981,36 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   // LZ4 chunks: a slot per chunk with the capacity the host path gives LZ4_decompress_safe (cloudini.cpp, PointcloudDecoder::
   // decodeInto: the bound of a chunk's stage-1 payload + 60); the decoders then read the slots as their stream buffer
   uint64_t decoder_stream_bytes = stream_bytes - base_off;
-  if (lz4 && n_chunks) {
+  const bool lz4 = stage2 == CLDN_HIP_STAGE2_LZ4, zstd = stage2 == CLDN_HIP_STAGE2_ZSTD;
+  ZstdDecodeLaunch Z;  // (the ZSTD part of this call: L.zstd points at it until stage1_launch_decode has returned)
+  memset(&Z, 0, sizeof(Z));
+  if ((lz4 || zstd) && n_chunks) {
     const uint64_t capacity = cldn_hip_stage1_bound(&c->plan, kPointsPerChunk) + 60u;
-    if (capacity > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "decode_lz4: a chunk of this schema may exceed 2 GiB");
+    if (capacity > 0x7fffffffull) return fail(CLDN_HIP_ERR_UNSUPPORTED, "decode_%s: a chunk of this schema may exceed 2 GiB", lz4 ? "lz4" : "zstd");
     const uint64_t stride = (capacity + 15u) & ~uint64_t(15);
     decoder_stream_bytes = stride * n_chunks;
     if ((rc = c->d_lzd_slots.ensure((size_t)decoder_stream_bytes + 256u)) != CLDN_HIP_OK) return rc;
     L.lz4_slots = (uint8_t*)c->d_lzd_slots.p;
     L.lz4_slot_stride = stride;
     L.lz4_capacity = (uint32_t)capacity;
+    if (zstd) {  // the frames' block records, sized from the bytes of the call
+      if (stream_bytes - base_off > 0x7fffffffull * 64u) return fail(CLDN_HIP_ERR_UNSUPPORTED, "decode_zstd: streams of more than 128 GiB");
+      const uint32_t max_recs = ZstdDecodeLaunch::records_for(n_chunks, stream_bytes - base_off, decoder_stream_bytes);
+      // [workspace | sizes u32 per chunk]
+      const size_t ws = (ZstdDecodeLaunch::workspace_bytes(max_recs, n_chunks) + 255u) & ~size_t(255);
+      if ((rc = c->d_zsd_ws.ensure(ws + (size_t)n_chunks * 4u)) != CLDN_HIP_OK) return rc;
+      Z.carve(c->d_zsd_ws.p, max_recs, n_chunks);
+      Z.stream = c->stream;
+      Z.frames = d_streams;
+      Z.n_frames = n_chunks;
+      Z.out = L.lz4_slots;
+      Z.sizes = (uint32_t*)((uint8_t*)c->d_zsd_ws.p + ws);
+      Z.status = (uint32_t*)c->d_status.p;
+      Z.chunks = L.chunks;
+      Z.slot_stride = stride;
+      Z.capacity = (uint32_t)capacity;
+      L.zstd = &Z;
+    }
   }
   if (plan.varint_and_raw && n_chunks) {  // one bit per stream byte + a word per chunk (k_mark_token_ends)
     if ((rc = c->d_dec_bits.ensure((size_t)(decoder_stream_bytes / 8u) + (size_t)n_chunks * 4u + 256u)) != CLDN_HIP_OK) return rc;
@@ -2116,6 +2149,87 @@ int cldn_hip_lz4_decompress(cldn_hip_codec_t* c, const void* blocks, int blocks_
   if (o_bytes) HIP_TRY(hipMemcpyAsync((uint8_t*)out + o0, d_outp, (size_t)o_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed (sizes[k] == 0xffffffff marks the blocks)");
+  return CLDN_HIP_OK;
+}
+
+int cldn_hip_zstd_decompress(cldn_hip_codec_t* c, const void* frames, int frames_loc, const uint64_t* frame_offsets, uint32_t n_frames,
+                            void* out, int out_loc, const uint64_t* out_offsets, uint32_t* sizes) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
+  if ((frames_loc != CLDN_HIP_HOST && frames_loc != CLDN_HIP_DEVICE) || (out_loc != CLDN_HIP_HOST && out_loc != CLDN_HIP_DEVICE))
+    return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  if (n_frames == 0) return CLDN_HIP_OK;
+  if (!frame_offsets || !out_offsets || !sizes) return fail(CLDN_HIP_ERR_ARG, "zstd_decompress: NULL offsets / sizes");
+  if (out_loc == CLDN_HIP_DEVICE && ((uintptr_t)sizes & 3u)) return fail(CLDN_HIP_ERR_ARG, "zstd_decompress: device sizes must be 4-byte aligned");
+  for (uint32_t k = 0; k < n_frames; ++k) {
+    if (frame_offsets[k + 1] < frame_offsets[k] || out_offsets[k + 1] < out_offsets[k])
+      return fail(CLDN_HIP_ERR_ARG, "zstd_decompress: offsets must be ascending");
+    if (frame_offsets[k + 1] - frame_offsets[k] > 0x7fffffffull || out_offsets[k + 1] - out_offsets[k] > 0x7fffffffull)
+      return fail(CLDN_HIP_ERR_UNSUPPORTED, "zstd_decompress: block or output span of more than 2 GiB");
+  }
+  const uint64_t b0 = frame_offsets[0], b_bytes = frame_offsets[n_frames] - b0;
+  const uint64_t o0 = out_offsets[0], o_bytes = out_offsets[n_frames] - o0;
+  if ((b_bytes && !frames) || (o_bytes && !out)) return fail(CLDN_HIP_ERR_ARG, "zstd_decompress: NULL buffer");
+  ENTER_DEVICE(c->device);
+  int rc;
+  if ((rc = c->d_status.ensure(256)) != CLDN_HIP_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, 256, c->stream));
+  // tables: [block offsets u64 | out offsets u64] relative to the first block / span, [sizes u32] for HOST outputs
+  const size_t ne = (size_t)n_frames + 1;
+  if ((rc = c->d_lzd_tables.ensure(ne * 16u + (size_t)n_frames * 4u)) != CLDN_HIP_OK) return rc;
+  // (staged through the decode calls' ring of page-locked buffers: no wait for the stream unless the ring has gone round)
+  const uint32_t slot = c->dec_stage_next++ % (uint32_t)cldn_hip_codec::kDecStageRing;
+  PinnedBuf& stage = c->h_dec_stage[slot];
+  if (c->dec_stage_ev[slot]) HIP_TRY(hipEventSynchronize(c->dec_stage_ev[slot]));  // its last upload has left the buffer
+  else HIP_TRY(hipEventCreateWithFlags(&c->dec_stage_ev[slot], hipEventDisableTiming));
+  if ((rc = stage.ensure(ne * 16u)) != CLDN_HIP_OK) return rc;
+  uint64_t* h_bo = (uint64_t*)stage.p;
+  uint64_t* h_oo = h_bo + ne;
+  for (size_t k = 0; k < ne; ++k) {
+    h_bo[k] = frame_offsets[k] - b0;
+    h_oo[k] = out_offsets[k] - o0;
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_lzd_tables.p, stage.p, ne * 16u, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->dec_stage_ev[slot], c->stream));
+  const uint8_t* d_frames = (const uint8_t*)frames + b0;
+  if (frames_loc == CLDN_HIP_HOST) {
+    if ((rc = c->d_in.ensure((size_t)std::max<uint64_t>(1, b_bytes))) != CLDN_HIP_OK) return rc;
+    if (b_bytes) HIP_TRY(hipMemcpyAsync(c->d_in.p, (const uint8_t*)frames + b0, (size_t)b_bytes, hipMemcpyHostToDevice, c->stream));
+    d_frames = (const uint8_t*)c->d_in.p;
+  }
+  uint8_t* d_outp = (uint8_t*)out + o0;
+  uint32_t* d_sizes = sizes;
+  if (out_loc == CLDN_HIP_HOST) {
+    c->pending_total = 0;  // the device output buffer is reused: a deferred encode output waiting in it is gone
+    if ((rc = c->d_out.ensure((size_t)std::max<uint64_t>(1, o_bytes))) != CLDN_HIP_OK) return rc;
+    d_outp = (uint8_t*)c->d_out.p;
+    // bytes of a span behind the decoded ones keep the caller's content: bring it along
+    if (o_bytes) HIP_TRY(hipMemcpyAsync(d_outp, (const uint8_t*)out + o0, (size_t)o_bytes, hipMemcpyHostToDevice, c->stream));
+    d_sizes = (uint32_t*)((uint8_t*)c->d_lzd_tables.p + ne * 16u);
+  }
+  const uint32_t max_recs = ZstdDecodeLaunch::records_for(n_frames, b_bytes, o_bytes);
+  if ((rc = c->d_zsd_ws.ensure(ZstdDecodeLaunch::workspace_bytes(max_recs, n_frames))) != CLDN_HIP_OK) return rc;
+  ZstdDecodeLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.carve(c->d_zsd_ws.p, max_recs, n_frames);
+  L.stream = c->stream;
+  L.frames = d_frames;
+  L.frame_offsets = (const uint64_t*)c->d_lzd_tables.p;
+  L.n_frames = n_frames;
+  L.out = d_outp;
+  L.out_offsets = (const uint64_t*)c->d_lzd_tables.p + ne;
+  L.sizes = d_sizes;
+  L.status = (uint32_t*)c->d_status.p;
+  if ((rc = zstd_launch_decode(L)) != CLDN_HIP_OK) return rc;
+  if (out_loc == CLDN_HIP_DEVICE) return CLDN_HIP_OK;
+  uint32_t st = 0;
+  HIP_TRY(hipMemcpyAsync(&st, c->d_status.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(sizes, d_sizes, (size_t)n_frames * 4u, hipMemcpyDeviceToHost, c->stream));
+  if (o_bytes) HIP_TRY(hipMemcpyAsync((uint8_t*)out + o0, d_outp, (size_t)o_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "ZSTD decompression failed (sizes[k] == 0xffffffff marks the frames)");
+  if (st & ST_ZSTD_HOST)
+    return fail(CLDN_HIP_ERR_UNSUPPORTED, "ZSTD frame carries sequences or options the device decoder does not take (sizes[k] == 0xfffffffe marks the frames)");
   return CLDN_HIP_OK;
 }
 
@@ -2351,8 +2465,9 @@ static int audit_streams_impl(cldn_hip_codec* c, const void* points, int points_
                               const double* limit, cldn_hip_audit_field_t* report, int report_loc) {
   if ((points_loc != CLDN_HIP_HOST && points_loc != CLDN_HIP_DEVICE) || (streams_loc != CLDN_HIP_HOST && streams_loc != CLDN_HIP_DEVICE))
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
-  if (stream_kind != CLDN_HIP_STAGE2_NONE && stream_kind != CLDN_HIP_STAGE2_LZ4)
-    return fail(CLDN_HIP_ERR_ARG, "audit_streams: stream_kind %d is neither framed stage-1 streams (0) nor LZ4 chunks (1)", stream_kind);
+  if (stream_kind != CLDN_HIP_STAGE2_NONE && stream_kind != CLDN_HIP_STAGE2_LZ4 && stream_kind != CLDN_HIP_STAGE2_ZSTD)
+    return fail(CLDN_HIP_ERR_ARG, "audit_streams: stream_kind %d is neither framed stage-1 streams (0) nor LZ4 chunks (1) nor ZSTD chunks (%d)", stream_kind,
+                (int)CLDN_HIP_STAGE2_ZSTD);
   int rc;
   if ((rc = report_check("audit", !c->plan.fields.empty(), n_clouds, report, report_loc)) != CLDN_HIP_OK) return rc;
   std::vector<AuditField> fields;
@@ -2388,7 +2503,7 @@ static int audit_streams_impl(cldn_hip_codec* c, const void* points, int points_
     d_streams = base + pts_b + dec_b;
   }
   if ((rc = decode_framed(c, d_streams, CLDN_HIP_DEVICE, rel.data(), cloud_points, n_clouds, nullptr, CLDN_HIP_HOST, d_dec, bytes,
-                          CLDN_HIP_DEVICE, stream_kind == CLDN_HIP_STAGE2_LZ4)) != CLDN_HIP_OK)
+                          CLDN_HIP_DEVICE, stream_kind)) != CLDN_HIP_OK)
     return rc;
   // the decode's verdict before the report is touched (also: the host buffers of this call have been read)
   uint32_t st = 0;

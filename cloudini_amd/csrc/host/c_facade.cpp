@@ -358,6 +358,12 @@ CLDN_EXPORT int cldn_amd_set_device_lz4_decode(int on) {
   Cloudini::amd_detail::setDeviceLz4Decode(on != 0);
   return Cloudini::amd_detail::deviceLz4Decode() ? 1 : 0;
 }
+CLDN_EXPORT int cldn_amd_device_zstd_decode(void) { return Cloudini::amd_detail::deviceZstdDecode() ? 1 : 0; }
+CLDN_EXPORT uint64_t cldn_amd_device_zstd_decode_count(void) { return Cloudini::amd_detail::deviceZstdDecodeCount(); }
+CLDN_EXPORT int cldn_amd_set_device_zstd_decode(int on) {
+  Cloudini::amd_detail::setDeviceZstdDecode(on != 0);
+  return Cloudini::amd_detail::deviceZstdDecode() ? 1 : 0;
+}
 
 CLDN_EXPORT uint32_t cldn_amd_stage2_threads(void) { return Cloudini::amd_detail::stage2Threads(); }
 CLDN_EXPORT uint32_t cldn_amd_set_stage2_threads(uint32_t n) {

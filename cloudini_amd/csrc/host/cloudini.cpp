@@ -25,6 +25,7 @@
 
 #include "cloudini_hip.h"
 #include "host_internal.hpp"
+#include "../zstd_decode_walk.h"
 #include "yaml_lite.hpp"
 
 // stage-2 libraries: only these entry points are used (prototypes instead of the vendor headers so that the build
@@ -960,6 +961,39 @@ void PointcloudDecoder::decodeInto(const EncodingInfo& info, ConstBufferView com
       if (rc != CLDN_HIP_OK) throw std::runtime_error(cldn_hip_last_error());
       return;
     }
+    if (info.compression_opt == CompressionOption::ZSTD && amd_detail::deviceZstdDecode() && points != 0 && !refs.empty()) {
+      // stage 2 undone on the device (amd_detail::setDeviceZstdDecode) where every frame is one the device decodes: the walk
+      // of zstd_decode_walk.h judges the headers of every chunk here, before anything is uploaded. A frame with sequences
+      // (libzstd's usual output), or anything else the device hands back, takes the host route below as it always did.
+      const uint64_t capacity = cldn_hip_stage1_bound(impl_->plan->plan, kPointsPerChunk) + 60u;
+      bool literal_only = true;
+      std::vector<cldn::ZdBlock> recs;
+      std::vector<uint8_t> weights;
+      cldn::ZdFse fse;
+      for (const ChunkRef& r : refs) {
+        uint32_t counted = 0, n = 0, total = 0;
+        (void)cldn::zd_walk(r.src, r.size, capacity, nullptr, 0, nullptr, &fse, &counted, &total);
+        recs.resize(std::max<size_t>(recs.size(), counted + 1u));
+        weights.resize(recs.size() * 256u);
+        if (cldn::zd_walk(r.src, r.size, capacity, recs.data(), counted, weights.data(), &fse, &n, &total) != cldn::kZdOk) {
+          literal_only = false;
+          break;
+        }
+      }
+      if (literal_only) {
+        const uint64_t offsets[2] = {0, compressed_data.size()};
+        cldn_hip_codec_set_decode_fill(impl_->codec, output_is_zero ? CLDN_HIP_FILL_ZERO : CLDN_HIP_FILL_KEEP);
+        const int rc = cldn_hip_decode_zstd(impl_->codec, compressed_data.data(), CLDN_HIP_HOST, offsets, &points, 1, output.data(),
+                                            out_bytes, CLDN_HIP_HOST);
+        cldn_hip_codec_set_decode_fill(impl_->codec, CLDN_HIP_FILL_KEEP);
+        if (rc == CLDN_HIP_OK) {
+          amd_detail::countDeviceZstdDecode();
+          return;
+        }
+        // (a finding inside a stream, or a stage-1 error: the host route gives the verdict and the error text it always gave;
+        // a failed call has copied no point into `output`)
+      }
+    }
     if (!direct && !refs.empty()) {
       // undo stage 2: every chunk into its own worst-case slot (concurrently when use_threads), then packed into the
       // framed stage-1 stream the device decoder takes
@@ -1042,6 +1076,20 @@ std::atomic<bool> g_device_lz4_decode{false};
 }
 bool deviceLz4Decode() { return g_device_lz4_decode.load(); }
 void setDeviceLz4Decode(bool on) { g_device_lz4_decode.store(on); }
+
+// ZSTD messages whose frames carry no sequences decoded by cldn_hip_decode_zstd. Off unless a caller turns it on: there is no
+// environment switch
+namespace {
+std::atomic<bool> g_device_zstd_decode{false};
+}
+bool deviceZstdDecode() { return g_device_zstd_decode.load(); }
+void setDeviceZstdDecode(bool on) { g_device_zstd_decode.store(on); }
+// messages whose stage 2 the device has undone through that switch (the others fell back to the host route silently)
+namespace {
+std::atomic<uint64_t> g_device_zstd_decoded{0};
+}
+void countDeviceZstdDecode() { g_device_zstd_decoded.fetch_add(1); }
+uint64_t deviceZstdDecodeCount() { return g_device_zstd_decoded.load(); }
 
 // the encode call the codec has just made, audited where its points and streams lie (include/cloudini_hip.h)
 static int auditLastEncode(cldn_hip_codec_t* codec, const EncodingInfo& info, uint32_t n_clouds, AuditRequest* audit) {

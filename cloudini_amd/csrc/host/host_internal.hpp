@@ -99,6 +99,11 @@ bool deviceZstd();               // PointcloudEncoder::encode with CompressionOp
 void setDeviceZstd(bool on);     // (default off; valid ZSTD frames, not libzstd's bytes)
 bool deviceLz4Decode();
 void setDeviceLz4Decode(bool on);
+// ZSTD messages of frames without sequences through cldn_hip_decode_zstd (PointcloudDecoder::decode); default off
+bool deviceZstdDecode();
+void setDeviceZstdDecode(bool on);
+void countDeviceZstdDecode();
+uint64_t deviceZstdDecodeCount();  // messages decoded through cldn_hip_decode_zstd since the library was loaded
 
 uint32_t decompressChunkTo(Cloudini::CompressionOption opt, const uint8_t* src, size_t size, uint8_t* dst, size_t dst_cap);
 // worst-case stage-1 bytes of one 32768-point chunk of this schema (without its [u32 size])

@@ -98,7 +98,8 @@ DecodeFacts decode_facts(const DecodeLaunch& L) {
   F.dv_hint = L.dv_hint;
   F.uses_v5 = L.uses_v5 != 0u;
   F.wide = L.wide != nullptr;
-  F.lz4 = L.lz4_slots != nullptr;
+  F.lz4 = L.lz4_slots != nullptr && L.zstd == nullptr;
+  F.zstd = L.zstd != nullptr;
   F.sizes_known = L.chunk_sizes != nullptr;
   F.fill_zero = L.fill_zero != 0u;
   F.out_aligned16 = ((uintptr_t)L.out & 15u) == 0u;
@@ -186,6 +187,11 @@ int stage1_launch_decode(const DecodeLaunch& L0) {
                L.cloud_first_point, L.cloud_first_chunk, L.n_clouds, L.chunks, L.status, T);
   if (R.lz4) {  // the table so far describes the LZ4 blocks: undo stage 2, chunk by chunk, into the slots
     const int rc = lz4_launch_decode_chunks(L.stream, L.streams, L.chunks, L.n_chunks, L.lz4_slots, L.lz4_slot_stride, L.lz4_capacity, L.status);
+    if (rc != CLDN_HIP_OK) return rc;
+    L.streams = L.lz4_slots;
+  }
+  if (R.zstd) {  // the same for ZSTD frames: the walk judges and numbers their blocks, the block decoder fills the slots
+    const int rc = zstd_launch_decode(*L.zstd);
     if (rc != CLDN_HIP_OK) return rc;
     L.streams = L.lz4_slots;
   }

@@ -60,6 +60,7 @@ struct DecodeFacts {
   bool out_aligned16;
   uint8_t cols;           // bit a: cols[a]
   bool dsec, sec_cols, reg_end_pre, slices_done, slice_rec, token_ends, wp_split;
+  bool zstd;              // cldn_hip_decode_zstd: the chunks are ZSTD frames
 };
 
 enum DecRegular : uint8_t {  // the kernel that decodes the regular streams
@@ -103,6 +104,7 @@ struct DecodeRoute {
   bool fast;             //   its `fast` argument: reg_end[] says what is left
   bool fast_sections;    //   sec_done[] says which sections are left
   uint32_t fixed_bytes;  // DR_FIXED: bytes of a point
+  bool zstd;             // k_zstd_walk, k_zstd_decode_blocks behind the table
 };
 
 inline DecodeRoute decode_route(const DevPlan& P, const DecodeFacts& F) {
@@ -111,6 +113,7 @@ inline DecodeRoute decode_route(const DevPlan& P, const DecodeFacts& F) {
   R.split_parts = 1u;
   R.build_chunks = F.sizes_known;
   R.lz4 = F.lz4 && F.n_chunks != 0u;
+  R.zstd = F.zstd && F.n_chunks != 0u;
   if (F.n_chunks == 0u) return R;
   if (F.wide) {  // schemas beyond the launch-argument plan: the serial decoder with the plan in device memory
     R.regular = DR_WIDE;
@@ -225,6 +228,7 @@ inline void decode_route_kernels(const DecodeRoute& R, std::vector<const char*>&
   auto section_columns = [&] { k.insert(k.end(), {"k_locate_sections", "k_section_offsets", "k_sections_w", "k_sections_done"}); };
   k.push_back(R.build_chunks ? "k_build_chunks" : "k_walk_chunks");
   if (R.lz4) k.push_back("k_lz4_decode_chunks");
+  if (R.zstd) k.insert(k.end(), {"k_zstd_walk", "k_zstd_decode_blocks"});
   if (R.regular == DR_NONE) return;
   if (R.columns == DC_MANY || R.regular == DR_STREAM_COLS) section_columns();
   if (R.columns == DC_COLS) {

@@ -135,7 +135,9 @@ enum : uint32_t {
   ST_CORRUPT = 2u,         // decode: malformed input
   ST_PALETTE_FULL = 4u,    // internal: LDS palette table overflowed (handled by the global-table path)
   ST_FINISH_TIMEOUT = 8u,  // internal: a workgroup of k_finish waited too long for a predecessor's chunk size
-  ST_LZ4_REJECT = 16u      // set next to ST_CORRUPT: what was malformed is an LZ4 block (lz4_decode.hip)
+  ST_LZ4_REJECT = 16u,     // set next to ST_CORRUPT: what was malformed is an LZ4 block (lz4_decode.hip)
+  ST_ZSTD_REJECT = 32u,    // set next to ST_CORRUPT: what was malformed is a ZSTD frame (zstd_decode.hip)
+  ST_ZSTD_HOST = 64u       // a ZSTD frame carries sequences or options the device decoder does not take
 };
 
 // ---- piece kernel (stage1_fused.h) ----

@@ -10,6 +10,7 @@
 #include "stage1_device.h"
 #include "stage1_encode_route.h"
 #include "stage1_report.h"
+#include "zstd_decode_walk.h"
 
 namespace cldn {
 
@@ -111,6 +112,9 @@ struct DecodeLaunch {
   uint8_t* lz4_slots;                 // device [n_chunks * lz4_slot_stride]
   uint64_t lz4_slot_stride;           // multiple of 16, >= lz4_capacity
   uint32_t lz4_capacity;              // what a block may decode to (what the host path gives LZ4_decompress_safe)
+  // cldn_hip_decode_zstd: the same slots (lz4_slots, lz4_slot_stride, lz4_capacity) filled from [u32 size][ZSTD frame] chunks
+  // by zstd_launch_decode (zstd_decode.hip) with this workspace; NULL = not a ZSTD call
+  const struct ZstdDecodeLaunch* zstd;
 };
 // bytes of the SPLIT workspace: per piece t0 (4) + aggregates (5 x 4) + carries (4 x 4), per chunk 4 flag words
 inline size_t wp_split_bytes(uint32_t n_chunks, uint32_t maxp) { return (size_t)n_chunks * maxp * 40u + (size_t)n_chunks * 16u + 256u; }
@@ -309,6 +313,56 @@ int lz4_launch_decompress(const Lz4DecompressLaunch& L);
 // points at the slot (src_off = c * slot_stride, src_size = decoded bytes), a refused block clears `valid` and raises ST_CORRUPT
 int lz4_launch_decode_chunks(hipStream_t stream, const uint8_t* streams, DecChunk* chunks, uint32_t n_chunks, uint8_t* slots,
                              uint64_t slot_stride, uint32_t capacity, uint32_t* status);
+
+// ---- ZSTD frames without sequences back into bytes on the device (zstd_decode.hip, zstd_decode_walk.h) ----
+struct ZstdDecodeLaunch {
+  hipStream_t stream;
+  const uint8_t* frames;          // device
+  uint32_t n_frames;
+  uint8_t* out;                   // device
+  uint32_t* sizes;                // device [n_frames], 4-byte aligned: decoded bytes, kZdSizeCorrupt or kZdSizeHost
+  uint32_t* status;               // ST_CORRUPT | ST_ZSTD_REJECT when a frame is refused, ST_ZSTD_HOST when one needs the host
+  // either: frame k = [frame_offsets[k], frame_offsets[k + 1]) of `frames`, it may write [out_offsets[k], out_offsets[k + 1]) of `out`
+  const uint64_t* frame_offsets;  // device [n_frames + 1]
+  const uint64_t* out_offsets;    // device [n_frames + 1]
+  // or (chunks != NULL) the chunks of a decode call: chunk c (valid == 1, src_off / src_size = its frame in `frames`) -> slot c of
+  // `out`; on success the entry points at the slot, any other verdict clears `valid`
+  DecChunk* chunks;
+  uint64_t slot_stride;
+  uint32_t capacity;
+  // the workspace (carve); recs and weights start at multiples of 256 bytes
+  uint32_t max_recs;              // block records of the batch (records_for)
+  ZdBlock* recs;                  // [max_recs]
+  uint8_t* weights;               // [max_recs * 256]: the weights of record i's tree description
+  ZdFse* fse;                     // [1024]: scratch of the walk's lanes
+  uint64_t* frame_src;            // [n_frames]: where a frame starts in `frames`
+  uint64_t* frame_dst;            // [n_frames]: where its content starts in `out`
+  uint32_t* n_recs;               // records in use
+  // the sum of zd_record_limit over the frames is at most this (out_bytes: the sum of the frames' capacities)
+  static uint32_t records_for(uint32_t n_frames, uint64_t src_bytes, uint64_t out_bytes) {
+    const uint64_t n = 2u * (uint64_t)n_frames + src_bytes / 256u + out_bytes / kZdBlockMax;
+    return n > 0x7fffff00ull ? 0x7fffff00u : (uint32_t)n;
+  }
+  static size_t workspace_bytes(uint32_t max_recs, uint32_t n_frames) {
+    return (((size_t)max_recs * sizeof(ZdBlock) + 255u) & ~size_t(255)) + (size_t)max_recs * 256u + 1024u * sizeof(ZdFse) +
+           (size_t)n_frames * 16u + 256u;
+  }
+  void carve(void* ws, uint32_t max_recs_, uint32_t n_frames_) {
+    uint8_t* p = (uint8_t*)ws;
+    max_recs = max_recs_;
+    recs = (ZdBlock*)p;
+    p += ((size_t)max_recs * sizeof(ZdBlock) + 255u) & ~size_t(255);
+    weights = p;
+    p += (size_t)max_recs * 256u;
+    fse = (ZdFse*)p;
+    p += 1024u * sizeof(ZdFse);
+    frame_src = (uint64_t*)p;
+    frame_dst = frame_src + n_frames_;
+    n_recs = (uint32_t*)(frame_dst + n_frames_);
+  }
+};
+static_assert(sizeof(ZdFse) % 8 == 0 && sizeof(ZdBlock) == 48, "workspace layout");
+int zstd_launch_decode(const ZstdDecodeLaunch& L);  // the walk + the block decoder
 
 // applyVizLossyPreprocessing for a ragged batch of clouds (viz_kernels.hip)
 constexpr uint32_t kVizBlockPoints = 1024;  // points per workgroup; blocks are cut per cloud, a cloud's last one may be partial

@@ -154,6 +154,10 @@ def lib() -> C.CDLL:
     L.cldn_hip_lz4_decompress.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int, u64p, vp]
     L.cldn_hip_decode_lz4.restype = C.c_int
     L.cldn_hip_decode_lz4.argtypes = [vp, vp, C.c_int, u64p, u64p, C.c_uint32, vp, C.c_uint64, C.c_int]
+    L.cldn_hip_zstd_decompress.restype = C.c_int
+    L.cldn_hip_zstd_decompress.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int, u64p, vp]
+    L.cldn_hip_decode_zstd.restype = C.c_int
+    L.cldn_hip_decode_zstd.argtypes = [vp, vp, C.c_int, u64p, u64p, C.c_uint32, vp, C.c_uint64, C.c_int]
     L.cldn_hip_audit_clouds.restype = C.c_int
     L.cldn_hip_audit_clouds.argtypes = [vp, vp, C.c_int, vp, C.c_int, u64p, C.c_uint32, vp, vp, C.c_int]
     L.cldn_hip_audit_streams.restype = C.c_int
@@ -630,6 +634,70 @@ class Codec:
         so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
         cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
         _check(lib().cldn_hip_decode_lz4(
+            self._h, C.c_void_p(streams_ptr), DEVICE, so.ctypes.data_as(C.POINTER(C.c_uint64)),
+            cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, C.c_void_p(out_ptr), int(out_capacity), DEVICE))
+
+    # ---- ZSTD frames without sequences back into bytes (cldn_hip_zstd_decompress / cldn_hip_decode_zstd) ----------
+    def zstd_decompress_host(self, frames: Sequence[bytes], capacities: Sequence[int], out: Optional[np.ndarray] = None):
+        """A batch of ZSTD frames from host memory; frame k may decode to capacities[k] bytes. Returns (out, sizes): the spans
+        back to back in `out` (span k starts at sum(capacities[:k])), sizes[k] = decoded bytes, 0xffffffff for a refused
+        frame, 0xfffffffe for one that needs the host (sequences, checksum, ...). Raises CloudiniHipError (CORRUPT, else
+        UNSUPPORTED) for those unless `out` is given -- then the error is returned as a third element so that the caller
+        can look at the other frames."""
+        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in frames]
+        bo = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        bo[1:] = np.cumsum([a.size for a in arrs])
+        oo = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        oo[1:] = np.cumsum([int(c) for c in capacities])
+        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        keep = out is not None
+        if out is None:
+            out = np.zeros(max(1, int(oo[-1])), dtype=np.uint8)
+        sizes = np.zeros(max(1, len(arrs)), dtype=np.uint32)
+        rc = lib().cldn_hip_zstd_decompress(self._h, data.ctypes.data_as(C.c_void_p), HOST, bo.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           len(arrs), out.ctypes.data_as(C.c_void_p), HOST,
+                                           oo.ctypes.data_as(C.POINTER(C.c_uint64)), sizes.ctypes.data_as(C.c_void_p))
+        if keep:
+            return out, sizes[: len(arrs)], rc
+        _check(rc)
+        return out, sizes[: len(arrs)]
+
+    def zstd_decompress_device(self, frames_ptr: int, frame_offsets: np.ndarray, out_ptr: int, out_offsets: np.ndarray,
+                              sizes_ptr: int):
+        """The same on device buffers (asynchronous; the verdicts show in sizes and in status())."""
+        bo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uint64)
+        _check(lib().cldn_hip_zstd_decompress(self._h, C.c_void_p(frames_ptr), DEVICE, bo.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             bo.size - 1, C.c_void_p(out_ptr), DEVICE, oo.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             C.c_void_p(sizes_ptr)))
+
+    def decode_zstd_host(self, streams: Sequence[np.ndarray], cloud_points: Sequence[int],
+                        out: Optional[np.ndarray] = None) -> List[np.ndarray]:
+        """decode_host for streams whose chunks are [u32 frame size][ZSTD frame] (the body of a ZSTD message); UNSUPPORTED
+        when a frame carries sequences or options the device decoder does not take."""
+        step = self.plan.point_step
+        arrs = [np.ascontiguousarray(s).view(np.uint8).reshape(-1) for s in streams]
+        offs = np.zeros(len(arrs) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([a.size for a in arrs])
+        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        npts = np.array(list(cloud_points), dtype=np.uint64)
+        total = int(npts.sum()) * step
+        if out is None:
+            out = np.zeros(max(1, total), dtype=np.uint8)
+        _check(lib().cldn_hip_decode_zstd(
+            self._h, data.ctypes.data_as(C.c_void_p), HOST, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+            npts.ctypes.data_as(C.POINTER(C.c_uint64)), len(arrs), out.ctypes.data_as(C.c_void_p), total, HOST))
+        res, pos = [], 0
+        for n in npts:
+            res.append(out[pos:pos + int(n) * step])
+            pos += int(n) * step
+        return res
+
+    def decode_zstd_device(self, streams_ptr: int, stream_offsets: np.ndarray, cloud_points: np.ndarray, out_ptr: int,
+                          out_capacity: int):
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
+        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
+        _check(lib().cldn_hip_decode_zstd(
             self._h, C.c_void_p(streams_ptr), DEVICE, so.ctypes.data_as(C.POINTER(C.c_uint64)),
             cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, C.c_void_p(out_ptr), int(out_capacity), DEVICE))
 

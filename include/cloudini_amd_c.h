@@ -152,6 +152,20 @@ uint32_t cldn_amd_set_stage2_threads(uint32_t n);
  * messages and ZSTD keep the host route. Off by default, no environment variable. Both return the value in effect (0, 1). */
 int cldn_amd_device_lz4_decode(void);
 int cldn_amd_set_device_lz4_decode(int on);
+/* Stage 2 of ZSTD messages UNDONE on the GPU (include/cloudini_hip.h, cldn_hip_decode_zstd): PointcloudDecoder::decode of a
+ * message with compression_opt == ZSTD and wire version >= 3 walks the headers of every chunk's frame on the host; where all
+ * frames are without sequences (what CLDN_HIP_STAGE2_ZSTD writes; libzstd's own output only sometimes) the compressed body is
+ * uploaded as it is and decompressed on the device, otherwise -- and whenever the device hands a frame back -- the message
+ * takes the host route exactly as before. The batch transcoder's decompress direction stays on the host pool. Measured
+ * (DESIGN.md 4h): a single message is 6 to 20 times SLOWER this way (8.6 ms against 1.35 ms on 16 host threads for 1 M XYZI points):
+ * the device decoder pays for device-resident batches (cldn_hip_decode_zstd), the switch exists for callers whose messages must
+ * not touch the host pool. Off by default, no environment
+ * variable. Both return the value in effect (0, 1). */
+int cldn_amd_device_zstd_decode(void);
+int cldn_amd_set_device_zstd_decode(int on);
+/* messages that took the device route through that switch since the library was loaded (a message that falls back to the host
+ * route is not counted: the fall-back is silent by design, this is how a caller sees which route its messages take) */
+uint64_t cldn_amd_device_zstd_decode_count(void);
 /* Stage 2 of ZSTD streams on the GPU (include/cloudini_hip.h, CLDN_HIP_STAGE2_ZSTD): PointcloudEncoder::encode with
  * compression_opt == ZSTD then receives [u32 size][ZSTD frame] per chunk from the device. The frames are valid ZSTD frames of
  * literal-only blocks (Huffman-coded literals, no sequences) that the reference's decoder and this library's read; they are

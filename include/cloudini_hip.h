@@ -284,6 +284,44 @@ int cldn_hip_lz4_decompress(cldn_hip_codec_t* codec, const void* blocks, int blo
 int cldn_hip_decode_lz4(cldn_hip_codec_t* codec, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                         const uint64_t* cloud_points, uint32_t n_clouds, void* points_out, uint64_t out_capacity, int out_loc);
 
+/* ZSTD frames WITHOUT SEQUENCES back into bytes on the device (zstd_decode.hip): the read side of CLDN_HIP_STAGE2_ZSTD, and of
+ * any other writer's frames whose blocks are Raw, RLE, or Compressed with a literals section (Raw, RLE, Huffman-coded with one
+ * or four streams, direct or FSE-described weights, treeless) and the sequences byte 0x00. The rule set is
+ * tests/zstd_lit_rules.py's, with three verdicts per frame:
+ *   decoded    sizes[k] = the decoded bytes; ZSTD_decompress gives the same bytes
+ *   HOST       sizes[k] = 0xfffffffe: the frame may be valid but is outside what the device decodes -- a block with sequences, a
+ *              dictionary id, the content checksum, a skippable frame, more than one frame in the span, a Huffman table log
+ *              above 11, a window above 2^27, more blocks than 2 + frame bytes / 256 + capacity / 128 KiB, and the few places
+ *              where libzstd's own decoders disagree with each other (the bits in front of a stream's last symbol)
+ *   refused    sizes[k] = 0xffffffff: libzstd refuses the frame too -- bad magic, the reserved header bit, block type 3,
+ *              sizes that run past the span, a content size that differs from the regenerated total or a total beyond the
+ *              span's capacity, bytes behind the sequences byte, a treeless block without an earlier table, weights that do
+ *              not complete a power of two, a damaged FSE description, a stream that runs out or has no end marker
+ * A verdict found in the headers leaves the frame's output span untouched; one found inside a stream may have written inside
+ * the span. Nothing is ever written outside it, and the other frames of the batch are still decoded.
+ *
+ * cldn_hip_zstd_decompress mirrors cldn_hip_lz4_decompress argument for argument (frame_offsets, out_offsets: HOST
+ * [n_frames + 1]; sizes: [n_frames] where `out` lives, DEVICE: 4-byte aligned; the span's length is the capacity and takes part
+ * in the verdict). It returns CLDN_HIP_ERR_CORRUPT if any frame was refused, else CLDN_HIP_ERR_UNSUPPORTED if any needs the
+ * host, else CLDN_HIP_OK: at once for HOST outputs, through cldn_hip_codec_status() for DEVICE outputs.
+ *
+ * cldn_hip_decode_zstd: the contract of cldn_hip_decode_lz4 with [u32 LE frame size][ZSTD frame] per chunk: the body of a
+ * message with compression_opt == ZSTD, and exactly what the encode calls write under CLDN_HIP_STAGE2_ZSTD. The same slots
+ * with the capacity cldn_hip_stage1_bound(plan, 32768) + 60, the same chunk-table rewrite. A refused frame reports "ZSTD
+ * decompression failed" (CLDN_HIP_ERR_CORRUPT); a frame that needs the host reports CLDN_HIP_ERR_UNSUPPORTED, "ZSTD frame
+ * carries sequences or options the device decoder does not take": no point of that call is returned for HOST outputs, and
+ * DEVICE outputs are undefined (cldn_hip_codec_status() tells). libzstd's own level-1 output usually carries sequences: walk
+ * the frames first (zstd_decode_walk.h, as the host mirror does) or be ready to take the host route.
+ * Measured (MI355X, profiles/r16_a_zstd_decode_bench.txt, _trace.txt): 32 x 1 M XYZI clouds, frames in HBM: 10.1 ms per call, of
+ * which 9.75 ms ZSTD (21 GB/s of decoded payload; 64 x 130048 Velodyne clouds 8.4 ms, 8.4 GB/s); the host route needs 43.2 / 24.9 ms
+ * for the same clouds with 16 threads. A block offers 1 or 4 serial chains of up to 32 Ki symbols at ~0.22 us per symbol, so ONE
+ * message takes 8.6 ms (1 M XYZI) or 7.7 ms (Velodyne) against 1.35 / 0.39 ms on the host: the call pays for compressed data that
+ * is already on the device or comes in batches, never for a single host message. */
+int cldn_hip_zstd_decompress(cldn_hip_codec_t* codec, const void* frames, int frames_loc, const uint64_t* frame_offsets,
+                             uint32_t n_frames, void* out, int out_loc, const uint64_t* out_offsets, uint32_t* sizes);
+int cldn_hip_decode_zstd(cldn_hip_codec_t* codec, const void* streams, int streams_loc, const uint64_t* stream_offsets,
+                         const uint64_t* cloud_points, uint32_t n_clouds, void* points_out, uint64_t out_capacity, int out_loc);
+
 /* Wire version 2 (streams written before the chunked format; the reference still reads them, src/cloudini.cpp:665-667):
  * the whole stage-1 payload is ONE unframed run of points without [u32 size] prefixes and without state resets, decoded
  * until it is empty (DecodeV4Stage1Chunk with expected_points = 0, src/v4_codec.cpp:108-115). The output capacity bounds
@@ -372,7 +410,8 @@ typedef struct cldn_hip_audit_field {
  * enqueues work.
  *
  * cldn_hip_audit_streams: `points` against the decode of `streams`. stream_kind = CLDN_HIP_STAGE2_NONE: framed stage-1 streams
- * (the contract of cldn_hip_decode_stage1); CLDN_HIP_STAGE2_LZ4: [u32 size][LZ4 block] per chunk (cldn_hip_decode_lz4).
+ * (the contract of cldn_hip_decode_stage1); CLDN_HIP_STAGE2_LZ4: [u32 size][LZ4 block] per chunk (cldn_hip_decode_lz4);
+ * CLDN_HIP_STAGE2_ZSTD: [u32 size][ZSTD frame] per chunk (cldn_hip_decode_zstd, with its verdicts).
  * stream_offsets: HOST [n_clouds + 1]. The existing decoders write into the audit's workspace, which is filled with zeros
  * first (the decode fill setting has no part in the verdict); no decoded byte leaves the device. The call reads the decode's
  * 4-byte status word back and synchronises before it touches the report: a malformed stream returns what the decode call
