@@ -21,9 +21,9 @@
 //   * fused Palette: the size of the section (3 + U * bpv + ceil(bits * n / 8), v5_codec.cpp:298-306) is known as soon
 //     as the hash table holds the chunk's distinct values -- halfway through the section's work. The workgroup
 //     publishes then, and finishes the section (ranks, palette values, bit-packed indexes) straight into the final
-//     stream, no slot round trip. Even chunks finish their section first and copy their regular segments second, odd
-//     chunks the other way round, so that the LDS-latency-bound half of one workgroup overlaps the HBM-bound half of
-//     its neighbours on the same CU.
+//     stream, no slot round trip, and copies its regular segments after that. (Until the index pack requested its
+//     values in batches, odd chunks copied first, to overlap the pack's memory waits with the neighbours' copies: with
+//     the waits gone the two orders measure the same)
 #pragma once
 
 namespace cldn {
@@ -426,9 +426,7 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
   const uint32_t wid = leader_copies ? y * (T / 64) + wave : (y - 1u) * (T / 64) + wave;
   const uint32_t n_waves = (leader_copies ? A.splits : A.splits - 1u) * (T / 64);
   const bool copies = leader_copies || !leader;
-  // fused Palette: even chunks build the section first, odd chunks copy first
-  const bool section_first = !fuse || !leader || (c & 1u) == 0u;
-  if (!section_first && copies) fin_copy(L, slot, chunk_out, wid, n_waves, lane);
+  // fused Palette: the section first, then the copy
   if (FUSE_BPV != 0 && fuse && leader) {
     const P p(smem);
     uint8_t* sec = chunk_out + 4u + L.doff[s_a];
@@ -446,7 +444,7 @@ __global__ __launch_bounds__(T, (T == 1024 ? 4 : 8)) __attribute__((amdgpu_num_s
       sec[2] = (uint8_t)((U >> 8) & 0xffu);  // static_cast<uint16_t>(palette.size()), v5_codec.cpp:464
     }
   }
-  if (section_first && copies) fin_copy(L, slot, chunk_out, wid, n_waves, lane);
+  if (copies) fin_copy(L, slot, chunk_out, wid, n_waves, lane);
 }
 
 }  // namespace cldn

@@ -1567,7 +1567,7 @@ int launch_sections(const EncodeLaunch& L) {
 #define SEC_ARGS(FL) \
   *L.plan, FL, L.chunks, L.cols, L.modes, L.slots, R.slot_stride, R.reg_stride, L.segs, R.segs_per_chunk, R.subs, L.fallback_flags, R.append
   if (R.runs.n) TRY_LAUNCH("k_section_fast", k_section_fast, dim3(nch, R.runs.n), dim3(kS2Threads), kD32Lds, L.stream, SEC_ARGS(R.runs));
-  // 512-thread workgroups (two bitmap words and two groups of 32 values per thread): four of them fit a CU, so a batch of
+  // 512-thread workgroups (two bitmap words and eight groups of 8 values per thread): four of them fit a CU, so a batch of
   // up to 1024 chunks is one generation (C2: sections 0.066 ms with 1024 threads, 0.062 ms with 512)
   if (R.pal16.n)
     TRY_LAUNCH("k_section_palette", (k_section_palette32<uint16_t, 512>), dim3(nch, R.pal16.n), dim3(512), kPal16Lds, L.stream, SEC_ARGS(R.pal16),

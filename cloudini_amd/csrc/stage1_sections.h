@@ -482,7 +482,7 @@ __device__ __forceinline__ Grp8<RawT> grp8_load(const RawT* col, uint32_t i0) {
 //   pass 1  all values, 8 per thread and step; the home words of the 8 are read together and the CAS / probe /
 //           atomicMin path runs only for new keys or lower indexes
 //   ranks   bitmap over the chunk's indexes with one bit per first occurrence; rank = set bits below (one block scan)
-//   pass 3  thread t packs the ranks of values [32t, 32t+32) into `bits` dwords (appendBitpackedIndexes,
+//   pass 3  pass 1's walk once more: a thread packs the ranks of its 8 values into `bits` bytes (appendBitpackedIndexes,
 //           v5_codec.cpp:209-227)
 // ---------------------------------------------------------------------------------------------------------
 template <typename RawT>
@@ -549,72 +549,65 @@ struct Pal32 {
   }
 };
 
-// ranks of values [i0, i0 + cnt) (cnt <= 32) packed BITS bits each into BITS dwords at `out` (any byte alignment: the
-// stores are unaligned dword / dwordx4 stores, which gfx950 performs natively)
-template <typename RawT, uint32_t BITS, bool AHEAD = false>
-__device__ __forceinline__ void pal32_pack(const Pal32<RawT>& p, const RawT* col, uint32_t i0, uint32_t n, uint32_t cnt,
-                                           uint8_t* out) {
+// ranks of the values g[0..cnt) (one group of 8, cnt <= 8; cnt == 0: nothing is written) packed BITS bits each, LSB first,
+// into the ceil(cnt * BITS / 8) bytes at `out`. The index stream is ONE bit stream (appendBitpackedIndexes,
+// v5_codec.cpp:209-227), so a whole group is exactly BITS bytes and starts on a byte wherever it lies in the chunk; the
+// bytes behind it are the next group's (another lane's) or, behind the chunk's last group, the next chunk's size word: a
+// lane writes its own bytes and no more. `out` has any alignment (gfx950 performs unaligned stores natively).
+// Nothing but the stores depends on a branch over cnt -- a load whose only use sits behind one is moved there by hipcc and
+// waited for on its own. Values whose home word holds another key go through ONE probe site, picked off a bit mask (as
+// in pass 1); elements behind the chunk's end may hold a value the table does not have and are left out of the mask.
+template <typename RawT, uint32_t BITS>
+__device__ __forceinline__ void pal32_pack(const Pal32<RawT>& p, const Grp8<RawT>& g, uint32_t cnt, uint8_t* out) {
   using P = Pal32<RawT>;
-  uint32_t w[BITS];
+  constexpr uint32_t NW = (BITS + 3u) / 4u;  // dwords that hold BITS bytes: 1..3
+  typename P::Word tw[8];
 #pragma unroll
-  for (uint32_t k = 0; k < BITS; ++k) w[k] = 0u;
-  // AHEAD (the 1024-thread workgroups of small batches, 128 VGPRs): the four groups of 8 values are requested together,
-  // without a branch (round 6: a conditional load per group cost one memory latency each -- 4.5 us of a one-cloud call's
-  // k_finish); elements behind the chunk's end are read and ignored. The 512-thread workgroups of large batches have 64
-  // VGPRs and enough chunks in flight to hide the latency: one group at a time.
-  Grp8<RawT> grp[AHEAD ? 4 : 1];
-  if constexpr (AHEAD) {
+  for (int j = 0; j < 8; ++j) tw[j] = p.tab[P::home(g.get(j))];  // independent reads
+  uint32_t x[8], todo = 0u;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) grp[g] = grp8_load<RawT>(col, i0 + 8u * g < n ? i0 + 8u * g : i0);
+  for (int j = 0; j < 8; ++j) {
+    const bool hit = tw[j] != P::kFree && P::key_of(tw[j]) == g.get(j);
+    x[j] = (uint32_t)j < cnt ? P::low_of(tw[j]) : 0u;
+    todo |= ((uint32_t)j < cnt && !hit) ? (1u << j) : 0u;
   }
+  while (todo != 0u) {
+    const uint32_t j = (uint32_t)__builtin_ctz(todo);
+    todo &= todo - 1u;
+    const uint32_t v = g.get_dyn(j);
+    const uint32_t r = p.find_rank(v, p.tab[P::home(v)]);
 #pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    uint32_t v[8];
-    if constexpr (AHEAD) {
+    for (uint32_t k = 0; k < 8u; ++k) x[k] = j == k ? r : x[k];
+  }
+  uint32_t w[NW];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = grp[g].get(j);
+  for (uint32_t k = 0; k < NW; ++k) w[k] = 0u;
+#pragma unroll
+  for (uint32_t j = 0; j < 8u; ++j) {
+    const uint32_t bit = j * BITS;
+    w[bit >> 5] |= x[j] << (bit & 31u);
+    if ((bit & 31u) + BITS > 32u) w[(bit >> 5) + 1u] |= x[j] >> (32u - (bit & 31u));
+  }
+  if (cnt == 8u) {
+    // BITS bytes: whole dwords (one store of up to 12 bytes), then 2 bytes, then 1; 7 and 11 bytes end with a dword that
+    // writes the lane's own byte in front of the last three once more -- two stores instead of three
+    constexpr uint32_t ND = BITS / 4u;
+    if (ND != 0u) __builtin_memcpy(out, w, 4u * ND);
+    if (ND != 0u && (BITS & 3u) == 3u) {
+      const uint32_t e = (w[ND - 1u] >> 24) | (w[NW - 1u] << 8);
+      __builtin_memcpy(out + BITS - 4u, &e, 4);
     } else {
-      RawT rv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) rv[j] = (RawT)0;
-      if (i0 + 8u * g < n) load8<RawT>(col, i0 + 8u * g, n, rv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (uint32_t)rv[j];
-    }
-    typename P::Word tw[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) tw[j] = p.tab[P::home(v[j])];  // independent reads
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t e = (uint32_t)(8 * g + j);
-      uint32_t x = 0u;
-      if (e < cnt) {
-        const bool hit = tw[j] != P::kFree && P::key_of(tw[j]) == v[j];
-        x = hit ? P::low_of(tw[j]) : p.find_rank(v[j], tw[j]);
+      if (BITS & 2u) {
+        const uint16_t h = (uint16_t)w[NW - 1u];
+        __builtin_memcpy(out + 4u * ND, &h, 2);
       }
-      const uint32_t bit = e * BITS;
-      w[bit >> 5] |= x << (bit & 31u);
-      if ((bit & 31u) + BITS > 32u) w[(bit >> 5) + 1u] |= x >> (32u - (bit & 31u));
+      if (BITS & 1u) out[BITS - 1u] = (uint8_t)(w[NW - 1u] >> ((BITS & 2u) * 8u));
     }
-  }
-  // byte-exact: the chunk's last (short) group ends with the section's last byte -- in the final stream the next byte
-  // belongs to the following chunk
-  const uint32_t n_bytes = (cnt * BITS + 7u) >> 3;
-  const uint32_t n_dw = n_bytes >> 2;
-  if (n_dw == BITS && BITS % 4u == 0u) {
+  } else if (cnt != 0u) {  // the chunk's last group
+    const uint32_t n_bytes = (cnt * BITS + 7u) >> 3;
 #pragma unroll
-    for (uint32_t k = 0; k < BITS; k += 4u) {
-      const uint4 q = make_uint4(w[k], w[k + 1u], w[k + 2u], w[k + 3u]);
-      __builtin_memcpy(out + 4u * k, &q, 16);
-    }
-  } else {
-#pragma unroll
-    for (uint32_t k = 0; k < BITS; ++k) {
-      if (k < n_dw) __builtin_memcpy(out + 4u * k, &w[k], 4);
-      else if (k == n_dw) {
-        for (uint32_t b = 0; b < (n_bytes & 3u); ++b) out[4u * k + b] = (uint8_t)(w[k] >> (8u * b));
-      }
-    }
+    for (uint32_t k = 0; k < NW; ++k)
+      for (uint32_t b = 0; b < 4u && 4u * k + b < n_bytes; ++b) out[4u * k + b] = (uint8_t)(w[k] >> (8u * b));
   }
 }
 
@@ -755,34 +748,69 @@ __device__ __forceinline__ void pal32_values(const Pal32<RawT>& p, uint8_t* vals
   }
 }
 
-// pass 3: thread t packs the ranks of its groups of 32 values into `bits` dwords each (appendBitpackedIndexes,
-// v5_codec.cpp:209-227); idx_out = where the packed indexes begin (any alignment)
+// pass 3, pass 1's lane mapping: thread t of round q owns the 8 values from (q * T + t) * 8 on, so every load instruction
+// of a wave reads 1 KiB in one piece and every store instruction writes the wave's 64 * BITS consecutive bytes. The groups
+// of a batch are requested together before the first is touched (branch-free loads with clamped indexes -- the columns
+// end in 64 spare bytes -- : one memory latency per batch; 8 groups of 2-byte values at T = 512, 4 at T = 1024, 4 groups
+// of 4-byte values = 32 VGPRs, still packed).
+template <typename RawT, int T, uint32_t BITS>
+__device__ __forceinline__ void pal32_pack_rounds(const Pal32<RawT>& p, const RawT* col, uint32_t n, uint8_t* idx_out) {
+  constexpr uint32_t STEPS = 4096u / T;
+  constexpr uint32_t GB = sizeof(RawT) == 2 ? (STEPS < 8u ? STEPS : 8u) : 4u;
+  uint32_t tid = threadIdx.x;
+  // (pass 1 loads from the same addresses: seen as the same, they are kept from there to here and, in the section kernel
+  // with its 64-bit lane addresses, spilled and reloaded one in front of every load)
+  asm volatile("" : "+v"(tid));
+#pragma unroll
+  for (uint32_t b = 0; b < STEPS; b += GB) {
+    Grp8<RawT> g[GB];
+#pragma unroll
+    for (uint32_t k = 0; k < GB; ++k) {
+      const uint32_t i0 = ((b + k) * T + tid) * 8u;
+      g[k] = grp8_load<RawT>(col, i0 < n ? i0 : 0u);
+    }
+    // (without it the scheduler moves the first group's unpacking in front of the other groups' loads: they would be
+    // requested one memory latency late)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (uint32_t k = 0; k < GB; ++k) {
+      const uint32_t grp = (b + k) * T + tid;  // group of 8 values = BITS bytes of the index stream
+      const uint32_t i0 = grp * 8u;
+      pal32_pack<RawT, BITS>(p, g[k], i0 < n ? min(8u, n - i0) : 0u, idx_out + (size_t)grp * BITS);
+    }
+  }
+}
+
+// a pointer that is the same in every lane, moved to scalar registers: under the 64-VGPR budget of the 512-thread
+// kernels a lane copy of it is spilled and reloaded in front of the loads and stores that use it
+template <typename X>
+__device__ __forceinline__ X* uniform_ptr(X* q) {
+  const uintptr_t a = (uintptr_t)q;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
+  return (X*)(((uintptr_t)hi << 32) | lo);
+}
+
+// col, idx_out (where the packed indexes begin, any alignment) and `bits` are uniform in the workgroup
 template <typename RawT, int T>
 __device__ __forceinline__ void pal32_pack_chunk(const Pal32<RawT>& p, const RawT* col, uint32_t n, uint32_t bits,
                                                  uint8_t* idx_out) {
-  constexpr uint32_t WPT = kS2Threads / T;
-  const uint32_t tid = threadIdx.x;
-  for (uint32_t g = 0; g < WPT; ++g) {
-    const uint32_t grp = g * T + tid;  // group of 32 values
-    const uint32_t i0 = grp * 32u;
-    const uint32_t cnt = i0 < n ? min(32u, n - i0) : 0u;
-    if (bits != 0u && cnt != 0u) {
-      uint8_t* o = idx_out + (size_t)grp * bits * 4u;
-      switch (bits) {  // block-uniform
-        case 1: pal32_pack<RawT, 1, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 2: pal32_pack<RawT, 2, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 3: pal32_pack<RawT, 3, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 4: pal32_pack<RawT, 4, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 5: pal32_pack<RawT, 5, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 6: pal32_pack<RawT, 6, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 7: pal32_pack<RawT, 7, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 8: pal32_pack<RawT, 8, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 9: pal32_pack<RawT, 9, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 10: pal32_pack<RawT, 10, T == 1024>(p, col, i0, n, cnt, o); break;
-        case 11: pal32_pack<RawT, 11, T == 1024>(p, col, i0, n, cnt, o); break;
-        default: pal32_pack<RawT, 12, T == 1024>(p, col, i0, n, cnt, o); break;  // U <= kS2PalCapacity = 3072: <= 12 bits
-      }
-    }
+  col = uniform_ptr(col);
+  idx_out = uniform_ptr(idx_out);
+  switch (bits) {
+    case 0: break;  // one distinct value: no index bytes
+    case 1: pal32_pack_rounds<RawT, T, 1>(p, col, n, idx_out); break;
+    case 2: pal32_pack_rounds<RawT, T, 2>(p, col, n, idx_out); break;
+    case 3: pal32_pack_rounds<RawT, T, 3>(p, col, n, idx_out); break;
+    case 4: pal32_pack_rounds<RawT, T, 4>(p, col, n, idx_out); break;
+    case 5: pal32_pack_rounds<RawT, T, 5>(p, col, n, idx_out); break;
+    case 6: pal32_pack_rounds<RawT, T, 6>(p, col, n, idx_out); break;
+    case 7: pal32_pack_rounds<RawT, T, 7>(p, col, n, idx_out); break;
+    case 8: pal32_pack_rounds<RawT, T, 8>(p, col, n, idx_out); break;
+    case 9: pal32_pack_rounds<RawT, T, 9>(p, col, n, idx_out); break;
+    case 10: pal32_pack_rounds<RawT, T, 10>(p, col, n, idx_out); break;
+    case 11: pal32_pack_rounds<RawT, T, 11>(p, col, n, idx_out); break;
+    default: pal32_pack_rounds<RawT, T, 12>(p, col, n, idx_out); break;  // U <= kS2PalCapacity = 3072: <= 12 bits
   }
 }
 
