@@ -306,7 +306,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, 8)
                       fs_off[0] == 16u && ((uintptr_t)base & 15u) == 0u;
 
   // ---------------------------------------------------------------------------------------------------------
-  // pieces. v = payload offset + a0 (a0 = misalignment of the payload): piece p owns v in [p, p + 1) * 1008
+  // pieces. v = payload offset + a0 (a0 = misalignment of the payload): piece p owns v in [p, p + 1) * 992 (kWpPiece; with
+  // its halo unit it reads up to p * 992 + 1008)
   // ---------------------------------------------------------------------------------------------------------
   const uint32_t a0 = (uint32_t)((uintptr_t)src & 15u);
   const uint8_t* src_al = src - a0;
