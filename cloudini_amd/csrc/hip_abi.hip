@@ -202,6 +202,7 @@ struct cldn_hip_codec {
   DevBuf d_zsd_ws;  // ZSTD decode (zstd_decode.hip): block records, weights, frame tables
   DevBuf d_finrec;            // k_finish look-back records (rec, rec2), cleared only when (re)allocated
   int decode_fill = CLDN_HIP_FILL_KEEP;  // cldn_hip_codec_set_decode_fill
+  int zstd_sequences = 0;                // cldn_hip_codec_set_zstd_sequences
   DevBuf d_dec_bits;          // k_mark_token_ends: token-end bitmap of the streams of a decode call
   DevBuf d_dec_secs;          // k_section_offsets: per (field, chunk) section records + per-chunk counters
   DevBuf d_dec_rec;           // k_sections_cols_fast slice records, tagged with dec_epoch, cleared only when (re)allocated
@@ -743,6 +744,9 @@ __attribute__((visibility("default"))) int cldn_hip_debug_decode_split(cldn_hip_
   c->test_split_parts = parts;
   return CLDN_HIP_OK;
 }
+
+// Test hook: the bytes of k_zstd_seq_exec's LDS ring (zstd_seq_decode.hip), for the tests that place matches at its boundary
+__attribute__((visibility("default"))) uint32_t cldn_hip_debug_zstd_seq_ring(void) { return zstd_seq_ring_bytes(); }
 
 // Test hook, outside the boundary like the ones above: what the codec's last decode call decided, read from its workspace behind a
 // stream synchronise (tests/test_gpu_locate.py holds it against tests/locate_model.py). words: status words 8..15 (kStatFastRegular
@@ -1709,6 +1713,14 @@ int cldn_hip_codec_set_decode_fill(cldn_hip_codec_t* c, int fill) {
   return CLDN_HIP_OK;
 }
 
+int cldn_hip_codec_set_zstd_sequences(cldn_hip_codec_t* c, int on) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->zstd_sequences = on ? 1 : 0;
+  return CLDN_HIP_OK;
+}
+
+int cldn_hip_codec_zstd_sequences(const cldn_hip_codec_t* c) { return c && c->zstd_sequences ? 1 : 0; }
+
 int cldn_hip_codec_decode_stats(cldn_hip_codec_t* c, uint32_t stats[4]) {
   if (!c || !stats) return fail(CLDN_HIP_ERR_ARG, "decode_stats: NULL argument");
   memset(stats, 0, 4 * sizeof(uint32_t));
@@ -1995,11 +2007,12 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
     L.lz4_capacity = (uint32_t)capacity;
     if (zstd) {  // the frames' block records, sized from the bytes of the call
       if (stream_bytes - base_off > 0x7fffffffull * 64u) return fail(CLDN_HIP_ERR_UNSUPPORTED, "decode_zstd: streams of more than 128 GiB");
-      const uint32_t max_recs = ZstdDecodeLaunch::records_for(n_chunks, stream_bytes - base_off, decoder_stream_bytes);
+      const uint32_t max_recs = ZstdDecodeLaunch::records_for(n_chunks, stream_bytes - base_off, decoder_stream_bytes, c->zstd_sequences != 0);
       // [workspace | sizes u32 per chunk]
-      const size_t ws = (ZstdDecodeLaunch::workspace_bytes(max_recs, n_chunks) + 255u) & ~size_t(255);
+      const bool seq_on = c->zstd_sequences != 0;  // (frames with sequences: their scratch mirrors the slots)
+      const size_t ws = (ZstdDecodeLaunch::workspace_bytes(max_recs, n_chunks, seq_on, decoder_stream_bytes) + 255u) & ~size_t(255);
       if ((rc = c->d_zsd_ws.ensure(ws + (size_t)n_chunks * 4u)) != CLDN_HIP_OK) return rc;
-      Z.carve(c->d_zsd_ws.p, max_recs, n_chunks);
+      Z.carve(c->d_zsd_ws.p, max_recs, n_chunks, seq_on, decoder_stream_bytes);
       Z.stream = c->stream;
       Z.frames = d_streams;
       Z.n_frames = n_chunks;
@@ -2207,11 +2220,12 @@ int cldn_hip_zstd_decompress(cldn_hip_codec_t* c, const void* frames, int frames
     if (o_bytes) HIP_TRY(hipMemcpyAsync(d_outp, (const uint8_t*)out + o0, (size_t)o_bytes, hipMemcpyHostToDevice, c->stream));
     d_sizes = (uint32_t*)((uint8_t*)c->d_lzd_tables.p + ne * 16u);
   }
-  const uint32_t max_recs = ZstdDecodeLaunch::records_for(n_frames, b_bytes, o_bytes);
-  if ((rc = c->d_zsd_ws.ensure(ZstdDecodeLaunch::workspace_bytes(max_recs, n_frames))) != CLDN_HIP_OK) return rc;
+  const uint32_t max_recs = ZstdDecodeLaunch::records_for(n_frames, b_bytes, o_bytes, c->zstd_sequences != 0);
+  const bool seq_on = c->zstd_sequences != 0;  // (frames with sequences: their scratch mirrors the output spans)
+  if ((rc = c->d_zsd_ws.ensure(ZstdDecodeLaunch::workspace_bytes(max_recs, n_frames, seq_on, o_bytes))) != CLDN_HIP_OK) return rc;
   ZstdDecodeLaunch L;
   memset(&L, 0, sizeof(L));
-  L.carve(c->d_zsd_ws.p, max_recs, n_frames);
+  L.carve(c->d_zsd_ws.p, max_recs, n_frames, seq_on, o_bytes);
   L.stream = c->stream;
   L.frames = d_frames;
   L.frame_offsets = (const uint64_t*)c->d_lzd_tables.p;

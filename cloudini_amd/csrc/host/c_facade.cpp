@@ -365,6 +365,12 @@ CLDN_EXPORT int cldn_amd_set_device_zstd_decode(int on) {
   return Cloudini::amd_detail::deviceZstdDecode() ? 1 : 0;
 }
 
+CLDN_EXPORT int cldn_amd_device_zstd_sequences(void) { return Cloudini::amd_detail::deviceZstdSequences() ? 1 : 0; }
+CLDN_EXPORT int cldn_amd_set_device_zstd_sequences(int on) {
+  Cloudini::amd_detail::setDeviceZstdSequences(on != 0);
+  return Cloudini::amd_detail::deviceZstdSequences() ? 1 : 0;
+}
+
 CLDN_EXPORT uint32_t cldn_amd_stage2_threads(void) { return Cloudini::amd_detail::stage2Threads(); }
 CLDN_EXPORT uint32_t cldn_amd_set_stage2_threads(uint32_t n) {
   Cloudini::amd_detail::setStage2Threads(n);

@@ -965,17 +965,33 @@ void PointcloudDecoder::decodeInto(const EncodingInfo& info, ConstBufferView com
       // stage 2 undone on the device (amd_detail::setDeviceZstdDecode) where every frame is one the device decodes: the walk
       // of zstd_decode_walk.h judges the headers of every chunk here, before anything is uploaded. A frame with sequences
       // (libzstd's usual output), or anything else the device hands back, takes the host route below as it always did.
+      // With amd_detail::setDeviceZstdSequences the walk is zd_walk_seq and frames with sequences go up too.
       const uint64_t capacity = cldn_hip_stage1_bound(impl_->plan->plan, kPointsPerChunk) + 60u;
-      bool literal_only = true;
+      const bool sequences = amd_detail::deviceZstdSequences();
+      bool literal_only = true;  // (or, with `sequences`, frames the device takes with that switch)
       std::vector<cldn::ZdBlock> recs;
+      std::vector<cldn::ZdSeqBlock> srecs;
       std::vector<uint8_t> weights;
       cldn::ZdFse fse;
       for (const ChunkRef& r : refs) {
-        uint32_t counted = 0, n = 0, total = 0;
-        (void)cldn::zd_walk(r.src, r.size, capacity, nullptr, 0, nullptr, &fse, &counted, &total);
-        recs.resize(std::max<size_t>(recs.size(), counted + 1u));
-        weights.resize(recs.size() * 256u);
-        if (cldn::zd_walk(r.src, r.size, capacity, recs.data(), counted, weights.data(), &fse, &n, &total) != cldn::kZdOk) {
+        uint32_t counted = 0, n = 0, total = 0, verdict;
+        if (sequences) {
+          cldn::ZdSeqSums sums;
+          const uint32_t cv = cldn::zd_walk_seq(r.src, r.size, capacity, false, nullptr, nullptr, 0, nullptr, &fse, &counted, &total, &sums);
+          const bool all = sums.has_seq != 0u;
+          if (all) counted = sums.n_all + (cv != cldn::kZdOk ? 1u : 0u);
+          recs.resize(std::max<size_t>(recs.size(), counted + 1u));
+          srecs.resize(recs.size());
+          weights.resize(recs.size() * 256u);
+          verdict = cldn::zd_walk_seq(r.src, r.size, capacity, all, recs.data(), srecs.data(), counted, weights.data(), &fse, &n, &total, &sums);
+          if (counted > (all ? cldn::zd_record_limit_seq(r.size, capacity) : cldn::zd_record_limit(r.size, capacity))) verdict = cldn::kZdHost;
+        } else {
+          (void)cldn::zd_walk(r.src, r.size, capacity, nullptr, 0, nullptr, &fse, &counted, &total);
+          recs.resize(std::max<size_t>(recs.size(), counted + 1u));
+          weights.resize(recs.size() * 256u);
+          verdict = cldn::zd_walk(r.src, r.size, capacity, recs.data(), counted, weights.data(), &fse, &n, &total);
+        }
+        if (verdict != cldn::kZdOk) {
           literal_only = false;
           break;
         }
@@ -983,8 +999,10 @@ void PointcloudDecoder::decodeInto(const EncodingInfo& info, ConstBufferView com
       if (literal_only) {
         const uint64_t offsets[2] = {0, compressed_data.size()};
         cldn_hip_codec_set_decode_fill(impl_->codec, output_is_zero ? CLDN_HIP_FILL_ZERO : CLDN_HIP_FILL_KEEP);
+        cldn_hip_codec_set_zstd_sequences(impl_->codec, sequences ? 1 : 0);
         const int rc = cldn_hip_decode_zstd(impl_->codec, compressed_data.data(), CLDN_HIP_HOST, offsets, &points, 1, output.data(),
                                             out_bytes, CLDN_HIP_HOST);
+        cldn_hip_codec_set_zstd_sequences(impl_->codec, 0);
         cldn_hip_codec_set_decode_fill(impl_->codec, CLDN_HIP_FILL_KEEP);
         if (rc == CLDN_HIP_OK) {
           amd_detail::countDeviceZstdDecode();
@@ -1088,6 +1106,11 @@ void setDeviceZstdDecode(bool on) { g_device_zstd_decode.store(on); }
 namespace {
 std::atomic<uint64_t> g_device_zstd_decoded{0};
 }
+namespace {
+std::atomic<bool> g_device_zstd_sequences{false};
+}
+bool deviceZstdSequences() { return g_device_zstd_sequences.load(); }
+void setDeviceZstdSequences(bool on) { g_device_zstd_sequences.store(on); }
 void countDeviceZstdDecode() { g_device_zstd_decoded.fetch_add(1); }
 uint64_t deviceZstdDecodeCount() { return g_device_zstd_decoded.load(); }
 

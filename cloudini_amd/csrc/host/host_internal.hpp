@@ -104,6 +104,10 @@ bool deviceZstdDecode();
 void setDeviceZstdDecode(bool on);
 void countDeviceZstdDecode();
 uint64_t deviceZstdDecodeCount();  // messages decoded through cldn_hip_decode_zstd since the library was loaded
+// ... and libzstd's own messages too (frames with sequences, cldn_hip_codec_set_zstd_sequences); it has meaning only while
+// deviceZstdDecode() is on; default off
+bool deviceZstdSequences();
+void setDeviceZstdSequences(bool on);
 
 uint32_t decompressChunkTo(Cloudini::CompressionOption opt, const uint8_t* src, size_t size, uint8_t* dst, size_t dst_cap);
 // worst-case stage-1 bytes of one 32768-point chunk of this schema (without its [u32 size])

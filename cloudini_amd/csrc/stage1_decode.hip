@@ -100,6 +100,7 @@ DecodeFacts decode_facts(const DecodeLaunch& L) {
   F.wide = L.wide != nullptr;
   F.lz4 = L.lz4_slots != nullptr && L.zstd == nullptr;
   F.zstd = L.zstd != nullptr;
+  F.zstd_seq = L.zstd != nullptr && L.zstd->seq != 0u;
   F.sizes_known = L.chunk_sizes != nullptr;
   F.fill_zero = L.fill_zero != 0u;
   F.out_aligned16 = ((uintptr_t)L.out & 15u) == 0u;

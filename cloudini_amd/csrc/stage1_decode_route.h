@@ -61,6 +61,7 @@ struct DecodeFacts {
   uint8_t cols;           // bit a: cols[a]
   bool dsec, sec_cols, reg_end_pre, slices_done, slice_rec, token_ends, wp_split;
   bool zstd;              // cldn_hip_decode_zstd: the chunks are ZSTD frames
+  bool zstd_seq;          //   ... and the codec takes frames with sequences (cldn_hip_codec_set_zstd_sequences)
 };
 
 enum DecRegular : uint8_t {  // the kernel that decodes the regular streams
@@ -105,6 +106,7 @@ struct DecodeRoute {
   bool fast_sections;    //   sec_done[] says which sections are left
   uint32_t fixed_bytes;  // DR_FIXED: bytes of a point
   bool zstd;             // k_zstd_walk, k_zstd_decode_blocks behind the table
+  bool zstd_seq;         //   ... then k_zstd_seq_decode, k_zstd_seq_exec
 };
 
 inline DecodeRoute decode_route(const DevPlan& P, const DecodeFacts& F) {
@@ -114,6 +116,7 @@ inline DecodeRoute decode_route(const DevPlan& P, const DecodeFacts& F) {
   R.build_chunks = F.sizes_known;
   R.lz4 = F.lz4 && F.n_chunks != 0u;
   R.zstd = F.zstd && F.n_chunks != 0u;
+  R.zstd_seq = R.zstd && F.zstd_seq;
   if (F.n_chunks == 0u) return R;
   if (F.wide) {  // schemas beyond the launch-argument plan: the serial decoder with the plan in device memory
     R.regular = DR_WIDE;
@@ -229,6 +232,7 @@ inline void decode_route_kernels(const DecodeRoute& R, std::vector<const char*>&
   k.push_back(R.build_chunks ? "k_build_chunks" : "k_walk_chunks");
   if (R.lz4) k.push_back("k_lz4_decode_chunks");
   if (R.zstd) k.insert(k.end(), {"k_zstd_walk", "k_zstd_decode_blocks"});
+  if (R.zstd_seq) k.insert(k.end(), {"k_zstd_seq_decode", "k_zstd_seq_exec"});
   if (R.regular == DR_NONE) return;
   if (R.columns == DC_MANY || R.regular == DR_STREAM_COLS) section_columns();
   if (R.columns == DC_COLS) {

@@ -338,16 +338,32 @@ struct ZstdDecodeLaunch {
   uint64_t* frame_src;            // [n_frames]: where a frame starts in `frames`
   uint64_t* frame_dst;            // [n_frames]: where its content starts in `out`
   uint32_t* n_recs;               // records in use
+  // frames with sequences (cldn_hip_codec_set_zstd_sequences; zstd_seq_decode.hip). seq == 0: none of this exists, and a frame
+  // with sequences is HOST. The scratch is sized from the bytes `out` may take (seq_out_bytes): a frame's literals lie at its
+  // content's offset in `lit`, its sequences from slot (offset + 2) / 3 of `seqbuf`
+  uint32_t seq;
+  ZdSeqBlock* srecs;              // [max_recs]: next to recs
+  ZdSeqSums* frame_sums;          // [n_frames]
+  uint32_t* frame_first;          // [n_frames]: the frame's first record
+  uint32_t* frame_nrec;           // [n_frames]: its records if it is one the execution takes, else 0
+  uint64_t* seqbuf;               // [seq_out_bytes / 3 + 1]: ll | (ml - 3) << 17 | offset value << 34
+  uint8_t* lit;                   // [seq_out_bytes]
   // the sum of zd_record_limit over the frames is at most this (out_bytes: the sum of the frames' capacities)
-  static uint32_t records_for(uint32_t n_frames, uint64_t src_bytes, uint64_t out_bytes) {
-    const uint64_t n = 2u * (uint64_t)n_frames + src_bytes / 256u + out_bytes / kZdBlockMax;
+  // (seq: of zd_record_limit_seq)
+  static uint32_t records_for(uint32_t n_frames, uint64_t src_bytes, uint64_t out_bytes, bool seq = false) {
+    const uint64_t n = (seq ? 4u : 2u) * (uint64_t)n_frames + src_bytes / (seq ? 16u : 256u) + out_bytes / kZdBlockMax;
     return n > 0x7fffff00ull ? 0x7fffff00u : (uint32_t)n;
   }
-  static size_t workspace_bytes(uint32_t max_recs, uint32_t n_frames) {
-    return (((size_t)max_recs * sizeof(ZdBlock) + 255u) & ~size_t(255)) + (size_t)max_recs * 256u + 1024u * sizeof(ZdFse) +
-           (size_t)n_frames * 16u + 256u;
+  static size_t seq_bytes(uint32_t max_recs, uint32_t n_frames, uint64_t seq_out_bytes) {
+    return (size_t)max_recs * sizeof(ZdSeqBlock) + (size_t)n_frames * (sizeof(ZdSeqSums) + 8u) + ((size_t)(seq_out_bytes / 3u) + 1u) * 8u +
+           (size_t)seq_out_bytes + 1024u;
   }
-  void carve(void* ws, uint32_t max_recs_, uint32_t n_frames_) {
+  // seq_on: the sequences switch; seq_out_bytes: the bytes of `out` the frames may write (0 is a size like any other)
+  static size_t workspace_bytes(uint32_t max_recs, uint32_t n_frames, bool seq_on = false, uint64_t seq_out_bytes = 0u) {
+    return (((size_t)max_recs * sizeof(ZdBlock) + 255u) & ~size_t(255)) + (size_t)max_recs * 256u + 1024u * sizeof(ZdFse) +
+           (size_t)n_frames * 16u + 256u + (seq_on ? seq_bytes(max_recs, n_frames, seq_out_bytes) : 0u);
+  }
+  void carve(void* ws, uint32_t max_recs_, uint32_t n_frames_, bool seq_on = false, uint64_t seq_out_bytes = 0u) {
     uint8_t* p = (uint8_t*)ws;
     max_recs = max_recs_;
     recs = (ZdBlock*)p;
@@ -359,10 +375,30 @@ struct ZstdDecodeLaunch {
     frame_src = (uint64_t*)p;
     frame_dst = frame_src + n_frames_;
     n_recs = (uint32_t*)(frame_dst + n_frames_);
+    seq = seq_on ? 1u : 0u;
+    if (!seq) return;
+    auto up = [](uint8_t* q) { return (uint8_t*)(((uintptr_t)q + 255u) & ~(uintptr_t)255u); };
+    p = up((uint8_t*)(n_recs + 1));
+    srecs = (ZdSeqBlock*)p;
+    p += (size_t)max_recs * sizeof(ZdSeqBlock);
+    frame_sums = (ZdSeqSums*)p;
+    p += (size_t)n_frames_ * sizeof(ZdSeqSums);
+    frame_first = (uint32_t*)p;
+    frame_nrec = frame_first + n_frames_;
+    p = up((uint8_t*)(frame_nrec + n_frames_));
+    seqbuf = (uint64_t*)p;
+    p += ((size_t)(seq_out_bytes / 3u) + 1u) * 8u;
+    lit = up(p);
   }
 };
-static_assert(sizeof(ZdFse) % 8 == 0 && sizeof(ZdBlock) == 48, "workspace layout");
-int zstd_launch_decode(const ZstdDecodeLaunch& L);  // the walk + the block decoder
+static_assert(sizeof(ZdFse) % 8 == 0 && sizeof(ZdBlock) == 48 && sizeof(ZdSeqBlock) == 48 && sizeof(ZdSeqSums) == 40, "workspace layout");
+int zstd_launch_decode(const ZstdDecodeLaunch& L);  // the walk + the block decoder (+ zstd_launch_seq with L.seq)
+int zstd_launch_seq(const ZstdDecodeLaunch& L);     // zstd_seq_decode.hip: the sequence decoder + the execution
+// Bytes of k_zstd_seq_exec's LDS ring (dynamic LDS of the launch): a match further back reads global memory. 32 KiB, not the
+// 64 KiB of lz4_decode.hip's: a workgroup is one wave, and with 64 KiB only two of them fit a CU's 160 KiB. Measured on 992
+// frames (32 x 1 M XYZI, profiles/r20_a_zstd_seq_trace.txt's call): the kernel took 8.1 ms with 64 KiB against 4.5 ms with 32.
+constexpr uint32_t kZdSeqRing = 32768u;
+uint32_t zstd_seq_ring_bytes();
 
 // applyVizLossyPreprocessing for a ragged batch of clouds (viz_kernels.hip)
 constexpr uint32_t kVizBlockPoints = 1024;  // points per workgroup; blocks are cut per cloud, a cloud's last one may be partial

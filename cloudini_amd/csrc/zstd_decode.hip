@@ -25,6 +25,10 @@
 // its last symbol, an empty stream, a last byte 0, a jump table beyond the literals: CORRUPT; the bits in front of the last
 // symbol are not its code's length: HOST -- is raised on the frame's verdict with atomicMax. A verdict of the walk leaves the
 // frame's output span untouched; one found in a stream may have written inside the span, never outside.
+//
+// With ZstdDecodeLaunch::seq (cldn_hip_codec_set_zstd_sequences) the walk is zd_walk_seq: a frame with a block that carries
+// sequences is not HOST, it gets a record for EVERY block, its literals (ZdBlock::pad == 1) go to the frame's literal buffer
+// instead of the output, and zstd_seq_decode.hip's two kernels behind these leave its size. Without it nothing here changes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -82,37 +86,61 @@ __global__ __launch_bounds__(1024) void k_zstd_walk(const ZstdDecodeLaunch L) {
     ZdSpan s;
     s.valid = false;
     uint32_t counted = 0u, total = 0u;
+    ZdSeqSums sums;
+    bool all = false;  // the frame has a block with sequences: every block gets a record (zd_walk_seq)
     if (f < L.n_frames) {
       s = zd_span(L, f);
-      if (s.valid) (void)zd_walk(s.src, s.n, s.capacity, nullptr, 0u, nullptr, fse, &counted, &total);
+      if (s.valid && !L.seq) (void)zd_walk(s.src, s.n, s.capacity, nullptr, 0u, nullptr, fse, &counted, &total);
+      if (s.valid && L.seq) {
+        const uint32_t cv = zd_walk_seq(s.src, s.n, s.capacity, false, nullptr, nullptr, 0u, nullptr, fse, &counted, &total, &sums);
+        all = sums.has_seq != 0u;
+        if (all) counted = sums.n_all + (cv != kZdOk ? 1u : 0u);
+      }
     }
-    const bool too_many = f < L.n_frames && s.valid && counted > zd_record_limit(s.n, s.capacity);
+    const bool too_many = f < L.n_frames && s.valid && counted > (all ? zd_record_limit_seq(s.n, s.capacity) : zd_record_limit(s.n, s.capacity));
     if (too_many) counted = 0u;
     const uint32_t first = block_running_scan(counted, wtot, carry);
+    // (a chunk whose framing is damaged has no frame to walk: it owns no record, and the execution must find that written)
+    if (f < L.n_frames && !s.valid && L.seq) L.frame_nrec[f] = 0u;
     if (f >= L.n_frames || !s.valid) continue;
     // the records [first, first + counted) are this frame's: what the full walk does not fill stays a record nobody decodes
     const bool room = !too_many && (uint64_t)first + counted <= L.max_recs;
     uint32_t verdict = kZdHost, n_recs = 0u;
-    if (room) verdict = zd_walk(s.src, s.n, s.capacity, L.recs + first, counted, L.weights + 256u * (uint64_t)first, fse, &n_recs, &total);
+    if (room && !L.seq) verdict = zd_walk(s.src, s.n, s.capacity, L.recs + first, counted, L.weights + 256u * (uint64_t)first, fse, &n_recs, &total);
+    if (room && L.seq)
+      verdict = zd_walk_seq(s.src, s.n, s.capacity, all, L.recs + first, L.srecs + first, counted, L.weights + 256u * (uint64_t)first, fse,
+                            &n_recs, &total, &sums);
+    const bool exec = L.seq && all && verdict == kZdOk;  // its size and its chunk table entry are k_zstd_seq_exec's to leave
     const uint32_t end = (uint64_t)first + counted <= L.max_recs ? first + counted : (first < L.max_recs ? L.max_recs : first);
     for (uint32_t i = first; i < end; ++i) {
       ZdBlock& r = L.recs[i];
       if (verdict != kZdOk || i >= first + n_recs) {
         r.kind = kZdSkip;
+        if (L.seq) L.srecs[i].nb = 0u;
       } else {
         r.frame = f;
         if (r.tree != kZdNoTree) r.tree += first;
+        if (L.seq && !exec) L.srecs[i].nb = 0u;
+        if (exec)
+          for (uint32_t k = 0u; k < 3u; ++k)
+            if (L.srecs[i].rep[k] != kZdNoRec) L.srecs[i].rep[k] += first;
       }
+    }
+    if (L.seq) {
+      sums.capacity = (uint32_t)s.capacity;
+      L.frame_sums[f] = sums;
+      L.frame_first[f] = first;
+      L.frame_nrec[f] = exec ? n_recs : 0u;
     }
     L.frame_src[f] = (uint64_t)(s.src - L.frames);
     L.frame_dst[f] = s.dst_off;
-    const uint32_t size = verdict == kZdOk ? total : verdict == kZdHost ? kZdSizeHost : kZdSizeCorrupt;
+    const uint32_t size = exec ? 0u : verdict == kZdOk ? total : verdict == kZdHost ? kZdSizeHost : kZdSizeCorrupt;
     L.sizes[f] = size;
     if (verdict != kZdOk) atomicOr(L.status, verdict == kZdHost ? (uint32_t)ST_ZSTD_HOST : (uint32_t)(ST_CORRUPT | ST_ZSTD_REJECT));
     if (L.chunks) {
       if (verdict != kZdOk) {
         L.chunks[f].valid = 0u;
-      } else {
+      } else if (!exec) {
         L.chunks[f].src_off = s.dst_off;
         L.chunks[f].src_size = total;
       }
@@ -182,7 +210,7 @@ __global__ __launch_bounds__(64) void k_zstd_decode_blocks(const ZstdDecodeLaunc
     const ZdBlock r = blk[b];
     if (r.kind == kZdSkip) continue;
     const uint8_t* src = L.frames + L.frame_src[r.frame] + r.src;
-    uint8_t* dst = L.out + L.frame_dst[r.frame] + r.out;
+    uint8_t* dst = (r.pad ? L.lit : L.out) + L.frame_dst[r.frame] + r.out;  // (pad: literals of a frame with sequences)
     if (r.kind == kZdRaw) {
       copy_bytes_16(src, dst, r.regen, lane, 64u);
     } else if (r.kind == kZdRle) {
@@ -257,7 +285,7 @@ __global__ __launch_bounds__(64) void k_zstd_decode_blocks(const ZstdDecodeLaunc
     lg = tlog[b];
     const uint8_t* data = L.frames + L.frame_src[r.frame] + r.src + r.desc;
     const uint32_t len = r.size - r.desc;
-    dst = L.out + L.frame_dst[r.frame] + r.out;
+    dst = (r.pad ? L.lit : L.out) + L.frame_dst[r.frame] + r.out;
     if (r.streams == 1u) {
       s = data;
       m = len;
@@ -368,6 +396,7 @@ int zstd_launch_decode(const ZstdDecodeLaunch& L) {
   if (groups == 0u) return CLDN_HIP_OK;
   hipLaunchKernelGGL(k_zstd_decode_blocks, dim3(groups), dim3(64), 0, L.stream, L);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_zstd_decode_blocks");
+  if (L.seq) return zstd_launch_seq(L);
   return CLDN_HIP_OK;
 }
 

@@ -120,6 +120,10 @@ def lib() -> C.CDLL:
     L.cldn_hip_debug_viz_group_slots.argtypes = [vp, C.c_uint64]
     L.cldn_hip_codec_set_decode_fill.argtypes = [vp, C.c_int]
     L.cldn_hip_codec_set_decode_fill.restype = C.c_int
+    L.cldn_hip_codec_set_zstd_sequences.argtypes = [vp, C.c_int]
+    L.cldn_hip_codec_set_zstd_sequences.restype = C.c_int
+    L.cldn_hip_codec_zstd_sequences.argtypes = [vp]
+    L.cldn_hip_codec_zstd_sequences.restype = C.c_int
     L.cldn_hip_codec_decode_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cldn_hip_codec_decode_stats.restype = C.c_int
     L.cldn_hip_debug_decode_trace.restype = C.c_int
@@ -410,6 +414,14 @@ class Codec:
             kept.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(out_ptr), int(out_capacity), DEVICE,
             C.c_void_p(stream_offsets_ptr), C.c_void_p(chunk_sizes_ptr), C.c_void_p(modes_ptr)))
         return kept[: cp.size]
+
+    def set_zstd_sequences(self, on: bool):
+        """cldn_hip_codec_set_zstd_sequences: True = the ZSTD read side takes frames with sequences (default off: they are
+        handed to the host). See include/cloudini_hip.h for what it costs."""
+        _check(lib().cldn_hip_codec_set_zstd_sequences(self._h, 1 if on else 0))
+
+    def zstd_sequences(self) -> bool:
+        return bool(lib().cldn_hip_codec_zstd_sequences(self._h))
 
     def set_decode_fill(self, zero: bool):
         """cldn_hip_codec_set_decode_fill: True = bytes no field covers may be written as 0 (no round trip of a host buffer)."""

@@ -166,6 +166,16 @@ int cldn_amd_set_device_zstd_decode(int on);
 /* messages that took the device route through that switch since the library was loaded (a message that falls back to the host
  * route is not counted: the fall-back is silent by design, this is how a caller sees which route its messages take) */
 uint64_t cldn_amd_device_zstd_decode_count(void);
+/* ... and libzstd's own messages too: with this switch on (it has meaning only while cldn_amd_set_device_zstd_decode is on) the
+ * host classifies with the walk that reads sequences sections, and messages whose frames carry sequences take the device route
+ * (cldn_hip_codec_set_zstd_sequences); every frame the device hands to the host, and anything the device call returns, still
+ * falls back to the host route silently, and cldn_amd_device_zstd_decode_count counts the messages the device took. One wave
+ * executes a frame serially. Measured: a single message is 11 to 23 times SLOWER this way than libzstd on 16
+ * host threads (1 M XYZI points: 16.4 ms against 1.5 ms, 5.4 ms on one thread), so leave it off for host messages; it exists
+ * for callers whose messages must not touch the host pool. Off by default, no environment variable.
+ * Both return the value in effect (0, 1). */
+int cldn_amd_device_zstd_sequences(void);
+int cldn_amd_set_device_zstd_sequences(int on);
 /* Stage 2 of ZSTD streams on the GPU (include/cloudini_hip.h, CLDN_HIP_STAGE2_ZSTD): PointcloudEncoder::encode with
  * compression_opt == ZSTD then receives [u32 size][ZSTD frame] per chunk from the device. The frames are valid ZSTD frames of
  * literal-only blocks (Huffman-coded literals, no sequences) that the reference's decoder and this library's read; they are

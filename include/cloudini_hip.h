@@ -596,6 +596,21 @@ int cldn_hip_sweep_modes_last_encode(cldn_hip_codec_t* codec, cldn_hip_mode_cell
 #define CLDN_HIP_FILL_ZERO 1
 int cldn_hip_codec_set_decode_fill(cldn_hip_codec_t* codec, int fill);
 
+/* ZSTD frames WITH sequences on the device (zstd_seq_decode.hip): what ZSTD_compress writes at every level. Default 0: such a
+ * frame is handed to the host (sizes[k] == 0xfffffffe, CLDN_HIP_ERR_UNSUPPORTED), exactly as before this switch existed. With 1,
+ * cldn_hip_zstd_decompress, cldn_hip_decode_zstd and cldn_hip_audit_streams (kind ZSTD) decode them: Predefined, RLE,
+ * FSE_Compressed and Repeat tables, repeat offsets, matches of any reach inside the frame. Still for the host: dictionary id,
+ * checksum, skippable or several frames, window log above 27 (above 24 with sequences), Huffman table log above 11, and the
+ * forms on which libzstd's versions disagree (tests/zstd_seq_rules.py lists them). Verdicts, status bits and texts are
+ * unchanged. Cost while it is on: device workspace of 1 + 8/3 bytes per byte the outputs may take (a literal buffer and
+ * 8-byte sequence records) and 22 bytes per compressed byte (block records), sized from the call's totals. One wave executes
+ * a frame serially. Measured (profiles/r20_a_zstd_seq_bench.txt): a call takes about as long as its slowest
+ * frame -- 18.1 ms for 32 x 1 M XYZI clouds of libzstd level-1 frames resident in HBM (11.5 GB/s of payload; libzstd on 16 host
+ * threads: 49 ms), 9.1 ms for 64 x 130048 Velodyne clouds (host: 25.1 ms). Recommendation: on for device-resident batches of
+ * tens of clouds, off for single frames (a lone 1 M-point message takes 16.4 ms against 1.5 ms on the host pool). */
+int cldn_hip_codec_set_zstd_sequences(cldn_hip_codec_t* codec, int on);
+int cldn_hip_codec_zstd_sequences(const cldn_hip_codec_t* codec);
+
 /* Which kernels the last cldn_hip_decode_stage1 call used, in chunks (synchronises):
  *   stats[0] regular stream by the parallel decoder      stats[1] V5 sections by the parallel decoder
  *   stats[2] whole chunks by the serial decoder          stats[3] only the sections by the serial decoder */

@@ -7,7 +7,11 @@ and 64 x 130048 velodyne_xyzir.
   messages   the same clouds as ZSTD messages in host memory, one PointcloudDecoder::decode per message: the host route (libzstd
              on the stage-2 pool) with 1 and 16 threads, switch (set_device_zstd_decode) off and on
 Interleaved: every round runs every variant once, in the same order; 3 warm-up rounds, then 12 measured: median [min .. max].
-`zstddecbench.py once` makes the resident calls once each (for a kernel trace)."""
+`zstddecbench.py once` makes the resident calls once each (for a kernel trace).
+`zstddecbench.py seq [once]` measures frames WITH sequences instead (zstd_seq_decode.hip, cldn_hip_codec_set_zstd_sequences):
+the same clouds' stage-1 chunks compressed by libzstd (level 1, what PointcloudEncoder writes), HBM-resident against the plain
+stage-1 call, then as host messages: the host route on 1 and 16 threads against the device route with both switches on
+(set_device_zstd_decode, set_device_zstd_sequences). The workloads, rounds and batch sizes are the same."""
 import ctypes as C
 import os, sys, time
 import numpy as np
@@ -19,7 +23,8 @@ from cloudini_amd.schema import CompressionOption
 
 dev = torch.device("cuda", 0)
 ZSTD = 3
-ONCE = len(sys.argv) > 1 and sys.argv[1] == "once"
+ONCE = "once" in sys.argv[1:]
+SEQ = "seq" in sys.argv[1:]
 WARM, REPS = (0, 1) if ONCE else (3, 12)
 
 
@@ -47,6 +52,11 @@ for wl, gen, n_clouds in (("lidar_xyzi 1M", lambda: synth.lidar_xyzi(1_000_000),
     codec.set_stage2(ZSTD)
     frames = codec.encode_host([data])[0][0]
     codec.set_stage2(0)
+    if SEQ:  # libzstd's frames of the same chunks: the body of a host message
+        zi = info.copy(compression_opt=CompressionOption.ZSTD, use_threads=True)
+        e = api.PointcloudEncoder(zi)
+        frames = np.ascontiguousarray(e.encode(data)[len(e.getHeader()):])
+        codec.set_zstd_sequences(True)
     d_pts = torch.zeros(data.size * n_clouds, dtype=torch.uint8, device=dev)
 
     def resident(stream):
@@ -68,7 +78,7 @@ for wl, gen, n_clouds in (("lidar_xyzi 1M", lambda: synth.lidar_xyzi(1_000_000),
     codec.status()
     part = np.asarray(times["ZSTD frames"]) - np.asarray(times["stage-1 streams"])
     print(f"decode {wl} x{n_clouds}, HBM-resident: stage-1 streams {fmt(times['stage-1 streams'])} ({payload/1e6:.1f} MB of payload)")
-    print(f"decode {wl} x{n_clouds}, HBM-resident: device ZSTD frames ({frames.size*n_clouds/1e6:.1f} MB) {fmt(times['ZSTD frames'])} -> "
+    print(f"decode {wl} x{n_clouds}, HBM-resident: {'libzstd' if SEQ else 'device'} ZSTD frames ({frames.size*n_clouds/1e6:.1f} MB) {fmt(times['ZSTD frames'])} -> "
           f"ZSTD part {fmt(part)}, {payload/np.median(part)/1e9:.2f} GB/s of decoded payload")
     codec.close()
     if ONCE:
@@ -78,6 +88,8 @@ for wl, gen, n_clouds in (("lidar_xyzi 1M", lambda: synth.lidar_xyzi(1_000_000),
     enc = api.PointcloudEncoder(zinfo)
     hdr = len(enc.getHeader())
     bodies = {"libzstd": np.ascontiguousarray(enc.encode(data)[hdr:]), "device frames": np.ascontiguousarray(frames)}
+    if SEQ:
+        del bodies["device frames"]
     L = api.lib()
     ci, _keep = api._c_info(zinfo)
     out = np.zeros(data.size, dtype=np.uint8)
@@ -92,12 +104,14 @@ for wl, gen, n_clouds in (("lidar_xyzi 1M", lambda: synth.lidar_xyzi(1_000_000),
             tag, threads, on = row
             api.set_stage2_threads(threads)
             api.set_device_zstd_decode(on)
+            api.set_device_zstd_sequences(on and SEQ)
             try:
                 t = one(lambda: decode_all(bodies[tag]), lambda: None)
             finally:
                 api.set_device_zstd_decode(False)
+                api.set_device_zstd_sequences(False)
             if r >= WARM:
                 times[row].append(t)
     for (tag, threads, on), t in times.items():
-        print(f"decode {wl} x{n_clouds}, host messages ({tag}), {threads:2d} stage-2 thread(s), switch {'on ' if on else 'off'}: {fmt(t)} "
+        print(f"decode {wl} x{n_clouds}, host messages ({tag}), {threads:2d} stage-2 thread(s), switch{'es' if SEQ else ''} {'on ' if on else 'off'}: {fmt(t)} "
               f"({np.median(t)/n_clouds*1e3:.3f} ms per message)")
