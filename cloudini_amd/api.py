@@ -103,6 +103,9 @@ def lib() -> C.CDLL:
     L.cldn_amd_device_zstd_sequences.restype = C.c_int
     L.cldn_amd_set_device_zstd_sequences.restype = C.c_int
     L.cldn_amd_set_device_zstd_sequences.argtypes = [C.c_int]
+    L.cldn_amd_device_zstd_matches.restype = C.c_int
+    L.cldn_amd_set_device_zstd_matches.restype = C.c_int
+    L.cldn_amd_set_device_zstd_matches.argtypes = [C.c_int]
     L.cldn_amd_device_zstd.restype = C.c_int
     L.cldn_amd_set_device_zstd.restype = C.c_int
     L.cldn_amd_set_device_zstd.argtypes = [C.c_int]
@@ -212,6 +215,17 @@ def set_device_zstd_sequences(on) -> bool:
 def device_zstd_decode_count() -> int:
     """Messages that took the device route through set_device_zstd_decode since the library was loaded (fall-backs are silent)."""
     return int(lib().cldn_amd_device_zstd_decode_count())
+
+
+def device_zstd_matches() -> bool:
+    return bool(lib().cldn_amd_device_zstd_matches())
+
+
+def set_device_zstd_matches(on) -> bool:
+    """On top of set_device_zstd(True): the device's ZSTD frames carry sequences from its match search
+    (cldn_hip_codec_set_zstd_matches). Pays where the stage-1 bytes repeat (ring fields, lossless float64 stamps); token streams
+    stay as they are. Off by default; returns the value in effect."""
+    return bool(lib().cldn_amd_set_device_zstd_matches(1 if on else 0))
 
 
 def device_zstd() -> bool:

@@ -65,7 +65,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(ROOT, "build", "hip")
     os.makedirs(objdir, exist_ok=True)
-    names = ["stage1_kernels", "stage1_decode", "viz_kernels", "audit_kernels", "sweep_kernels", "hist_kernels", "mode_kernels", "lz4_kernels", "lz4_decode", "zstd_kernels", "zstd_decode", "zstd_seq_decode", "hip_abi"]
+    names = ["stage1_kernels", "stage1_decode", "viz_kernels", "audit_kernels", "sweep_kernels", "hist_kernels", "mode_kernels", "lz4_kernels", "lz4_decode", "zstd_kernels", "zstd_seq_kernels", "zstd_decode", "zstd_seq_decode", "hip_abi"]
     deps = _sources(CSRC, (".h",)) + _sources(os.path.join(ROOT, "include"), (".h",))
     deps = [d for d in deps if os.sep + "host" + os.sep not in d]
     jobs = []

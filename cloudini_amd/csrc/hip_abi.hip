@@ -203,6 +203,8 @@ struct cldn_hip_codec {
   DevBuf d_finrec;            // k_finish look-back records (rec, rec2), cleared only when (re)allocated
   int decode_fill = CLDN_HIP_FILL_KEEP;  // cldn_hip_codec_set_decode_fill
   int zstd_sequences = 0;                // cldn_hip_codec_set_zstd_sequences
+  int zstd_matches = 0;                  // cldn_hip_codec_set_zstd_matches
+  DevBuf d_zs_seq;                       // ... its workspace (ZstdSeqLaunch); the match lists are d_lz_matches
   DevBuf d_dec_bits;          // k_mark_token_ends: token-end bitmap of the streams of a decode call
   DevBuf d_dec_secs;          // k_section_offsets: per (field, chunk) section records + per-chunk counters
   DevBuf d_dec_rec;           // k_sections_cols_fast slice records, tagged with dec_epoch, cleared only when (re)allocated
@@ -659,7 +661,7 @@ void cldn_hip_codec_destroy(cldn_hip_codec_t* c) {
   (void)guard.enter(c->device);
   (void)hipStreamSynchronize(c->stream);
   DevBuf* bufs[] = {&c->d_in, &c->d_out, &c->d_slots, &c->d_chunks, &c->d_cloud_first, &c->d_finrec, &c->d_dec_rec, &c->d_dec_bits, &c->d_dec_secs, &c->d_s1, &c->d_s1_offsets,
-                    &c->d_lz_matches, &c->d_stage2_ws, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables, &c->d_zsd_ws,
+                    &c->d_lz_matches, &c->d_zs_seq, &c->d_stage2_ws, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables, &c->d_zsd_ws,
                     &c->d_payload, &c->d_dst, &c->d_offsets, &c->d_modes, &c->d_status, &c->d_dec_meta, &c->d_pre_ptrs, &c->d_dec_cols[0], &c->d_dec_cols[1], &c->d_dec_cols[2], &c->d_dec_cols[3], &c->d_dec_cols[4], &c->d_dec_cols[5], &c->d_dec_cols[6], &c->d_dec_cols[7],
                     &c->d_viz_keys, &c->d_viz_slot, &c->d_viz_blocks, &c->d_viz_bits, &c->d_viz_tables, &c->d_viz_kept, &c->d_viz_out,
                     &c->d_pieces, &c->d_audit, &c->d_audit_tab, &c->d_audit_rep};
@@ -940,6 +942,32 @@ static int stage_host_input(cldn_hip_codec* c, const void* points, const void* c
   return CLDN_HIP_OK;
 }
 
+// How many sub-ranges the match lists of a stage-2 call are sized for (LZ4, and ZSTD with matches): every chunk has
+// ceil(payload / sub-range bytes) of them. *stage1_failed: no stage 2 over stale sizes -- the stream offsets are cleared and the
+// status handling of the caller (ticket retry / error) takes it from here.
+static int size_match_lists(cldn_hip_codec_t* c, uint32_t n_chunks, uint32_t n_clouds, uint64_t need_s1, uint32_t lz_sub, uint32_t lz_mm,
+                            uint64_t* max_subs_out, bool* stage1_failed_out) {
+  uint64_t max_subs = need_s1 / lz_sub + n_chunks;
+  // the match lists take as many bytes as the payloads they describe: sized from the worst-case stage-1 bound that is
+  // gigabytes for a large batch (32 x 1 M XYZI points: 1.3 GB for 207 MB of payload). Beyond 256 MB the call waits for
+  // stage 1 and sizes them from the bytes it really wrote (one 8-byte read; the wait is ~5 % of what the LZ4 stage takes)
+  bool stage1_failed = false;
+  if (max_subs * lz_mm * sizeof(LzMatch) > (256ull << 20)) {
+    uint64_t total_s1 = 0;
+    uint32_t st1 = 0;  // the status word travels with the total: behind a stage 1 that gave up (ST_FINISH_TIMEOUT: k_finish
+                       // returned before it wrote offsets, payload sizes and positions) the total is a stale number
+    HIP_TRY(hipMemcpyAsync(&total_s1, (const uint64_t*)c->d_s1_offsets.p + n_clouds, sizeof(total_s1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&st1, c->d_status.p, sizeof(st1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    stage1_failed = st1 != 0u;
+    if (!stage1_failed && total_s1 <= need_s1) max_subs = total_s1 / lz_sub + n_chunks;  // (every chunk's last sub-range may be partial)
+  }
+  if (stage1_failed) HIP_TRY(hipMemsetAsync(c->d_offsets.p, 0, (size_t)(n_clouds + 1) * sizeof(uint64_t), c->stream));
+  *max_subs_out = max_subs;
+  *stage1_failed_out = stage1_failed;
+  return CLDN_HIP_OK;
+}
+
 // Stage 2 on the device, behind stage1_launch_encode of a call whose codec asks for it: the chunks' stage-1 payloads in d_s1 become
 // LZ4 blocks (lz4_kernels.hip) or ZSTD frames of literal-only blocks (zstd_kernels.hip), written straight into the framed streams
 // at `out`, with their sizes and the clouds' stream offsets (d_offsets). *d_sizes becomes the buffer chunk_sizes reports where a
@@ -968,10 +996,22 @@ static int launch_device_stage2(cldn_hip_codec_t* c, uint32_t n_chunks, uint32_t
   if (c->stage2 == CLDN_HIP_STAGE2_ZSTD) {
     // every chunk has ceil(payload / 128 KiB) blocks, one at least
     const uint64_t max_blocks = need_s1 / kZsBlockBytes + n_chunks;
+    ZstdSeqLaunch Q;
+    if (c->zstd_matches) {  // the match search of the LZ4 route with the standard parameters, its lists sized by the same rule
+      uint64_t max_subs = 0;
+      bool stage1_failed = false;
+      if ((rc = size_match_lists(c, n_chunks, n_clouds, need_s1, kLzSubBytes, kLzMaxMatches, &max_subs, &stage1_failed)) != CLDN_HIP_OK) return rc;
+      if (stage1_failed) return CLDN_HIP_OK;
+      if ((rc = c->d_lz_matches.ensure((size_t)max_subs * kLzMaxMatches * sizeof(LzMatch))) != CLDN_HIP_OK) return rc;
+      if ((rc = c->d_zs_seq.ensure(ZstdSeqLaunch::workspace_bytes(max_subs, max_blocks, n_chunks))) != CLDN_HIP_OK) return rc;
+      Q.matches = (LzMatch*)c->d_lz_matches.p;
+      Q.carve(c->d_zs_seq.p, max_subs, max_blocks, n_chunks);
+    }
     if ((rc = c->d_stage2_ws.ensure(ZstdLaunch::workspace_bytes(max_blocks, n_chunks))) != CLDN_HIP_OK) return rc;
     ZstdLaunch Z;
     Z.io = io;
     Z.carve(c->d_stage2_ws.p, max_blocks, n_chunks);
+    Z.seq = c->zstd_matches ? &Q : nullptr;
     if ((rc = zstd_launch(Z)) != CLDN_HIP_OK) return rc;
     *d_sizes = c->d_payload2.p;
     return CLDN_HIP_OK;
@@ -979,25 +1019,10 @@ static int launch_device_stage2(cldn_hip_codec_t* c, uint32_t n_chunks, uint32_t
   // every chunk has ceil(payload / sub-range bytes) sub-ranges
   const bool lz4_fast = c->stage2 == CLDN_HIP_STAGE2_LZ4_FAST;
   const uint32_t lz_sub = lz4_fast ? kLzFastSubBytes : kLzSubBytes, lz_mm = lz4_fast ? kLzFastMaxMatches : kLzMaxMatches;
-  uint64_t max_subs = need_s1 / lz_sub + n_chunks;
-  // the match lists take as many bytes as the payloads they describe: sized from the worst-case stage-1 bound that is
-  // gigabytes for a large batch (32 x 1 M XYZI points: 1.3 GB for 207 MB of payload). Beyond 256 MB the call waits for
-  // stage 1 and sizes them from the bytes it really wrote (one 8-byte read; the wait is ~5 % of what the LZ4 stage takes)
+  uint64_t max_subs = 0;
   bool stage1_failed = false;
-  if (max_subs * lz_mm * sizeof(LzMatch) > (256ull << 20)) {
-    uint64_t total_s1 = 0;
-    uint32_t st1 = 0;  // the status word travels with the total: behind a stage 1 that gave up (ST_FINISH_TIMEOUT: k_finish
-                       // returned before it wrote offsets, payload sizes and positions) the total is a stale number
-    HIP_TRY(hipMemcpyAsync(&total_s1, (const uint64_t*)c->d_s1_offsets.p + n_clouds, sizeof(total_s1), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&st1, c->d_status.p, sizeof(st1), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    stage1_failed = st1 != 0u;
-    if (!stage1_failed && total_s1 <= need_s1) max_subs = total_s1 / lz_sub + n_chunks;  // (every chunk's last sub-range may be partial)
-  }
-  if (stage1_failed) {  // no LZ4 stage over stale sizes: the status handling of the caller (ticket retry / error) takes it from here
-    HIP_TRY(hipMemsetAsync(c->d_offsets.p, 0, (size_t)(n_clouds + 1) * sizeof(uint64_t), c->stream));
-    return CLDN_HIP_OK;
-  }
+  if ((rc = size_match_lists(c, n_chunks, n_clouds, need_s1, lz_sub, lz_mm, &max_subs, &stage1_failed)) != CLDN_HIP_OK) return rc;
+  if (stage1_failed) return CLDN_HIP_OK;
   if ((rc = c->d_lz_matches.ensure((size_t)max_subs * lz_mm * sizeof(LzMatch))) != CLDN_HIP_OK) return rc;
   if ((rc = c->d_stage2_ws.ensure(Lz4Launch::workspace_bytes(max_subs, n_chunks))) != CLDN_HIP_OK) return rc;
   Lz4Launch Z;
@@ -1720,6 +1745,14 @@ int cldn_hip_codec_set_zstd_sequences(cldn_hip_codec_t* c, int on) {
 }
 
 int cldn_hip_codec_zstd_sequences(const cldn_hip_codec_t* c) { return c && c->zstd_sequences ? 1 : 0; }
+
+int cldn_hip_codec_set_zstd_matches(cldn_hip_codec_t* c, int on) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->zstd_matches = on ? 1 : 0;
+  return CLDN_HIP_OK;
+}
+
+int cldn_hip_codec_zstd_matches(const cldn_hip_codec_t* c) { return c && c->zstd_matches ? 1 : 0; }
 
 int cldn_hip_codec_decode_stats(cldn_hip_codec_t* c, uint32_t stats[4]) {
   if (!c || !stats) return fail(CLDN_HIP_ERR_ARG, "decode_stats: NULL argument");

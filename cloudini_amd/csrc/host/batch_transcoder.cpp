@@ -309,7 +309,8 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     Run& run = b.runs[n_runs++];
     run.estimated = false;
     run.packed = opt.device_zstd && opt.compression == Cloudini::CompressionOption::ZSTD;
-    const int stage2_mode = run.packed ? CLDN_HIP_STAGE2_ZSTD : CLDN_HIP_STAGE2_NONE;
+    const int stage2_mode = run.packed ? CLDN_HIP_STAGE2_ZSTD | (opt.device_zstd_matches ? Cloudini::amd_detail::kStage2ZstdMatches : 0)
+                                       : CLDN_HIP_STAGE2_NONE;
     run.first = r0;
     run.count = static_cast<uint32_t>(r1 - r0);
     const Cloudini::EncodingInfo& info0 = b.parsed[r0].info;
@@ -847,6 +848,9 @@ void checkOptions(const TranscodeOptions& opt) {
   if (opt.decode && opt.modes != TranscodeOptions::Modes::Off)
     throw std::invalid_argument("TranscodeOptions: modes is not available together with decode");
   if (opt.decode && opt.device_zstd) throw std::invalid_argument("TranscodeOptions: device_zstd is not available together with decode");
+  if (opt.decode && opt.device_zstd_matches)
+    throw std::invalid_argument("TranscodeOptions: device_zstd_matches is not available together with decode");
+  if (opt.device_zstd_matches && !opt.device_zstd) throw std::invalid_argument("TranscodeOptions: device_zstd_matches needs device_zstd");
   for (const auto& named : opt.sweep)
     if (named.second.size() > CLDN_HIP_SWEEP_MAX_CANDIDATES)
       throw std::invalid_argument("TranscodeOptions: the sweep ladder of " + named.first + " has more than 16 resolutions");

@@ -347,6 +347,11 @@ CLDN_EXPORT int cldn_amd_set_device_lz4(int on) {
   return Cloudini::amd_detail::deviceLz4Level();
 }
 
+CLDN_EXPORT int cldn_amd_device_zstd_matches(void) { return Cloudini::amd_detail::deviceZstdMatches() ? 1 : 0; }
+CLDN_EXPORT int cldn_amd_set_device_zstd_matches(int on) {
+  Cloudini::amd_detail::setDeviceZstdMatches(on != 0);
+  return Cloudini::amd_detail::deviceZstdMatches() ? 1 : 0;
+}
 CLDN_EXPORT int cldn_amd_device_zstd(void) { return Cloudini::amd_detail::deviceZstd() ? 1 : 0; }
 CLDN_EXPORT int cldn_amd_set_device_zstd(int on) {
   Cloudini::amd_detail::setDeviceZstd(on != 0);

@@ -789,10 +789,15 @@ size_t PointcloudEncoder::encode(ConstBufferView cloud_data, BufferView& output,
     // ZSTD (amd_detail::setDeviceZstd): [u32 size][frame of literal-only blocks] per chunk -- valid frames, not libzstd's bytes.
     struct Reset {
       cldn_hip_codec_t* codec;
-      ~Reset() { (void)cldn_hip_codec_set_stage2(codec, CLDN_HIP_STAGE2_NONE); }  // the codec goes back to the pool
+      ~Reset() {  // the codec goes back to the pool
+        (void)cldn_hip_codec_set_stage2(codec, CLDN_HIP_STAGE2_NONE);
+        (void)cldn_hip_codec_set_zstd_matches(codec, 0);
+      }
     } reset{impl_->codec};
     const int lz_mode = device_zstd ? CLDN_HIP_STAGE2_ZSTD : amd_detail::deviceLz4Level() >= 2 ? CLDN_HIP_STAGE2_LZ4_FAST : CLDN_HIP_STAGE2_LZ4;
     if (cldn_hip_codec_set_stage2(impl_->codec, lz_mode) != CLDN_HIP_OK) throw std::runtime_error(cldn_hip_last_error());
+    if (cldn_hip_codec_set_zstd_matches(impl_->codec, device_zstd && amd_detail::deviceZstdMatches() ? 1 : 0) != CLDN_HIP_OK)
+      throw std::runtime_error(cldn_hip_last_error());
     uint64_t offsets[2] = {0, 0};
     if (cldn_hip_encode_stage1(impl_->codec, cloud_data.data(), CLDN_HIP_HOST, &points, 1, dst + written, output.size() - written,
                                CLDN_HIP_HOST, offsets, impl_->chunk_sizes.data(), nullptr) != CLDN_HIP_OK)
@@ -1088,6 +1093,9 @@ std::atomic<bool> g_device_zstd{false};
 }
 bool deviceZstd() { return g_device_zstd.load(); }
 void setDeviceZstd(bool on) { g_device_zstd.store(on); }
+std::atomic<bool> g_device_zstd_matches{false};
+bool deviceZstdMatches() { return g_device_zstd_matches.load(); }
+void setDeviceZstdMatches(bool on) { g_device_zstd_matches.store(on); }
 
 namespace {
 std::atomic<bool> g_device_lz4_decode{false};
@@ -1184,13 +1192,15 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
     }
     return rc;
   };
-  int rc = cldn_hip_codec_set_stage2(codec, stage2);
+  int rc = cldn_hip_codec_set_stage2(codec, stage2 & 0xff);
+  if (rc == CLDN_HIP_OK) rc = cldn_hip_codec_set_zstd_matches(codec, (stage2 & kStage2ZstdMatches) ? 1 : 0);
   if (rc == CLDN_HIP_OK) rc = encode();
   if (rc == CLDN_HIP_OK && modes) rc = modesLastEncode(codec, plan.plan, n_clouds, modes, encode);
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
   (void)cldn_hip_codec_set_stage2(codec, CLDN_HIP_STAGE2_NONE);  // the codec goes back to the pool
+  (void)cldn_hip_codec_set_zstd_matches(codec, 0);
   pool().release(info, codec);
   if (rc != CLDN_HIP_OK) throw std::runtime_error(err);
   chunk_sizes.resize((size_t)n_chunks);
@@ -1218,13 +1228,15 @@ void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_
     }
     return rc;
   };
-  int rc = cldn_hip_codec_set_stage2(codec, stage2);
+  int rc = cldn_hip_codec_set_stage2(codec, stage2 & 0xff);
+  if (rc == CLDN_HIP_OK) rc = cldn_hip_codec_set_zstd_matches(codec, (stage2 & kStage2ZstdMatches) ? 1 : 0);
   if (rc == CLDN_HIP_OK) rc = encode();  // (a second encode filters again: the same survivors)
   if (rc == CLDN_HIP_OK && modes) rc = modesLastEncode(codec, plan.plan, n_clouds, modes, encode);
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
   (void)cldn_hip_codec_set_stage2(codec, CLDN_HIP_STAGE2_NONE);  // the codec goes back to the pool
+  (void)cldn_hip_codec_set_zstd_matches(codec, 0);
   pool().release(info, codec);
   if (rc != CLDN_HIP_OK) throw std::runtime_error(err);
   kept_points.resize(n_clouds);

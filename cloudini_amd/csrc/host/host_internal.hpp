@@ -66,7 +66,9 @@ void encodeStage1Batch(const Cloudini::EncodingInfo& info, const uint8_t* const*
                        ModesRequest* modes = nullptr, int stage2 = 0);
 // `stage2` (both calls): the codec's stage-2 mode for the call (cldn_hip_codec_set_stage2; 0 = CLDN_HIP_STAGE2_NONE). With
 // CLDN_HIP_STAGE2_ZSTD the streams are [u32 size][ZSTD frame] per chunk and chunk_sizes the frame sizes: finished chunks of
-// a ZSTD message, nothing is left for the host's stage 2.
+// a ZSTD message, nothing is left for the host's stage 2. kStage2ZstdMatches added to it turns cldn_hip_codec_set_zstd_matches on
+// for the call.
+constexpr int kStage2ZstdMatches = 0x100;
 // The same behind the viz pre-filter (cldn_hip_encode_stage1_viz_gather): every cloud is filtered on its own, the survivors
 // are encoded without leaving the device. kept_points gets n_clouds survivor counts; stream_offsets and chunk_sizes describe
 // the filtered clouds (a cloud that loses every point has an empty stream and no chunk).
@@ -97,6 +99,10 @@ void setDeviceLz4Level(int level);
 // environment variable; with it off every path is what it was.
 bool deviceZstd();               // PointcloudEncoder::encode with CompressionOption::ZSTD writes the device's literal-only frames
 void setDeviceZstd(bool on);     // (default off; valid ZSTD frames, not libzstd's bytes)
+// ... with sequences from the device's match search (cldn_hip_codec_set_zstd_matches); it has meaning only while deviceZstd() is
+// on; default off, no environment variable
+bool deviceZstdMatches();
+void setDeviceZstdMatches(bool on);
 bool deviceLz4Decode();
 void setDeviceLz4Decode(bool on);
 // ZSTD messages of frames without sequences through cldn_hip_decode_zstd (PointcloudDecoder::decode); default off

@@ -712,25 +712,35 @@ __global__ __launch_bounds__(1024) void k_lz4_offsets(const uint32_t* __restrict
   cloud_stream_offsets(cloud_first_chunk, n_clouds, n_chunks, [&](uint32_t c) { return block_dst[c]; }, total, stream_offsets, tid, 1024u);
 }
 
+int lz4_launch_match(const Stage2Io& io, uint32_t fast, uint64_t max_subs, uint32_t* sub_first, LzMatch* matches, uint32_t* counts,
+                     uint32_t* last_end, uint32_t* sub_chunk) {
+  hipError_t e;
+  const uint32_t sub_bytes = fast ? kLzFastSubBytes : kLzSubBytes;
+  hipLaunchKernelGGL(k_lz4_plan, dim3(1), dim3(1024), 0, io.stream, io.chunk_payload, io.n_chunks, sub_first, sub_bytes,
+                     (uint32_t)std::min<uint64_t>(max_subs, 0xffffffffu), io.status);
+  if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_plan");
+  // one wave per sub-range, at most `max_subs` of them: workgroups beyond the real number find nothing to do
+  // (round 5: one workgroup per sub-range -- the dispatcher balances them; 8192 looping workgroups ran 1.68 rounds)
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(max_subs, 1u << 20);
+  if (fast)
+    hipLaunchKernelGGL((k_lz4_match<kLzFastSubBytes, kLzFastHashBits, kLzFastMaxMatches>), dim3(grid), dim3(64), 0, io.stream, io.stage1,
+                       io.chunk_dst, io.chunk_payload, io.n_chunks, sub_first, matches, counts, last_end, sub_chunk);
+  else
+    hipLaunchKernelGGL((k_lz4_match<kLzSubBytes, kLzHashBits, kLzMaxMatches>), dim3(grid), dim3(64), 0, io.stream, io.stage1, io.chunk_dst,
+                       io.chunk_payload, io.n_chunks, sub_first, matches, counts, last_end, sub_chunk);
+  if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_match");
+  return CLDN_HIP_OK;
+}
+
 int lz4_launch(const Lz4Launch& L) {
   const Stage2Io& io = L.io;
   if (io.n_chunks == 0u) return CLDN_HIP_OK;
   hipError_t e;
+  int rc;
   const uint32_t sub_bytes = L.fast ? kLzFastSubBytes : kLzSubBytes;
   const uint32_t max_matches = L.fast ? kLzFastMaxMatches : kLzMaxMatches;
-  hipLaunchKernelGGL(k_lz4_plan, dim3(1), dim3(1024), 0, io.stream, io.chunk_payload, io.n_chunks, L.sub_first, sub_bytes,
-                     (uint32_t)std::min<uint64_t>(L.max_subs, 0xffffffffu), io.status);
-  if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_plan");
-  // one wave per sub-range, at most `max_subs` of them: workgroups beyond the real number find nothing to do
-  // (round 5: one workgroup per sub-range -- the dispatcher balances them; 8192 looping workgroups ran 1.68 rounds)
+  if ((rc = lz4_launch_match(io, L.fast, L.max_subs, L.sub_first, L.matches, L.counts, L.last_end, L.sub_chunk)) != CLDN_HIP_OK) return rc;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(L.max_subs, 1u << 20);
-  if (L.fast)
-    hipLaunchKernelGGL((k_lz4_match<kLzFastSubBytes, kLzFastHashBits, kLzFastMaxMatches>), dim3(grid), dim3(64), 0, io.stream, io.stage1,
-                       io.chunk_dst, io.chunk_payload, io.n_chunks, L.sub_first, L.matches, L.counts, L.last_end, L.sub_chunk);
-  else
-    hipLaunchKernelGGL((k_lz4_match<kLzSubBytes, kLzHashBits, kLzMaxMatches>), dim3(grid), dim3(64), 0, io.stream, io.stage1, io.chunk_dst,
-                       io.chunk_payload, io.n_chunks, L.sub_first, L.matches, L.counts, L.last_end, L.sub_chunk);
-  if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_match");
   hipLaunchKernelGGL(k_lz4_sizes, dim3(grid), dim3(64), 0, io.stream, io.n_chunks, L.sub_first, L.matches, L.counts, L.last_end,
                      L.anchor_in, L.sub_size, max_matches, L.sub_chunk);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_lz4_sizes");

@@ -240,6 +240,10 @@ struct Lz4Launch {
   }
 };
 int lz4_launch(const Lz4Launch& L);
+// the front of it, which the ZSTD writer with matches shares: k_lz4_plan (sub_first[n_chunks + 1]) and k_lz4_match (matches,
+// counts, last_end, sub_chunk: [max_subs] each) over the payloads of `io`
+int lz4_launch_match(const Stage2Io& io, uint32_t fast, uint64_t max_subs, uint32_t* sub_first, LzMatch* matches, uint32_t* counts,
+                     uint32_t* last_end, uint32_t* sub_chunk);
 
 // ---- ZSTD frame of literal-only blocks per chunk (zstd_kernels.hip; restated in tests/zstd_lit_model.py) ----
 constexpr uint32_t kZsBlockBytes = 131072;  // a frame's blocks: consecutive pieces of the payload
@@ -247,6 +251,7 @@ constexpr uint32_t kZsMinHuf = 64;          // a block below this is Raw
 constexpr uint32_t kZsFourStreams = 256;    // one Huffman stream below, four from here on
 constexpr uint32_t kZsDescBytes = 128;      // a tree description: its head byte and at most 127 more
 constexpr uint32_t kZsRaw = 0, kZsRle = 1, kZsHuf = 2;  // (the block types of the format)
+constexpr uint32_t kZsChunkBad = 0u, kZsChunkPlanned = 1u, kZsChunkFits = 2u;  // chunk_state: k_zstd_plan, k_zstd_offsets
 struct ZsBlock {
   uint32_t chunk, off, n;   // the block is [off, off + n) of the chunk's payload
   uint32_t kind;
@@ -256,6 +261,69 @@ struct ZsBlock {
   uint32_t comp;            // tree description + jump table + streams
   uint32_t stream[4];       // bytes of the streams
   uint32_t rle;             // the byte of an RLE block
+  uint32_t n_lit;           // literals: n, or what the kept matches of a block with sequences leave
+  // a block with sequences (cldn_hip_codec_set_zstd_matches; n_seq != 0): kind is kZsHuf (Compressed) and the fields above describe
+  // its literals section where it is Huffman-coded
+  uint32_t n_seq;
+  uint32_t lit_kind;        // kZsRaw / kZsRle / kZsHuf literals
+  uint32_t lit_bytes;       // the literals section, header included
+};
+// ---- ... with sequences from the LZ4 match search (zstd_seq_kernels.hip; restated in tests/zstd_match_model.py) ----
+struct ZsSeqPlan {
+  uint32_t n_seq, n_lit;    // kept matches of a block (0: it stays a literal-only block) and the bytes they leave
+};
+struct ZsSeqInfo {
+  uint32_t bytes;           // the block's sequence bit stream
+  uint32_t tail_pos;        // bit position of the closing states
+  uint32_t tail_bits;       // match-length, offset and literal-length state and the final 1 bit: 18 bits
+  uint32_t pad;
+};
+// Everything per sequence and per literal is indexed by sub-range: block idx of chunk c owns the sub-ranges from
+// sub_first[c] + 16 * (idx - blk_first[c]) on, kLzMaxMatches records and kLzSubBytes literals each.
+struct ZstdSeqLaunch {
+  uint64_t max_subs;              // as Lz4Launch's, with the standard parameters
+  LzMatch* matches;               // [max_subs * kLzMaxMatches], a buffer of its own
+  // the workspace, in this order (carve); every array starts at a multiple of 64 bytes
+  uint8_t* lits;                  // [max_subs * kLzSubBytes]: the literals of the blocks with sequences, compacted
+  uint64_t* seq_bits;             // [max_subs * kLzMaxMatches]: bits of a sequence, in stream order (the last sequence first)
+  LzMatch* seqs;                  // [max_subs * kLzMaxMatches]: the kept matches, compacted
+  uint32_t* seq_pos;              // [max_subs * kLzMaxMatches]: where those bits start in the block's bit stream
+  uint32_t* counts;               // [max_subs]  k_lz4_match
+  uint32_t* last_end;             // [max_subs]  k_lz4_match
+  uint32_t* sub_chunk;            // [max_subs]  k_lz4_match
+  uint32_t* seq_first;            // [max_subs]: kept matches of the block's earlier sub-ranges
+  uint32_t* lit_first;            // [max_subs]: literals of the block's earlier sub-ranges
+  uint32_t* sub_first;            // [n_chunks + 1]
+  ZsSeqPlan* plan;                // [max_blocks]
+  ZsSeqInfo* info;                // [max_blocks]
+  static size_t up64(size_t v) { return (v + 63u) & ~size_t(63); }
+  static size_t workspace_bytes(uint64_t max_subs, uint64_t max_blocks, uint32_t n_chunks) {
+    const size_t m = (size_t)max_subs;
+    return up64(m * kLzSubBytes) + up64(m * kLzMaxMatches * 8u) * 2u + up64(m * kLzMaxMatches * 4u) + up64(m * 4u) * 5u +
+           up64(((size_t)n_chunks + 1u) * 4u) + up64((size_t)max_blocks * sizeof(ZsSeqPlan)) + up64((size_t)max_blocks * sizeof(ZsSeqInfo));
+  }
+  void carve(void* ws, uint64_t max_subs_, uint64_t max_blocks, uint32_t n_chunks) {
+    const size_t m = (size_t)max_subs_;
+    uint8_t* p = (uint8_t*)ws;
+    auto take = [&p](size_t bytes) {
+      uint8_t* at = p;
+      p += up64(bytes);
+      return at;
+    };
+    max_subs = max_subs_;
+    lits = take(m * kLzSubBytes);
+    seq_bits = (uint64_t*)take(m * kLzMaxMatches * 8u);
+    seqs = (LzMatch*)take(m * kLzMaxMatches * 8u);
+    seq_pos = (uint32_t*)take(m * kLzMaxMatches * 4u);
+    counts = (uint32_t*)take(m * 4u);
+    last_end = (uint32_t*)take(m * 4u);
+    sub_chunk = (uint32_t*)take(m * 4u);
+    seq_first = (uint32_t*)take(m * 4u);
+    lit_first = (uint32_t*)take(m * 4u);
+    sub_first = (uint32_t*)take(((size_t)n_chunks + 1u) * 4u);
+    plan = (ZsSeqPlan*)take((size_t)max_blocks * sizeof(ZsSeqPlan));
+    info = (ZsSeqInfo*)take((size_t)max_blocks * sizeof(ZsSeqInfo));
+  }
 };
 struct ZstdLaunch {
   Stage2Io io;
@@ -267,6 +335,7 @@ struct ZstdLaunch {
   uint64_t* block_dst;            // [max_blocks + 1]: where a block's header goes in io.out (a chunk's first: its [u32] prefix)
   uint32_t* blk_first;            // [n_chunks + 1]: compact block numbering
   uint32_t* chunk_state;          // [n_chunks]
+  const ZstdSeqLaunch* seq = nullptr;  // cldn_hip_codec_set_zstd_matches: blocks may hold sequences; NULL = literal-only blocks
   struct Layout {
     size_t codes, descs, block_dst, blk_first, chunk_state, bytes;
   };
@@ -294,6 +363,10 @@ struct ZstdLaunch {
   }
 };
 int zstd_launch(const ZstdLaunch& L);
+// zstd_seq_kernels.hip, called by zstd_launch where L.seq is set: behind k_zstd_plan (match search, per-block plan, compaction,
+// sequence coder) and behind k_zstd_emit_lits (the bit streams)
+int zstd_seq_launch_front(const ZstdLaunch& L, uint32_t max_blocks);
+int zstd_seq_launch_emit(const ZstdLaunch& L, uint32_t max_blocks);
 
 // ---- LZ4 blocks back into bytes on the device (lz4_decode.hip) ----
 constexpr uint32_t kLz4Rejected = 0xffffffffu;  // sizes[k] of a block the strict rules refuse

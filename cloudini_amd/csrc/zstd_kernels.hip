@@ -35,7 +35,6 @@ namespace cldn {
 namespace {
 
 constexpr uint32_t kZsMaxLen = 11u;
-constexpr uint32_t kZsChunkBad = 0u, kZsChunkPlanned = 1u, kZsChunkFits = 2u;
 // bytes of a stream's image: 32768 symbols of 11 bits, the closing bit, 15 bytes of alignment, whole 16-byte units
 constexpr uint32_t kZsImgBytes = ((kZsBlockBytes / 4u * kZsMaxLen / 8u + 1u + 15u + 15u) / 16u) * 16u;
 
@@ -97,12 +96,26 @@ __global__ __launch_bounds__(1024) void k_zstd_plan(const uint32_t* __restrict__
   if (bad) atomicOr(status, (uint32_t)ST_OUT_OVERFLOW);
 }
 
-// one workgroup of four waves per block
-__global__ __launch_bounds__(256) void k_zstd_code(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ chunk_dst,
-                                                   const uint32_t* __restrict__ chunk_payload, uint32_t n_chunks,
-                                                   const uint32_t* __restrict__ blk_first, const uint32_t* __restrict__ chunk_state,
-                                                   ZsBlock* __restrict__ blocks, uint32_t* __restrict__ codes,
-                                                   uint8_t* __restrict__ descs) {
+namespace {
+
+// bytes of the header of a Raw or RLE literals section of n literals
+__device__ __forceinline__ uint32_t zs_raw_lit_header(uint32_t n) { return n < 32u ? 1u : n < 4096u ? 2u : 3u; }
+
+// where the literals (zstd_seq_kernels.hip) and the sequence records of block idx of chunk c start, in sub-ranges
+__device__ __forceinline__ uint32_t zs_first_sub(const uint32_t* __restrict__ sub_first, const uint32_t* __restrict__ blk_first, uint32_t c,
+                                                 uint32_t idx) {
+  return sub_first[c] + (idx - blk_first[c]) * (kZsBlockBytes / kLzSubBytes);
+}
+
+// SEQ (cldn_hip_codec_set_zstd_matches): a block with kept matches (plan[idx].n_seq != 0) codes its compacted literals, and the
+// record describes a literals section; every other block goes the way it goes without the switch
+template <bool SEQ>
+__device__ __forceinline__ void zs_code_body(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ chunk_dst,
+                                             const uint32_t* __restrict__ chunk_payload, uint32_t n_chunks,
+                                             const uint32_t* __restrict__ blk_first, const uint32_t* __restrict__ chunk_state,
+                                             ZsBlock* __restrict__ blocks, uint32_t* __restrict__ codes, uint8_t* __restrict__ descs,
+                                             const ZsSeqPlan* __restrict__ plan, const uint32_t* __restrict__ sub_first,
+                                             const uint8_t* __restrict__ lits) {
   __shared__ uint32_t hist[4][8][256];
   __shared__ uint32_t cnt[4][256];
   __shared__ uint32_t ukey[256], key[256];
@@ -131,15 +144,34 @@ __global__ __launch_bounds__(256) void k_zstd_code(const uint8_t* __restrict__ s
     rec.comp = 0u;
     rec.rle = 0u;
     for (uint32_t j = 0; j < 4u; ++j) rec.stream[j] = 0u;
+    rec.n_seq = 0u;
+    rec.lit_kind = 0u;
+    rec.lit_bytes = 0u;
     const bool planned = chunk_state[c] != kZsChunkBad;
-    const uint32_t n = planned ? min(chunk_payload[c] - rec.off, kZsBlockBytes) : 0u;
-    rec.n = n;
-    rec.body = n;
+    const uint32_t bn = planned ? min(chunk_payload[c] - rec.off, kZsBlockBytes) : 0u;
+    rec.n = bn;
+    rec.body = bn;
+    uint32_t n = bn;  // the literals: the whole block unless it has kept matches
+    bool matched = false;
+    const uint8_t* in = nullptr;
+    if constexpr (SEQ) {
+      const ZsSeqPlan p = plan[idx];
+      if (p.n_seq) {
+        matched = true;
+        n = p.n_lit;
+        rec.n_seq = p.n_seq;
+        rec.kind = kZsHuf;  // a Compressed block, unless k_zstd_offsets finds it not smaller than Raw
+        rec.lit_kind = kZsRaw;
+        rec.lit_bytes = zs_raw_lit_header(n) + n;
+        in = lits + (size_t)zs_first_sub(sub_first, blk_first, c, idx) * kLzSubBytes;
+      }
+    }
+    rec.n_lit = n;
     if (n < kZsMinHuf) {  // (uniform) Raw
       if (tid == 0u) blocks[idx] = rec;
       continue;
     }
-    const uint8_t* in = stream + chunk_dst[c] + 4u + rec.off;
+    if (!matched) in = stream + chunk_dst[c] + 4u + rec.off;
     const bool four = n >= kZsFourStreams;
     const uint32_t seg = four ? (n + 3u) / 4u : n;
     __syncthreads();  // the previous block's LDS contents are done with
@@ -181,8 +213,13 @@ __global__ __launch_bounds__(256) void k_zstd_code(const uint8_t* __restrict__ s
     }
     __syncthreads();
     if (m == 1u) {  // (uniform) RLE
-      rec.kind = kZsRle;
-      rec.body = 1u;
+      if (matched) {
+        rec.lit_kind = kZsRle;
+        rec.lit_bytes = zs_raw_lit_header(n) + 1u;
+      } else {
+        rec.kind = kZsRle;
+        rec.body = 1u;
+      }
       rec.rle = key[255] & 255u;
       if (tid == 0u) blocks[idx] = rec;
       continue;
@@ -392,9 +429,11 @@ __global__ __launch_bounds__(256) void k_zstd_code(const uint8_t* __restrict__ s
         comp += rec.stream[j];
       }
       const uint32_t hdr = (!four || (n < 1024u && comp < 1024u)) ? 3u : (n < 16384u && comp < 16384u) ? 4u : 5u;
-      if (bytes && comp < 262144u && hdr + comp + 1u < n) {
+      if (matched ? bytes && comp < 262144u && hdr + comp < rec.lit_bytes : bytes && comp < 262144u && hdr + comp + 1u < n) {
         rec.kind = kZsHuf;
         rec.body = hdr + comp + 1u;
+        rec.lit_kind = kZsHuf;
+        rec.lit_bytes = hdr + comp;
         rec.form = !four ? 0u : hdr - 2u;
         rec.hdr_bytes = hdr;
         rec.desc_bytes = bytes;
@@ -410,14 +449,40 @@ __global__ __launch_bounds__(256) void k_zstd_code(const uint8_t* __restrict__ s
   }
 }
 
+}  // namespace
+
+// one workgroup of four waves per block
+__global__ __launch_bounds__(256) void k_zstd_code(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ chunk_dst,
+                                                   const uint32_t* __restrict__ chunk_payload, uint32_t n_chunks,
+                                                   const uint32_t* __restrict__ blk_first, const uint32_t* __restrict__ chunk_state,
+                                                   ZsBlock* __restrict__ blocks, uint32_t* __restrict__ codes,
+                                                   uint8_t* __restrict__ descs) {
+  zs_code_body<false>(stream, chunk_dst, chunk_payload, n_chunks, blk_first, chunk_state, blocks, codes, descs, nullptr, nullptr, nullptr);
+}
+
+// the same behind the match search (cldn_hip_codec_set_zstd_matches): blocks with kept matches code their compacted literals
+__global__ __launch_bounds__(256) void k_zstd_code_lits(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ chunk_dst,
+                                                        const uint32_t* __restrict__ chunk_payload, uint32_t n_chunks,
+                                                        const uint32_t* __restrict__ blk_first, const uint32_t* __restrict__ chunk_state,
+                                                        ZsBlock* __restrict__ blocks, uint32_t* __restrict__ codes,
+                                                        uint8_t* __restrict__ descs, const ZsSeqPlan* __restrict__ plan,
+                                                        const uint32_t* __restrict__ sub_first, const uint8_t* __restrict__ lits) {
+  zs_code_body<true>(stream, chunk_dst, chunk_payload, n_chunks, blk_first, chunk_state, blocks, codes, descs, plan, sub_first, lits);
+}
+
 // one workgroup: positions of the blocks (one scan), then the chunks' prefixes and frame headers, sizes and stream offsets,
 // then every block's headers, tree description and jump table
-__global__ __launch_bounds__(1024) void k_zstd_offsets(const ZsBlock* __restrict__ blocks, const uint8_t* __restrict__ descs,
-                                                      const uint32_t* __restrict__ blk_first, const uint32_t* __restrict__ chunk_payload,
-                                                      uint32_t n_chunks, const uint32_t* __restrict__ cloud_first_chunk, uint32_t n_clouds,
-                                                      uint32_t* __restrict__ chunk_state, uint64_t* __restrict__ block_dst,
-                                                      uint32_t* __restrict__ chunk_sizes, uint64_t* __restrict__ stream_offsets,
-                                                      uint8_t* __restrict__ out, uint64_t out_capacity, uint32_t* __restrict__ status) {
+// SEQ: a block with sequences takes its size from the literals section and the exact bytes of its bit stream (info); one that
+// is not smaller than the block becomes Raw here, in the record too. It also gets its sequences-section header.
+namespace {
+template <bool SEQ>
+__device__ __forceinline__ void zs_offsets_body(ZsBlock* __restrict__ blocks, const uint8_t* __restrict__ descs,
+                                                const uint32_t* __restrict__ blk_first, const uint32_t* __restrict__ chunk_payload,
+                                                uint32_t n_chunks, const uint32_t* __restrict__ cloud_first_chunk, uint32_t n_clouds,
+                                                uint32_t* __restrict__ chunk_state, uint64_t* __restrict__ block_dst,
+                                                uint32_t* __restrict__ chunk_sizes, uint64_t* __restrict__ stream_offsets,
+                                                uint8_t* __restrict__ out, uint64_t out_capacity, uint32_t* __restrict__ status,
+                                                const ZsSeqInfo* __restrict__ info) {
   __shared__ unsigned long long wtot[16];
   const uint32_t tid = threadIdx.x;
   const uint32_t total_blocks = blk_first[n_chunks];
@@ -426,7 +491,20 @@ __global__ __launch_bounds__(1024) void k_zstd_offsets(const ZsBlock* __restrict
     const uint32_t b = base + tid;
     unsigned long long mine = 0ull;
     if (b < total_blocks) {
-      const ZsBlock r = blocks[b];
+      ZsBlock r = blocks[b];
+      if constexpr (SEQ) {
+        if (r.n_seq) {
+          const uint32_t body = r.lit_bytes + (r.n_seq < 128u ? 1u : 2u) + 1u + info[b].bytes;
+          if (body >= r.n) {
+            r.kind = kZsRaw;
+            r.n_seq = 0u;
+            r.body = r.n;
+          } else {
+            r.body = body;
+          }
+          blocks[b] = r;
+        }
+      }
       if (chunk_state[r.chunk] != kZsChunkBad) mine = 3ull + r.body + (blk_first[r.chunk] == b ? 13ull : 0ull);
     }
     const unsigned long long dst = block_running_scan(mine, wtot, total);
@@ -474,15 +552,33 @@ __global__ __launch_bounds__(1024) void k_zstd_offsets(const ZsBlock* __restrict
     o[2] = (uint8_t)(bh >> 16);
     if (r.kind != kZsHuf) continue;
     o += 3;
-    o[r.body - 1u] = 0u;  // the sequences section: "0 sequences"
+    if (SEQ && r.n_seq) {  // the sequences section: count, "Predefined tables"; the bit stream is k_zstd_seq_emit's
+      uint8_t* q = o + r.lit_bytes;
+      if (r.n_seq < 128u) {
+        q[0] = (uint8_t)r.n_seq;
+        q[1] = 0u;
+      } else {
+        q[0] = (uint8_t)((r.n_seq >> 8) + 0x80u);
+        q[1] = (uint8_t)r.n_seq;
+        q[2] = 0u;
+      }
+      if (r.lit_kind != kZsHuf) {  // Raw or RLE literals
+        const uint32_t hb = zs_raw_lit_header(r.n_lit);
+        const uint32_t v = r.lit_kind | (hb == 1u ? r.n_lit << 3 : ((hb == 2u ? 1u : 3u) << 2) | (r.n_lit << 4));
+        for (uint32_t k = 0; k < hb; ++k) o[k] = (uint8_t)(v >> (8u * k));
+        continue;
+      }
+    } else {
+      o[r.body - 1u] = 0u;  // the sequences section: "0 sequences"
+    }
     const uint32_t bits = r.form <= 1u ? 10u : r.form == 2u ? 14u : 18u;
-    const uint64_t lh = 2ull | ((uint64_t)r.form << 2) | ((uint64_t)r.n << 4) | ((uint64_t)r.comp << (4u + bits));
+    const uint64_t lh = 2ull | ((uint64_t)r.form << 2) | ((uint64_t)r.n_lit << 4) | ((uint64_t)r.comp << (4u + bits));
     for (uint32_t k = 0; k < r.hdr_bytes; ++k) o[k] = (uint8_t)(lh >> (8u * k));
     o += r.hdr_bytes;
     const uint8_t* d = descs + (size_t)b * kZsDescBytes;
     for (uint32_t k = 0; k < r.desc_bytes; ++k) o[k] = d[k];
     o += r.desc_bytes;
-    if (r.n >= kZsFourStreams) {
+    if (r.n_lit >= kZsFourStreams) {
 #pragma unroll
       for (uint32_t j = 0; j < 3u; ++j) {
         const uint32_t bytes = r.stream[j];  // (streams 1-3; the fourth takes the rest)
@@ -492,13 +588,39 @@ __global__ __launch_bounds__(1024) void k_zstd_offsets(const ZsBlock* __restrict
     }
   }
 }
+}  // namespace
+
+__global__ __launch_bounds__(1024) void k_zstd_offsets(const ZsBlock* __restrict__ blocks, const uint8_t* __restrict__ descs,
+                                                      const uint32_t* __restrict__ blk_first, const uint32_t* __restrict__ chunk_payload,
+                                                      uint32_t n_chunks, const uint32_t* __restrict__ cloud_first_chunk, uint32_t n_clouds,
+                                                      uint32_t* __restrict__ chunk_state, uint64_t* __restrict__ block_dst,
+                                                      uint32_t* __restrict__ chunk_sizes, uint64_t* __restrict__ stream_offsets,
+                                                      uint8_t* __restrict__ out, uint64_t out_capacity, uint32_t* __restrict__ status) {
+  zs_offsets_body<false>(const_cast<ZsBlock*>(blocks), descs, blk_first, chunk_payload, n_chunks, cloud_first_chunk, n_clouds, chunk_state,
+                         block_dst, chunk_sizes, stream_offsets, out, out_capacity, status, nullptr);
+}
+
+__global__ __launch_bounds__(1024) void k_zstd_offsets_seq(ZsBlock* __restrict__ blocks, const uint8_t* __restrict__ descs,
+                                                          const uint32_t* __restrict__ blk_first, const uint32_t* __restrict__ chunk_payload,
+                                                          uint32_t n_chunks, const uint32_t* __restrict__ cloud_first_chunk, uint32_t n_clouds,
+                                                          uint32_t* __restrict__ chunk_state, uint64_t* __restrict__ block_dst,
+                                                          uint32_t* __restrict__ chunk_sizes, uint64_t* __restrict__ stream_offsets,
+                                                          uint8_t* __restrict__ out, uint64_t out_capacity, uint32_t* __restrict__ status,
+                                                          const ZsSeqInfo* __restrict__ info) {
+  zs_offsets_body<true>(blocks, descs, blk_first, chunk_payload, n_chunks, cloud_first_chunk, n_clouds, chunk_state, block_dst,
+                        chunk_sizes, stream_offsets, out, out_capacity, status, info);
+}
 
 // workgroup 4 * b + j: stream j of block b (a Raw block: quarter j of its bytes)
-__global__ __launch_bounds__(256) void k_zstd_emit(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ chunk_dst,
-                                                   uint32_t n_chunks, const uint32_t* __restrict__ blk_first,
-                                                   const uint32_t* __restrict__ chunk_state, const ZsBlock* __restrict__ blocks,
-                                                   const uint32_t* __restrict__ codes, const uint64_t* __restrict__ block_dst,
-                                                   uint8_t* __restrict__ out) {
+// SEQ: the literals of a block with sequences are its compacted ones, Raw and RLE literals sections included
+namespace {
+template <bool SEQ>
+__device__ __forceinline__ void zs_emit_body(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ chunk_dst,
+                                             uint32_t n_chunks, const uint32_t* __restrict__ blk_first,
+                                             const uint32_t* __restrict__ chunk_state, const ZsBlock* __restrict__ blocks,
+                                             const uint32_t* __restrict__ codes, const uint64_t* __restrict__ block_dst,
+                                             uint8_t* __restrict__ out, const uint32_t* __restrict__ sub_first,
+                                             const uint8_t* __restrict__ lits) {
   __shared__ __attribute__((aligned(16))) uint32_t img[kZsImgBytes / 4u];
   __shared__ uint32_t tab[256];
   __shared__ uint32_t wtot[4];
@@ -508,7 +630,9 @@ __global__ __launch_bounds__(256) void k_zstd_emit(const uint8_t* __restrict__ s
     const uint32_t b = unit >> 2, j = unit & 3u;
     const ZsBlock r = blocks[b];
     if (chunk_state[r.chunk] != kZsChunkFits) continue;
-    const uint8_t* in = stream + chunk_dst[r.chunk] + 4u + r.off;
+    const bool matched = SEQ && r.n_seq != 0u;
+    const uint8_t* in = matched ? lits + (size_t)zs_first_sub(sub_first, blk_first, r.chunk, b) * kLzSubBytes
+                                : stream + chunk_dst[r.chunk] + 4u + r.off;
     uint8_t* o = out + block_dst[b] + (blk_first[r.chunk] == b ? 13u : 0u) + 3u;
     if (r.kind == kZsRle) {
       if (j == 0u && tid == 0u) o[0] = (uint8_t)r.rle;
@@ -520,10 +644,22 @@ __global__ __launch_bounds__(256) void k_zstd_emit(const uint8_t* __restrict__ s
       copy_bytes_16(in + s0, o + s0, s1 - s0, tid, 256u);
       continue;
     }
-    const bool four = r.n >= kZsFourStreams;
+    if (matched && r.lit_kind != kZsHuf) {
+      const uint32_t hb = zs_raw_lit_header(r.n_lit);
+      if (r.lit_kind == kZsRle) {
+        if (j == 0u && tid == 0u) o[hb] = (uint8_t)r.rle;
+      } else {
+        const uint32_t q = ((r.n_lit + 63u) / 64u) * 16u;
+        const uint32_t s0 = min(r.n_lit, j * q), s1 = min(r.n_lit, s0 + q);
+        copy_bytes_16(in + s0, o + hb + s0, s1 - s0, tid, 256u);
+      }
+      continue;
+    }
+    const uint32_t n_lit = r.n_lit;
+    const bool four = n_lit >= kZsFourStreams;
     if (!four && j) continue;
-    const uint32_t seg = four ? (r.n + 3u) / 4u : r.n;
-    const uint32_t L = min(r.n, (j + 1u) * seg) - j * seg;  // symbols of the stream
+    const uint32_t seg = four ? (n_lit + 3u) / 4u : n_lit;
+    const uint32_t L = min(n_lit, (j + 1u) * seg) - j * seg;  // symbols of the stream
     const uint8_t* sym = in + j * seg;
     uint32_t before = r.hdr_bytes + r.desc_bytes + (four ? 6u : 0u);
     uint32_t sbytes = 0u;
@@ -615,6 +751,24 @@ __global__ __launch_bounds__(256) void k_zstd_emit(const uint8_t* __restrict__ s
     }
   }
 }
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_zstd_emit(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ chunk_dst,
+                                                   uint32_t n_chunks, const uint32_t* __restrict__ blk_first,
+                                                   const uint32_t* __restrict__ chunk_state, const ZsBlock* __restrict__ blocks,
+                                                   const uint32_t* __restrict__ codes, const uint64_t* __restrict__ block_dst,
+                                                   uint8_t* __restrict__ out) {
+  zs_emit_body<false>(stream, chunk_dst, n_chunks, blk_first, chunk_state, blocks, codes, block_dst, out, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_zstd_emit_lits(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ chunk_dst,
+                                                        uint32_t n_chunks, const uint32_t* __restrict__ blk_first,
+                                                        const uint32_t* __restrict__ chunk_state, const ZsBlock* __restrict__ blocks,
+                                                        const uint32_t* __restrict__ codes, const uint64_t* __restrict__ block_dst,
+                                                        uint8_t* __restrict__ out, const uint32_t* __restrict__ sub_first,
+                                                        const uint8_t* __restrict__ lits) {
+  zs_emit_body<true>(stream, chunk_dst, n_chunks, blk_first, chunk_state, blocks, codes, block_dst, out, sub_first, lits);
+}
 
 int zstd_launch(const ZstdLaunch& L) {
   const Stage2Io& io = L.io;
@@ -624,6 +778,22 @@ int zstd_launch(const ZstdLaunch& L) {
   hipLaunchKernelGGL(k_zstd_plan, dim3(1), dim3(1024), 0, io.stream, io.chunk_payload, io.chunk_dst, io.n_chunks, io.stage1_capacity,
                      L.blk_first, L.chunk_state, max_blocks, io.status);
   if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_zstd_plan");
+  if (L.seq) {  // cldn_hip_codec_set_zstd_matches: the match search, the blocks' sequences and literals, and the kernels below told of them
+    const ZstdSeqLaunch& S = *L.seq;
+    int rc;
+    if ((rc = zstd_seq_launch_front(L, max_blocks)) != CLDN_HIP_OK) return rc;
+    hipLaunchKernelGGL(k_zstd_code_lits, dim3(max_blocks), dim3(256), 0, io.stream, io.stage1, io.chunk_dst, io.chunk_payload, io.n_chunks,
+                       L.blk_first, L.chunk_state, L.blocks, L.codes, L.descs, S.plan, S.sub_first, S.lits);
+    if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_zstd_code_lits");
+    hipLaunchKernelGGL(k_zstd_offsets_seq, dim3(1), dim3(1024), 0, io.stream, L.blocks, L.descs, L.blk_first, io.chunk_payload, io.n_chunks,
+                       io.cloud_first_chunk, io.n_clouds, L.chunk_state, L.block_dst, io.chunk_sizes, io.stream_offsets, io.out,
+                       io.out_capacity, io.status, S.info);
+    if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_zstd_offsets_seq");
+    hipLaunchKernelGGL(k_zstd_emit_lits, dim3(4u * max_blocks), dim3(256), 0, io.stream, io.stage1, io.chunk_dst, io.n_chunks, L.blk_first,
+                       L.chunk_state, L.blocks, L.codes, L.block_dst, io.out, S.sub_first, S.lits);
+    if ((e = hipGetLastError()) != hipSuccess) return launch_fail(e, "k_zstd_emit_lits");
+    return zstd_seq_launch_emit(L, max_blocks);
+  }
   // one workgroup per block, at most `max_blocks` of them: workgroups beyond the real number find nothing to do
   hipLaunchKernelGGL(k_zstd_code, dim3(max_blocks), dim3(256), 0, io.stream, io.stage1, io.chunk_dst, io.chunk_payload, io.n_chunks,
                      L.blk_first, L.chunk_state, L.blocks, L.codes, L.descs);

@@ -124,6 +124,10 @@ def lib() -> C.CDLL:
     L.cldn_hip_codec_set_zstd_sequences.restype = C.c_int
     L.cldn_hip_codec_zstd_sequences.argtypes = [vp]
     L.cldn_hip_codec_zstd_sequences.restype = C.c_int
+    L.cldn_hip_codec_set_zstd_matches.argtypes = [vp, C.c_int]
+    L.cldn_hip_codec_set_zstd_matches.restype = C.c_int
+    L.cldn_hip_codec_zstd_matches.argtypes = [vp]
+    L.cldn_hip_codec_zstd_matches.restype = C.c_int
     L.cldn_hip_codec_decode_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cldn_hip_codec_decode_stats.restype = C.c_int
     L.cldn_hip_debug_decode_trace.restype = C.c_int
@@ -422,6 +426,14 @@ class Codec:
 
     def zstd_sequences(self) -> bool:
         return bool(lib().cldn_hip_codec_zstd_sequences(self._h))
+
+    def set_zstd_matches(self, on: bool):
+        """cldn_hip_codec_set_zstd_matches: True = the ZSTD writer (set_stage2(STAGE2_ZSTD)) turns matches of the device's match
+        search into sequences (default off: literal-only blocks). See include/cloudini_hip.h for when it pays."""
+        _check(lib().cldn_hip_codec_set_zstd_matches(self._h, 1 if on else 0))
+
+    def zstd_matches(self) -> bool:
+        return bool(lib().cldn_hip_codec_zstd_matches(self._h))
 
     def set_decode_fill(self, zero: bool):
         """cldn_hip_codec_set_decode_fill: True = bytes no field covers may be written as 0 (no round trip of a host buffer)."""

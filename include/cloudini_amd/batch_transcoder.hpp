@@ -186,6 +186,10 @@ struct TranscodeOptions {
   // `estimate`'s estimate_actual_bytes still adds up what was written. Other compressions ignore the option. Not available
   // together with `decode`.
   bool device_zstd = false;
+  // ... with sequences from the device's match search (cldn_hip_codec_set_zstd_matches): blocks with a match of 12 bytes or more
+  // carry a sequences section. It brings the schemas named above to within 6 - 19 % of libzstd level 1 and costs about another
+  // literal-only stage of GPU time. Needs `device_zstd`; not available together with `decode`.
+  bool device_zstd_matches = false;
   // Test hook (tests/cpp/transcoder_order.cpp, runs without a GPU): when set, `test_workers` stage threads call it instead of
   // the GPU stage and stage 2 passes the batch on untouched -- what remains is the pipeline itself: batches handed to
   // whichever stage is free, the writer putting them back into input order, an error on any stage stopping all of them.

@@ -183,6 +183,12 @@ int cldn_amd_set_device_zstd_sequences(int on);
  * variable. Both return the value in effect (0, 1). */
 int cldn_amd_device_zstd(void);
 int cldn_amd_set_device_zstd(int on);
+/* ... with sequences from the device's match search (cldn_hip_codec_set_zstd_matches, include/cloudini_hip.h): blocks that hold
+ * a match of 12 bytes or more carry a sequences section, which brings layouts whose bytes repeat (a ring field, lossless float64
+ * stamps) from about twice libzstd level 1 to within 6 - 19 % of it and leaves token streams as they are. It has effect only
+ * while cldn_amd_set_device_zstd is on. Off by default, no environment variable. Both return the value in effect (0, 1). */
+int cldn_amd_device_zstd_matches(void);
+int cldn_amd_set_device_zstd_matches(int on);
 
 #ifdef __cplusplus
 }

@@ -187,6 +187,8 @@ int cldn_hip_encode_stage1_gather(cldn_hip_codec_t* codec, const void* const* cl
  * libzstd's bytes, or its ratio where ZSTD finds matches: the writer searches none (cloudini_amd/csrc/zstd_kernels.hip,
  * restated serially in tests/zstd_lit_model.py). On the token streams of lossy stage 1 that costs about a tenth of a percent
  * up to a percent against level 1; lossless float64 streams can come out up to about twice as large.
+ * cldn_hip_codec_set_zstd_matches (below) adds a match search and sequences sections for such streams; all of this paragraph
+ * describes the mode with that switch off, and what it says about validity, sizes' bound and the reports holds with it on.
  * There is no device decoder for this mode: behind such a call cldn_hip_audit_last_encode decodes, and
  * cldn_hip_stream_hist_last_encode counts, the stage-1 streams the frames were made from (they stay in the codec's workspace),
  * so both report what they report behind a CLDN_HIP_STAGE2_NONE call and the histogram still composes with
@@ -610,6 +612,21 @@ int cldn_hip_codec_set_decode_fill(cldn_hip_codec_t* codec, int fill);
  * tens of clouds, off for single frames (a lone 1 M-point message takes 16.4 ms against 1.5 ms on the host pool). */
 int cldn_hip_codec_set_zstd_sequences(cldn_hip_codec_t* codec, int on);
 int cldn_hip_codec_zstd_sequences(const cldn_hip_codec_t* codec);
+
+/* ZSTD frames with matches from the device writer (zstd_seq_kernels.hip), on top of cldn_hip_codec_set_stage2(codec,
+ * CLDN_HIP_STAGE2_ZSTD). Default 0: every call writes the literal-only frames described above, with the same kernels as before
+ * this switch existed. With 1 -- it has effect only while stage 2 is CLDN_HIP_STAGE2_ZSTD -- the LZ4 route's match search
+ * (k_lz4_match, 8 KiB sub-ranges) runs over the payloads, and a 128 KiB block that has a match of 12 bytes or more becomes a
+ * Compressed block with a sequences section (Predefined tables, no repeat offsets) over Huffman-coded, Raw or RLE literals; a
+ * block without one, and a block the section does not make smaller, is written as without the switch. Any ZSTD decoder reads
+ * the frames; this library's device decoder takes them with cldn_hip_codec_set_zstd_sequences(codec, 1).
+ * cldn_hip_stage2_bound is unchanged (a frame never exceeds payload + 9 + 3 per block), the chunk-table call keeps refusing the
+ * mode, and the frames are restated byte for byte in tests/zstd_match_model.py. Cost while it is on: device workspace of
+ * about 4.5 bytes per payload byte (match lists, sequence records and bits, compacted literals), sized like the LZ4 route's
+ * lists. Sizes and times: DESIGN.md 4j. Recommendation: off for token streams (XYZI, Velodyne: nothing to gain), on for
+ * layouts whose bytes repeat (lossless float64 stamps, ring / channel fields that stage 1 copies). */
+int cldn_hip_codec_set_zstd_matches(cldn_hip_codec_t* codec, int on);
+int cldn_hip_codec_zstd_matches(const cldn_hip_codec_t* codec);
 
 /* Which kernels the last cldn_hip_decode_stage1 call used, in chunks (synchronises):
  *   stats[0] regular stream by the parallel decoder      stats[1] V5 sections by the parallel decoder

@@ -100,7 +100,9 @@ int main(int argc, char** argv) {
                  "  --estimate                             with --sweep: estimated ZSTD bytes per field and rung (files unchanged)\n"
                  "  --device-zstd                          with --compression zstd: the GPU writes the ZSTD frames (literal-only blocks:\n"
                  "                                        valid frames every ZSTD decoder reads, not libzstd's bytes); other compressions ignore it\n"
-                 "  --sweep, --modes and --device-zstd are not available with --decode\n", argv[0]);
+                 "  --device-zstd-matches                  with --device-zstd: blocks with a match of 12 bytes or more carry sequences (layouts\n"
+                 "                                        whose bytes repeat come within 6-19 %% of libzstd level 1; token streams stay as they are)\n"
+                 "  --sweep, --modes, --device-zstd and --device-zstd-matches are not available with --decode\n", argv[0]);
     return 2;
   }
   cloudini_amd::TranscodeOptions opt;
@@ -140,6 +142,7 @@ int main(int argc, char** argv) {
     }
     else if (a == "--estimate") opt.estimate = true;
     else if (a == "--device-zstd") opt.device_zstd = true;
+    else if (a == "--device-zstd-matches") opt.device_zstd_matches = true;
     else if (a == "--modes" && i + 1 < argc) {
       const std::string v = argv[++i];
       if (v != "report" && v != "best") {
@@ -175,6 +178,14 @@ int main(int argc, char** argv) {
   }
   if (opt.decode && opt.device_zstd) {
     std::fprintf(stderr, "--device-zstd is not available with --decode\n");
+    return 2;
+  }
+  if (opt.decode && opt.device_zstd_matches) {
+    std::fprintf(stderr, "--device-zstd-matches is not available with --decode\n");
+    return 2;
+  }
+  if (opt.device_zstd_matches && !opt.device_zstd) {
+    std::fprintf(stderr, "--device-zstd-matches needs --device-zstd\n");
     return 2;
   }
   if (opt.decode && opt.modes != cloudini_amd::TranscodeOptions::Modes::Off) {

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Device-side ZSTD (cloudini_amd/csrc/zstd_kernels.hip: frames of literal-only blocks) on device-resident batches:
 32 x 1 M lidar_xyzi and 64 x 130048 velodyne_xyzir. One encode_device call per measurement, the modes interleaved
-(stage 1 only, device ZSTD, device LZ4, device LZ4 FAST, round after round); median [min .. max] of the repetitions. The
-stage-2 part of a mode is its call minus the stage-1-only call of the same round. Next to it what the host route has to do
+(stage 1 only, device ZSTD, device ZSTD with matches -- cldn_hip_codec_set_zstd_matches, zstd_seq_kernels.hip --, device LZ4,
+device LZ4 FAST, round after round); median [min .. max] of the repetitions. The stage-2 part of a mode is its call minus the
+stage-1-only call of the same round; the mode with matches is also held against the literal-only mode of the same round. Next to it what the host route has to do
 for the same chunks once they are in host memory: ZSTD_compress(level 1) per chunk on 1 and 16 threads (the stage-2 pool's
 work alone, no copies), and the sizes of all routes side by side.
 
-`zstdbench.py once` runs one device-ZSTD call per batch and nothing else (for a kernel trace)."""
+`zstdbench.py once` runs one device-ZSTD call per batch and nothing else (for a kernel trace); `zstdbench.py once-matches` the
+same with the matches switch on."""
 import ctypes as C
 import os, sys, time
 from concurrent.futures import ThreadPoolExecutor
@@ -18,8 +20,9 @@ from cloudini_amd import native, synth
 
 dev = torch.device("cuda", 0)
 REPS = int(os.environ.get("ZSTDBENCH_REPS", "12")) if len(sys.argv) < 3 else int(sys.argv[2])
-once = len(sys.argv) > 1 and sys.argv[1] == "once"
-MODES = [(0, "stage 1 only"), (3, "device ZSTD"), (1, "device LZ4"), (2, "device LZ4 FAST")]
+once = len(sys.argv) > 1 and sys.argv[1] in ("once", "once-matches")
+ZSTD_MATCHES = 3 | 0x100   # a key of this script: stage 2 = 3 with set_zstd_matches(True)
+MODES = [(0, "stage 1 only"), (3, "device ZSTD"), (ZSTD_MATCHES, "ZSTD + matches"), (1, "device LZ4"), (2, "device LZ4 FAST")]
 
 z = C.CDLL("libzstd.so.1")
 z.ZSTD_compress.restype = C.c_size_t
@@ -41,22 +44,24 @@ for wl, gen, n_clouds in (("lidar_xyzi 1M", lambda k: synth.lidar_xyzi(1_000_000
     codec = native.Codec(plan)
     d_in = torch.from_numpy(np.concatenate([distinct[k % 4][1] for k in range(n_clouds)])).to(dev)
     cp = np.full(n_clouds, pts, dtype=np.uint64)
-    cap = max(plan.stage2_bound(pts, m) for m, _ in MODES) * n_clouds
+    cap = max(plan.stage2_bound(pts, m & 0xff) for m, _ in MODES) * n_clouds
     d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
     d_off = torch.zeros(n_clouds + 1, dtype=torch.int64, device=dev)
 
     def call(mode):
-        codec.set_stage2(mode)
+        codec.set_stage2(mode & 0xff)
+        codec.set_zstd_matches(mode == ZSTD_MATCHES)
         t0 = time.perf_counter()
         codec.encode_device(d_in.data_ptr(), cp, d_out.data_ptr(), cap, d_off.data_ptr())
         codec.synchronize()
         return time.perf_counter() - t0
 
     if once:
-        call(3)
-        call(3)
+        which = ZSTD_MATCHES if sys.argv[1] == "once-matches" else 3
+        call(which)
+        call(which)
         codec.status()
-        print(f"{wl} x{n_clouds}: two device-ZSTD calls, {int(d_off.cpu()[-1])} bytes")
+        print(f"{wl} x{n_clouds}: two device-ZSTD calls{' with matches' if which != 3 else ''}, {int(d_off.cpu()[-1])} bytes")
         codec.close()
         continue
     size = {}
@@ -109,4 +114,8 @@ for wl, gen, n_clouds in (("lidar_xyzi 1M", lambda k: synth.lidar_xyzi(1_000_000
               f"{payload / np.median(t) / 1e9:.2f} GB/s of payload")
     print(f"  size: device ZSTD / host ZSTD = {size[3] / host_bytes:.4f}; device ZSTD part / host 16 threads = "
           f"{np.median(np.array(times[3]) - base) / np.median(host[16]):.4f}")
+    lit_part, seq_part = np.array(times[3]) - base, np.array(times[ZSTD_MATCHES]) - base
+    print(f"  with matches: size / host ZSTD = {size[ZSTD_MATCHES] / host_bytes:.4f}, / literal-only = {size[ZSTD_MATCHES] / size[3]:.4f}; "
+          f"stage-2 part / literal-only part of the same round = {np.median(seq_part / lit_part):.3f} "
+          f"[{(seq_part / lit_part).min():.3f} .. {(seq_part / lit_part).max():.3f}]")
     codec.close()
