@@ -115,8 +115,11 @@ __device__ __forceinline__ void load8(const RawT* col, uint32_t i0, uint32_t n, 
 
 // ---------------------------------------------------------------------------------------------------------
 // Mode probe (analyzeAdaptiveIntField + selectBestAdaptiveIntMode, src/v5_codec.cpp:258-316, :381-412) over the
-// first W <= 4096 values of a cloud: thread t owns values [4t, 4t+4), every size is thread-local work plus one
-// block-wide scan / reduction.
+// first W <= 4096 values of a cloud: thread t of T owns the 4096 / T values [VPT t, VPT t + VPT) -- 4 of them in
+// k_probe_fast and k_wide_probe (1024 threads, waves of 256 values), 16 in the probe workgroups of k_encode_fused (256
+// threads, waves of 1024 values). Every size is thread-local work plus one block-wide scan / reduction. The four sizes
+// stay in the workgroup: only the argmin (strict '<' in mode order) is written, so an error of one byte in a size shows
+// only where two sizes lie within a byte of each other (tests/probe_tie_cases.py is a grid of such columns).
 // ---------------------------------------------------------------------------------------------------------
 
 template <int T>
@@ -280,7 +283,7 @@ __device__ __forceinline__ uint8_t probe_mode(const RawT* col, uint32_t n, uint3
   return probe_mode_t<RawT, kS2Threads>([&](uint32_t i) { return col[i]; }, n, type, smem, kProbeSlots, wtot);
 }
 
-// grid = (n_clouds, n_adaptive). Exact for every window (the general probe kernel is only the A/B reference).
+// grid = (n_clouds, n_adaptive). Exact for every window.
 __global__ __launch_bounds__(kS2Threads) void k_probe_fast(const DevPlan plan, const ChunkDesc* __restrict__ chunks,
                                                            const uint32_t* __restrict__ cloud_first_chunk,
                                                            const ColumnPtrs cols, uint8_t* __restrict__ modes) {
