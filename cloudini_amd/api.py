@@ -88,6 +88,9 @@ def lib() -> C.CDLL:
                                                      C.c_uint64]
     L.cldn_amd_transcode_directory.restype = C.c_int64
     L.cldn_amd_transcode_directory.argtypes = [C.c_char_p, C.c_char_p, C.c_float, C.c_uint8, C.c_int, C.c_uint32, C.POINTER(C.c_double)]
+    L.cldn_amd_decode_directory_stage2.restype = C.c_int64
+    L.cldn_amd_decode_directory_stage2.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_int32), C.c_uint32, C.c_int,
+                                                   C.POINTER(C.c_double), C.c_char_p, C.c_uint64]
     L.cldn_amd_decode_directory.restype = C.c_int64
     L.cldn_amd_decode_directory.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_double)]
     L.cldn_amd_stage2_threads.restype = C.c_uint32
@@ -324,14 +327,21 @@ def transcode_directory(in_dir: str, out_dir: str, resolution: float = 0.001, co
     return out
 
 
-def decode_directory(in_dir: str, out_dir: str, batch_messages: int = 64, devices=None) -> dict:
+def decode_directory(in_dir: str, out_dir: str, batch_messages: int = 64, devices=None, device_stage2: bool = False) -> dict:
     """The way back: every CDR CompressedPointCloud2 file of in_dir -> PointCloud2 file of the same name in out_dir
-    (batched GPU decode). Returns the statistics."""
+    (batched GPU decode). Returns the statistics. device_stage2 (TranscodeOptions::device_stage2_decode): LZ4 and ZSTD stage 2
+    is undone on the device too -- the same files; device_stage2_chunks, host_stage2_chunks and device_stage2_retries tell
+    what happened (all 0 without the option)."""
+    import json
     st = (C.c_double * 8)()
     dv, nd = _device_list(devices)
-    _check(lib().cldn_amd_decode_directory_on(in_dir.encode(), out_dir.encode(), batch_messages, dv, nd, st))
+    text = C.create_string_buffer(1 << 10)
+    _check(lib().cldn_amd_decode_directory_stage2(in_dir.encode(), out_dir.encode(), batch_messages, dv, nd, 1 if device_stage2 else 0,
+                                                  st, text, len(text)))
     keys = ("messages", "points", "input_bytes", "output_bytes", "gpu_batches", "seconds_total", "seconds_gpu", "seconds_stage2")
-    return dict(zip(keys, [float(x) for x in st]))
+    out = dict(zip(keys, [float(x) for x in st]))
+    out.update(json.loads(text.value.decode()))
+    return out
 
 
 def MaxCompressedSize(info, points_count: int, include_header: bool = True) -> int:

@@ -94,7 +94,7 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     if not srcs:
         return ""
     deps = srcs + _sources(host_dir, (".hpp", ".h")) + _sources(os.path.join(ROOT, "include"), (".h", ".hpp")) + \
-        [HIP_SO, os.path.join(CSRC, "zstd_decode_walk.h")]
+        [HIP_SO, os.path.join(CSRC, "zstd_decode_walk.h"), os.path.join(CSRC, "stage2_decode_plan.h")]
     if force or _newer(HOST_SO, deps):
         # default visibility: the C++ API of include/cloudini_lib/*.hpp is what callers link against
         cmd = ["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall",

@@ -200,6 +200,7 @@ struct cldn_hip_codec {
   // LZ4 blocks back into bytes (cldn_hip_decode_lz4 / cldn_hip_lz4_decompress): one worst-case slot per chunk, the offset tables
   DevBuf d_lzd_slots, d_lzd_tables;
   DevBuf d_zsd_ws;  // ZSTD decode (zstd_decode.hip): block records, weights, frame tables
+  DevBuf d_s2_gather;  // cldn_hip_decode_lz4_gather / _zstd_gather: [expanded sizes u32 | verdicts u32] per chunk
   DevBuf d_finrec;            // k_finish look-back records (rec, rec2), cleared only when (re)allocated
   int decode_fill = CLDN_HIP_FILL_KEEP;  // cldn_hip_codec_set_decode_fill
   int zstd_sequences = 0;                // cldn_hip_codec_set_zstd_sequences
@@ -661,7 +662,7 @@ void cldn_hip_codec_destroy(cldn_hip_codec_t* c) {
   (void)guard.enter(c->device);
   (void)hipStreamSynchronize(c->stream);
   DevBuf* bufs[] = {&c->d_in, &c->d_out, &c->d_slots, &c->d_chunks, &c->d_cloud_first, &c->d_finrec, &c->d_dec_rec, &c->d_dec_bits, &c->d_dec_secs, &c->d_s1, &c->d_s1_offsets,
-                    &c->d_lz_matches, &c->d_zs_seq, &c->d_stage2_ws, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables, &c->d_zsd_ws,
+                    &c->d_lz_matches, &c->d_zs_seq, &c->d_stage2_ws, &c->d_payload2, &c->d_dst2, &c->d_dec_split, &c->d_lzd_slots, &c->d_lzd_tables, &c->d_zsd_ws, &c->d_s2_gather,
                     &c->d_payload, &c->d_dst, &c->d_offsets, &c->d_modes, &c->d_status, &c->d_dec_meta, &c->d_pre_ptrs, &c->d_dec_cols[0], &c->d_dec_cols[1], &c->d_dec_cols[2], &c->d_dec_cols[3], &c->d_dec_cols[4], &c->d_dec_cols[5], &c->d_dec_cols[6], &c->d_dec_cols[7],
                     &c->d_viz_keys, &c->d_viz_slot, &c->d_viz_blocks, &c->d_viz_bits, &c->d_viz_tables, &c->d_viz_kept, &c->d_viz_out,
                     &c->d_pieces, &c->d_audit, &c->d_audit_tab, &c->d_audit_rep};
@@ -1841,11 +1842,19 @@ static int decode_verdict(uint32_t st) {
   return CLDN_HIP_OK;
 }
 
+// cldn_hip_decode_lz4_gather / _zstd_gather: what they add to the contiguous calls (all HOST memory)
+struct DecodeGather {
+  const void* const* body_ptrs;    // [n_clouds]: `streams` of the call is NULL, stream_offsets the prefix sums of the bodies' sizes
+  const void* const* expanded;     // [n_chunks] or NULL
+  const uint32_t* expanded_sizes;  // [n_chunks] or NULL
+  uint32_t* verdicts;              // [n_chunks] or NULL
+};
+
 // the framed decode calls. stage2 = CLDN_HIP_STAGE2_LZ4: every chunk of `streams` is [u32 block size][LZ4 block]
 // (cldn_hip_decode_lz4); CLDN_HIP_STAGE2_ZSTD: [u32 frame size][ZSTD frame] (cldn_hip_decode_zstd)
 static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                          const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
-                         void* points_out, uint64_t out_capacity, int out_loc, int stage2);
+                         void* points_out, uint64_t out_capacity, int out_loc, int stage2, const struct DecodeGather* gather = nullptr);
 
 int cldn_hip_decode_stage1_sized(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                                  const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
@@ -1868,7 +1877,7 @@ int cldn_hip_decode_zstd(cldn_hip_codec_t* c, const void* streams, int streams_l
 
 static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                          const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, int chunk_sizes_loc,
-                         void* points_out, uint64_t out_capacity, int out_loc, int stage2) {
+                         void* points_out, uint64_t out_capacity, int out_loc, int stage2, const DecodeGather* gather) {
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   c->enc.drop();
   if (chunk_sizes && chunk_sizes_loc != CLDN_HIP_HOST && chunk_sizes_loc != CLDN_HIP_DEVICE)
@@ -1894,7 +1903,7 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   if (out_capacity < need) return fail(CLDN_HIP_ERR_CAPACITY, "Output buffer is too small to hold the decoded data");
   if (need && !points_out) return fail(CLDN_HIP_ERR_ARG, "points_out is NULL");
   const uint64_t stream_bytes = stream_offsets[n_clouds];
-  if (stream_bytes && !streams) return fail(CLDN_HIP_ERR_ARG, "streams is NULL");
+  if (stream_bytes && !streams && !gather) return fail(CLDN_HIP_ERR_ARG, "streams is NULL");
 
   int rc;
   if ((rc = c->d_status.ensure(256)) != CLDN_HIP_OK) return rc;
@@ -1952,9 +1961,15 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   const uint8_t* d_streams = (const uint8_t*)streams + base_off;
   if (streams_loc == CLDN_HIP_HOST) {
     if ((rc = c->d_in.ensure((size_t)std::max<uint64_t>(1, stream_bytes - base_off))) != CLDN_HIP_OK) return rc;
-    if (stream_bytes > base_off)
+    if (gather) {  // every body from where it lies to its place: no gathering copy on the host
+      for (uint32_t k = 0; k < n_clouds; ++k)
+        if (stream_offsets[k + 1] > stream_offsets[k])
+          HIP_TRY(hipMemcpyAsync((uint8_t*)c->d_in.p + (stream_offsets[k] - base_off), gather->body_ptrs[k],
+                                 (size_t)(stream_offsets[k + 1] - stream_offsets[k]), hipMemcpyHostToDevice, c->stream));
+    } else if (stream_bytes > base_off) {
       HIP_TRY(hipMemcpyAsync(c->d_in.p, (const uint8_t*)streams + base_off, (size_t)(stream_bytes - base_off),
                              hipMemcpyHostToDevice, c->stream));
+    }
     d_streams = (const uint8_t*)c->d_in.p;
   }
   uint8_t* d_outp = (uint8_t*)points_out;
@@ -2057,6 +2072,31 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
       Z.capacity = (uint32_t)capacity;
       L.zstd = &Z;
     }
+    if (gather) {
+      // expanded chunks: their payloads go up into their slots now (no kernel of the call writes an expanded chunk's slot),
+      // their sizes into the table k_stage2_hold_expanded / _place_expanded read; the verdicts lie behind it
+      if ((rc = c->d_s2_gather.ensure((size_t)n_chunks * 8u)) != CLDN_HIP_OK) return rc;
+      uint32_t* const d_exp = (uint32_t*)c->d_s2_gather.p;
+      const uint32_t gslot = c->dec_stage_next++ % (uint32_t)cldn_hip_codec::kDecStageRing;
+      PinnedBuf& gstage = c->h_dec_stage[gslot];
+      if (c->dec_stage_ev[gslot]) HIP_TRY(hipEventSynchronize(c->dec_stage_ev[gslot]));  // its last upload has left the buffer
+      else HIP_TRY(hipEventCreateWithFlags(&c->dec_stage_ev[gslot], hipEventDisableTiming));
+      if ((rc = gstage.ensure((size_t)n_chunks * 4u)) != CLDN_HIP_OK) return rc;
+      uint32_t* const h_exp = (uint32_t*)gstage.p;
+      for (uint32_t k = 0; k < n_chunks; ++k) {
+        const bool given = gather->expanded && gather->expanded[k];
+        h_exp[k] = given ? gather->expanded_sizes[k] : kNotExpanded;
+        if (given && h_exp[k] > capacity)
+          return fail(CLDN_HIP_ERR_ARG, "expanded chunk %u has %u bytes: more than a slot's %llu", k, h_exp[k], (unsigned long long)capacity);
+      }
+      HIP_TRY(hipMemcpyAsync(d_exp, h_exp, (size_t)n_chunks * 4u, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipEventRecord(c->dec_stage_ev[gslot], c->stream));
+      for (uint32_t k = 0; k < n_chunks; ++k)
+        if (h_exp[k] != kNotExpanded && h_exp[k] != 0u)
+          HIP_TRY(hipMemcpyAsync(L.lz4_slots + (uint64_t)k * stride, gather->expanded[k], h_exp[k], hipMemcpyHostToDevice, c->stream));
+      L.expanded_sizes = d_exp;
+      L.verdicts = d_exp + n_chunks;
+    }
   }
   if (plan.varint_and_raw && n_chunks) {  // one bit per stream byte + a word per chunk (k_mark_token_ends)
     if ((rc = c->d_dec_bits.ensure((size_t)(decoder_stream_bytes / 8u) + (size_t)n_chunks * 4u + 256u)) != CLDN_HIP_OK) return rc;
@@ -2114,13 +2154,45 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
     c->dec_stats_chunks = n_chunks;
   }
 
-  if (out_loc == CLDN_HIP_DEVICE) return CLDN_HIP_OK;
+  if (out_loc == CLDN_HIP_DEVICE && !gather) return CLDN_HIP_OK;
   uint32_t st = 0;
   HIP_TRY(hipMemcpyAsync(&st, c->d_status.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+  if (gather && gather->verdicts && L.verdicts)  // (in front of the verdict of the call: a caller that retries reads them)
+    HIP_TRY(hipMemcpyAsync(gather->verdicts, L.verdicts, (size_t)n_chunks * 4u, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if ((rc = decode_verdict(st)) != CLDN_HIP_OK) return rc;
-  if (need) HIP_TRY(hipMemcpy(points_out, d_outp, (size_t)need, hipMemcpyDeviceToHost));
+  if (need && out_loc == CLDN_HIP_HOST) HIP_TRY(hipMemcpy(points_out, d_outp, (size_t)need, hipMemcpyDeviceToHost));
   return CLDN_HIP_OK;
+}
+
+static int decode_gather(cldn_hip_codec_t* c, const void* const* body_ptrs, const uint64_t* body_sizes, const uint64_t* cloud_points,
+                         uint32_t n_clouds, const uint32_t* chunk_sizes, const void* const* expanded, const uint32_t* expanded_sizes,
+                         uint32_t* verdicts, void* points_out, uint64_t out_capacity, int out_loc, int stage2) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (n_clouds && (!body_ptrs || !body_sizes || !cloud_points)) return fail(CLDN_HIP_ERR_ARG, "NULL body_ptrs / body_sizes / cloud_points");
+  if ((expanded != nullptr) != (expanded_sizes != nullptr)) return fail(CLDN_HIP_ERR_ARG, "expanded and expanded_sizes go together");
+  std::vector<uint64_t> offsets((size_t)n_clouds + 1, 0);
+  for (uint32_t k = 0; k < n_clouds; ++k) {
+    if (body_sizes[k] && !body_ptrs[k]) return fail(CLDN_HIP_ERR_ARG, "body %u is NULL", k);
+    if (__builtin_add_overflow(offsets[k], body_sizes[k], &offsets[k + 1])) return fail(CLDN_HIP_ERR_ARG, "batch too large");
+  }
+  const DecodeGather G = {body_ptrs, expanded, expanded_sizes, verdicts};
+  return decode_framed(c, nullptr, CLDN_HIP_HOST, offsets.data(), cloud_points, n_clouds, chunk_sizes, CLDN_HIP_HOST, points_out,
+                       out_capacity, out_loc, stage2, &G);
+}
+
+int cldn_hip_decode_lz4_gather(cldn_hip_codec_t* c, const void* const* body_ptrs, const uint64_t* body_sizes, const uint64_t* cloud_points,
+                               uint32_t n_clouds, const uint32_t* chunk_sizes, const void* const* expanded, const uint32_t* expanded_sizes,
+                               uint32_t* verdicts, void* points_out, uint64_t out_capacity, int out_loc) {
+  return decode_gather(c, body_ptrs, body_sizes, cloud_points, n_clouds, chunk_sizes, expanded, expanded_sizes, verdicts, points_out,
+                       out_capacity, out_loc, CLDN_HIP_STAGE2_LZ4);
+}
+
+int cldn_hip_decode_zstd_gather(cldn_hip_codec_t* c, const void* const* body_ptrs, const uint64_t* body_sizes, const uint64_t* cloud_points,
+                                uint32_t n_clouds, const uint32_t* chunk_sizes, const void* const* expanded, const uint32_t* expanded_sizes,
+                                uint32_t* verdicts, void* points_out, uint64_t out_capacity, int out_loc) {
+  return decode_gather(c, body_ptrs, body_sizes, cloud_points, n_clouds, chunk_sizes, expanded, expanded_sizes, verdicts, points_out,
+                       out_capacity, out_loc, CLDN_HIP_STAGE2_ZSTD);
 }
 
 int cldn_hip_lz4_decompress(cldn_hip_codec_t* c, const void* blocks, int blocks_loc, const uint64_t* block_offsets, uint32_t n_blocks,

@@ -26,6 +26,7 @@
 #include <thread>
 #include <unordered_map>
 
+#include "../stage2_decode_plan.h"
 #include "host_internal.hpp"
 
 namespace cloudini_amd {
@@ -599,8 +600,122 @@ uint64_t messageCloudBytes(uint32_t width, uint32_t height, uint32_t point_step)
 
 // ---- the way back: CompressedPointCloud2 -> PointCloud2 ---------------------------------------------------------------
 
-// per message: CDR parse + Cloudini header; per schema run: stage 2 undone on the host pool, ONE batched GPU decode
-void decodeGpuPhase(Batch& b, TranscodeStats* stats) {
+// One run through the route without TranscodeOptions::device_stage2_decode: stage 2 undone chunk by chunk on the host pool
+// into worst-case slots, packed into the framed stage-1 streams of the run, ONE batched GPU decode
+void decodeRunOnHost(Batch& b, Run& run, const std::vector<Cloudini::ConstBufferView>& body, size_t slot, TranscodeStats* stats) {
+  const size_t r0 = run.first;
+  const Cloudini::EncodingInfo& info0 = b.parsed[r0].info;
+  const auto t_gpu = Clock::now();
+  std::vector<Cloudini::amd_detail::ChunkRef> refs, all_refs;
+  std::vector<size_t> first_ref(run.count + 1, 0);
+  for (uint32_t k = 0; k < run.count; ++k) {
+    Cloudini::amd_detail::walkCompressedChunks(body[r0 + k], b.parsed[r0 + k].points, refs);
+    first_ref[k] = all_refs.size();
+    all_refs.insert(all_refs.end(), refs.begin(), refs.end());
+  }
+  first_ref[run.count] = all_refs.size();
+  if (run.stage1.size() < slot * all_refs.size()) run.stage1.resize(slot * all_refs.size());
+  uint8_t* scratch = run.stage1.data();
+  std::vector<uint32_t> got(all_refs.size());
+  const Cloudini::CompressionOption comp = info0.compression_opt;  // part of the schema key: the same for the whole run
+  Cloudini::amd_detail::runOnStage2Pool(all_refs.size(), [&](size_t c) {
+    got[c] = Cloudini::amd_detail::decompressChunkTo(comp, all_refs[c].src, all_refs[c].size, scratch + c * slot + 4, slot - 4);
+  });
+  run.offsets.assign(run.count + 1, 0);
+  run.out_at.assign(run.count + 1, 0);
+  std::vector<uint64_t> pts(run.count);
+  size_t produced = 0;
+  for (uint32_t k = 0; k < run.count; ++k) {
+    run.offsets[k] = produced;
+    for (size_t c = first_ref[k]; c < first_ref[k + 1]; ++c) {  // slot c starts at or behind `produced`
+      std::memcpy(scratch + c * slot, &got[c], 4);
+      if (produced != c * slot) std::memmove(scratch + produced, scratch + c * slot, 4u + size_t(got[c]));
+      produced += 4u + size_t(got[c]);
+    }
+    pts[k] = b.parsed[r0 + k].points;
+    run.out_at[k + 1] = run.out_at[k] + pts[k] * info0.point_step;
+  }
+  run.offsets[run.count] = produced;
+  const uint64_t out_bytes = run.out_at[run.count];
+  if (run.decoded.size() < out_bytes) run.decoded.resize(out_bytes);
+  // bytes of a point that no field covers read zero, like in the freshly resized vector the reference decodes into
+  // (src/ros_msg_utils.cpp:150-153): CLDN_HIP_FILL_ZERO -- the device buffer is cleared, every byte of `decoded` comes
+  // back from it (no memset of 600 MB on this thread, no upload of zeros)
+  Cloudini::amd_detail::decodeStage1Batch(info0, scratch, run.offsets.data(), pts.data(), run.count, run.decoded.data(),
+                                          out_bytes, true);
+  if (stats) {
+    stats->seconds_gpu += since(t_gpu);
+    stats->gpu_batches += 1;
+  }
+}
+
+// One run with TranscodeOptions::device_stage2_decode: the compressed bodies go up from where they arrived and the device
+// undoes stage 2 (decodeStage2Batch). The first call is optimistic -- no look at a frame header here, the device judges every
+// chunk anyway; what it hands back or refuses is decompressed on the host pool, exactly those chunks, for ONE second call
+// (stage2_decode_plan.h). Same bytes and same errors as decodeRunOnHost.
+void decodeRunOnDevice(Batch& b, Run& run, const std::vector<Cloudini::ConstBufferView>& body, size_t slot, TranscodeStats* stats) {
+  const size_t r0 = run.first;
+  const Cloudini::EncodingInfo& info0 = b.parsed[r0].info;
+  const auto t_gpu = Clock::now();
+  std::vector<Cloudini::amd_detail::ChunkRef> refs, all_refs;
+  std::vector<const uint8_t*> bodies(run.count);
+  std::vector<uint64_t> body_sizes(run.count), pts(run.count);
+  run.out_at.assign(run.count + 1, 0);
+  for (uint32_t k = 0; k < run.count; ++k) {  // (the chunk chain's errors are thrown here, as on the other route)
+    Cloudini::amd_detail::walkCompressedChunks(body[r0 + k], b.parsed[r0 + k].points, refs);
+    all_refs.insert(all_refs.end(), refs.begin(), refs.end());
+    bodies[k] = body[r0 + k].data();
+    body_sizes[k] = body[r0 + k].size();
+    pts[k] = b.parsed[r0 + k].points;
+    run.out_at[k + 1] = run.out_at[k] + pts[k] * info0.point_step;
+  }
+  const size_t n_chunks = all_refs.size();
+  std::vector<uint32_t> chunk_sizes(n_chunks), verdicts(n_chunks, 0u);
+  for (size_t c = 0; c < n_chunks; ++c) chunk_sizes[c] = all_refs[c].size;
+  const uint64_t out_bytes = run.out_at[run.count];
+  if (run.decoded.size() < out_bytes) run.decoded.resize(out_bytes);
+  std::string error;
+  int rc = Cloudini::amd_detail::decodeStage2Batch(info0, bodies.data(), body_sizes.data(), pts.data(), run.count, chunk_sizes.data(),
+                                                   nullptr, nullptr, verdicts.data(), run.decoded.data(), out_bytes, true, error);
+  uint64_t host_chunks = 0;
+  if (rc != CLDN_HIP_OK) {
+    const cldn::Stage2Retry retry = cldn::plan_stage2_retry(rc, verdicts.data(), static_cast<uint32_t>(n_chunks));
+    if (!retry.retry) throw std::runtime_error(error);
+    std::vector<size_t> picked;
+    for (size_t c = 0; c < n_chunks; ++c)
+      if (retry.expanded[c]) picked.push_back(c);
+    const size_t cap = slot - 4;  // what the other route gives the library for a chunk
+    if (run.stage1.size() < cap * picked.size()) run.stage1.resize(cap * picked.size());
+    std::vector<const uint8_t*> expanded(n_chunks, nullptr);
+    std::vector<uint32_t> expanded_sizes(n_chunks, 0u);
+    const Cloudini::CompressionOption comp = info0.compression_opt;
+    Cloudini::amd_detail::runOnStage2Pool(picked.size(), [&](size_t j) {  // (the host refuses one too: its exception is the run's)
+      const size_t c = picked[j];
+      expanded[c] = run.stage1.data() + j * cap;
+      expanded_sizes[c] = Cloudini::amd_detail::decompressChunkTo(comp, all_refs[c].src, all_refs[c].size, run.stage1.data() + j * cap, cap);
+    });
+    if (!cldn::stage2_retry_fits(retry, expanded_sizes.data(), cap - 4)) {
+      decodeRunOnHost(b, run, body, slot, stats);
+      return;
+    }
+    rc = Cloudini::amd_detail::decodeStage2Batch(info0, bodies.data(), body_sizes.data(), pts.data(), run.count, chunk_sizes.data(),
+                                                 expanded.data(), expanded_sizes.data(), verdicts.data(), run.decoded.data(), out_bytes,
+                                                 true, error);
+    if (rc != CLDN_HIP_OK) throw std::runtime_error(error);
+    host_chunks = picked.size();
+  }
+  if (stats) {
+    stats->seconds_gpu += since(t_gpu);
+    stats->gpu_batches += 1;
+    stats->device_stage2_chunks += n_chunks - host_chunks;
+    stats->host_stage2_chunks += host_chunks;
+    stats->device_stage2_retries += host_chunks != 0 ? 1 : 0;
+  }
+}
+
+// per message: CDR parse + Cloudini header; per schema run: stage 2 undone on the host pool or, with
+// TranscodeOptions::device_stage2_decode, on the device; ONE batched GPU decode
+void decodeGpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
   const size_t n = b.in.size();
   b.parsed.assign(n, Parsed());
   b.out.assign(n, {});
@@ -634,15 +749,15 @@ void decodeGpuPhase(Batch& b, TranscodeStats* stats) {
     }
   }
   size_t n_runs = 0;
-  std::vector<Cloudini::amd_detail::ChunkRef> refs, all_refs;
+  std::vector<cldn::Stage2Message> msgs;
   for (size_t r0 = 0; r0 < n;) {
     if (b.parsed[r0].key.empty()) {  // empty or odd message: no GPU work here
       ++r0;
       continue;
     }
     const Cloudini::EncodingInfo& info0 = b.parsed[r0].info;
-    // stage 2 is undone chunk by chunk into worst-case slots, then packed into the framed stage-1 streams of the run; a run
-    // ends where its slots would pass kDecodeScratchBytes (wide points: one chunk can be tens of megabytes)
+    // stage 2 is undone chunk by chunk into worst-case slots (host: then packed into the framed stage-1 streams of the run); a
+    // run ends where its slots would pass kDecodeScratchBytes (wide points: one chunk can be tens of megabytes)
     const size_t slot = 4u + Cloudini::amd_detail::stage1ChunkBound(info0) + 64u;
     constexpr size_t kDecodeScratchBytes = size_t(256) << 20;
     auto chunks_of = [&](size_t i) { return size_t((b.parsed[i].points + 32767) / 32768); };
@@ -651,52 +766,18 @@ void decodeGpuPhase(Batch& b, TranscodeStats* stats) {
       run_chunks += chunks_of(r1);
       ++r1;
     }
-    if (b.runs.size() <= n_runs) b.runs.emplace_back();
-    Run& run = b.runs[n_runs++];
-    run.estimated = false;
-    run.first = r0;
-    run.count = static_cast<uint32_t>(r1 - r0);
-    const auto t_gpu = Clock::now();
-    all_refs.clear();
-    std::vector<size_t> first_ref(run.count + 1, 0);
-    for (uint32_t k = 0; k < run.count; ++k) {
-      Cloudini::amd_detail::walkCompressedChunks(body[r0 + k], b.parsed[r0 + k].points, refs);
-      first_ref[k] = all_refs.size();
-      all_refs.insert(all_refs.end(), refs.begin(), refs.end());
-    }
-    first_ref[run.count] = all_refs.size();
-    if (run.stage1.size() < slot * all_refs.size()) run.stage1.resize(slot * all_refs.size());
-    uint8_t* scratch = run.stage1.data();
-    std::vector<uint32_t> got(all_refs.size());
-    const Cloudini::CompressionOption comp = info0.compression_opt;  // part of the schema key: the same for the whole run
-    Cloudini::amd_detail::runOnStage2Pool(all_refs.size(), [&](size_t c) {
-      got[c] = Cloudini::amd_detail::decompressChunkTo(comp, all_refs[c].src, all_refs[c].size, scratch + c * slot + 4, slot - 4);
-    });
-    run.offsets.assign(run.count + 1, 0);
-    run.out_at.assign(run.count + 1, 0);
-    std::vector<uint64_t> pts(run.count);
-    size_t produced = 0;
-    for (uint32_t k = 0; k < run.count; ++k) {
-      run.offsets[k] = produced;
-      for (size_t c = first_ref[k]; c < first_ref[k + 1]; ++c) {  // slot c starts at or behind `produced`
-        std::memcpy(scratch + c * slot, &got[c], 4);
-        if (produced != c * slot) std::memmove(scratch + produced, scratch + c * slot, 4u + size_t(got[c]));
-        produced += 4u + size_t(got[c]);
-      }
-      pts[k] = b.parsed[r0 + k].points;
-      run.out_at[k + 1] = run.out_at[k] + pts[k] * info0.point_step;
-    }
-    run.offsets[run.count] = produced;
-    const uint64_t out_bytes = run.out_at[run.count];
-    if (run.decoded.size() < out_bytes) run.decoded.resize(out_bytes);
-    // bytes of a point that no field covers read zero, like in the freshly resized vector the reference decodes into
-    // (src/ros_msg_utils.cpp:150-153): CLDN_HIP_FILL_ZERO -- the device buffer is cleared, every byte of `decoded` comes
-    // back from it (no memset of 600 MB on this thread, no upload of zeros)
-    Cloudini::amd_detail::decodeStage1Batch(info0, scratch, run.offsets.data(), pts.data(), run.count, run.decoded.data(),
-                                            out_bytes, true);
-    if (stats) {
-      stats->seconds_gpu += since(t_gpu);
-      stats->gpu_batches += 1;
+    // who undoes stage 2 (stage2_decode_plan.h; the schema key holds the compression: one group, whatever the plan's rule)
+    msgs.clear();
+    for (size_t i = r0; i < r1; ++i)
+      msgs.push_back({static_cast<uint8_t>(b.parsed[i].info.compression_opt), static_cast<uint32_t>(chunks_of(i))});
+    for (const cldn::Stage2Group& g : cldn::plan_stage2_groups(opt.device_stage2_decode, msgs.data(), static_cast<uint32_t>(msgs.size()))) {
+      if (b.runs.size() <= n_runs) b.runs.emplace_back();
+      Run& run = b.runs[n_runs++];
+      run.estimated = false;
+      run.first = r0 + g.first;
+      run.count = g.count;
+      if (g.call == cldn::S2_HOST_STAGE1) decodeRunOnHost(b, run, body, slot, stats);
+      else decodeRunOnDevice(b, run, body, slot, stats);
     }
     r0 = r1;
   }
@@ -851,6 +932,7 @@ void checkOptions(const TranscodeOptions& opt) {
   if (opt.decode && opt.device_zstd_matches)
     throw std::invalid_argument("TranscodeOptions: device_zstd_matches is not available together with decode");
   if (opt.device_zstd_matches && !opt.device_zstd) throw std::invalid_argument("TranscodeOptions: device_zstd_matches needs device_zstd");
+  if (opt.device_stage2_decode && !opt.decode) throw std::invalid_argument("TranscodeOptions: device_stage2_decode needs decode");
   for (const auto& named : opt.sweep)
     if (named.second.size() > CLDN_HIP_SWEEP_MAX_CANDIDATES)
       throw std::invalid_argument("TranscodeOptions: the sweep ladder of " + named.first + " has more than 16 resolutions");
@@ -894,7 +976,7 @@ void transcodeBatch(const std::vector<Message>& in, const TranscodeOptions& opt,
     b.in[i].bytes.assign(in[i].bytes.begin(), in[i].bytes.end());
   }
   if (opt.decode) {
-    decodeGpuPhase(b, stats);
+    decodeGpuPhase(b, opt, stats);
     decodeWrapPhase(b, stats);
   } else {
     gpuPhase(b, opt, stats);
@@ -1043,7 +1125,7 @@ TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, co
                 if (cldn_hip_set_current_device(devices[w]) != CLDN_HIP_OK) throw std::runtime_error(cldn_hip_last_error());
                 device_set = true;
               }
-              if (opt.decode) decodeGpuPhase(*b, &mine);
+              if (opt.decode) decodeGpuPhase(*b, opt, &mine);
               else gpuPhase(*b, opt, &mine);
             }
           } catch (...) {
@@ -1067,6 +1149,9 @@ TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, co
         stats.estimate_stage1_bytes += mine.estimate_stage1_bytes;
         stats.mergeModes(mine.modes);
         stats.mode_reencoded_runs += mine.mode_reencoded_runs;
+        stats.device_stage2_chunks += mine.device_stage2_chunks;
+        stats.host_stage2_chunks += mine.host_stage2_chunks;
+        stats.device_stage2_retries += mine.device_stage2_retries;
       }
       if (gpu_workers_left.fetch_sub(1) == 1) to_stage2.close();
     });

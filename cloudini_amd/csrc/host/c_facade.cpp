@@ -336,6 +336,32 @@ CLDN_EXPORT int64_t cldn_amd_decode_directory_on(const char* in_dir, const char*
   });
 }
 
+CLDN_EXPORT int64_t cldn_amd_decode_directory_stage2(const char* in_dir, const char* out_dir, uint32_t batch_messages,
+                                                     const int32_t* devices, uint32_t n_devices, int device_stage2, double* stats_out,
+                                                     char* stage2_json, uint64_t stage2_capacity) {
+  return guarded([&] {
+    cloudini_amd::DirectorySource source(in_dir);
+    cloudini_amd::DirectorySink sink(out_dir);
+    cloudini_amd::TranscodeOptions opt;
+    opt.decode = true;
+    opt.device_stage2_decode = device_stage2 != 0;
+    if (batch_messages) opt.batch_messages = batch_messages;
+    if (devices) opt.devices.assign(devices, devices + n_devices);
+    const cloudini_amd::TranscodeStats st = cloudini_amd::transcodePointClouds(source, sink, opt);
+    if (stats_out) {
+      const double v[8] = {(double)st.messages,    (double)st.points,  (double)st.input_bytes, (double)st.output_bytes,
+                           (double)st.gpu_batches, st.seconds_total, st.seconds_gpu,         st.seconds_stage2};
+      for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
+    }
+    const std::string json = "{\"device_stage2_chunks\": " + std::to_string(st.device_stage2_chunks) + ", \"host_stage2_chunks\": " +
+                             std::to_string(st.host_stage2_chunks) + ", \"device_stage2_retries\": " +
+                             std::to_string(st.device_stage2_retries) + "}";
+    if (json.size() + 1 > stage2_capacity) throw std::runtime_error("decode_directory_stage2: the summary needs " + std::to_string(json.size() + 1) + " bytes");
+    std::memcpy(stage2_json, json.c_str(), json.size() + 1);
+    return (int64_t)st.messages;
+  });
+}
+
 CLDN_EXPORT int64_t cldn_amd_decode_directory(const char* in_dir, const char* out_dir, uint32_t batch_messages,
                                               double* stats_out) {
   return cldn_amd_decode_directory_on(in_dir, out_dir, batch_messages, nullptr, 0, stats_out);

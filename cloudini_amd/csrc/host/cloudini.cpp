@@ -1321,6 +1321,31 @@ void decodeStage1Batch(const EncodingInfo& info, const uint8_t* streams, const u
   if (rc != CLDN_HIP_OK) throw std::runtime_error(err);
 }
 
+int decodeStage2Batch(const EncodingInfo& info, const uint8_t* const* bodies, const uint64_t* body_sizes, const uint64_t* cloud_points,
+                      uint32_t n_clouds, const uint32_t* chunk_sizes, const uint8_t* const* expanded, const uint32_t* expanded_sizes,
+                      uint32_t* verdicts, uint8_t* out, uint64_t out_capacity, bool out_is_zero, std::string& error) {
+  if (info.point_step == 0) throw std::runtime_error("point_step cannot be 0");
+  if (info.version < 3) throw std::runtime_error("decodeStage2Batch: framed streams (wire version >= 3) only");
+  const bool zstd = info.compression_opt == CompressionOption::ZSTD;
+  if (!zstd && info.compression_opt != CompressionOption::LZ4) throw std::runtime_error("decodeStage2Batch: LZ4 or ZSTD messages only");
+  PlanHandle plan(info);
+  cldn_hip_codec_t* codec = pool().acquire(info, plan);
+  cldn_hip_codec_set_decode_fill(codec, out_is_zero ? CLDN_HIP_FILL_ZERO : CLDN_HIP_FILL_KEEP);
+  const int sequences_were = cldn_hip_codec_zstd_sequences(codec);  // (the codec is pooled: it goes back as it came)
+  cldn_hip_codec_set_zstd_sequences(codec, 1);
+  const void* const* body_ptrs = reinterpret_cast<const void* const*>(bodies);
+  const void* const* exp_ptrs = reinterpret_cast<const void* const*>(expanded);
+  const int rc = zstd ? cldn_hip_decode_zstd_gather(codec, body_ptrs, body_sizes, cloud_points, n_clouds, chunk_sizes, exp_ptrs,
+                                                    expanded_sizes, verdicts, out, out_capacity, CLDN_HIP_HOST)
+                      : cldn_hip_decode_lz4_gather(codec, body_ptrs, body_sizes, cloud_points, n_clouds, chunk_sizes, exp_ptrs,
+                                                   expanded_sizes, verdicts, out, out_capacity, CLDN_HIP_HOST);
+  cldn_hip_codec_set_zstd_sequences(codec, sequences_were);
+  cldn_hip_codec_set_decode_fill(codec, CLDN_HIP_FILL_KEEP);
+  error = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
+  pool().release(info, codec);
+  return rc;
+}
+
 void runOnStage2Pool(size_t n, const std::function<void(size_t)>& fn) {
   const unsigned threads = Cloudini::stage2Threads();
   if (n <= 1 || threads <= 1) {

@@ -125,6 +125,16 @@ size_t stage1ChunkBound(const Cloudini::EncodingInfo& info);
 void decodeStage1Batch(const Cloudini::EncodingInfo& info, const uint8_t* streams, const uint64_t* offsets,
                        const uint64_t* cloud_points, uint32_t n_clouds, uint8_t* out, uint64_t out_capacity,
                        bool out_is_zero = false);
+// The same with stage 2 undone on the device (TranscodeOptions::device_stage2_decode): n LZ4 or ZSTD clouds of one schema, body
+// k = the chunks of message k behind its Cloudini header, wherever it lies (cldn_hip_decode_lz4_gather / _zstd_gather, the
+// sequences switch on for the call). chunk_sizes: what walkCompressedChunks found; expanded / expanded_sizes (or both NULL):
+// stage-1 payloads of chunks the caller decompressed; verdicts: [total chunks], written when the device judged the chunks.
+// Returns the call's CLDN_HIP_* code and its text in `error`: what to do about CLDN_HIP_ERR_UNSUPPORTED / _CORRUPT is the
+// caller's plan (stage2_decode_plan.h). Throws std::runtime_error for what no call was made for.
+int decodeStage2Batch(const Cloudini::EncodingInfo& info, const uint8_t* const* bodies, const uint64_t* body_sizes,
+                      const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes, const uint8_t* const* expanded,
+                      const uint32_t* expanded_sizes, uint32_t* verdicts, uint8_t* out, uint64_t out_capacity, bool out_is_zero,
+                      std::string& error);
 // fn(i) for i in [0, n) on the bounded stage-2 pool (the caller takes part)
 void runOnStage2Pool(size_t n, const std::function<void(size_t)>& fn);
 

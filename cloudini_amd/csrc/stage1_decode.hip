@@ -22,6 +22,7 @@
 
 #include "cloudini_hip.h"
 #include "stage1_launch.h"
+#include "stage2_expanded.h"
 
 namespace cldn {
 
@@ -102,6 +103,7 @@ DecodeFacts decode_facts(const DecodeLaunch& L) {
   F.zstd = L.zstd != nullptr;
   F.zstd_seq = L.zstd != nullptr && L.zstd->seq != 0u;
   F.sizes_known = L.chunk_sizes != nullptr;
+  F.gather = L.expanded_sizes != nullptr && L.verdicts != nullptr;
   F.fill_zero = L.fill_zero != 0u;
   F.out_aligned16 = ((uintptr_t)L.out & 15u) == 0u;
   for (uint32_t a = 0; a < 8u; ++a) F.cols |= (uint8_t)((L.cols[a] != nullptr) << a);
@@ -186,6 +188,10 @@ int stage1_launch_decode(const DecodeLaunch& L0) {
   else
     TRY_LAUNCH("k_walk_chunks", k_walk_chunks, dim3((L.n_clouds + 63u) / 64u), dim3(64), 0, L.stream, L.streams, L.stream_offsets,
                L.cloud_first_point, L.cloud_first_chunk, L.n_clouds, L.chunks, L.status, T);
+  const dim3 table_grid((L.n_chunks + 255u) / 256u);
+  if (R.gather)  // chunks the caller expanded leave the table until the stage-2 kernels are through
+    TRY_LAUNCH("k_stage2_hold_expanded", k_stage2_hold_expanded, table_grid, dim3(256), 0, L.stream, L.chunks, L.n_chunks, L.expanded_sizes,
+               L.zstd ? L.zstd->sizes : (uint32_t*)nullptr);
   if (R.lz4) {  // the table so far describes the LZ4 blocks: undo stage 2, chunk by chunk, into the slots
     const int rc = lz4_launch_decode_chunks(L.stream, L.streams, L.chunks, L.n_chunks, L.lz4_slots, L.lz4_slot_stride, L.lz4_capacity, L.status);
     if (rc != CLDN_HIP_OK) return rc;
@@ -196,6 +202,9 @@ int stage1_launch_decode(const DecodeLaunch& L0) {
     if (rc != CLDN_HIP_OK) return rc;
     L.streams = L.lz4_slots;
   }
+  if (R.gather)  // ... and come back pointing at their slots; every chunk's verdict
+    TRY_LAUNCH("k_stage2_place_expanded", k_stage2_place_expanded, table_grid, dim3(256), 0, L.stream, L.chunks, L.n_chunks, L.expanded_sizes,
+               L.zstd ? (const uint32_t*)L.zstd->sizes : (const uint32_t*)nullptr, L.lz4_slot_stride, L.verdicts);
   if (R.regular == DR_WIDE)
     TRY_LAUNCH("k_decode_wide", k_decode_wide, chunks, dim3(64), 0, L.stream, *L.wide, L.streams, L.chunks, L.out, L.uses_v5, L.status,
                reinterpret_cast<uint8_t*>(L.wide_state));

@@ -62,6 +62,7 @@ struct DecodeFacts {
   bool dsec, sec_cols, reg_end_pre, slices_done, slice_rec, token_ends, wp_split;
   bool zstd;              // cldn_hip_decode_zstd: the chunks are ZSTD frames
   bool zstd_seq;          //   ... and the codec takes frames with sequences (cldn_hip_codec_set_zstd_sequences)
+  bool gather;            // cldn_hip_decode_lz4_gather / _zstd_gather: chunks the caller expanded, a verdict per chunk
 };
 
 enum DecRegular : uint8_t {  // the kernel that decodes the regular streams
@@ -107,6 +108,7 @@ struct DecodeRoute {
   uint32_t fixed_bytes;  // DR_FIXED: bytes of a point
   bool zstd;             // k_zstd_walk, k_zstd_decode_blocks behind the table
   bool zstd_seq;         //   ... then k_zstd_seq_decode, k_zstd_seq_exec
+  bool gather;           // k_stage2_hold_expanded in front of the stage-2 kernels, k_stage2_place_expanded behind them
 };
 
 inline DecodeRoute decode_route(const DevPlan& P, const DecodeFacts& F) {
@@ -117,6 +119,7 @@ inline DecodeRoute decode_route(const DevPlan& P, const DecodeFacts& F) {
   R.lz4 = F.lz4 && F.n_chunks != 0u;
   R.zstd = F.zstd && F.n_chunks != 0u;
   R.zstd_seq = R.zstd && F.zstd_seq;
+  R.gather = F.gather && (R.lz4 || R.zstd);
   if (F.n_chunks == 0u) return R;
   if (F.wide) {  // schemas beyond the launch-argument plan: the serial decoder with the plan in device memory
     R.regular = DR_WIDE;
@@ -230,9 +233,11 @@ inline DecodeRoute decode_route(const DevPlan& P, const DecodeFacts& F) {
 inline void decode_route_kernels(const DecodeRoute& R, std::vector<const char*>& k) {
   auto section_columns = [&] { k.insert(k.end(), {"k_locate_sections", "k_section_offsets", "k_sections_w", "k_sections_done"}); };
   k.push_back(R.build_chunks ? "k_build_chunks" : "k_walk_chunks");
+  if (R.gather) k.push_back("k_stage2_hold_expanded");
   if (R.lz4) k.push_back("k_lz4_decode_chunks");
   if (R.zstd) k.insert(k.end(), {"k_zstd_walk", "k_zstd_decode_blocks"});
   if (R.zstd_seq) k.insert(k.end(), {"k_zstd_seq_decode", "k_zstd_seq_exec"});
+  if (R.gather) k.push_back("k_stage2_place_expanded");
   if (R.regular == DR_NONE) return;
   if (R.columns == DC_MANY || R.regular == DR_STREAM_COLS) section_columns();
   if (R.columns == DC_COLS) {

@@ -115,7 +115,12 @@ struct DecodeLaunch {
   // cldn_hip_decode_zstd: the same slots (lz4_slots, lz4_slot_stride, lz4_capacity) filled from [u32 size][ZSTD frame] chunks
   // by zstd_launch_decode (zstd_decode.hip) with this workspace; NULL = not a ZSTD call
   const struct ZstdDecodeLaunch* zstd;
+  // cldn_hip_decode_lz4_gather / _zstd_gather (stage2_expanded.h): chunks whose stage-1 payload the caller has put into their
+  // slots are kept from the stage-2 kernels and enter the table behind them; every chunk gets a verdict. NULL = neither.
+  const uint32_t* expanded_sizes;     // device [n_chunks]: payload bytes in the slot, or kNotExpanded
+  uint32_t* verdicts;                 // device [n_chunks]: decoded bytes, kZdSizeHost or kZdSizeCorrupt (= kLz4Rejected)
 };
+constexpr uint32_t kNotExpanded = 0xffffffffu;
 // bytes of the SPLIT workspace: per piece t0 (4) + aggregates (5 x 4) + carries (4 x 4), per chunk 4 flag words
 inline size_t wp_split_bytes(uint32_t n_chunks, uint32_t maxp) { return (size_t)n_chunks * maxp * 40u + (size_t)n_chunks * 16u + 256u; }
 // Launch errors go to the ABI's thread-local error string (cldn_hip_last_error), implemented in hip_abi.hip.

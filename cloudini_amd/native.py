@@ -166,6 +166,9 @@ def lib() -> C.CDLL:
     L.cldn_hip_zstd_decompress.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int, u64p, vp]
     L.cldn_hip_decode_zstd.restype = C.c_int
     L.cldn_hip_decode_zstd.argtypes = [vp, vp, C.c_int, u64p, u64p, C.c_uint32, vp, C.c_uint64, C.c_int]
+    for fn in (L.cldn_hip_decode_lz4_gather, L.cldn_hip_decode_zstd_gather):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, u64p, u64p, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, C.c_int]
     L.cldn_hip_audit_clouds.restype = C.c_int
     L.cldn_hip_audit_clouds.argtypes = [vp, vp, C.c_int, vp, C.c_int, u64p, C.c_uint32, vp, vp, C.c_int]
     L.cldn_hip_audit_streams.restype = C.c_int
@@ -724,6 +727,49 @@ class Codec:
         _check(lib().cldn_hip_decode_zstd(
             self._h, C.c_void_p(streams_ptr), DEVICE, so.ctypes.data_as(C.POINTER(C.c_uint64)),
             cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, C.c_void_p(out_ptr), int(out_capacity), DEVICE))
+
+    # ---- LZ4 / ZSTD message bodies where they lie (cldn_hip_decode_lz4_gather / cldn_hip_decode_zstd_gather) ---------
+    def decode_stage2_gather(self, stage2: int, bodies: Sequence[np.ndarray], cloud_points: Sequence[int], chunk_sizes=None,
+                             expanded=None, out: Optional[np.ndarray] = None):
+        """stage2: STAGE2_LZ4 or STAGE2_ZSTD. bodies: one uint8 array per message, read at the address it has (a view at any
+        offset of a larger array is taken as it is). chunk_sizes: the [u32 size] prefixes, or None. expanded: None, or one
+        entry per chunk of the batch -- None or the chunk's stage-1 payload (uint8 array / bytes). Returns (clouds, verdicts,
+        rc): the decoded clouds (views of `out`), the per-chunk verdicts, the call's return code (0 = OK; the error text is
+        cldn_hip_last_error's)."""
+        step = self.plan.point_step
+        arrs = [b if isinstance(b, np.ndarray) and b.dtype == np.uint8 and b.ndim == 1 and b.strides[0] == 1
+                else np.frombuffer(bytes(b), dtype=np.uint8) for b in bodies]
+        n = len(arrs)
+        ptrs = (C.c_void_p * max(1, n))(*[a.ctypes.data if a.size else None for a in arrs])
+        sizes = np.array([a.size for a in arrs], dtype=np.uint64)
+        npts = np.array(list(cloud_points), dtype=np.uint64)
+        n_chunks = int(sum((int(k) + 32767) // 32768 for k in npts))
+        total = int(npts.sum()) * step
+        if out is None:
+            out = np.zeros(max(1, total), dtype=np.uint8)
+        cs = None if chunk_sizes is None else np.ascontiguousarray(chunk_sizes, dtype=np.uint32)
+        if cs is not None and cs.size < n_chunks:
+            raise ValueError(f"chunk_sizes has {cs.size} entries, the batch has {n_chunks} chunks")
+        verdicts = np.full(max(1, n_chunks), 0xEEEEEEEE, dtype=np.uint32)
+        exp_ptrs = exp_sizes = None
+        keep = []
+        if expanded is not None:
+            if len(expanded) != n_chunks:
+                raise ValueError(f"expanded has {len(expanded)} entries, the batch has {n_chunks} chunks")
+            # (one spare byte behind every payload: an empty one still has an address)
+            keep = [None if e is None else np.frombuffer(bytes(e) + b"\0", dtype=np.uint8)[:len(bytes(e))] for e in expanded]
+            exp_ptrs = (C.c_void_p * max(1, n_chunks))(*[None if e is None else e.ctypes.data for e in keep])
+            exp_sizes = np.array([0 if e is None else e.size for e in keep], dtype=np.uint32)
+        fn = lib().cldn_hip_decode_lz4_gather if stage2 == STAGE2_LZ4 else lib().cldn_hip_decode_zstd_gather
+        rc = fn(self._h, ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), npts.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                None if cs is None else cs.ctypes.data_as(C.c_void_p), exp_ptrs,
+                None if exp_sizes is None else exp_sizes.ctypes.data_as(C.c_void_p), verdicts.ctypes.data_as(C.c_void_p),
+                out.ctypes.data_as(C.c_void_p), total, HOST)
+        res, pos = [], 0
+        for k in npts:
+            res.append(out[pos:pos + int(k) * step])
+            pos += int(k) * step
+        return res, verdicts[:n_chunks], rc
 
     # ---- audit: per-field error reports (cldn_hip_audit_*) -----------------------------------------------------------
     def _audit_report(self, n_clouds: int) -> np.ndarray:

@@ -190,6 +190,15 @@ struct TranscodeOptions {
   // carry a sequences section. It brings the schemas named above to within 6 - 19 % of libzstd level 1 and costs about another
   // literal-only stage of GPU time. Needs `device_zstd`; not available together with `decode`.
   bool device_zstd_matches = false;
+  // The way back with stage 2 on the device (include/cloudini_hip.h, cldn_hip_decode_lz4_gather / _zstd_gather). Needs `decode`.
+  // Every schema run of LZ4 or ZSTD messages uploads the compressed bodies from the page-locked Message::bytes they arrived in
+  // and undoes stage 2 on the device, ZSTD frames with sequences included; no libzstd / liblz4 call on the host. A run in
+  // which the device hands a chunk back (a frame with the content checksum, a skippable frame, a block the strict LZ4 rules
+  // refuse ...) decompresses exactly those chunks on the stage-2 pool and makes ONE second call with them expanded; what the
+  // host refuses too throws what a run without the option throws. Every output message and every error is the same as without
+  // the option; TranscodeStats::device_stage2_chunks / host_stage2_chunks / device_stage2_retries tell what happened.
+  // Messages with compression NONE, wire version 2 or a geometry that differs from their header keep their paths.
+  bool device_stage2_decode = false;
   // Test hook (tests/cpp/transcoder_order.cpp, runs without a GPU): when set, `test_workers` stage threads call it instead of
   // the GPU stage and stage 2 passes the batch on untouched -- what remains is the pipeline itself: batches handed to
   // whichever stage is free, the writer putting them back into input order, an error on any stage stopping all of them.
@@ -259,6 +268,9 @@ struct TranscodeStats {
   std::vector<ModeFieldSummary> modes;   // TranscodeOptions::modes: one entry per field name, in order of first appearance
   uint64_t mode_reencoded_runs = 0;      // Modes::Best: schema runs that were encoded a second time
   void mergeModes(const std::vector<ModeFieldSummary>& other);
+  // TranscodeOptions::device_stage2_decode (all 0 without it): chunks whose stage 2 the device undid, chunks the host pool
+  // decompressed for a second call, and schema runs that needed that second call
+  uint64_t device_stage2_chunks = 0, host_stage2_chunks = 0, device_stage2_retries = 0;
 };
 
 // The reference's profile strings (McapConverter::addProfile, tools/src/mcap_converter.cpp:325-353):

@@ -88,6 +88,15 @@ int64_t cldn_amd_transcode_directory_on(const char* in_dir, const char* out_dir,
 int64_t cldn_amd_decode_directory_on(const char* in_dir, const char* out_dir, uint32_t batch_messages, const int32_t* devices,
                                      uint32_t n_devices, double* stats_out);
 
+/* cldn_amd_decode_directory_on with TranscodeOptions::device_stage2_decode (device_stage2 != 0): LZ4 and ZSTD messages have
+ * stage 2 undone on the device (include/cloudini_hip.h, cldn_hip_decode_lz4_gather / _zstd_gather), chunks the device hands
+ * back go through the host pool and one second call. The files and the errors are those of cldn_amd_decode_directory_on.
+ * stage2_json receives one line of JSON, {"device_stage2_chunks", "host_stage2_chunks", "device_stage2_retries"} (all 0 with
+ * device_stage2 == 0); a buffer that is too small is an error. */
+int64_t cldn_amd_decode_directory_stage2(const char* in_dir, const char* out_dir, uint32_t batch_messages, const int32_t* devices,
+                                         uint32_t n_devices, int device_stage2, double* stats_out, char* stage2_json,
+                                         uint64_t stage2_capacity);
+
 /* cldn_amd_transcode_directory_on with the audit of every encode call (TranscodeOptions::audit; include/cloudini_hip.h,
  * cldn_hip_audit_last_encode): the files are the same, audit_json receives the per-field summary as one line of JSON -- a
  * list of {"name", "is_float", "n_bitwise_diff", "n_class_diff", "n_over_limit", "max_abs_err", "first_bad_message"}, sums

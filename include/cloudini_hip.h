@@ -324,7 +324,37 @@ int cldn_hip_zstd_decompress(cldn_hip_codec_t* codec, const void* frames, int fr
 int cldn_hip_decode_zstd(cldn_hip_codec_t* codec, const void* streams, int streams_loc, const uint64_t* stream_offsets,
                          const uint64_t* cloud_points, uint32_t n_clouds, void* points_out, uint64_t out_capacity, int out_loc);
 
-/* Wire version 2 (streams written before the chunked format; the reference still reads them, src/cloudini.cpp:665-667):
+/* cldn_hip_decode_lz4 / cldn_hip_decode_zstd for message bodies that lie where they arrived: the read side's twin of
+ * cldn_hip_encode_stage1_gather, and the calls behind the batch transcoder's TranscodeOptions::device_stage2_decode.
+ *   body_ptrs, body_sizes   HOST arrays [n_clouds] of HOST pointers / byte counts: body k is the chunks of message k behind its
+ *                           Cloudini header, [u32 size][LZ4 block or ZSTD frame] ... Every body is copied straight to its place
+ *                           in one device buffer by a stream-ordered copy of its own (page-locked bodies: no staging, no
+ *                           gathering copy on the host); there the bodies lie back to back, as the contiguous calls take them.
+ *   chunk_sizes             HOST [total chunks] or NULL: the [u32 size] prefixes the caller's own walk found. Given, the chunk
+ *                           table is built in parallel (cldn_hip_decode_stage1_sized); every entry is still checked against the
+ *                           prefix in the body, a mismatch is CLDN_HIP_ERR_CORRUPT.
+ *   verdicts                HOST [total chunks] or NULL, written whenever the kernels of the call ran, also when it fails: per
+ *                           chunk the decoded bytes, 0xfffffffe (the chunk needs the host) or 0xffffffff (refused, or a chunk
+ *                           of a damaged chunk chain) -- cldn_hip_lz4_decompress's / cldn_hip_zstd_decompress's sizes[k], for
+ *                           ZSTD under the codec's cldn_hip_codec_set_zstd_sequences setting. An expanded chunk reports its size.
+ *   expanded, expanded_sizes  HOST [total chunks] or both NULL; entries may be NULL. A non-NULL entry is that chunk's stage-1
+ *                           payload, decompressed by the caller: it is uploaded into the chunk's slot, the chunk's compressed
+ *                           bytes are neither decoded nor judged, and the stage-1 decoders read the slot through the rewritten
+ *                           chunk table like any other. A size above the slot capacity, cldn_hip_stage1_bound(plan, 32768) + 60,
+ *                           is CLDN_HIP_ERR_ARG.
+ * Everything else -- slots, chunk chain errors, error texts, cldn_hip_codec_set_decode_fill, cldn_hip_codec_decode_stats and
+ * _decode_ms, no point returned to HOST outputs by a failed call -- is the contiguous calls'. Both calls wait for the stream
+ * and report the verdict at once, for DEVICE outputs too. */
+int cldn_hip_decode_lz4_gather(cldn_hip_codec_t* codec, const void* const* body_ptrs, const uint64_t* body_sizes,
+                               const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes,
+                               const void* const* expanded, const uint32_t* expanded_sizes, uint32_t* verdicts,
+                               void* points_out, uint64_t out_capacity, int out_loc);
+int cldn_hip_decode_zstd_gather(cldn_hip_codec_t* codec, const void* const* body_ptrs, const uint64_t* body_sizes,
+                                const uint64_t* cloud_points, uint32_t n_clouds, const uint32_t* chunk_sizes,
+                                const void* const* expanded, const uint32_t* expanded_sizes, uint32_t* verdicts,
+                                void* points_out, uint64_t out_capacity, int out_loc);
+
+/* Wire version 2(streams written before the chunked format; the reference still reads them, src/cloudini.cpp:665-667):
  * the whole stage-1 payload is ONE unframed run of points without [u32 size] prefixes and without state resets, decoded
  * until it is empty (DecodeV4Stage1Chunk with expected_points = 0, src/v4_codec.cpp:108-115). The output capacity bounds
  * the point count ("Output buffer is too small to hold the decoded data" = CLDN_HIP_ERR_CORRUPT here); points behind the

@@ -24,6 +24,10 @@
 //       of a run without --modes. `best` also encodes a schema run a second time with the best modes forced wherever a cloud's
 //       best mode is not the probed one: those messages are NOT the reference encoder's bytes -- they are valid streams that
 //       every Cloudini decoder decodes to the same points. Not available with --decode (exit status 2).
+//   ... --decode --device-stage2   LZ4 and ZSTD messages: the compressed bodies go up as they arrived and the device undoes stage 2
+//       (cldn_hip_decode_lz4_gather / _zstd_gather); chunks it hands back are decompressed on the host pool for one second call.
+//       The files are the files of a run without the option; the JSON line's device_stage2_chunks / host_stage2_chunks /
+//       device_stage2_retries tell what happened. Without --decode: exit status 2.
 //   ... --devices 0,1,2,3   spreads the batches over these GPUs (one GPU stage per entry; "0,0" = two stages on GPU 0)
 //   cloudini_batch_transcode <in.mcap> <out.mcap> [...same options] [--mcap-compression none|lz4|zstd]
 //       a bag: point-cloud messages converted, everything else copied (McapConverter, tools/src/mcap_converter.cpp:141-300);
@@ -102,6 +106,8 @@ int main(int argc, char** argv) {
                  "                                        valid frames every ZSTD decoder reads, not libzstd's bytes); other compressions ignore it\n"
                  "  --device-zstd-matches                  with --device-zstd: blocks with a match of 12 bytes or more carry sequences (layouts\n"
                  "                                        whose bytes repeat come within 6-19 %% of libzstd level 1; token streams stay as they are)\n"
+                 "  --device-stage2                        with --decode: LZ4 / ZSTD stage 2 is undone on the device (same files; chunks the\n"
+                 "                                        device hands back go through the host pool)\n"
                  "  --sweep, --modes, --device-zstd and --device-zstd-matches are not available with --decode\n", argv[0]);
     return 2;
   }
@@ -143,6 +149,7 @@ int main(int argc, char** argv) {
     else if (a == "--estimate") opt.estimate = true;
     else if (a == "--device-zstd") opt.device_zstd = true;
     else if (a == "--device-zstd-matches") opt.device_zstd_matches = true;
+    else if (a == "--device-stage2") opt.device_stage2_decode = true;
     else if (a == "--modes" && i + 1 < argc) {
       const std::string v = argv[++i];
       if (v != "report" && v != "best") {
@@ -188,6 +195,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--device-zstd-matches needs --device-zstd\n");
     return 2;
   }
+  if (opt.device_stage2_decode && !opt.decode) {
+    std::fprintf(stderr, "--device-stage2 needs --decode\n");
+    return 2;
+  }
   if (opt.decode && opt.modes != cloudini_amd::TranscodeOptions::Modes::Off) {
     std::fprintf(stderr, "--modes is not available with --decode\n");
     return 2;
@@ -202,10 +213,13 @@ int main(int argc, char** argv) {
       if (opt.estimate) printEstimate(ms.pipeline);
       if (modes) printModes(ms.pipeline);
       std::printf("{\"messages\": %llu, \"converted\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"points\": %llu, "
-                  "\"seconds_total\": %.6f, \"gpu_batches\": %llu, \"peak_held_bytes\": %llu}\n",
+                  "\"seconds_total\": %.6f, \"gpu_batches\": %llu, \"peak_held_bytes\": %llu, \"device_stage2_chunks\": %llu, "
+                  "\"host_stage2_chunks\": %llu, \"device_stage2_retries\": %llu}\n",
                   (unsigned long long)ms.messages, (unsigned long long)ms.converted, (unsigned long long)ms.input_bytes,
                   (unsigned long long)ms.output_bytes, (unsigned long long)ms.pipeline.points, ms.pipeline.seconds_total,
-                  (unsigned long long)ms.pipeline.gpu_batches, (unsigned long long)ms.peak_held_bytes);
+                  (unsigned long long)ms.pipeline.gpu_batches, (unsigned long long)ms.peak_held_bytes,
+                  (unsigned long long)ms.pipeline.device_stage2_chunks, (unsigned long long)ms.pipeline.host_stage2_chunks,
+                  (unsigned long long)ms.pipeline.device_stage2_retries);
       if (std::getenv("CLDN_DEBUG_MEM")) {  // diagnostics: the process's memory high-water marks
         if (FILE* f = std::fopen("/proc/self/status", "r")) {
           char line[256];
@@ -224,10 +238,13 @@ int main(int argc, char** argv) {
     if (opt.estimate) printEstimate(st);
     if (modes) printModes(st);
     std::printf("{\"messages\": %llu, \"points\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"gpu_batches\": %llu, "
-                "\"seconds_total\": %.6f, \"seconds_gpu\": %.6f, \"seconds_stage2\": %.6f, \"gpu_stages\": %llu, \"Mpoints_per_s\": %.1f}\n",
+                "\"seconds_total\": %.6f, \"seconds_gpu\": %.6f, \"seconds_stage2\": %.6f, \"gpu_stages\": %llu, \"Mpoints_per_s\": %.1f, "
+                "\"device_stage2_chunks\": %llu, \"host_stage2_chunks\": %llu, \"device_stage2_retries\": %llu}\n",
                 (unsigned long long)st.messages, (unsigned long long)st.points, (unsigned long long)st.input_bytes,
                 (unsigned long long)st.output_bytes, (unsigned long long)st.gpu_batches, st.seconds_total, st.seconds_gpu,
-                st.seconds_stage2, (unsigned long long)st.gpu_workers, st.seconds_total > 0 ? st.points / st.seconds_total / 1e6 : 0.0);
+                st.seconds_stage2, (unsigned long long)st.gpu_workers, st.seconds_total > 0 ? st.points / st.seconds_total / 1e6 : 0.0,
+                (unsigned long long)st.device_stage2_chunks, (unsigned long long)st.host_stage2_chunks,
+                (unsigned long long)st.device_stage2_retries);
     if (!clean) return 3;
   } catch (const std::exception& e) {
     std::fprintf(stderr, "cloudini_batch_transcode: %s\n", e.what());
