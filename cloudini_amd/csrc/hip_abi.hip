@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "cloudini_hip.h"
+#include "decode_workspace.h"
 #include "stage1_device.h"
 #include "stage1_launch.h"
 
@@ -104,6 +105,13 @@ struct DevBuf {
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
+  }
+  // a workspace with one carve function (decode_workspace.h): sized by its run over NULL, carved where it then lies
+  template <class CarveFn>
+  int ensure_carved(CarveFn carve) {
+    const int rc = ensure(carve((void*)nullptr));
+    if (rc == CLDN_HIP_OK) carve(p);
+    return rc;
   }
 };
 
@@ -299,6 +307,22 @@ struct cldn_hip_codec {
     void drop() { valid = await_frame = false; }
   } enc;
 };
+
+// The decode calls' staging ring, first step: the next slot of h_dec_stage, with room for `bytes`, once its last upload has left it
+static int dec_stage_take(cldn_hip_codec* c, size_t bytes, uint32_t* slot, void** host) {
+  *slot = c->dec_stage_next++ % (uint32_t)cldn_hip_codec::kDecStageRing;
+  if (c->dec_stage_ev[*slot]) HIP_TRY(hipEventSynchronize(c->dec_stage_ev[*slot]));
+  else HIP_TRY(hipEventCreateWithFlags(&c->dec_stage_ev[*slot], hipEventDisableTiming));
+  const int rc = c->h_dec_stage[*slot].ensure(bytes);
+  *host = c->h_dec_stage[*slot].p;
+  return rc;
+}
+// ... second step: the slot's first `bytes` go to `dst` on the codec's stream, and the slot's event is recorded behind the copy
+static int dec_stage_send(cldn_hip_codec* c, uint32_t slot, void* dst, size_t bytes) {
+  HIP_TRY(hipMemcpyAsync(dst, c->h_dec_stage[slot].p, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->dec_stage_ev[slot], c->stream));
+  return CLDN_HIP_OK;
+}
 
 extern "C" {
 
@@ -1919,15 +1943,10 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   uint64_t* h_so = inl_so;
   uint64_t* h_fp = inl_fp;
   uint32_t* h_fc = inl_fc;
-  PinnedBuf* stage_p = nullptr;
   if (!inline_tables) {
-    slot = c->dec_stage_next++ % (uint32_t)cldn_hip_codec::kDecStageRing;
-    PinnedBuf& stage = c->h_dec_stage[slot];
-    if (c->dec_stage_ev[slot]) HIP_TRY(hipEventSynchronize(c->dec_stage_ev[slot]));  // its last upload has left the buffer
-    else HIP_TRY(hipEventCreateWithFlags(&c->dec_stage_ev[slot], hipEventDisableTiming));
-    if ((rc = stage.ensure(table_bytes)) != CLDN_HIP_OK) return rc;
-    stage_p = &stage;
-    h_so = (uint64_t*)stage.p;
+    void* stage;
+    if ((rc = dec_stage_take(c, table_bytes, &slot, &stage)) != CLDN_HIP_OK) return rc;
+    h_so = (uint64_t*)stage;
     h_fp = h_so + ne;
     h_fc = (uint32_t*)(h_fp + ne);
   }
@@ -1944,19 +1963,16 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   h_so[n_clouds] = stream_bytes - base_off;
   h_fp[n_clouds] = fp;
   h_fc[n_clouds] = fc;
-  const size_t chunk_table_bytes = ((size_t)std::max(1u, n_chunks) * sizeof(DecChunk) + 63) & ~size_t(63);
-  if ((rc = c->d_dec_meta.ensure(((table_bytes + 63) & ~size_t(63)) + chunk_table_bytes + (size_t)std::max(1u, n_chunks) * 18u + 64u)) != CLDN_HIP_OK)
-    return rc;
+  DecodeLaunch L;
+  memset(&L, 0, sizeof(L));
+  uint32_t* d_sizes = nullptr;  // (where HOST chunk_sizes go)
+  if ((rc = c->d_dec_meta.ensure_carved([&](void* p) { return carve_dec_meta(p, n_clouds, n_chunks, L, &d_sizes); })) != CLDN_HIP_OK) return rc;
   const bool dec_cols = c->plan.uses_v5 && plan.n_adaptive >= 1u && plan.n_adaptive <= kSoMaxFields;
   for (uint32_t a = 0; a < 8u; ++a)
     if (dec_cols && a < plan.n_adaptive && plan.adaptive[a].bpv <= 4u &&
         (rc = c->d_dec_cols[a].ensure((size_t)n_points * plan.adaptive[a].bpv + 64)) != CLDN_HIP_OK)
       return rc;
-  uint8_t* meta = (uint8_t*)c->d_dec_meta.p;
-  if (!inline_tables) {
-    HIP_TRY(hipMemcpyAsync(meta, stage_p->p, table_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->dec_stage_ev[slot], c->stream));
-  }
+  if (!inline_tables && (rc = dec_stage_send(c, slot, c->d_dec_meta.p, table_bytes)) != CLDN_HIP_OK) return rc;  // the three tables
 
   const uint8_t* d_streams = (const uint8_t*)streams + base_off;
   if (streams_loc == CLDN_HIP_HOST) {
@@ -1984,15 +2000,10 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
     }
   }
 
-  DecodeLaunch L;
-  memset(&L, 0, sizeof(L));
   L.plan = &plan;
   L.stream = c->stream;
   L.uses_v5 = c->plan.uses_v5 ? 1u : 0u;
   L.streams = d_streams;
-  L.stream_offsets = (const uint64_t*)meta;
-  L.cloud_first_point = (const uint64_t*)(meta + ne * 8);
-  L.cloud_first_chunk = (const uint32_t*)(meta + ne * 16);
   if (inline_tables) {
     L.h_stream_offsets = h_so;
     L.h_cloud_first_point = h_fp;
@@ -2000,14 +2011,6 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   }
   L.n_clouds = n_clouds;
   L.n_chunks = n_chunks;
-  L.chunks = (DecChunk*)(meta + ((table_bytes + 63) & ~size_t(63)));
-  L.reg_end = (uint32_t*)(meta + ((table_bytes + 63) & ~size_t(63)) + chunk_table_bytes);
-  L.reg_end_pre = L.reg_end + std::max(1u, n_chunks);
-  L.sec_done = (uint8_t*)(L.reg_end_pre + std::max(1u, n_chunks));
-  L.sec_cols = L.sec_done + std::max(1u, n_chunks);
-  L.chunk_sizes = nullptr;
-  uint32_t* const d_sizes = (uint32_t*)(((uintptr_t)(L.sec_cols + std::max(1u, n_chunks)) + 3u) & ~uintptr_t(3));
-  L.slices_done = d_sizes + std::max(1u, n_chunks);
   if (dec_cols && plan.n_adaptive == 1u && n_chunks) {  // slice records of k_sections_cols_fast
     const void* before = c->d_dec_rec.p;
     if ((rc = c->d_dec_rec.ensure((size_t)n_chunks * 48u * 16u)) != CLDN_HIP_OK) return rc;
@@ -2028,16 +2031,10 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   }
   for (uint32_t a = 0; a < 8u; ++a)
     L.cols[a] = (dec_cols && a < plan.n_adaptive && plan.adaptive[a].bpv <= 4u) ? (uint8_t*)c->d_dec_cols[a].p : nullptr;
-  L.dsec = nullptr;
-  L.secs_ok = nullptr;
-  L.done_cnt = nullptr;
-  if (c->plan.uses_v5 && plan.n_adaptive >= 1u && plan.n_adaptive <= kSoMaxFields && n_chunks) {  // sections side by side (stage1_decode_sections_w.h)
-    const size_t rows = (size_t)plan.n_adaptive * n_chunks * sizeof(DecChunk);
-    if ((rc = c->d_dec_secs.ensure(rows + (size_t)n_chunks * 8u + 256u)) != CLDN_HIP_OK) return rc;
-    L.dsec = (DecChunk*)c->d_dec_secs.p;
-    L.done_cnt = (uint32_t*)((uint8_t*)c->d_dec_secs.p + ((rows + 63u) & ~size_t(63)));
-    L.secs_ok = (uint8_t*)(L.done_cnt + n_chunks);
-  }
+  // sections side by side (stage1_decode_sections_w.h): L.dsec, L.done_cnt, L.secs_ok; NULL without them
+  if (c->plan.uses_v5 && plan.n_adaptive >= 1u && plan.n_adaptive <= kSoMaxFields && n_chunks &&
+      (rc = c->d_dec_secs.ensure_carved([&](void* p) { return carve_dec_secs(p, plan.n_adaptive, n_chunks, L); })) != CLDN_HIP_OK)
+    return rc;
   // LZ4 chunks: a slot per chunk with the capacity the host path gives LZ4_decompress_safe (cloudini.cpp, PointcloudDecoder::
   // decodeInto: the bound of a chunk's stage-1 payload + 60); the decoders then read the slots as their stream buffer
   uint64_t decoder_stream_bytes = stream_bytes - base_off;
@@ -2055,17 +2052,15 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
     L.lz4_capacity = (uint32_t)capacity;
     if (zstd) {  // the frames' block records, sized from the bytes of the call
       if (stream_bytes - base_off > 0x7fffffffull * 64u) return fail(CLDN_HIP_ERR_UNSUPPORTED, "decode_zstd: streams of more than 128 GiB");
-      const uint32_t max_recs = ZstdDecodeLaunch::records_for(n_chunks, stream_bytes - base_off, decoder_stream_bytes, c->zstd_sequences != 0);
-      // [workspace | sizes u32 per chunk]
       const bool seq_on = c->zstd_sequences != 0;  // (frames with sequences: their scratch mirrors the slots)
-      const size_t ws = (ZstdDecodeLaunch::workspace_bytes(max_recs, n_chunks, seq_on, decoder_stream_bytes) + 255u) & ~size_t(255);
-      if ((rc = c->d_zsd_ws.ensure(ws + (size_t)n_chunks * 4u)) != CLDN_HIP_OK) return rc;
-      Z.carve(c->d_zsd_ws.p, max_recs, n_chunks, seq_on, decoder_stream_bytes);
+      const uint32_t max_recs = ZstdDecodeLaunch::records_for(n_chunks, stream_bytes - base_off, decoder_stream_bytes, seq_on);
+      // [workspace | Z.sizes: u32 per chunk]
+      if ((rc = c->d_zsd_ws.ensure_carved([&](void* p) { return carve_zstd_chunks(p, max_recs, n_chunks, seq_on, decoder_stream_bytes, Z); })) != CLDN_HIP_OK)
+        return rc;
       Z.stream = c->stream;
       Z.frames = d_streams;
       Z.n_frames = n_chunks;
       Z.out = L.lz4_slots;
-      Z.sizes = (uint32_t*)((uint8_t*)c->d_zsd_ws.p + ws);
       Z.status = (uint32_t*)c->d_status.p;
       Z.chunks = L.chunks;
       Z.slot_stride = stride;
@@ -2075,27 +2070,23 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
     if (gather) {
       // expanded chunks: their payloads go up into their slots now (no kernel of the call writes an expanded chunk's slot),
       // their sizes into the table k_stage2_hold_expanded / _place_expanded read; the verdicts lie behind it
-      if ((rc = c->d_s2_gather.ensure((size_t)n_chunks * 8u)) != CLDN_HIP_OK) return rc;
-      uint32_t* const d_exp = (uint32_t*)c->d_s2_gather.p;
-      const uint32_t gslot = c->dec_stage_next++ % (uint32_t)cldn_hip_codec::kDecStageRing;
-      PinnedBuf& gstage = c->h_dec_stage[gslot];
-      if (c->dec_stage_ev[gslot]) HIP_TRY(hipEventSynchronize(c->dec_stage_ev[gslot]));  // its last upload has left the buffer
-      else HIP_TRY(hipEventCreateWithFlags(&c->dec_stage_ev[gslot], hipEventDisableTiming));
-      if ((rc = gstage.ensure((size_t)n_chunks * 4u)) != CLDN_HIP_OK) return rc;
-      uint32_t* const h_exp = (uint32_t*)gstage.p;
+      uint32_t* d_exp = nullptr;
+      if ((rc = c->d_s2_gather.ensure_carved([&](void* p) { return carve_s2_gather(p, n_chunks, &d_exp, &L.verdicts); })) != CLDN_HIP_OK) return rc;
+      uint32_t gslot;
+      void* gstage;
+      if ((rc = dec_stage_take(c, (size_t)n_chunks * 4u, &gslot, &gstage)) != CLDN_HIP_OK) return rc;
+      uint32_t* const h_exp = (uint32_t*)gstage;
       for (uint32_t k = 0; k < n_chunks; ++k) {
         const bool given = gather->expanded && gather->expanded[k];
         h_exp[k] = given ? gather->expanded_sizes[k] : kNotExpanded;
         if (given && h_exp[k] > capacity)
           return fail(CLDN_HIP_ERR_ARG, "expanded chunk %u has %u bytes: more than a slot's %llu", k, h_exp[k], (unsigned long long)capacity);
       }
-      HIP_TRY(hipMemcpyAsync(d_exp, h_exp, (size_t)n_chunks * 4u, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hipEventRecord(c->dec_stage_ev[gslot], c->stream));
+      if ((rc = dec_stage_send(c, gslot, d_exp, (size_t)n_chunks * 4u)) != CLDN_HIP_OK) return rc;
       for (uint32_t k = 0; k < n_chunks; ++k)
         if (h_exp[k] != kNotExpanded && h_exp[k] != 0u)
           HIP_TRY(hipMemcpyAsync(L.lz4_slots + (uint64_t)k * stride, gather->expanded[k], h_exp[k], hipMemcpyHostToDevice, c->stream));
       L.expanded_sizes = d_exp;
-      L.verdicts = d_exp + n_chunks;
     }
   }
   if (plan.varint_and_raw && n_chunks) {  // one bit per stream byte + a word per chunk (k_mark_token_ends)
@@ -2139,7 +2130,7 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
     (void)hipEventRecord(L.events[2], c->stream);
   }
   ++c->dec_call_index;
-  c->dec_trace = {n_chunks, meta, L.reg_end, L.reg_end_pre, L.slices_done, L.sec_done, L.sec_cols};
+  c->dec_trace = {n_chunks, c->d_dec_meta.p, L.reg_end, L.reg_end_pre, L.slices_done, L.sec_done, L.sec_cols};
   if ((rc = stage1_launch_decode(L)) != CLDN_HIP_OK) return rc;
   if (L.events) {
     (void)hipEventRecord(L.events[3], c->stream);
@@ -2195,50 +2186,52 @@ int cldn_hip_decode_zstd_gather(cldn_hip_codec_t* c, const void* const* body_ptr
                        out_capacity, out_loc, CLDN_HIP_STAGE2_ZSTD);
 }
 
-int cldn_hip_lz4_decompress(cldn_hip_codec_t* c, const void* blocks, int blocks_loc, const uint64_t* block_offsets, uint32_t n_blocks,
+// cldn_hip_lz4_decompress / cldn_hip_zstd_decompress: span k of `src`, an LZ4 block or a ZSTD frame, decodes into span k of `out`.
+// kind = CLDN_HIP_STAGE2_LZ4 / _ZSTD decides the name in the error texts, the launch (ZSTD: with its workspace) and the verdict.
+static int decompress_spans(cldn_hip_codec_t* c, int kind, const void* src, int src_loc, const uint64_t* src_offsets, uint32_t n,
                             void* out, int out_loc, const uint64_t* out_offsets, uint32_t* sizes) {
+  const bool zstd = kind == CLDN_HIP_STAGE2_ZSTD;
+  const char* const who = zstd ? "zstd" : "lz4";
   if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
   c->enc.drop();
-  if ((blocks_loc != CLDN_HIP_HOST && blocks_loc != CLDN_HIP_DEVICE) || (out_loc != CLDN_HIP_HOST && out_loc != CLDN_HIP_DEVICE))
+  if ((src_loc != CLDN_HIP_HOST && src_loc != CLDN_HIP_DEVICE) || (out_loc != CLDN_HIP_HOST && out_loc != CLDN_HIP_DEVICE))
     return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
-  if (n_blocks == 0) return CLDN_HIP_OK;
-  if (!block_offsets || !out_offsets || !sizes) return fail(CLDN_HIP_ERR_ARG, "lz4_decompress: NULL offsets / sizes");
-  if (out_loc == CLDN_HIP_DEVICE && ((uintptr_t)sizes & 3u)) return fail(CLDN_HIP_ERR_ARG, "lz4_decompress: device sizes must be 4-byte aligned");
-  for (uint32_t k = 0; k < n_blocks; ++k) {
-    if (block_offsets[k + 1] < block_offsets[k] || out_offsets[k + 1] < out_offsets[k])
-      return fail(CLDN_HIP_ERR_ARG, "lz4_decompress: offsets must be ascending");
-    if (block_offsets[k + 1] - block_offsets[k] > 0x7fffffffull || out_offsets[k + 1] - out_offsets[k] > 0x7fffffffull)
-      return fail(CLDN_HIP_ERR_UNSUPPORTED, "lz4_decompress: block or output span of more than 2 GiB");
+  if (n == 0) return CLDN_HIP_OK;
+  if (!src_offsets || !out_offsets || !sizes) return fail(CLDN_HIP_ERR_ARG, "%s_decompress: NULL offsets / sizes", who);
+  if (out_loc == CLDN_HIP_DEVICE && ((uintptr_t)sizes & 3u)) return fail(CLDN_HIP_ERR_ARG, "%s_decompress: device sizes must be 4-byte aligned", who);
+  for (uint32_t k = 0; k < n; ++k) {
+    if (src_offsets[k + 1] < src_offsets[k] || out_offsets[k + 1] < out_offsets[k])
+      return fail(CLDN_HIP_ERR_ARG, "%s_decompress: offsets must be ascending", who);
+    if (src_offsets[k + 1] - src_offsets[k] > 0x7fffffffull || out_offsets[k + 1] - out_offsets[k] > 0x7fffffffull)
+      return fail(CLDN_HIP_ERR_UNSUPPORTED, "%s_decompress: block or output span of more than 2 GiB", who);
   }
-  const uint64_t b0 = block_offsets[0], b_bytes = block_offsets[n_blocks] - b0;
-  const uint64_t o0 = out_offsets[0], o_bytes = out_offsets[n_blocks] - o0;
-  if ((b_bytes && !blocks) || (o_bytes && !out)) return fail(CLDN_HIP_ERR_ARG, "lz4_decompress: NULL buffer");
+  const uint64_t b0 = src_offsets[0], b_bytes = src_offsets[n] - b0;
+  const uint64_t o0 = out_offsets[0], o_bytes = out_offsets[n] - o0;
+  if ((b_bytes && !src) || (o_bytes && !out)) return fail(CLDN_HIP_ERR_ARG, "%s_decompress: NULL buffer", who);
   ENTER_DEVICE(c->device);
   int rc;
   if ((rc = c->d_status.ensure(256)) != CLDN_HIP_OK) return rc;
   HIP_TRY(hipMemsetAsync(c->d_status.p, 0, 256, c->stream));
-  // tables: [block offsets u64 | out offsets u64] relative to the first block / span, [sizes u32] for HOST outputs
-  const size_t ne = (size_t)n_blocks + 1;
-  if ((rc = c->d_lzd_tables.ensure(ne * 16u + (size_t)n_blocks * 4u)) != CLDN_HIP_OK) return rc;
+  // tables: [src offsets u64 | out offsets u64] relative to the first block / span, [sizes u32] for HOST outputs
+  const size_t ne = (size_t)n + 1;
+  SpanTables T;
+  if ((rc = c->d_lzd_tables.ensure_carved([&](void* p) { return carve_span_tables(p, n, T); })) != CLDN_HIP_OK) return rc;
   // (staged through the decode calls' ring of page-locked buffers: no wait for the stream unless the ring has gone round)
-  const uint32_t slot = c->dec_stage_next++ % (uint32_t)cldn_hip_codec::kDecStageRing;
-  PinnedBuf& stage = c->h_dec_stage[slot];
-  if (c->dec_stage_ev[slot]) HIP_TRY(hipEventSynchronize(c->dec_stage_ev[slot]));  // its last upload has left the buffer
-  else HIP_TRY(hipEventCreateWithFlags(&c->dec_stage_ev[slot], hipEventDisableTiming));
-  if ((rc = stage.ensure(ne * 16u)) != CLDN_HIP_OK) return rc;
-  uint64_t* h_bo = (uint64_t*)stage.p;
+  uint32_t slot;
+  void* stage;
+  if ((rc = dec_stage_take(c, ne * 16u, &slot, &stage)) != CLDN_HIP_OK) return rc;
+  uint64_t* h_bo = (uint64_t*)stage;
   uint64_t* h_oo = h_bo + ne;
   for (size_t k = 0; k < ne; ++k) {
-    h_bo[k] = block_offsets[k] - b0;
+    h_bo[k] = src_offsets[k] - b0;
     h_oo[k] = out_offsets[k] - o0;
   }
-  HIP_TRY(hipMemcpyAsync(c->d_lzd_tables.p, stage.p, ne * 16u, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(c->dec_stage_ev[slot], c->stream));
-  const uint8_t* d_blocks = (const uint8_t*)blocks + b0;
-  if (blocks_loc == CLDN_HIP_HOST) {
+  if ((rc = dec_stage_send(c, slot, T.src_offsets, ne * 16u)) != CLDN_HIP_OK) return rc;  // both offset tables
+  const uint8_t* d_src = (const uint8_t*)src + b0;
+  if (src_loc == CLDN_HIP_HOST) {
     if ((rc = c->d_in.ensure((size_t)std::max<uint64_t>(1, b_bytes))) != CLDN_HIP_OK) return rc;
-    if (b_bytes) HIP_TRY(hipMemcpyAsync(c->d_in.p, (const uint8_t*)blocks + b0, (size_t)b_bytes, hipMemcpyHostToDevice, c->stream));
-    d_blocks = (const uint8_t*)c->d_in.p;
+    if (b_bytes) HIP_TRY(hipMemcpyAsync(c->d_in.p, (const uint8_t*)src + b0, (size_t)b_bytes, hipMemcpyHostToDevice, c->stream));
+    d_src = (const uint8_t*)c->d_in.p;
   }
   uint8_t* d_outp = (uint8_t*)out + o0;
   uint32_t* d_sizes = sizes;
@@ -2248,108 +2241,58 @@ int cldn_hip_lz4_decompress(cldn_hip_codec_t* c, const void* blocks, int blocks_
     d_outp = (uint8_t*)c->d_out.p;
     // bytes of a span behind the decoded ones keep the caller's content: bring it along
     if (o_bytes) HIP_TRY(hipMemcpyAsync(d_outp, (const uint8_t*)out + o0, (size_t)o_bytes, hipMemcpyHostToDevice, c->stream));
-    d_sizes = (uint32_t*)((uint8_t*)c->d_lzd_tables.p + ne * 16u);
+    d_sizes = T.sizes;
   }
-  Lz4DecompressLaunch L;
-  L.stream = c->stream;
-  L.blocks = d_blocks;
-  L.block_offsets = (const uint64_t*)c->d_lzd_tables.p;
-  L.n_blocks = n_blocks;
-  L.out = d_outp;
-  L.out_offsets = (const uint64_t*)c->d_lzd_tables.p + ne;
-  L.sizes = d_sizes;
-  L.status = (uint32_t*)c->d_status.p;
-  if ((rc = lz4_launch_decompress(L)) != CLDN_HIP_OK) return rc;
-  if (out_loc == CLDN_HIP_DEVICE) return CLDN_HIP_OK;
+  if (zstd) {
+    const bool seq_on = c->zstd_sequences != 0;  // (frames with sequences: their scratch mirrors the output spans)
+    const uint32_t max_recs = ZstdDecodeLaunch::records_for(n, b_bytes, o_bytes, seq_on);
+    if ((rc = c->d_zsd_ws.ensure(ZstdDecodeLaunch::workspace_bytes(max_recs, n, seq_on, o_bytes))) != CLDN_HIP_OK) return rc;
+    ZstdDecodeLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.carve(c->d_zsd_ws.p, max_recs, n, seq_on, o_bytes);
+    L.stream = c->stream;
+    L.frames = d_src;
+    L.frame_offsets = T.src_offsets;
+    L.n_frames = n;
+    L.out = d_outp;
+    L.out_offsets = T.out_offsets;
+    L.sizes = d_sizes;
+    L.status = (uint32_t*)c->d_status.p;
+    rc = zstd_launch_decode(L);
+  } else {
+    Lz4DecompressLaunch L;
+    L.stream = c->stream;
+    L.blocks = d_src;
+    L.block_offsets = T.src_offsets;
+    L.n_blocks = n;
+    L.out = d_outp;
+    L.out_offsets = T.out_offsets;
+    L.sizes = d_sizes;
+    L.status = (uint32_t*)c->d_status.p;
+    rc = lz4_launch_decompress(L);
+  }
+  if (rc != CLDN_HIP_OK || out_loc == CLDN_HIP_DEVICE) return rc;
   uint32_t st = 0;
   HIP_TRY(hipMemcpyAsync(&st, c->d_status.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(sizes, d_sizes, (size_t)n_blocks * 4u, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(sizes, d_sizes, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
   if (o_bytes) HIP_TRY(hipMemcpyAsync((uint8_t*)out + o0, d_outp, (size_t)o_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed (sizes[k] == 0xffffffff marks the blocks)");
+  if (st & ST_CORRUPT)
+    return fail(CLDN_HIP_ERR_CORRUPT, zstd ? "ZSTD decompression failed (sizes[k] == 0xffffffff marks the frames)"
+                                           : "LZ4 decompression failed (sizes[k] == 0xffffffff marks the blocks)");
+  if (zstd && (st & ST_ZSTD_HOST))
+    return fail(CLDN_HIP_ERR_UNSUPPORTED, "ZSTD frame carries sequences or options the device decoder does not take (sizes[k] == 0xfffffffe marks the frames)");
   return CLDN_HIP_OK;
 }
 
-int cldn_hip_zstd_decompress(cldn_hip_codec_t* c, const void* frames, int frames_loc, const uint64_t* frame_offsets, uint32_t n_frames,
+int cldn_hip_lz4_decompress(cldn_hip_codec_t* c, const void* blocks, int blocks_loc, const uint64_t* block_offsets, uint32_t n_blocks,
                             void* out, int out_loc, const uint64_t* out_offsets, uint32_t* sizes) {
-  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
-  c->enc.drop();
-  if ((frames_loc != CLDN_HIP_HOST && frames_loc != CLDN_HIP_DEVICE) || (out_loc != CLDN_HIP_HOST && out_loc != CLDN_HIP_DEVICE))
-    return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
-  if (n_frames == 0) return CLDN_HIP_OK;
-  if (!frame_offsets || !out_offsets || !sizes) return fail(CLDN_HIP_ERR_ARG, "zstd_decompress: NULL offsets / sizes");
-  if (out_loc == CLDN_HIP_DEVICE && ((uintptr_t)sizes & 3u)) return fail(CLDN_HIP_ERR_ARG, "zstd_decompress: device sizes must be 4-byte aligned");
-  for (uint32_t k = 0; k < n_frames; ++k) {
-    if (frame_offsets[k + 1] < frame_offsets[k] || out_offsets[k + 1] < out_offsets[k])
-      return fail(CLDN_HIP_ERR_ARG, "zstd_decompress: offsets must be ascending");
-    if (frame_offsets[k + 1] - frame_offsets[k] > 0x7fffffffull || out_offsets[k + 1] - out_offsets[k] > 0x7fffffffull)
-      return fail(CLDN_HIP_ERR_UNSUPPORTED, "zstd_decompress: block or output span of more than 2 GiB");
-  }
-  const uint64_t b0 = frame_offsets[0], b_bytes = frame_offsets[n_frames] - b0;
-  const uint64_t o0 = out_offsets[0], o_bytes = out_offsets[n_frames] - o0;
-  if ((b_bytes && !frames) || (o_bytes && !out)) return fail(CLDN_HIP_ERR_ARG, "zstd_decompress: NULL buffer");
-  ENTER_DEVICE(c->device);
-  int rc;
-  if ((rc = c->d_status.ensure(256)) != CLDN_HIP_OK) return rc;
-  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, 256, c->stream));
-  // tables: [block offsets u64 | out offsets u64] relative to the first block / span, [sizes u32] for HOST outputs
-  const size_t ne = (size_t)n_frames + 1;
-  if ((rc = c->d_lzd_tables.ensure(ne * 16u + (size_t)n_frames * 4u)) != CLDN_HIP_OK) return rc;
-  // (staged through the decode calls' ring of page-locked buffers: no wait for the stream unless the ring has gone round)
-  const uint32_t slot = c->dec_stage_next++ % (uint32_t)cldn_hip_codec::kDecStageRing;
-  PinnedBuf& stage = c->h_dec_stage[slot];
-  if (c->dec_stage_ev[slot]) HIP_TRY(hipEventSynchronize(c->dec_stage_ev[slot]));  // its last upload has left the buffer
-  else HIP_TRY(hipEventCreateWithFlags(&c->dec_stage_ev[slot], hipEventDisableTiming));
-  if ((rc = stage.ensure(ne * 16u)) != CLDN_HIP_OK) return rc;
-  uint64_t* h_bo = (uint64_t*)stage.p;
-  uint64_t* h_oo = h_bo + ne;
-  for (size_t k = 0; k < ne; ++k) {
-    h_bo[k] = frame_offsets[k] - b0;
-    h_oo[k] = out_offsets[k] - o0;
-  }
-  HIP_TRY(hipMemcpyAsync(c->d_lzd_tables.p, stage.p, ne * 16u, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(c->dec_stage_ev[slot], c->stream));
-  const uint8_t* d_frames = (const uint8_t*)frames + b0;
-  if (frames_loc == CLDN_HIP_HOST) {
-    if ((rc = c->d_in.ensure((size_t)std::max<uint64_t>(1, b_bytes))) != CLDN_HIP_OK) return rc;
-    if (b_bytes) HIP_TRY(hipMemcpyAsync(c->d_in.p, (const uint8_t*)frames + b0, (size_t)b_bytes, hipMemcpyHostToDevice, c->stream));
-    d_frames = (const uint8_t*)c->d_in.p;
-  }
-  uint8_t* d_outp = (uint8_t*)out + o0;
-  uint32_t* d_sizes = sizes;
-  if (out_loc == CLDN_HIP_HOST) {
-    c->pending_total = 0;  // the device output buffer is reused: a deferred encode output waiting in it is gone
-    if ((rc = c->d_out.ensure((size_t)std::max<uint64_t>(1, o_bytes))) != CLDN_HIP_OK) return rc;
-    d_outp = (uint8_t*)c->d_out.p;
-    // bytes of a span behind the decoded ones keep the caller's content: bring it along
-    if (o_bytes) HIP_TRY(hipMemcpyAsync(d_outp, (const uint8_t*)out + o0, (size_t)o_bytes, hipMemcpyHostToDevice, c->stream));
-    d_sizes = (uint32_t*)((uint8_t*)c->d_lzd_tables.p + ne * 16u);
-  }
-  const uint32_t max_recs = ZstdDecodeLaunch::records_for(n_frames, b_bytes, o_bytes, c->zstd_sequences != 0);
-  const bool seq_on = c->zstd_sequences != 0;  // (frames with sequences: their scratch mirrors the output spans)
-  if ((rc = c->d_zsd_ws.ensure(ZstdDecodeLaunch::workspace_bytes(max_recs, n_frames, seq_on, o_bytes))) != CLDN_HIP_OK) return rc;
-  ZstdDecodeLaunch L;
-  memset(&L, 0, sizeof(L));
-  L.carve(c->d_zsd_ws.p, max_recs, n_frames, seq_on, o_bytes);
-  L.stream = c->stream;
-  L.frames = d_frames;
-  L.frame_offsets = (const uint64_t*)c->d_lzd_tables.p;
-  L.n_frames = n_frames;
-  L.out = d_outp;
-  L.out_offsets = (const uint64_t*)c->d_lzd_tables.p + ne;
-  L.sizes = d_sizes;
-  L.status = (uint32_t*)c->d_status.p;
-  if ((rc = zstd_launch_decode(L)) != CLDN_HIP_OK) return rc;
-  if (out_loc == CLDN_HIP_DEVICE) return CLDN_HIP_OK;
-  uint32_t st = 0;
-  HIP_TRY(hipMemcpyAsync(&st, c->d_status.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(sizes, d_sizes, (size_t)n_frames * 4u, hipMemcpyDeviceToHost, c->stream));
-  if (o_bytes) HIP_TRY(hipMemcpyAsync((uint8_t*)out + o0, d_outp, (size_t)o_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (st & ST_CORRUPT) return fail(CLDN_HIP_ERR_CORRUPT, "ZSTD decompression failed (sizes[k] == 0xffffffff marks the frames)");
-  if (st & ST_ZSTD_HOST)
-    return fail(CLDN_HIP_ERR_UNSUPPORTED, "ZSTD frame carries sequences or options the device decoder does not take (sizes[k] == 0xfffffffe marks the frames)");
-  return CLDN_HIP_OK;
+  return decompress_spans(c, CLDN_HIP_STAGE2_LZ4, blocks, blocks_loc, block_offsets, n_blocks, out, out_loc, out_offsets, sizes);
+}
+
+int cldn_hip_zstd_decompress(cldn_hip_codec_t* c, const void* frames, int frames_loc, const uint64_t* frame_offsets, uint32_t n_frames,
+                             void* out, int out_loc, const uint64_t* out_offsets, uint32_t* sizes) {
+  return decompress_spans(c, CLDN_HIP_STAGE2_ZSTD, frames, frames_loc, frame_offsets, n_frames, out, out_loc, out_offsets, sizes);
 }
 
 int cldn_hip_decode_stage1_unframed(cldn_hip_codec_t* c, const void* payload, uint64_t size, int payload_loc,

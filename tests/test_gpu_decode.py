@@ -703,3 +703,69 @@ def test_a_wrong_delta_varint_guess_from_the_end_is_found_out(oracle):
             assert int(tr["reg_end"][0]) == loc.truth != int(tr["reg_end_pre"][0])
             assert (int(tr["sec_cols"][0]), int(tr["sec_done"][0]), tr["words"][5], tr["words"][6]) == (0, 1, 0, 1), (n, tr)
     assert hits >= 3
+
+
+def _tiny_batch(oracle, n_clouds, seed):
+    """n_clouds XYZI clouds of three points: (info, streams back to back, stream offsets, what they decode to over 0x5A)"""
+    info = None
+    streams, want = [], []
+    for k in range(n_clouds):
+        info, data = synth.lidar_xyzi(3, seed=seed * 100 + k)
+        streams.append(oracle.encode_stage1(info, data))
+        want.append(oracle.decode_stage1(info, streams[-1], 3, fill=0x5A))
+    offsets = np.zeros(n_clouds + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([s.size for s in streams])
+    return info, np.concatenate(streams), offsets, np.concatenate(want)
+
+
+def test_staged_tables_of_back_to_back_calls_go_round_the_ring(oracle):
+    """Calls of more than 8 clouds stage their per-cloud tables in a ring of 4 page-locked buffers, each guarded by the event
+    behind its upload. Six such calls without a synchronisation in between use slots 0 and 1 twice: no call's tables may be
+    overwritten before its upload has read them. A seventh call of 8 clouds passes its tables as a kernel argument."""
+    import torch
+    from cloudini_amd import native
+    dev = torch.device("cuda", 0)
+    batches = [_tiny_batch(oracle, 9, seed) for seed in range(1, 7)] + [_tiny_batch(oracle, 8, 7)]
+    assert len({b[1].tobytes() for b in batches}) == 7                      # every call has values of its own
+    codec = native.Codec(native.Plan(batches[0][0]))
+    d_streams = [torch.from_numpy(b[1]).to(dev) for b in batches]
+    d_outs = [torch.full((b[3].size,), 0x5A, dtype=torch.uint8, device=dev) for b in batches]
+    torch.cuda.synchronize(dev)
+    for k in range(6):
+        codec.decode_device(d_streams[k].data_ptr(), batches[k][2], np.full(9, 3, dtype=np.uint64), d_outs[k].data_ptr(), batches[k][3].size)
+    codec.synchronize()
+    codec.status()
+    for k in range(6):
+        assert np.array_equal(d_outs[k].cpu().numpy(), batches[k][3]), k
+    codec.decode_device(d_streams[6].data_ptr(), batches[6][2], np.full(8, 3, dtype=np.uint64), d_outs[6].data_ptr(), batches[6][3].size)
+    tr = codec.decode_trace()                                               # (synchronises)
+    codec.status()
+    assert tr["n_chunks"] == 8 and tr["words"][0] + tr["words"][2] == 8     # every chunk decoded, by the parallel or the serial kernel
+    assert np.array_equal(d_outs[6].cpu().numpy(), batches[6][3])
+    codec.close()
+
+
+@pytest.mark.parametrize("n", [5, 32769])
+def test_host_chunk_sizes_of_one_and_two_chunks_land_behind_the_flag_arrays(oracle, n):
+    """The decode call's per-chunk arrays are at their shortest: reg_end, reg_end_pre (u32), sec_done, sec_cols (u8), then the
+    uploaded chunk sizes at the next multiple of 4 -- two flag bytes of one chunk leave a gap of two, four of two chunks none --
+    then slices_done. One adaptive field (the u16 intensity). Sizes from HOST memory go through that slot and are checked against
+    the [u32] prefixes; the trace reads every array back."""
+    from cloudini_amd import native
+    info, data = synth.lidar_xyzi(n, seed=90 + n % 7)
+    stream = oracle.encode_stage1(info, data)
+    chunk_sizes = [c.size for c in _split_chunks(stream)]
+    assert len(chunk_sizes) == (n + 32767) // 32768
+    codec = native.Codec(native.Plan(info))
+    assert codec.plan.adaptive_fields == 1
+    want = oracle.decode_stage1(info, stream, n, fill=0x5A)
+    got = codec.decode_host([stream], [n], out=np.full(data.size, 0x5A, dtype=np.uint8), chunk_sizes=chunk_sizes)[0]
+    assert np.array_equal(got, want)
+    tr = codec.decode_trace()
+    assert tr["n_chunks"] == len(chunk_sizes) and codec.decode_stats()[0] == len(chunk_sizes)
+    assert all(0 < int(e) <= s for e, s in zip(tr["reg_end"], chunk_sizes)), tr      # the regular stream ends inside its payload
+    wrong = list(chunk_sizes)
+    wrong[-1] += 1                                                          # (the uploaded sizes are what the kernels read)
+    with pytest.raises(native.CloudiniHipError):
+        codec.decode_host([stream], [n], chunk_sizes=wrong)
+    codec.close()

@@ -316,3 +316,70 @@ def test_the_gather_calls(oracle, comp):
     assert verdicts[1] in (NEEDS_HOST, REFUSED) and [int(v) for k, v in enumerate(verdicts) if k != 1] == [s for k, s in enumerate(sizes_of) if k != 1]
     assert codec.decode_stats() is not None
     codec.close()
+
+
+def test_four_kinds_of_decode_call_share_the_staging_ring(oracle):
+    """cldn_hip_lz4_decompress, a gather call (tables and expanded sizes: two slots), cldn_hip_zstd_decompress and
+    cldn_hip_decode_lz4 stage their tables in the same ring of 4 page-locked buffers. One after the other on one codec, with
+    no synchronisation added between them, the fifth upload waits for the first one's event: every call gives what it gives
+    on a codec of its own, which is what the inputs were built from."""
+    import torch
+    from cloudini_amd import native, synth
+    dev = torch.device("cuda", 0)
+    LZ4, ZSTD = CompressionOption.LZ4, CompressionOption.ZSTD
+    rs = np.random.RandomState(5)
+    lits = [rs.randint(0, 256, 18).astype(np.uint8).tobytes() for _ in range(2)]
+    blocks = [bytes([0xF0, 3]) + p for p in lits]                                   # one run of 18 literals: 20 bytes
+    assert all(len(b) == 20 and LR.decode(b, 64) == p for b, p in zip(blocks, lits))
+    texts = [bytes(rs.randint(0, 4, n).astype(np.uint8)) for n in (40, 100)]
+    frames = [S.stage2(ZSTD, t) for t in texts]
+    info = synth.lidar_xyzi(3)[0]
+    clouds = [synth.lidar_xyzi(3, seed=300 + k)[1] for k in range(18)]
+    bodies, payloads = {}, {}
+    for comp, part in ((ZSTD, clouds[:9]), (LZ4, clouds[9:])):
+        made = [S.body_of(oracle, info, c, comp) for c in part]
+        bodies[comp], payloads[comp] = [b for b, _p in made], [p[0] for _b, p in made]
+    want_points = {comp: [oracle.decode_stage1(info, lz4_body.frame([p]), 3, fill=0x5A) for p in payloads[comp]] for comp in (ZSTD, LZ4)}
+    expanded = [None] * 9
+    expanded[4] = payloads[ZSTD][4]
+
+    def spans(parts, caps):
+        data = np.frombuffer(b"".join(parts), dtype=np.uint8).copy()
+        so, oo = np.zeros(len(parts) + 1, dtype=np.uint64), np.zeros(len(parts) + 1, dtype=np.uint64)
+        so[1:], oo[1:] = np.cumsum([len(p) for p in parts]), np.cumsum(caps)
+        return (torch.from_numpy(data).to(dev), so, torch.full((int(oo[-1]),), 0xA5, dtype=torch.uint8, device=dev), oo,
+                torch.full((len(parts),), 0x77777777, dtype=torch.int32, device=dev))
+
+    def run(codecs):
+        for c in codecs:
+            c.set_zstd_sequences(True)
+        b_in, b_so, b_out, b_oo, b_sizes = spans(blocks, [32, 32])
+        f_in, f_so, f_out, f_oo, f_sizes = spans(frames, [64, 128])
+        body = np.concatenate(bodies[LZ4])
+        offs = np.zeros(10, dtype=np.uint64)
+        offs[1:] = np.cumsum([b.size for b in bodies[LZ4]])
+        d_body = torch.from_numpy(body).to(dev)
+        d_points = torch.full((9 * 3 * info.point_step,), 0x5A, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        codecs[0].lz4_decompress_device(b_in.data_ptr(), b_so, b_out.data_ptr(), b_oo, b_sizes.data_ptr())
+        got, verdicts, rc = codecs[1].decode_stage2_gather(native.STAGE2_ZSTD, bodies[ZSTD], [3] * 9, expanded=expanded,
+                                                           out=np.full(9 * 3 * info.point_step, 0x5A, dtype=np.uint8))
+        codecs[2].zstd_decompress_device(f_in.data_ptr(), f_so, f_out.data_ptr(), f_oo, f_sizes.data_ptr())
+        codecs[3].decode_lz4_device(d_body.data_ptr(), offs, np.full(9, 3, dtype=np.uint64), d_points.data_ptr(), d_points.numel())
+        for c in set(codecs):
+            c.synchronize()
+            c.status()
+        return (b_out.cpu().numpy().tobytes(), b_sizes.cpu().tolist(), [g.tobytes() for g in got], verdicts.tolist(), rc,
+                f_out.cpu().numpy().tobytes(), f_sizes.cpu().tolist(), d_points.cpu().numpy().tobytes())
+
+    shared = native.Codec(native.Plan(info))
+    fresh = [native.Codec(native.Plan(info)) for _ in range(4)]
+    a, b = run([shared] * 4), run(fresh)
+    for c in [shared] + fresh:
+        c.close()
+    assert a == b
+    b_out, b_sizes, got, verdicts, rc, f_out, f_sizes, points = a
+    assert b_sizes == [18, 18] and b_out == lits[0] + b"\xa5" * 14 + lits[1] + b"\xa5" * 14
+    assert rc == 0 and got == [w.tobytes() for w in want_points[ZSTD]] and verdicts == [p.size for p in payloads[ZSTD]]
+    assert f_sizes == [40, 100] and f_out == texts[0] + b"\xa5" * 24 + texts[1] + b"\xa5" * 28
+    assert points == b"".join(w.tobytes() for w in want_points[LZ4])

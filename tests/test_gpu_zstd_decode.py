@@ -249,3 +249,56 @@ def test_zstd_decompress_more_blocks_than_the_workspace_is_host():
     codec.close()
     assert code == ERR_UNSUPPORTED and [int(s) for s in sizes] == [c, HOST, c]
     assert spans[0].tobytes() == p and spans[2].tobytes() == p and np.all(spans[1] == FILL)
+
+
+# ---- the arguments either decompress call refuses: the code and the text of cldn_hip_last_error, in the order of the checks ------
+ERR_ARG = -1
+_SPAN_2GIB = 1 << 31
+
+
+def _refused_arguments():
+    """(label, overrides of a valid one-span HOST call, return code, error text with {who} for lz4 / zstd)"""
+    return [
+        ("source tag", dict(src_loc=7), ERR_ARG, "invalid memory location tag"),
+        ("output tag", dict(out_loc=7), ERR_ARG, "invalid memory location tag"),
+        ("no source offsets", dict(src_offsets=None), ERR_ARG, "{who}_decompress: NULL offsets / sizes"),
+        ("no output offsets", dict(out_offsets=None), ERR_ARG, "{who}_decompress: NULL offsets / sizes"),
+        ("no sizes", dict(sizes=None), ERR_ARG, "{who}_decompress: NULL offsets / sizes"),
+        ("device sizes at an odd address", dict(out_loc=1, sizes_shift=1), ERR_ARG, "{who}_decompress: device sizes must be 4-byte aligned"),
+        ("descending source offsets", dict(src_offsets=[5, 1]), ERR_ARG, "{who}_decompress: offsets must be ascending"),
+        ("descending output offsets", dict(out_offsets=[9, 4]), ERR_ARG, "{who}_decompress: offsets must be ascending"),
+        ("source span of 2 GiB", dict(src=None, out=None, src_offsets=[0, _SPAN_2GIB], out_offsets=[0, 0]), ERR_UNSUPPORTED,
+         "{who}_decompress: block or output span of more than 2 GiB"),
+        ("output span of 2 GiB", dict(src=None, out=None, src_offsets=[0, 0], out_offsets=[7, 7 + _SPAN_2GIB]), ERR_UNSUPPORTED,
+         "{who}_decompress: block or output span of more than 2 GiB"),
+        ("no source", dict(src=None), ERR_ARG, "{who}_decompress: NULL buffer"),
+        ("no output", dict(out=None), ERR_ARG, "{who}_decompress: NULL buffer"),
+    ]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("who", ["lz4", "zstd"])
+def test_decompress_calls_refuse_arguments_with_their_code_and_text(who):
+    """None of these reaches a kernel: every check lies in front of the call's first device work."""
+    import ctypes as C
+    from cloudini_amd import native
+    codec = _codec()
+    fn = getattr(native.lib(), f"cldn_hip_{who}_decompress")
+    u64p = C.POINTER(C.c_uint64)
+
+    def call(src_loc=0, out_loc=0, src=b"\0", out=b"\0\0\0\0", src_offsets=(0, 1), out_offsets=(0, 4), sizes=True, sizes_shift=0, n=1):
+        src_a = None if src is None else np.frombuffer(src, dtype=np.uint8).copy()
+        out_a = None if out is None else np.frombuffer(out, dtype=np.uint8).copy()
+        so = None if src_offsets is None else np.array(src_offsets, dtype=np.uint64)
+        oo = None if out_offsets is None else np.array(out_offsets, dtype=np.uint64)
+        sz = np.zeros(2, dtype=np.uint32) if sizes else None
+        rc = fn(codec._h, None if src_a is None else src_a.ctypes.data, src_loc, None if so is None else so.ctypes.data_as(u64p), n,
+                None if out_a is None else out_a.ctypes.data, out_loc, None if oo is None else oo.ctypes.data_as(u64p),
+                None if sz is None else sz.ctypes.data + sizes_shift)
+        return rc, native.lib().cldn_hip_last_error().decode()
+
+    for label, overrides, code, text in _refused_arguments():
+        assert call(**overrides) == (code, text.format(who=who)), label
+    # no spans: OK whatever else is missing
+    assert call(n=0, src=None, out=None, src_offsets=None, out_offsets=None, sizes=None)[0] == 0
+    codec.close()
