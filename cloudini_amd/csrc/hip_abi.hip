@@ -1554,7 +1554,7 @@ static int viz_check_args(int points_loc, int out_loc, uint32_t point_step, uint
   return CLDN_HIP_OK;
 }
 
-// points of the batch, after the per-cloud and per-batch limits
+// points of the batch, after the per-cloud and per-batch limits (nothing is allocated or read before them)
 static int viz_batch_points(const uint64_t* cloud_points, uint32_t n_clouds, uint64_t* total_out) {
   uint64_t total = 0;
   for (uint32_t k = 0; k < n_clouds; ++k) {
@@ -1563,6 +1563,11 @@ static int viz_batch_points(const uint64_t* cloud_points, uint32_t n_clouds, uin
     if (total >= 0xffffffffull)  // (block offsets and ranks are 32-bit)
       return fail(CLDN_HIP_ERR_UNSUPPORTED, "viz_preprocess: more than 2^32 - 2 points in one batch");
   }
+  // a cloud's table has viz_table_capacity(n) slots and a slot index is kept in 32 bits, 0xffffffff meaning "dropped": 2^31
+  // slots (n <= 2^30) is the largest table in which every slot has an index of its own
+  for (uint32_t k = 0; k < n_clouds; ++k)
+    if (cloud_points[k] > (1ull << 30))
+      return fail(CLDN_HIP_ERR_UNSUPPORTED, "viz_preprocess: more than 2^30 points in one cloud");
   *total_out = total;
   return CLDN_HIP_OK;
 }

@@ -377,8 +377,11 @@ int cldn_hip_viz_preprocess(cldn_hip_codec_t* codec, const void* points, int poi
  * xyz_offset and resolution) is filtered on its own -- a voxel is never shared between clouds, two identical clouds each keep
  * what they would keep alone. The survivors of all clouds land back to back in `out`, batch order: the `points` layout of
  * cldn_hip_encode_stage1 with cloud_points = kept_points. kept_points: HOST [n_clouds]. `out` must hold every input point
- * (sum of cloud_points[k] * point_step bytes) and must not overlap `points`; buffers may have any byte alignment. A cloud is
- * limited to 2^32 - 2 points, and so is the batch. The launch count does not depend on n_clouds: one table clear, four
+ * (sum of cloud_points[k] * point_step bytes) and must not overlap `points`; buffers may have any byte alignment. The
+ * batch is limited to 2^32 - 2 points (ranks are 32-bit) and a cloud to 2^30 points: its table then has at most 2^31 slots,
+ * the largest in which every slot has a 32-bit index of its own next to the "dropped" mark. More is
+ * CLDN_HIP_ERR_UNSUPPORTED, for cldn_hip_viz_preprocess and the fused calls below as well, before anything is allocated
+ * or read. The launch count does not depend on n_clouds: one table clear, four
  * kernels, one copy of n_clouds + 1 counts, ONE synchronisation per call. cldn_hip_viz_preprocess is the n_clouds == 1 case.
  *
  * Workspace (grow-only, the codec's): 16 bytes per table slot, cloud k taking the smallest power of two >= 2 * cloud_points[k]
