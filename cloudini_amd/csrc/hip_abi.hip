@@ -19,6 +19,7 @@
 
 #include "cloudini_hip.h"
 #include "decode_workspace.h"
+#include "encode_workspace.h"
 #include "stage1_device.h"
 #include "stage1_launch.h"
 
@@ -776,8 +777,8 @@ __attribute__((visibility("default"))) int cldn_hip_debug_decode_split(cldn_hip_
 __attribute__((visibility("default"))) uint32_t cldn_hip_debug_zstd_seq_ring(void) { return zstd_seq_ring_bytes(); }
 
 // Test hook, outside the boundary like the ones above: what the codec's last decode call decided, read from its workspace behind a
-// stream synchronise (tests/test_gpu_locate.py holds it against tests/locate_model.py). words: status words 8..15 (kStatFastRegular
-// .. kStatDvGuess, stage1_decode.h). Per chunk, `capacity` entries each (any may be NULL): reg_end_pre / slices_done / sec_cols as the
+// stream synchronise (tests/test_gpu_locate.py holds it against tests/locate_model.py). words: the decode counters (kStatFastRegular
+// .. kStatDvGuess, status_block.h). Per chunk, `capacity` entries each (any may be NULL): reg_end_pre / slices_done / sec_cols as the
 // kernels in front of the point kernel left them, reg_end / sec_done as the call left them. Arrays no kernel of the call's route
 // writes hold stale bytes, and any later call of the codec reuses the status block: ask straight after the decode call.
 // *n_chunks: chunks of that call (0: no decode call yet); more than `capacity` is an error.
@@ -785,7 +786,7 @@ __attribute__((visibility("default"))) int cldn_hip_debug_decode_trace(cldn_hip_
                                                                        uint32_t* n_chunks, uint32_t* reg_end_pre, uint32_t* slices_done,
                                                                        uint8_t* sec_cols, uint32_t* reg_end, uint8_t* sec_done) {
   if (!c || !words || !n_chunks) return fail(CLDN_HIP_ERR_ARG, "decode_trace: NULL argument");
-  memset(words, 0, 8 * sizeof(uint32_t));
+  memset(words, 0, kStatCount * sizeof(uint32_t));
   const cldn_hip_codec::DecTrace& t = c->dec_trace;
   *n_chunks = t.n_chunks;
   if (!c->d_status.p) return CLDN_HIP_OK;
@@ -793,7 +794,7 @@ __attribute__((visibility("default"))) int cldn_hip_debug_decode_trace(cldn_hip_
   if (t.n_chunks > capacity) return fail(CLDN_HIP_ERR_CAPACITY, "decode_trace: %u chunks, room for %u", t.n_chunks, capacity);
   ENTER_DEVICE(c->device);
   HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(words, (const uint32_t*)c->d_status.p + 8, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(words, (const uint32_t*)c->d_status.p + kStatFirst, kStatCount * sizeof(uint32_t), hipMemcpyDeviceToHost));
   const size_t n = t.n_chunks;
   if (n && reg_end_pre) HIP_TRY(hipMemcpy(reg_end_pre, t.reg_end_pre, n * 4u, hipMemcpyDeviceToHost));
   if (n && slices_done) HIP_TRY(hipMemcpy(slices_done, t.slices_done, n * 4u, hipMemcpyDeviceToHost));
@@ -1584,14 +1585,14 @@ static int viz_filter_batch(cldn_hip_codec* c, const uint8_t* d_points, const ui
     n_blocks64 += (cloud_points[k] + kVizBlockPoints - 1u) / kVizBlockPoints;
   }
   const uint32_t n_blocks = (uint32_t)n_blocks64;  // (< 2^32 points in the batch)
-  const size_t clouds_b = ((size_t)n_clouds * sizeof(VizCloud) + 63u) & ~size_t(63);
-  const size_t blocks_b = ((size_t)n_blocks * sizeof(VizBlock) + 63u) & ~size_t(63);
   const size_t kept_b = (size_t)(n_clouds + 1u) * sizeof(uint64_t);
+  VizCloud* hc;
+  VizBlock* hb;
+  uint64_t* h_kept;
+  size_t tables_b;  // what the device gets: the clouds and the blocks
   // (the previous viz call ended with a synchronisation behind its upload and its readback: the staging buffer is free)
-  if ((rc = c->h_viz.ensure(clouds_b + blocks_b + kept_b)) != CLDN_HIP_OK) return rc;
-  VizCloud* hc = (VizCloud*)c->h_viz.p;
-  VizBlock* hb = (VizBlock*)((uint8_t*)c->h_viz.p + clouds_b);
-  uint64_t* h_kept = (uint64_t*)((uint8_t*)c->h_viz.p + clouds_b + blocks_b);
+  if ((rc = c->h_viz.ensure(carve_viz_tables(nullptr, n_clouds, n_blocks, &hc, &hb, &tables_b, &h_kept))) != CLDN_HIP_OK) return rc;
+  carve_viz_tables(c->h_viz.p, n_clouds, n_blocks, &hc, &hb, &tables_b, &h_kept);
   const uint64_t limit = c->viz_group_slots ? c->viz_group_slots : (uint64_t)CLDN_HIP_VIZ_GROUP_SLOTS;
   std::vector<VizGroup> groups(1, VizGroup{0u, 0u, 0ull});
   uint64_t first = 0, max_slots = 0;
@@ -1617,13 +1618,13 @@ static int viz_filter_batch(cldn_hip_codec* c, const uint8_t* d_points, const ui
     max_slots = std::max(max_slots, G.table_slots);
     first += n;
   }
-  if ((rc = c->d_viz_tables.ensure(clouds_b + blocks_b)) != CLDN_HIP_OK) return rc;
+  if ((rc = c->d_viz_tables.ensure(tables_b)) != CLDN_HIP_OK) return rc;
   if ((rc = c->d_viz_keys.ensure((size_t)max_slots * 16u)) != CLDN_HIP_OK) return rc;  // {key, first index, pad} per slot
   if ((rc = c->d_viz_slot.ensure((size_t)n_points * 4u)) != CLDN_HIP_OK) return rc;
   if ((rc = c->d_viz_blocks.ensure((size_t)n_blocks * 4u + 16u)) != CLDN_HIP_OK) return rc;
   if ((rc = c->d_viz_bits.ensure((size_t)n_blocks * (kVizBlockPoints / 8u) + 16u)) != CLDN_HIP_OK) return rc;
   if ((rc = c->d_viz_kept.ensure(kept_b)) != CLDN_HIP_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_viz_tables.p, c->h_viz.p, clouds_b + blocks_b, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_viz_tables.p, c->h_viz.p, tables_b, hipMemcpyHostToDevice, c->stream));
   VizLaunch L;
   L.stream = c->stream;
   L.points = d_points;
@@ -1632,8 +1633,7 @@ static int viz_filter_batch(cldn_hip_codec* c, const uint8_t* d_points, const ui
   L.point_step = point_step;
   L.xyz_offset = xyz_offset;
   L.inv_res = 1.0f / resolution;  // const float inv_res = 1.0f / xyz_res (ros_msg_utils.cpp:272)
-  L.clouds = (const VizCloud*)c->d_viz_tables.p;
-  L.blocks = (const VizBlock*)((const uint8_t*)c->d_viz_tables.p + clouds_b);
+  carve_viz_tables(c->d_viz_tables.p, n_clouds, n_blocks, &L.clouds, &L.blocks, &tables_b);
   L.groups = groups.data();
   L.n_groups = (uint32_t)groups.size();
   L.keys = (unsigned long long*)c->d_viz_keys.p;
@@ -1786,10 +1786,10 @@ int cldn_hip_codec_zstd_matches(const cldn_hip_codec_t* c) { return c && c->zstd
 
 int cldn_hip_codec_decode_stats(cldn_hip_codec_t* c, uint32_t stats[4]) {
   if (!c || !stats) return fail(CLDN_HIP_ERR_ARG, "decode_stats: NULL argument");
-  memset(stats, 0, 4 * sizeof(uint32_t));
+  memset(stats, 0, kStatPublicCount * sizeof(uint32_t));
   if (!c->d_status.p) return CLDN_HIP_OK;
   ENTER_DEVICE(c->device);
-  HIP_TRY(hipMemcpyAsync(stats, (const uint32_t*)c->d_status.p + 8, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(stats, (const uint32_t*)c->d_status.p + kStatFirst, kStatPublicCount * sizeof(uint32_t), hipMemcpyDeviceToHost,
                          c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return CLDN_HIP_OK;
@@ -1935,8 +1935,8 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   if (stream_bytes && !streams && !gather) return fail(CLDN_HIP_ERR_ARG, "streams is NULL");
 
   int rc;
-  if ((rc = c->d_status.ensure(256)) != CLDN_HIP_OK) return rc;
-  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, 256, c->stream));
+  if ((rc = c->d_status.ensure(kStatusBytes)) != CLDN_HIP_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, kStatusBytes, c->stream));
   // tables: [stream_offsets u64 | cloud_first_point u64 | cloud_first_chunk u32] (n_clouds + 1 entries each)
   const size_t ne = (size_t)n_clouds + 1;
   const size_t table_bytes = ne * 8 + ne * 8 + ne * 4;
@@ -2108,9 +2108,9 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   }
   if (c->dec_stats_chunks && c->ev_dec_stats && hipEventQuery(c->ev_dec_stats) == hipSuccess) {  // an earlier call's counters have landed
     const uint32_t* hs = (const uint32_t*)c->h_dec_stats.p;
-    c->dec_palette_hint = hs[4] == c->dec_stats_chunks && hs[2] == 0u && hs[3] == 0u;  // all folded by the guess, nothing serial
-    // (kStatDvChunks = word 13, kStatDvMode = word 14: no chunk with a DeltaVarint section / every chunk's decoded by k_section_dv_w)
-    c->dec_dv_hint = hs[6] == 0u ? 1u : (hs[5] == c->dec_stats_chunks && hs[2] == 0u && hs[3] == 0u ? 2u : 0u);
+    const bool none_serial = hs[kStatSerialChunks - kStatFirst] == 0u && hs[kStatSerialSections - kStatFirst] == 0u;
+    c->dec_palette_hint = hs[kStatFoldedByGuess - kStatFirst] == c->dec_stats_chunks && none_serial;
+    c->dec_dv_hint = hs[kStatDvMode - kStatFirst] == 0u ? 1u : (hs[kStatDvChunks - kStatFirst] == c->dec_stats_chunks && none_serial ? 2u : 0u);
     c->dec_stats_chunks = 0;
     c->dec_stats_seen = true;
   }
@@ -2145,7 +2145,7 @@ static int decode_framed(cldn_hip_codec_t* c, const void* streams, int streams_l
   if (n_chunks && c->plan.uses_v5 && c->dec_stats_chunks == 0 && (!c->dec_stats_seen || (c->dec_call_index & 3u) == 0u) &&
       c->h_dec_stats.ensure(64) == CLDN_HIP_OK) {  // (no copy in flight)
     if (!c->ev_dec_stats) HIP_TRY(hipEventCreateWithFlags(&c->ev_dec_stats, hipEventDisableTiming));
-    HIP_TRY(hipMemcpyAsync(c->h_dec_stats.p, (const uint32_t*)c->d_status.p + 8, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_dec_stats.p, (const uint32_t*)c->d_status.p + kStatFirst, kStatCount * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(c->ev_dec_stats, c->stream));
     c->dec_stats_chunks = n_chunks;
   }
@@ -2215,8 +2215,8 @@ static int decompress_spans(cldn_hip_codec_t* c, int kind, const void* src, int 
   if ((b_bytes && !src) || (o_bytes && !out)) return fail(CLDN_HIP_ERR_ARG, "%s_decompress: NULL buffer", who);
   ENTER_DEVICE(c->device);
   int rc;
-  if ((rc = c->d_status.ensure(256)) != CLDN_HIP_OK) return rc;
-  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, 256, c->stream));
+  if ((rc = c->d_status.ensure(kStatusBytes)) != CLDN_HIP_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, kStatusBytes, c->stream));
   // tables: [src offsets u64 | out offsets u64] relative to the first block / span, [sizes u32] for HOST outputs
   const size_t ne = (size_t)n + 1;
   SpanTables T;
@@ -2314,8 +2314,8 @@ int cldn_hip_decode_stage1_unframed(cldn_hip_codec_t* c, const void* payload, ui
   const uint32_t step = c->plan.dev.point_step;
   const uint64_t cap_points = std::min<uint64_t>(out_capacity / step, 0xffffffffull);
   int rc;
-  if ((rc = c->d_status.ensure(256)) != CLDN_HIP_OK) return rc;
-  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, 256, c->stream));
+  if ((rc = c->d_status.ensure(kStatusBytes)) != CLDN_HIP_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, kStatusBytes, c->stream));
   if ((rc = c->d_dec_meta.ensure(256)) != CLDN_HIP_OK) return rc;
   const uint8_t* d_payload = (const uint8_t*)payload;
   if (payload_loc == CLDN_HIP_HOST) {

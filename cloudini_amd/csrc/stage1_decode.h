@@ -18,23 +18,7 @@
 
 namespace cldn {
 
-// decode statistics behind the status word (uint32 indexes into the codec's status buffer): chunks whose regular
-// stream / sections went through the parallel kernels, and chunks / section sets the serial kernel had to do
-constexpr uint32_t kStatFastRegular = 8, kStatFastSections = 9, kStatSerialChunks = 10, kStatSerialSections = 11;
-// round 5: chunks whose sections the point kernel folded as small Palettes found from the end of the payload (not taken from
-// columns): when that was every chunk of a call, the codec's next call skips the kernels that locate sections and decode them
-// into columns (hip_abi.hip: dec_palette_hint)
-constexpr uint32_t kStatFoldedByGuess = 12;
-// round 6: chunks whose lone DeltaVarint section k_section_dv_w decoded. All of a call's chunks: the codec's next calls do not
-// launch k_sections_cols_fast (it would find nothing to do); no chunk with a DeltaVarint section at all (kStatDvMode): they do
-// not launch k_section_dv_w. Both are accelerators in
-// front of k_decode_sections_cols, which decodes whatever is left whichever was launched (hip_abi.hip: dec_dv_hint)
-constexpr uint32_t kStatDvChunks = 13;
-constexpr uint32_t kStatDvMode = 14;  // chunks whose section k_locate_sections found to begin with mode byte 0 (whoever decodes it)
-// chunks k_locate_sections located by its DeltaVarint guess from the payload's end. Read by tests only (cldn_hip_debug_decode_trace):
-// a guess that was right leaves the same offset, mode byte and kStatDvMode as the count from the front
-constexpr uint32_t kStatDvGuess = 15;
-
+// (the decode counters kStat*: status_block.h)
 // (struct DecChunk: stage1_device.h -- the LZ4 block decoder of lz4_decode.hip fills the same table)
 
 // The three per-cloud tables of a call (stream offsets, first point, first chunk; n_clouds + 1 entries each) for calls of a

@@ -3,6 +3,8 @@
 
 #include <stdint.h>
 
+#include "status_block.h"  // the status word's ST_* bits and the words behind it
+
 #if defined(__HIPCC__) || __has_include(<hip/hip_runtime.h>)
 #include <hip/hip_runtime.h>
 #else
@@ -127,17 +129,6 @@ struct DecChunk {
   uint32_t cloud;
   uint32_t valid;     // 0 = do not touch; 1 = chunk of n_points points; 2 = unframed payload of a wire-version-2 stream:
                       // points until the payload is empty, n_points = the points the output buffer has room for
-};
-
-// status word bits (device side, sticky)
-enum : uint32_t {
-  ST_OUT_OVERFLOW = 1u,    // compacted stream did not fit the output capacity
-  ST_CORRUPT = 2u,         // decode: malformed input
-  ST_PALETTE_FULL = 4u,    // internal: LDS palette table overflowed (handled by the global-table path)
-  ST_FINISH_TIMEOUT = 8u,  // internal: a workgroup of k_finish waited too long for a predecessor's chunk size
-  ST_LZ4_REJECT = 16u,     // set next to ST_CORRUPT: what was malformed is an LZ4 block (lz4_decode.hip)
-  ST_ZSTD_REJECT = 32u,    // set next to ST_CORRUPT: what was malformed is a ZSTD frame (zstd_decode.hip)
-  ST_ZSTD_HOST = 64u       // a ZSTD frame carries sequences or options the device decoder does not take
 };
 
 // ---- piece kernel (stage1_fused.h) ----

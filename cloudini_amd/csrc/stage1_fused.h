@@ -194,8 +194,8 @@ struct FusedArgs {
   // clear != 0 (never with intra): the launch zeroes what the call's later launches expect zeroed, so that no memset runs in
   // front of it (a launch and a dependent boundary on the stream per call). Per chunk, by the workgroup of its quad 0: the
   // segment entries [P/4, segs_per_chunk) -- the regular entries a short chunk does not use and the two per adaptive field --
-  // and the chunk's n_adaptive fallback flags. Once, by the first piece workgroup: the 256-byte status block (status word,
-  // counters, k_finish's ticket, contiguity flag) and k_finish's anchors. No workgroup of this launch reads or writes any of
+  // and the chunk's n_adaptive fallback flags. Once, by the first piece workgroup: the status block (status_block.h: status
+  // word, counters, k_finish's ticket, contiguity flag) and k_finish's anchors. No workgroup of this launch reads or writes any of
   // these (the status word is touched by the intra branch only); every reader runs in a later launch of the stream.
   uint32_t clear;
   uint32_t n_anchor;             // words of `anchor`
@@ -670,7 +670,8 @@ __device__ __forceinline__ void fused_body(const DevPlan& plan, const FusedArgs&
       if (tid < na) A.flags[(size_t)pd.chunk * na + tid] = 0u;
     }
     if (blockIdx.x == A.n_probe) {  // the first piece workgroup, with or without probe workgroups in front of it
-      if (tid < 64u) A.status[tid] = 0u;
+      static_assert(kStatusWords <= kFusedThreads, "one thread per word of the status block");
+      if (tid < kStatusWords) A.status[tid] = 0u;
       for (uint32_t i = tid; i < A.n_anchor; i += kFusedThreads) A.anchor[i] = 0ull;
     }
   }

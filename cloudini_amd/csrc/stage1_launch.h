@@ -196,6 +196,7 @@ struct VizBlock {
   uint32_t cloud;
   uint32_t first;                 // cloud-local index of the block's first point
 };
+static_assert(sizeof(VizCloud) == 40 && sizeof(VizBlock) == 8, "tests/workspace_shim.cpp carves the tables with stand-ins of these sizes");
 struct VizGroup {                 // consecutive clouds whose tables share the table memory
   uint32_t first_block, n_blocks;
   uint64_t table_slots;           // sum of the group's table capacities

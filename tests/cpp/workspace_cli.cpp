@@ -1,4 +1,4 @@
-// Every workspace of stage2_launch.h and decode_workspace.h, allocated with malloc at exactly the size its carve gives over
+// Every workspace of stage2_launch.h, decode_workspace.h and encode_workspace.h, allocated with malloc at exactly the size its carve gives over
 // NULL, carved, and every array written over the length its struct documents with a byte value of its own, then read back.
 // The lengths and alignments below restate the comments of the structs; nothing here asks the carver for them. Built with
 // -fsanitize=address,undefined by tests/test_workspace_carve.py: a write behind the allocation aborts, two arrays that
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "decode_workspace.h"
+#include "encode_workspace.h"
 
 using namespace cldn;
 
@@ -197,9 +198,41 @@ bool zstd_chunks(uint32_t mr, uint32_t nc, bool seq, uint64_t slot_bytes) {
   return check("d_zsd_ws", b.p, total, r, 0);
 }
 
+// ---- encode_workspace.h ----
+struct VizCloudLike {  // as large as VizCloud and VizBlock (stage1_launch.h holds them to these sizes)
+  uint64_t q[4];
+  uint32_t w[2];
+};
+struct VizBlockLike {
+  uint32_t w[2];
+};
+struct VizPtrs {  // h_viz's tables (and VizLaunch::clouds, ::blocks of the device copy)
+  VizCloudLike* clouds;
+  VizBlockLike* blocks;
+};
+
+bool viz_tables(uint32_t n_clouds, uint32_t n_blocks) {
+  VizPtrs H, D;
+  uint64_t* kept = nullptr;
+  size_t dev = 0, dev2 = 0;
+  const size_t total = carve_viz_tables(nullptr, n_clouds, n_blocks, &H.clouds, &H.blocks, &dev, &kept);
+  Block b(total);
+  if (carve_viz_tables(b.p, n_clouds, n_blocks, &H.clouds, &H.blocks, &dev, &kept) != total || (uint8_t*)kept != b.p + dev) return false;
+  if (!check("h_viz", b.p, total,
+             {{"clouds", H.clouds, (size_t)n_clouds * sizeof(VizCloudLike), 8}, {"blocks", H.blocks, (size_t)n_blocks * sizeof(VizBlockLike), 64},
+              {"kept", kept, ((size_t)n_clouds + 1) * 8, 64}},
+             0))
+    return false;
+  --g_checked;  // (one case: the device copy below belongs to it)
+  Block d(dev);  // d_viz_tables: the prefix in front of the kept counts
+  if (carve_viz_tables(d.p, n_clouds, n_blocks, &D.clouds, &D.blocks, &dev2) != total || dev2 != dev) return false;
+  return check("d_viz_tables", d.p, dev,
+               {{"clouds", D.clouds, (size_t)n_clouds * sizeof(VizCloudLike), 8}, {"blocks", D.blocks, (size_t)n_blocks * sizeof(VizBlockLike), 64}}, 0);
+}
+
 }  // namespace
 
-#define RUN(call)                             \
+#define RUN(call)                            \
   do {                                        \
     if (!(call)) {                            \
       fprintf(stderr, "failed: %s\n", #call); \
@@ -230,6 +263,8 @@ int main() {
       for (int seq = 0; seq < 2; ++seq)
         for (uint32_t mr : {1, 100}) RUN(zstd_chunks(mr, nc, seq != 0, (uint64_t)nc * 12352u));
     }
+  for (uint32_t n_clouds : {1, 8, 300})
+    for (uint32_t n_blocks : {0, 1, 1000}) RUN(viz_tables(n_clouds, n_blocks));
   printf("ok %d\n", g_checked);
   return 0;
 }

@@ -218,8 +218,8 @@ def test_the_modes_array_at_any_address(oracle, offsets, sizes):
 
 
 def test_paths_that_keep_the_memset_between_calls_that_lost_it(oracle):
-    """framed, chunk table + cldn_hip_frame_chunks, framed, device LZ4, forced modes, framed -- one codec, another batch shape
-    every time."""
+    """framed, chunk table + cldn_hip_frame_chunks, a decode call, framed, device LZ4, forced modes, framed -- one codec, another
+    batch shape every time."""
     d = Dev()
     a = [xyzi(70000, 100), xyzi(33000, 101)]
     b = [xyzi(33000, 102 + k) for k in range(3)]
@@ -231,6 +231,16 @@ def test_paths_that_keep_the_memset_between_calls_that_lost_it(oracle):
         assert table.n_chunks == sum((int(n) + 32767) // 32768 for n in counts)
         d.codec.frame_chunks_device(d_out.data_ptr(), cap, d_off.data_ptr(), d_sizes.data_ptr())
     d.check(oracle, b, "chunk table", run=chunk_table)
+    # a decode call in between zeroes the status block alone and leaves its counters there: the streams just produced (the
+    # oracle's, byte for byte) back into points -- the input within the resolution, the oracle's decode to the byte
+    streams, offs, _sizes, _modes = expect(oracle, b)
+    d_streams = d.torch.from_numpy(streams).to(d.dev)
+    d_dec = d.torch.full((sum(q.size for q in b),), 0x5A, dtype=d.torch.uint8, device=d.dev)
+    d.codec.decode_device(d_streams.data_ptr(), offs.astype(np.uint64), np.array([q.size // 16 for q in b], dtype=np.uint64),
+                          d_dec.data_ptr(), d_dec.numel())
+    d.codec.synchronize()
+    d.codec.status()
+    assert np.array_equal(d_dec.cpu().numpy(), np.concatenate([oracle.decode_stage1(_INFO, want_of(oracle, q)[0], q.size // 16, fill=0x5A) for q in b]))
     d.check(oracle, c, "framed 2")
 
     d.codec.set_stage2(1)

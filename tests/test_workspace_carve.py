@@ -1,15 +1,18 @@
-"""The memory the stage-2 kernels and the decode calls run in: every workspace is laid out by one carve function
+"""The memory the stage-2 kernels and the viz and decode calls run in: every workspace is laid out by one carve function
 (cloudini_amd/csrc/workspace_carve.h), whose run over NULL is the size the call allocates. No GPU:
-  * stage2_launch.h builds by itself with a plain compiler;
+  * stage2_launch.h, status_block.h and encode_workspace.h each build by themselves with a plain compiler;
   * the sizes against the closed forms the code had before the carve (restated here from stage1_launch.h and hip_abi.hip of
     that time, with the record sizes the shim exports): the encoder workspaces are as large as they were to the byte, the
-    others at least as large and less than one alignment step larger;
+    others at least as large and less than one alignment step larger; the viz tables (encode_workspace.h) as large as they
+    were to the byte;
+  * hip_abi.hip addresses the decode counters and the size of the status block (status_block.h) by name;
   * tests/cpp/workspace_cli.cpp under sanitizers: every array written over its documented length inside an allocation of
     exactly that size -- no overrun, no overlap, the documented alignment, the slack behind the last array;
   * the carver itself."""
 import ctypes as C
 import itertools
 import os
+import re
 import subprocess
 
 import pytest
@@ -27,7 +30,9 @@ ZSTD_SEQ_GRID = list(itertools.product((0, 1, 5, 1025), (0, 1, 9), CHUNKS))     
 ZSTD_GRID = list(itertools.product((0, 1, 9, 257), CHUNKS))                                     # max_blocks, chunks
 ZSTD_DECODE_GRID = list(itertools.product((0, 1, 100, 4097), CHUNKS, (0, 1, 2, 3, 12345, 1000003), (0, 1)))  # max_recs, frames, output bytes, sequences
 ABI_GRID = list(itertools.product((1, 8, 9, 300), (0, 1, 2, 1000)))                             # n_clouds, n_chunks
-PROGRAM_CASES = len(LZ4_GRID) + len(ZSTD_SEQ_GRID) + len(ZSTD_GRID) + len(ZSTD_DECODE_GRID) + len(ABI_GRID) + 4 * (2 + 1 + 1 + 4)
+VIZ_GRID = list(itertools.product((1, 8, 300), (0, 1, 1000)))                                   # n_clouds, viz blocks
+PROGRAM_CASES = (len(LZ4_GRID) + len(ZSTD_SEQ_GRID) + len(ZSTD_GRID) + len(ZSTD_DECODE_GRID) + len(ABI_GRID) + 4 * (2 + 1 + 1 + 4) +
+                 len(VIZ_GRID))
 
 
 @pytest.fixture(scope="module")
@@ -39,7 +44,8 @@ def shim(tmp_path_factory):
     for name, args in (("ws_lz4", [u64, u32]), ("ws_zstd_seq", [u64, u64, u32]), ("ws_zstd", [u64, u32]),
                        ("ws_zstd_decode", [u32, u32, C.c_int, u64]), ("ws_dec_meta", [u32, u32]), ("ws_dec_secs", [u32, u32]),
                        ("ws_span_tables", [u32]), ("ws_s2_gather", [u32]), ("ws_zstd_chunks", [u32, u32, C.c_int, u64, C.POINTER(u64)]),
-                       ("ws_carver", [u64, C.POINTER(u64), u32, C.POINTER(u64)]), ("ws_carver_natural", [C.POINTER(u64)])):
+                       ("ws_carver", [u64, C.POINTER(u64), u32, C.POINTER(u64)]), ("ws_carver_natural", [C.POINTER(u64)]),
+                       ("ws_viz_tables", [u32, u32, C.POINTER(u64), C.POINTER(u64)])):
         getattr(L, name).argtypes = args
         getattr(L, name).restype = u64
     L.ws_sizeof.restype = u32
@@ -48,7 +54,8 @@ def shim(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def sizes(shim):
-    names = ("ZdBlock", "ZdFse", "ZdSeqBlock", "ZdSeqSums", "ZsBlock", "ZsSeqPlan", "ZsSeqInfo", "DecChunk", "LzMatch")
+    names = ("ZdBlock", "ZdFse", "ZdSeqBlock", "ZdSeqSums", "ZsBlock", "ZsSeqPlan", "ZsSeqInfo", "DecChunk", "LzMatch",
+             "VizCloud", "VizBlock")
     s = {n: shim.ws_sizeof(k) for k, n in enumerate(names)}
     assert all(s.values()) and s["LzMatch"] == 8      # (the old ZstdSeqLaunch formula wrote LzMatch as 8u)
     return s
@@ -92,12 +99,26 @@ def old_dec_secs(s, n_adaptive, n_chunks):
     return n_adaptive * n_chunks * s["DecChunk"] + n_chunks * 8 + 256
 
 
+# (hip_abi.hip: clouds_b + blocks_b + kept_b of the viz filter)
+def old_viz_tables(s, n_clouds, n_blocks):
+    return up(n_clouds * s["VizCloud"], 64) + up(n_blocks * s["VizBlock"], 64) + (n_clouds + 1) * 8
+
+
 # ---- tests -----------------------------------------------------------------------------------------------------------------
 
-def test_header_builds_alone(tmp_path):
+def _builds_alone(tmp_path, header):
     src = tmp_path / "alone.cpp"
-    src.write_text('#include "stage2_launch.h"\n')
+    src.write_text('#include "%s"\n' % header)
     subprocess.run(GXX + ["-fsyntax-only", str(src)], check=True)
+
+
+def test_header_builds_alone(tmp_path):
+    _builds_alone(tmp_path, "stage2_launch.h")
+
+
+@pytest.mark.parametrize("header", ["status_block.h", "encode_workspace.h"])
+def test_the_status_block_and_encode_workspace_headers_build_alone(tmp_path, header):
+    _builds_alone(tmp_path, header)
 
 
 def test_encoder_workspaces_are_as_large_as_they_were(shim, sizes):
@@ -125,6 +146,22 @@ def test_abi_workspaces_are_no_smaller_and_less_than_256_bytes_larger(shim, size
             assert 0 <= grown < 256, ("d_dec_secs", na, nc, grown)
         assert shim.ws_span_tables(nc) == (nc + 1) * 16 + nc * 4       # d_lzd_tables
         assert shim.ws_s2_gather(nc) == nc * 8                         # d_s2_gather
+
+
+def test_viz_tables_are_as_large_as_they_were(shim, sizes):
+    at = (C.c_uint64 * 3)()
+    dev = C.c_uint64()
+    for n_clouds, nb in VIZ_GRID:                                                 # h_viz, and its prefix d_viz_tables
+        assert shim.ws_viz_tables(n_clouds, nb, at, C.byref(dev)) == old_viz_tables(sizes, n_clouds, nb), (n_clouds, nb)
+        clouds_b, blocks_b = up(n_clouds * sizes["VizCloud"], 64), up(nb * sizes["VizBlock"], 64)
+        assert list(at) == [0, clouds_b, clouds_b + blocks_b] and dev.value == clouds_b + blocks_b
+
+
+def test_hip_abi_addresses_the_decode_counters_and_the_block_s_size_by_name():
+    """(The encode call still reaches k_finish's ticket and the contiguity flag as d_status.p + 40 and + 42.)"""
+    text = open(os.path.join(CSRC, "hip_abi.hip")).read()
+    assert not re.search(r"d_status\.p\s*\+\s*8\b", text) and not re.search(r"\bhs\[\s*\d", text)
+    assert not re.search(r"d_status\.ensure\(\d", text) and not re.search(r"Memset\w*\(c->d_status\.p, 0, \d", text)  # (its size)
 
 
 def test_zstd_workspace_of_a_decode_call_keeps_the_chunk_sizes_behind_the_decoder_s(shim, sizes):

@@ -1,8 +1,10 @@
-// C entry points around cloudini_amd/csrc/workspace_carve.h, stage2_launch.h and decode_workspace.h for
+// C entry points around cloudini_amd/csrc/workspace_carve.h, stage2_launch.h, decode_workspace.h and encode_workspace.h for
 // tests/test_workspace_carve.py (built with g++; the HIP headers only declare types, no HIP function is called).
 #include <stdint.h>
+#include <string.h>
 
 #include "decode_workspace.h"
+#include "encode_workspace.h"
 
 using namespace cldn;
 
@@ -14,15 +16,24 @@ struct Ptrs {  // the members of DecodeLaunch that carve_dec_meta and carve_dec_
   uint32_t *reg_end, *reg_end_pre, *slices_done, *done_cnt;
   uint8_t *sec_done, *sec_cols, *secs_ok;
 };
+struct VizCloudLike {  // as large as VizCloud and VizBlock (stage1_launch.h holds them to these sizes)
+  uint64_t q[4];
+  uint32_t w[2];
+};
+struct VizBlockLike {
+  uint32_t w[2];
+};
+uint8_t* const kBase = (uint8_t*)(uintptr_t)0x100000;  // (never read or written)
+uint64_t at(const void* p) { return (uint64_t)((const uint8_t*)p - kBase); }
 }  // namespace
 
 extern "C" {
 
-// ZdBlock, ZdFse, ZdSeqBlock, ZdSeqSums, ZsBlock, ZsSeqPlan, ZsSeqInfo, DecChunk, LzMatch
+// ZdBlock, ZdFse, ZdSeqBlock, ZdSeqSums, ZsBlock, ZsSeqPlan, ZsSeqInfo, DecChunk, LzMatch, VizCloud, VizBlock
 uint32_t ws_sizeof(int which) {
-  const size_t s[9] = {sizeof(ZdBlock), sizeof(ZdFse), sizeof(ZdSeqBlock), sizeof(ZdSeqSums), sizeof(ZsBlock), sizeof(ZsSeqPlan),
-                       sizeof(ZsSeqInfo), sizeof(DecChunk), sizeof(LzMatch)};
-  return which >= 0 && which < 9 ? (uint32_t)s[which] : 0u;
+  const size_t s[11] = {sizeof(ZdBlock), sizeof(ZdFse), sizeof(ZdSeqBlock), sizeof(ZdSeqSums), sizeof(ZsBlock), sizeof(ZsSeqPlan),
+                        sizeof(ZsSeqInfo), sizeof(DecChunk), sizeof(LzMatch), sizeof(VizCloudLike), sizeof(VizBlockLike)};
+  return which >= 0 && which < 11 ? (uint32_t)s[which] : 0u;
 }
 
 uint64_t ws_lz4(uint64_t max_subs, uint32_t n_chunks) { return Lz4Launch::workspace_bytes(max_subs, n_chunks); }
@@ -55,6 +66,20 @@ uint64_t ws_zstd_chunks(uint32_t max_recs, uint32_t n_chunks, int seq_on, uint64
   const size_t bytes = carve_zstd_chunks(base, max_recs, n_chunks, seq_on != 0, slot_bytes, Z);
   *sizes_at = (uint64_t)((uint8_t*)Z.sizes - base);
   return bytes == carve_zstd_chunks(nullptr, max_recs, n_chunks, seq_on != 0, slot_bytes, Z) ? bytes : ~0ull;
+}
+
+// The viz tables: the bytes of the run over NULL (~0 if the run over an address differs); `where`: the offsets of clouds,
+// blocks and kept counts; *device_bytes: the prefix that d_viz_tables copies.
+uint64_t ws_viz_tables(uint32_t n_clouds, uint32_t n_blocks, uint64_t where[3], uint64_t* device_bytes) {  // clouds, blocks, kept
+  const VizCloudLike* clouds;  // (const as in VizLaunch)
+  const VizBlockLike* blocks;
+  uint64_t* kept;
+  size_t dev, dev0;
+  const size_t bytes = carve_viz_tables(kBase, n_clouds, n_blocks, &clouds, &blocks, &dev, &kept);
+  const uint64_t w[3] = {at(clouds), at(blocks), at(kept)};
+  memcpy(where, w, sizeof(w));
+  *device_bytes = dev;
+  return bytes == carve_viz_tables(nullptr, n_clouds, n_blocks, &clouds, &blocks, &dev0) && dev0 == dev ? bytes : ~0ull;
 }
 
 // The carver by itself. steps: [n][3] = element bytes (1, 2, 4, 8; 0 = pad), count, alignment. at: [n] the pointers take
