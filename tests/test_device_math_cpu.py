@@ -100,6 +100,27 @@ def test_quantisation_matches_x86_semantics(mathlib):
         assert mathlib.m_quant_rne_i32(float(v), float(m)) == int(np.rint(t))
 
 
+def test_quantisation_on_the_value_grid(mathlib):
+    """Every product of the value grid's rounding and range families (tests/value_grid_cases.py, C and D) through the host branch of the
+    three quant_* functions, against the numpy model the grid's marks are proven in (sweep_model._quantise)."""
+    import sweep_model as SM
+    import value_grid_cases as V
+    fn = {SM.FLOATN: mathlib.m_quant_rne_i32, SM.SCALAR32: mathlib.m_quant_away_f32, SM.SCALAR64: mathlib.m_quant_away_f64}
+    seen = {k: 0 for k in fn}
+    for fam, layout in V.GROUPS:
+        if fam not in ("C", "D"):
+            continue
+        for c in V.family(fam, layout):
+            r32 = np.float32(c.res)
+            for kind, v in zip(V.kinds_of(layout), c.v):
+                m = np.float32(1.0) / r32 if kind == SM.FLOATN else np.float32(1.0 / np.float64(r32)) if kind == SM.SCALAR32 else 1.0 / np.float64(r32)
+                want = SM._quantise(kind, v, r32)
+                for x, w in zip(v[~np.isnan(v)].tolist(), want[~np.isnan(v)].tolist()):
+                    assert fn[kind](x, float(m)) == w, (c.name, kind, x)
+                    seen[kind] += 1
+    assert min(seen.values()) > 1000, seen
+
+
 def test_int_field_widening(mathlib):
     assert mathlib.m_int_as_i64(0xFFFF, 3) == -1 and mathlib.m_int_as_i64(0xFFFF, 4) == 65535
     assert mathlib.m_int_as_i64(0xFFFFFFFF, 5) == -1 and mathlib.m_int_as_i64(0xFFFFFFFF, 6) == 2**32 - 1

@@ -475,3 +475,20 @@ def test_arguments_are_refused_as_the_sweep_refuses_them():
         ones = np.ones((4, n_cand), np.float32)
         both(lambda: codec.sweep_hist_last_encode(ones), lambda: codec.sweep_last_encode(ones))
     _same(codec.sweep_hist_last_encode(good), want, "a refused call leaves the state")
+
+
+# ---- the value grid (tests/value_grid_cases.py): rounding, range and 2^21 edges, each field at res, res / 2 and 2 res -----------------
+import value_grid_cases as VG  # noqa: E402
+
+
+REPORT_GROUPS = VG.report_groups()
+
+
+@pytest.mark.parametrize("name,cs", REPORT_GROUPS, ids=[g[0] for g in REPORT_GROUPS])
+def test_histograms_equal_the_model_on_the_value_grid(name, cs):
+    by_res = {}
+    for c in cs:
+        by_res.setdefault(c.res, []).append(c)
+    for res, group in by_res.items():
+        info = group[0].info()
+        _run(info, [c.cloud() for c in group], S.default_ladders(info, (1.0, 0.5, 2.0)), name, walks=(0, 3))

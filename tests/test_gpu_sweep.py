@@ -442,3 +442,32 @@ def test_arguments():
             codec.sweep_last_encode(np.ones((4, n_cand), np.float32))
         assert e.value.code == -1, n_cand
     _same(codec.sweep_last_encode(good), want)                        # a refused sweep leaves the state too
+
+
+# ---- the value grid (tests/value_grid_cases.py): rounding, range and 2^21 edges, each field at res, res / 2 and 2 res -----------------
+import value_grid_cases as VG  # noqa: E402
+
+
+REPORT_GROUPS = VG.report_groups()
+
+
+def value_grid_batches(cs):
+    """[(info, clouds, ladders)]: the clouds of the group, one batch per resolution"""
+    by_res = {}
+    for c in cs:
+        by_res.setdefault(c.res, []).append(c)
+    out = []
+    for res, group in by_res.items():
+        info = group[0].info()
+        out.append((info, [c.cloud() for c in group], S.default_ladders(info, (1.0, 0.5, 2.0))))
+    return out
+
+
+@pytest.mark.parametrize("name,cs", REPORT_GROUPS, ids=[g[0] for g in REPORT_GROUPS])
+def test_sweep_equals_the_model_on_the_value_grid(name, cs):
+    for info, clouds, ladders in value_grid_batches(cs):
+        sizes = [c.size // info.point_step for c in clouds]
+        want = S.sweep(info, np.concatenate(clouds), sizes, ladders)
+        codec = _codec(info)
+        _same(codec.sweep_clouds_host(clouds, ladders), want, name)
+        codec.close()
