@@ -330,6 +330,11 @@ class Codec:
     def status(self):
         _check(lib().cldn_hip_codec_status(self._h))
 
+    def stream(self) -> int:
+        """cldn_hip_codec_stream: the raw hipStream_t the codec enqueues on (the caller's, or the one it created), as an
+        int -- e.g. for torch.cuda.ExternalStream."""
+        return int(lib().cldn_hip_codec_stream(self._h) or 0)
+
     def viz_preprocess_host(self, cloud, point_step: int, xyz_offset: int, resolution: float) -> np.ndarray:
         """applyVizLossyPreprocessing's data path on host buffers: the surviving points, order preserved."""
         data = np.ascontiguousarray(cloud).view(np.uint8).reshape(-1)
@@ -601,6 +606,12 @@ class Codec:
             self._h, C.c_void_p(streams_ptr), DEVICE, so.ctypes.data_as(C.POINTER(C.c_uint64)),
             cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, C.c_void_p(chunk_sizes_ptr), DEVICE, C.c_void_p(out_ptr),
             int(out_capacity), DEVICE))
+
+    def decode_unframed_device(self, payload_ptr: int, size: int, out_ptr: int, out_capacity: int):
+        """cldn_hip_decode_stage1_unframed on device buffers (wire version 2: one run of points without [u32 size] prefixes,
+        decoded until it is empty). Asynchronous: a payload that holds more points than out_capacity shows in status()."""
+        _check(lib().cldn_hip_decode_stage1_unframed(self._h, C.c_void_p(payload_ptr), int(size), DEVICE, C.c_void_p(out_ptr),
+                                                     int(out_capacity), DEVICE))
 
     # ---- LZ4 blocks back into bytes (cldn_hip_lz4_decompress / cldn_hip_decode_lz4) --------------------------------
     def lz4_decompress_host(self, blocks: Sequence[bytes], capacities: Sequence[int], out: Optional[np.ndarray] = None):

@@ -21,6 +21,22 @@
  * Memory: every data pointer is tagged CLDN_HIP_HOST or CLDN_HIP_DEVICE. With DEVICE pointers a call only
  * enqueues work on the codec's HIP stream (no synchronisation, outputs valid after the stream drains);
  * with HOST outputs the call returns after the results are in host memory.
+ * "No synchronisation" is about results: nothing a DEVICE call hands out is valid before the stream drains. Some DEVICE calls
+ * nevertheless WAIT for the stream inside, for buffers of their own (a pipelined caller plans for these; none changes a byte):
+ *   - an encode call (plain, chunks, viz) whose batch shape -- the cloud_points array -- differs from the previous encode call's:
+ *     the chunk and piece tables go through one pinned staging buffer; a call with the previous shape uploads nothing;
+ *   - every encode call while modes are forced (cldn_hip_codec_force_modes[_per_cloud]);
+ *   - every encode call with at least one point of a plan with a Gorilla-coded field (FLOAT64 without a resolution, wire
+ *     version >= 4), WIDE plans included: the addresses of its pre-pass buffers are uploaded from the call's stack;
+ *   - an encode call with stage 2 on the device whose match lists would exceed 256 MB by the worst-case bound (about 6 M XYZI
+ *     points per call): it waits for stage 1 and reads its size;
+ *   - the viz encode calls, for the survivor counts; cldn_hip_viz_preprocess[_batch]; the gather calls (host inputs anyway);
+ *   - a decode call of more than 8 clouds waits for the table upload of the decode call four such calls earlier (a ring of 4
+ *     pinned buffers); a report call (audit, sweep, histograms, modes) for the table upload of the previous report call;
+ *   - cldn_hip_audit_streams (it reads the decode's status word) and, behind an encode call with DEVICE outputs, the
+ *     *_last_encode calls that decode or read the streams (they read the stream offsets back);
+ *   - any call that has to grow a workspace: hipFree waits for the whole device.
+ * tests/test_gpu_stream_order.py runs every DEVICE call back to back on a busy stream.
  */
 #ifndef CLOUDINI_HIP_H
 #define CLOUDINI_HIP_H

@@ -257,6 +257,7 @@ def _legs(oracle, codec, plan, info, data, n, s1, body, want, number, every_leg)
         d_body = torch.zeros(body.size + 32, dtype=torch.uint8, device=dev)
         d_body[mis_in:mis_in + body.size] = torch.from_numpy(body.copy()).to(dev)
         d_pts = torch.full((data.size + 32,), FILL, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.decode_lz4_device(d_body.data_ptr() + mis_in, np.array([0, body.size], dtype=np.uint64), np.array([n], dtype=np.uint64),
                                 d_pts.data_ptr() + mis_out, data.size)
         codec.status()
@@ -284,11 +285,13 @@ def _legs(oracle, codec, plan, info, data, n, s1, body, want, number, every_leg)
             cap = plan.stage2_bound(n, stage2)
             d_stream = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
             d_off = torch.zeros(2, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
             codec.encode_device(d_in.data_ptr(), np.array([n], dtype=np.uint64), d_stream.data_ptr() + 5, cap, d_off.data_ptr())
             codec.status()
             offs = d_off.cpu().numpy().astype(np.uint64)
             codec.set_stage2(0)
             d_pts = torch.full((max(1, data.size),), FILL, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
             codec.decode_lz4_device(d_stream.data_ptr() + 5, offs, np.array([n], dtype=np.uint64), d_pts.data_ptr(), data.size)
             codec.status()
             assert np.array_equal(d_pts.cpu().numpy()[: data.size], want[: data.size]), (number, "own blocks", stage2)

@@ -77,6 +77,7 @@ def _legs(oracle, plan, info, data, n, s1, body, want):
     d_body = torch.zeros(body.size + 32, dtype=torch.uint8, device=dev)
     d_body[mis_in:mis_in + body.size] = torch.from_numpy(body.copy()).to(dev)
     d_pts = torch.full((data.size + 32,), FILL, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.decode_zstd_device(d_body.data_ptr() + mis_in, np.array([0, body.size], dtype=np.uint64), np.array([n], dtype=np.uint64),
                              d_pts.data_ptr() + mis_out, data.size)
     codec.status()
@@ -204,6 +205,7 @@ def test_decode_zstd_reports_refused_and_host_frames():
         assert e.value.code == code and text in e.value.message
         d_body = torch.from_numpy(bad).to("cuda")
         d_pts = torch.full((data.size,), FILL, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.decode_zstd_device(d_body.data_ptr(), np.array([0, bad.size], dtype=np.uint64), np.array([n], dtype=np.uint64), d_pts.data_ptr(), data.size)
         with pytest.raises(native.CloudiniHipError) as e:
             codec.status()

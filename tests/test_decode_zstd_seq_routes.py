@@ -65,6 +65,7 @@ def test_decode_zstd_of_libzstd_bodies_equals_the_oracle(oracle, name):
     d_body = torch.zeros(body.size + 32, dtype=torch.uint8, device=dev)
     d_body[mis_in:mis_in + body.size] = torch.from_numpy(body.copy()).to(dev)
     d_pts = torch.full((data.size + 32,), FILL, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.decode_zstd_device(d_body.data_ptr() + mis_in, np.array([0, body.size], dtype=np.uint64), np.array([n], dtype=np.uint64),
                              d_pts.data_ptr() + mis_out, data.size)
     codec.status()
@@ -161,6 +162,7 @@ def test_damaged_chunk_framing_in_mid_batch_is_refused_and_the_neighbours_decode
     dev = torch.device("cuda", 0)
     d_body = torch.from_numpy(np.concatenate(bodies)).to(dev)
     d_pts = torch.full((3 * data.size,), FILL, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.decode_zstd_device(d_body.data_ptr(), offs, np.array([n, n, n], dtype=np.uint64), d_pts.data_ptr(), 3 * data.size)
     with pytest.raises(native.CloudiniHipError) as e:
         codec.status()

@@ -140,6 +140,7 @@ def _run_device(codec, cases, r_in=0, r_out=0):
     d_out = torch.full((512 + total + 512,), FILL, dtype=torch.uint8, device=dev)
     base_out = (-d_out.data_ptr()) % 256 + 256 + r_out
     d_sizes = torch.full((len(blocks),), 0x77777777, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.lz4_decompress_device(d_in.data_ptr() + base_in, bo, d_out.data_ptr() + base_out, oo, d_sizes.data_ptr())
     raised = False
     try:
@@ -382,11 +383,13 @@ def test_decode_lz4_equals_the_reference(reflib, oracle, name):
         cap = codec.plan.stage2_bound(n, stage2)
         d_stream = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
         d_off = torch.zeros(2, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.encode_device(d_in.data_ptr(), np.array([n], dtype=np.uint64), d_stream.data_ptr() + 5, cap, d_off.data_ptr())
         codec.status()
         offs = d_off.cpu().numpy().astype(np.uint64)
         codec.set_stage2(0)
         d_pts = torch.zeros(max(1, data.size), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.decode_lz4_device(d_stream.data_ptr() + 5, offs, np.array([n], dtype=np.uint64), d_pts.data_ptr(), data.size)
         codec.status()
         assert np.array_equal(d_pts.cpu().numpy()[: data.size], want), stage2

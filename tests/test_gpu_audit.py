@@ -450,6 +450,7 @@ def test_audit_last_encode_after_encode_device(oracle, stage2, residue):
     _tp, pp, check_p = _dev(data[:sum(sizes) * info.point_step], residue)
     d_out = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
     d_off = torch.zeros(len(sizes) + 1, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.encode_device(pp, sizes, d_out.data_ptr() + residue, cap, d_off.data_ptr())
     got = codec.audit_last_encode()
     dec = [_round_trip(oracle, info, c) for c in clouds]
@@ -472,6 +473,7 @@ def test_audit_last_encode_after_a_framed_chunk_table(oracle):
     codec.encode_chunks_device(pp, [70000])
     cap = codec.plan.stage1_bound(70000)
     d_out = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.frame_chunks_device(d_out.data_ptr(), cap)
     _same(codec.audit_last_encode(), M.audit(info, data, _round_trip(oracle, info, data), [70000]))
 

@@ -542,10 +542,12 @@ def test_decode_with_the_chunk_sizes_given(oracle):
     d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
     d_off = torch.zeros(2, dtype=torch.int64, device=dev)
     d_sizes = torch.zeros(10, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     c5.encode_device(d_in.data_ptr(), np.array([320000], dtype=np.uint64), d_out.data_ptr(), cap, d_off.data_ptr(), d_sizes.data_ptr())
     c5.synchronize()
     offs = d_off.cpu().numpy().astype(np.uint64)
     d_dec = torch.zeros(data.size, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     c5.decode_device(d_out.data_ptr(), offs, np.array([320000], dtype=np.uint64), d_dec.data_ptr(), data.size, d_sizes.data_ptr())
     c5.synchronize()
     c5.status()

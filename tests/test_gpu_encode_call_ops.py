@@ -8,52 +8,15 @@ everything a call hands out with the C oracle, byte for byte: the streams, strea
 import numpy as np
 import pytest
 
-import cases
 from cloudini_amd import synth
+from stream_order_cases import mode_cloud, xyzi  # (the clouds and mode generators, shared with the stream-order plans)
 
 pytestmark = pytest.mark.gpu
 
 DELTA_VARINT, PALETTE, RLE, DELTA_RLE = 0, 1, 2, 3
 
-_XYZI = np.dtype({"names": ["x", "y", "z", "i", "pad"], "formats": ["<f4", "<f4", "<f4", "<u2", "<u2"],
-                  "offsets": [0, 4, 8, 12, 14], "itemsize": 16})
 _INFO = synth.xyzi_info(1)
 _cache = {}
-
-
-def xyzi(n, seed):
-    key = ("xyzi", n, seed)
-    if key not in _cache:
-        _cache[key] = synth.lidar_xyzi(n, seed=seed)[1]
-    return _cache[key]
-
-
-def xyzi_with(values, seed):
-    """An XYZI cloud whose intensity column is `values` (one of the integer generators of tests/cases.py, as uint16)."""
-    v = np.asarray(values)
-    data = xyzi(v.size, seed).copy()
-    data.view(_XYZI)["i"] = v.astype(np.uint16)
-    return data
-
-
-def _gen_values(info_data, n):
-    info, data = info_data
-    v = data.view({1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[info.point_step])
-    return np.resize(v, n)
-
-
-def mode_cloud(mode, n, seed):
-    """n XYZI points whose intensity commits `mode` (asserted on the oracle by the callers, before the device runs)."""
-    seqs = {s[0]: (s[1], s[2]) for s in cases.reference_int_sequences()}
-    if mode == PALETTE:
-        v = _gen_values(cases.palette_stress("grows_u16", n=max(n, 5000), seed=23 + seed), n)
-    elif mode == DELTA_VARINT:
-        v = _gen_values(seqs["ref_u32_random16"], n)      # values below 2^16
-    elif mode == RLE:
-        v = _gen_values(seqs["ref_u16_steps"], n)
-    else:
-        v = _gen_values(seqs["ref_u32_linear"], n) - 100000    # 3 i: no wrap of the 16 bits inside the probe window
-    return xyzi_with(v, seed)
 
 
 def want_of(oracle, cloud, forced=None):
@@ -109,6 +72,7 @@ class Dev:
         d_off = torch.full((len(clouds) + 1,), -1, dtype=torch.int64, device=self.dev)
         d_sizes = torch.full((max(1, n_chunks),), -1, dtype=torch.int32, device=self.dev)
         d_modes = torch.full((len(clouds) + 8,), 0xEE, dtype=torch.uint8, device=self.dev)
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         return d_in, counts, cap, d_out, d_off, d_sizes, d_modes, n_chunks
 
     def check(self, oracle, clouds, tag, offsets=True, sizes=True, modes_at=0, forced=None, run=None):
@@ -236,6 +200,7 @@ def test_paths_that_keep_the_memset_between_calls_that_lost_it(oracle):
     streams, offs, _sizes, _modes = expect(oracle, b)
     d_streams = d.torch.from_numpy(streams).to(d.dev)
     d_dec = d.torch.full((sum(q.size for q in b),), 0x5A, dtype=d.torch.uint8, device=d.dev)
+    d.torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     d.codec.decode_device(d_streams.data_ptr(), offs.astype(np.uint64), np.array([q.size // 16 for q in b], dtype=np.uint64),
                           d_dec.data_ptr(), d_dec.numel())
     d.codec.synchronize()

@@ -317,6 +317,7 @@ def test_chunk_table_holds_the_reference_payloads(oracle, case):
     npts = np.array([c.size // step for c in clouds], dtype=np.uint64)
     host = np.concatenate(clouds) if sum(c.size for c in clouds) else np.zeros(1, np.uint8)
     d_in = torch.from_numpy(host).to(dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     for _round in range(2):  # (the second call runs with the mode hint of the first)
         table = codec.encode_chunks_device(d_in.data_ptr(), npts)
         codec.synchronize()
@@ -342,6 +343,7 @@ def test_chunk_table_holds_the_reference_payloads(oracle, case):
         cap = int(sum(codec.plan.stage1_bound(int(n)) for n in npts))
         d_out = torch.empty(max(1, cap), dtype=torch.uint8, device=dev)
         d_off = torch.zeros(len(clouds) + 1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.frame_chunks_device(d_out.data_ptr(), cap, d_off.data_ptr())
         codec.synchronize()
         codec.status()
@@ -378,12 +380,14 @@ def test_wide_route_through_the_other_entry_points(oracle):
     d_off = torch.zeros(2, dtype=torch.int64, device=dev)
     d_sizes = torch.zeros(2, dtype=torch.int32, device=dev)
     cp = np.array([n], dtype=np.uint64)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.encode_device(d_in.data_ptr(), cp, d_out.data_ptr(), cap, d_off.data_ptr(), d_sizes.data_ptr(), 0)
     codec.synchronize()
     codec.status()
     offs = d_off.cpu().numpy().astype(np.uint64)
     assert int(offs[1]) == want.size and np.array_equal(d_out[: want.size].cpu().numpy(), want)
     d_dec = torch.full((data.size,), 0xC3, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.decode_device(d_out.data_ptr(), offs, cp, d_dec.data_ptr(), data.size, d_sizes.data_ptr())
     codec.synchronize()
     codec.status()

@@ -134,6 +134,7 @@ def _other_entry_points(oracle, codec, plan, info, data, want, n, seed):
         d_off = torch.zeros(2, dtype=torch.int64, device=dev)
         n_chunks = (n + 32767) // 32768
         d_sizes = torch.zeros(max(1, n_chunks), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.encode_device(d_buf.data_ptr() + mis_in, np.array([n], dtype=np.uint64), d_out.data_ptr() + mis_out, cap,
                             d_off.data_ptr(), d_sizes.data_ptr(), 0)
         codec.status()
@@ -141,6 +142,7 @@ def _other_entry_points(oracle, codec, plan, info, data, want, n, seed):
         assert int(offs[0]) == 0 and int(offs[1]) == want.size, (seed, offs, want.size)
         assert np.array_equal(d_out[mis_out:mis_out + want.size].cpu().numpy(), want), (seed, "device resident", mis_in, mis_out)
         d_dec = torch.full((data.size + 16,), 0x6D, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.decode_device(d_out.data_ptr() + mis_out, offs, np.array([n], dtype=np.uint64), d_dec.data_ptr() + mis_in, data.size,
                             d_sizes.data_ptr())
         codec.status()
@@ -156,6 +158,7 @@ def _other_entry_points(oracle, codec, plan, info, data, want, n, seed):
         d_out = torch.zeros(cap + 32, dtype=torch.uint8, device=dev)
         d_off = torch.zeros(2, dtype=torch.int64, device=dev)
         for _round in range(2):
+            torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
             codec.encode_chunks_device(d_pts.data_ptr(), np.array([n], dtype=np.uint64))
             codec.frame_chunks_device(d_out.data_ptr() + mis, cap, d_off.data_ptr())
             codec.status()

@@ -381,6 +381,7 @@ def test_last_encode_behind_device_outputs():
     _tp, pp, check_p = _dev(data, 7)
     d_out = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
     d_off = torch.zeros(3, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.encode_device(pp, sizes, d_out.data_ptr() + 7, cap, d_off.data_ptr())
     got = codec.stream_hist_last_encode()
     offs = d_off.cpu().numpy()
@@ -412,6 +413,7 @@ def test_refused_without_state_and_behind_the_chunk_table_call():
     cap = codec.plan.stage1_bound(70000)
     d_out = torch.zeros(cap, dtype=torch.uint8, device=dev)
     d_off = torch.zeros(2, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.frame_chunks_device(d_out.data_ptr(), cap, d_off.data_ptr())
     stream = d_out.cpu().numpy()[:int(d_off.cpu().numpy()[1])]
     _same(codec.stream_hist_last_encode(), H.stream_hist([stream]), "framed")

@@ -269,6 +269,7 @@ def test_force_modes_per_cloud_through_every_encode_entry_point(oracle):
     d_modes = torch.full((len(sizes) * 2,), 0xEE, dtype=torch.uint8, device=dev)
     for how in ("device", "chunks"):
         d_out.zero_()
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         if how == "device":
             codec.encode_device(pp, sizes, d_out.data_ptr() + 3, cap, d_off.data_ptr(), 0, d_modes.data_ptr())
         else:

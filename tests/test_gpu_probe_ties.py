@@ -176,6 +176,7 @@ def _run_device_modes_at_an_odd_address(oracle, shim, layout, batch, probe):
     d_off = torch.zeros(len(batch) + 1, dtype=torch.int64, device=dev)
     d_modes = torch.full((256 + len(batch) * na + 256,), 0xEE, dtype=torch.uint8, device=dev)
     at = (-d_modes.data_ptr()) % 256 + 1
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.encode_device(flat.data_ptr(), sizes, d_out.data_ptr(), cap, d_off.data_ptr(), 0, d_modes.data_ptr() + at)
     codec.status()
     torch.cuda.synchronize()

@@ -331,6 +331,7 @@ def test_sweep_last_encode_after_encode_device(oracle, residue):
     _tp, pp, check_p = _dev(data, residue)
     d_out = torch.zeros(cap + 64, dtype=torch.uint8, device=dev)
     d_off = torch.zeros(3, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.encode_device(pp, sizes, d_out.data_ptr() + residue, cap, d_off.data_ptr())
     got = codec.sweep_last_encode(ladders)
     _same(got, S.sweep(info, data, sizes, ladders))
@@ -354,6 +355,7 @@ def test_sweep_last_encode_between_the_chunk_table_and_its_framing(oracle):
     cap = codec.plan.stage1_bound(70000)
     d_out = torch.zeros(cap, dtype=torch.uint8, device=dev)
     d_off = torch.zeros(2, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.frame_chunks_device(d_out.data_ptr(), cap, d_off.data_ptr())
     stream = d_out.cpu().numpy()[:int(d_off.cpu().numpy()[1])]
     assert stream.tobytes() == oracle.encode_stage1(info, data).tobytes()   # the sweep in between disturbed nothing

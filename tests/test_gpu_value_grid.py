@@ -131,12 +131,14 @@ def test_tail_and_wide_layouts_through_the_other_entry_points(oracle, group):
         d_off = torch.zeros(2, dtype=torch.int64, device=dev)
         d_sizes = torch.zeros(2, dtype=torch.int32, device=dev)
         cp = np.array([c.n], dtype=np.uint64)
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.encode_device(d_in.data_ptr(), cp, d_out.data_ptr(), cap, d_off.data_ptr(), d_sizes.data_ptr(), 0)
         codec.synchronize()
         codec.status()
         offs = d_off.cpu().numpy().astype(np.uint64)
         assert int(offs[1]) == want.size and np.array_equal(d_out[: want.size].cpu().numpy(), want), c.name
         d_dec = torch.full((data.size,), FILL, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.decode_device(d_out.data_ptr(), offs, cp, d_dec.data_ptr(), data.size, d_sizes.data_ptr())
         codec.synchronize()
         codec.status()
@@ -148,6 +150,7 @@ def test_tail_and_wide_layouts_through_the_other_entry_points(oracle, group):
         payloads, _segs, _flag = _read_chunk_table(table, torch)
         assert len(payloads) == 1 and np.array_equal(payloads[0], want[4:]), c.name
         d_out.zero_()
+        torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
         codec.frame_chunks_device(d_out.data_ptr(), cap, d_off.data_ptr())
         codec.synchronize()
         codec.status()

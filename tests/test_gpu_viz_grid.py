@@ -80,6 +80,7 @@ def test_device_resident_at_every_misalignment(oracle, case):
             d_out = torch.full((front + data.size + 16 + 256,), 0xA5, dtype=torch.uint8, device=dev)
             assert d_in.data_ptr() % 256 == 0 and d_out.data_ptr() % 256 == 0, "the caching allocator's base alignment"
             d_in[mi:mi + data.size] = torch.from_numpy(data).to(dev)
+            torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
             kept = codec.viz_preprocess_batch_device(d_in.data_ptr() + mi, npts, step, case.off, case.res,
                                                      d_out.data_ptr() + front + mo, data.size)
             codec.synchronize()

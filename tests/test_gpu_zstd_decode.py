@@ -85,6 +85,7 @@ def _run_device(codec, cases, r_in=0, r_out=0):
     d_out = torch.full((512 + total + 512,), FILL, dtype=torch.uint8, device=dev)
     base_out = (-d_out.data_ptr()) % 256 + 256 + r_out
     d_sizes = torch.full((len(frames),), 0x77777777, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.zstd_decompress_device(d_in.data_ptr() + base_in, bo, d_out.data_ptr() + base_out, oo, d_sizes.data_ptr())
     code = 0
     try:

@@ -154,6 +154,7 @@ def test_host_device_and_two_step_outputs_agree(oracle):
     d_out = torch.zeros(cap, dtype=torch.uint8, device=dev)
     d_off = torch.zeros(len(clouds) + 1, dtype=torch.int64, device=dev)
     d_sizes = torch.zeros(len(chunk_sizes), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     codec.encode_device(d_in.data_ptr(), npts, d_out.data_ptr(), cap, d_off.data_ptr(), d_sizes.data_ptr(), 0)
     codec.synchronize()
     codec.status()
@@ -195,6 +196,7 @@ def test_capacity_one_byte_short_of_the_produced_size():
     assert produced - 1 < int(sum(plan.stage2_bound(int(n), ZSTD) for n in npts))
     d_in = torch.from_numpy(np.concatenate(clouds)).to(dev)
     d_out = torch.full((256 + produced + 256,), 0xA5, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     with pytest.raises(native.CloudiniHipError) as e:
         codec.encode_device(d_in.data_ptr(), npts, d_out.data_ptr() + 256, produced - 1)
     assert e.value.code == -2

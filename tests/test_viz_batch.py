@@ -68,6 +68,7 @@ def test_batch_filter_matches_the_oracle_per_cloud(oracle, seed):
     d_in = torch.zeros(data.size + 8, dtype=torch.uint8, device=dev)
     d_in[mi:mi + data.size] = torch.from_numpy(data).to(dev)
     d_out = torch.full((data.size + 8 + 256,), 0xA5, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     kept = codec.viz_preprocess_batch_device(d_in.data_ptr() + mi, npts, step, off, res, d_out.data_ptr() + mo, data.size)
     codec.synchronize()
     assert [int(k) for k in kept] == [w.size // step for w in want], (seed, "device resident")
@@ -262,6 +263,7 @@ def test_fused_call_equals_the_encode_of_the_filtered_clouds(oracle, name, info,
     d_offs = torch.zeros(len(clouds) + 1, dtype=torch.int64, device=dev)
     d_sizes = torch.zeros(max(1, n_chunks_in), dtype=torch.int32, device=dev)
     d_modes = torch.full((max(1, len(clouds) * max(1, na)),), 0xEE, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     got_kept = codec.encode_viz_device(d_in.data_ptr(), npts, off, res, d_out.data_ptr(), cap, d_offs.data_ptr(),
                                        d_sizes.data_ptr(), d_modes.data_ptr())
     codec.synchronize()

@@ -126,6 +126,7 @@ def test_gpu_matches_oracle_on_random_clouds(oracle, seed):
     d_in = torch.zeros(data.size + 8, dtype=torch.uint8, device=dev)
     d_in[mi:mi + data.size] = torch.from_numpy(data).to(dev)
     d_out = torch.zeros(data.size + 8, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (prepared on the null stream; the codec works on a stream of its own)
     kept = codec.viz_preprocess_device(d_in.data_ptr() + mi, n, step, off, res, d_out.data_ptr() + mo, data.size)
     codec.synchronize()
     assert kept * step == want.size and np.array_equal(d_out[mo:mo + kept * step].cpu().numpy(), want), (seed, "device resident")
