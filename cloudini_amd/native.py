@@ -43,6 +43,88 @@ class _Field(C.Structure):
                 ("reserved", C.c_uint8 * 2), ("resolution", C.c_float)]
 
 
+_INT, _U8, _U32, _U64, _I64, _F32 = C.c_int, C.c_uint8, C.c_uint32, C.c_uint64, C.c_int64, C.c_float
+_VP, _U8P, _U32P, _U64P, _F32P, _VPP = (C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_float), C.POINTER(C.c_void_p))
+
+# name -> (restype, argtypes) of every prototype of include/cloudini_hip.h, in its order, and of the debug hooks hip_abi.hip
+# exports outside it. lib() applies the table; tests/test_host_api.py holds it against the C declarations.
+SIGNATURES = {
+    "cldn_hip_last_error": (C.c_char_p, []),
+    "cldn_hip_abi_version": (_INT, []),
+    "cldn_hip_device_count": (_INT, []),
+    "cldn_hip_current_device": (_INT, []),
+    "cldn_hip_set_current_device": (_INT, [_INT]),
+    "cldn_hip_host_alloc": (_VP, [C.c_size_t]),
+    "cldn_hip_host_free": (None, [_VP]),
+    "cldn_hip_plan_create": (_INT, [C.POINTER(_Field), _U32, _U32, _U8, _U8, _VPP]),
+    "cldn_hip_plan_destroy": (None, [_VP]),
+    "cldn_hip_plan_uses_v5": (_INT, [_VP]),
+    "cldn_hip_plan_adaptive_fields": (_U32, [_VP]),
+    "cldn_hip_plan_adaptive_field_index": (_U32, [_VP, _U32]),
+    "cldn_hip_plan_max_point_bytes": (_U32, [_VP]),
+    "cldn_hip_stage1_bound": (_U64, [_VP, _U64]),
+    "cldn_hip_codec_create": (_INT, [_VP, _INT, _VP, _VPP]),
+    "cldn_hip_codec_destroy": (None, [_VP]),
+    "cldn_hip_codec_synchronize": (_INT, [_VP]),
+    "cldn_hip_codec_stream": (_VP, [_VP]),
+    "cldn_hip_codec_device": (_INT, [_VP]),
+    "cldn_hip_encode_stage1": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _U64, _INT, _VP, _VP, _VP]),
+    "cldn_hip_encode_stage1_chunks": (_INT, [_VP, _VP, _INT, _U64P, _U32, C.POINTER(ChunkTable), _VP]),
+    "cldn_hip_frame_chunks": (_INT, [_VP, _VP, _U64, _INT, _VP, _VP]),
+    "cldn_hip_codec_fetch_output": (_INT, [_VP, _VP, _U64]),
+    "cldn_hip_encode_stage1_gather": (_INT, [_VP, _VPP, _U64P, _U32, _VP, _U64, _INT, _VP, _VP, _VP]),
+    "cldn_hip_codec_set_stage2": (_INT, [_VP, _INT]),
+    "cldn_hip_stage2_bound": (_U64, [_VP, _U64, _INT]),
+    "cldn_hip_codec_force_modes": (_INT, [_VP, _U8P, _U32]),
+    "cldn_hip_codec_force_modes_per_cloud": (_INT, [_VP, _U8P, _U32]),
+    "cldn_hip_codec_pipeline": (_INT, [_VP, _INT, _VP]),
+    "cldn_hip_decode_stage1": (_INT, [_VP, _VP, _INT, _U64P, _U64P, _U32, _VP, _U64, _INT]),
+    "cldn_hip_decode_stage1_sized": (_INT, [_VP, _VP, _INT, _U64P, _U64P, _U32, _VP, _INT, _VP, _U64, _INT]),
+    "cldn_hip_lz4_decompress": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _INT, _U64P, _VP]),
+    "cldn_hip_decode_lz4": (_INT, [_VP, _VP, _INT, _U64P, _U64P, _U32, _VP, _U64, _INT]),
+    "cldn_hip_zstd_decompress": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _INT, _U64P, _VP]),
+    "cldn_hip_decode_zstd": (_INT, [_VP, _VP, _INT, _U64P, _U64P, _U32, _VP, _U64, _INT]),
+    "cldn_hip_decode_lz4_gather": (_INT, [_VP, _VP, _U64P, _U64P, _U32, _VP, _VP, _VP, _VP, _VP, _U64, _INT]),
+    "cldn_hip_decode_zstd_gather": (_INT, [_VP, _VP, _U64P, _U64P, _U32, _VP, _VP, _VP, _VP, _VP, _U64, _INT]),
+    "cldn_hip_decode_stage1_unframed": (_INT, [_VP, _VP, _U64, _INT, _VP, _U64, _INT]),
+    "cldn_hip_viz_preprocess": (_INT, [_VP, _VP, _INT, _U64, _U32, _U32, _F32, _VP, _U64, _INT, _U64P]),
+    "cldn_hip_viz_preprocess_batch": (_INT, [_VP, _VP, _INT, _U64P, _U32, _U32, _U32, _F32, _VP, _U64, _INT, _U64P]),
+    "cldn_hip_encode_stage1_viz": (_INT, [_VP, _VP, _INT, _U64P, _U32, _U32, _F32, _U64P, _VP, _U64, _INT, _VP, _VP, _VP]),
+    "cldn_hip_encode_stage1_viz_gather": (_INT, [_VP, _VPP, _U64P, _U32, _U32, _F32, _U64P, _VP, _U64, _INT, _VP, _VP, _VP]),
+    "cldn_hip_audit_clouds": (_INT, [_VP, _VP, _INT, _VP, _INT, _U64P, _U32, _VP, _VP, _INT]),
+    "cldn_hip_audit_streams": (_INT, [_VP, _VP, _INT, _VP, _INT, _U64P, _U64P, _U32, _INT, _VP, _VP, _INT]),
+    "cldn_hip_audit_last_encode": (_INT, [_VP, _VP, _VP, _INT]),
+    "cldn_hip_audit_last_encode_clouds": (_I64, [_VP]),
+    "cldn_hip_sweep_clouds": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _U32, _VP, _INT]),
+    "cldn_hip_sweep_last_encode": (_INT, [_VP, _VP, _U32, _VP, _INT]),
+    "cldn_hip_sweep_last_encode_clouds": (_I64, [_VP]),
+    "cldn_hip_sweep_hist_clouds": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _U32, _VP, _INT]),
+    "cldn_hip_sweep_hist_last_encode": (_INT, [_VP, _VP, _U32, _VP, _INT]),
+    "cldn_hip_stream_hist": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _INT]),
+    "cldn_hip_stream_hist_last_encode": (_INT, [_VP, _VP, _INT]),
+    "cldn_hip_hist_entropy_bytes": (C.c_double, [_VP]),
+    "cldn_hip_sweep_modes_clouds": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _INT]),
+    "cldn_hip_sweep_modes_last_encode": (_INT, [_VP, _VP, _INT]),
+    "cldn_hip_codec_set_decode_fill": (_INT, [_VP, _INT]),
+    "cldn_hip_codec_set_zstd_sequences": (_INT, [_VP, _INT]),
+    "cldn_hip_codec_zstd_sequences": (_INT, [_VP]),
+    "cldn_hip_codec_set_zstd_matches": (_INT, [_VP, _INT]),
+    "cldn_hip_codec_zstd_matches": (_INT, [_VP]),
+    "cldn_hip_codec_decode_stats": (_INT, [_VP, _U32P]),
+    "cldn_hip_codec_status": (_INT, [_VP]),
+    "cldn_hip_codec_finish_retries": (_U32, [_VP]),
+    "cldn_hip_codec_enable_timing": (_INT, [_VP, _U32]),
+    "cldn_hip_codec_kernel_ms": (_INT, [_VP, _U32, _F32P]),
+    "cldn_hip_codec_decode_ms": (_INT, [_VP, _F32P]),
+    "cldn_hip_debug_finish_timeout_once": (_INT, [_VP]),
+    "cldn_hip_debug_decode_split": (_INT, [_VP, _U32]),
+    "cldn_hip_debug_zstd_seq_ring": (_U32, []),
+    "cldn_hip_debug_decode_trace": (_INT, [_VP, _U32P, _U32, _U32P, _VP, _VP, _VP, _VP, _VP]),
+    "cldn_hip_debug_viz_group_slots": (_INT, [_VP, _U64]),
+    "cldn_hip_debug_hist_walk": (_INT, [_VP, _U32]),
+}
+
 _lib = None
 
 
@@ -62,145 +144,9 @@ def lib() -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(HIP_SO)
-    vp, u8p, u32p, u64p = C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
-    L.cldn_hip_last_error.restype = C.c_char_p
-    L.cldn_hip_abi_version.restype = C.c_int
-    L.cldn_hip_device_count.restype = C.c_int
-    L.cldn_hip_current_device.restype = C.c_int
-    L.cldn_hip_set_current_device.restype = C.c_int
-    L.cldn_hip_set_current_device.argtypes = [C.c_int]
-    L.cldn_hip_codec_device.restype = C.c_int
-    L.cldn_hip_codec_device.argtypes = [vp]
-    L.cldn_hip_host_alloc.restype = vp
-    L.cldn_hip_host_alloc.argtypes = [C.c_size_t]
-    L.cldn_hip_host_free.restype = None
-    L.cldn_hip_host_free.argtypes = [vp]
-    L.cldn_hip_plan_create.restype = C.c_int
-    L.cldn_hip_plan_create.argtypes = [C.POINTER(_Field), C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8,
-                                       C.POINTER(vp)]
-    L.cldn_hip_plan_destroy.argtypes = [vp]
-    L.cldn_hip_plan_destroy.restype = None
-    L.cldn_hip_plan_uses_v5.argtypes = [vp]
-    L.cldn_hip_plan_uses_v5.restype = C.c_int
-    L.cldn_hip_plan_adaptive_fields.argtypes = [vp]
-    L.cldn_hip_plan_adaptive_fields.restype = C.c_uint32
-    L.cldn_hip_plan_max_point_bytes.argtypes = [vp]
-    L.cldn_hip_plan_max_point_bytes.restype = C.c_uint32
-    L.cldn_hip_stage1_bound.argtypes = [vp, C.c_uint64]
-    L.cldn_hip_stage1_bound.restype = C.c_uint64
-    L.cldn_hip_codec_create.restype = C.c_int
-    L.cldn_hip_codec_create.argtypes = [vp, C.c_int, vp, C.POINTER(vp)]
-    L.cldn_hip_codec_destroy.argtypes = [vp]
-    L.cldn_hip_codec_destroy.restype = None
-    L.cldn_hip_codec_synchronize.argtypes = [vp]
-    L.cldn_hip_codec_synchronize.restype = C.c_int
-    L.cldn_hip_codec_stream.argtypes = [vp]
-    L.cldn_hip_codec_stream.restype = vp
-    L.cldn_hip_codec_status.argtypes = [vp]
-    L.cldn_hip_codec_status.restype = C.c_int
-    L.cldn_hip_codec_enable_timing.argtypes = [vp, C.c_uint32]
-    L.cldn_hip_codec_enable_timing.restype = C.c_int
-    L.cldn_hip_codec_kernel_ms.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float)]
-    L.cldn_hip_codec_kernel_ms.restype = C.c_int
-    L.cldn_hip_codec_decode_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    L.cldn_hip_codec_decode_ms.restype = C.c_int
-    L.cldn_hip_viz_preprocess.restype = C.c_int
-    L.cldn_hip_viz_preprocess.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, vp, C.c_uint64,
-                                          C.c_int, u64p]
-    L.cldn_hip_viz_preprocess_batch.restype = C.c_int
-    L.cldn_hip_viz_preprocess_batch.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp,
-                                                C.c_uint64, C.c_int, u64p]
-    L.cldn_hip_encode_stage1_viz.restype = C.c_int
-    L.cldn_hip_encode_stage1_viz.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, C.c_uint32, C.c_float, u64p, vp, C.c_uint64,
-                                             C.c_int, vp, vp, vp]
-    L.cldn_hip_encode_stage1_viz_gather.restype = C.c_int
-    L.cldn_hip_encode_stage1_viz_gather.argtypes = [vp, C.POINTER(vp), u64p, C.c_uint32, C.c_uint32, C.c_float, u64p, vp,
-                                                    C.c_uint64, C.c_int, vp, vp, vp]
-    L.cldn_hip_debug_viz_group_slots.restype = C.c_int
-    L.cldn_hip_debug_viz_group_slots.argtypes = [vp, C.c_uint64]
-    L.cldn_hip_codec_set_decode_fill.argtypes = [vp, C.c_int]
-    L.cldn_hip_codec_set_decode_fill.restype = C.c_int
-    L.cldn_hip_codec_set_zstd_sequences.argtypes = [vp, C.c_int]
-    L.cldn_hip_codec_set_zstd_sequences.restype = C.c_int
-    L.cldn_hip_codec_zstd_sequences.argtypes = [vp]
-    L.cldn_hip_codec_zstd_sequences.restype = C.c_int
-    L.cldn_hip_codec_set_zstd_matches.argtypes = [vp, C.c_int]
-    L.cldn_hip_codec_set_zstd_matches.restype = C.c_int
-    L.cldn_hip_codec_zstd_matches.argtypes = [vp]
-    L.cldn_hip_codec_zstd_matches.restype = C.c_int
-    L.cldn_hip_codec_decode_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
-    L.cldn_hip_codec_decode_stats.restype = C.c_int
-    L.cldn_hip_debug_decode_trace.restype = C.c_int
-    L.cldn_hip_debug_decode_trace.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), vp, vp, vp, vp, vp]
-    L.cldn_hip_codec_finish_retries.argtypes = [vp]
-    L.cldn_hip_codec_finish_retries.restype = C.c_uint32
-    L.cldn_hip_codec_force_modes.argtypes = [vp, C.POINTER(C.c_uint8), C.c_uint32]
-    L.cldn_hip_codec_force_modes.restype = C.c_int
-    L.cldn_hip_encode_stage1_chunks.restype = C.c_int
-    L.cldn_hip_encode_stage1_chunks.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, C.POINTER(ChunkTable), vp]
-    L.cldn_hip_frame_chunks.restype = C.c_int
-    L.cldn_hip_frame_chunks.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp]
-    L.cldn_hip_codec_set_stage2.argtypes = [vp, C.c_int]
-    L.cldn_hip_codec_set_stage2.restype = C.c_int
-    L.cldn_hip_stage2_bound.argtypes = [vp, C.c_uint64, C.c_int]
-    L.cldn_hip_stage2_bound.restype = C.c_uint64
-    L.cldn_hip_codec_pipeline.argtypes = [vp, C.c_int, vp]
-    L.cldn_hip_codec_pipeline.restype = C.c_int
-    L.cldn_hip_encode_stage1.restype = C.c_int
-    L.cldn_hip_encode_stage1.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_uint64, C.c_int, vp, vp, vp]
-    L.cldn_hip_encode_stage1_gather.restype = C.c_int
-    L.cldn_hip_encode_stage1_gather.argtypes = [vp, C.POINTER(vp), u64p, C.c_uint32, vp, C.c_uint64, C.c_int, vp, vp, vp]
-    L.cldn_hip_codec_fetch_output.restype = C.c_int
-    L.cldn_hip_codec_fetch_output.argtypes = [vp, vp, C.c_uint64]
-    L.cldn_hip_decode_stage1.restype = C.c_int
-    L.cldn_hip_decode_stage1.argtypes = [vp, vp, C.c_int, u64p, u64p, C.c_uint32, vp, C.c_uint64, C.c_int]
-    L.cldn_hip_decode_stage1_sized.restype = C.c_int
-    L.cldn_hip_decode_stage1_sized.argtypes = [vp, vp, C.c_int, u64p, u64p, C.c_uint32, vp, C.c_int, vp, C.c_uint64, C.c_int]
-    L.cldn_hip_decode_stage1_unframed.restype = C.c_int
-    L.cldn_hip_decode_stage1_unframed.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.c_uint64, C.c_int]
-    L.cldn_hip_lz4_decompress.restype = C.c_int
-    L.cldn_hip_lz4_decompress.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int, u64p, vp]
-    L.cldn_hip_decode_lz4.restype = C.c_int
-    L.cldn_hip_decode_lz4.argtypes = [vp, vp, C.c_int, u64p, u64p, C.c_uint32, vp, C.c_uint64, C.c_int]
-    L.cldn_hip_zstd_decompress.restype = C.c_int
-    L.cldn_hip_zstd_decompress.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int, u64p, vp]
-    L.cldn_hip_decode_zstd.restype = C.c_int
-    L.cldn_hip_decode_zstd.argtypes = [vp, vp, C.c_int, u64p, u64p, C.c_uint32, vp, C.c_uint64, C.c_int]
-    for fn in (L.cldn_hip_decode_lz4_gather, L.cldn_hip_decode_zstd_gather):
-        fn.restype = C.c_int
-        fn.argtypes = [vp, vp, u64p, u64p, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, C.c_int]
-    L.cldn_hip_audit_clouds.restype = C.c_int
-    L.cldn_hip_audit_clouds.argtypes = [vp, vp, C.c_int, vp, C.c_int, u64p, C.c_uint32, vp, vp, C.c_int]
-    L.cldn_hip_audit_streams.restype = C.c_int
-    L.cldn_hip_audit_streams.argtypes = [vp, vp, C.c_int, vp, C.c_int, u64p, u64p, C.c_uint32, C.c_int, vp, vp, C.c_int]
-    L.cldn_hip_audit_last_encode.restype = C.c_int
-    L.cldn_hip_audit_last_encode.argtypes = [vp, vp, vp, C.c_int]
-    L.cldn_hip_audit_last_encode_clouds.restype = C.c_int64
-    L.cldn_hip_audit_last_encode_clouds.argtypes = [vp]
-    L.cldn_hip_sweep_clouds.restype = C.c_int
-    L.cldn_hip_sweep_clouds.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_uint32, vp, C.c_int]
-    L.cldn_hip_sweep_last_encode.restype = C.c_int
-    L.cldn_hip_sweep_last_encode.argtypes = [vp, vp, C.c_uint32, vp, C.c_int]
-    L.cldn_hip_sweep_last_encode_clouds.restype = C.c_int64
-    L.cldn_hip_sweep_last_encode_clouds.argtypes = [vp]
-    L.cldn_hip_sweep_hist_clouds.restype = C.c_int
-    L.cldn_hip_sweep_hist_clouds.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_uint32, vp, C.c_int]
-    L.cldn_hip_sweep_hist_last_encode.restype = C.c_int
-    L.cldn_hip_sweep_hist_last_encode.argtypes = [vp, vp, C.c_uint32, vp, C.c_int]
-    L.cldn_hip_stream_hist.restype = C.c_int
-    L.cldn_hip_stream_hist.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int]
-    L.cldn_hip_stream_hist_last_encode.restype = C.c_int
-    L.cldn_hip_stream_hist_last_encode.argtypes = [vp, vp, C.c_int]
-    L.cldn_hip_hist_entropy_bytes.restype = C.c_double
-    L.cldn_hip_hist_entropy_bytes.argtypes = [vp]
-    L.cldn_hip_debug_hist_walk.restype = C.c_int
-    L.cldn_hip_debug_hist_walk.argtypes = [vp, C.c_uint32]
-    L.cldn_hip_sweep_modes_clouds.restype = C.c_int
-    L.cldn_hip_sweep_modes_clouds.argtypes = [vp, vp, C.c_int, u64p, C.c_uint32, vp, C.c_int]
-    L.cldn_hip_sweep_modes_last_encode.restype = C.c_int
-    L.cldn_hip_sweep_modes_last_encode.argtypes = [vp, vp, C.c_int]
-    L.cldn_hip_codec_force_modes_per_cloud.restype = C.c_int
-    L.cldn_hip_codec_force_modes_per_cloud.argtypes = [vp, C.POINTER(C.c_uint8), C.c_uint32]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -216,14 +162,121 @@ def device_count() -> int:
     return n
 
 
-def _fields_array(info):
-    arr = (_Field * max(1, len(info.fields)))()
-    for i, f in enumerate(info.fields):
-        arr[i].offset = int(f.offset)
-        arr[i].type = int(f.type)
-        arr[i].has_resolution = 0 if f.resolution is None else 1
-        arr[i].resolution = 0.0 if f.resolution is None else float(f.resolution)
-    return arr
+def zstd_seq_ring() -> int:
+    """Test hook (cldn_hip_debug_zstd_seq_ring, a host function): the bytes of k_zstd_seq_exec's LDS ring."""
+    return lib().cldn_hip_debug_zstd_seq_ring()
+
+
+def _ptr(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _p64(a: np.ndarray):
+    return a.ctypes.data_as(_U64P)
+
+
+def _bytes(a) -> np.ndarray:
+    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+
+def _prefix(sizes) -> np.ndarray:
+    """The [n + 1] uint64 prefix offsets of n sizes."""
+    offs = np.zeros(len(sizes) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(sizes, dtype=np.uint64)
+    return offs
+
+
+def _pack(arrs: List[np.ndarray]):
+    """uint8 arrays as (one buffer, its prefix offsets). One spare byte lies behind the last: an empty batch still has an address."""
+    return np.concatenate(arrs + [np.zeros(1, np.uint8)]), _prefix([a.size for a in arrs])
+
+
+def _pack_clouds(clouds, step: int):
+    """Host clouds as (one buffer, cloud_points); refused when a cloud is no whole number of points."""
+    arrs = [_bytes(c) for c in clouds]
+    if any(a.size % step for a in arrs):
+        raise ValueError("Input cloud_data size is not a multiple of point_step")
+    return _pack(arrs)[0], np.array([a.size // step for a in arrs], dtype=np.uint64)
+
+
+def _split(out: np.ndarray, offs) -> List[np.ndarray]:
+    """One view of `out` per span of the prefix offsets."""
+    return [out[int(offs[k]):int(offs[k + 1])] for k in range(len(offs) - 1)]
+
+
+def _n_chunks(cloud_points) -> int:
+    return int(sum((int(n) + 32767) // 32768 for n in cloud_points))
+
+
+def _chunk_sizes(chunk_sizes, cloud_points):
+    """(keep-alive array, pointer) of a decode call's `chunk_sizes`: None = the C side reads the [u32 size] prefixes."""
+    if chunk_sizes is None:
+        return None, None
+    cs = np.ascontiguousarray(chunk_sizes, dtype=np.uint32)
+    if cs.size < _n_chunks(cloud_points):  # the C side reads n_chunks sizes
+        raise ValueError(f"chunk_sizes has {cs.size} entries, the batch has {_n_chunks(cloud_points)} chunks")
+    return cs, _ptr(cs)
+
+
+def _decode_host(codec, fn, streams, cloud_points, out, *sized) -> List[np.ndarray]:
+    """A framed decode call on host buffers: fn is cldn_hip_decode_lz4 / _zstd, or cldn_hip_decode_stage1_sized with
+    sized = (chunk_sizes pointer, HOST). Returns one view of `out` per cloud."""
+    data, offs = _pack([_bytes(s) for s in streams])
+    npts = np.array(list(cloud_points), dtype=np.uint64)
+    ends = _prefix(npts * codec.plan.point_step)
+    if out is None:
+        out = np.zeros(max(1, int(ends[-1])), dtype=np.uint8)
+    _check(fn(codec._h, _ptr(data), HOST, _p64(offs), _p64(npts), offs.size - 1, *sized, _ptr(out), int(ends[-1]), HOST))
+    return _split(out, ends)
+
+
+def _decode_device(codec, fn, streams_ptr, stream_offsets, cloud_points, out_ptr, out_capacity):
+    """The same on device pointers, for cldn_hip_decode_lz4 / _zstd (decode_device makes its call itself)."""
+    so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
+    cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
+    _check(fn(codec._h, C.c_void_p(streams_ptr), DEVICE, _p64(so), _p64(cp), cp.size, C.c_void_p(out_ptr), int(out_capacity),
+              DEVICE))
+
+
+def _decompress_host(codec, fn, spans, capacities, out):
+    """cldn_hip_lz4_decompress / cldn_hip_zstd_decompress on host buffers; the return shapes of lz4_decompress_host."""
+    data, bo = _pack([np.frombuffer(bytes(b), dtype=np.uint8) for b in spans])
+    oo = _prefix([int(c) for c in capacities])
+    n = bo.size - 1
+    keep = out is not None
+    if out is None:
+        out = np.zeros(max(1, int(oo[-1])), dtype=np.uint8)
+    sizes = np.zeros(max(1, n), dtype=np.uint32)
+    rc = fn(codec._h, _ptr(data), HOST, _p64(bo), n, _ptr(out), HOST, _p64(oo), _ptr(sizes))
+    if keep:
+        return out, sizes[:n], rc
+    _check(rc)
+    return out, sizes[:n]
+
+
+def _decompress_device(codec, fn, spans_ptr, span_offsets, out_ptr, out_offsets, sizes_ptr):
+    bo = np.ascontiguousarray(span_offsets, dtype=np.uint64)
+    oo = np.ascontiguousarray(out_offsets, dtype=np.uint64)
+    _check(fn(codec._h, C.c_void_p(spans_ptr), DEVICE, _p64(bo), bo.size - 1, C.c_void_p(out_ptr), DEVICE, _p64(oo),
+              C.c_void_p(sizes_ptr)))
+
+
+def _report(shape, dtype) -> np.ndarray:
+    rep = np.zeros(shape, dtype=dtype)
+    rep.view(np.uint8)[...] = 0xEE  # (a call that fails leaves it as it was)
+    return rep
+
+
+def _report_arg(rep, report_ptr: int):
+    """The (report pointer, location) pair of a report call: the caller's device array, else the host report."""
+    return (C.c_void_p(report_ptr), DEVICE) if report_ptr else (_ptr(rep), HOST)
+
+
+def _last_encode_clouds(fn, codec) -> int:
+    """cldn_hip_audit_last_encode_clouds / cldn_hip_sweep_last_encode_clouds: the rows a *_last_encode report needs."""
+    n = int(fn(codec._h))
+    _check(n)
+    return n
 
 
 # cldn_hip_audit_field_t: one record per (cloud, field)
@@ -272,7 +325,12 @@ class Plan:
 
     def __init__(self, info):
         self._h = C.c_void_p()
-        arr = _fields_array(info)
+        arr = (_Field * max(1, len(info.fields)))()
+        for i, f in enumerate(info.fields):
+            arr[i].offset = int(f.offset)
+            arr[i].type = int(f.type)
+            arr[i].has_resolution = 0 if f.resolution is None else 1
+            arr[i].resolution = 0.0 if f.resolution is None else float(f.resolution)
         _check(lib().cldn_hip_plan_create(arr, len(info.fields), int(info.point_step), int(info.version),
                                           int(info.encoding_opt), C.byref(self._h)))
         self.point_step = int(info.point_step)
@@ -297,9 +355,7 @@ class Plan:
 
     def adaptive_field_index(self, a: int) -> int:
         """Index among the schema's fields of adaptive field a (cldn_hip_plan_adaptive_field_index)."""
-        f = lib().cldn_hip_plan_adaptive_field_index
-        f.restype, f.argtypes = C.c_uint32, [C.c_void_p, C.c_uint32]
-        return int(f(self._h, int(a)))
+        return int(lib().cldn_hip_plan_adaptive_field_index(self._h, int(a)))
 
     def stage1_bound(self, n_points: int) -> int:
         return int(lib().cldn_hip_stage1_bound(self._h, int(n_points)))
@@ -337,12 +393,11 @@ class Codec:
 
     def viz_preprocess_host(self, cloud, point_step: int, xyz_offset: int, resolution: float) -> np.ndarray:
         """applyVizLossyPreprocessing's data path on host buffers: the surviving points, order preserved."""
-        data = np.ascontiguousarray(cloud).view(np.uint8).reshape(-1)
-        n = data.size // point_step
+        data = _bytes(cloud)
         out = np.empty(max(1, data.size), dtype=np.uint8)
         kept = C.c_uint64(0)
-        _check(lib().cldn_hip_viz_preprocess(self._h, data.ctypes.data_as(C.c_void_p), HOST, n, point_step, xyz_offset,
-                                             resolution, out.ctypes.data_as(C.c_void_p), out.size, HOST, C.byref(kept)))
+        _check(lib().cldn_hip_viz_preprocess(self._h, _ptr(data), HOST, data.size // point_step, point_step, xyz_offset,
+                                             resolution, _ptr(out), out.size, HOST, C.byref(kept)))
         return out[: kept.value * point_step].copy()
 
     def viz_preprocess_device(self, points_ptr: int, n_points: int, point_step: int, xyz_offset: int, resolution: float,
@@ -360,27 +415,25 @@ class Codec:
                                   guard: int = 0):
         """cldn_hip_viz_preprocess_batch on host buffers. Returns (survivors per cloud, kept_points, tail): `tail` is the output
         buffer behind the last survivor, `guard` bytes of it beyond the capacity handed to the call (filled with 0xA5)."""
-        arrs = [np.ascontiguousarray(c).view(np.uint8).reshape(-1) for c in clouds]
+        arrs = [_bytes(c) for c in clouds]
         npts = np.array([a.size // point_step for a in arrs], dtype=np.uint64)
-        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        data, _ = _pack(arrs)
         cap = int(npts.sum()) * point_step
         out = np.full(cap + guard + 1, 0xA5, dtype=np.uint8)
         kept = np.zeros(max(1, len(arrs)), dtype=np.uint64)
-        _check(lib().cldn_hip_viz_preprocess_batch(
-            self._h, data.ctypes.data_as(C.c_void_p), HOST, npts.ctypes.data_as(C.POINTER(C.c_uint64)), len(arrs), point_step,
-            xyz_offset, resolution, out.ctypes.data_as(C.c_void_p), cap, HOST, kept.ctypes.data_as(C.POINTER(C.c_uint64))))
+        _check(lib().cldn_hip_viz_preprocess_batch(self._h, _ptr(data), HOST, _p64(npts), len(arrs), point_step, xyz_offset,
+                                                   resolution, _ptr(out), cap, HOST, _p64(kept)))
         kept = kept[: len(arrs)]
-        ends = np.concatenate([[0], np.cumsum(kept.astype(np.int64) * point_step)])
-        return [out[int(ends[k]):int(ends[k + 1])].copy() for k in range(len(arrs))], kept, out[int(ends[-1]):cap + guard]
+        ends = _prefix(kept * int(point_step))
+        return [v.copy() for v in _split(out, ends)], kept, out[int(ends[-1]):cap + guard]
 
     def viz_preprocess_batch_device(self, points_ptr: int, cloud_points, point_step: int, xyz_offset: int, resolution: float,
                                     out_ptr: int, out_capacity: int) -> np.ndarray:
         """The same on device buffers; returns kept_points (the call has synchronised)."""
         cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
         kept = np.zeros(max(1, cp.size), dtype=np.uint64)
-        _check(lib().cldn_hip_viz_preprocess_batch(
-            self._h, C.c_void_p(points_ptr), DEVICE, cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, point_step, xyz_offset,
-            resolution, C.c_void_p(out_ptr), int(out_capacity), DEVICE, kept.ctypes.data_as(C.POINTER(C.c_uint64))))
+        _check(lib().cldn_hip_viz_preprocess_batch(self._h, C.c_void_p(points_ptr), DEVICE, _p64(cp), cp.size, point_step, xyz_offset,
+                                                   resolution, C.c_void_p(out_ptr), int(out_capacity), DEVICE, _p64(kept)))
         return kept[: cp.size]
 
     def encode_viz(self, clouds: Sequence[np.ndarray], xyz_offset: int, resolution: float, gather: bool = False,
@@ -389,32 +442,29 @@ class Codec:
         two_step: out = NULL, then cldn_hip_codec_fetch_output. Returns (streams, chunk_sizes, modes, kept_points) of the
         filtered clouds, shaped like encode_host's."""
         step = self.plan.point_step
-        arrs = [np.ascontiguousarray(c).view(np.uint8).reshape(-1) for c in clouds]
+        arrs = [_bytes(c) for c in clouds]
         npts = np.array([a.size // step for a in arrs], dtype=np.uint64)
         n = len(arrs)
-        cap = int(sum(self.plan.stage2_bound(int(p), getattr(self, "_stage2", 0)) for p in npts))
+        cap = self._out_capacity(npts)
         out = np.empty(max(cap, 1), dtype=np.uint8)
         offs = np.zeros(n + 1, dtype=np.uint64)
-        chunk_sizes = np.zeros(max(1, int(sum((int(p) + 32767) // 32768 for p in npts))), dtype=np.uint32)
+        chunk_sizes = np.zeros(max(1, _n_chunks(npts)), dtype=np.uint32)
         na = self.plan.adaptive_fields
         modes = np.full(max(1, n * max(1, na)), 0xEE, dtype=np.uint8)
         kept = np.zeros(max(1, n), dtype=np.uint64)
-        tail = (None if two_step else out.ctypes.data_as(C.c_void_p), 0 if two_step else cap, HOST,
-                offs.ctypes.data_as(C.c_void_p), chunk_sizes.ctypes.data_as(C.c_void_p), modes.ctypes.data_as(C.c_void_p))
-        cp, kp = npts.ctypes.data_as(C.POINTER(C.c_uint64)), kept.ctypes.data_as(C.POINTER(C.c_uint64))
+        tail = (None if two_step else _ptr(out), 0 if two_step else cap, HOST, _ptr(offs), _ptr(chunk_sizes), _ptr(modes))
         if gather:
             ptrs = (C.c_void_p * max(1, n))(*[a.ctypes.data if a.size else None for a in arrs])
-            _check(lib().cldn_hip_encode_stage1_viz_gather(self._h, ptrs, cp, n, xyz_offset, resolution, kp, *tail))
+            _check(lib().cldn_hip_encode_stage1_viz_gather(self._h, ptrs, _p64(npts), n, xyz_offset, resolution, _p64(kept), *tail))
         else:
-            data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
-            _check(lib().cldn_hip_encode_stage1_viz(self._h, data.ctypes.data_as(C.c_void_p), HOST, cp, n, xyz_offset, resolution,
-                                                    kp, *tail))
+            data, _ = _pack(arrs)
+            _check(lib().cldn_hip_encode_stage1_viz(self._h, _ptr(data), HOST, _p64(npts), n, xyz_offset, resolution, _p64(kept),
+                                                    *tail))
         if two_step:
-            _check(lib().cldn_hip_codec_fetch_output(self._h, out.ctypes.data_as(C.c_void_p), int(offs[n])))
+            _check(lib().cldn_hip_codec_fetch_output(self._h, _ptr(out), int(offs[n])))
         kept = kept[:n]
-        n_chunks = int(sum((int(p) + 32767) // 32768 for p in kept))
-        streams = [out[int(offs[k]):int(offs[k + 1])].copy() for k in range(n)]
-        return streams, chunk_sizes[:n_chunks].copy(), modes[: n * na].reshape(n, na).copy(), kept
+        streams = [v.copy() for v in _split(out, offs)]
+        return streams, chunk_sizes[:_n_chunks(kept)].copy(), modes[: n * na].reshape(n, na).copy(), kept
 
     def encode_viz_device(self, points_ptr: int, cloud_points, xyz_offset: int, resolution: float, out_ptr: int,
                           out_capacity: int, stream_offsets_ptr: int = 0, chunk_sizes_ptr: int = 0, modes_ptr: int = 0):
@@ -422,9 +472,8 @@ class Codec:
         cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
         kept = np.zeros(max(1, cp.size), dtype=np.uint64)
         _check(lib().cldn_hip_encode_stage1_viz(
-            self._h, C.c_void_p(points_ptr), DEVICE, cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, xyz_offset, resolution,
-            kept.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(out_ptr), int(out_capacity), DEVICE,
-            C.c_void_p(stream_offsets_ptr), C.c_void_p(chunk_sizes_ptr), C.c_void_p(modes_ptr)))
+            self._h, C.c_void_p(points_ptr), DEVICE, _p64(cp), cp.size, xyz_offset, resolution, _p64(kept), C.c_void_p(out_ptr),
+            int(out_capacity), DEVICE, C.c_void_p(stream_offsets_ptr), C.c_void_p(chunk_sizes_ptr), C.c_void_p(modes_ptr)))
         return kept[: cp.size]
 
     def set_zstd_sequences(self, on: bool):
@@ -462,9 +511,8 @@ class Codec:
         n = C.c_uint32(0)
         u32 = [np.zeros(max(1, max_chunks), dtype=np.uint32) for _ in range(3)]
         u8 = [np.zeros(max(1, max_chunks), dtype=np.uint8) for _ in range(2)]
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        _check(lib().cldn_hip_debug_decode_trace(self._h, words, max_chunks, C.byref(n), p(u32[0]), p(u32[1]), p(u8[0]), p(u32[2]),
-                                                 p(u8[1])))
+        _check(lib().cldn_hip_debug_decode_trace(self._h, words, max_chunks, C.byref(n), _ptr(u32[0]), _ptr(u32[1]), _ptr(u8[0]),
+                                                 _ptr(u32[2]), _ptr(u8[1])))
         k = int(n.value)
         return {"words": tuple(int(x) for x in words), "n_chunks": k, "reg_end_pre": u32[0][:k].copy(),
                 "slices_done": u32[1][:k].copy(), "sec_cols": u8[0][:k].copy(), "reg_end": u32[2][:k].copy(),
@@ -473,6 +521,16 @@ class Codec:
     def finish_retries(self) -> int:
         """Calls redone through k_finish's ticket order after ST_FINISH_TIMEOUT (cldn_hip_codec_finish_retries)."""
         return int(lib().cldn_hip_codec_finish_retries(self._h))
+
+    def finish_timeout_once(self) -> int:
+        """Test hook (cldn_hip_debug_finish_timeout_once): the next encode call reports ST_FINISH_TIMEOUT on its first attempt.
+        Returns the C return code."""
+        return lib().cldn_hip_debug_finish_timeout_once(self._h)
+
+    def decode_split(self, parts: int) -> int:
+        """Test hook (cldn_hip_debug_decode_split): the point decoder's launch shape -- 0 = by the number of chunks (default),
+        1 = the chained launch, 2..16 = a SPLIT launch with that many workgroups per chunk. Returns the C return code."""
+        return lib().cldn_hip_debug_decode_split(self._h, int(parts))
 
     def force_modes(self, modes=None):
         """Adaptive-int modes committed elsewhere (cldn_hip_codec_force_modes); None / empty returns to probing."""
@@ -525,26 +583,22 @@ class Codec:
     # ---- host buffers (numpy) -------------------------------------------------------------------------
     def encode_host(self, clouds: Sequence[np.ndarray]):
         """Encode a batch of host-resident clouds. Returns (list of framed stage-1 streams, chunk_sizes, modes)."""
-        step = self.plan.point_step
-        arrs = [np.ascontiguousarray(c).view(np.uint8).reshape(-1) for c in clouds]
-        npts = np.array([a.size // step for a in arrs], dtype=np.uint64)
-        for a in arrs:
-            if a.size % step:
-                raise ValueError("Input cloud_data size is not a multiple of point_step")
-        data = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
-        cap = int(sum(self.plan.stage2_bound(int(n), getattr(self, "_stage2", 0)) for n in npts))
+        data, npts = _pack_clouds(clouds, self.plan.point_step)
+        n = npts.size
+        cap = self._out_capacity(npts)
         out = np.empty(max(cap, 1), dtype=np.uint8)
-        offs = np.zeros(len(arrs) + 1, dtype=np.uint64)
-        n_chunks = int(sum((int(n) + 32767) // 32768 for n in npts))
-        chunk_sizes = np.zeros(max(1, n_chunks), dtype=np.uint32)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        chunk_sizes = np.zeros(max(1, _n_chunks(npts)), dtype=np.uint32)
         na = self.plan.adaptive_fields
-        modes = np.zeros(max(1, len(arrs) * max(1, na)), dtype=np.uint8)
-        _check(lib().cldn_hip_encode_stage1(
-            self._h, data.ctypes.data_as(C.c_void_p), HOST, npts.ctypes.data_as(C.POINTER(C.c_uint64)), len(arrs),
-            out.ctypes.data_as(C.c_void_p), cap, HOST, offs.ctypes.data_as(C.c_void_p),
-            chunk_sizes.ctypes.data_as(C.c_void_p), modes.ctypes.data_as(C.c_void_p)))
-        streams = [out[int(offs[k]):int(offs[k + 1])].copy() for k in range(len(arrs))]
-        return streams, chunk_sizes[:n_chunks], modes[: len(arrs) * na].reshape(len(arrs), na)
+        modes = np.zeros(max(1, n * max(1, na)), dtype=np.uint8)
+        _check(lib().cldn_hip_encode_stage1(self._h, _ptr(data), HOST, _p64(npts), n, _ptr(out), cap, HOST, _ptr(offs),
+                                            _ptr(chunk_sizes), _ptr(modes)))
+        streams = [v.copy() for v in _split(out, offs)]
+        return streams, chunk_sizes[:_n_chunks(npts)], modes[: n * na].reshape(n, na)
+
+    def _out_capacity(self, cloud_points) -> int:
+        """Bytes that the streams of a batch can take under the codec's stage 2."""
+        return int(sum(self.plan.stage2_bound(int(n), getattr(self, "_stage2", 0)) for n in cloud_points))
 
     # ---- chunk-table output ----------------------------------------------------------------------------
     def encode_chunks_device(self, points_ptr: int, cloud_points: np.ndarray, modes_ptr: int = 0) -> ChunkTable:
@@ -570,31 +624,9 @@ class Codec:
 
     def decode_host(self, streams: Sequence[np.ndarray], cloud_points: Sequence[int],
                     out: Optional[np.ndarray] = None, chunk_sizes=None) -> List[np.ndarray]:
-        step = self.plan.point_step
-        arrs = [np.ascontiguousarray(s).view(np.uint8).reshape(-1) for s in streams]
-        offs = np.zeros(len(arrs) + 1, dtype=np.uint64)
-        offs[1:] = np.cumsum([a.size for a in arrs])
-        data = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
-        npts = np.array(list(cloud_points), dtype=np.uint64)
-        total = int(npts.sum()) * step
-        if out is None:
-            out = np.zeros(max(1, total), dtype=np.uint8)
-        cs = None if chunk_sizes is None else np.ascontiguousarray(chunk_sizes, dtype=np.uint32)
-        if cs is not None:
-            n_chunks = int(sum((int(n) + 32767) // 32768 for n in npts))
-            if cs.size < n_chunks:  # the C side reads n_chunks sizes
-                raise ValueError(f"chunk_sizes has {cs.size} entries, the batch has {n_chunks} chunks")
-        _check(lib().cldn_hip_decode_stage1_sized(
-            self._h, data.ctypes.data_as(C.c_void_p), HOST, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-            npts.ctypes.data_as(C.POINTER(C.c_uint64)), len(arrs), None if cs is None else cs.ctypes.data_as(C.c_void_p), HOST,
-            out.ctypes.data_as(C.c_void_p), total, HOST))
-        res, pos = [], 0
-        for n in npts:
-            res.append(out[pos:pos + int(n) * step])
-            pos += int(n) * step
-        return res
+        cloud_points = list(cloud_points)
+        cs, cs_ptr = _chunk_sizes(chunk_sizes, cloud_points)
+        return _decode_host(self, lib().cldn_hip_decode_stage1_sized, streams, cloud_points, out, cs_ptr, HOST)
 
     def decode_device(self, streams_ptr: int, stream_offsets: np.ndarray, cloud_points: np.ndarray, out_ptr: int,
                       out_capacity: int, chunk_sizes_ptr: int = 0):
@@ -619,61 +651,21 @@ class Codec:
         back to back in `out` (span k starts at sum(capacities[:k])), sizes[k] = decoded bytes or 0xffffffff for a refused
         block. Raises CloudiniHipError (CORRUPT) when a block is refused unless `out` is given -- then the error is returned
         as a third element so that the caller can look at the other blocks."""
-        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blocks]
-        bo = np.zeros(len(arrs) + 1, dtype=np.uint64)
-        bo[1:] = np.cumsum([a.size for a in arrs])
-        oo = np.zeros(len(arrs) + 1, dtype=np.uint64)
-        oo[1:] = np.cumsum([int(c) for c in capacities])
-        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
-        keep = out is not None
-        if out is None:
-            out = np.zeros(max(1, int(oo[-1])), dtype=np.uint8)
-        sizes = np.zeros(max(1, len(arrs)), dtype=np.uint32)
-        rc = lib().cldn_hip_lz4_decompress(self._h, data.ctypes.data_as(C.c_void_p), HOST, bo.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                           len(arrs), out.ctypes.data_as(C.c_void_p), HOST,
-                                           oo.ctypes.data_as(C.POINTER(C.c_uint64)), sizes.ctypes.data_as(C.c_void_p))
-        if keep:
-            return out, sizes[: len(arrs)], rc
-        _check(rc)
-        return out, sizes[: len(arrs)]
+        return _decompress_host(self, lib().cldn_hip_lz4_decompress, blocks, capacities, out)
 
     def lz4_decompress_device(self, blocks_ptr: int, block_offsets: np.ndarray, out_ptr: int, out_offsets: np.ndarray,
                               sizes_ptr: int):
         """The same on device buffers (asynchronous; refused blocks show in sizes and in status())."""
-        bo = np.ascontiguousarray(block_offsets, dtype=np.uint64)
-        oo = np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        _check(lib().cldn_hip_lz4_decompress(self._h, C.c_void_p(blocks_ptr), DEVICE, bo.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             bo.size - 1, C.c_void_p(out_ptr), DEVICE, oo.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             C.c_void_p(sizes_ptr)))
+        _decompress_device(self, lib().cldn_hip_lz4_decompress, blocks_ptr, block_offsets, out_ptr, out_offsets, sizes_ptr)
 
     def decode_lz4_host(self, streams: Sequence[np.ndarray], cloud_points: Sequence[int],
                         out: Optional[np.ndarray] = None) -> List[np.ndarray]:
         """decode_host for streams whose chunks are [u32 block size][LZ4 block] (the body of an LZ4 message)."""
-        step = self.plan.point_step
-        arrs = [np.ascontiguousarray(s).view(np.uint8).reshape(-1) for s in streams]
-        offs = np.zeros(len(arrs) + 1, dtype=np.uint64)
-        offs[1:] = np.cumsum([a.size for a in arrs])
-        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
-        npts = np.array(list(cloud_points), dtype=np.uint64)
-        total = int(npts.sum()) * step
-        if out is None:
-            out = np.zeros(max(1, total), dtype=np.uint8)
-        _check(lib().cldn_hip_decode_lz4(
-            self._h, data.ctypes.data_as(C.c_void_p), HOST, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-            npts.ctypes.data_as(C.POINTER(C.c_uint64)), len(arrs), out.ctypes.data_as(C.c_void_p), total, HOST))
-        res, pos = [], 0
-        for n in npts:
-            res.append(out[pos:pos + int(n) * step])
-            pos += int(n) * step
-        return res
+        return _decode_host(self, lib().cldn_hip_decode_lz4, streams, cloud_points, out)
 
     def decode_lz4_device(self, streams_ptr: int, stream_offsets: np.ndarray, cloud_points: np.ndarray, out_ptr: int,
                           out_capacity: int):
-        so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
-        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
-        _check(lib().cldn_hip_decode_lz4(
-            self._h, C.c_void_p(streams_ptr), DEVICE, so.ctypes.data_as(C.POINTER(C.c_uint64)),
-            cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, C.c_void_p(out_ptr), int(out_capacity), DEVICE))
+        _decode_device(self, lib().cldn_hip_decode_lz4, streams_ptr, stream_offsets, cloud_points, out_ptr, out_capacity)
 
     # ---- ZSTD frames without sequences back into bytes (cldn_hip_zstd_decompress / cldn_hip_decode_zstd) ----------
     def zstd_decompress_host(self, frames: Sequence[bytes], capacities: Sequence[int], out: Optional[np.ndarray] = None):
@@ -682,62 +674,22 @@ class Codec:
         frame, 0xfffffffe for one that needs the host (sequences, checksum, ...). Raises CloudiniHipError (CORRUPT, else
         UNSUPPORTED) for those unless `out` is given -- then the error is returned as a third element so that the caller
         can look at the other frames."""
-        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in frames]
-        bo = np.zeros(len(arrs) + 1, dtype=np.uint64)
-        bo[1:] = np.cumsum([a.size for a in arrs])
-        oo = np.zeros(len(arrs) + 1, dtype=np.uint64)
-        oo[1:] = np.cumsum([int(c) for c in capacities])
-        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
-        keep = out is not None
-        if out is None:
-            out = np.zeros(max(1, int(oo[-1])), dtype=np.uint8)
-        sizes = np.zeros(max(1, len(arrs)), dtype=np.uint32)
-        rc = lib().cldn_hip_zstd_decompress(self._h, data.ctypes.data_as(C.c_void_p), HOST, bo.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                           len(arrs), out.ctypes.data_as(C.c_void_p), HOST,
-                                           oo.ctypes.data_as(C.POINTER(C.c_uint64)), sizes.ctypes.data_as(C.c_void_p))
-        if keep:
-            return out, sizes[: len(arrs)], rc
-        _check(rc)
-        return out, sizes[: len(arrs)]
+        return _decompress_host(self, lib().cldn_hip_zstd_decompress, frames, capacities, out)
 
     def zstd_decompress_device(self, frames_ptr: int, frame_offsets: np.ndarray, out_ptr: int, out_offsets: np.ndarray,
                               sizes_ptr: int):
         """The same on device buffers (asynchronous; the verdicts show in sizes and in status())."""
-        bo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
-        oo = np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        _check(lib().cldn_hip_zstd_decompress(self._h, C.c_void_p(frames_ptr), DEVICE, bo.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             bo.size - 1, C.c_void_p(out_ptr), DEVICE, oo.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             C.c_void_p(sizes_ptr)))
+        _decompress_device(self, lib().cldn_hip_zstd_decompress, frames_ptr, frame_offsets, out_ptr, out_offsets, sizes_ptr)
 
     def decode_zstd_host(self, streams: Sequence[np.ndarray], cloud_points: Sequence[int],
                         out: Optional[np.ndarray] = None) -> List[np.ndarray]:
         """decode_host for streams whose chunks are [u32 frame size][ZSTD frame] (the body of a ZSTD message); UNSUPPORTED
         when a frame carries sequences or options the device decoder does not take."""
-        step = self.plan.point_step
-        arrs = [np.ascontiguousarray(s).view(np.uint8).reshape(-1) for s in streams]
-        offs = np.zeros(len(arrs) + 1, dtype=np.uint64)
-        offs[1:] = np.cumsum([a.size for a in arrs])
-        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
-        npts = np.array(list(cloud_points), dtype=np.uint64)
-        total = int(npts.sum()) * step
-        if out is None:
-            out = np.zeros(max(1, total), dtype=np.uint8)
-        _check(lib().cldn_hip_decode_zstd(
-            self._h, data.ctypes.data_as(C.c_void_p), HOST, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-            npts.ctypes.data_as(C.POINTER(C.c_uint64)), len(arrs), out.ctypes.data_as(C.c_void_p), total, HOST))
-        res, pos = [], 0
-        for n in npts:
-            res.append(out[pos:pos + int(n) * step])
-            pos += int(n) * step
-        return res
+        return _decode_host(self, lib().cldn_hip_decode_zstd, streams, cloud_points, out)
 
     def decode_zstd_device(self, streams_ptr: int, stream_offsets: np.ndarray, cloud_points: np.ndarray, out_ptr: int,
                           out_capacity: int):
-        so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
-        cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
-        _check(lib().cldn_hip_decode_zstd(
-            self._h, C.c_void_p(streams_ptr), DEVICE, so.ctypes.data_as(C.POINTER(C.c_uint64)),
-            cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, C.c_void_p(out_ptr), int(out_capacity), DEVICE))
+        _decode_device(self, lib().cldn_hip_decode_zstd, streams_ptr, stream_offsets, cloud_points, out_ptr, out_capacity)
 
     # ---- LZ4 / ZSTD message bodies where they lie (cldn_hip_decode_lz4_gather / cldn_hip_decode_zstd_gather) ---------
     def decode_stage2_gather(self, stage2: int, bodies: Sequence[np.ndarray], cloud_points: Sequence[int], chunk_sizes=None,
@@ -754,13 +706,12 @@ class Codec:
         ptrs = (C.c_void_p * max(1, n))(*[a.ctypes.data if a.size else None for a in arrs])
         sizes = np.array([a.size for a in arrs], dtype=np.uint64)
         npts = np.array(list(cloud_points), dtype=np.uint64)
-        n_chunks = int(sum((int(k) + 32767) // 32768 for k in npts))
-        total = int(npts.sum()) * step
+        n_chunks = _n_chunks(npts)
+        ends = _prefix(npts * step)
+        total = int(ends[-1])
         if out is None:
             out = np.zeros(max(1, total), dtype=np.uint8)
-        cs = None if chunk_sizes is None else np.ascontiguousarray(chunk_sizes, dtype=np.uint32)
-        if cs is not None and cs.size < n_chunks:
-            raise ValueError(f"chunk_sizes has {cs.size} entries, the batch has {n_chunks} chunks")
+        cs, cs_ptr = _chunk_sizes(chunk_sizes, npts)
         verdicts = np.full(max(1, n_chunks), 0xEEEEEEEE, dtype=np.uint32)
         exp_ptrs = exp_sizes = None
         keep = []
@@ -772,35 +723,22 @@ class Codec:
             exp_ptrs = (C.c_void_p * max(1, n_chunks))(*[None if e is None else e.ctypes.data for e in keep])
             exp_sizes = np.array([0 if e is None else e.size for e in keep], dtype=np.uint32)
         fn = lib().cldn_hip_decode_lz4_gather if stage2 == STAGE2_LZ4 else lib().cldn_hip_decode_zstd_gather
-        rc = fn(self._h, ptrs, sizes.ctypes.data_as(C.POINTER(C.c_uint64)), npts.ctypes.data_as(C.POINTER(C.c_uint64)), n,
-                None if cs is None else cs.ctypes.data_as(C.c_void_p), exp_ptrs,
-                None if exp_sizes is None else exp_sizes.ctypes.data_as(C.c_void_p), verdicts.ctypes.data_as(C.c_void_p),
-                out.ctypes.data_as(C.c_void_p), total, HOST)
-        res, pos = [], 0
-        for k in npts:
-            res.append(out[pos:pos + int(k) * step])
-            pos += int(k) * step
-        return res, verdicts[:n_chunks], rc
+        rc = fn(self._h, ptrs, _p64(sizes), _p64(npts), n, cs_ptr, exp_ptrs, None if exp_sizes is None else _ptr(exp_sizes),
+                _ptr(verdicts), _ptr(out), total, HOST)
+        return _split(out, ends), verdicts[:n_chunks], rc
 
     # ---- audit: per-field error reports (cldn_hip_audit_*) -----------------------------------------------------------
-    def _audit_report(self, n_clouds: int) -> np.ndarray:
-        rep = np.zeros((int(n_clouds), self.plan.n_fields), dtype=AUDIT_DTYPE)
-        rep.view(np.uint8)[...] = 0xEE  # (a call that fails leaves it as it was)
-        return rep
-
     def audit_clouds_host(self, a: Sequence[np.ndarray], b: Sequence[np.ndarray], limit=None, report: Optional[np.ndarray] = None):
         """cldn_hip_audit_clouds on host buffers: clouds a[k] against b[k]. Returns the (n_clouds, n_fields) report."""
         step = self.plan.point_step
-        aa = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in a]
-        bb = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in b]
+        aa, bb = [_bytes(x) for x in a], [_bytes(x) for x in b]
         if [x.size for x in aa] != [x.size for x in bb] or any(x.size % step for x in aa):
             raise ValueError("the two batches must have the same whole number of points per cloud")
         cp = np.array([x.size // step for x in aa], dtype=np.uint64)
-        da, db = np.concatenate(aa + [np.zeros(1, np.uint8)]), np.concatenate(bb + [np.zeros(1, np.uint8)])
-        rep = self._audit_report(len(aa)) if report is None else report
+        (da, _), (db, _) = _pack(aa), _pack(bb)
+        rep = _report((len(aa), self.plan.n_fields), AUDIT_DTYPE) if report is None else report
         lim, lp = _limit_ptr(limit, self.plan.n_fields)
-        _check(lib().cldn_hip_audit_clouds(self._h, da.ctypes.data_as(C.c_void_p), HOST, db.ctypes.data_as(C.c_void_p), HOST,
-                                           cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, lp, rep.ctypes.data_as(C.c_void_p), HOST))
+        _check(lib().cldn_hip_audit_clouds(self._h, _ptr(da), HOST, _ptr(db), HOST, _p64(cp), cp.size, lp, _ptr(rep), HOST))
         return rep
 
     def audit_clouds_device(self, a_ptr: int, b_ptr: int, cloud_points, limit=None, report_ptr: int = 0, a_loc: int = DEVICE,
@@ -809,29 +747,22 @@ class Codec:
         enqueues work when both buffers are on the device; returns None), 0 = host report (returned)."""
         cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
         lim, lp = _limit_ptr(limit, self.plan.n_fields)
-        rep = None if report_ptr else self._audit_report(cp.size)
-        _check(lib().cldn_hip_audit_clouds(self._h, C.c_void_p(a_ptr), a_loc, C.c_void_p(b_ptr), b_loc,
-                                           cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size, lp,
-                                           C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                           DEVICE if report_ptr else HOST))
+        rep = None if report_ptr else _report((cp.size, self.plan.n_fields), AUDIT_DTYPE)
+        _check(lib().cldn_hip_audit_clouds(self._h, C.c_void_p(a_ptr), a_loc, C.c_void_p(b_ptr), b_loc, _p64(cp), cp.size, lp,
+                                           *_report_arg(rep, report_ptr)))
         return rep
 
     def audit_streams_host(self, clouds: Sequence[np.ndarray], streams: Sequence[np.ndarray], stream_kind: int = 0, limit=None,
                            report: Optional[np.ndarray] = None):
         """cldn_hip_audit_streams on host buffers: clouds[k] against the decode of streams[k] (stream_kind 0: framed stage-1
         streams, 1: [u32 size][LZ4 block] per chunk)."""
-        step = self.plan.point_step
-        pts = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in clouds]
-        ss = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in streams]
-        cp = np.array([x.size // step for x in pts], dtype=np.uint64)
-        offs = np.zeros(len(ss) + 1, dtype=np.uint64)
-        offs[1:] = np.cumsum([x.size for x in ss])
-        dp, ds = np.concatenate(pts + [np.zeros(1, np.uint8)]), np.concatenate(ss + [np.zeros(1, np.uint8)])
-        rep = self._audit_report(len(pts)) if report is None else report
+        pts = [_bytes(x) for x in clouds]
+        cp = np.array([x.size // self.plan.point_step for x in pts], dtype=np.uint64)
+        (dp, _), (ds, offs) = _pack(pts), _pack([_bytes(x) for x in streams])
+        rep = _report((len(pts), self.plan.n_fields), AUDIT_DTYPE) if report is None else report
         lim, lp = _limit_ptr(limit, self.plan.n_fields)
-        _check(lib().cldn_hip_audit_streams(self._h, dp.ctypes.data_as(C.c_void_p), HOST, ds.ctypes.data_as(C.c_void_p), HOST,
-                                            offs.ctypes.data_as(C.POINTER(C.c_uint64)), cp.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                            cp.size, int(stream_kind), lp, rep.ctypes.data_as(C.c_void_p), HOST))
+        _check(lib().cldn_hip_audit_streams(self._h, _ptr(dp), HOST, _ptr(ds), HOST, _p64(offs), _p64(cp), cp.size, int(stream_kind),
+                                            lp, _ptr(rep), HOST))
         return rep
 
     def audit_streams_device(self, points_ptr: int, streams_ptr: int, stream_offsets, cloud_points, stream_kind: int = 0,
@@ -840,40 +771,25 @@ class Codec:
         so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
         cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
         lim, lp = _limit_ptr(limit, self.plan.n_fields)
-        rep = None if report_ptr else self._audit_report(cp.size)
-        _check(lib().cldn_hip_audit_streams(self._h, C.c_void_p(points_ptr), DEVICE, C.c_void_p(streams_ptr), DEVICE,
-                                            so.ctypes.data_as(C.POINTER(C.c_uint64)), cp.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                            cp.size, int(stream_kind), lp,
-                                            C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                            DEVICE if report_ptr else HOST))
+        rep = None if report_ptr else _report((cp.size, self.plan.n_fields), AUDIT_DTYPE)
+        _check(lib().cldn_hip_audit_streams(self._h, C.c_void_p(points_ptr), DEVICE, C.c_void_p(streams_ptr), DEVICE, _p64(so),
+                                            _p64(cp), cp.size, int(stream_kind), lp, *_report_arg(rep, report_ptr)))
         return rep
 
     def audit_last_encode(self, limit=None, report_ptr: int = 0):
         """cldn_hip_audit_last_encode: this codec's most recent encode call against the decode of what it wrote; one row per
         cloud of that call (the filtered clouds of a viz call). Raises CloudiniHipError (ARG) when another call came between."""
-        n = int(lib().cldn_hip_audit_last_encode_clouds(self._h))
-        _check(n)
+        n = _last_encode_clouds(lib().cldn_hip_audit_last_encode_clouds, self)
         lim, lp = _limit_ptr(limit, self.plan.n_fields)
-        rep = None if report_ptr else self._audit_report(n)
-        _check(lib().cldn_hip_audit_last_encode(self._h, lp, C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                                DEVICE if report_ptr else HOST))
+        rep = None if report_ptr else _report((n, self.plan.n_fields), AUDIT_DTYPE)
+        _check(lib().cldn_hip_audit_last_encode(self._h, lp, *_report_arg(rep, report_ptr)))
         return rep
 
     # ---- resolution sweep: size and error per field and candidate (cldn_hip_sweep_*) ---------------------------------
-    def _sweep_report(self, n_clouds: int, n_candidates: int) -> np.ndarray:
-        rep = np.zeros((int(n_clouds), self.plan.n_fields, int(n_candidates)), dtype=SWEEP_DTYPE)
-        rep.view(np.uint8)[...] = 0xEE  # (a call that fails leaves it as it was)
-        return rep
-
     def sweep_clouds_host(self, clouds: Sequence[np.ndarray], resolutions) -> np.ndarray:
         """cldn_hip_sweep_clouds on host buffers. resolutions: (n_fields, n_candidates), one ladder per field, 0 = skip.
         Returns the (n_clouds, n_fields, n_candidates) report."""
-        step = self.plan.point_step
-        arrs = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in clouds]
-        if any(x.size % step for x in arrs):
-            raise ValueError("Input cloud_data size is not a multiple of point_step")
-        cp = np.array([x.size // step for x in arrs], dtype=np.uint64)
-        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        data, cp = _pack_clouds(clouds, self.plan.point_step)
         return self.sweep_clouds_device(data.ctypes.data, cp, resolutions, points_loc=HOST)
 
     def sweep_clouds_device(self, points_ptr: int, cloud_points, resolutions, report_ptr: int = 0, points_loc: int = DEVICE):
@@ -881,32 +797,22 @@ class Codec:
         only enqueues work when the points are on the device; returns None), 0 = host report (returned)."""
         cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
         res = _ladders(resolutions, self.plan.n_fields)
-        rep = None if report_ptr else self._sweep_report(cp.size, res.shape[1])
-        _check(lib().cldn_hip_sweep_clouds(self._h, C.c_void_p(points_ptr), points_loc, cp.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                           cp.size, res.ctypes.data_as(C.c_void_p), res.shape[1],
-                                           C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                           DEVICE if report_ptr else HOST))
+        rep = None if report_ptr else _report((cp.size, self.plan.n_fields, res.shape[1]), SWEEP_DTYPE)
+        _check(lib().cldn_hip_sweep_clouds(self._h, C.c_void_p(points_ptr), points_loc, _p64(cp), cp.size, _ptr(res), res.shape[1],
+                                           *_report_arg(rep, report_ptr)))
         return rep
 
     def sweep_last_encode(self, resolutions, report_ptr: int = 0):
         """cldn_hip_sweep_last_encode: the points of this codec's most recent encode call (the survivors of a viz call), one row
         per cloud of that call. Valid from the encode call on (a chunk table need not be framed); leaves the state for
         audit_last_encode as it found it. Raises CloudiniHipError (ARG) when another call came between."""
-        n = int(lib().cldn_hip_sweep_last_encode_clouds(self._h))
-        _check(n)
+        n = _last_encode_clouds(lib().cldn_hip_sweep_last_encode_clouds, self)
         res = _ladders(resolutions, self.plan.n_fields)
-        rep = None if report_ptr else self._sweep_report(n, res.shape[1])
-        _check(lib().cldn_hip_sweep_last_encode(self._h, res.ctypes.data_as(C.c_void_p), res.shape[1],
-                                                C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                                DEVICE if report_ptr else HOST))
+        rep = None if report_ptr else _report((n, self.plan.n_fields, res.shape[1]), SWEEP_DTYPE)
+        _check(lib().cldn_hip_sweep_last_encode(self._h, _ptr(res), res.shape[1], *_report_arg(rep, report_ptr)))
         return rep
 
     # ---- byte histograms for the stage-2 estimate (cldn_hip_sweep_hist_*, cldn_hip_stream_hist*) ---------------------
-    def _hist_report(self, *shape) -> np.ndarray:
-        rep = np.zeros(tuple(int(n) for n in shape) + (256,), dtype=np.uint64)
-        rep.view(np.uint8)[...] = 0xEE  # (a call that fails leaves it as it was)
-        return rep
-
     def hist_walk(self, blocks: int):
         """Test and measurement hook (cldn_hip_debug_hist_walk): 1024-point blocks per workgroup of k_sweep_hist, 0 = default."""
         _check(lib().cldn_hip_debug_hist_walk(self._h, int(blocks)))
@@ -914,42 +820,29 @@ class Codec:
     def sweep_hist_clouds_host(self, clouds: Sequence[np.ndarray], resolutions) -> np.ndarray:
         """cldn_hip_sweep_hist_clouds on host buffers; arguments as sweep_clouds_host. Returns the
         (n_clouds, n_fields, n_candidates, 256) uint64 report."""
-        step = self.plan.point_step
-        arrs = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in clouds]
-        if any(x.size % step for x in arrs):
-            raise ValueError("Input cloud_data size is not a multiple of point_step")
-        cp = np.array([x.size // step for x in arrs], dtype=np.uint64)
-        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        data, cp = _pack_clouds(clouds, self.plan.point_step)
         return self.sweep_hist_clouds_device(data.ctypes.data, cp, resolutions, points_loc=HOST)
 
     def sweep_hist_clouds_device(self, points_ptr: int, cloud_points, resolutions, report_ptr: int = 0, points_loc: int = DEVICE):
         """cldn_hip_sweep_hist_clouds on a raw pointer; report_ptr as in sweep_clouds_device (2048 bytes per histogram)."""
         cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
         res = _ladders(resolutions, self.plan.n_fields)
-        rep = None if report_ptr else self._hist_report(cp.size, self.plan.n_fields, res.shape[1])
-        _check(lib().cldn_hip_sweep_hist_clouds(self._h, C.c_void_p(points_ptr), points_loc, cp.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                cp.size, res.ctypes.data_as(C.c_void_p), res.shape[1],
-                                                C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                                DEVICE if report_ptr else HOST))
+        rep = None if report_ptr else _report((cp.size, self.plan.n_fields, res.shape[1], 256), np.uint64)
+        _check(lib().cldn_hip_sweep_hist_clouds(self._h, C.c_void_p(points_ptr), points_loc, _p64(cp), cp.size, _ptr(res),
+                                                res.shape[1], *_report_arg(rep, report_ptr)))
         return rep
 
     def sweep_hist_last_encode(self, resolutions, report_ptr: int = 0):
         """cldn_hip_sweep_hist_last_encode: the points of this codec's most recent encode call; state rules as sweep_last_encode."""
-        n = int(lib().cldn_hip_sweep_last_encode_clouds(self._h))
-        _check(n)
+        n = _last_encode_clouds(lib().cldn_hip_sweep_last_encode_clouds, self)
         res = _ladders(resolutions, self.plan.n_fields)
-        rep = None if report_ptr else self._hist_report(n, self.plan.n_fields, res.shape[1])
-        _check(lib().cldn_hip_sweep_hist_last_encode(self._h, res.ctypes.data_as(C.c_void_p), res.shape[1],
-                                                     C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                                     DEVICE if report_ptr else HOST))
+        rep = None if report_ptr else _report((n, self.plan.n_fields, res.shape[1], 256), np.uint64)
+        _check(lib().cldn_hip_sweep_hist_last_encode(self._h, _ptr(res), res.shape[1], *_report_arg(rep, report_ptr)))
         return rep
 
     def stream_hist_host(self, streams: Sequence[np.ndarray]) -> np.ndarray:
         """cldn_hip_stream_hist on host buffers: one (256,) uint64 histogram per stream."""
-        ss = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in streams]
-        offs = np.zeros(len(ss) + 1, dtype=np.uint64)
-        offs[1:] = np.cumsum([x.size for x in ss])
-        data = np.concatenate(ss + [np.zeros(1, np.uint8)])
+        data, offs = _pack([_bytes(x) for x in streams])
         return self.stream_hist_device(data.ctypes.data, offs, streams_loc=HOST)
 
     def stream_hist_device(self, streams_ptr: int, stream_offsets, report_ptr: int = 0, streams_loc: int = DEVICE):
@@ -957,53 +850,37 @@ class Codec:
         histograms (returns None), 0 = host report (returned)."""
         so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
         n = max(0, so.size - 1)
-        rep = None if report_ptr else self._hist_report(n)
-        _check(lib().cldn_hip_stream_hist(self._h, C.c_void_p(streams_ptr), streams_loc, so.ctypes.data_as(C.POINTER(C.c_uint64)), n,
-                                          C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                          DEVICE if report_ptr else HOST))
+        rep = None if report_ptr else _report((n, 256), np.uint64)
+        _check(lib().cldn_hip_stream_hist(self._h, C.c_void_p(streams_ptr), streams_loc, _p64(so), n, *_report_arg(rep, report_ptr)))
         return rep
 
     def stream_hist_last_encode(self, report_ptr: int = 0):
         """cldn_hip_stream_hist_last_encode: the streams this codec's most recent framed encode call wrote, one row per cloud."""
-        n = int(lib().cldn_hip_audit_last_encode_clouds(self._h))
-        _check(n)
-        rep = None if report_ptr else self._hist_report(n)
-        _check(lib().cldn_hip_stream_hist_last_encode(self._h, C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                                      DEVICE if report_ptr else HOST))
+        n = _last_encode_clouds(lib().cldn_hip_audit_last_encode_clouds, self)
+        rep = None if report_ptr else _report((n, 256), np.uint64)
+        _check(lib().cldn_hip_stream_hist_last_encode(self._h, *_report_arg(rep, report_ptr)))
         return rep
 
     # ---- adaptive integer modes: section bytes per mode, probed and best mode (cldn_hip_sweep_modes_*) ---------------
-    def _mode_report(self, n_clouds: int) -> np.ndarray:
-        rep = np.zeros((int(n_clouds), self.plan.adaptive_fields), dtype=MODE_DTYPE)
-        rep.view(np.uint8)[...] = 0xEE  # (a call that fails leaves it as it was)
-        return rep
-
     def sweep_modes_host(self, clouds: Sequence[np.ndarray]) -> np.ndarray:
         """cldn_hip_sweep_modes_clouds on host buffers. Returns the (n_clouds, adaptive fields) report."""
-        step = self.plan.point_step
-        arrs = [np.ascontiguousarray(x).view(np.uint8).reshape(-1) for x in clouds]
-        if any(x.size % step for x in arrs):
-            raise ValueError("Input cloud_data size is not a multiple of point_step")
-        cp = np.array([x.size // step for x in arrs], dtype=np.uint64)
-        data = np.concatenate(arrs + [np.zeros(1, np.uint8)])
+        data, cp = _pack_clouds(clouds, self.plan.point_step)
         return self.sweep_modes_device(data.ctypes.data, cp, points_loc=HOST)
 
     def sweep_modes_device(self, points_ptr: int, cloud_points, report_ptr: int = 0, points_loc: int = DEVICE):
         """cldn_hip_sweep_modes_clouds on a raw pointer. report_ptr: device array of n_clouds * adaptive fields cells (the call
         only enqueues work when the points are on the device; returns None), 0 = host report (returned)."""
         cp = np.ascontiguousarray(cloud_points, dtype=np.uint64)
-        rep = None if report_ptr else self._mode_report(cp.size)
-        _check(lib().cldn_hip_sweep_modes_clouds(self._h, C.c_void_p(points_ptr), points_loc, cp.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                 cp.size, C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                                 DEVICE if report_ptr else HOST))
+        rep = None if report_ptr else _report((cp.size, self.plan.adaptive_fields), MODE_DTYPE)
+        _check(lib().cldn_hip_sweep_modes_clouds(self._h, C.c_void_p(points_ptr), points_loc, _p64(cp), cp.size,
+                                                 *_report_arg(rep, report_ptr)))
         return rep
 
     def sweep_modes_last_encode(self, report_ptr: int = 0):
         """cldn_hip_sweep_modes_last_encode: the points of this codec's most recent encode call (the survivors of a viz call),
         one row per cloud of that call; leaves the state for audit_last_encode and sweep_last_encode as it found it."""
-        n = int(lib().cldn_hip_sweep_last_encode_clouds(self._h))
-        _check(n)
-        rep = None if report_ptr else self._mode_report(n)
-        _check(lib().cldn_hip_sweep_modes_last_encode(self._h, C.c_void_p(report_ptr) if report_ptr else rep.ctypes.data_as(C.c_void_p),
-                                                      DEVICE if report_ptr else HOST))
+        n = _last_encode_clouds(lib().cldn_hip_sweep_last_encode_clouds, self)
+        rep = None if report_ptr else _report((n, self.plan.adaptive_fields), MODE_DTYPE)
+        _check(lib().cldn_hip_sweep_modes_last_encode(self._h, *_report_arg(rep, report_ptr)))
         return rep
+

@@ -315,7 +315,7 @@ def _legs(oracle, codec, plan, info, data, n, s1, body, want, number, every_leg)
         # the point kernel's launch shape: chained, 2 and 16 workgroups per chunk
         for parts in (1, 2, 16):
             c4 = native.Codec(plan)
-            assert native.lib().cldn_hip_debug_decode_split(c4._h, parts) == 0
+            assert c4.decode_split(parts) == 0
             got = c4.decode_lz4_host([body, body], [n, n], out=_filled(2 * data.size))
             assert np.array_equal(got[0], want) and np.array_equal(got[1], want), (number, "split", parts)
             c4.close()

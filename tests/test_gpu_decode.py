@@ -6,6 +6,8 @@ import pytest
 import cases
 import gorilla_cases as GC
 import gorilla_model as GM
+import lz4_body
+import zstd_lit_model
 from cloudini_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -651,7 +653,7 @@ def test_chained_and_split_launches_of_the_point_kernel_agree(oracle, parts):
         step = info.point_step
         n = data.size // step
         codec = native.Codec(native.Plan(info))
-        assert native.lib().cldn_hip_debug_decode_split(codec._h, parts) == 0
+        assert codec.decode_split(parts) == 0
         stream = oracle.encode_stage1(info, data)
         out = np.full(max(1, data.size), 0x5A, dtype=np.uint8)
         got = codec.decode_host([stream, stream], [n, n], out=np.concatenate([out, out]))
@@ -770,4 +772,59 @@ def test_host_chunk_sizes_of_one_and_two_chunks_land_behind_the_flag_arrays(orac
     wrong[-1] += 1                                                          # (the uploaded sizes are what the kernels read)
     with pytest.raises(native.CloudiniHipError):
         codec.decode_host([stream], [n], chunk_sizes=wrong)
+    codec.close()
+
+
+def _zstd_body(stream):
+    """[u32 size][ZSTD frame of literal-only blocks] per chunk of a framed stage-1 stream"""
+    return lz4_body.frame([bytes(zstd_lit_model.frame(p)) for p in lz4_body.chunks_of(stream)])
+
+
+@pytest.mark.parametrize("counts", [[], [0], [1], [32768], [32769], [0, 1, 0]], ids=str)
+def test_smallest_batches_through_the_three_framed_host_decodes(oracle, counts):
+    """The shapes at which the packing of a host batch can go wrong -- no stream at all, a stream of no bytes (the batch's
+    buffer is then the spare byte alone), one point, one chunk and two -- through decode_host (with and without the chunks'
+    sizes), decode_lz4_host and decode_zstd_host, into a fresh output and into the caller's: the oracle's points, in views
+    of the caller's array."""
+    from cloudini_amd import native
+    info = synth.lidar_xyzi(10)[0]
+    step = info.point_step
+    clouds = [synth.lidar_xyzi(n, seed=40 + n % 11)[1] for n in counts]
+    streams = [oracle.encode_stage1(info, c) for c in clouds]
+    sizes = [p.size for s in streams for p in lz4_body.chunks_of(s)]
+    assert len(sizes) == sum((n + 32767) // 32768 for n in counts)
+    codec = native.Codec(native.Plan(info))
+    routes = [("stage1", lambda **kw: codec.decode_host(streams, counts, **kw)),
+              ("stage1 sized", lambda **kw: codec.decode_host(streams, counts, chunk_sizes=sizes, **kw)),
+              ("lz4", lambda **kw: codec.decode_lz4_host([lz4_body.body_of(s) for s in streams], counts, **kw)),
+              ("zstd", lambda **kw: codec.decode_zstd_host([_zstd_body(s) for s in streams], counts, **kw))]
+    for fill in (0, 0x5A):
+        want = [oracle.decode_stage1(info, s, n, fill=fill) for s, n in zip(streams, counts)]
+        for name, route in routes:
+            out = np.full(sum(counts) * step + 3, 0x5A, dtype=np.uint8) if fill else None   # (the call leaves the 3 alone)
+            got = route(out=out) if fill else route()
+            assert [g.size for g in got] == [n * step for n in counts], name
+            for k in range(len(counts)):
+                assert np.array_equal(got[k], want[k]), (name, fill, k)
+            if fill:
+                assert all(np.shares_memory(g, out) for g in got if g.size) and (out[sum(counts) * step:] == 0x5A).all(), name
+    codec.close()
+
+
+def test_decompress_calls_with_no_span_and_with_an_empty_one():
+    """lz4_decompress_host / zstd_decompress_host with an empty batch, and with one block / frame of an empty payload into
+    a span of no bytes: the rules' verdicts (tests/lz4_block_rules.py, tests/zstd_lit_rules.py), no byte written."""
+    from cloudini_amd import native
+    import lz4_block_rules
+    import zstd_lit_rules
+    codec = native.Codec(native.Plan(synth.lidar_xyzi(10)[0]))
+    block, frame = lz4_block_rules.lz4_compress(b""), bytes(zstd_lit_model.frame(np.zeros(0, np.uint8)))
+    assert lz4_block_rules.decode(block, 0) == b"" and zstd_lit_rules.decode(frame, 0) == (zstd_lit_rules.OK, b"")
+    for call, span in ((codec.lz4_decompress_host, block), (codec.zstd_decompress_host, frame)):
+        for spans, caps, want in (([], [], []), ([span], [0], [0])):
+            out, sizes = call(spans, caps)
+            assert list(sizes) == want and sizes.dtype == np.uint32 and out.size == 1 and out[0] == 0
+            mine = np.full(4, 0x5A, dtype=np.uint8)
+            out, sizes, rc = call(spans, caps, out=mine)
+            assert rc == 0 and out is mine and list(sizes) == want and (mine == 0x5A).all()
     codec.close()

@@ -144,7 +144,7 @@ def test_status_and_ticket_word_are_cleared_by_the_kernel(oracle):
     clouds = [xyzi(70000, 70), xyzi(33000, 71)]
     d = Dev()
     d.check(oracle, clouds, "before")
-    assert native.lib().cldn_hip_debug_finish_timeout_once(d.codec._h) == 0
+    assert d.codec.finish_timeout_once() == 0
     d_in, counts, cap, d_out, d_off, d_sizes, d_modes, _n = d.buffers(clouds)
     d.codec.encode_device(d_in.data_ptr(), counts, d_out.data_ptr(), cap, d_off.data_ptr(), d_sizes.data_ptr(), d_modes.data_ptr())
     d.codec.synchronize()

@@ -48,7 +48,7 @@ def test_trace_of_a_decode_call_equals_the_model(oracle, fillers, case, split):
         want += [(f_want, f_loc, f_out)] * LC.FILLERS
     codec = native.Codec(native.Plan(info))
     if split:
-        assert native.lib().cldn_hip_debug_decode_split(codec._h, split) == 0
+        assert codec.decode_split(split) == 0
     for call in range(2):      # the second call: the first one's hints have landed, a column left from it would show
         out = np.full(sum(npts) * info.point_step, FILL, dtype=np.uint8)
         got = codec.decode_host(streams, npts, out=out)

@@ -107,7 +107,7 @@ def _check_route_taken(row, M, stats, tr, what):
 
 def _set_split(codec, parts):
     from cloudini_amd import native
-    assert native.lib().cldn_hip_debug_decode_split(codec._h, parts) == 0
+    assert codec.decode_split(parts) == 0
 
 
 def _as_itself_and_pinned(row):

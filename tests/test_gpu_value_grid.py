@@ -40,7 +40,7 @@ def _decode_all(oracle, layout, infos, streams, ns, what):
     codec = native.Codec(native.Plan(info))
     for parts in (SPLITS if layout in V.POINT_DECODER_LAYOUTS else (0,)):
         if parts:
-            assert native.lib().cldn_hip_debug_decode_split(codec._h, parts) == 0
+            assert codec.decode_split(parts) == 0
         out = np.full(sum(ns) * info.point_step, FILL, dtype=np.uint8)
         got = codec.decode_host(streams, ns, out=out)
         for k, (g, w) in enumerate(zip(got, want)):

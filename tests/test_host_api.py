@@ -49,6 +49,67 @@ def test_c_abi_exports_every_declared_symbol():
     assert hip.cldn_hip_abi_version() == 1
 
 
+_C_SCALARS = {"int": C.c_int, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "int64_t": C.c_int64,
+              "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+
+
+def _c_prototypes():
+    """name -> (return type, [parameter declarations]) of every prototype of include/cloudini_hip.h and of the debug hooks
+    that cloudini_amd/csrc/hip_abi.hip exports outside it, as C text without comments."""
+    def text(*path):
+        src = open(os.path.join(ROOT, *path)).read()
+        return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", src, flags=re.S))
+
+    def params(s):
+        return [] if s.strip() == "void" else [" ".join(p.split()) for p in s.split(",")]
+
+    out = {}
+    for m in re.finditer(r"([A-Za-z_][\w \t]*?[\w*])\s*\b(cldn_hip_\w+)\s*\(([^()]*)\)\s*;", text("include", "cloudini_hip.h")):
+        out[m.group(2)] = (" ".join(m.group(1).split()), params(m.group(3)))
+    hooks = re.finditer(r'__attribute__\(\(visibility\("default"\)\)\)\s*([\w \t*]+?)\s*\b(cldn_hip_\w+)\s*\(([^()]*)\)\s*\{',
+                        text("cloudini_amd", "csrc", "hip_abi.hip"))
+    for m in hooks:
+        assert m.group(2) not in out, m.group(2)
+        out[m.group(2)] = (" ".join(m.group(1).split()), params(m.group(3)))
+    return out
+
+
+def _ctype_matches(c_type: str, ctype) -> bool:
+    """c_type: a return type or a parameter's type without its name. A pointer or array takes any pointer ctype; a scalar
+    takes the ctype of its kind (integer / floating), width and signedness; void (a return type) takes None."""
+    if "*" in c_type or "[" in c_type:
+        return ctype is not None and (ctype in (C.c_void_p, C.c_char_p) or issubclass(ctype, C._Pointer))
+    if c_type == "void":
+        return ctype is None
+    want = _C_SCALARS[c_type]
+    if ctype is None or not issubclass(ctype, C._SimpleCData) or ctype in (C.c_void_p, C.c_char_p):
+        return False
+    kind = lambda t: (t._type_ in "fd", t._type_ if t._type_ in "fd" else t._type_.islower(), C.sizeof(t))
+    return kind(ctype) == kind(want)
+
+
+def test_ctypes_signatures_match_the_c_declarations():
+    """native.SIGNATURES is a second copy of the C declarations: every prototype of include/cloudini_hip.h and every exported
+    debug hook of hip_abi.hip has an entry, no entry is left over, and each entry has the C side's number of parameters,
+    a pointer ctype per pointer / array and the scalar ctype of the same width and signedness, the return type included.
+    No GPU: the library loads without one."""
+    from cloudini_amd import native
+    protos = _c_prototypes()
+    assert len(protos) >= 73 and sum(n.startswith("cldn_hip_debug_") for n in protos) == 6
+    assert set(protos) == set(native.SIGNATURES), sorted(set(protos) ^ set(native.SIGNATURES))
+    for name, (ret, params) in protos.items():
+        restype, argtypes = native.SIGNATURES[name]
+        assert _ctype_matches(ret, restype), (name, ret, restype)
+        assert len(argtypes) == len(params), (name, params, argtypes)
+        for p, ctype in zip(params, argtypes):
+            c_type = p if "[" in p else p.rsplit(" ", 1)[0].replace("const ", "")  # (the last word is the parameter's name)
+            assert _ctype_matches(c_type, ctype), (name, p, ctype)
+    hip = native.lib()
+    for name, (restype, argtypes) in native.SIGNATURES.items():
+        fn = getattr(hip, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes) and fn.restype is restype, name
+
+
 def test_shipped_libraries_read_only_the_production_environment_variables():
     """The library carries no development switch: libcloudini_hip.so names no CLDN_HIP_*
     variable at all and its sources read no environment variable (csrc/host/, the host mirror, reads its three

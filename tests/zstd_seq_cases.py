@@ -27,8 +27,7 @@ LIBZSTD_HOST = {"constant/small_blocks/40000": "record limit"}
 def ring():
     """the bytes of k_zstd_seq_exec's LDS ring, from the library itself (a host function: no GPU)"""
     from cloudini_amd import native
-    native.lib().cldn_hip_debug_zstd_seq_ring.restype = __import__("ctypes").c_uint32
-    return int(native.lib().cldn_hip_debug_zstd_seq_ring())
+    return int(native.zstd_seq_ring())
 
 
 def _code(value, base, bits):

@@ -69,7 +69,7 @@ def run():
         if c.get("lz4"):
             codec.set_stage2(1)
         if c.get("force_parts"):
-            assert native.lib().cldn_hip_debug_decode_split(codec._h, c["force_parts"]) == 0
+            assert codec.decode_split(c["force_parts"]) == 0
         cp = np.array([n], dtype=np.uint64)
         cap = plan.stage2_bound(n, 1 if c.get("lz4") else 0)
         d_points = torch.from_numpy(host).to(dev)
