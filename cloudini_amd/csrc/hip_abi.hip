@@ -39,6 +39,10 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// ST_PALETTE_FULL (pal32_slow_first, section_palette): no stream was produced
+constexpr const char* kPaletteFullMessage =
+    "Palette section: too many distinct values share one hash partition at the largest partition count; encode this cloud under another mode";
+
 #define HIP_TRY(expr)                                                                               \
   do {                                                                                              \
     hipError_t _e = (expr);                                                                         \
@@ -845,6 +849,7 @@ int cldn_hip_codec_status(cldn_hip_codec_t* c) {
     c->force_ticket = true;  // (device-resident outputs cannot be redone here: the caller repeats the call, which then takes tickets)
     return fail(CLDN_HIP_ERR_DEVICE, "k_finish: a workgroup waited too long for the sizes of the chunks before it (status 0x%x); the codec uses the ticket order from now on, repeat the call", st);
   }
+  if (st & ST_PALETTE_FULL) return fail(CLDN_HIP_ERR_UNSUPPORTED, kPaletteFullMessage);
   if (st & ST_OUT_OVERFLOW) return fail(CLDN_HIP_ERR_CAPACITY, "Output buffer too small for the encoded stream");
   if (st & ST_LZ4_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "LZ4 decompression failed");
   if (st & ST_ZSTD_REJECT) return fail(CLDN_HIP_ERR_CORRUPT, "ZSTD decompression failed");
@@ -1410,6 +1415,7 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
     }
     return fail(CLDN_HIP_ERR_DEVICE, "k_finish: a workgroup waited too long for the sizes of the chunks before it (status 0x%x)", *h_status);
   }
+  if (*h_status & ST_PALETTE_FULL) return fail(CLDN_HIP_ERR_UNSUPPORTED, kPaletteFullMessage);
   if (*h_status & ST_OUT_OVERFLOW)
     return fail(CLDN_HIP_ERR_CAPACITY, "Output buffer too small for uncompressed chunk");  // chunk_writer.cpp:34-36
   const uint64_t total = h_off[n_clouds];
@@ -1528,6 +1534,7 @@ int cldn_hip_frame_chunks(cldn_hip_codec_t* c, void* out, uint64_t out_capacity,
   HIP_TRY(hipMemcpyAsync(h_status, c->d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (*h_status & ST_FINISH_TIMEOUT) return fail(CLDN_HIP_ERR_DEVICE, "k_finish: a workgroup waited too long (status 0x%x)", *h_status);
+  if (*h_status & ST_PALETTE_FULL) return fail(CLDN_HIP_ERR_UNSUPPORTED, kPaletteFullMessage);
   if (*h_status & ST_OUT_OVERFLOW) return fail(CLDN_HIP_ERR_CAPACITY, "Output buffer too small for uncompressed chunk");
   const uint64_t total = h_off[n_clouds];
   if (total) HIP_TRY(hipMemcpyAsync(out, d_outp, (size_t)total, hipMemcpyDeviceToHost, c->stream));

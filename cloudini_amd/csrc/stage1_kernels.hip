@@ -1167,9 +1167,21 @@ __device__ uint32_t palette_pass(const uint8_t* col, uint32_t bpv, uint32_t n, u
 
 // Full palette section of one chunk. Writes segment A ([0x01][u16 U][U values]) at dst and segment B (bit-packed
 // indexes) at dst + kPaletteIndexOffset; returns their sizes.
+// More than kPalCapacity distinct values: the values are split by (hash_u64 >> 20) % parts, one table pass per partition.
+// The hash is no guarantee, so parts doubles from 8 until every pass fits, as pal32_slow_first does (the reference's
+// table has no limit, buildPaletteIndexes :369-379). The 12 bits of the partition index are used up at kPalMaxParts:
+// keys that still share a partition there fail the call with ST_PALETTE_FULL, and both sizes are 0. first_idx is read
+// only after every pass has returned a count, i.e. after every entry has been written.
+// Cost: a round at P partitions is up to P table passes over the chunk (fewer when a pass overflows: the round ends there),
+// all in this one workgroup, so a column that only 4096 partitions separate takes 8 + 16 + ... + 4096, about 8000 passes.
+// Not measured; by the pass's work (32 tiles of one probe per value) tens to hundreds of milliseconds: slow, finite, no hang.
+// Only keys built against the hash get there: 32768 hashed keys put about 4096 into each of 8 partitions. The growth is by
+// 2 where pal32_slow_first's is by 4: a pass here costs a sweep of the chunk, and doubling overshoots the count less.
+constexpr uint32_t kPalMaxParts = 4096;
+
 template <int T>
 __device__ void section_palette(const uint8_t* col, uint32_t bpv, uint32_t n, uint8_t* dst, uint16_t* first_idx,
-                                uint8_t* lds, uint32_t* wtot, uint32_t* size_a, uint32_t* size_b) {
+                                uint8_t* lds, uint32_t* wtot, uint32_t* size_a, uint32_t* size_b, uint32_t* status) {
   // LDS carve (bytes): keys 64 KiB | first 16 KiB | tile_vals 8 KiB | miss_mask 128 | flags 16
   PalTable tab;
   tab.keys = reinterpret_cast<uint64_t*>(lds);
@@ -1179,10 +1191,17 @@ __device__ void section_palette(const uint8_t* col, uint32_t bpv, uint32_t n, ui
   uint32_t* flags = reinterpret_cast<uint32_t*>(lds + kPalSlots * 10u + T * 8u + 128u);
 
   uint32_t u = palette_pass<T>(col, bpv, n, 0u, 1u, tab, tile_vals, miss_mask, flags, first_idx);
-  if (u == 0xffffffffu) {
-    for (uint32_t p = 0; p < 8u; ++p) {
+  for (uint32_t parts = 8u; u == 0xffffffffu; parts *= 2u) {  // (every test is uniform: palette_pass returns one value to all)
+    if (parts > kPalMaxParts) {
+      if (threadIdx.x == 0) atomicOr(status, (uint32_t)ST_PALETTE_FULL);
+      *size_a = 0u;
+      *size_b = 0u;
+      return;
+    }
+    u = 0u;
+    for (uint32_t p = 0; p < parts && u != 0xffffffffu; ++p) {
       __syncthreads();
-      (void)palette_pass<T>(col, bpv, n, p, 8u, tab, tile_vals, miss_mask, flags, first_idx);
+      u = palette_pass<T>(col, bpv, n, p, parts, tab, tile_vals, miss_mask, flags, first_idx);
     }
   }
   __threadfence_block();
@@ -1273,7 +1292,8 @@ __global__ __launch_bounds__(kSecThreads) void k_encode_sections(const DevPlan p
                                                                  uint64_t reg_stride, Seg* __restrict__ segs,
                                                                  uint32_t segs_per_chunk, const ColumnPtrs rank_cols,
                                                                  uint32_t subs, const uint8_t* __restrict__ handled_flags,
-                                                                 uint32_t fused_field, uint32_t n_chunks) {
+                                                                 uint32_t fused_field, uint32_t n_chunks,
+                                                                 uint32_t* __restrict__ status) {
   constexpr int T = kSecThreads;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const SecLds l = sec_lds_carve(smem);
@@ -1304,7 +1324,7 @@ __global__ __launch_bounds__(kSecThreads) void k_encode_sections(const DevPlan p
     size_a = section_runs<T, true, true>(col, bpv, type, n, l.ring, l.wtot, dst, l.list_pos, l.list_key);
   } else {
     uint16_t* first_idx = reinterpret_cast<uint16_t*>(rank_cols.p[a]) + cd.first_point;
-    section_palette<T>(col, bpv, n, dst, first_idx, l.main, l.wtot, &size_a, &size_b);
+    section_palette<T>(col, bpv, n, dst, first_idx, l.main, l.wtot, &size_a, &size_b, status);
   }
   if (threadIdx.x == 0) {
     Seg s;
@@ -1553,6 +1573,7 @@ int launch_wide(const EncodeLaunch& L) {
   A.segs = L.segs;
   A.scratch = L.wide_scratch;
   A.pre = L.wide_pre;
+  A.status = L.status;
   if (R.probe == EB_WIDE)
     TRY_LAUNCH("k_wide_probe", k_wide_probe, dim3(L.n_clouds * A.plan.n_adaptive), dim3(kS2Threads), kProbeLds, L.stream, A, L.n_clouds);
   return launch("k_wide_encode", k_wide_encode, dim3(L.n_chunks), dim3(kWideThreads), kSecLdsTotal, L.stream, A);
@@ -1579,7 +1600,8 @@ int launch_sections(const EncodeLaunch& L) {
     TRY_LAUNCH("k_section_palette", k_section_palette<uint64_t>, dim3(nch, R.pal64.n), dim3(kS2Threads), kS2PalLds, L.stream, SEC_ARGS(R.pal64));
 #undef SEC_ARGS
   return launch("k_encode_sections", k_encode_sections, dim3(R.sec_grid), dim3(kSecThreads), kSecLdsTotal, L.stream, *L.plan, L.chunks, L.cols,
-                L.modes, L.slots, R.slot_stride, R.reg_stride, L.segs, R.segs_per_chunk, rank_cols, R.subs, L.fallback_flags, R.fused_field, nch);
+                L.modes, L.slots, R.slot_stride, R.reg_stride, L.segs, R.segs_per_chunk, rank_cols, R.subs, L.fallback_flags, R.fused_field, nch,
+                L.status);
 }
 }  // namespace
 

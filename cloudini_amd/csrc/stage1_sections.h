@@ -822,8 +822,10 @@ __device__ __forceinline__ void pal32_pack_chunk(const Pal32<RawT>& p, const Raw
 // of EVERY value goes to a scratch column in global memory (`first`, n entries). Ranks then come from the bitmap of
 // first occurrences alone: rank(i) = first occurrences below first[i]. Slow (P + 2 sweeps over the chunk), exact.
 // 16-bit keys are partitioned by key range (32 ranges of 2048 keys can never overflow a table); 32-bit keys by a hash,
-// P grows until every partition fits (kPalSlowMaxParts: beyond it the call fails loudly with ST_PALETTE_FULL).
-constexpr uint32_t kPalSlowMaxParts = 4096;
+// P grows by 4 from 32 until every partition fits: 32, 128, 512, 2048, 8192. kPalSlowMaxParts is the last count tried:
+// when it overflows too the call fails with ST_PALETTE_FULL. (The constant said 4096, which the sequence never takes, so
+// the loop has always stopped behind 8192; the constant now says what the loop does.)
+constexpr uint32_t kPalSlowMaxParts = 8192;
 
 template <typename RawT>
 __device__ __forceinline__ uint32_t pal32_part(uint32_t v, uint32_t parts) {

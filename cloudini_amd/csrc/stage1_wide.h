@@ -46,6 +46,7 @@ struct WideEncodeArgs {
   Seg* segs;                       // [n_chunks]: one segment per chunk
   uint8_t* scratch;                // [n_chunks * kWideScratchBytes]
   const uint4* const* pre;         // device [n_gorilla]: k_gorilla_tokens' token buffers
+  uint32_t* status;                // the status block: ST_PALETTE_FULL (section_palette)
 };
 
 // the `size` bytes at p, any alignment, nothing else touched
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide_encode(const WideEncodeAr
     } else if (mode == 3u) {
       size_a = section_runs<T, true, true>(col, bpv, f.type, n, l.ring, l.wtot, sec, l.list_pos, l.list_key);
     } else {
-      section_palette<T>(col, bpv, n, sec, first_idx, l.main, l.wtot, &size_a, &size_b);
+      section_palette<T>(col, bpv, n, sec, first_idx, l.main, l.wtot, &size_a, &size_b, A.status);
     }
     __syncthreads();  // the section's bytes are in `sec` (and its indexes at kPaletteIndexOffset)
     for (uint32_t i = tid; i < size_a; i += T) slot[R + i] = sec[i];

@@ -16,7 +16,7 @@ constexpr uint32_t kStatusWord = 0;
 enum : uint32_t {
   ST_OUT_OVERFLOW = 1u,    // compacted stream did not fit the output capacity
   ST_CORRUPT = 2u,         // decode: malformed input
-  ST_PALETTE_FULL = 4u,    // internal: LDS palette table overflowed (handled by the global-table path)
+  ST_PALETTE_FULL = 4u,    // encode: a Palette section's values could not be partitioned into table passes; the call fails
   ST_FINISH_TIMEOUT = 8u,  // internal: a workgroup of k_finish waited too long for a predecessor's chunk size
   ST_LZ4_REJECT = 16u,     // set next to ST_CORRUPT: what was malformed is an LZ4 block (lz4_decode.hip)
   ST_ZSTD_REJECT = 32u,    // set next to ST_CORRUPT: what was malformed is a ZSTD frame (zstd_decode.hip)
