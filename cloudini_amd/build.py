@@ -65,7 +65,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(ROOT, "build", "hip")
     os.makedirs(objdir, exist_ok=True)
-    names = ["stage1_kernels", "stage1_decode", "viz_kernels", "audit_kernels", "sweep_kernels", "hist_kernels", "mode_kernels", "lz4_kernels", "lz4_decode", "zstd_kernels", "zstd_seq_kernels", "zstd_decode", "zstd_seq_decode", "hip_abi"]
+    names = ["stage1_kernels", "stage1_decode", "viz_kernels", "audit_kernels", "sweep_kernels", "hist_kernels", "crc_kernels", "mode_kernels", "lz4_kernels", "lz4_decode", "zstd_kernels", "zstd_seq_kernels", "zstd_decode", "zstd_seq_decode", "hip_abi"]
     deps = _sources(CSRC, (".h",)) + _sources(os.path.join(ROOT, "include"), (".h",))
     deps = [d for d in deps if os.sep + "host" + os.sep not in d]
     jobs = []
@@ -94,7 +94,8 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     if not srcs:
         return ""
     deps = srcs + _sources(host_dir, (".hpp", ".h")) + _sources(os.path.join(ROOT, "include"), (".h", ".hpp")) + \
-        [HIP_SO, os.path.join(CSRC, "zstd_decode_walk.h"), os.path.join(CSRC, "stage2_decode_plan.h")]
+        [HIP_SO, os.path.join(CSRC, "zstd_decode_walk.h"), os.path.join(CSRC, "stage2_decode_plan.h"),
+         os.path.join(CSRC, "crc32_combine.h")]
     if force or _newer(HOST_SO, deps):
         # default visibility: the C++ API of include/cloudini_lib/*.hpp is what callers link against
         cmd = ["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall",

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "cloudini_hip.h"
+#include "crc32_combine.h"
 #include "decode_workspace.h"
 #include "encode_workspace.h"
 #include "stage1_device.h"
@@ -307,7 +308,7 @@ struct cldn_hip_codec {
     std::vector<uint64_t> offsets;        // host copy (calls with host outputs have read them anyway)
     std::vector<uint64_t> cloud_points;
     int kind = CLDN_HIP_STAGE2_NONE;
-    const uint8_t* s1_streams = nullptr;      // kind == CLDN_HIP_STAGE2_ZSTD: the framed stage-1 streams behind the frames
+    const uint8_t* s1_streams = nullptr;      // kind != CLDN_HIP_STAGE2_NONE: the framed stage-1 streams behind the blocks / frames
     const uint64_t* d_s1_offsets = nullptr;   // ... and their offsets, device [n_clouds + 1]
     void drop() { valid = await_frame = false; }
   } enc;
@@ -1377,8 +1378,8 @@ static int encode_stage1_once(cldn_hip_codec_t* c, const void* points, int point
   c->enc.d_offsets = direct_offsets ? stream_offsets : (const uint64_t*)c->d_offsets.p;
   c->enc.offsets.clear();
   // (no device decoder reads the ZSTD frames: the audit of such a call decodes the stage-1 streams they were made from)
-  c->enc.s1_streams = zstd ? (const uint8_t*)c->d_s1.p : nullptr;
-  c->enc.d_s1_offsets = zstd ? (const uint64_t*)c->d_s1_offsets.p : nullptr;
+  c->enc.s1_streams = device_stage2 ? (const uint8_t*)c->d_s1.p : nullptr;  // (LZ4 too: cldn_hip_stream_crc32_last_encode)
+  c->enc.d_s1_offsets = device_stage2 ? (const uint64_t*)c->d_s1_offsets.p : nullptr;
   if (out_loc == CLDN_HIP_DEVICE) {
     c->enc.valid = true;
     if (stream_offsets && !direct_offsets)
@@ -2924,6 +2925,127 @@ double cldn_hip_hist_entropy_bytes(const cldn_hip_hist_t* h) {
     if (v) bits += (double)v * std::log2((double)n / (double)v);
   const double bytes = bits / 8.0;
   return bytes < (double)n ? bytes : (double)n;
+}
+
+}  // extern "C"
+
+// ---- CRC-32 of each span of a byte buffer (crc_kernels.hip) ----
+
+static int crc_check(const char* who, uint32_t n_spans, const void* crc, int crc_loc) {
+  if (crc_loc != CLDN_HIP_HOST && crc_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  if (n_spans && !crc) return fail(CLDN_HIP_ERR_ARG, "%s: crc is NULL", who);
+  if (crc_loc == CLDN_HIP_DEVICE && ((uintptr_t)crc & 3u)) return fail(CLDN_HIP_ERR_ARG, "%s: a device crc array must be 4-byte aligned", who);
+  return CLDN_HIP_OK;
+}
+
+// device spans -> crc: the item table up, one clear, one kernel; HOST crc: one copy, one synchronisation.
+// offsets: HOST [n_spans + 1], ascending, in bytes of d_streams. The items are cut where the kernel's lanes are: at the
+// ADDRESSES that are multiples of kCrcSegmentBytes from the span's first 128-byte line. An item's multiplier is that of the
+// item behind it times x^(8 * that item's length): one generic power per span (its last item), a constant for the others.
+static int stream_crc32_device(cldn_hip_codec* c, const uint8_t* d_streams, const uint64_t* offsets, uint32_t n_spans, uint32_t* crc,
+                               int crc_loc) {
+  const size_t crc_bytes = (size_t)n_spans * sizeof(uint32_t);
+  if (crc_bytes == 0) return CLDN_HIP_OK;
+  static const CrcConstMul seg_pow(crc32_xpow8(kCrcSegmentBytes));  // (built once: 1024 multiplications)
+  std::vector<CrcItem> items;
+  for (uint32_t k = 0; k < n_spans; ++k) {
+    if (offsets[k + 1] == offsets[k]) continue;
+    const uintptr_t a = (uintptr_t)d_streams + offsets[k], e = (uintptr_t)d_streams + offsets[k + 1];
+    const uintptr_t frame = a & ~(uintptr_t)(kCrcLaneBytes - 1u);
+    const size_t first = items.size();
+    for (uintptr_t at = frame; at < e; at += kCrcSegmentBytes) {
+      const uintptr_t b = std::max(at, a), t = std::min<uintptr_t>(at + kCrcSegmentBytes, e);
+      items.push_back(CrcItem{offsets[k] + (b - a), offsets[k] + (t - a), k, kCrcOne, at == frame ? 1u : 0u, 0u});
+    }
+    for (size_t j = items.size() - 1; j > first; --j)
+      items[j - 1].mult = j + 1 == items.size() ? crc32_xpow8(items[j].end - items[j].begin) : seg_pow(items[j].mult);
+  }
+  // (one workgroup per item: HIP refuses a launch of 2^32 threads or more)
+  if (items.size() > 0xffffffffull / kCrcThreads) return fail(CLDN_HIP_ERR_UNSUPPORTED, "stream_crc32: more than 2^24 pieces of 32 KiB");
+  int rc;
+  CrcLaunch L;
+  const ReportBatch B = {nullptr, n_spans, 0u};
+  TableSection sec[1] = {TableSection{items.size() * sizeof(CrcItem), items.data(), nullptr, nullptr}};
+  if (!items.empty() && (rc = upload_tables(c, B, sec, 1)) != CLDN_HIP_OK) return rc;
+  unsigned long long* d_crc;
+  if ((rc = report_place(c, crc, crc_loc, crc_bytes, &d_crc)) != CLDN_HIP_OK) return rc;
+  L.stream = c->stream;
+  L.streams = d_streams;
+  L.n_spans = n_spans;
+  L.n_items = (uint32_t)items.size();
+  L.items = (const CrcItem*)sec[0].dev;
+  L.crc = (uint32_t*)d_crc;
+  if ((rc = stream_crc32_launch(L)) != CLDN_HIP_OK) return rc;
+  return report_fetch(c, crc, crc_loc, L.crc, crc_bytes);
+}
+
+extern "C" {
+
+int cldn_hip_stream_crc32(cldn_hip_codec_t* c, const void* streams, int streams_loc, const uint64_t* stream_offsets, uint32_t n_streams,
+                          uint32_t* crc, int crc_loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  c->enc.drop();
+  if (streams_loc != CLDN_HIP_HOST && streams_loc != CLDN_HIP_DEVICE) return fail(CLDN_HIP_ERR_ARG, "invalid memory location tag");
+  int rc;
+  if ((rc = crc_check("stream_crc32", n_streams, crc, crc_loc)) != CLDN_HIP_OK) return rc;
+  if (n_streams == 0) return CLDN_HIP_OK;
+  if (!stream_offsets) return fail(CLDN_HIP_ERR_ARG, "stream_crc32: stream_offsets is NULL");
+  for (uint32_t k = 0; k < n_streams; ++k)
+    if (stream_offsets[k + 1] < stream_offsets[k]) return fail(CLDN_HIP_ERR_ARG, "stream_offsets must be ascending");
+  const uint64_t s0 = stream_offsets[0], s_bytes = stream_offsets[n_streams] - s0;
+  if (s_bytes && !streams) return fail(CLDN_HIP_ERR_ARG, "stream_crc32: streams is NULL");
+  ENTER_DEVICE(c->device);
+  std::vector<uint64_t> rel(stream_offsets, stream_offsets + n_streams + 1);
+  for (uint64_t& o : rel) o -= s0;
+  const uint8_t* d_streams;
+  if ((rc = stage_host_points(c, (const uint8_t*)streams + s0, streams_loc, s_bytes, 0u, (size_t)s_bytes, &d_streams)) != CLDN_HIP_OK)
+    return rc;
+  rc = stream_crc32_device(c, d_streams, rel.data(), n_streams, crc, crc_loc);
+  if (rc == CLDN_HIP_OK && streams_loc == CLDN_HIP_HOST && s_bytes && crc_loc == CLDN_HIP_DEVICE) HIP_TRY(hipStreamSynchronize(c->stream));
+  return rc;
+}
+
+int cldn_hip_stream_crc32_last_encode(cldn_hip_codec_t* c, uint32_t* crc, uint64_t* sizes, int loc) {
+  if (!c) return fail(CLDN_HIP_ERR_ARG, "codec is NULL");
+  if (!c->enc.valid) return no_last_encode("stream_crc32_last_encode");  // (a chunk table has no streams before its framing)
+  cldn_hip_codec::LastEncode& E = c->enc;  // the state stays; only the offsets of a DEVICE-output call are added to it
+  const uint32_t n_clouds = (uint32_t)E.cloud_points.size();
+  int rc;
+  if ((rc = crc_check("stream_crc32_last_encode", n_clouds, crc, loc)) != CLDN_HIP_OK) return rc;
+  if (loc == CLDN_HIP_DEVICE && ((uintptr_t)sizes & 7u)) return fail(CLDN_HIP_ERR_ARG, "stream_crc32_last_encode: a device sizes array must be 8-byte aligned");
+  if (n_clouds == 0) return CLDN_HIP_OK;
+  ENTER_DEVICE(c->device);
+  uint64_t n_points = 0;
+  for (uint64_t n : E.cloud_points) n_points += n;
+  // behind stage 2 on the device (LZ4 blocks, ZSTD frames): the stage-1 streams they were made from, still in the workspace
+  const bool behind = E.kind != CLDN_HIP_STAGE2_NONE;
+  const uint8_t* d_streams = behind ? E.s1_streams : E.streams;
+  std::vector<uint64_t> read((size_t)n_clouds + 1, 0);
+  const std::vector<uint64_t>* offs = &read;
+  if (n_points == 0) {  // nothing was launched and nothing written: empty streams
+    d_streams = nullptr;
+  } else if (behind || E.offsets.empty()) {  // (DEVICE outputs: the encode call has not read its offsets)
+    HIP_TRY(hipMemcpyAsync(read.data(), behind ? E.d_s1_offsets : E.d_offsets, read.size() * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < n_clouds; ++k)
+      if (read[k + 1] < read[k]) return fail(CLDN_HIP_ERR_DEVICE, "stream_crc32_last_encode: the encode call left no valid stream offsets (see cldn_hip_codec_status)");
+    if (!behind) E.offsets = read;  // kept: the state describes the same call
+  } else {
+    offs = &E.offsets;
+  }
+  const std::vector<uint64_t> o = *offs;  // (a copy: the call below may not touch the state, but the reference would alias it)
+  if (sizes) {
+    std::vector<uint64_t> s(n_clouds);
+    for (uint32_t k = 0; k < n_clouds; ++k) s[k] = o[k + 1] - o[k];
+    if (loc == CLDN_HIP_HOST) {
+      memcpy(sizes, s.data(), s.size() * sizeof(uint64_t));
+    } else {
+      HIP_TRY(hipMemcpyAsync(sizes, s.data(), s.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));  // (a pageable source)
+    }
+  }
+  return stream_crc32_device(c, d_streams, o.data(), n_clouds, crc, loc);
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 
 #include "../stage2_decode_plan.h"
 #include "host_internal.hpp"
+#include "zstd_stitch.hpp"
 
 namespace cloudini_amd {
 
@@ -231,6 +232,10 @@ DirectorySink::DirectorySink(const std::string& dir) : dir_(dir) {
   if (stat(dir.c_str(), &st) != 0 && mkdir(dir.c_str(), 0755) != 0) throw std::runtime_error("cannot create directory " + dir);
 }
 
+void MessageSink::writeStitched(const std::string& name, const StitchedMessage&) {
+  throw std::logic_error("message " + name + ": this sink does not take stitched messages (TranscodeOptions::mcap_device_zstd needs transcodeMcap)");
+}
+
 void DirectorySink::write(const std::string& name, const uint8_t* data, size_t size) {
   std::ofstream f(dir_ + "/" + name, std::ios::binary | std::ios::trunc);
   if (!f || (size && !f.write(reinterpret_cast<const char*>(data), static_cast<std::streamsize>(size))))
@@ -249,6 +254,9 @@ struct Run {                       // messages [first, first + count) share a sc
   std::vector<uint32_t> chunk_sizes;
   bool estimated = false;          // TranscodeOptions::estimate took this run's histograms: stage 2 reports its actual size
   bool packed = false;             // TranscodeOptions::device_zstd: `stage1` holds finished [u32 size][ZSTD frame] chunks
+  bool stitched = false;           // TranscodeOptions::mcap_device_zstd: the same frames, for messages that say NONE; with
+  std::vector<uint32_t> crc;       // ... the CRC-32 and the length of every cloud's framed stage-1 stream behind them
+  std::vector<uint64_t> s1_sizes;
   PinnedBytes decoded;             // decode direction: the points of the run's clouds, back to back
   std::vector<uint64_t> out_at;    // decode direction: where every message's points start in `decoded`
 };
@@ -259,6 +267,9 @@ struct Batch {
   std::vector<Parsed> parsed;
   std::vector<Run> runs;
   std::vector<std::vector<uint8_t>> out;
+  // TranscodeOptions::mcap_device_zstd: message i goes to MessageSink::writeStitched where stitched[i].chunks is not empty;
+  // out[i] then holds its head and its tail back to back
+  std::vector<StitchedMessage> stitched;
 };
 
 // the front of the reference's loop message by message (mcap_converter.cpp:187-203), then one GPU call per schema run
@@ -310,8 +321,12 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     Run& run = b.runs[n_runs++];
     run.estimated = false;
     run.packed = opt.device_zstd && opt.compression == Cloudini::CompressionOption::ZSTD;
-    const int stage2_mode = run.packed ? CLDN_HIP_STAGE2_ZSTD | (opt.device_zstd_matches ? Cloudini::amd_detail::kStage2ZstdMatches : 0)
-                                       : CLDN_HIP_STAGE2_NONE;
+    run.stitched = opt.mcap_device_zstd;
+    const int stage2_mode = run.packed || run.stitched
+                                ? CLDN_HIP_STAGE2_ZSTD | (opt.device_zstd_matches ? Cloudini::amd_detail::kStage2ZstdMatches : 0)
+                                : CLDN_HIP_STAGE2_NONE;
+    Cloudini::amd_detail::StreamCrcRequest crc;
+    Cloudini::amd_detail::StreamCrcRequest* const crc_p = run.stitched ? &crc : nullptr;
     run.first = r0;
     run.count = static_cast<uint32_t>(r1 - r0);
     const Cloudini::EncodingInfo& info0 = b.parsed[r0].info;
@@ -375,7 +390,7 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     if (b.parsed[r0].viz) {
       Cloudini::amd_detail::encodeStage1BatchViz(info0, ptrs.data(), pts.data(), run.count, b.parsed[r0].viz_xyz_offset,
                                                  b.parsed[r0].viz_resolution, grow, run.offsets, run.chunk_sizes, kept, audit_p,
-                                                 sweep_p, modes_p, stage2_mode);
+                                                 sweep_p, modes_p, stage2_mode, crc_p);
       for (uint32_t k = 0; k < run.count; ++k) {  // what the reference's function leaves behind (src/ros_msg_utils.cpp:326-335)
         Parsed& p = b.parsed[r0 + k];
         p.points = kept[k];
@@ -391,8 +406,10 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       }
     } else {
       Cloudini::amd_detail::encodeStage1Batch(info0, ptrs.data(), pts.data(), run.count, grow, run.offsets, run.chunk_sizes, audit_p,
-                                              sweep_p, modes_p, stage2_mode);
+                                              sweep_p, modes_p, stage2_mode, crc_p);
     }
+    run.crc.swap(crc.crc);
+    run.s1_sizes.swap(crc.sizes);
     if (modes_p && stats && modes.adaptive_fields) {  // the run's cells, summed over its messages, into the per-name summary
       std::vector<ModeFieldSummary> part(modes.adaptive_fields);  // names from the plan's own list of adaptive fields
       for (size_t a = 0; a < part.size(); ++a) part[a].name = info0.fields.at(modes.field_index[a]).name;
@@ -457,7 +474,7 @@ void gpuPhase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       }
       stats->mergeEstimate(part);
       for (uint32_t k = 0; k < run.count; ++k) stats->estimate_own_bytes += moved(k, nullptr, nullptr);
-      if (run.packed) {  // the offsets describe the frames; the stream histograms are of the stage-1 streams behind them
+      if (run.packed || run.stitched) {  // the offsets describe the frames; the stream histograms are of the stage-1 streams behind them
         for (uint32_t k = 0; k < run.count; ++k)
           for (int i = 0; i < 256; ++i) stats->estimate_stage1_bytes += sweep.stream_hist[k].bin[i];
       } else {
@@ -509,8 +526,10 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
     uint32_t packed = 0;
     bool estimated = false;  // the run's histograms were taken and the output is ZSTD: its size goes next to the estimate
     bool finished = false;   // the GPU stage wrote the chunk's ZSTD frame already: it is copied
+    bool expand = false;     // mcap_device_zstd, a message that takes the ordinary path after all: the frame is expanded
   };
   const size_t n = b.in.size();
+  b.stitched.assign(opt.mcap_device_zstd ? n : 0, StitchedMessage());
   std::vector<Job> jobs;
   std::vector<size_t> first_job(n + 1, 0), scratch_at(n, 0), payload_at(n, 0), length_at(n, 0);
   std::vector<uint8_t> header;
@@ -526,10 +545,61 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
       enc.encode(static_cast<uint32_t>(0));
       payload_at[i] = msg.size();
       first_job[i] = jobs.size();
-      if (p.pc.data.size() == 0) continue;  // empty cloud: no Cloudini header either (ros_msg_utils.cpp:178-183)
+      if (p.pc.data.size() == 0) {  // empty cloud: no Cloudini header either (ros_msg_utils.cpp:178-183)
+        if (stats && opt.mcap_device_zstd) stats->mcap_host_fallback_messages += 1;
+        continue;
+      }
       Cloudini::EncodeHeader(p.info, header);
       const uint64_t n_chunks = (p.points + 32767) / 32768;
       const uint8_t* s = run.stage1.data() + run.offsets[k];
+      if (run.stitched) {
+        // the frames stay where they are: head = CDR fields + Cloudini header, tail = what follows the data. The tail's CDR
+        // alignment is that of the whole message, so it is encoded behind a stand-in of the same length modulo 8.
+        StitchedMessage& sm = b.stitched[i];
+        uint64_t stream = 0;
+        try {
+          for (uint64_t c = 0; c < n_chunks; ++c) {
+            const uint32_t frame_size = run.chunk_sizes[chunk_index + c];
+            if (opt.test_refuse_stitch && opt.test_refuse_stitch(b.in[i].name, c)) throw cldn_stitch::StitchError("refused by the test hook");
+            const cldn_stitch::BlockRun cut = cldn_stitch::cut_device_frame(s + 4, frame_size);
+            StitchedMessage::Chunk ch;
+            ch.payload_size = (uint32_t)cut.content;
+            ch.blocks = cut.p;
+            ch.blocks_size = cut.bytes;
+            ch.last_header = cut.last_header;
+            sm.chunks.push_back(ch);
+            stream += 4u + ch.payload_size;
+            s += 4 + frame_size;
+          }
+        } catch (const cldn_stitch::StitchError&) {
+          sm.chunks.clear();  // not the device writer's form: this message takes the ordinary path, its frames expanded here
+        }
+        if (!sm.chunks.empty()) {
+          if (stream != run.s1_sizes[k]) throw std::runtime_error("mcap_device_zstd: the frames' content sizes and the stream length disagree");
+          const uint32_t encoded32 = static_cast<uint32_t>(header.size() + stream);
+          std::memcpy(msg.data() + length_at[i], &encoded32, 4);
+          msg.insert(msg.end(), header.begin(), header.end());
+          const size_t head_size = msg.size(), true_end = head_size + stream;
+          std::vector<uint8_t> stand_in(8 + true_end % 8, 0);
+          const size_t tail_at = stand_in.size();
+          nanocdr::Encoder tail(p.pc.cdr_header, stand_in, /*append=*/true);
+          tail.encode(p.pc.is_dense);
+          tail.encode(std::string("cloudini"));
+          msg.insert(msg.end(), stand_in.begin() + tail_at, stand_in.end());
+          sm.head_size = head_size;
+          sm.tail_size = msg.size() - head_size;
+          sm.stream_crc = run.crc[k];
+          sm.stream_size = stream;
+          if (stats) {
+            stats->mcap_device_messages += 1;
+            stats->output_bytes += true_end + sm.tail_size;
+          }
+          chunk_index += n_chunks;
+          continue;
+        }
+        if (stats) stats->mcap_host_fallback_messages += 1;
+        s = run.stage1.data() + run.offsets[k];
+      }
       size_t slot = 0;
       for (uint64_t c = 0; c < n_chunks; ++c) {
         const uint32_t size = run.chunk_sizes[chunk_index + c];
@@ -540,8 +610,9 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
         j.slot = slot;
         j.estimated = run.estimated && opt.compression == Cloudini::CompressionOption::ZSTD;
         j.finished = run.packed;
+        j.expand = run.stitched;
         jobs.push_back(j);
-        slot += 4 + Cloudini::amd_detail::compressedChunkBound(opt.compression, size);
+        slot += 4 + (j.expand ? Cloudini::amd_detail::stage1ChunkBound(p.info) : Cloudini::amd_detail::compressedChunkBound(opt.compression, size));
         s += 4 + size;
       }
       chunk_index += n_chunks;
@@ -554,7 +625,10 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
   Cloudini::amd_detail::runOnStage2Pool(jobs.size(), [&](size_t ji) {
     Job& j = jobs[ji];
     uint8_t* dst = b.out[j.msg].data() + scratch_at[j.msg] + j.slot;
-    if (direct || j.finished) {
+    if (j.expand) {
+      j.packed = Cloudini::amd_detail::decompressChunkTo(Cloudini::CompressionOption::ZSTD, j.src, j.src_size, dst + 4,
+                                                         Cloudini::amd_detail::stage1ChunkBound(b.parsed[j.msg].info));
+    } else if (direct || j.finished) {
       std::memcpy(dst + 4, j.src, j.src_size);
       j.packed = j.src_size;
     } else {
@@ -565,6 +639,7 @@ void stage2Phase(Batch& b, const TranscodeOptions& opt, TranscodeStats* stats) {
   });
   // close the gaps between a message's chunks, patch the length, finish the CDR message
   for (size_t i = 0; i < n; ++i) {
+    if (!b.stitched.empty() && !b.stitched[i].chunks.empty()) continue;  // (finished above: head and tail)
     const Parsed& p = b.parsed[i];
     std::vector<uint8_t>& msg = b.out[i];
     size_t end = payload_at[i];
@@ -931,7 +1006,12 @@ void checkOptions(const TranscodeOptions& opt) {
   if (opt.decode && opt.device_zstd) throw std::invalid_argument("TranscodeOptions: device_zstd is not available together with decode");
   if (opt.decode && opt.device_zstd_matches)
     throw std::invalid_argument("TranscodeOptions: device_zstd_matches is not available together with decode");
-  if (opt.device_zstd_matches && !opt.device_zstd) throw std::invalid_argument("TranscodeOptions: device_zstd_matches needs device_zstd");
+  if (opt.device_zstd_matches && !opt.device_zstd && !opt.mcap_device_zstd)
+    throw std::invalid_argument("TranscodeOptions: device_zstd_matches needs device_zstd");
+  if (opt.mcap_device_zstd && opt.decode) throw std::invalid_argument("TranscodeOptions: mcap_device_zstd is not available together with decode");
+  if (opt.mcap_device_zstd && opt.device_zstd) throw std::invalid_argument("TranscodeOptions: mcap_device_zstd is not available together with device_zstd");
+  if (opt.mcap_device_zstd && opt.compression != Cloudini::CompressionOption::NONE)
+    throw std::invalid_argument("TranscodeOptions: mcap_device_zstd needs compression NONE (the container's ZSTD chunks are the second stage)");
   if (opt.device_stage2_decode && !opt.decode) throw std::invalid_argument("TranscodeOptions: device_stage2_decode needs decode");
   for (const auto& named : opt.sweep)
     if (named.second.size() > CLDN_HIP_SWEEP_MAX_CANDIDATES)
@@ -969,6 +1049,7 @@ std::map<std::string, std::vector<float>> parseSweepString(const std::string& te
 void transcodeBatch(const std::vector<Message>& in, const TranscodeOptions& opt, std::vector<std::vector<uint8_t>>& out,
                     TranscodeStats* stats) {
   checkOptions(opt);
+  if (opt.mcap_device_zstd) throw std::invalid_argument("TranscodeOptions: mcap_device_zstd needs a sink that takes stitched messages (transcodeMcap)");
   Batch b;
   b.in.resize(in.size());
   for (size_t i = 0; i < in.size(); ++i) {
@@ -1180,8 +1261,16 @@ TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, co
       if (!failed.load()) {
         try {
           const auto t_write = Clock::now();
-          parallelFor(x->in.size(), sink.concurrent() ? io_threads : 1u,
-                      [&](size_t i) { sink.write(x->in[i].name, x->out[i].data(), x->out[i].size()); });
+          parallelFor(x->in.size(), sink.concurrent() ? io_threads : 1u, [&](size_t i) {
+            if (i < x->stitched.size() && !x->stitched[i].chunks.empty()) {
+              StitchedMessage& sm = x->stitched[i];  // (out[i] has stopped moving)
+              sm.head = x->out[i].data();
+              sm.tail = sm.head + sm.head_size;
+              sink.writeStitched(x->in[i].name, sm);
+            } else {
+              sink.write(x->in[i].name, x->out[i].data(), x->out[i].size());
+            }
+          });
           seconds_write += since(t_write);
         } catch (...) {
           writer_error = std::current_exception();
@@ -1227,6 +1316,8 @@ TranscodeStats transcodePointClouds(MessageSource& source, MessageSink& sink, co
   if (writer_error) std::rethrow_exception(writer_error);
   stats.output_bytes = stats2.output_bytes;
   stats.estimate_actual_bytes = stats2.estimate_actual_bytes;
+  stats.mcap_device_messages = stats2.mcap_device_messages;
+  stats.mcap_host_fallback_messages = stats2.mcap_host_fallback_messages;
   stats.seconds_stage2 = stats2.seconds_stage2;
   stats.seconds_total = since(t0);
   stats.gpu_workers = n_workers;

@@ -1145,6 +1145,14 @@ static int sweepLastEncode(cldn_hip_codec_t* codec, const EncodingInfo& info, ui
   return cldn_hip_stream_hist_last_encode(codec, sweep->stream_hist.data(), CLDN_HIP_HOST);
 }
 
+// CRC-32 and length of every stream of that encode call (under a device stage 2: of the stage-1 streams behind it)
+static int crcLastEncode(cldn_hip_codec_t* codec, uint32_t n_clouds, StreamCrcRequest* crc) {
+  crc->crc.assign(n_clouds, 0u);
+  crc->sizes.assign(n_clouds, 0u);
+  if (n_clouds == 0) return CLDN_HIP_OK;
+  return cldn_hip_stream_crc32_last_encode(codec, crc->crc.data(), crc->sizes.data(), CLDN_HIP_HOST);
+}
+
 // The adaptive integer modes of that encode call's points; with apply_best and a cloud whose best mode is not the probed one,
 // `encode` (the call and the fetch of its output) runs once more with the best modes forced per cloud.
 static int modesLastEncode(cldn_hip_codec_t* codec, const cldn_hip_plan_t* plan, uint32_t n_clouds, ModesRequest* modes,
@@ -1175,7 +1183,7 @@ static int modesLastEncode(cldn_hip_codec_t* codec, const cldn_hip_plan_t* plan,
 void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
                        std::vector<uint32_t>& chunk_sizes, AuditRequest* audit, SweepRequest* sweep, ModesRequest* modes,
-                       int stage2) {
+                       int stage2, StreamCrcRequest* crc) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1196,6 +1204,7 @@ void encodeStage1Batch(const EncodingInfo& info, const uint8_t* const* cloud_ptr
   if (rc == CLDN_HIP_OK) rc = cldn_hip_codec_set_zstd_matches(codec, (stage2 & kStage2ZstdMatches) ? 1 : 0);
   if (rc == CLDN_HIP_OK) rc = encode();
   if (rc == CLDN_HIP_OK && modes) rc = modesLastEncode(codec, plan.plan, n_clouds, modes, encode);
+  if (rc == CLDN_HIP_OK && crc) rc = crcLastEncode(codec, n_clouds, crc);
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";
@@ -1210,7 +1219,7 @@ void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
                           std::vector<uint64_t>& kept_points, AuditRequest* audit, SweepRequest* sweep, ModesRequest* modes,
-                          int stage2) {
+                          int stage2, StreamCrcRequest* crc) {
   PlanHandle plan(info);
   uint64_t n_chunks = 0;  // of the input: an upper bound of what the filtered clouds have
   for (uint32_t k = 0; k < n_clouds; ++k) n_chunks += (cloud_points[k] + kPointsPerChunk - 1) / kPointsPerChunk;
@@ -1232,6 +1241,7 @@ void encodeStage1BatchViz(const EncodingInfo& info, const uint8_t* const* cloud_
   if (rc == CLDN_HIP_OK) rc = cldn_hip_codec_set_zstd_matches(codec, (stage2 & kStage2ZstdMatches) ? 1 : 0);
   if (rc == CLDN_HIP_OK) rc = encode();  // (a second encode filters again: the same survivors)
   if (rc == CLDN_HIP_OK && modes) rc = modesLastEncode(codec, plan.plan, n_clouds, modes, encode);
+  if (rc == CLDN_HIP_OK && crc) rc = crcLastEncode(codec, n_clouds, crc);
   if (rc == CLDN_HIP_OK && audit) rc = auditLastEncode(codec, info, n_clouds, audit);
   if (rc == CLDN_HIP_OK && sweep) rc = sweepLastEncode(codec, info, n_clouds, sweep);
   const std::string err = rc != CLDN_HIP_OK ? cldn_hip_last_error() : "";

@@ -60,10 +60,17 @@ struct ModesRequest {
   bool reencoded = false;
   std::vector<cldn_hip_mode_cell_t> report;
 };
+// `crc` (optional): behind the encode call (and behind a second one that `modes` made) the CRC-32 and the length of every
+// cloud's framed stage-1 stream, taken on the device (cldn_hip_stream_crc32_last_encode): under a device stage 2 the checksum
+// of what the blocks or frames decode to.
+struct StreamCrcRequest {
+  std::vector<uint32_t> crc;
+  std::vector<uint64_t> sizes;
+};
 void encodeStage1Batch(const Cloudini::EncodingInfo& info, const uint8_t* const* cloud_ptrs, const uint64_t* cloud_points,
                        uint32_t n_clouds, const std::function<uint8_t*(uint64_t)>& grow, std::vector<uint64_t>& stream_offsets,
                        std::vector<uint32_t>& chunk_sizes, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr,
-                       ModesRequest* modes = nullptr, int stage2 = 0);
+                       ModesRequest* modes = nullptr, int stage2 = 0, StreamCrcRequest* crc = nullptr);
 // `stage2` (both calls): the codec's stage-2 mode for the call (cldn_hip_codec_set_stage2; 0 = CLDN_HIP_STAGE2_NONE). With
 // CLDN_HIP_STAGE2_ZSTD the streams are [u32 size][ZSTD frame] per chunk and chunk_sizes the frame sizes: finished chunks of
 // a ZSTD message, nothing is left for the host's stage 2. kStage2ZstdMatches added to it turns cldn_hip_codec_set_zstd_matches on
@@ -76,7 +83,7 @@ void encodeStage1BatchViz(const Cloudini::EncodingInfo& info, const uint8_t* con
                           uint32_t n_clouds, uint32_t xyz_offset, float resolution, const std::function<uint8_t*(uint64_t)>& grow,
                           std::vector<uint64_t>& stream_offsets, std::vector<uint32_t>& chunk_sizes,
                           std::vector<uint64_t>& kept_points, AuditRequest* audit = nullptr, SweepRequest* sweep = nullptr,
-                          ModesRequest* modes = nullptr, int stage2 = 0);
+                          ModesRequest* modes = nullptr, int stage2 = 0, StreamCrcRequest* crc = nullptr);
 // detail::CompressChunk (src/codec_common.cpp:220-258) and its worst-case output size
 uint32_t compressChunkTo(Cloudini::CompressionOption opt, const uint8_t* src, size_t src_size, uint8_t* dst, size_t dst_cap);
 size_t compressedChunkBound(Cloudini::CompressionOption opt, size_t stage1_bytes);

@@ -11,6 +11,9 @@
 #include <mutex>
 #include <stdexcept>
 
+#include "../crc32_combine.h"
+#include "zstd_stitch.hpp"
+
 extern "C" {
 size_t ZSTD_compress(void* dst, size_t dstCapacity, const void* src, size_t srcSize, int compressionLevel);
 size_t ZSTD_decompress(void* dst, size_t dstCapacity, const void* src, size_t compressedSize);
@@ -151,6 +154,11 @@ std::vector<uint8_t> lz4FrameDecompress(const uint8_t* src, size_t n, size_t exp
   return out;
 }
 
+// A chunk's uncompressed_crc against its records. 0 means "not computed": every chunk a host compressor made here carries it.
+void checkChunkCrc(uint32_t crc, const uint8_t* records, size_t n) {
+  if (crc != 0u && cldn::crc32_bytes(records, n) != crc) bad("chunk crc mismatch");
+}
+
 // the records of a compressed chunk. The record's own size claim is not trusted with an allocation: bounded, and checked
 // against the compressed frame
 std::vector<uint8_t> decompressChunk(const std::string& comp, const uint8_t* p, uint64_t n, uint64_t usize) {
@@ -241,15 +249,17 @@ void McapFile::parseRecords(const uint8_t* p, const uint8_t* end, bool in_chunk)
         c.u64();  // message_start_time
         c.u64();  // message_end_time
         const uint64_t usize = c.u64();
-        c.u32();  // uncompressed_crc (0 = not computed; not checked)
+        const uint32_t crc = c.u32();  // uncompressed_crc: 0 = not computed
         const std::string comp = c.str();
         const uint64_t n = c.u64();
         c.need(n);
         if (comp.empty()) {
           if (n != usize) bad("uncompressed chunk whose sizes disagree");
+          checkChunkCrc(crc, c.p, n);
           parseRecords(c.p, c.p + n, true);
         } else {
           std::vector<uint8_t> raw = decompressChunk(comp, c.p, n, usize);
+          checkChunkCrc(crc, raw.data(), raw.size());
           chunks_.push_back(std::move(raw));
           parseRecords(chunks_.back().data(), chunks_.back().data() + chunks_.back().size(), true);
         }
@@ -368,7 +378,7 @@ bool McapStream::next(Record& r) {
       c.u64();  // message_start_time
       c.u64();  // message_end_time
       const uint64_t usize = c.u64();
-      c.u32();  // uncompressed_crc (0 = not computed; not checked)
+      const uint32_t crc = c.u32();  // uncompressed_crc: 0 = not computed
       const std::string comp = c.str();
       const uint64_t n = c.u64();
       c.need(n);
@@ -378,6 +388,7 @@ bool McapStream::next(Record& r) {
       } else {
         chunk_ = decompressChunk(comp, c.p, n, usize);
       }
+      checkChunkCrc(crc, chunk_.data(), chunk_.size());
       chunk_at_ = 0;
       in_chunk_ = true;
     }
@@ -467,6 +478,7 @@ void McapWriter::put(const std::vector<uint8_t>& r) {
 }
 
 void McapWriter::addSchema(const McapSchema& s) {
+  flushStitched();  // (a record of the ordinary chunk that follows: the stitched chunk in front of it is written first)
   Rec r(OP_SCHEMA);
   r.u16(s.id);
   r.str(s.name);
@@ -479,6 +491,7 @@ void McapWriter::addSchema(const McapSchema& s) {
 }
 
 void McapWriter::addChannel(const McapChannel& c) {
+  flushStitched();
   Rec r(OP_CHANNEL);
   r.u16(c.id);
   r.u16(c.schema_id);
@@ -493,6 +506,7 @@ void McapWriter::addChannel(const McapChannel& c) {
 
 void McapWriter::addMetadata(const McapMetadata& m) {
   flushChunk();  // metadata records live outside chunks
+  flushStitched();
   Rec r(OP_METADATA);
   r.str(m.name);
   r.map(m.entries);
@@ -509,8 +523,15 @@ void McapWriter::writeMessage(uint16_t channel_id, uint32_t sequence, uint64_t l
   r.u64(publish_time);
   r.raw(data, size);
   const auto& rec = r.done();
-  chunk_msgs_[channel_id].emplace_back(log_time, (uint64_t)chunk_.size());  // MessageIndex: offset of the record in the uncompressed chunk
+  flushStitched();  // (file order: a stitched chunk in front of this message is written first)
+  noteMessage(channel_id, log_time, (uint64_t)chunk_.size());
   chunk_.insert(chunk_.end(), rec.begin(), rec.end());
+  if (chunk_.size() >= chunk_size_) flushChunk();
+}
+
+// A message joins the open chunk at `offset` of its uncompressed records: MessageIndex entry, the chunk's and the file's times, counts
+void McapWriter::noteMessage(uint16_t channel_id, uint64_t log_time, uint64_t offset) {
+  chunk_msgs_[channel_id].emplace_back(log_time, offset);
   if (!chunk_has_msg_) {
     chunk_t0_ = chunk_t1_ = log_time;
     chunk_has_msg_ = true;
@@ -526,7 +547,92 @@ void McapWriter::writeMessage(uint16_t channel_id, uint32_t sequence, uint64_t l
   }
   ++n_messages_;
   ++channel_counts_[channel_id];
-  if (chunk_.size() >= chunk_size_) flushChunk();
+}
+
+void McapWriter::addStitchedMessage(const McapStitchedMessage& m) {
+  if (compression_ != McapCompression::Zstd) bad("a stitched chunk needs a zstd-compressed container");
+  uint64_t data_size = 0;
+  for (const McapPiece& p : m.pieces) {
+    data_size += p.runs.empty() ? p.size : 0;
+    for (const McapBlockRun& run : p.runs) {
+      if ((run.size == 0) != (run.content == 0) || (run.size != 0 && run.last_header + 3 > run.size))
+        bad("a block run whose blocks, content size and last block header disagree");
+      data_size += 4u + run.content;
+    }
+  }
+  flushChunk();  // the open chunk of ordinary records comes first
+  Rec r(OP_MESSAGE);
+  r.u16(m.channel_id);
+  r.u32(m.sequence);
+  r.u64(m.log_time);
+  r.u64(m.publish_time);
+  std::vector<uint8_t> head = r.done();
+  const uint64_t len = head.size() - 9 + data_size;  // (the record's length covers the data that follows in pieces)
+  std::memcpy(&head[1], &len, 8);
+  noteMessage(m.channel_id, m.log_time, stitched_size_);
+  // host bytes join the Raw part in front of them; `checked`: the writer takes their CRC itself
+  auto host = [&](const void* p, size_t n, bool checked) {
+    if (n == 0) return;
+    if (stitched_.empty() || stitched_.back().blocks) stitched_.emplace_back();
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    stitched_.back().bytes.insert(stitched_.back().bytes.end(), b, b + n);
+    if (checked) stitched_crc_ = cldn::crc32_bytes(p, n, stitched_crc_);
+    stitched_size_ += n;
+  };
+  host(head.data(), head.size(), true);
+  for (const McapPiece& p : m.pieces) {
+    if (p.runs.empty()) {
+      host(p.data, p.size, true);
+      continue;
+    }
+    uint64_t stream = 0;  // [u32 content][the run's content] per run, all of it under p.crc
+    for (const McapBlockRun& run : p.runs) {
+      host(&run.content, 4, false);
+      stream += 4u + run.content;
+      if (run.size == 0) continue;
+      stitched_.emplace_back();
+      StitchedPart& s = stitched_.back();
+      s.bytes.assign(run.data, run.data + run.size);
+      s.blocks = true;
+      s.last_header = run.last_header;
+      s.content = run.content;
+      stitched_size_ += run.content;
+    }
+    stitched_crc_ = cldn::crc32_combine(stitched_crc_, p.crc, stream);
+  }
+  if (stitched_size_ >= chunk_size_) flushStitched();
+}
+
+void McapWriter::writeStitchedChunk(const std::vector<McapStitchedMessage>& messages) {
+  for (const McapStitchedMessage& m : messages) addStitchedMessage(m);
+  flushStitched();
+}
+
+// The open stitched chunk: one ZSTD frame of Raw blocks (the host's bytes) and the device's block runs, as they are
+void McapWriter::flushStitched() {
+  if (stitched_.empty()) return;
+  cldn_stitch::FrameAssembler frame;
+  for (const StitchedPart& s : stitched_) {
+    if (!s.blocks) {
+      frame.raw(s.bytes.data(), s.bytes.size());
+      continue;
+    }
+    cldn_stitch::BlockRun run;
+    run.p = s.bytes.data();
+    run.bytes = s.bytes.size();
+    run.last_header = s.last_header;
+    run.content = s.content;
+    frame.run(run);
+  }
+  if (frame.content_size() != stitched_size_) bad("stitched chunk: sizes disagree");
+  std::vector<uint8_t> body;
+  frame.finish(&body);
+  // (a CRC of 0 means "not computed" to a reader: a chunk whose CRC happens to be 0 goes unchecked, nothing worse)
+  writeChunkRecord(stitched_size_, stitched_crc_, "zstd", body);
+  ++n_stitched_chunks_;
+  stitched_.clear();
+  stitched_size_ = 0;
+  stitched_crc_ = 0;
 }
 
 void McapWriter::flushChunk() {
@@ -547,16 +653,22 @@ void McapWriter::flushChunk() {
     name = "lz4";
   }
   const std::vector<uint8_t>& body = compression_ == McapCompression::None ? chunk_ : packed;
+  writeChunkRecord(chunk_.size(), 0u, name, body);  // uncompressed_crc: 0 = not computed
+  chunk_.clear();
+}
+
+// The Chunk record of the open chunk (ordinary or stitched), its MessageIndex records and its ChunkIndex entry
+void McapWriter::writeChunkRecord(uint64_t uncompressed_size, uint32_t crc, const char* name, const std::vector<uint8_t>& body) {
   Rec r(OP_CHUNK);
   r.u64(chunk_t0_);
   r.u64(chunk_t1_);
-  r.u64(chunk_.size());
-  r.u32(0u);  // uncompressed_crc: 0 = not computed
+  r.u64(uncompressed_size);
+  r.u32(crc);
   r.str(name);
   r.u64(body.size());
   r.raw(body.data(), body.size());
   const auto& rec = r.done();
-  ChunkIndex ci{chunk_t0_, chunk_t1_, pos_, rec.size(), body.size(), chunk_.size(), {}, 0};
+  ChunkIndex ci{chunk_t0_, chunk_t1_, pos_, rec.size(), body.size(), uncompressed_size, {}, 0};
   put(rec);
   // one MessageIndex record per channel with messages in the chunk, right behind it (ascending channel ids)
   const uint64_t index_start = pos_;
@@ -574,7 +686,6 @@ void McapWriter::flushChunk() {
   ci.message_index_length = pos_ - index_start;
   chunk_msgs_.clear();
   chunk_index_.push_back(ci);
-  chunk_.clear();
   chunk_has_msg_ = false;
   chunk_t0_ = chunk_t1_ = 0;
 }
@@ -596,6 +707,7 @@ void McapWriter::close() {
 
 void McapWriter::finish() {
   flushChunk();
+  flushStitched();
   {
     Rec r(OP_DATA_END);
     r.u32(0u);  // data_section_crc: 0 = not computed
@@ -872,13 +984,45 @@ class McapSink : public MessageSink {
  public:
   explicit McapSink(McapFlow& flow) : flow_(flow) {}
   void write(const std::string& name, const uint8_t* data, size_t size) override {
+    deliver(name, size, [&](const McapMessage& h) { flow_.out.writeMessage(h.channel_id, h.sequence, h.log_time, h.publish_time, data, size); });
+  }
+  // head | [u32 payload size][the frame's blocks] per chunk | tail, the chunk part under the one CRC the device took of it
+  void writeStitched(const std::string& name, const StitchedMessage& sm) override {
+    deliver(name, sm.head_size + sm.stream_size + sm.tail_size, [&](const McapMessage& h) {
+      McapStitchedMessage m;
+      m.channel_id = h.channel_id;
+      m.sequence = h.sequence;
+      m.log_time = h.log_time;
+      m.publish_time = h.publish_time;
+      m.pieces.resize(3);
+      m.pieces[0].data = sm.head;
+      m.pieces[0].size = sm.head_size;
+      for (const StitchedMessage::Chunk& ch : sm.chunks) {
+        McapBlockRun run;
+        run.data = ch.blocks;
+        run.size = ch.blocks_size;
+        run.last_header = ch.last_header;
+        run.content = ch.payload_size;
+        m.pieces[1].runs.push_back(run);
+      }
+      m.pieces[1].crc = sm.stream_crc;
+      m.pieces[2].data = sm.tail;
+      m.pieces[2].size = sm.tail_size;
+      flow_.out.addStitchedMessage(m);
+    });
+  }
+
+ private:
+  // the converted message `name` leaves through `put`, with the copied-through messages in front of and behind it
+  template <typename Put>
+  void deliver(const std::string& name, uint64_t size, Put&& put) {
     const uint64_t id = std::stoull(name);
     std::lock_guard<std::mutex> lock(flow_.mutex);
     try {
       flow_.flushCopies();
       if (flow_.pending.empty() || flow_.pending.front().id != id) bad("converted messages arrived out of order");
       const McapMessage& h = flow_.pending.front().head;
-      flow_.out.writeMessage(h.channel_id, h.sequence, h.log_time, h.publish_time, data, size);
+      put(h);
       flow_.stats.input_bytes += h.size;
       flow_.stats.output_bytes += size;
       ++flow_.stats.converted;
@@ -892,8 +1036,6 @@ class McapSink : public MessageSink {
       throw;
     }
   }
-
- private:
   McapFlow& flow_;
 };
 
@@ -905,6 +1047,8 @@ McapTranscodeStats transcodeMcap(const std::string& file_in, const std::string& 
   McapTranscodeStats stats;
   // no need to compress twice (mcap_converter.cpp:199-202)
   if (!options.decode && mcap_compression == McapCompression::Zstd) options.compression = Cloudini::CompressionOption::NONE;
+  if (options.mcap_device_zstd && (options.decode || mcap_compression != McapCompression::Zstd))
+    throw std::invalid_argument("mcap_device_zstd needs the encode direction and a zstd-compressed container");
 
   McapWriter out(file_out, in.profile, mcap_compression);
   McapFlow flow(in, out, options.decode, stats);
@@ -924,6 +1068,7 @@ McapTranscodeStats transcodeMcap(const std::string& file_in, const std::string& 
     if (!flow.pending.empty()) bad("point clouds were read but not converted");
   }
   out.close();
+  stats.pipeline.mcap_device_chunks = out.stitchedChunks();
   return stats;
 }
 

@@ -303,6 +303,31 @@ struct StreamHistLaunch {
 int sweep_hist_launch(const SweepLaunch& L, uint32_t walk);  // one clear + one kernel
 int stream_hist_launch(const StreamHistLaunch& L);           // one clear + one kernel
 
+// ---- CRC-32 of byte spans (crc_kernels.hip; the arithmetic: crc32_combine.h) ----
+// A span is cut at absolute addresses: its frame starts at the span's first byte rounded down to kCrcLaneBytes, lane t of
+// workgroup j takes the bytes of the span in [frame + j * kCrcSegmentBytes + t * kCrcLaneBytes, ... + kCrcLaneBytes).
+constexpr uint32_t kCrcThreads = 256;
+constexpr uint32_t kCrcLaneBytes = 128;                                 // one cache line per lane
+constexpr uint32_t kCrcWaveBytes = 64u * kCrcLaneBytes;
+constexpr uint32_t kCrcSegmentBytes = kCrcThreads * kCrcLaneBytes;      // per workgroup: 32 KiB
+struct CrcItem {
+  uint64_t begin, end;           // bytes of `streams`, begin < end, inside one segment of the span's frame
+  uint32_t span;
+  uint32_t mult;                 // x^(8 * bytes of the span behind `end`) mod P
+  uint32_t first;                // 1: the span starts here (initial value and final xor go in with this item)
+  uint32_t pad;
+};
+static_assert(sizeof(CrcItem) == 32, "two per 64-byte line");
+struct CrcLaunch {
+  hipStream_t stream;
+  const uint8_t* streams;        // device, any alignment
+  uint32_t n_spans;
+  uint32_t n_items;
+  const CrcItem* items;          // device [n_items]
+  uint32_t* crc;                 // device [n_spans], 4-byte aligned: cleared, then filled
+};
+int stream_crc32_launch(const CrcLaunch& L);                 // one clear + one kernel
+
 // ---- sweep of the V5 adaptive integer modes (mode_kernels.hip; record: cldn_hip_mode_cell_t, five 64-bit words) ----
 constexpr uint32_t kModeProbeUnit = 0xffffffffu;  // ModeUnit::chunk of the unit that probes a cloud's first kProbePoints values
 struct ModeField {

@@ -103,6 +103,8 @@ SIGNATURES = {
     "cldn_hip_sweep_hist_last_encode": (_INT, [_VP, _VP, _U32, _VP, _INT]),
     "cldn_hip_stream_hist": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _INT]),
     "cldn_hip_stream_hist_last_encode": (_INT, [_VP, _VP, _INT]),
+    "cldn_hip_stream_crc32": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _INT]),
+    "cldn_hip_stream_crc32_last_encode": (_INT, [_VP, _VP, _VP, _INT]),
     "cldn_hip_hist_entropy_bytes": (C.c_double, [_VP]),
     "cldn_hip_sweep_modes_clouds": (_INT, [_VP, _VP, _INT, _U64P, _U32, _VP, _INT]),
     "cldn_hip_sweep_modes_last_encode": (_INT, [_VP, _VP, _INT]),
@@ -860,6 +862,33 @@ class Codec:
         rep = None if report_ptr else _report((n, 256), np.uint64)
         _check(lib().cldn_hip_stream_hist_last_encode(self._h, *_report_arg(rep, report_ptr)))
         return rep
+
+    # ---- CRC-32 of byte spans (cldn_hip_stream_crc32*) --------------------------------------------------------------
+    def stream_crc32_host(self, streams: Sequence[np.ndarray]) -> np.ndarray:
+        """cldn_hip_stream_crc32 on host buffers: zlib.crc32 of each stream, a (n,) uint32 array."""
+        data, offs = _pack([_bytes(x) for x in streams])
+        return self.stream_crc32_device(data.ctypes.data, offs, streams_loc=HOST)
+
+    def stream_crc32_device(self, streams_ptr: int, stream_offsets, crc_ptr: int = 0, streams_loc: int = DEVICE):
+        """cldn_hip_stream_crc32 on a raw pointer. stream_offsets: host [n + 1]; crc_ptr: device array of n uint32 (returns
+        None), 0 = host result (returned)."""
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uint64)
+        n = max(0, so.size - 1)
+        crc = None if crc_ptr else _report((n,), np.uint32)
+        _check(lib().cldn_hip_stream_crc32(self._h, C.c_void_p(streams_ptr), streams_loc, _p64(so), n, *_report_arg(crc, crc_ptr)))
+        return crc
+
+    def stream_crc32_last_encode(self, crc_ptr: int = 0, sizes_ptr: int = 0):
+        """cldn_hip_stream_crc32_last_encode: CRC-32 and length of the framed stage-1 stream of each cloud of this codec's most
+        recent framed encode call, whatever its stage 2. Returns (crc uint32 [n], sizes uint64 [n]) on the host, or None when
+        crc_ptr names a device array (sizes_ptr: a device array as well, or 0 for none)."""
+        n = _last_encode_clouds(lib().cldn_hip_audit_last_encode_clouds, self)
+        if crc_ptr:
+            _check(lib().cldn_hip_stream_crc32_last_encode(self._h, C.c_void_p(crc_ptr), C.c_void_p(sizes_ptr), DEVICE))
+            return None
+        crc, sizes = _report((n,), np.uint32), _report((n,), np.uint64)
+        _check(lib().cldn_hip_stream_crc32_last_encode(self._h, _ptr(crc), _ptr(sizes), HOST))
+        return crc, sizes
 
     # ---- adaptive integer modes: section bytes per mode, probed and best mode (cldn_hip_sweep_modes_*) ---------------
     def sweep_modes_host(self, clouds: Sequence[np.ndarray]) -> np.ndarray:

@@ -96,10 +96,33 @@ class MessageSource {
   virtual bool more() const { return false; }
 };
 
+// A converted message whose stage-1 chunks arrive as ZSTD frames of the device writer (TranscodeOptions::mcap_device_zstd):
+// the message's bytes are head | [u32 payload_size][what the frame decodes to] per chunk | tail. stream_crc / stream_size:
+// CRC-32 and length of the chunk part as it reads uncompressed (cldn_hip_stream_crc32_last_encode). Everything points into the
+// batch and is valid during the call.
+struct StitchedMessage {
+  struct Chunk {
+    uint32_t payload_size = 0;     // stage-1 bytes of the chunk: the [u32] prefix of the uncompressed message
+    const uint8_t* blocks = nullptr;  // the frame's blocks (zstd_stitch.hpp, cut_device_frame)
+    size_t blocks_size = 0;
+    size_t last_header = 0;        // of the last of them, in `blocks`
+  };
+  const uint8_t* head = nullptr;
+  size_t head_size = 0;
+  const uint8_t* tail = nullptr;
+  size_t tail_size = 0;
+  std::vector<Chunk> chunks;
+  uint32_t stream_crc = 0;
+  uint64_t stream_size = 0;
+};
+
 class MessageSink {
  public:
   virtual ~MessageSink() = default;
   virtual void write(const std::string& name, const uint8_t* data, size_t size) = 0;  // called in input order
+  // TranscodeOptions::mcap_device_zstd hands such messages over in place of write(). A sink that cannot store compressed
+  // pieces has no business decompressing them behind the caller's back: it fails.
+  virtual void writeStitched(const std::string& name, const StitchedMessage& message);
   // Optional: a sink whose messages are independent (one file each) may be written by several threads at once; batches
   // still arrive in input order, the messages inside a batch in any order.
   virtual bool concurrent() const { return false; }
@@ -190,6 +213,17 @@ struct TranscodeOptions {
   // carry a sequences section. It brings the schemas named above to within 6 - 19 % of libzstd level 1 and costs about another
   // literal-only stage of GPU time. Needs `device_zstd`; not available together with `decode`.
   bool device_zstd_matches = false;
+  // ZSTD container chunks stitched from the device's blocks (transcodeMcap with McapCompression::Zstd only). The
+  // messages say compression_opt NONE, as that converter's default path writes them, but the GPU stage encodes with
+  // CLDN_HIP_STAGE2_ZSTD (device_zstd_matches: with sequences) and fetches the frames, their stage-1 streams' CRC-32s and sizes
+  // (cldn_hip_stream_crc32_last_encode): no stage-1 byte crosses the link or meets a host compressor. The sink receives
+  // MessageSink::writeStitched. Per message, an empty cloud and a message one of whose frames zstd_stitch.hpp refuses take the
+  // ordinary path (the refused frames are expanded on the host): TranscodeStats::mcap_* count both kinds. Needs `compression`
+  // NONE; not available together with `decode` or `device_zstd`.
+  bool mcap_device_zstd = false;
+  // Test hook (tests/cpp/mcap_refuse_stitch.cpp): when set and true for (message name, chunk of the message), that frame counts
+  // as one zstd_stitch.hpp refused -- the device writer makes none, so nothing else reaches the ordinary path of such a message.
+  std::function<bool(const std::string& name, uint64_t chunk)> test_refuse_stitch;
   // The way back with stage 2 on the device (include/cloudini_hip.h, cldn_hip_decode_lz4_gather / _zstd_gather). Needs `decode`.
   // Every schema run of LZ4 or ZSTD messages uploads the compressed bodies from the page-locked Message::bytes they arrived in
   // and undoes stage 2 on the device, ZSTD frames with sequences included; no libzstd / liblz4 call on the host. A run in
@@ -271,6 +305,9 @@ struct TranscodeStats {
   // TranscodeOptions::device_stage2_decode (all 0 without it): chunks whose stage 2 the device undid, chunks the host pool
   // decompressed for a second call, and schema runs that needed that second call
   uint64_t device_stage2_chunks = 0, host_stage2_chunks = 0, device_stage2_retries = 0;
+  // TranscodeOptions::mcap_device_zstd (all 0 without it): container chunks stitched from device blocks, messages inside them,
+  // and point-cloud messages that took the ordinary path instead (empty clouds, refused frames)
+  uint64_t mcap_device_chunks = 0, mcap_device_messages = 0, mcap_host_fallback_messages = 0;
 };
 
 // The reference's profile strings (McapConverter::addProfile, tools/src/mcap_converter.cpp:325-353):

@@ -19,6 +19,10 @@
 //               uncompressed chunk)), their places in the ChunkIndex's message_index_offsets -- indexed readers pick the
 //               chunks to read from that map. The file is written under "<path>.partial" and renamed by close(): a
 //               conversion that fails leaves no well-formed file that is silently missing its tail.
+//               addStitchedMessage / writeStitchedChunk: messages whose data arrives partly COMPRESSED -- streams of block
+//               runs cut from the device ZSTD writer's frames (cloudini_amd/csrc/host/zstd_stitch.hpp) with their
+//               uncompressed lengths and the stream's CRC-32 -- go into "zstd" chunks whose frame is stitched, not compressed here, and whose uncompressed_crc is
+//               combined from the pieces' CRCs (cloudini_amd/csrc/crc32_combine.h). Every other chunk keeps CRC 0.
 //   transcodeMcap  the converter: schemas and channels duplicated with the point-cloud schema swapped, metadata copied,
 //               PointCloud2 (or CompressedPointCloud2) messages through the batched GPU pipeline, everything else copied.
 #pragma once
@@ -111,6 +115,30 @@ class McapStream {
 
 enum class McapCompression { None, Lz4, Zstd };
 
+// One part of a message's data for McapWriter::addStitchedMessage. Host bytes (runs empty), or a STREAM as the device
+// checksums it: per entry of `runs` a [u32 content] prefix, which the writer spells, and what the run decodes to; `crc` is the
+// CRC-32 of that whole stream as it reads uncompressed. A run is the blocks of one frame of the device ZSTD writer as
+// zstd_stitch.hpp's cut_device_frame returns them: `size` bytes of whole blocks at `data`, the header of the last of them at
+// `last_header`, `content` bytes when decoded (size 0 and content 0: a chunk without bytes). All bytes are copied.
+struct McapBlockRun {
+  const uint8_t* data = nullptr;
+  size_t size = 0;
+  size_t last_header = 0;
+  uint32_t content = 0;
+};
+struct McapPiece {
+  const uint8_t* data = nullptr;
+  size_t size = 0;
+  std::vector<McapBlockRun> runs;
+  uint32_t crc = 0;
+};
+struct McapStitchedMessage {
+  uint16_t channel_id = 0;
+  uint32_t sequence = 0;
+  uint64_t log_time = 0, publish_time = 0;
+  std::vector<McapPiece> pieces;  // the message's data, in order
+};
+
 class McapWriter {
  public:
   McapWriter(const std::string& path, const std::string& profile, McapCompression compression, size_t chunk_size = 2u << 20);
@@ -119,7 +147,14 @@ class McapWriter {
   void addChannel(const McapChannel& c);
   void addMetadata(const McapMetadata& m);
   void writeMessage(uint16_t channel_id, uint32_t sequence, uint64_t log_time, uint64_t publish_time, const uint8_t* data, size_t size);
+  // A message into the open STITCHED chunk (McapCompression::Zstd only; throws otherwise). An open chunk of ordinary messages
+  // is written first, and an ordinary message (or schema, channel, metadata) that follows closes the stitched chunk: the file
+  // order of messages is the order of the calls. The chunk closes at chunk_size UNCOMPRESSED bytes, as every chunk does.
+  void addStitchedMessage(const McapStitchedMessage& m);
+  // The messages of one chunk: addStitchedMessage for each, then the chunk is closed whatever its size.
+  void writeStitchedChunk(const std::vector<McapStitchedMessage>& messages);
   void close();
+  uint64_t stitchedChunks() const { return n_stitched_chunks_; }  // stitched chunks written so far
 
  private:
   struct ChunkIndex {
@@ -128,6 +163,9 @@ class McapWriter {
     uint64_t message_index_length = 0;
   };
   void flushChunk();
+  void flushStitched();
+  void writeChunkRecord(uint64_t uncompressed_size, uint32_t crc, const char* compression, const std::vector<uint8_t>& body);
+  void noteMessage(uint16_t channel_id, uint64_t log_time, uint64_t offset);
   void finish();
   void put(const std::vector<uint8_t>& record);
   void* file_ = nullptr;
@@ -139,6 +177,17 @@ class McapWriter {
   std::vector<uint8_t> chunk_;  // uncompressed records of the open chunk
   uint64_t chunk_t0_ = 0, chunk_t1_ = 0;
   bool chunk_has_msg_ = false;
+  // the open stitched chunk: what its frame is made of (host bytes and block runs, copied), its uncompressed size and CRC
+  struct StitchedPart {
+    std::vector<uint8_t> bytes;
+    bool blocks = false;
+    size_t last_header = 0;
+    uint64_t content = 0;
+  };
+  std::vector<StitchedPart> stitched_;
+  uint64_t stitched_size_ = 0;
+  uint32_t stitched_crc_ = 0;
+  uint64_t n_stitched_chunks_ = 0;
   std::vector<std::vector<uint8_t>> schema_records_, channel_records_;
   std::vector<ChunkIndex> chunk_index_;
   std::map<uint16_t, uint64_t> channel_counts_;

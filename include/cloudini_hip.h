@@ -595,6 +595,27 @@ int cldn_hip_stream_hist(cldn_hip_codec_t* codec, const void* streams, int strea
                          uint32_t n_clouds, cldn_hip_hist_t* report, int report_loc);
 int cldn_hip_stream_hist_last_encode(cldn_hip_codec_t* codec, cldn_hip_hist_t* report, int report_loc);
 
+/* CRC-32 of byte spans where they lie: zlib.crc32 / the chunk CRC of MCAP (reflected polynomial 0xEDB88320, initial value and
+ * final xor 0xFFFFFFFF). crc[k] is the checksum of the bytes [stream_offsets[k], stream_offsets[k + 1]) of `streams`; any byte
+ * alignment is served, a span without bytes gives 0. stream_offsets: HOST [n_streams + 1], ascending. crc: [n_streams], HOST
+ * or DEVICE per crc_loc (DEVICE: 4-byte aligned). The codec lends its device, stream and workspace, as in
+ * cldn_hip_lz4_decompress: HOST streams are uploaded into the audit's workspace. Per call: one clear, one kernel (32 KiB of a
+ * span per workgroup, one 128-byte line per lane; cloudini_amd/csrc/crc_kernels.hip), one upload of its table; the workgroups'
+ * remainders are combined with the arithmetic of cloudini_amd/csrc/crc32_combine.h, which also compiles for the host. The
+ * result is a xor of integers: deterministic to the bit. Like every call that takes buffers, cldn_hip_stream_crc32 drops the
+ * state the *_last_encode calls need.
+ * cldn_hip_stream_crc32_last_encode: one CRC per cloud over the framed stage-1 streams of this codec's most recent FRAMED
+ * encode call -- [u32 size][payload] per chunk, the bytes a message with compression_opt == NONE holds behind its header --
+ * and, where `sizes` is not NULL, their lengths in bytes ([n_clouds], in the same memory as crc; DEVICE: 8-byte aligned).
+ * Rows, "no previous encode" (CLDN_HIP_ERR_ARG in the audit's wording) and the order on a caller's stream are those of
+ * cldn_hip_stream_hist_last_encode, with one difference: behind CLDN_HIP_STAGE2_LZ4 as behind CLDN_HIP_STAGE2_ZSTD the call
+ * reads the stage-1 streams the blocks and frames were made from (they stay in the codec's workspace), so all stage-2 modes
+ * report what CLDN_HIP_STAGE2_NONE reports: the checksum of what a decoder of the frames gets back. Such a call, and a call
+ * behind DEVICE outputs, reads the n_clouds + 1 offsets back once. The state stays as it was. */
+int cldn_hip_stream_crc32(cldn_hip_codec_t* codec, const void* streams, int streams_loc, const uint64_t* stream_offsets,
+                          uint32_t n_streams, uint32_t* crc, int crc_loc);
+int cldn_hip_stream_crc32_last_encode(cldn_hip_codec_t* codec, uint32_t* crc, uint64_t* sizes, int loc);
+
 /* Host only, no device: min(N, sum over the non-zero bins of c * log2(N / c) / 8) with N = the sum of the bins; 0 for an empty
  * histogram. Histograms may be added and subtracted bin by bin before the call (the identities above). */
 double cldn_hip_hist_entropy_bytes(const cldn_hip_hist_t* h);

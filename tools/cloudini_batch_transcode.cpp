@@ -31,7 +31,13 @@
 //   ... --devices 0,1,2,3   spreads the batches over these GPUs (one GPU stage per entry; "0,0" = two stages on GPU 0)
 //   cloudini_batch_transcode <in.mcap> <out.mcap> [...same options] [--mcap-compression none|lz4|zstd]
 //       a bag: point-cloud messages converted, everything else copied (McapConverter, tools/src/mcap_converter.cpp:141-300);
-//       read as a stream, a chunk at a time. CLDN_DEBUG_MEM=1 prints the process's memory high-water marks to stderr
+//       read as a stream, a chunk at a time.
+//   ... --mcap-device-zstd   with --mcap-compression zstd (the default): the container's ZSTD chunks are stitched from blocks the
+//       GPU wrote (CLDN_HIP_STAGE2_ZSTD; --device-zstd-matches: with sequences) and carry a CRC-32 the GPU took; the messages
+//       read exactly as without the option once a reader has decompressed the chunk, only chunk boundaries differ. The JSON
+//       line's mcap_device_chunks / mcap_device_messages / mcap_host_fallback_messages tell what happened (empty clouds take
+//       the ordinary path). With --decode, a directory, or another --mcap-compression: exit status 2.
+//       CLDN_DEBUG_MEM=1 prints the process's memory high-water marks to stderr
 //       (VmHWM of /proc/self/status; tests/test_mcap_io.py checks that they do not follow the size of the bag).
 #include <cstdio>
 #include <cstdlib>
@@ -108,7 +114,9 @@ int main(int argc, char** argv) {
                  "                                        whose bytes repeat come within 6-19 %% of libzstd level 1; token streams stay as they are)\n"
                  "  --device-stage2                        with --decode: LZ4 / ZSTD stage 2 is undone on the device (same files; chunks the\n"
                  "                                        device hands back go through the host pool)\n"
-                 "  --sweep, --modes, --device-zstd and --device-zstd-matches are not available with --decode\n", argv[0]);
+                 "  --mcap-device-zstd                     bags with --mcap-compression zstd: stitch the container's ZSTD chunks from the GPU's\n"
+                 "                                        blocks (with --device-zstd-matches: blocks with sequences) and give them a CRC-32\n"
+                 "  --sweep, --modes, --device-zstd, --device-zstd-matches and --mcap-device-zstd are not available with --decode\n", argv[0]);
     return 2;
   }
   cloudini_amd::TranscodeOptions opt;
@@ -150,6 +158,7 @@ int main(int argc, char** argv) {
     else if (a == "--device-zstd") opt.device_zstd = true;
     else if (a == "--device-zstd-matches") opt.device_zstd_matches = true;
     else if (a == "--device-stage2") opt.device_stage2_decode = true;
+    else if (a == "--mcap-device-zstd") opt.mcap_device_zstd = true;
     else if (a == "--modes" && i + 1 < argc) {
       const std::string v = argv[++i];
       if (v != "report" && v != "best") {
@@ -191,9 +200,17 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--device-zstd-matches is not available with --decode\n");
     return 2;
   }
-  if (opt.device_zstd_matches && !opt.device_zstd) {
-    std::fprintf(stderr, "--device-zstd-matches needs --device-zstd\n");
+  if (opt.device_zstd_matches && !opt.device_zstd && !opt.mcap_device_zstd) {
+    std::fprintf(stderr, "--device-zstd-matches needs --device-zstd or --mcap-device-zstd\n");
     return 2;
+  }
+  if (opt.mcap_device_zstd) {
+    const std::string in_path = argv[1];
+    const bool bag = in_path.size() > 5 && in_path.compare(in_path.size() - 5, 5, ".mcap") == 0;
+    if (opt.decode || !bag || mcap_comp != cloudini_amd::McapCompression::Zstd || opt.device_zstd) {
+      std::fprintf(stderr, "--mcap-device-zstd needs a bag and --mcap-compression zstd, and is not available with --decode or --device-zstd\n");
+      return 2;
+    }
   }
   if (opt.device_stage2_decode && !opt.decode) {
     std::fprintf(stderr, "--device-stage2 needs --decode\n");
@@ -214,12 +231,14 @@ int main(int argc, char** argv) {
       if (modes) printModes(ms.pipeline);
       std::printf("{\"messages\": %llu, \"converted\": %llu, \"input_bytes\": %llu, \"output_bytes\": %llu, \"points\": %llu, "
                   "\"seconds_total\": %.6f, \"gpu_batches\": %llu, \"peak_held_bytes\": %llu, \"device_stage2_chunks\": %llu, "
-                  "\"host_stage2_chunks\": %llu, \"device_stage2_retries\": %llu}\n",
+                  "\"host_stage2_chunks\": %llu, \"device_stage2_retries\": %llu, \"mcap_device_chunks\": %llu, "
+                  "\"mcap_device_messages\": %llu, \"mcap_host_fallback_messages\": %llu}\n",
                   (unsigned long long)ms.messages, (unsigned long long)ms.converted, (unsigned long long)ms.input_bytes,
                   (unsigned long long)ms.output_bytes, (unsigned long long)ms.pipeline.points, ms.pipeline.seconds_total,
                   (unsigned long long)ms.pipeline.gpu_batches, (unsigned long long)ms.peak_held_bytes,
                   (unsigned long long)ms.pipeline.device_stage2_chunks, (unsigned long long)ms.pipeline.host_stage2_chunks,
-                  (unsigned long long)ms.pipeline.device_stage2_retries);
+                  (unsigned long long)ms.pipeline.device_stage2_retries, (unsigned long long)ms.pipeline.mcap_device_chunks,
+                  (unsigned long long)ms.pipeline.mcap_device_messages, (unsigned long long)ms.pipeline.mcap_host_fallback_messages);
       if (std::getenv("CLDN_DEBUG_MEM")) {  // diagnostics: the process's memory high-water marks
         if (FILE* f = std::fopen("/proc/self/status", "r")) {
           char line[256];
